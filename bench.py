@@ -6,7 +6,7 @@ followed by PDE::solve (Dirichlet reduction + Jacobi-PCG to rtol 1e-10), all on 
 samples, Dirichlet data) are resident in HBM when the timed region starts; nothing but the solver's convergence flag
 crosses PCIe inside it.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--nx 119]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--nx 119] [--dump-outputs DIR]
 
 N = 1: the whole C3 mesh (119^3 x 6 = 10 110 954 tetrahedra, 1 728 000 DOFs) on one MI355X.
 N > 1: the same mesh, element-partitioned over N ranks, one per GPU (strong scaling).  Started either by
@@ -68,7 +68,32 @@ def parse():
     ap.add_argument("--no-extra", action="store_true", help="skip the secondary single-GPU results (BASELINE configs C2 and C5) appended as `extra`")
     ap.add_argument("--time-spmv", type=int, default=32,
                     help="multi-launch path: SpMV launches per step timed with dispatch-attached HIP events (each costs a ~6 us bubble)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: after the timed steps, write what the last one handed its caller (solution, force, stiffness and mass values) as "
+                         "DIR/<name>.npy in float64; an output longer than 2 000 000 entries is stored as a fixed seeded sample of that many")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs is implemented for --gpus 1 only")
+    return args
+
+
+DUMP_MAX_ENTRIES = 2_000_000   # per output: the four outputs of a step stay under 64 MB in all
+DUMP_SEED = 12345
+
+
+def dump_outputs(path, arrays):
+    """arrays: name -> what the timed path returned -> path/<name>.npy, float64.  An output longer than DUMP_MAX_ENTRIES is stored as the entries at
+    DUMP_MAX_ENTRIES indices drawn with DUMP_SEED (ascending; the same for the same length), so two builds can be compared output for output."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        if a.size > DUMP_MAX_ENTRIES:
+            a = a[np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, DUMP_MAX_ENTRIES, replace=False))]
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -519,6 +544,9 @@ def run_single(args):
     t_asm = float(np.mean([i.t_assemble_ms for i in infos]))
     t_sol = float(np.mean([i.t_solve_ms for i in infos]))
     u = ctx.solution()
+    if args.dump_outputs:   # (before anything below assembles again)
+        dump_outputs(args.dump_outputs, {"solution": u, "force": ctx.force(), "stiff_values": ctx.matrix_values(capi.MAT_STIFF),
+                                         "mass_values": ctx.matrix_values(capi.MAT_MASS)})
     _, _, coords = ctx.dofs_get()
     err = float(np.abs(u - u_exact(coords)).max())
     setup_ms = ctx.info().t_setup_ms + 1e3 * t_prep
@@ -793,9 +821,6 @@ def main():
     # cross-process hipIpc on this pool needs the dmabuf IPC mode; set BEFORE anything loads the HIP runtime, and in every kind of rank process
     # (self-launched, canary, started by torch.distributed.run), so that the canary's verdict holds for the ranks that follow it
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    # extra.multi_device_context names the box's one GPU several times: its ranks' persistent launches need a hardware queue each (the runtime multiplexes
-    # a process's streams onto 4 by default; real devices have their own) -- asked for before anything initialises the runtime; no effect on the other results
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
     args = parse()
     if args.nx is None:
         args.nx = 87 if args.workload == "c5" else 119

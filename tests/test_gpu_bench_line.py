@@ -11,12 +11,20 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_single_gpu_line_has_first_call_and_hygiene_fields():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--nx", "40", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extra"],
-                         stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, cwd=ROOT)
+def test_single_gpu_line_has_first_call_and_hygiene_fields(tmp_path):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--nx", "40", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extra",
+                          "--dump-outputs", str(tmp_path)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert rec["n_gpus"] == 1 and rec["scaling"] == "strong" and rec["dtype"] == "f64" and rec["vs_baseline"] is None
+    assert rec["steps"] == 2 and rec["ms_per_step"] > 0
+    # --dump-outputs: what the last timed step handed its caller, whole at this size
+    import numpy as np
+
+    dump = {k: np.load(tmp_path / f"{k}.npy") for k in ("solution", "force", "stiff_values", "mass_values")}
+    assert all(a.dtype == np.float64 and np.isfinite(a).all() for a in dump.values())
+    assert dump["solution"].size == dump["force"].size == 41**3 and dump["stiff_values"].size == dump["mass_values"].size > 41**3
+    assert np.abs(dump["solution"]).max() <= 1.1 and dump["mass_values"].min() >= 0.0
     cfg, roof = rec["config"], rec["roofline"]
     ph = cfg["first_call_phases_ms"]
     for k in ("dofs_build_ms", "set_forcing_ms", "set_dirichlet_ms", "solver_prepare_ms", "first_init_ms", "first_solve_ms", "mesh_upload_ms_not_counted",

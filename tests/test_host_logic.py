@@ -214,3 +214,31 @@ def test_parity_check_fails_the_bench_when_a_bar_is_missed():
     assert r["ok"] is False and r["pattern_equal"] is False
     bad = dict(gpu, u=u * (1 + 1e-6))
     assert bench.parity_against_oracle(bad, dofs, bnd, A, Mm, rhs, u, "self")["ok"] is False
+
+
+def test_bench_output_dump_is_float64_and_a_fixed_sample_of_large_outputs(tmp_path):
+    """bench.py --dump-outputs: outputs up to DUMP_MAX_ENTRIES are written whole, longer ones as the same seeded sample every time"""
+    import sys
+
+    ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, ROOT)
+    import bench
+
+    small = np.arange(10, dtype=np.float32)
+    big = np.random.default_rng(0).standard_normal(bench.DUMP_MAX_ENTRIES + 1000)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"small": small, "big": big})
+    s, b = np.load(tmp_path / "a" / "small.npy"), np.load(tmp_path / "a" / "big.npy")
+    assert s.dtype == np.float64 and np.array_equal(s, small)
+    assert b.dtype == np.float64 and b.size == bench.DUMP_MAX_ENTRIES and np.isin(b, big).all()
+    assert np.array_equal(b, np.load(tmp_path / "b" / "big.npy"))
+    assert 4 * 8 * bench.DUMP_MAX_ENTRIES <= 64e6   # the four outputs of a step stay under 64 MB
+
+
+def test_bench_refuses_zero_steps():
+    import subprocess
+    import sys
+
+    ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps" in r.stderr

@@ -1,6 +1,6 @@
-import sys, time
+import os, sys, time
 import numpy as np
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from fdapde_loader import load_package
 capi = load_package().capi
 from fdapde_core_amd import meshgen

@@ -1,13 +1,11 @@
 """Set-up and step time of the multi-device context (fdapde_ctx_create_multi) at C3's size with the "devices" all GPU 0, next to the single-device
 context: what the split costs (<= 0.5 s for partition + rank set-up; dist.py needed 16.3 s).  usage: group_time.py [nx] [n_dev ...]"""
+import os
 import sys
 import time
 
 import numpy as np
 
-import os
-
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")   # (ranks sharing ONE GPU: a hardware queue per launch, see tests/conftest.py)
 sys.path.insert(0, ".")
 from fdapde_loader import load_package
 

@@ -1,5 +1,5 @@
 import sys, os, time, numpy as np
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.environ["FDAPDE_DEBUG_SETUP"]="1"
 from fdapde_loader import load_package
 load_package()
