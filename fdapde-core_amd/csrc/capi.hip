@@ -75,6 +75,7 @@ void fdapde_ctx_destroy(fdapde_ctx* c) {
     if (!c) return;
     if (c->group) fdapde_engine::g_destroy(c);   // (the rank contexts and their threads first)
     fdapde_engine::pmg_release(c);               // (... and the coarse level's context)
+    fdapde_engine::amg_release(c);               // (... and the aggregation hierarchies)
     if (c->has_device) {
         (void)hipSetDevice(c->device);
         fdapde_engine::partition_free(c);
@@ -258,11 +259,13 @@ int fdapde_solver_layout_kind(fdapde_ctx* c, int32_t with_dirichlet, int32_t* ki
 }
 int fdapde_solve(fdapde_ctx* c, const fdapde_options* opt, fdapde_info* info) {
     if (!c) return FDAPDE_EINVAL;
+    if (c->group && opt && opt->method == FDAPDE_SOLVER_AMG) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_AMG takes one-GPU contexts, not a multi-device context");
     if (c->group) return fdapde_engine::g_solve(c, opt, info);
     return fdapde_engine::e_solve(c, opt, info);
 }
 int fdapde_solve_parabolic(fdapde_ctx* c, const fdapde_options* opt, int32_t n_times, double delta_t, const double* initial_condition, const double* dirichlet, double* solution, fdapde_info* info) {
     if (!c) return FDAPDE_EINVAL;
+    if (c->group && opt && opt->method == FDAPDE_SOLVER_AMG) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_AMG takes one-GPU contexts, not a multi-device context");
     if (c->group) return fdapde_engine::g_solve_parabolic(c, opt, n_times, delta_t, initial_condition, dirichlet, solution, info);
     return fdapde_engine::e_solve_parabolic(c, opt, n_times, delta_t, initial_condition, dirichlet, solution, info);
 }
@@ -273,6 +276,7 @@ int fdapde_lin_compute(fdapde_ctx* c, int32_t which, const double* values, int32
 }
 int fdapde_lin_solve(fdapde_ctx* c, const fdapde_options* opt, const double* b, int32_t n_rhs, double* x, fdapde_info* info) {
     if (!c) return FDAPDE_EINVAL;
+    if (c->group && opt && opt->method == FDAPDE_SOLVER_AMG) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_AMG takes one-GPU contexts, not a multi-device context");
     if (c->group) return fdapde_engine::g_lin_solve(c, opt, b, n_rhs, x, info);
     return fdapde_engine::e_lin_solve(c, opt, b, n_rhs, x, info);
 }
@@ -433,6 +437,8 @@ int fdapde_tune(fdapde_ctx* c, const char* key, int32_t value) {
     else if (k == "pmg_blocked" && (value == 0 || value == 1)) c->pmg_blocked = value;
     else if (k == "pmg_smooth" && (value == 0 || value == 1)) c->pmg_smooth = value;
     else if (k == "pmg_setup_check" && (value == 0 || value == 1)) c->pmg_setup_check = value;
+    else if (k == "amg_coarse_rows" && value >= 1 && value <= 8192) c->amg_coarse_rows = value;
+    else if (k == "amg_setup_check" && (value == 0 || value == 1)) c->amg_setup_check = value;
     else if (k == "pmg_restart" && value >= 2 && value <= 50) c->pmg_restart = (int)value;
     else if (k == "pmg_outer" && (value == 0 || value == 1)) c->pmg_outer = value;
     else if (k == "pmg_auto_rows" && value >= 0) c->pmg_auto_rows = value;

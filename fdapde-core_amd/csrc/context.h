@@ -23,6 +23,7 @@
 
 namespace fdapde_engine {
 struct Group;            // eng_group.hip: the ranks of a multi-device context
+struct AmgHierarchy;     // eng_amg.hip: the aggregation hierarchy of FDAPDE_SOLVER_AMG
 }
 namespace fdapde_hip {
 struct DevPartition;     // dev_partition.h
@@ -481,6 +482,12 @@ struct fdapde_ctx {
         double omega_extra = 0.0;
         SolveState coarse_ss;            // the coarse context's solver, prepared ONCE per coarse operator (coarse_prepare / coarse_solve, eng_solve.hip)
     } pmg;
+    // FDAPDE_SOLVER_AMG (eng_amg.hip): the hierarchy of fdapde_solve / fdapde_solve_parabolic, and the factor-once handle's; rebuilt lazily by a clone
+    fdapde_engine::AmgHierarchy* amg = nullptr;
+    fdapde_engine::AmgHierarchy* amg_lin = nullptr;
+    int64_t amg_lin_epoch = 0;    // fdapde_lin_compute calls: the handle's hierarchy belongs to the matrix of one of them
+    int64_t amg_coarse_rows = 1024;   // knob: coarsening stops at a level of at most that many rows, which is inverted once (dense_build_estimate_ms(1024) ~ 2.5 ms)
+    int amg_setup_check = 0;      // knob: 1 = host loops also build the aggregates and the coarse matrices, compared bit for bit (an error if they differ)
     int64_t init_count = 0;       // the assembled stiffness matrix's EPOCH: fdapde_init calls that may have changed its values (who caches something derived from them compares).
                                   // A repeated fdapde_init of the SAME operator with the row-owner sweep reproduces the matrix bit for bit (only the load vector is new): same epoch
     bool matrix_dirty = true;     // the operator (or the space) changed since the last fdapde_init, or fdapde_assemble rewrote the stiffness matrix
@@ -504,7 +511,9 @@ struct fdapde_ctx {
         DBuf<double> X;             // n x n, internal DOF order
         int64_t n = 0;
         int use_bnd = 0;            // the Dirichlet rows were replaced by unit rows (fem_solver_base.h:142-155)
-        const double* A = nullptr;  // the matrix values it inverts (device, internal slots): one step of refinement reads them
+        const double* A = nullptr;  // the matrix values it inverts (device, internal slots): one step of refinement reads them ...
+        const int32_t *rowptr = nullptr, *colidx = nullptr;   // ... on this pattern (the context's, or a level of FDAPDE_SOLVER_AMG) ...
+        const uint8_t* bnd = nullptr;                         // ... with these Dirichlet flags (use_bnd)
         bool ready = false, refine = false, failed = false;
         double check = 0, build_ms = 0;   // max |I - A X|; what the build cost (host wall clock)
     } lin_dense, step_dense, solve_dense;

@@ -1,0 +1,918 @@
+// eng_amg.hip -- FDAPDE_SOLVER_AMG: flexible GMRES around a K-cycle over an AGGREGATION hierarchy built from the matrix alone.
+//
+// Why: the reference solves every system with SparseLU (fem_linear_elliptic_solver.h:38-47, the factor-once handle of utils/symbols.h:133-160), which
+// does not care about mesh size or conditioning; Jacobi-preconditioned Krylov needs O(1 / h) iterations.  The two-level solver (eng_pmg.hip) takes
+// that away for order-2 spaces only, and its P1 level is itself solved by Jacobi-Krylov.  A hierarchy built from the matrix serves P1 and P2, 2-D and
+// 3-D, fdapde_solve, the parabolic stepper and the handle (whose matrix has no mesh behind it) alike.
+//
+// What:
+//   set-up    level 0 is the system the reference solves (the row-zeroed matrix of fem_solver_base.h:142-155: the Dirichlet DOFs belong to no aggregate,
+//             their correction is 0 on every level) or the handle's matrix, in the internal (locality) DOF order.  A level's aggregates come from TWO
+//             pairwise passes of handshake matching on the strength graph (-a_ij >= theta max_k -a_ik on the symmetric part; a row without negative
+//             couplings goes by |a_ij|): every free node proposes to its strongest unmatched strong neighbour (ties: a hash of the index pair), mutual proposals
+//             pair, kAmgRounds rounds (from kAmgStrongRounds on weak couplings count too), leftovers stay single -- the second pass on the Galerkin matrix of the first: aggregates of at most 4 nodes.  The
+//             coarse matrix is P^T A P with piecewise-constant P, built as a stable key sort of the (agg(i), agg(j)) pairs and a segmented sum in
+//             ascending fine-slot order: no float atomics, the same bits every run.  Levels until one has at most `amg_coarse_rows` rows; that one is
+//             inverted once (dense_build_csr, kernels_dense.h).
+//   cycle     on every level: damped Jacobi (1.5 / lambda_max(D^-1 A)), the coarse correction, damped Jacobi.  Below the finest level the coarse
+//             correction is two steps of flexible CG (GCR for a non-symmetric level) preconditioned by the next level's cycle: the K-cycle of
+//             Notay & Vassilevski -- with unsmoothed aggregation a V-cycle does not give counts independent of the mesh size.  Scalars stay on the
+//             device (fixed-order reductions, k_amg_coef); nothing returns to the host inside the cycle.
+//   outer     the flexible GMRES of the two-level solver (fgmres_outer, eng_pmg.hip).
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <memory>
+#include <string>
+#include <type_traits>
+#include <vector>
+
+#include <hipcub/hipcub.hpp>
+
+#include "context.h"
+#include "engine.h"
+#include "kernels_reduce.h"
+
+namespace fdapde_engine {
+
+namespace {
+using namespace fdapde_hip;
+
+constexpr double kAmgTheta = 0.25;   // strength threshold of a coupling, relative to the row's strongest
+constexpr int kAmgRounds = 10;       // handshake rounds per pairwise pass ...
+constexpr int kAmgStrongRounds = 3;  // ... the first of them on strong couplings only
+constexpr double kAmgStall = 0.8;    // a level that keeps more than this share of its rows ends the hierarchy (inverted if the dense limit allows: else unsupported)
+constexpr int kMateFree = -1, kMateExcluded = -2;
+constexpr int64_t kAmgMaxCoarse = 8192;   // the dense inverse's limit (kernels_dense.h kDenseMaxRows)
+
+inline unsigned gn(int64_t n) { return (unsigned)((n + 255) / 256); }
+
+// ---- set-up kernels (one thread per row: a set-up pass, not a hot path) ----
+// the coupling of (i, j) in the symmetric part, as a positive number for an M-matrix entry: -(a_ij + a_ji) -- a_ji looked up even where the matrix is
+// symmetric (an assembled a_ji need not carry a_ij's last bit): the same word from both ends, which the matching's order of the edges relies on
+__device__ __host__ inline double amg_sym_coupling(const int32_t* rp, const int32_t* ci, const double* a, int32_t k, int32_t i, int32_t j) {
+    double at = 0.0;
+    for (int32_t q = rp[j]; q < rp[j + 1]; ++q)
+        if (ci[q] == i) {
+            at = a[q];
+            break;
+        }
+    return -(a[k] + at);
+}
+// sw[k] = the strength of entry k: > 0 a strong coupling, < 0 (minus its strength) a weak one, 0 none (the diagonal, excluded rows and columns)
+__device__ __host__ inline void amg_strength_row(int64_t i, const int32_t* rp, const int32_t* ci, const double* a, const uint8_t* excl, double* sw) {
+    const int32_t b = rp[i], e = rp[i + 1];
+    if (excl && excl[i]) {
+        for (int32_t k = b; k < e; ++k) sw[k] = 0.0;
+        return;
+    }
+    double mneg = 0.0, mabs = 0.0;
+    for (int32_t k = b; k < e; ++k) {
+        const int32_t j = ci[k];
+        if (j == (int32_t)i || (excl && excl[j])) continue;
+        const double s = amg_sym_coupling(rp, ci, a, k, (int32_t)i, j);
+        mneg = s > mneg ? s : mneg;
+        const double sa = s < 0.0 ? -s : s;
+        mabs = sa > mabs ? sa : mabs;
+    }
+    const bool neg = mneg > 0.0;
+    const double thr = kAmgTheta * (neg ? mneg : mabs);
+    for (int32_t k = b; k < e; ++k) {
+        const int32_t j = ci[k];
+        double w = 0.0;
+        if (j != (int32_t)i && !(excl && excl[j]) && (neg || mabs > 0.0)) {
+            const double s = amg_sym_coupling(rp, ci, a, k, (int32_t)i, j);
+            const double v = neg ? s : (s < 0.0 ? -s : s);
+            if (v > 0.0) w = v >= thr ? v : -v;   // (negative: a weak coupling, for the relaxed rounds)
+        }
+        sw[k] = w;
+    }
+}
+// a tie between equally strong couplings is broken by a hash of the index pair -- the same word from both ends: a total order on the edges, so that a
+// coupling that is the best of both its ends is proposed from both (breaking ties by the smaller index alone pairs almost nothing on a uniform stencil:
+// every node proposes to its smallest neighbour, which proposes further down)
+__device__ __host__ inline uint32_t amg_pair_hash(int32_t i, int32_t j) {
+    const uint32_t lo = (uint32_t)(i < j ? i : j), hi = (uint32_t)(i < j ? j : i);
+    uint64_t z = ((uint64_t)hi << 32 | lo) * 0x9E3779B97F4A7C15ull;
+    z ^= z >> 29, z *= 0xBF58476D1CE4E5B9ull, z ^= z >> 32;
+    return (uint32_t)z;
+}
+// relaxed (the rounds from kAmgStrongRounds on): weak couplings count too -- a node whose strong neighbours have all been taken pairs along a weaker one
+// instead of staying single (3-D P1 -Lap, the 250 k interior rows of unit_cube(64): strong couplings only, every round, stalled at 3 829 rows four levels down)
+__device__ __host__ inline int32_t amg_propose_row(int64_t i, const int32_t* rp, const int32_t* ci, const double* sw, const int32_t* mate, int relaxed) {
+    if (mate[i] != kMateFree) return -1;
+    int32_t best = -1;
+    double bw = 0.0;
+    uint32_t bh = 0;
+    for (int32_t k = rp[i]; k < rp[i + 1]; ++k) {
+        const int32_t j = ci[k];
+        const double w = relaxed ? (sw[k] < 0.0 ? -sw[k] : sw[k]) : sw[k];
+        if (!(w > 0.0) || j == (int32_t)i || mate[j] != kMateFree) continue;
+        const uint32_t h = amg_pair_hash((int32_t)i, j);
+        if (w > bw || (w == bw && (h > bh || (h == bh && j < best)))) bw = w, bh = h, best = j;
+    }
+    return best;
+}
+__device__ __host__ inline bool amg_leader(int64_t i, const int32_t* mate) { return mate[i] == kMateFree || (mate[i] >= 0 && (int64_t)mate[i] > i); }
+
+__global__ void k_amg_init_mate(int64_t n, const uint8_t* excl, int32_t* mate) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) mate[i] = (excl && excl[i]) ? kMateExcluded : kMateFree;
+}
+__global__ void k_amg_strength(int64_t n, const int32_t* rp, const int32_t* ci, const double* a, const uint8_t* excl, double* sw) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) amg_strength_row(i, rp, ci, a, excl, sw);
+}
+__global__ void k_amg_propose(int64_t n, const int32_t* rp, const int32_t* ci, const double* sw, const int32_t* mate, int relaxed, int32_t* prop) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) prop[i] = amg_propose_row(i, rp, ci, sw, mate, relaxed);
+}
+// mutual proposals pair (each side writes its own word: the outcome does not depend on who runs first)
+__global__ void k_amg_accept(int64_t n, const int32_t* prop, int32_t* mate) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || mate[i] != kMateFree) return;
+    const int32_t j = prop[i];
+    if (j >= 0 && prop[j] == (int32_t)i) mate[i] = j;
+}
+__global__ void k_amg_leaders(int64_t n, const int32_t* mate, int32_t* lead) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) lead[i] = amg_leader(i, mate) ? 1 : 0;
+}
+__global__ void k_amg_assign(int64_t n, const int32_t* mate, const int32_t* id, int32_t* agg) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int32_t m = mate[i];
+    agg[i] = m == kMateExcluded ? -1 : amg_leader(i, mate) ? id[i] : id[m];
+}
+__global__ void k_amg_compose(int64_t n, const int32_t* agg1, const int32_t* agg2, int32_t* agg) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) agg[i] = agg1[i] < 0 ? -1 : agg2[agg1[i]];
+}
+// Galerkin product: every entry's (agg(i) nc + agg(j)) key, `sentinel` where a side has no aggregate
+__global__ void k_amg_gkeys(int64_t n, const int32_t* rp, const int32_t* ci, const int32_t* agg, uint64_t nc, uint64_t sentinel, uint64_t* keys, int32_t* idx) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int32_t ai = agg[i];
+    for (int32_t k = rp[i]; k < rp[i + 1]; ++k) {
+        const int32_t aj = agg[ci[k]];
+        keys[k] = (ai >= 0 && aj >= 0) ? (uint64_t)ai * nc + (uint64_t)aj : sentinel;
+        idx[k] = k;
+    }
+}
+__global__ void k_amg_heads(int64_t m, const uint64_t* keys, uint64_t sentinel, int32_t* head) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < m) head[e] = (keys[e] != sentinel && (e == 0 || keys[e] != keys[e - 1])) ? 1 : 0;
+}
+// one thread per coarse entry: the sum of its fine entries in ascending slot order (the stable sort kept them so)
+__global__ void k_amg_gsum(int64_t m, const uint64_t* keys, const int32_t* idx, const double* a, const int32_t* head, const int32_t* pos, uint64_t nc,
+                           int32_t* rp_c, int32_t* ci_c, double* a_c) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= m || !head[e]) return;
+    const uint64_t key = keys[e];
+    double s = 0.0;
+    for (int64_t q = e; q < m && keys[q] == key; ++q) s += a[idx[q]];
+    const int32_t p = pos[e];
+    const uint64_t row = key / nc;
+    a_c[p] = s, ci_c[p] = (int32_t)(key - row * nc);
+    if (e == 0 || keys[e - 1] / nc != row) rp_c[row] = p;
+}
+// members of every aggregate, ascending: keys agg(i) (nc for none), sorted stably with the row index
+__global__ void k_amg_mkeys(int64_t n, const int32_t* agg, uint32_t nc, uint32_t* keys, int32_t* idx) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) keys[i] = agg[i] >= 0 ? (uint32_t)agg[i] : nc, idx[i] = (int32_t)i;
+}
+__global__ void k_amg_mptr(int64_t n, const uint32_t* keys, uint32_t nc, int32_t* mptr) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    if (e == 0 || keys[e] != keys[e - 1]) mptr[keys[e]] = (int32_t)e;   // (keys[e] <= nc: mptr has nc + 1 words)
+    if (e == n - 1 && keys[e] < nc) mptr[nc] = (int32_t)n;
+}
+// D^-1 (0 on the excluded rows); flag: a free row without a usable diagonal entry
+__global__ void k_amg_dinv(int64_t n, const int32_t* rp, const int32_t* ci, const double* a, const uint8_t* excl, double* dinv, int32_t* flag) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (excl && excl[i]) {
+        dinv[i] = 0.0;
+        return;
+    }
+    double d = 0.0;
+    for (int32_t k = rp[i]; k < rp[i + 1]; ++k)
+        if (ci[k] == (int32_t)i) d = a[k];
+    const double v = 1.0 / d;
+    if (!(d != 0.0) || !isfinite(v)) atomicOr(flag, 1), dinv[i] = 0.0;
+    else dinv[i] = v;
+}
+// y = D^-1 A x (the power iteration's operator)
+__global__ void k_amg_dax(int64_t n, const int32_t* rp, const int32_t* ci, const double* a, const double* dinv, const double* x, double* y) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double s = 0.0;
+    for (int32_t k = rp[i]; k < rp[i + 1]; ++k) s += a[k] * x[ci[k]];
+    y[i] = dinv[i] * s;
+}
+__global__ void k_amg_hashvec(int64_t n, const double* dinv, double* x) {   // a fixed pseudo-random start (0 where D^-1 is)
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint64_t z = (uint64_t)i * 0x9E3779B97F4A7C15ull + 0x632BE59BD9B4E019ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull, z = (z ^ (z >> 27)) * 0x94D049BB133111EBull, z ^= z >> 31;
+    x[i] = dinv[i] == 0.0 ? 0.0 : (double)(z >> 11) * (2.0 / 9007199254740992.0) - 1.0;
+}
+__global__ void k_amg_scale(int64_t n, const double* a, double f, double* out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = f * a[i];
+}
+
+// ---- cycle kernels: a team of T lanes per row (coarse levels are latency-bound: few launches, each fused as far as the data flow allows) ----
+// pre-smoothing from zero and the restricted residual in one pass, a team per aggregate: zt_i = om d_i r_i for its members, and
+// rc_a = sum over members i of (r_i - sum_j a_ij om d_j r_j)
+template <int T>
+__global__ __launch_bounds__(256) void k_amg_pre_restrict(int64_t nc, const int32_t* mptr, const int32_t* midx, const int32_t* rp, const int32_t* ci,
+                                                          const double* a, const double* dinv, double om, const double* r, double* zt, double* rc) {
+    const int lane = threadIdx.x & (T - 1);
+    const int64_t ag = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / T;
+    if (ag >= nc) return;   // (whole teams leave together: T divides the wavefront)
+    double acc = 0.0;
+    for (int32_t q = mptr[ag]; q < mptr[ag + 1]; ++q) {
+        const int32_t i = midx[q];
+        double s = 0.0;
+        for (int32_t k = rp[i] + lane; k < rp[i + 1]; k += T) {
+            const int32_t j = ci[k];
+            s += a[k] * (dinv[j] * r[j]);
+        }
+        s = team_sum<T>(s);
+        const double ri = r[i];
+        if (lane == 0) zt[i] = om * dinv[i] * ri;
+        acc += ri - om * s;
+    }
+    if (lane == 0) rc[ag] = acc;
+}
+// out_i = z_i + om d_i (r_i - sum_j a_ij z_j) with z = zt + P e (the coarse correction prolongated on the fly)
+template <int T>
+__global__ __launch_bounds__(256) void k_amg_post(int64_t n, const int32_t* rp, const int32_t* ci, const double* a, const double* dinv, double om, const int32_t* agg,
+                                                  const double* e, const double* r, const double* zt, double* out) {
+    const int lane = threadIdx.x & (T - 1);
+    const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / T;
+    if (i >= n) return;
+    double s = 0.0;
+    for (int32_t k = rp[i] + lane; k < rp[i + 1]; k += T) {
+        const int32_t j = ci[k], g = agg[j];
+        s += a[k] * (zt[j] + (g >= 0 ? e[g] : 0.0));
+    }
+    s = team_sum<T>(s);
+    if (lane == 0) {
+        const int32_t g = agg[i];
+        const double zi = zt[i] + (g >= 0 ? e[g] : 0.0);
+        out[i] = zi + om * dinv[i] * (r[i] - s);
+    }
+}
+// y = A x and up to three dot products p_q . q_q (any of them may be y itself) as per-workgroup partials: a fixed grid, the same bits every run
+template <int T>
+__global__ __launch_bounds__(256) void k_amg_spmv_dots(int64_t n, const int32_t* rp, const int32_t* ci, const double* a, const double* x, double* y, const double* p0,
+                                                       const double* q0, const double* p1, const double* q1, const double* p2, const double* q2, double* part) {
+    __shared__ double red[3][4];
+    const int lane = threadIdx.x & (T - 1);
+    double d0 = 0.0, d1 = 0.0, d2 = 0.0;
+    const int64_t teams = (int64_t)gridDim.x * blockDim.x / T;
+    for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / T; i < n; i += teams) {
+        double s = 0.0;
+        for (int32_t k = rp[i] + lane; k < rp[i + 1]; k += T) s += a[k] * x[ci[k]];
+        s = team_sum<T>(s);
+        if (lane == 0) {
+            y[i] = s;
+            auto val = [&](const double* v) { return v == y ? s : v[i]; };
+            d0 += val(p0) * val(q0);
+            d1 += val(p1) * val(q1);
+            if (p2) d2 += val(p2) * val(q2);
+        }
+    }
+    d0 = wave_sum(d0), d1 = wave_sum(d1), d2 = wave_sum(d2);
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) red[0][w] = d0, red[1][w] = d1, red[2][w] = d2;
+    __syncthreads();
+    if (threadIdx.x < 3) part[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
+}
+// the K-cycle's scalars from the partials of k_amg_spmv_dots (one workgroup).  Stage 1 (c = B b, v = A c): FCG rho1 = c.v, alpha1 = c.b; GCR rho1 = v.v,
+// alpha1 = v.b; sc[0] = rho1, sc[1] = alpha1 / rho1.  Stage 2 (rt = b - sc[1] v, d = B rt, w = A d): FCG gamma = d.v, rho2 = d.w - gamma^2 / rho1,
+// alpha2 = d.rt; GCR gamma = v.w, rho2 = w.w - gamma^2 / rho1, alpha2 = w.rt; the correction e = sc[2] c + sc[3] d.  A step that cannot be taken
+// (rho <= 0, not finite) contributes nothing.
+__global__ __launch_bounds__(256) void k_amg_coef(const double* part, int np, int stage, double* sc) {
+    __shared__ double red[5];
+    double t[3];
+    for (int q = 0; q < 3; ++q) {
+        double s = 0.0;
+        for (int i = threadIdx.x; i < np; i += 256) s += part[(size_t)q * np + i];
+        t[q] = block_sum(s, red);
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    if (stage == 1) {
+        const double rho1 = t[0], a1 = rho1 > 0.0 && isfinite(rho1) ? t[1] / rho1 : 0.0;
+        sc[0] = rho1, sc[1] = isfinite(a1) ? a1 : 0.0;
+    } else {
+        const double rho1 = sc[0], gamma = t[0];
+        const double rho2 = rho1 > 0.0 ? t[1] - gamma * gamma / rho1 : 0.0;
+        double cd = rho2 > 0.0 && isfinite(rho2) ? t[2] / rho2 : 0.0;
+        double cc = sc[1] - (rho1 > 0.0 ? cd * gamma / rho1 : 0.0);
+        if (!isfinite(cd) || !isfinite(cc)) cd = 0.0, cc = sc[1];
+        sc[2] = cc, sc[3] = cd;
+    }
+}
+__global__ void k_amg_axpy_sc(int64_t n, const double* b, const double* v, const double* sc, double* rt) {   // rt = b - sc[1] v
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) rt[i] = b[i] - sc[1] * v[i];
+}
+__global__ void k_amg_comb2(int64_t n, const double* cv, const double* dv, const double* sc, double* e) {   // e = sc[2] c + sc[3] d
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) e[i] = sc[2] * cv[i] + sc[3] * dv[i];
+}
+// the finest level's system: y = K x (the Dirichlet rows as unit rows if use_bnd); with f: r = rhs - K x (rhs = f, g on the Dirichlet rows)
+template <int T>
+__global__ __launch_bounds__(256) void k_amg_apply_K(int64_t n, const int32_t* rp, const int32_t* ci, const double* a, const uint8_t* bnd, int use_bnd, const double* x,
+                                                     const double* f, const double* g, double* y) {
+    const int lane = threadIdx.x & (T - 1);
+    const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / T;
+    if (i >= n) return;
+    const bool unit = use_bnd && bnd[i];
+    double s = 0.0;
+    if (!unit)
+        for (int32_t k = rp[i] + lane; k < rp[i + 1]; k += T) s += a[k] * x[ci[k]];
+    s = team_sum<T>(s);
+    if (lane == 0) {
+        const double kx = unit ? x[i] : s;
+        y[i] = f ? (unit ? g[i] : f[i]) - kx : kx;
+    }
+}
+// x = g on the Dirichlet rows; elsewhere x0 (a warm start) or 0
+__global__ void k_amg_start(int64_t n, const uint8_t* bnd, int use_bnd, const double* g, const double* x0, double* x) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) x[i] = (use_bnd && bnd[i]) ? g[i] : (x0 ? x0[i] : 0.0);
+}
+
+// the handle's columns between the reference numbering and the internal order
+__global__ void k_amg_gather(int64_t n, const int32_t* idx, const double* src, double* dst) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] = src[idx[i]];
+}
+__global__ void k_amg_scatter(int64_t n, const int32_t* idx, const double* src, double* dst) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[idx[i]] = src[i];
+}
+
+template <typename F> void by_team(int T, F&& f) {
+    if (T <= 4) f(std::integral_constant<int, 4>{});
+    else if (T <= 8) f(std::integral_constant<int, 8>{});
+    else f(std::integral_constant<int, 16>{});
+}
+}   // namespace
+
+struct AmgLevel {
+    int64_t n = 0, nnz = 0;
+    DBuf<int32_t> rp_own, ci_own;
+    DBuf<double> a_own;
+    const int32_t *rp = nullptr, *ci = nullptr;   // level 0: the context's pattern and the caller's values; below: the level's own arrays
+    const double* a = nullptr;
+    const uint8_t* excl = nullptr;                // rows that belong to no aggregate (level 0's Dirichlet DOFs)
+    DBuf<double> dinv;
+    double om = 0.0;
+    int team = 4, np = 1;
+    DBuf<int32_t> agg, mptr, midx;                // row -> row of the next level (-1: none); members of each next-level row, ascending
+    DBuf<double> b, zt, cv, v, dv, w, rt, e, part, sc;   // work vectors (b: the restricted right-hand side; e: this level's correction)
+};
+
+struct AmgHierarchy {
+    std::vector<std::unique_ptr<AmgLevel>> lv;
+    fdapde_ctx::Dense D;                          // the coarsest level's inverse
+    bool sym = true;
+    int use_bnd = 0;
+    const double* A = nullptr;
+    int64_t key = -1;
+    double setup_ms = 0.0, op_complexity = 0.0;
+    DBuf<double> vec, basis, part, dots;          // the outer iteration's vectors (x, r, t) and flexible GMRES basis
+    int np = 1, mk = 0;
+    ~AmgHierarchy() {
+        D.X.release();
+        for (auto& l : lv)
+            for (DBuf<double>* p : {&l->a_own, &l->dinv, &l->b, &l->zt, &l->cv, &l->v, &l->dv, &l->w, &l->rt, &l->e, &l->part, &l->sc}) p->release();
+    }
+};
+
+namespace {
+// ---- the host loops of the same set-up (knob amg_setup_check): the same arithmetic in the same order ----
+struct HostCsr {
+    int64_t n = 0;
+    std::vector<int32_t> rp, ci;
+    std::vector<double> a;
+};
+void host_pairwise(const HostCsr& A, const uint8_t* excl, std::vector<int32_t>& agg, int32_t& nc) {
+    const int64_t n = A.n;
+    std::vector<double> sw(A.a.size());
+    for (int64_t i = 0; i < n; ++i) amg_strength_row(i, A.rp.data(), A.ci.data(), A.a.data(), excl, sw.data());
+    std::vector<int32_t> mate((size_t)n), prop((size_t)n);
+    for (int64_t i = 0; i < n; ++i) mate[(size_t)i] = (excl && excl[i]) ? kMateExcluded : kMateFree;
+    for (int round = 0; round < kAmgRounds; ++round) {
+        for (int64_t i = 0; i < n; ++i) prop[(size_t)i] = amg_propose_row(i, A.rp.data(), A.ci.data(), sw.data(), mate.data(), round >= kAmgStrongRounds ? 1 : 0);
+        for (int64_t i = 0; i < n; ++i) {
+            if (mate[(size_t)i] != kMateFree) continue;
+            const int32_t j = prop[(size_t)i];
+            if (j >= 0 && prop[(size_t)j] == (int32_t)i) mate[(size_t)i] = j;
+        }
+    }
+    std::vector<int32_t> id((size_t)n);
+    nc = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        id[(size_t)i] = nc;
+        nc += amg_leader(i, mate.data()) ? 1 : 0;
+    }
+    agg.assign((size_t)n, -1);
+    for (int64_t i = 0; i < n; ++i) {
+        const int32_t m = mate[(size_t)i];
+        agg[(size_t)i] = m == kMateExcluded ? -1 : amg_leader(i, mate.data()) ? id[(size_t)i] : id[(size_t)m];
+    }
+}
+void host_galerkin(const HostCsr& A, const std::vector<int32_t>& agg, int32_t nc, HostCsr& C) {
+    std::vector<std::pair<uint64_t, int32_t>> ent;
+    for (int64_t i = 0; i < A.n; ++i)
+        for (int32_t k = A.rp[(size_t)i]; k < A.rp[(size_t)i + 1]; ++k) {
+            const int32_t ai = agg[(size_t)i], aj = agg[(size_t)A.ci[(size_t)k]];
+            if (ai >= 0 && aj >= 0) ent.emplace_back((uint64_t)ai * (uint64_t)nc + (uint64_t)aj, k);
+        }
+    std::stable_sort(ent.begin(), ent.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
+    C.n = nc, C.rp.assign((size_t)nc + 1, 0), C.ci.clear(), C.a.clear();
+    for (size_t e = 0; e < ent.size();) {
+        const uint64_t key = ent[e].first;
+        double s = 0.0;
+        for (; e < ent.size() && ent[e].first == key; ++e) s += A.a[(size_t)ent[e].second];
+        const uint64_t row = key / (uint64_t)nc;
+        C.ci.push_back((int32_t)(key - row * (uint64_t)nc)), C.a.push_back(s), ++C.rp[(size_t)row + 1];
+    }
+    for (int32_t r = 0; r < nc; ++r) C.rp[(size_t)r + 1] += C.rp[(size_t)r];
+}
+template <typename T> bool same_dev(const T* p, size_t n, const std::vector<T>& h) {
+    if (h.size() != n) return false;
+    std::vector<T> g(n);
+    if (n && hipMemcpy(g.data(), p, sizeof(T) * n, hipMemcpyDeviceToHost) != hipSuccess) return false;
+    return n == 0 || std::memcmp(g.data(), h.data(), sizeof(T) * n) == 0;
+}
+template <typename T> int fetch(fdapde_ctx* c, const T* p, size_t n, std::vector<T>& h) {
+    h.resize(n);
+    if (n) HIPCHK(c, hipMemcpy(h.data(), p, sizeof(T) * n, hipMemcpyDeviceToHost));
+    return FDAPDE_OK;
+}
+
+// one pairwise pass on the device: agg (n words), *nc; scratch kept by the caller
+int dev_pairwise(fdapde_ctx* c, int64_t n, int64_t nnz, const int32_t* rp, const int32_t* ci, const double* a, const uint8_t* excl, DBuf<int32_t>& agg, int32_t* nc) {
+    hipStream_t st = c->stream;
+    const dim3 bv(256);
+    DBuf<double> sw;
+    DBuf<int32_t> mate, prop, lead, id;
+    DBuf<char> tmp;
+    HIPCHK(c, sw.alloc((size_t)nnz));
+    HIPCHK(c, mate.alloc((size_t)n));
+    HIPCHK(c, prop.alloc((size_t)n));
+    HIPCHK(c, lead.alloc((size_t)n + 1));
+    HIPCHK(c, id.alloc((size_t)n + 1));
+    HIPCHK(c, agg.alloc((size_t)n));
+    hipLaunchKernelGGL(k_amg_strength, dim3(gn(n)), bv, 0, st, n, rp, ci, a, excl, sw.p);
+    hipLaunchKernelGGL(k_amg_init_mate, dim3(gn(n)), bv, 0, st, n, excl, mate.p);
+    for (int round = 0; round < kAmgRounds; ++round) {
+        hipLaunchKernelGGL(k_amg_propose, dim3(gn(n)), bv, 0, st, n, rp, ci, sw.p, mate.p, round >= kAmgStrongRounds ? 1 : 0, prop.p);
+        hipLaunchKernelGGL(k_amg_accept, dim3(gn(n)), bv, 0, st, n, prop.p, mate.p);
+    }
+    HIPCHK(c, hipMemsetAsync(lead.p + n, 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(k_amg_leaders, dim3(gn(n)), bv, 0, st, n, mate.p, lead.p);
+    size_t need = 0;
+    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, need, lead.p, id.p, (int)(n + 1), st));
+    HIPCHK(c, tmp.alloc(need));
+    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(tmp.p, need, lead.p, id.p, (int)(n + 1), st));
+    hipLaunchKernelGGL(k_amg_assign, dim3(gn(n)), bv, 0, st, n, mate.p, id.p, agg.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(nc, id.p + n, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    return FDAPDE_OK;
+}
+inline int key_bits(uint64_t v) {
+    int b = 1;
+    while (b < 64 && (v >> b) != 0) ++b;
+    return b;
+}
+// the Galerkin product P^T A P of piecewise-constant P (agg) on the device: a stable key sort, a segmented sum in ascending fine-slot order
+int dev_galerkin(fdapde_ctx* c, int64_t n, int64_t nnz, const int32_t* rp, const int32_t* ci, const double* a, const int32_t* agg, int32_t nc, AmgLevel& out) {
+    hipStream_t st = c->stream;
+    const dim3 bv(256);
+    const uint64_t ncu = (uint64_t)nc, sentinel = ncu * ncu;
+    DBuf<uint64_t> keys, keys_s;
+    DBuf<int32_t> idx, idx_s, head, pos;
+    DBuf<char> tmp;
+    HIPCHK(c, keys.alloc((size_t)nnz));
+    HIPCHK(c, keys_s.alloc((size_t)nnz));
+    HIPCHK(c, idx.alloc((size_t)nnz));
+    HIPCHK(c, idx_s.alloc((size_t)nnz));
+    HIPCHK(c, head.alloc((size_t)nnz + 1));
+    HIPCHK(c, pos.alloc((size_t)nnz + 1));
+    hipLaunchKernelGGL(k_amg_gkeys, dim3(gn(n)), bv, 0, st, n, rp, ci, agg, ncu, sentinel, keys.p, idx.p);
+    const int end_bit = key_bits(sentinel);
+    size_t need_sort = 0, need_scan = 0;
+    HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(nullptr, need_sort, keys.p, keys_s.p, idx.p, idx_s.p, (int)nnz, 0, end_bit, st));
+    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, need_scan, head.p, pos.p, (int)(nnz + 1), st));
+    HIPCHK(c, tmp.alloc(std::max(need_sort, need_scan)));
+    HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(tmp.p, need_sort, keys.p, keys_s.p, idx.p, idx_s.p, (int)nnz, 0, end_bit, st));
+    HIPCHK(c, hipMemsetAsync(head.p + nnz, 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(k_amg_heads, dim3(gn(nnz)), bv, 0, st, nnz, keys_s.p, sentinel, head.p);
+    HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(tmp.p, need_scan, head.p, pos.p, (int)(nnz + 1), st));
+    int32_t nnz_c = 0;
+    HIPCHK(c, hipMemcpyAsync(&nnz_c, pos.p + nnz, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    out.n = nc, out.nnz = nnz_c;
+    HIPCHK(c, out.rp_own.alloc((size_t)nc + 1));
+    HIPCHK(c, out.ci_own.alloc((size_t)std::max(nnz_c, 1)));
+    HIPCHK(c, out.a_own.alloc((size_t)std::max(nnz_c, 1) + 2));
+    HIPCHK(c, hipMemcpyAsync(out.rp_own.p + nc, &nnz_c, sizeof(int32_t), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_amg_gsum, dim3(gn(nnz)), bv, 0, st, nnz, keys_s.p, idx_s.p, a, head.p, pos.p, ncu, out.rp_own.p, out.ci_own.p, out.a_own.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(st));   // (nnz_c is this frame's; the scratch goes out of scope)
+    out.rp = out.rp_own.p, out.ci = out.ci_own.p, out.a = out.a_own.p;
+    return FDAPDE_OK;
+}
+// members of each aggregate (CSR, ascending row index)
+int dev_members(fdapde_ctx* c, int64_t n, const int32_t* agg, int32_t nc, DBuf<int32_t>& mptr, DBuf<int32_t>& midx) {
+    hipStream_t st = c->stream;
+    const dim3 bv(256);
+    DBuf<uint32_t> keys, keys_s;
+    DBuf<int32_t> idx;
+    DBuf<char> tmp;
+    HIPCHK(c, keys.alloc((size_t)n));
+    HIPCHK(c, keys_s.alloc((size_t)n));
+    HIPCHK(c, idx.alloc((size_t)n));
+    HIPCHK(c, midx.alloc((size_t)n));
+    HIPCHK(c, mptr.alloc((size_t)nc + 1));
+    hipLaunchKernelGGL(k_amg_mkeys, dim3(gn(n)), bv, 0, st, n, agg, (uint32_t)nc, keys.p, idx.p);
+    size_t need = 0;
+    const int end_bit = key_bits((uint64_t)nc);
+    HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(nullptr, need, keys.p, keys_s.p, idx.p, midx.p, (int)n, 0, end_bit, st));
+    HIPCHK(c, tmp.alloc(need));
+    HIPCHK(c, hipcub::DeviceRadixSort::SortPairs(tmp.p, need, keys.p, keys_s.p, idx.p, midx.p, (int)n, 0, end_bit, st));
+    hipLaunchKernelGGL(k_amg_mptr, dim3(gn(n)), bv, 0, st, n, keys_s.p, (uint32_t)nc, mptr.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(st));
+    return FDAPDE_OK;
+}
+// D^-1, the Jacobi damping 1.5 / lambda_max(D^-1 A) (15 power iterations), team width and work vectors of a level
+int level_prepare(fdapde_ctx* c, AmgLevel& L, bool has_next) {
+    hipStream_t st = c->stream;
+    const dim3 bv(256);
+    const int64_t n = L.n;
+    HIPCHK(c, L.dinv.alloc((size_t)n));
+    DBuf<int32_t> flag;
+    HIPCHK(c, flag.alloc(1));
+    HIPCHK(c, hipMemsetAsync(flag.p, 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(k_amg_dinv, dim3(gn(n)), bv, 0, st, n, L.rp, L.ci, L.a, L.excl, L.dinv.p, flag.p);
+    int32_t bad = 0;
+    HIPCHK(c, hipMemcpyAsync(&bad, flag.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (bad) return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_AMG: a level has a zero diagonal entry (its damped Jacobi smoother needs one)");
+    const double per_row = n > 0 ? (double)L.nnz / (double)n : 1.0;
+    L.team = per_row <= 10.0 ? 4 : per_row <= 24.0 ? 8 : 16;
+    L.np = (int)std::min<int64_t>(1024, std::max<int64_t>(1, (n * L.team + 1023) / 1024));
+    for (DBuf<double>* p : {&L.b, &L.zt, &L.cv, &L.v, &L.dv, &L.w, &L.rt, &L.e}) HIPCHK(c, p->alloc((size_t)std::max<int64_t>(n, 1)));
+    HIPCHK(c, hipMemsetAsync(L.zt.p, 0, sizeof(double) * (size_t)std::max<int64_t>(n, 1), st));   // (rows of no aggregate are never written: their 0 stays)
+    HIPCHK(c, L.part.alloc(3 * (size_t)std::max(L.np, 1024)));
+    HIPCHK(c, L.sc.alloc(8));
+    HIPCHK(c, hipMemsetAsync(L.sc.p, 0, 8 * sizeof(double), st));
+    L.om = 0.0;
+    if (!has_next) return FDAPDE_OK;   // (the coarsest level is inverted, not smoothed)
+    // lambda_max(D^-1 A) by the power iteration (as the two-level solver's); the dots in a fixed order
+    double* x = L.v.p;
+    double* y = L.w.p;
+    double h[3] = {0, 0, 0};
+    hipLaunchKernelGGL(k_amg_hashvec, dim3(gn(n)), bv, 0, st, n, L.dinv.p, x);
+    const int np = (int)std::min<int64_t>(1024, std::max<int64_t>(1, (n + 4095) / 4096));
+    double lam = 0.0;
+    for (int pi = 0; pi < 15; ++pi) {
+        hipLaunchKernelGGL(k_amg_dax, dim3(gn(n)), bv, 0, st, n, L.rp, L.ci, L.a, L.dinv.p, x, y);
+        fixed_dots(st, n, np, x, x, y, y, nullptr, nullptr, L.part.p, L.sc.p);
+        HIPCHK(c, hipMemcpyAsync(h, L.sc.p, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        if (!(h[0] > 0.0) || !std::isfinite(h[1])) break;
+        lam = std::sqrt(h[1] / h[0]);
+        if (!(h[1] > 0.0)) break;
+        hipLaunchKernelGGL(k_amg_scale, dim3(gn(n)), bv, 0, st, n, y, 1.0 / std::sqrt(h[1]), x);
+    }
+    HIPCHK(c, hipMemsetAsync(L.sc.p, 0, 8 * sizeof(double), st));
+    L.om = lam > 0.0 && std::isfinite(lam) ? 1.5 / lam : 0.0;
+    return FDAPDE_OK;
+}
+}   // namespace
+
+bool amg_eligible(const fdapde_ctx* c) {
+    return c->has_device && c->dev_ready && c->comm == nullptr && c->ar_fn == nullptr && !c->halo_ready && !c->rd.ready && !c->group;
+}
+
+void amg_release(fdapde_ctx* c) {
+    if (c->has_device) (void)hipSetDevice(c->device);
+    delete c->amg;
+    delete c->amg_lin;
+    c->amg = c->amg_lin = nullptr;
+}
+
+// the hierarchy of A (the context's pattern, internal order); use_bnd: level 0's Dirichlet DOFs (c->bnd) belong to no aggregate
+int amg_build(fdapde_ctx* c, AmgHierarchy** slot, const double* A, int use_bnd, bool symmetric) {
+    delete *slot;
+    *slot = nullptr;
+    HIPCHK(c, hipSetDevice(c->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    std::unique_ptr<AmgHierarchy> H(new AmgHierarchy());
+    H->sym = symmetric, H->use_bnd = use_bnd, H->A = A;
+    const int64_t coarse_rows = std::max<int64_t>(1, std::min<int64_t>(c->amg_coarse_rows, kAmgMaxCoarse));
+    {
+        std::unique_ptr<AmgLevel> L0(new AmgLevel());
+        L0->n = c->hs.n_dofs, L0->nnz = c->hs.nnz, L0->rp = c->rowptr.p, L0->ci = c->colidx.p, L0->a = A, L0->excl = use_bnd ? c->bnd.p : nullptr;
+        H->lv.push_back(std::move(L0));
+    }
+    std::vector<uint8_t> excl_h;
+    if (c->amg_setup_check && use_bnd) {
+        if (int rc = fetch(c, c->bnd.p, (size_t)c->hs.n_dofs, excl_h)) return rc;
+    }
+    while (H->lv.back()->n > coarse_rows) {
+        AmgLevel& F = *H->lv.back();
+        // pass 1 on the level, pass 2 on the Galerkin matrix of pass 1 (the pair graph): aggregates of at most four rows
+        DBuf<int32_t> agg1, agg2;
+        int32_t n1 = 0, n2 = 0;
+        if (int rc = dev_pairwise(c, F.n, F.nnz, F.rp, F.ci, F.a, F.excl, agg1, &n1)) return rc;
+        if (n1 == 0) return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_AMG: a level above the dense limit has no free rows to aggregate");
+        AmgLevel T;
+        if (int rc = dev_galerkin(c, F.n, F.nnz, F.rp, F.ci, F.a, agg1.p, n1, T)) return rc;
+        if (int rc = dev_pairwise(c, T.n, T.nnz, T.rp, T.ci, T.a, nullptr, agg2, &n2)) return rc;
+        std::unique_ptr<AmgLevel> N(new AmgLevel());
+        if (int rc = dev_galerkin(c, T.n, T.nnz, T.rp, T.ci, T.a, agg2.p, n2, *N)) return rc;
+        HIPCHK(c, F.agg.alloc((size_t)F.n));
+        hipLaunchKernelGGL(k_amg_compose, dim3(gn(F.n)), dim3(256), 0, c->stream, F.n, agg1.p, agg2.p, F.agg.p);
+        if (int rc = dev_members(c, F.n, F.agg.p, n2, F.mptr, F.midx)) return rc;
+        if (c->amg_setup_check) {   // the same level by the host loops, compared bit for bit
+            HostCsr hf, ht, hn;
+            hf.n = F.n;
+            if (int rc = fetch(c, F.rp, (size_t)F.n + 1, hf.rp)) return rc;
+            if (int rc = fetch(c, F.ci, (size_t)F.nnz, hf.ci)) return rc;
+            if (int rc = fetch(c, F.a, (size_t)F.nnz, hf.a)) return rc;
+            std::vector<int32_t> a1, a2, comp((size_t)F.n), mptr((size_t)n2 + 1, 0), midx;
+            int32_t m1 = 0, m2 = 0;
+            host_pairwise(hf, H->lv.size() == 1 && use_bnd ? excl_h.data() : nullptr, a1, m1);
+            host_galerkin(hf, a1, m1, ht);
+            host_pairwise(ht, nullptr, a2, m2);
+            host_galerkin(ht, a2, m2, hn);
+            for (int64_t i = 0; i < F.n; ++i) comp[(size_t)i] = a1[(size_t)i] < 0 ? -1 : a2[(size_t)a1[(size_t)i]];
+            for (int64_t i = 0; i < F.n; ++i)
+                if (comp[(size_t)i] >= 0) ++mptr[(size_t)comp[(size_t)i] + 1];
+            for (int32_t q = 0; q < m2; ++q) mptr[(size_t)q + 1] += mptr[(size_t)q];
+            midx.resize((size_t)mptr[(size_t)m2]);
+            {
+                std::vector<int32_t> fill(mptr.begin(), mptr.end() - 1);
+                for (int64_t i = 0; i < F.n; ++i)
+                    if (comp[(size_t)i] >= 0) midx[(size_t)fill[(size_t)comp[(size_t)i]]++] = (int32_t)i;
+            }
+            std::string which;
+            if (m1 != n1 || !same_dev(agg1.p, (size_t)F.n, a1)) which += " pass-1 aggregates";
+            if (m2 != n2 || (m1 == n1 && !same_dev(agg2.p, (size_t)n1, a2))) which += " pass-2 aggregates";
+            if (which.empty()) {
+                if (!same_dev(T.rp, (size_t)n1 + 1, ht.rp) || !same_dev(T.ci, (size_t)T.nnz, ht.ci)) which += " pair-graph pattern";
+                else if (!same_dev(T.a, (size_t)T.nnz, ht.a)) which += " pair-graph values";
+                if (!same_dev(N->rp, (size_t)n2 + 1, hn.rp) || !same_dev(N->ci, (size_t)N->nnz, hn.ci)) which += " coarse pattern";
+                else if (!same_dev(N->a, (size_t)N->nnz, hn.a)) which += " coarse values";
+                if (!same_dev(F.agg.p, (size_t)F.n, comp)) which += " composite aggregates";
+                if (!same_dev(F.mptr.p, (size_t)n2 + 1, mptr) || !same_dev(F.midx.p, midx.size(), midx)) which += " members";
+            }
+            if (!which.empty()) {
+                c->err = "amg_setup_check: level " + std::to_string(H->lv.size() - 1) + ": the device-built hierarchy differs from the host-built one:" + which;
+                return FDAPDE_EHIP;
+            }
+        }
+        if ((double)n2 > kAmgStall * (double)F.n && n2 > coarse_rows) {   // coarsening stalled: a level the dense inverse takes ends the hierarchy
+            if (F.n > kAmgMaxCoarse)
+                return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_AMG: coarsening stalled above the dense limit (a level kept more than 0.8 of its rows): the matrix has too few strong couplings for pairwise aggregation");
+            F.agg.release(), F.mptr.release(), F.midx.release();
+            break;
+        }
+        H->lv.push_back(std::move(N));
+    }
+    double nnz_all = 0.0;
+    for (size_t l = 0; l < H->lv.size(); ++l) {
+        if (int rc = level_prepare(c, *H->lv[l], l + 1 < H->lv.size())) return rc;
+        nnz_all += (double)H->lv[l]->nnz;
+    }
+    H->op_complexity = nnz_all / std::max(1.0, (double)H->lv[0]->nnz);
+    AmgLevel& C = *H->lv.back();
+    const int dense_bnd = H->lv.size() == 1 ? use_bnd : 0;
+    if (int rc = dense_build_csr(c, C.n, C.rp, C.ci, C.a, dense_bnd ? c->bnd.p : nullptr, dense_bnd, H->D)) return rc;
+    if (!H->D.ready)
+        return fail(c, FDAPDE_ENOCONV, "FDAPDE_SOLVER_AMG: the coarsest level is singular to working precision (a pure Neumann problem has no unique solution)");
+    H->setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    *slot = H.release();
+    return FDAPDE_OK;
+}
+
+namespace {
+// e_m = (level m's system)^-1 b_m approximately: the dense inverse on the coarsest level, two flexible CG / GCR steps around the cycle elsewhere
+int amg_correction(fdapde_ctx* c, AmgHierarchy& H, size_t m);
+// out = the cycle of level l on r (l < coarsest): Jacobi, the coarse correction, Jacobi
+int amg_cycle(fdapde_ctx* c, AmgHierarchy& H, size_t l, const double* r, double* out) {
+    hipStream_t st = c->stream;
+    AmgLevel& L = *H.lv[l];
+    AmgLevel& N = *H.lv[l + 1];
+    by_team(L.team, [&](auto t) {
+        constexpr int T = decltype(t)::value;
+        hipLaunchKernelGGL(k_amg_pre_restrict<T>, dim3(gn(N.n * T)), dim3(256), 0, st, N.n, L.mptr.p, L.midx.p, L.rp, L.ci, L.a, L.dinv.p, L.om, r, L.zt.p, N.b.p);
+    });
+    if (int rc = amg_correction(c, H, l + 1)) return rc;
+    by_team(L.team, [&](auto t) {
+        constexpr int T = decltype(t)::value;
+        hipLaunchKernelGGL(k_amg_post<T>, dim3(gn(L.n * T)), dim3(256), 0, st, L.n, L.rp, L.ci, L.a, L.dinv.p, L.om, L.agg.p, N.e.p, r, L.zt.p, out);
+    });
+    return FDAPDE_OK;
+}
+int amg_correction(fdapde_ctx* c, AmgHierarchy& H, size_t m) {
+    hipStream_t st = c->stream;
+    AmgLevel& L = *H.lv[m];
+    if (m + 1 == H.lv.size()) return dense_apply(c, H.D, 1, L.b.p, L.e.p);
+    const int64_t n = L.n;
+    const bool fcg = H.sym;
+    auto spmv_dots = [&](const double* x, double* y, const double* p0, const double* q0, const double* p1, const double* q1, const double* p2, const double* q2) {
+        by_team(L.team, [&](auto t) {
+            constexpr int T = decltype(t)::value;
+            hipLaunchKernelGGL(k_amg_spmv_dots<T>, dim3((unsigned)L.np), dim3(256), 0, st, n, L.rp, L.ci, L.a, x, y, p0, q0, p1, q1, p2, q2, L.part.p);
+        });
+    };
+    // step 1: c = B b, v = A c
+    if (int rc = amg_cycle(c, H, m, L.b.p, L.cv.p)) return rc;
+    if (fcg) spmv_dots(L.cv.p, L.v.p, L.cv.p, L.v.p, L.cv.p, L.b.p, nullptr, nullptr);
+    else spmv_dots(L.cv.p, L.v.p, L.v.p, L.v.p, L.v.p, L.b.p, nullptr, nullptr);
+    hipLaunchKernelGGL(k_amg_coef, dim3(1), dim3(256), 0, st, L.part.p, L.np, 1, L.sc.p);
+    hipLaunchKernelGGL(k_amg_axpy_sc, dim3(gn(n)), dim3(256), 0, st, n, L.b.p, L.v.p, L.sc.p, L.rt.p);
+    // step 2: d = B rt, w = A d
+    if (int rc = amg_cycle(c, H, m, L.rt.p, L.dv.p)) return rc;
+    if (fcg) spmv_dots(L.dv.p, L.w.p, L.dv.p, L.v.p, L.dv.p, L.w.p, L.dv.p, L.rt.p);
+    else spmv_dots(L.dv.p, L.w.p, L.v.p, L.w.p, L.w.p, L.w.p, L.w.p, L.rt.p);
+    hipLaunchKernelGGL(k_amg_coef, dim3(1), dim3(256), 0, st, L.part.p, L.np, 2, L.sc.p);
+    hipLaunchKernelGGL(k_amg_comb2, dim3(gn(n)), dim3(256), 0, st, n, L.cv.p, L.dv.p, L.sc.p, L.e.p);
+    return FDAPDE_OK;
+}
+}   // namespace
+
+int amg_run(fdapde_ctx* c, AmgHierarchy* hp, const double* A, const double* f_dev, const double* g_dev, int use_bnd, const double* x0_dev, double rtol, int maxit) {
+    AmgHierarchy& H = *hp;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    AmgLevel& L0 = *H.lv[0];
+    const int64_t n = L0.n;
+    const auto t_begin = std::chrono::steady_clock::now();
+    const dim3 gv(gn(n)), bv(256);
+    H.np = (int)std::min<int64_t>(1024, std::max<int64_t>(1, (n + 4095) / 4096));
+    int mk = (int)std::min<int64_t>(50, std::max<int64_t>(5, (int64_t)(16e9 / (16.0 * (double)n))));   // (at most ~16 GB of basis)
+    mk = std::max(1, std::min(mk, std::max(maxit, 1)));
+    HIPCHK(c, H.vec.alloc(3 * (size_t)n));
+    HIPCHK(c, H.basis.alloc((size_t)(2 * mk + 1) * (size_t)n));
+    HIPCHK(c, H.part.alloc((size_t)(mk + 2) * (size_t)H.np));
+    HIPCHK(c, H.dots.alloc((size_t)(mk + 4)));
+    double *x = H.vec.p, *r = x + n, *t = r + n;
+    const uint8_t* bnd = c->bnd.p;
+    double h[3] = {0, 0, 0};
+    auto dots = [&](const double* a0, const double* b0) -> int {
+        fixed_dots(st, n, H.np, a0, b0, nullptr, nullptr, nullptr, nullptr, H.part.p, H.dots.p);
+        HIPCHK(c, hipMemcpyAsync(h, H.dots.p, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        return FDAPDE_OK;
+    };
+    auto apply_K = [&](const double* in, const double* f, double* out) {   // out = K in, or (f given) rhs - K in
+        by_team(L0.team, [&](auto tt) {
+            constexpr int T = decltype(tt)::value;
+            hipLaunchKernelGGL(k_amg_apply_K<T>, dim3(gn(n * T)), bv, 0, st, n, L0.rp, L0.ci, A, bnd, use_bnd, in, f, g_dev, out);
+        });
+    };
+    // the lift of the Dirichlet data: the stop rule is relative to its residual (as the two-level solver's)
+    hipLaunchKernelGGL(k_amg_start, gv, bv, 0, st, n, bnd, use_bnd, g_dev, (const double*)nullptr, x);
+    apply_K(x, f_dev, r);
+    if (int rc = dots(r, r)) return rc;
+    const double bb = h[0];
+    double rr = h[0];
+    if (x0_dev) {
+        hipLaunchKernelGGL(k_amg_start, gv, bv, 0, st, n, bnd, use_bnd, g_dev, x0_dev, x);
+        apply_K(x, f_dev, r);
+        if (int rc = dots(r, r)) return rc;
+        rr = h[0];
+    }
+    int it = 0;
+    bool converged = rr <= rtol * rtol * bb, broke = false;
+    const bool one_level = H.lv.size() == 1;
+    auto precond = [&](const double* v, double* z, double* w, bool&) -> int {
+        if (one_level) {
+            if (int rc = dense_apply(c, H.D, 1, v, z)) return rc;
+        } else if (int rc = amg_cycle(c, H, 0, v, z))
+            return rc;
+        apply_K(z, nullptr, w);
+        return FDAPDE_OK;
+    };
+    auto residual = [&](double& rr_out) -> int {
+        apply_K(x, f_dev, r);
+        if (int rc = dots(r, r)) return rc;
+        rr_out = h[0];
+        return FDAPDE_OK;
+    };
+    FgmresSpace fs{n, mk, H.basis.p, H.basis.p + (size_t)(mk + 1) * (size_t)n, H.part.p, H.dots.p, H.np};
+    if (int rc = fgmres_outer(c, fs, x, r, nullptr, rtol, maxit, bb, precond, residual, rr, it, converged, broke)) return rc;
+    // the TRUE residual of what is handed out
+    apply_K(x, f_dev, t);
+    if (int rc = dots(t, t)) return rc;
+    const double true_rel = bb > 0 ? std::sqrt(h[0] / bb) : 0.0;
+    if (converged && !(true_rel <= 10.0 * rtol)) converged = false;
+    HIPCHK(c, c->u.alloc((size_t)n));
+    HIPCHK(c, hipMemcpyAsync(c->u.p, x, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    const double t_asm = c->info.t_assemble_ms;
+    c->info = fdapde_info{};
+    c->info.t_assemble_ms = t_asm;
+    c->info.method_used = FDAPDE_SOLVER_AMG, c->info.iters = it, c->info.converged = converged ? 1 : 0, c->info.relres = true_rel, c->info.persistent = 0;
+    c->info.t_solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    if (std::getenv("FDAPDE_DEBUG_SETUP")) {
+        std::string rows;
+        for (size_t l = 0; l < H.lv.size(); ++l) rows += (l ? " / " : "") + std::to_string(H.lv[l]->n);
+        std::fprintf(stderr, "amg: %zu levels, rows %s, operator complexity %.3f, set-up %.2f ms, solve %.2f ms, %d iterations, true relres %.2e\n", H.lv.size(),
+                     rows.c_str(), H.op_complexity, H.setup_ms, c->info.t_solve_ms, it, true_rel);
+    }
+    if (!converged) {
+        c->err = broke ? "FDAPDE_SOLVER_AMG: the flexible GMRES broke down" : "FDAPDE_SOLVER_AMG: maxit reached";
+        return FDAPDE_ENOCONV;
+    }
+    return FDAPDE_OK;
+}
+
+// fdapde_solve with FDAPDE_SOLVER_AMG: the reference's row-zeroed system (fem_linear_elliptic_solver.h:38-47), its hierarchy kept while the matrix epoch and
+// the Dirichlet variant stay
+int e_solve_amg(fdapde_ctx* c, const fdapde_options* opt, fdapde_info* info) {
+    if (!amg_eligible(c)) return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_AMG takes one-GPU contexts");
+    const double rtol = (opt && opt->rtol > 0) ? opt->rtol : 1e-10;
+    const int maxit = (opt && opt->maxit > 0) ? opt->maxit : 200;
+    const double* A = c->vals[FDAPDE_MAT_STIFF].p;
+    const int use_bnd = c->have_g ? 1 : 0;
+    const int64_t key = 2 * c->init_count + use_bnd;
+    if (!c->amg || c->amg->key != key || c->amg->A != A) {
+        if (int rc = amg_build(c, &c->amg, A, use_bnd, c->op_symmetric)) {
+            c->info = fdapde_info{};
+            c->info.method_used = FDAPDE_SOLVER_AMG;
+            if (info) *info = c->info;
+            return rc;
+        }
+        c->amg->key = key;
+    }
+    const int rc = amg_run(c, c->amg, A, c->force.p, c->g.p, use_bnd, nullptr, rtol, maxit);
+    if (rc != FDAPDE_OK && rc != FDAPDE_ENOCONV) return rc;
+    c->solved = true, c->dirichlet_applied = c->have_g;
+    if (info) *info = c->info;
+    return rc;
+}
+
+void amg_forget(fdapde_ctx* c) {
+    delete c->amg;
+    c->amg = nullptr;
+}
+
+// fdapde_lin_solve with FDAPDE_SOLVER_AMG: the hierarchy of the handle's matrix (no Dirichlet reduction), built by the first solve after fdapde_lin_compute and
+// shared by every later column; columns one after the other
+int amg_lin_solve(fdapde_ctx* c, const fdapde_options* opt, const double* b, int32_t n_rhs, double* x, fdapde_info* info) {
+    if (!amg_eligible(c)) return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_AMG takes one-GPU contexts");
+    const double rtol = (opt && opt->rtol > 0) ? opt->rtol : 1e-10;
+    const int maxit = (opt && opt->maxit > 0) ? opt->maxit : 200;
+    const int64_t n = c->hs.n_dofs;
+    hipStream_t st = c->stream;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!c->amg_lin || c->amg_lin->key != c->amg_lin_epoch) {
+        if (int rc = amg_build(c, &c->amg_lin, c->lin_mat.p, 0, c->lin_symmetric)) {
+            c->info = fdapde_info{};
+            c->info.method_used = FDAPDE_SOLVER_AMG;
+            if (info) *info = c->info;
+            return rc;
+        }
+        c->amg_lin->key = c->amg_lin_epoch;
+    }
+    c->solved = false;   // c->u is about to hold the handle's solutions, not PDE::solution()
+    DBuf<double>& rhs = c->lin_rhs;
+    HIPCHK(c, rhs.alloc((size_t)n));
+    int total = 0, rc_all = FDAPDE_OK;
+    double worst = 0.0;
+    for (int32_t j = 0; j < n_rhs; ++j) {
+        HIPCHK(c, hipMemcpyAsync(c->tmp_e.p, b + (size_t)j * n, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_amg_gather, dim3(gn(n)), dim3(256), 0, st, n, c->dof_i2e.p, c->tmp_e.p, rhs.p);
+        const int rc = amg_run(c, c->amg_lin, c->lin_mat.p, rhs.p, nullptr, 0, nullptr, rtol, maxit);
+        if (rc != FDAPDE_OK && rc != FDAPDE_ENOCONV) return rc;
+        if (rc == FDAPDE_ENOCONV) rc_all = rc;
+        total += c->info.iters, worst = std::max(worst, c->info.relres);
+        hipLaunchKernelGGL(k_amg_scatter, dim3(gn(n)), dim3(256), 0, st, n, c->dof_i2e.p, c->u.p, c->tmp_e.p);
+        HIPCHK(c, hipMemcpyAsync(x + (size_t)j * n, c->tmp_e.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));   // (tmp_e is reused by the next column)
+    }
+    c->info.iters = total, c->info.relres = worst, c->info.converged = rc_all == FDAPDE_OK ? 1 : 0, c->info.method_used = FDAPDE_SOLVER_AMG, c->info.persistent = 0;
+    c->info.t_solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (rc_all != FDAPDE_OK) c->err = "FDAPDE_SOLVER_AMG: maxit reached in at least one column";
+    if (info) *info = c->info;
+    return rc_all;
+}
+
+}   // namespace fdapde_engine

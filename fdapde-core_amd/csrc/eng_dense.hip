@@ -58,9 +58,13 @@ double dense_build_estimate_ms(int64_t n) {
 // D.X = (the matrix A of the pattern, its Dirichlet rows replaced by unit rows if use_bnd)^-1, internal DOF order.  D.ready, or D.failed where the
 // matrix is singular to working precision / the launch could not run: the caller keeps its Krylov path.
 int dense_build(fdapde_ctx* c, const double* A, int use_bnd, fdapde_ctx::Dense& D) {
-    const int64_t n = c->hs.n_dofs;
+    return dense_build_csr(c, c->hs.n_dofs, c->rowptr.p, c->colidx.p, A, c->bnd.p, use_bnd, D);
+}
+
+// ... of any matrix of n rows in CSR form (device arrays in the context's stream order; FDAPDE_SOLVER_AMG's coarsest level); bnd is read only where use_bnd
+int dense_build_csr(fdapde_ctx* c, int64_t n, const int32_t* rowptr, const int32_t* colidx, const double* A, const uint8_t* bnd, int use_bnd, fdapde_ctx::Dense& D) {
     hipStream_t st = c->stream;
-    D.ready = false, D.failed = true, D.n = n, D.use_bnd = use_bnd, D.A = A;
+    D.ready = false, D.failed = true, D.n = n, D.use_bnd = use_bnd, D.A = A, D.rowptr = rowptr, D.colidx = colidx, D.bnd = bnd;
     const auto t0 = std::chrono::steady_clock::now();
     DBuf<double> S;
     DBuf<int32_t> perm, status;
@@ -92,7 +96,7 @@ int dense_build(fdapde_ctx* c, const double* A, int use_bnd, fdapde_ctx::Dense& 
     HIPCHK(c, hipMemsetAsync(cand.p, 0, 2 * (size_t)G * sizeof(unsigned long long), st));
     HIPCHK(c, hipMemsetAsync(status.p, 0, 4 * sizeof(int32_t), st));
     HIPCHK(c, hipMemsetAsync(worst.p, 0, 2 * sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(k_dense_fill, dim3((unsigned)n), dim3(256), 0, st, n, ld, c->rowptr.p, c->colidx.p, A, c->bnd.p, use_bnd, S.p);
+    hipLaunchKernelGGL(k_dense_fill, dim3((unsigned)n), dim3(256), 0, st, n, ld, rowptr, colidx, A, bnd, use_bnd, S.p);
     const double* result = S.p;
     if (blocked) {
         HIPCHK(c, S1.alloc((size_t)n * (size_t)ld));
@@ -143,7 +147,7 @@ int dense_build(fdapde_ctx* c, const double* A, int use_bnd, fdapde_ctx::Dense& 
         hipLaunchKernelGGL(k_dense_invert, dim3((unsigned)G), dim3(kDenseT), lds, st, a);
     }
     hipLaunchKernelGGL(k_dense_unpermute, dim3((unsigned)n), dim3(256), 0, st, n, ld, result, perm.p, D.X.p);
-    hipLaunchKernelGGL(k_dense_check, dim3((unsigned)n), dim3(256), 0, st, n, c->rowptr.p, c->colidx.p, A, c->bnd.p, use_bnd, D.X.p, worst.p);
+    hipLaunchKernelGGL(k_dense_check, dim3((unsigned)n), dim3(256), 0, st, n, rowptr, colidx, A, bnd, use_bnd, D.X.p, worst.p);
     HIPCHK(c, hipGetLastError());
     int32_t h_status[4] = {0, 0, 0, 0};
     unsigned long long h_worst = 0;
@@ -199,7 +203,7 @@ int dense_apply(fdapde_ctx* c, fdapde_ctx::Dense& D, int nc, const double* b, do
     launch_gemv(c, D, nc, b, x, 0);
     if (D.refine) {
         if (int rc = ensure_dense_work(c, (size_t)n * nc)) return rc;
-        hipLaunchKernelGGL(k_dense_residual, dim3(g1(n * nc)), dim3(256), 0, c->stream, n, nc, c->rowptr.p, c->colidx.p, D.A, c->bnd.p, D.use_bnd, b, x, c->dn_r.p);
+        hipLaunchKernelGGL(k_dense_residual, dim3(g1(n * nc)), dim3(256), 0, c->stream, n, nc, D.rowptr, D.colidx, D.A, D.bnd, D.use_bnd, b, x, c->dn_r.p);
         launch_gemv(c, D, nc, c->dn_r.p, x, 1);
     }
     HIPCHK(c, hipGetLastError());

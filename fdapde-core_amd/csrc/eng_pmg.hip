@@ -22,6 +22,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <vector>
 
 #include <hipcub/hipcub.hpp>
@@ -242,6 +243,115 @@ __global__ void k_pmg_cell_mean(int64_t n_cells, int nq2, int nq1, int width, co
 }
 inline unsigned g1n(int64_t n) { return (unsigned)((n + 255) / 256); }
 }   // namespace
+
+// up to three dot products a_q . b_q into out[0 .. 2] (device), per-workgroup partials in part[3 * np] summed in a fixed order: the same bits every run
+void fixed_dots(hipStream_t st, int64_t n, int np, const double* a0, const double* b0, const double* a1, const double* b1, const double* a2, const double* b2,
+                double* part, double* out) {
+    hipLaunchKernelGGL(k_pmg_dots, dim3((unsigned)np), dim3(256), 0, st, n, a0, b0, a1, b1, a2, b2, part);
+    hipLaunchKernelGGL(k_pmg_reduce, dim3(1), dim3(256), 0, st, part, np, out);
+}
+
+// ---- the outer method, FLEXIBLE GMRES (right-preconditioned: A Z_k = V_{k+1} H_k with Z_j = M^-1 v_j kept, so M^-1 may be a different operator every time it
+// is applied).  One preconditioner application per iteration -- precond(v_j, z_j, w, stop) leaves z_j and w = A z_j (stop: no further iteration makes sense) --,
+// the residual norm from the Givens recurrence; the residual of the iterate computed at every restart by residual(rr) (r = rhs - A x, rr = r.r: the recurrence's
+// word is not taken for convergence).  Gram-Schmidt twice per vector (the Krylov basis of a solve to 1e-10 is ill-conditioned by then); restart after s.mk vectors.
+// On entry r holds the residual of x and rr its square; x += Z y [* comb_dinv] per cycle.  Shared by the two-level solver and FDAPDE_SOLVER_AMG (eng_amg.hip).
+int fgmres_outer(fdapde_ctx* c, const FgmresSpace& s, double* x, double* r, const double* comb_dinv, double rtol, int maxit, double bb,
+                 const std::function<int(const double*, double*, double*, bool&)>& precond, const std::function<int(double&)>& residual, double& rr, int& it,
+                 bool& converged, bool& broke) {
+    hipStream_t st = c->stream;
+    const int64_t n2 = s.n;
+    const int mk = s.mk;
+    const dim3 gv(g1n(n2)), bv(256);
+    double* V = s.V;
+    double* Z = s.Z;
+    std::vector<double> H((size_t)(mk + 1) * mk, 0.0), cs((size_t)mk), sn((size_t)mk), gg((size_t)mk + 1), hj((size_t)mk + 4), yy((size_t)mk);
+    auto Hat = [&](int i, int j) -> double& { return H[(size_t)j * (mk + 1) + i]; };
+    const unsigned gnp = (unsigned)s.np;
+    while (!converged && !broke && it < maxit) {
+        // (r holds the residual of x, rr its square)
+        const double beta = std::sqrt(rr);
+        if (!(beta > 0.0) || !std::isfinite(beta)) {
+            broke = !std::isfinite(beta);
+            converged = !broke;
+            break;
+        }
+        hipLaunchKernelGGL(k_pmg_scale, gv, bv, 0, st, n2, r, 1.0 / beta, V);
+        std::fill(gg.begin(), gg.end(), 0.0);
+        gg[0] = beta;
+        int k = 0;   // columns of this cycle
+        bool cycle_done = false;
+        while (!cycle_done && k < mk && it < maxit) {
+            const int j = k;
+            double* zj = Z + (size_t)j * (size_t)n2;
+            double* w = V + (size_t)(j + 1) * (size_t)n2;
+            const double* vj = V + (size_t)j * (size_t)n2;
+            bool stop = false;
+            if (int rc = precond(vj, zj, w, stop)) return rc;
+            if (stop) {
+                broke = true;
+                break;
+            }
+            // Gram-Schmidt, twice: h = V^T w, w -= V h, then the same on what is left (its coefficients add to h)
+            double wnorm2 = 0;
+            for (int pass = 0; pass < 2; ++pass) {
+                hipLaunchKernelGGL(k_pmg_mdot, dim3(gnp), bv, 0, st, n2, V, n2, j + 1, w, s.part);
+                hipLaunchKernelGGL(k_pmg_mreduce, dim3((unsigned)(j + 2)), bv, 0, st, s.part, s.np, s.dots);
+                hipLaunchKernelGGL(k_pmg_msub, dim3(gnp), bv, 0, st, n2, V, n2, j + 1, s.dots, w, s.part);
+                hipLaunchKernelGGL(k_pmg_mreduce, dim3(1), bv, 0, st, s.part, s.np, s.dots + (j + 2));
+                HIPCHK(c, hipMemcpyAsync(hj.data(), s.dots, sizeof(double) * (size_t)(j + 3), hipMemcpyDeviceToHost, st));
+                HIPCHK(c, hipStreamSynchronize(st));
+                for (int i = 0; i <= j; ++i) Hat(i, j) = pass == 0 ? hj[(size_t)i] : Hat(i, j) + hj[(size_t)i];
+                wnorm2 = hj[(size_t)j + 2];
+            }
+            const double hn = std::sqrt(wnorm2);
+            if (!std::isfinite(hn)) {
+                broke = true;
+                break;
+            }
+            Hat(j + 1, j) = hn;
+            for (int i = 0; i < j; ++i) {
+                const double a0 = Hat(i, j), a1 = Hat(i + 1, j);
+                Hat(i, j) = cs[(size_t)i] * a0 + sn[(size_t)i] * a1, Hat(i + 1, j) = -sn[(size_t)i] * a0 + cs[(size_t)i] * a1;
+            }
+            const double d = std::hypot(Hat(j, j), Hat(j + 1, j));
+            if (!(d > 0.0)) {   // (a zero column: M^-1 v_j = 0 -- nothing this basis can do)
+                broke = true;
+                break;
+            }
+            cs[(size_t)j] = Hat(j, j) / d, sn[(size_t)j] = Hat(j + 1, j) / d;
+            Hat(j, j) = d, Hat(j + 1, j) = 0.0;
+            gg[(size_t)j + 1] = -sn[(size_t)j] * gg[(size_t)j], gg[(size_t)j] = cs[(size_t)j] * gg[(size_t)j];
+            ++k, ++it;
+            rr = gg[(size_t)k] * gg[(size_t)k];
+            if (rr <= rtol * rtol * bb || !(hn > 1e-300)) cycle_done = true;   // (hn = 0: the exact solution lies in this basis)
+            else hipLaunchKernelGGL(k_pmg_scale, gv, bv, 0, st, n2, w, 1.0 / hn, w);
+        }
+        if (k > 0) {   // x += Z y, H y = g (upper triangular after the rotations)
+            for (int i = k - 1; i >= 0; --i) {
+                double sacc = gg[(size_t)i];
+                for (int q = i + 1; q < k; ++q) sacc -= Hat(i, q) * yy[(size_t)q];
+                yy[(size_t)i] = sacc / Hat(i, i);
+            }
+            HIPCHK(c, hipMemcpyAsync(s.dots, yy.data(), sizeof(double) * (size_t)k, hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(k_pmg_comb, gv, bv, 0, st, n2, Z, n2, k, s.dots, comb_dinv, x);
+            HIPCHK(c, hipStreamSynchronize(st));   // (yy is the host's)
+        }
+        if (broke) break;
+        // the residual of the new iterate, computed (it starts the next cycle, and the recurrence's word is not taken for convergence)
+        if (int rc = residual(rr)) return rc;
+        if (!std::isfinite(rr)) {
+            broke = true;
+            break;
+        }
+        converged = rr <= rtol * rtol * bb;
+        if (!converged && k == 0) {
+            broke = true;
+            break;
+        }
+    }
+    return FDAPDE_OK;
+}
 
 void pmg_release(fdapde_ctx* c) {
     fdapde_ctx::Pmg& m = c->pmg;
@@ -710,110 +820,38 @@ int pmg_run(fdapde_ctx* c, const double* A, const double* f_dev, const double* g
         const bool cycle = smooth && om > 0.0;
         const double* comb_dinv = (fb || cycle) ? m.dinv.p : nullptr;
         (void)primed;
-        double* V = m.basis.p;
-        double* Z = V + (size_t)(mk + 1) * (size_t)n2;
-        std::vector<double> H((size_t)(mk + 1) * mk, 0.0), cs((size_t)mk), sn((size_t)mk), gg((size_t)mk + 1), hj((size_t)mk + 4), yy((size_t)mk);
-        auto Hat = [&](int i, int j) -> double& { return H[(size_t)j * (mk + 1) + i]; };
-        const unsigned gnp = (unsigned)m.np;
-        while (!converged && !broke && it < maxit) {
-            // (r holds the residual of x, rr its square)
-            const double beta = std::sqrt(rr);
-            if (!(beta > 0.0) || !std::isfinite(beta)) {
-                broke = !std::isfinite(beta);
-                converged = !broke;
-                break;
+        FgmresSpace fs{n2, mk, m.basis.p, m.basis.p + (size_t)(mk + 1) * (size_t)n2, m.part.p, m.dots.p, m.np};
+        auto precond = [&](const double* vj, double* zj, double* w, bool& stop) -> int {
+            if (cycle) {
+                KD(vj, tb);                                                                     // A z1, z1' = om v
+                hipLaunchKernelGGL(k_pmg_lin, gv, bv, 0, st, n2, vj, om, tb, rb);               // r1 = v - om A D^-1 v
+                if (int rc = coarse_and_apply(rb, vj, om, 1, zj)) return rc;                    // z2' = om v + D P A1^-1 P^T r1
+            } else if (int rc = apply_Minv(vj, zj))
+                return rc;
+            if (coarse_fail >= 4) {
+                stop = true;
+                return FDAPDE_OK;
             }
-            hipLaunchKernelGGL(k_pmg_scale, gv, bv, 0, st, n2, r, 1.0 / beta, V);
-            std::fill(gg.begin(), gg.end(), 0.0);
-            gg[0] = beta;
-            int k = 0;   // columns of this cycle
-            bool cycle_done = false;
-            while (!cycle_done && k < mk && it < maxit) {
-                const int j = k;
-                double* zj = Z + (size_t)j * (size_t)n2;
-                double* w = V + (size_t)(j + 1) * (size_t)n2;
-                const double* vj = V + (size_t)j * (size_t)n2;
-                if (cycle) {
-                    KD(vj, tb);                                                                     // A z1, z1' = om v
-                    hipLaunchKernelGGL(k_pmg_lin, gv, bv, 0, st, n2, vj, om, tb, rb);               // r1 = v - om A D^-1 v
-                    if (int rc = coarse_and_apply(rb, vj, om, 1, zj)) return rc;                    // z2' = om v + D P A1^-1 P^T r1
-                } else if (int rc = apply_Minv(vj, zj))
-                    return rc;
-                if (coarse_fail >= 4) {
-                    broke = true;
-                    break;
-                }
-                if (cycle) {
-                    KD(zj, tb);
-                    hipLaunchKernelGGL(k_pmg_post, gv, bv, 0, st, n2, vj, tb, om, zj, rb);          // r2 = v - A z2, z3' = z2' + om r2
-                    KD(rb, tb);
-                    hipLaunchKernelGGL(k_pmg_wfin, gv, bv, 0, st, n2, vj, rb, tb, om, w);           // w = A z3 = (v - r2) + om A D^-1 r2
-                    fine_apps += 3;
-                } else {
-                    apply_K_dir(zj, w);
-                    ++fine_apps;
-                }
-                // Gram-Schmidt, twice: h = V^T w, w -= V h, then the same on what is left (its coefficients add to h)
-                double wnorm2 = 0;
-                for (int pass = 0; pass < 2; ++pass) {
-                    hipLaunchKernelGGL(k_pmg_mdot, dim3(gnp), bv, 0, st, n2, V, n2, j + 1, w, m.part.p);
-                    hipLaunchKernelGGL(k_pmg_mreduce, dim3((unsigned)(j + 2)), bv, 0, st, m.part.p, m.np, m.dots.p);
-                    hipLaunchKernelGGL(k_pmg_msub, dim3(gnp), bv, 0, st, n2, V, n2, j + 1, m.dots.p, w, m.part.p);
-                    hipLaunchKernelGGL(k_pmg_mreduce, dim3(1), bv, 0, st, m.part.p, m.np, m.dots.p + (j + 2));
-                    HIPCHK(c, hipMemcpyAsync(hj.data(), m.dots.p, sizeof(double) * (size_t)(j + 3), hipMemcpyDeviceToHost, st));
-                    HIPCHK(c, hipStreamSynchronize(st));
-                    for (int i = 0; i <= j; ++i) Hat(i, j) = pass == 0 ? hj[(size_t)i] : Hat(i, j) + hj[(size_t)i];
-                    wnorm2 = hj[(size_t)j + 2];
-                }
-                const double hn = std::sqrt(wnorm2);
-                if (!std::isfinite(hn)) {
-                    broke = true;
-                    break;
-                }
-                Hat(j + 1, j) = hn;
-                for (int i = 0; i < j; ++i) {
-                    const double a0 = Hat(i, j), a1 = Hat(i + 1, j);
-                    Hat(i, j) = cs[(size_t)i] * a0 + sn[(size_t)i] * a1, Hat(i + 1, j) = -sn[(size_t)i] * a0 + cs[(size_t)i] * a1;
-                }
-                const double d = std::hypot(Hat(j, j), Hat(j + 1, j));
-                if (!(d > 0.0)) {   // (a zero column: M^-1 v_j = 0 -- nothing this basis can do)
-                    broke = true;
-                    break;
-                }
-                cs[(size_t)j] = Hat(j, j) / d, sn[(size_t)j] = Hat(j + 1, j) / d;
-                Hat(j, j) = d, Hat(j + 1, j) = 0.0;
-                gg[(size_t)j + 1] = -sn[(size_t)j] * gg[(size_t)j], gg[(size_t)j] = cs[(size_t)j] * gg[(size_t)j];
-                ++k, ++it;
-                rr = gg[(size_t)k] * gg[(size_t)k];
-                if (rr <= rtol * rtol * bb || !(hn > 1e-300)) cycle_done = true;   // (hn = 0: the exact solution lies in this basis)
-                else hipLaunchKernelGGL(k_pmg_scale, gv, bv, 0, st, n2, w, 1.0 / hn, w);
+            if (cycle) {
+                KD(zj, tb);
+                hipLaunchKernelGGL(k_pmg_post, gv, bv, 0, st, n2, vj, tb, om, zj, rb);          // r2 = v - A z2, z3' = z2' + om r2
+                KD(rb, tb);
+                hipLaunchKernelGGL(k_pmg_wfin, gv, bv, 0, st, n2, vj, rb, tb, om, w);           // w = A z3 = (v - r2) + om A D^-1 r2
+                fine_apps += 3;
+            } else {
+                apply_K_dir(zj, w);
+                ++fine_apps;
             }
-            if (k > 0) {   // x += Z y, H y = g (upper triangular after the rotations)
-                for (int i = k - 1; i >= 0; --i) {
-                    double sacc = gg[(size_t)i];
-                    for (int q = i + 1; q < k; ++q) sacc -= Hat(i, q) * yy[(size_t)q];
-                    yy[(size_t)i] = sacc / Hat(i, i);
-                }
-                HIPCHK(c, hipMemcpyAsync(m.dots.p, yy.data(), sizeof(double) * (size_t)k, hipMemcpyHostToDevice, st));
-                hipLaunchKernelGGL(k_pmg_comb, gv, bv, 0, st, n2, Z, n2, k, m.dots.p, comb_dinv, x);
-                HIPCHK(c, hipStreamSynchronize(st));   // (yy is the host's)
-            }
-            if (broke) break;
-            // the residual of the new iterate, computed (it starts the next cycle, and the recurrence's word is not taken for convergence)
+            return FDAPDE_OK;
+        };
+        auto residual = [&](double& rr_out) -> int {
             apply_K(x, v);
             hipLaunchKernelGGL(k_pmg_residual, gv, bv, 0, st, n2, c->bnd.p, use_bnd, f_dev, g_dev, v, r);
             if (int rc = dots(r, r, nullptr, nullptr, nullptr, nullptr)) return rc;
-            rr = h[0];
-            if (!std::isfinite(rr)) {
-                broke = true;
-                break;
-            }
-            converged = rr <= rtol * rtol * bb;
-            if (!converged && k == 0) {
-                broke = true;
-                break;
-            }
-        }
+            rr_out = h[0];
+            return FDAPDE_OK;
+        };
+        if (int rc = fgmres_outer(c, fs, x, r, comb_dinv, rtol, maxit, bb, precond, residual, rr, it, converged, broke)) return rc;
     } else
     while (!converged && it < maxit) {
         if (int rc = dots(r0, r, nullptr, nullptr, nullptr, nullptr)) return rc;

@@ -330,6 +330,7 @@ int e_dofs_build(fdapde_ctx* c, int order, int64_t* n_dofs) {
     c->assembled[0] = c->assembled[1] = c->force_ready = c->solved = c->dirichlet_applied = false;
     c->op.clear(), c->coef_of_op = false, c->fq_i.clear(), c->fq_cols = 0, c->g_i.clear(), c->have_g = false;
     pmg_release(c);   // (the coarse level of the space that is being replaced)
+    amg_release(c);
     c->matrix_dirty = true;
     c->halo_ready = false, c->lin_ready = false, c->sp_built[0] = c->sp_built[1] = false, c->sp_cur = -1;
     release_rowdist(c);   // (keys / owners / layouts of the row-distributed form belong to the space that is being replaced)
@@ -475,6 +476,7 @@ int e_dofs_set_boundary(fdapde_ctx* c, const uint8_t* bnd) {
     HostSpace& hs = c->hs;
     if (hs.n_dofs == 0) return fail(c, FDAPDE_ENOTINIT, "call fdapde_dofs_build first");
     pmg_release(c);   // (the coarse level of the two-level solver carries the boundary mask it was built with)
+    amg_release(c);   // (... and so do the aggregation hierarchies)
     if (c->dev_built) {
         HIPCHK(c, hipSetDevice(c->device));
         if (int rc = ensure_host(c, kHostPerm)) return rc;

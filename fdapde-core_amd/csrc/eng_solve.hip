@@ -1061,6 +1061,7 @@ int e_solve(fdapde_ctx* c, const fdapde_options* opt, fdapde_info* info) {
     const double* A = c->vals[FDAPDE_MAT_STIFF].p;
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     if (opt && opt->method == FDAPDE_SOLVER_PMG) return e_solve_pmg(c, opt, info);   // the two-level solver of order-2 spaces (eng_pmg.hip), by name
+    if (opt && opt->method == FDAPDE_SOLVER_AMG) return e_solve_amg(c, opt, info);   // the aggregation multilevel solver (eng_amg.hip), by name only
     if (opt && opt->method == FDAPDE_SOLVER_DENSE) {
         // the direct solve asked for by name (what the reference's SparseLU does, fem_linear_elliptic_solver.h:38-47): the reference's own row-zeroed matrix
         // inverted on the device, one product; no Krylov stage in front, no fall-back behind -- a singular matrix is reported (success = false)
@@ -1288,6 +1289,50 @@ int e_solve_parabolic(fdapde_ctx* c, const fdapde_options* opt, int32_t n_times,
             return FDAPDE_ENOCONV;
         }
     }
+    // FDAPDE_SOLVER_AMG by name: the hierarchy of K built once for the call, every step warm-started from the previous column (eng_amg.hip)
+    if (opt && opt->method == FDAPDE_SOLVER_AMG) {
+        if (!amg_eligible(c)) return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_AMG takes one-GPU contexts");
+        const int am_maxit = (opt->maxit > 0) ? opt->maxit : 200;
+        if (int rc = amg_build(c, &c->amg, kmat.p, dirichlet ? 1 : 0, c->op_symmetric)) {
+            c->info = fdapde_info{};
+            c->info.method_used = FDAPDE_SOLVER_AMG;
+            if (info) *info = c->info;
+            return rc;
+        }
+        to_internal(initial_condition);
+        HIPCHK(c, hipMemcpyAsync(uprev.p, tmp.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        int total = 0, rc_am = FDAPDE_OK;
+        double worst_am = 0;
+        for (int32_t i = 0; i + 1 < n_times; ++i) {
+            launch_spmv(c, c->vals[FDAPDE_MAT_MASS].p, uprev.p, c->s.p, nullptr, nullptr, nullptr);   // M u_i
+            hipLaunchKernelGGL(k_parabolic_rhs, dim3(g1(n)), dim3(256), 0, st, n, c->s.p, inv_dt, c->force.p + (size_t)(i + 1) * n, rhs.p);
+            if (dirichlet) {
+                HIPCHK(c, hipMemcpyAsync(c->tmp_i.p, dirichlet + (size_t)(i + 1) * n, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
+                hipLaunchKernelGGL(k_gather_f64, dim3(g1(n)), dim3(256), 0, st, n, c->dof_i2e.p, c->tmp_i.p, gcol.p);
+            }
+            const int rc = amg_run(c, c->amg, kmat.p, rhs.p, gcol.p, dirichlet ? 1 : 0, uprev.p, rtol, am_maxit);
+            if (rc != FDAPDE_OK && rc != FDAPDE_ENOCONV) return rc;
+            if (rc == FDAPDE_ENOCONV) rc_am = rc;
+            total += c->info.iters, worst_am = std::max(worst_am, c->info.relres);
+            HIPCHK(c, hipMemcpyAsync(uprev.p, c->u.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
+            hipLaunchKernelGGL(k_scatter_f64, dim3(g1(n)), dim3(256), 0, st, n, c->dof_i2e.p, c->u.p, c->tmp_e.p);
+            HIPCHK(c, hipMemcpyAsync(solution + (size_t)(i + 1) * n, c->tmp_e.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
+            HIPCHK(c, hipStreamSynchronize(st));   // (tmp_e is reused by the next step)
+        }
+        std::memcpy(solution, initial_condition, sizeof(double) * (size_t)n);   // solution_.col(0) = initial condition (line 46)
+        HIPCHK(c, hipEventRecord(c->ev1, st));
+        HIPCHK(c, hipEventSynchronize(c->ev1));
+        float ms_a = 0;
+        HIPCHK(c, hipEventElapsedTime(&ms_a, c->ev0, c->ev1));
+        c->info.t_solve_ms = ms_a, c->info.iters = total, c->info.relres = worst_am, c->info.converged = rc_am == FDAPDE_OK ? 1 : 0;
+        c->info.method_used = FDAPDE_SOLVER_AMG, c->info.persistent = 0;
+        amg_forget(c);   // (K belongs to this call)
+        if (info) *info = c->info;
+        if (rc_am != FDAPDE_OK) c->err = "FDAPDE_SOLVER_AMG: a step did not converge";
+        kmat.release(), uprev.release(), rhs.release(), gcol.release();
+        return rc_am;
+    }
     // Large order-2 systems (or FDAPDE_SOLVER_PMG by name): every step through the two-level solver (eng_pmg.hip) -- the coarse operator is the P1 assembly of
     // the same terms + M1 / dt, built once for the call; a step starts from the previous column.  A first step it does not solve sends the open method to
     // the Jacobi-preconditioned loop below.
@@ -1476,6 +1521,7 @@ int e_lin_compute(fdapde_ctx* c, int32_t which, const double* values, int32_t sy
     c->scaled_owner = fdapde_ctx::kScaledLin;   // scale / sval now belong to the handle
     c->lin_ready = true, c->lin_sq_ready = false;
     c->lin_dense.ready = c->lin_dense.failed = false, c->lin_cols = 0, c->lin_krylov_ms = 0;   // (a dense inverse belongs to the matrix it was built from)
+    ++c->amg_lin_epoch;   // (... and so does FDAPDE_SOLVER_AMG's hierarchy)
     return FDAPDE_OK;
 }
 
@@ -1495,6 +1541,7 @@ int e_lin_solve(fdapde_ctx* c, const fdapde_options* opt, const double* b, int32
             return e_lin_solve(c, opt, b_copy.data(), n_rhs, x, info);
         }
     }
+    if (opt && opt->method == FDAPDE_SOLVER_AMG) return amg_lin_solve(c, opt, b, n_rhs, x, info);   // (eng_amg.hip; after the in-place copy above)
     hipStream_t st = c->stream;
     const double rtol = (opt && opt->rtol > 0) ? opt->rtol : 1e-10;
     const int maxit = (opt && opt->maxit > 0) ? opt->maxit : default_maxit(c, n);

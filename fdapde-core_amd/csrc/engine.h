@@ -7,6 +7,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <functional>
 
 #include "context.h"
 
@@ -142,6 +143,8 @@ int g_layout_kind(fdapde_ctx* root, int32_t with_dirichlet, int32_t* kind, int32
 bool dense_eligible(const fdapde_ctx* c);
 double dense_build_estimate_ms(int64_t n);
 int dense_build(fdapde_ctx* c, const double* A, int use_bnd, fdapde_ctx::Dense& D);
+// ... of any CSR matrix of n rows (device arrays; bnd may be null where use_bnd = 0)
+int dense_build_csr(fdapde_ctx* c, int64_t n, const int32_t* rowptr, const int32_t* colidx, const double* A, const uint8_t* bnd, int use_bnd, fdapde_ctx::Dense& D);
 int dense_apply(fdapde_ctx* c, fdapde_ctx::Dense& D, int nc, const double* b, double* x);
 int dense_solve_host(fdapde_ctx* c, fdapde_ctx::Dense& D, const double* b_host, int nc, double* x_host);
 int dense_direct(fdapde_ctx* c, const double* A, int use_bnd, const double* f_dev, const double* g_dev, bool* solved);
@@ -159,6 +162,29 @@ void pmg_release(fdapde_ctx* c);
 int e_solve_pmg(fdapde_ctx* c, const fdapde_options* opt, fdapde_info* info);
 int pmg_run(fdapde_ctx* c, const double* A, const double* f_dev, const double* g_dev, int use_bnd, const double* x0_dev, double extra_reaction, int64_t coarse_key,
             double rtol, int maxit);
+// the flexible GMRES outer loop (eng_pmg.hip) and its basis: V_0 .. V_mk, Z_0 .. Z_{mk-1} (n apart), part >= (mk + 2) * np, dots >= mk + 4 doubles
+struct FgmresSpace {
+    int64_t n;
+    int mk;
+    double *V, *Z, *part, *dots;
+    int np;
+};
+int fgmres_outer(fdapde_ctx* c, const FgmresSpace& s, double* x, double* r, const double* comb_dinv, double rtol, int maxit, double bb,
+                 const std::function<int(const double*, double*, double*, bool&)>& precond, const std::function<int(double&)>& residual, double& rr, int& it,
+                 bool& converged, bool& broke);
+void fixed_dots(hipStream_t st, int64_t n, int np, const double* a0, const double* b0, const double* a1, const double* b1, const double* a2, const double* b2,
+                double* part, double* out);
+// eng_amg.hip: FDAPDE_SOLVER_AMG
+bool amg_eligible(const fdapde_ctx* c);
+void amg_release(fdapde_ctx* c);
+void amg_forget(fdapde_ctx* c);   // the fdapde_solve hierarchy no longer matches (the stepper built its own on a K of the call)
+int amg_lin_solve(fdapde_ctx* c, const fdapde_options* opt, const double* b, int32_t n_rhs, double* x, fdapde_info* info);
+int e_solve_amg(fdapde_ctx* c, const fdapde_options* opt, fdapde_info* info);
+// one solve of K u = rhs against the hierarchy h (K: A with the Dirichlet rows as unit rows if use_bnd; rhs = f on the free rows, g on the Dirichlet rows),
+// from x0_dev or from g / 0; result in c->u, outcome in c->info
+int amg_run(fdapde_ctx* c, AmgHierarchy* h, const double* A, const double* f_dev, const double* g_dev, int use_bnd, const double* x0_dev, double rtol, int maxit);
+// (re)build hierarchy *slot for A on the context's pattern (use_bnd: the Dirichlet DOFs belong to no aggregate)
+int amg_build(fdapde_ctx* c, AmgHierarchy** slot, const double* A, int use_bnd, bool symmetric);
 int dense_step_loop(fdapde_ctx* c, fdapde_ctx::Dense& D, int32_t n_times, double inv_dt, const double* g_ext_dev, double* u0, double* sol_ext);
 void preload_dense();
 

@@ -426,16 +426,19 @@ template <typename D, typename F, int R> class PDE<D, DifferentialExpr, F, FEM_H
             if (!computed_) throw std::runtime_error("SparseSolver: compute() first");
             DMatrix<double> x(b.rows(), b.cols());
             fdapde_info info;
-            const int rc = fdapde_lin_solve(ctx_.get(), nullptr, b.data(), (int32_t)b.cols(), x.data(), &info);
+            const int rc = fdapde_lin_solve(ctx_.get(), &opt_, b.data(), (int32_t)b.cols(), x.data(), &info);
             if (rc != FDAPDE_OK) throw std::runtime_error(fdapde_last_error(ctx_.get()));
             return x;
         }
         explicit operator bool() const { return computed_; }
+        // the options of every later solve(): method (e.g. FDAPDE_SOLVER_AMG), rtol, maxit; left as they are, the library's defaults
+        fdapde_options& solver_options() { return opt_; }
        private:
         friend class PDE;
         explicit SparseSolver(fdapde::hip::context_handle ctx) : ctx_(std::move(ctx)) { }
         fdapde::hip::context_handle ctx_;   // keeps the PDE's context alive; acts on it (the handle's matrix is no part of the PDE's state)
         bool computed_ = false;
+        fdapde_options opt_ {FDAPDE_SOLVER_AUTO, 0, 0.0, FDAPDE_ASSEMBLY_ROWS, 0, 0};   // (zeros: the same as no options)
     };
     // The handle works on the context this PDE holds NOW.  Copy the PDE afterwards and then change the original (init / solve / a setter): the
     // original leaves with a clone and the handle stays with the context the copy kept (fdapde_hip.hpp, observer()'s lifetime rule) -- take the

@@ -91,7 +91,18 @@ enum { FDAPDE_SOLVER_AUTO = 0, FDAPDE_SOLVER_CG = 1, FDAPDE_SOLVER_BICGSTAB = 2,
                                 fdapde_solve_parabolic (the factor-once handle keeps the Jacobi-preconditioned stages); the open method takes it from
                                 `pmg_auto_rows` (300 k) DOFs on -- below `pmg_auto_first_rows` (1 M) only from a context's second open-method solve on (the coarse level's
                                 set-up is rent-or-buy); a parabolic run of more than four steps at once.  Knobs: pmg_outer 1 = BiCGStab around the additive form D^-1 + P A1^-1 P^T (the first
-                                form), pmg_smooth 0 = flexible GMRES around that additive form, pmg_blocked 0 = the fine operator through the CSR kernel. */ };
+                                form), pmg_smooth 0 = flexible GMRES around that additive form, pmg_blocked 0 = the fine operator through the CSR kernel. */,
+       FDAPDE_SOLVER_AMG = 8 /* any order, any dimension, symmetric or not, one-GPU contexts: flexible GMRES with an ALGEBRAIC multilevel preconditioner --
+                                a K-cycle (damped Jacobi, two flexible CG / GCR steps on the next level, damped Jacobi) over aggregates of at most four DOFs
+                                from double pairwise matching on the matrix's strong couplings, Galerkin coarse matrices P^T A P (piecewise-constant P, a fixed
+                                summation order: the same bits every run), the last level -- at most `amg_coarse_rows` (1 024) rows, or where coarsening
+                                stalls below 8 192 rows -- inverted once on the device.  The hierarchy is built from the matrix alone: fdapde_solve (kept while the operator and the Dirichlet variant
+                                stay), fdapde_solve_parabolic (once per call, on K = M / dt + A; a step starts from the previous column) and the factor-once
+                                handle (once per fdapde_lin_compute; columns one after the other).  Taken by name only: the open method never chooses it.
+                                info.iters counts outer iterations, info.relres is the true relative residual of what is handed out, info.persistent = 0.
+                                rtol 1e-10 and maxit 200 by default; non-convergence is FDAPDE_ENOCONV (success = false), as is a singular coarsest level
+                                (pure Neumann data); coarsening that stalls above the dense limit, a rank of a multi-GPU job and a multi-device context are
+                                FDAPDE_EUNSUPPORTED. */ };
 /* ROWS: row-owner sweep (default; no atomics, bitwise reproducible).  The others are element-wise scatter forms kept as measured
  * alternatives and cross-checks: ATOMIC / COLOURED = lane per (cell, row) with a slot search, fp64 atomics / one launch per colour;
  * PARTITIONED = one workgroup per cell partition, colours walked inside the workgroup, atomics only on rows shared between
@@ -412,7 +423,9 @@ int fdapde_partition_peers(fdapde_ctx *ctx, int32_t rank, int32_t *n_peers, int3
  *                 "pmg_inner_maxit" (their budget; 200), "pmg_restart" (vectors per cycle of the flexible GMRES, 2 .. 50), "pmg_outer" (1: BiCGStab around the
  *                 additive preconditioner, the round's first form), "pmg_smooth" (0: flexible GMRES around the additive preconditioner instead of the V(1,1)
  *                 cycle), "pmg_blocked" (0: the fine operator through the CSR kernel instead of the blocked-ELL SpMV), "pmg_setup_check" (1: the transfer tables
- *                 are also built by host loops and compared; an error if they differ) */
+ *                 are also built by host loops and compared; an error if they differ)
+ *   multilevel    "amg_coarse_rows" (FDAPDE_SOLVER_AMG coarsens until a level has at most that many rows, 1 .. 8 192; 1 024), "amg_setup_check" (1: the aggregates,
+ *                 coarse patterns and coarse values are also built by host loops and compared bit for bit; an error if they differ) */
 int fdapde_tune(fdapde_ctx *ctx, const char *key, int32_t value);
 /* the context's HIP stream (hipStream_t) so that callers can bracket work with their own events */
 void *fdapde_stream(fdapde_ctx *ctx);
