@@ -146,6 +146,9 @@ const char* fdapde_last_error(const fdapde_ctx* c) { return c ? c->err.c_str() :
 int fdapde_mesh_upload(fdapde_ctx* c, int M, int N, int64_t n_nodes, const double* nodes, int64_t n_cells,
                        const int32_t* cells, const uint8_t* bnd) {
     if (!c) return FDAPDE_EINVAL;
+    if (c->group && M == 2 && N == 3)
+        return fail(c, FDAPDE_EUNSUPPORTED, "fdapde_mesh_upload: a surface mesh (Triangulation<2,3>) takes a one-GPU context; the multi-device partitioner "
+                                            "and its ranks are built for planar and volume meshes");
     c->space_ready = c->dev_ready = c->colour_ready = c->fq_blk_ready = c->fq_bc_ready = c->stiff_stat_valid = false;
     c->assembled[0] = c->assembled[1] = c->force_ready = c->solved = c->dirichlet_applied = false;
     c->op.clear(), c->coef_of_op = false, c->fq_i.clear(), c->fq_cols = 0, c->g_i.clear(), c->have_g = false;

@@ -32,7 +32,7 @@ void dev_topology_release(DevTopology* t);
 // edge midpoint in ReferenceElement<M,2>::nodes), dof_bnd = [node markers | edge markers], dof_coords column-major n_dofs x N with
 // an edge DOF placed by the FIRST cell that visits it (J * reference node + x0, lagrangian_basis.h:159-183).  refnodes: nb x M
 // reference coordinates of the local DOFs (BasisTables::refnodes).  Outputs are hipMalloc'd; the caller frees them.
-int dev_build_p2_dofs(int M, int64_t n_nodes, int64_t n_cells, const double* d_nodes, const int32_t* d_cells, const uint8_t* d_node_bnd,
+int dev_build_p2_dofs(int M, int N, int64_t n_nodes, int64_t n_cells, const double* d_nodes, const int32_t* d_cells, const uint8_t* d_node_bnd,
                       const double* refnodes, void* stream, int32_t** d_dofs, uint8_t** d_dof_bnd, double** d_dof_coords, int64_t* n_edges,
                       std::string& err);
 

@@ -364,18 +364,18 @@ int dev_build_topology(int M, int64_t n_nodes, int64_t n_cells, const int32_t* d
     return rc;
 }
 
-int dev_build_p2_dofs(int M, int64_t n_nodes, int64_t n_cells, const double* d_nodes, const int32_t* d_cells, const uint8_t* d_node_bnd,
+int dev_build_p2_dofs(int M, int N, int64_t n_nodes, int64_t n_cells, const double* d_nodes, const int32_t* d_cells, const uint8_t* d_node_bnd,
                       const double* refnodes, void* stream, int32_t** d_dofs, uint8_t** d_dof_bnd, double** d_dof_coords, int64_t* n_edges,
                       std::string& err) {
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (M != 2 && M != 3) return FDAPDE_EUNSUPPORTED;
+    if ((M != 2 && M != 3) || (N != M && !(M == 2 && N == 3))) return FDAPDE_EUNSUPPORTED;
     DevTopology t;
     if (int rc = dev_build_topology(M, n_nodes, n_cells, d_cells, d_node_bnd, stream, &t, err)) return rc;
     struct Guard {
         DevTopology* t;
         ~Guard() { dev_topology_release(t); }
     } guard{&t};
-    const int nb = M == 2 ? 6 : 10, N = M;
+    const int nb = M == 2 ? 6 : 10;   // (N: coordinates of the edge midpoints, 3 on a surface)
     const int64_t ne = t.n_edges, nd = n_nodes + ne;
     if (nd > INT32_MAX) {
         err = "too many DOFs";

@@ -149,7 +149,8 @@ int check_terms(fdapde_ctx* c, int32_t n_terms, const fdapde_term* terms, std::v
     return FDAPDE_OK;
 }
 
-template <int M, int R>
+// N: the embedding dimension (M, or 3 for a surface mesh: launch_assembly sends surfaces to the row-owner sweep only)
+template <int M, int R, int N = M>
 int launch_assembly_t(fdapde_ctx* c, AsmArgs a, const DevOp& op, int assembly) {
     const HostSpace& hs = c->hs;
     constexpr int NB = (M == 2) ? (R == 1 ? 3 : 6) : (R == 1 ? 4 : 10);
@@ -163,11 +164,18 @@ int launch_assembly_t(fdapde_ctx* c, AsmArgs a, const DevOp& op, int assembly) {
         if (!op.needs_rows) opk = 3;
         if (op.n == 1 && op.t[0].kind == FDAPDE_LAPLACIAN) opk = 1;
         if (op.n == 1 && op.t[0].kind == FDAPDE_REACTION && !op.t[0].space_varying) opk = 2;
-        if (std::getenv("FDAPDE_ASM_GENERIC")) opk = 0;
+        // (the generic integrand -- a measurement knob -- on planar and volume meshes only: its surface instantiation would be one more kernel with a
+        //  scratch copy of the operator; GEN stands in for it where the code must name a kernel)
+        constexpr int GEN = N == M ? 0 : 4;
+        if (std::getenv("FDAPDE_ASM_GENERIC")) {
+            if (N == M) opk = 0;
+            else std::fprintf(stderr, "FDAPDE_ASM_GENERIC: ignored on a surface mesh (no generic-integrand instantiation for Triangulation<2,3>): "
+                                      "the specialised integrand OPK %d runs\n", opk);
+        }
         if (op.kt_sym) a.reftab = reinterpret_cast<const DevRefTensors*>(c->reftab_sym.p), a.ref_doubles = kRefSymDoubles;   // (the compact tensors)
         else a.reftab = c->reftab.p, a.ref_doubles = kRefDoubles;
         const size_t tab = sizeof(DevTables) + (opk == 3 || opk == 5 ? sizeof(double) * (size_t)a.ref_doubles : 0) +
-                           (size_t)hs.max_blk_nodes * (M == 2 ? 2 : 3) * sizeof(double);
+                           (size_t)hs.max_blk_nodes * (N == 2 ? 2 : 3) * sizeof(double);
         size_t acc = (size_t)hs.max_blk_nnz * sizeof(double);
         // operator + mass in one sweep (a.vals2): both accumulator ranges of every block must fit the LDS, else two sweeps as before
         // ... and the second range must not cost occupancy: measured (tools/asm_fuse_ab.py) 2-D P1 C2 0.073 -> 0.046 ms (40 KB per workgroup), but
@@ -207,9 +215,9 @@ int launch_assembly_t(fdapde_ctx* c, AsmArgs a, const DevOp& op, int assembly) {
                                      !want_mass2 ? "one matrix" : (c->asm_items_fuse && (opk == 3 || opk == 1) && lds_items + acc_all + 4 * 1024 <= (size_t)160 * 1024) ? "operator and mass in ONE sweep (second accumulator range)" : "mass as second sweep");
 #define ITEMS_GO(OPK_, M2_, TH_)                                                                                                          \
     do {                                                                                                                                  \
-        const void* fn = reinterpret_cast<const void*>(&k_assemble_items<M, R, OPK_, M2_, TH_>);                                          \
+        const void* fn = reinterpret_cast<const void*>(&k_assemble_items<M, R, OPK_, M2_, TH_, N>);                                          \
         if (lds_items > 64 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_items);             \
-        hipLaunchKernelGGL((k_assemble_items<M, R, OPK_, M2_, TH_>), dim3(grid_i), dim3(TH_), lds_items, c->stream, a, op);               \
+        hipLaunchKernelGGL((k_assemble_items<M, R, OPK_, M2_, TH_, N>), dim3(grid_i), dim3(TH_), lds_items, c->stream, a, op);               \
     } while (0)
                     const char* th_env = std::getenv("FDAPDE_ASM_ITEMS_THREADS");   // (measurements: 512 instead of 1024 threads per block)
                     // both matrices in ONE sweep where a second accumulator range still fits the CU's LDS next to the first (3-D P2: 2 x 65 KB + 23 KB of
@@ -221,9 +229,9 @@ int launch_assembly_t(fdapde_ctx* c, AsmArgs a, const DevOp& op, int assembly) {
                         (void)lds_one;
 #define ITEMS_GO2(OPK_)                                                                                                                   \
     do {                                                                                                                                  \
-        const void* fn = reinterpret_cast<const void*>(&k_assemble_items<M, R, OPK_, 1, 1024>);                                           \
+        const void* fn = reinterpret_cast<const void*>(&k_assemble_items<M, R, OPK_, 1, 1024, N>);                                           \
         (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_two);                                          \
-        hipLaunchKernelGGL((k_assemble_items<M, R, OPK_, 1, 1024>), dim3(grid_i), dim3(1024), lds_two, c->stream, a, op);                 \
+        hipLaunchKernelGGL((k_assemble_items<M, R, OPK_, 1, 1024, N>), dim3(grid_i), dim3(1024), lds_two, c->stream, a, op);                 \
     } while (0)
                         if (opk == 3) ITEMS_GO2(3);
                         else ITEMS_GO2(1);
@@ -269,44 +277,44 @@ int launch_assembly_t(fdapde_ctx* c, AsmArgs a, const DevOp& op, int assembly) {
                          fuse_mass ? "mass fused (two ranges)" : seq_mass ? "mass as second pass" : "operator only");
         if (fuse_mass) {
             if (lds > 64 * 1024) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_assemble_rows<M, R, 1, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_assemble_rows<M, R, 3, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_assemble_rows<M, R, 1, 1, N>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_assemble_rows<M, R, 3, 1, N>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             }
-            if (opk == 3) hipLaunchKernelGGL((k_assemble_rows<M, R, 3, 1>), dim3(grid), dim3(kAsmBlock), lds, c->stream, a, op);
-            else hipLaunchKernelGGL((k_assemble_rows<M, R, 1, 1>), dim3(grid), dim3(kAsmBlock), lds, c->stream, a, op);
+            if (opk == 3) hipLaunchKernelGGL((k_assemble_rows<M, R, 3, 1, N>), dim3(grid), dim3(kAsmBlock), lds, c->stream, a, op);
+            else hipLaunchKernelGGL((k_assemble_rows<M, R, 1, 1, N>), dim3(grid), dim3(kAsmBlock), lds, c->stream, a, op);
             HIPCHK(c, hipGetLastError());
             return FDAPDE_OK;
         }
         if (seq_mass) {
             if (lds > 64 * 1024) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_assemble_rows<M, R, 1, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_assemble_rows<M, R, 3, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_assemble_rows<M, R, 1, 2, N>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_assemble_rows<M, R, 3, 2, N>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             }
-            if (opk == 3) hipLaunchKernelGGL((k_assemble_rows<M, R, 3, 2>), dim3(grid), dim3(kAsmBlock), lds, c->stream, a, op);
-            else hipLaunchKernelGGL((k_assemble_rows<M, R, 1, 2>), dim3(grid), dim3(kAsmBlock), lds, c->stream, a, op);
+            if (opk == 3) hipLaunchKernelGGL((k_assemble_rows<M, R, 3, 2, N>), dim3(grid), dim3(kAsmBlock), lds, c->stream, a, op);
+            else hipLaunchKernelGGL((k_assemble_rows<M, R, 1, 2, N>), dim3(grid), dim3(kAsmBlock), lds, c->stream, a, op);
             HIPCHK(c, hipGetLastError());
             return FDAPDE_OK;
         }
         if (lds > 64 * 1024)
-            for (const void* fn : {reinterpret_cast<const void*>(&k_assemble_rows<M, R, 0>),
-                                   reinterpret_cast<const void*>(&k_assemble_rows<M, R, 1>),
-                                   reinterpret_cast<const void*>(&k_assemble_rows<M, R, 2>),
-                                   reinterpret_cast<const void*>(&k_assemble_rows<M, R, 3>),
-                                   reinterpret_cast<const void*>(&k_assemble_rows<M, R, 4>),
-                                   reinterpret_cast<const void*>(&k_assemble_rows<M, R, 5>)})
+            for (const void* fn : {reinterpret_cast<const void*>(&k_assemble_rows<M, R, GEN, 0, N>),
+                                   reinterpret_cast<const void*>(&k_assemble_rows<M, R, 1, 0, N>),
+                                   reinterpret_cast<const void*>(&k_assemble_rows<M, R, 2, 0, N>),
+                                   reinterpret_cast<const void*>(&k_assemble_rows<M, R, 3, 0, N>),
+                                   reinterpret_cast<const void*>(&k_assemble_rows<M, R, 4, 0, N>),
+                                   reinterpret_cast<const void*>(&k_assemble_rows<M, R, 5, 0, N>)})
                 (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (opk == 4)
-            hipLaunchKernelGGL((k_assemble_rows<M, R, 4>), dim3(grid), dim3(kAsmBlock), lds, c->stream, a, op);
+            hipLaunchKernelGGL((k_assemble_rows<M, R, 4, 0, N>), dim3(grid), dim3(kAsmBlock), lds, c->stream, a, op);
         else if (opk == 5)
-            hipLaunchKernelGGL((k_assemble_rows<M, R, 5>), dim3(grid), dim3(kAsmBlock), lds, c->stream, a, op);
+            hipLaunchKernelGGL((k_assemble_rows<M, R, 5, 0, N>), dim3(grid), dim3(kAsmBlock), lds, c->stream, a, op);
         else if (opk == 3)
-            hipLaunchKernelGGL((k_assemble_rows<M, R, 3>), dim3(grid), dim3(kAsmBlock), lds, c->stream, a, op);
+            hipLaunchKernelGGL((k_assemble_rows<M, R, 3, 0, N>), dim3(grid), dim3(kAsmBlock), lds, c->stream, a, op);
         else if (opk == 1)
-            hipLaunchKernelGGL((k_assemble_rows<M, R, 1>), dim3(grid), dim3(kAsmBlock), lds, c->stream, a, op);
+            hipLaunchKernelGGL((k_assemble_rows<M, R, 1, 0, N>), dim3(grid), dim3(kAsmBlock), lds, c->stream, a, op);
         else if (opk == 2)
-            hipLaunchKernelGGL((k_assemble_rows<M, R, 2>), dim3(grid), dim3(kAsmBlock), lds, c->stream, a, op);
+            hipLaunchKernelGGL((k_assemble_rows<M, R, 2, 0, N>), dim3(grid), dim3(kAsmBlock), lds, c->stream, a, op);
         else
-            hipLaunchKernelGGL((k_assemble_rows<M, R, 0>), dim3(grid), dim3(kAsmBlock), lds, c->stream, a, op);
+            hipLaunchKernelGGL((k_assemble_rows<M, R, GEN, 0, N>), dim3(grid), dim3(kAsmBlock), lds, c->stream, a, op);
     } else {
         if (a.vals) HIPCHK(c, hipMemsetAsync(a.vals, 0, sizeof(double) * (size_t)hs.nnz, c->stream));
         if (a.force) HIPCHK(c, hipMemsetAsync(a.force, 0, sizeof(double) * (size_t)hs.n_dofs, c->stream));
@@ -406,6 +414,12 @@ int mirror_reference_lower(fdapde_ctx* c, double* vals) {
 int launch_assembly(fdapde_ctx* c, const AsmArgs& a, const DevOp& op, int assembly) {
     const int M = c->hs.M, R = c->hs.order;
     if (assembly < 0 || assembly > 4) return fail(c, FDAPDE_EINVAL, "unknown assembly variant");
+    if (M == 2 && c->hs.N == 3) {   // a surface mesh (Triangulation<2,3>): the row-owner sweep (P1) and its visit-parallel form (P2) only
+        if (assembly != FDAPDE_ASSEMBLY_ROWS)
+            return fail(c, FDAPDE_EUNSUPPORTED, "surface meshes (Triangulation<2,3>) are assembled by the row-owner sweep (FDAPDE_ASSEMBLY_ROWS) only: "
+                                                "the atomic, coloured, partitioned and wave variants have no surface geometry");
+        return R == 1 ? launch_assembly_t<2, 1, 3>(c, a, op, assembly) : launch_assembly_t<2, 2, 3>(c, a, op, assembly);
+    }
     if (M == 2 && R == 1) return launch_assembly_t<2, 1>(c, a, op, assembly);
     if (M == 2 && R == 2) return launch_assembly_t<2, 2>(c, a, op, assembly);
     if (M == 3 && R == 1) return launch_assembly_t<3, 1>(c, a, op, assembly);
@@ -633,6 +647,9 @@ int e_eval_pointwise(fdapde_ctx* c, int64_t n_locs, const double* locs_colmajor,
     HIPCHK(c, hipSetDevice(c->device));
     const HostSpace& hs = c->hs;
     const int M = hs.M;
+    if (hs.N != M)
+        return fail(c, FDAPDE_EUNSUPPORTED, "fdapde_eval_pointwise on a surface mesh (Triangulation<2,3>): locating a point needs its projection onto the surface, "
+                                            "which is not built");
     hipStream_t st = c->stream;
     // uniform bin grid over the mesh, built on the device once per mesh (dev_setup.hip dev_build_bin_grid; it was a serial host loop over
     // the cells on every call: 80 % of a call with 10^6 locations on a 10^6-cell mesh)
@@ -679,7 +696,9 @@ int e_cell_integrals(fdapde_ctx* c, double* measure, double* psi_int) {
     HIPCHK(c, d_m.alloc((size_t)hs.n_cells));
     HIPCHK(c, d_p.alloc((size_t)hs.n_cells * hs.nb));
     AsmArgs a = asm_args(c);
-    if (hs.M == 2)
+    if (hs.M == 2 && hs.N == 3)
+        hipLaunchKernelGGL((k_cell_integrals<2, 3>), dim3(g1(hs.n_cells)), dim3(256), 0, c->stream, a, hs.nb, hs.nq, c->cell_i2e.p, d_m.p, d_p.p);
+    else if (hs.M == 2)
         hipLaunchKernelGGL(k_cell_integrals<2>, dim3(g1(hs.n_cells)), dim3(256), 0, c->stream, a, hs.nb, hs.nq, c->cell_i2e.p, d_m.p, d_p.p);
     else
         hipLaunchKernelGGL(k_cell_integrals<3>, dim3(g1(hs.n_cells)), dim3(256), 0, c->stream, a, hs.nb, hs.nq, c->cell_i2e.p, d_m.p, d_p.p);
@@ -701,7 +720,9 @@ int e_quadrature_nodes(fdapde_ctx* c, double* out) {
     DBuf<double> d;
     HIPCHK(c, d.alloc((size_t)rows * hs.N));
     AsmArgs a = asm_args(c);
-    if (hs.M == 2)
+    if (hs.M == 2 && hs.N == 3)
+        hipLaunchKernelGGL((k_quadrature_nodes<2, 3>), dim3(g1(rows)), dim3(256), 0, c->stream, a, c->cell_i2e.p, hs.nq, d.p);
+    else if (hs.M == 2)
         hipLaunchKernelGGL(k_quadrature_nodes<2>, dim3(g1(rows)), dim3(256), 0, c->stream, a, c->cell_i2e.p, hs.nq, d.p);
     else
         hipLaunchKernelGGL(k_quadrature_nodes<3>, dim3(g1(rows)), dim3(256), 0, c->stream, a, c->cell_i2e.p, hs.nq, d.p);

@@ -379,7 +379,7 @@ int e_dofs_build(fdapde_ctx* c, int order, int64_t* n_dofs) {
             uint8_t* db = nullptr;
             double* dc = nullptr;
             int64_t ne = 0;
-            rc = dev_build_p2_dofs(hs.M, hs.n_nodes, hs.n_cells, d_nodes.p, d_cells.p, d_nbnd.p, c->tb.refnodes, c->stream, &dd, &db, &dc, &ne, c->err);
+            rc = dev_build_p2_dofs(hs.M, hs.N, hs.n_nodes, hs.n_cells, d_nodes.p, d_cells.p, d_nbnd.p, c->tb.refnodes, c->stream, &dd, &db, &dc, &ne, c->err);
             if (rc) return rc;
             hs.n_edges = ne, hs.n_dofs = hs.n_nodes + ne;
             adopt(c->dofs_e, dd, (size_t)hs.n_cells * hs.nb), adopt(c->coords_e, dc, (size_t)hs.n_dofs * hs.N), adopt(d_bnd, db, (size_t)hs.n_dofs);

@@ -398,8 +398,10 @@ int enumerate_edges(HostSpace& hs, hvec<int32_t>& cell_edge /* n_cells x (3|6), 
 
 int host_set_mesh(HostSpace& hs, int M, int N, int64_t n_nodes, const double* nodes, int64_t n_cells,
                   const int32_t* cells, const uint8_t* bnd, std::string& err) {
-    if (!((M == 2 && N == 2) || (M == 3 && N == 3))) {
-        err = "only Triangulation<2,2> and Triangulation<3,3> are on the accelerated path";
+    // Triangulation<2,3>: triangles of a surface in R^3.  Topology, DOF numbering and every index structure below depend on the connectivity (M) only;
+    // coordinates (DOF coordinates, locality keys, barycentres) are N-vectors throughout
+    if (!((M == 2 && N == 2) || (M == 2 && N == 3) || (M == 3 && N == 3))) {
+        err = "only Triangulation<2,2>, Triangulation<2,3> (surfaces) and Triangulation<3,3> are on the accelerated path";
         return FDAPDE_EUNSUPPORTED;
     }
     if (n_nodes <= 0 || n_cells <= 0 || !nodes || !cells || !bnd) {

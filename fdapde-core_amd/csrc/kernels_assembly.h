@@ -131,16 +131,31 @@ template <int NB, int NBW> __device__ __forceinline__ void add_row_lds(double* a
     for (int j = 0; j < NB; ++j) lds_add(acc_row + ((sw[j >> 1] >> ((j & 1) * 16)) & 0xffffu), val[j]);
 }
 
-template <int M> struct Geo {
-    double invJ[M][M];   // J^{-1}
-    double measure;      // |det J| / M!
+// N: the embedding dimension.  N == M: a planar / volume cell; M == 2, N == 3: a triangle of a surface in R^3 (Triangulation<2,3>).
+template <int M, int N = M> struct Geo {
+    double invJ[M][N];   // J^{-1}; on a surface the pseudo-inverse (J^T J)^{-1} J^T (2 x 3)
+    double measure;      // |det J| / M!; on a surface |(x1 - x0) x (x2 - x0)| / 2
 };
 
 // Simplex::initialize (fdaPDE/geometry/simplex.h:184-195): J col j = x_{j+1} - x_0, invJ, measure = |det J| / M!
 // p0..p3: vertex coordinates (global memory or the workgroup's LDS copy)
-template <int M>
-__device__ __forceinline__ void geo_from_vertices(const double* p0, const double* p1, const double* p2, const double* p3, Geo<M>& g) {
-    if constexpr (M == 2) {
+// Surface cells (M = 2, N = 3, the branch embed_dim != local_dim there): J = [a, b] is 3 x 2, invJ = (J^T J)^{-1} J^T, measure = |a x b| / 2.
+// Every weak form then sees invJ exactly as on a planar cell -- gradients are 3-vectors, K is 3 x 3, b a 3-vector -- and the
+// contractions below pull the cell back to the local dimension once (Gp = invJ K invJ^T is 2 x 2, beta = invJ b a 2-vector).
+template <int M, int N = M>
+__device__ __forceinline__ void geo_from_vertices(const double* p0, const double* p1, const double* p2, const double* p3, Geo<M, N>& g) {
+    if constexpr (M == 2 && N == 3) {
+        const double a0 = p1[0] - p0[0], a1 = p1[1] - p0[1], a2 = p1[2] - p0[2];
+        const double b0 = p2[0] - p0[0], b1 = p2[1] - p0[1], b2 = p2[2] - p0[2];
+        const double gaa = a0 * a0 + a1 * a1 + a2 * a2, gab = a0 * b0 + a1 * b1 + a2 * b2, gbb = b0 * b0 + b1 * b1 + b2 * b2;
+        const double id = 1.0 / (gaa * gbb - gab * gab);   // (J^T J)^{-1} = [gbb, -gab; -gab, gaa] / det
+        const double i00 = gbb * id, i01 = -gab * id, i11 = gaa * id;
+        g.invJ[0][0] = i00 * a0 + i01 * b0, g.invJ[0][1] = i00 * a1 + i01 * b1, g.invJ[0][2] = i00 * a2 + i01 * b2;
+        g.invJ[1][0] = i01 * a0 + i11 * b0, g.invJ[1][1] = i01 * a1 + i11 * b1, g.invJ[1][2] = i01 * a2 + i11 * b2;
+        const double c0 = a1 * b2 - a2 * b1, c1 = a2 * b0 - a0 * b2, c2 = a0 * b1 - a1 * b0;
+        g.measure = 0.5 * sqrt(c0 * c0 + c1 * c1 + c2 * c2);
+        (void)p3;
+    } else if constexpr (M == 2) {
         const double j00 = p1[0] - p0[0], j01 = p2[0] - p0[0], j10 = p1[1] - p0[1], j11 = p2[1] - p0[1];
         const double det = j00 * j11 - j01 * j10;
         const double id = 1.0 / det;
@@ -164,8 +179,14 @@ __device__ __forceinline__ void geo_from_vertices(const double* p0, const double
         g.measure = fabs(det) * (1.0 / 6.0);
     }
 }
-template <int M> __device__ __forceinline__ void cell_geometry(const AsmArgs& a, int cell, Geo<M>& g) {
-    if constexpr (M == 2) {
+template <int M, int N = M> __device__ __forceinline__ void cell_geometry(const AsmArgs& a, int cell, Geo<M, N>& g) {
+    if constexpr (M == 2 && N == 3) {   // (the coordinate table of a 3-D embedding is padded to 4 doubles per node)
+        const int32_t* cv = a.cverts + (int64_t)cell * 3;
+        const double4 x0 = *reinterpret_cast<const double4*>(a.vcoords + (int64_t)cv[0] * 4);
+        const double4 x1 = *reinterpret_cast<const double4*>(a.vcoords + (int64_t)cv[1] * 4);
+        const double4 x2 = *reinterpret_cast<const double4*>(a.vcoords + (int64_t)cv[2] * 4);
+        geo_from_vertices<2, 3>(&x0.x, &x1.x, &x2.x, nullptr, g);
+    } else if constexpr (M == 2) {
         const int32_t* cv = a.cverts + (int64_t)cell * 3;
         const double2 x0 = *reinterpret_cast<const double2*>(a.vcoords + (int64_t)cv[0] * 2);
         const double2 x1 = *reinterpret_cast<const double2*>(a.vcoords + (int64_t)cv[1] * 2);
@@ -181,10 +202,10 @@ template <int M> __device__ __forceinline__ void cell_geometry(const AsmArgs& a,
     }
 }
 
-// physical gradient J^{-T} grad_ref: out[r] = sum_k invJ[k][r] * d[k]   (buff_invJ = invJ^T, fem_assembler.h:81)
-template <int M> __device__ __forceinline__ void phys_grad(const Geo<M>& g, const double* d, double* out) {
+// physical gradient J^{-T} grad_ref: out[r] = sum_k invJ[k][r] * d[k]   (buff_invJ = invJ^T, fem_assembler.h:81); N components
+template <int M, int N = M> __device__ __forceinline__ void phys_grad(const Geo<M, N>& g, const double* d, double* out) {
 #pragma unroll
-    for (int r = 0; r < M; ++r) {
+    for (int r = 0; r < N; ++r) {
         double v = 0;
 #pragma unroll
         for (int k = 0; k < M; ++k) v += g.invJ[k][r] * d[k];
@@ -266,8 +287,9 @@ __device__ __forceinline__ double sym_pair(double g_kl, double g_lk, double a_k,
 //      the constant leaves through the reference tensors as OPK 3, the varying ones per node without any tensor pull-back --
 //        A_ij = |e| ( [OPK 3 sum of the constant leaves]_ij + sum_q w_q ( psi_i (J^-1 b_q . dpsi_j) + c_q psi_i psi_j ) )
 //      (C5-size mesh, -Lap + c(x): 23 ms with OPK 4 -> see DESIGN.md 4.3)
-template <int M, int R, int OPK, typename Emit>
-__device__ __forceinline__ double element_row(const AsmArgs& a, const DevOp& op, const DevTables* tb, const Geo<M>& g, int cell,
+// N (embedding dimension, = M but on surfaces): coefficients and physical gradients have N components, reference gradients M.
+template <int M, int R, int OPK, int N = M, typename Emit>
+__device__ __forceinline__ double element_row(const AsmArgs& a, const DevOp& op, const DevTables* tb, const Geo<M, N>& g, int cell,
                                               int il, bool want_matrix, Emit&& emit, const DevRefTensors* rt = nullptr,
                                               int64_t fcell = -1 /* >= 0: a.fq holds load coefficients per visit ... */,
                                               double fcoef = 0.0 /* ... and this is the visit's, loaded ahead by the caller */,
@@ -305,15 +327,15 @@ __device__ __forceinline__ double element_row(const AsmArgs& a, const DevOp& op,
 #pragma unroll QU5
             for (int q = 0; q < NQ; ++q) {
                 const int64_t qrow = qrow0 + q;
-                double bq[M], ctq = 0.0;
+                double bq[N], ctq = 0.0;
 #pragma unroll
-                for (int e = 0; e < M; ++e) bq[e] = 0.0;
+                for (int e = 0; e < N; ++e) bq[e] = 0.0;
                 for (int t = 0; t < op.n; ++t) {
                     const DevTerm& T = op.t[t];
                     if (!T.space_varying) continue;
                     if (T.kind == FDAPDE_ADVECTION) {
 #pragma unroll
-                        for (int e = 0; e < M; ++e) bq[e] += T.coef * T.data[qrow * M + e];
+                        for (int e = 0; e < N; ++e) bq[e] += T.coef * T.data[qrow * N + e];
                     } else if (T.kind == FDAPDE_REACTION) {
                         ctq += T.coef * T.data[qrow];
                     }
@@ -323,7 +345,7 @@ __device__ __forceinline__ double element_row(const AsmArgs& a, const DevOp& op,
                 for (int k = 0; k < M; ++k) {
                     double bv = 0;
 #pragma unroll
-                    for (int r = 0; r < M; ++r) bv += g.invJ[k][r] * bq[r];
+                    for (int r = 0; r < N; ++r) bv += g.invJ[k][r] * bq[r];
                     betaq[k] = bv;
                 }
                 const double pi = tb->psi[il * NQ + q], wq = tb->qw[q];
@@ -344,24 +366,24 @@ __device__ __forceinline__ double element_row(const AsmArgs& a, const DevOp& op,
         }
 #pragma unroll
         for (int k = 0; k < M; ++k) {
-            double kr[M];   // row k of J^-1 Kt
+            double kr[N];   // row k of J^-1 Kt
 #pragma unroll
-            for (int c = 0; c < M; ++c) {
+            for (int c = 0; c < N; ++c) {
                 double v = 0;
 #pragma unroll
-                for (int r = 0; r < M; ++r) v += g.invJ[k][r] * op.kt[r * M + c];
+                for (int r = 0; r < N; ++r) v += g.invJ[k][r] * op.kt[r * N + c];
                 kr[c] = v;
             }
 #pragma unroll
             for (int l = 0; l < M; ++l) {
                 double v = 0;
 #pragma unroll
-                for (int c = 0; c < M; ++c) v += kr[c] * g.invJ[l][c];
+                for (int c = 0; c < N; ++c) v += kr[c] * g.invJ[l][c];
                 Gp[k][l] = v;
             }
             double bv = 0;
 #pragma unroll
-            for (int r = 0; r < M; ++r) bv += g.invJ[k][r] * op.bt[r];
+            for (int r = 0; r < N; ++r) bv += g.invJ[k][r] * op.bt[r];
             beta[k] = bv;
         }
         const bool ksym = op.kt_sym != 0;   // (sym implies ksym)
@@ -428,52 +450,52 @@ __device__ __forceinline__ double element_row(const AsmArgs& a, const DevOp& op,
 #pragma unroll QU
         for (int q = 0; q < NQ; ++q) {
             const int64_t qrow = qrow0 + q;
-            double Kt[M * M], bt[M], ctq = 0.0;
+            double Kt[N * N], bt[N], ctq = 0.0;
 #pragma unroll
-            for (int e = 0; e < M * M; ++e) Kt[e] = 0.0;
+            for (int e = 0; e < N * N; ++e) Kt[e] = 0.0;
 #pragma unroll
-            for (int e = 0; e < M; ++e) bt[e] = 0.0;
+            for (int e = 0; e < N; ++e) bt[e] = 0.0;
             for (int t = 0; t < op.n; ++t) {
                 const DevTerm& T = op.t[t];
                 if (T.kind == FDAPDE_LAPLACIAN) {
 #pragma unroll
-                    for (int r = 0; r < M; ++r) Kt[r * M + r] += T.coef;
+                    for (int r = 0; r < N; ++r) Kt[r * N + r] += T.coef;
                 } else if (T.kind == FDAPDE_DIFFUSION) {
 #pragma unroll
-                    for (int e = 0; e < M * M; ++e) Kt[e] += T.coef * (T.space_varying ? T.data[qrow * (M * M) + e] : T.cst[e]);
+                    for (int e = 0; e < N * N; ++e) Kt[e] += T.coef * (T.space_varying ? T.data[qrow * (N * N) + e] : T.cst[e]);
                 } else if (T.kind == FDAPDE_ADVECTION) {
 #pragma unroll
-                    for (int e = 0; e < M; ++e) bt[e] += T.coef * (T.space_varying ? T.data[qrow * M + e] : T.cst[e]);
+                    for (int e = 0; e < N; ++e) bt[e] += T.coef * (T.space_varying ? T.data[qrow * N + e] : T.cst[e]);
                 } else if (T.kind == FDAPDE_REACTION) {
                     ctq += T.coef * (T.space_varying ? T.data[qrow] : T.cst[0]);
                 }
             }
             bool ksym = true;
 #pragma unroll
-            for (int r = 0; r < M; ++r)
+            for (int r = 0; r < N; ++r)
 #pragma unroll
-                for (int c2 = 0; c2 < r; ++c2) ksym = ksym && Kt[r * M + c2] == Kt[c2 * M + r];
+                for (int c2 = 0; c2 < r; ++c2) ksym = ksym && Kt[r * N + c2] == Kt[c2 * N + r];
             double Gp[M][M], beta[M];
 #pragma unroll
             for (int k = 0; k < M; ++k) {
-                double kr[M];   // row k of J^-1 Kt
+                double kr[N];   // row k of J^-1 Kt
 #pragma unroll
-                for (int c2 = 0; c2 < M; ++c2) {
+                for (int c2 = 0; c2 < N; ++c2) {
                     double v = 0;
 #pragma unroll
-                    for (int r = 0; r < M; ++r) v += g.invJ[k][r] * Kt[r * M + c2];
+                    for (int r = 0; r < N; ++r) v += g.invJ[k][r] * Kt[r * N + c2];
                     kr[c2] = v;
                 }
 #pragma unroll
                 for (int l = 0; l < M; ++l) {
                     double v = 0;
 #pragma unroll
-                    for (int c2 = 0; c2 < M; ++c2) v += kr[c2] * g.invJ[l][c2];
+                    for (int c2 = 0; c2 < N; ++c2) v += kr[c2] * g.invJ[l][c2];
                     Gp[k][l] = v;
                 }
                 double bv = 0;
 #pragma unroll
-                for (int r = 0; r < M; ++r) bv += g.invJ[k][r] * bt[r];
+                for (int r = 0; r < N; ++r) bv += g.invJ[k][r] * bt[r];
                 beta[k] = bv;
             }
             if (ksym) {
@@ -508,17 +530,17 @@ __device__ __forceinline__ double element_row(const AsmArgs& a, const DevOp& op,
         for (int j = 0; j < NB; ++j) emit(j, accj[j] * g.measure);
         return fsum;
     } else if constexpr (OPK == 1 && R == 1) {
-        double G[M + 1][M];   // physical gradients of the M+1 barycentric coordinates
+        double G[M + 1][N];   // physical gradients of the M+1 barycentric coordinates
 #pragma unroll
-        for (int r = 0; r < M; ++r) {
+        for (int r = 0; r < N; ++r) {
             double s0 = 0;
 #pragma unroll
             for (int k = 0; k < M; ++k) G[k + 1][r] = g.invJ[k][r], s0 -= g.invJ[k][r];
             G[0][r] = s0;
         }
-        double gi[M];
+        double gi[N];
 #pragma unroll
-        for (int r = 0; r < M; ++r) {
+        for (int r = 0; r < N; ++r) {
             double v = G[0][r];
 #pragma unroll
             for (int k = 1; k <= M; ++k) v = il == k ? G[k][r] : v;
@@ -529,33 +551,33 @@ __device__ __forceinline__ double element_row(const AsmArgs& a, const DevOp& op,
         for (int j = 0; j < NB; ++j) {
             double d = 0;
 #pragma unroll
-            for (int r = 0; r < M; ++r) d += gi[r] * G[j][r];
+            for (int r = 0; r < N; ++r) d += gi[r] * G[j][r];
             emit(j, cm * (-d));
         }
         return fsum;
     } else {
         // gradients of the owned test function at every quadrature node (P1: constant over the cell)
         constexpr int NGQ = R == 1 ? 1 : NQ;
-        double gi[NGQ][M];
+        double gi[NGQ][N];
 #pragma unroll
-        for (int q = 0; q < NGQ; ++q) phys_grad<M>(g, &tb->dpsi[(il * NQ + q) * 3], gi[q]);
+        for (int q = 0; q < NGQ; ++q) phys_grad<M, N>(g, &tb->dpsi[(il * NQ + q) * 3], gi[q]);
 #pragma unroll
         for (int j = 0; j < NB; ++j) {
-            double gj[NGQ][M];
+            double gj[NGQ][N];
 #pragma unroll
-            for (int q = 0; q < NGQ; ++q) phys_grad<M>(g, &tb->dpsi[(j * NQ + q) * 3], gj[q]);
+            for (int q = 0; q < NGQ; ++q) phys_grad<M, N>(g, &tb->dpsi[(j * NQ + q) * 3], gj[q]);
             double value = 0;
 #pragma unroll
             for (int q = 0; q < NQ; ++q) {
                 if constexpr (OPK == 1) {
                     double d = 0;
 #pragma unroll
-                    for (int r = 0; r < M; ++r) d += gi[q][r] * gj[q][r];
+                    for (int r = 0; r < N; ++r) d += gi[q][r] * gj[q][r];
                     value += (op.t[0].coef * (-d)) * tb->qw[q];
                 } else {
                     const double pi = op.needs_psi ? tb->psi[il * NQ + q] : 0.0;
                     const double pj = op.needs_psi ? tb->psi[j * NQ + q] : 0.0;
-                    value += weak_form<M>(op, qrow0 + q, pi, pj, gi[R == 1 ? 0 : q], gj[R == 1 ? 0 : q]) * tb->qw[q];
+                    value += weak_form<N>(op, qrow0 + q, pi, pj, gi[R == 1 ? 0 : q], gj[R == 1 ? 0 : q]) * tb->qw[q];
                 }
             }
             emit(j, value * g.measure);
@@ -586,11 +608,12 @@ __device__ __forceinline__ const DevTables* stage_tables(const DevTables* gsrc, 
 // MASS2 == 2: the mass rows in a SECOND pass over the block's visits inside the same launch, through the same accumulator range (no extra
 // LDS, hence no occupancy lost): the block's index streams, vertex slots and staged coordinates are re-read from L2 / LDS right after the
 // first pass instead of from HBM by a launch of its own.
-template <int M, int R, int OPK, int MASS2 = 0>
+// N: embedding dimension (3 for the triangles of a surface, M otherwise): it sets the staged coordinates and the cell geometry only.
+template <int M, int R, int OPK, int MASS2 = 0, int N = M>
 static __global__ __launch_bounds__(kAsmBlock) void k_assemble_rows(AsmArgs a, DevOp op) {
     constexpr int NB = (M == 2) ? (R == 1 ? 3 : 6) : (R == 1 ? 4 : 10);
     constexpr int NBW = (NB * 2 + 3) / 4;
-    constexpr int NP = M == 2 ? 2 : 3;   // doubles per staged vertex in LDS (unpadded: C3 blocks then fit three to a CU, not two)
+    constexpr int NP = N == 2 ? 2 : 3;   // doubles per staged vertex in LDS (unpadded: C3 blocks then fit three to a CU, not two)
     extern __shared__ double lds[];
     // XCD-aware block order: workgroups are dealt round-robin to the 8 XCDs (own L2 each), so workgroup b serves block
     // (b % 8) * band + b / 8 -- an XCD walks a contiguous range of blocks, and what neighbouring blocks share (vertex coordinates
@@ -629,7 +652,7 @@ static __global__ __launch_bounds__(kAsmBlock) void k_assemble_rows(AsmArgs a, D
     const int64_t bn0 = a.bn_off[blk], nbn = a.bn_off[blk + 1] - bn0;
     for (int i = threadIdx.x; i < nbn; i += kAsmBlock) {
         const int64_t node = a.bn_node[bn0 + i];
-        if constexpr (M == 2) {
+        if constexpr (N == 2) {
             *reinterpret_cast<double2*>(xyz + i * 2) = *reinterpret_cast<const double2*>(a.vcoords + node * 2);
         } else {
             const double4 v = *reinterpret_cast<const double4*>(a.vcoords + node * 4);   // global copy stays padded to 32 B
@@ -687,15 +710,15 @@ static __global__ __launch_bounds__(kAsmBlock) void k_assemble_rows(AsmArgs a, D
             load_sw(v + 1, sw_n);
             if (code < 0) continue;
             const int64_t bc = bc0 + (code >> 4);
-            Geo<M> g;
-            geo_from_vertices<M>(xyz + lv.x * NP, xyz + lv.y * NP, xyz + lv.z * NP, xyz + lv.w * NP, g);
+            Geo<M, N> g;
+            geo_from_vertices<M, N>(xyz + lv.x * NP, xyz + lv.y * NP, xyz + lv.z * NP, xyz + lv.w * NP, g);
             // the global cell id is needed by varying coefficients and by forcing samples kept in cell order only
             const int cell = ((a.fq != nullptr && a.fq_block == 0) || op.needs_rows) ? a.bc_cell[bc] : 0;
             if constexpr (R == 2) {   // the NB values of the visit's row first, then ONE read-modify-write round trip for all of them (add_row_lds)
                 double val[NB];
 #pragma unroll
                 for (int j = 0; j < NB; ++j) val[j] = 0.0;
-                fsum += rounded<R>(element_row<M, R, OPK>(a, op, tb, g, cell, code & 15, want_matrix, [&](int j, double value) { val[j] = rounded<R>(value); },
+                fsum += rounded<R>(element_row<M, R, OPK, N>(a, op, tb, g, cell, code & 15, want_matrix, [&](int j, double value) { val[j] = rounded<R>(value); },
                                                           rt, fblk ? bc : (int64_t)-1, fc, fbc ? bc : (int64_t)-1));
                 if (want_matrix) {
                     if (in_lds) {
@@ -706,7 +729,7 @@ static __global__ __launch_bounds__(kAsmBlock) void k_assemble_rows(AsmArgs a, D
                     }
                 }
             } else {
-                fsum += rounded<R>(element_row<M, R, OPK>(a, op, tb, g, cell, code & 15, want_matrix, [&](int j, double value) {
+                fsum += rounded<R>(element_row<M, R, OPK, N>(a, op, tb, g, cell, code & 15, want_matrix, [&](int j, double value) {
                     const uint32_t slot = (sw[j >> 1] >> ((j & 1) * 16)) & 0xffffu;
                     if (in_lds)
                         lds_add(&acc[my0 - base + (int32_t)slot], value);
@@ -771,8 +794,8 @@ static __global__ __launch_bounds__(kAsmBlock) void k_assemble_rows(AsmArgs a, D
                 lv_n = load_lv(code_n);
                 load_sw(v + 1, sw_n);
                 if (code < 0) continue;
-                Geo<M> g;
-                geo_from_vertices<M>(xyz + lv.x * NP, xyz + lv.y * NP, xyz + lv.z * NP, xyz + lv.w * NP, g);
+                Geo<M, N> g;
+                geo_from_vertices<M, N>(xyz + lv.x * NP, xyz + lv.y * NP, xyz + lv.z * NP, xyz + lv.w * NP, g);
                 const double cm = 1.0 * 1.0 * g.measure;   // (OPK 2's own formula with coefficient 1)
                 const int il = code & 15;
                 if constexpr (R == 2) {
@@ -819,11 +842,11 @@ static __global__ __launch_bounds__(kAsmBlock) void k_assemble_rows(AsmArgs a, D
 // second sweep over the items through the same accumulators, as in k_assemble_rows.
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int kItemsMaxVisits = 64;   // visit lists longer than this keep the row-walking kernel (the host checks)
-template <int M, int R, int OPK, int MASS2, int THREADS>
+template <int M, int R, int OPK, int MASS2, int THREADS, int N = M>
 static __global__ __launch_bounds__(THREADS) void k_assemble_items(AsmArgs a, DevOp op) {
     constexpr int NB = (M == 2) ? (R == 1 ? 3 : 6) : (R == 1 ? 4 : 10);
     constexpr int NBW = (NB * 2 + 3) / 4;
-    constexpr int NP = M == 2 ? 2 : 3;
+    constexpr int NP = N == 2 ? 2 : 3;
     constexpr int NW = THREADS / 64, RW = kAsmBlock / NW;   // wavefronts; rows (lane positions) a wavefront owns: w, w + NW, w + 2 NW, ...
     static_assert(RW <= 64 && RW * NW == kAsmBlock, "a wavefront owns at most 64 rows");
     extern __shared__ double lds[];
@@ -859,7 +882,7 @@ static __global__ __launch_bounds__(THREADS) void k_assemble_items(AsmArgs a, De
     const int64_t bn0 = a.bn_off[blk], nbn = a.bn_off[blk + 1] - bn0;
     for (int i = tid; i < nbn; i += THREADS) {
         const int64_t node = a.bn_node[bn0 + i];
-        if constexpr (M == 2) {
+        if constexpr (N == 2) {
             *reinterpret_cast<double2*>(xyz + i * 2) = *reinterpret_cast<const double2*>(a.vcoords + node * 2);
         } else {
             const double4 v = *reinterpret_cast<const double4*>(a.vcoords + node * 4);
@@ -929,8 +952,8 @@ static __global__ __launch_bounds__(THREADS) void k_assemble_items(AsmArgs a, De
                 const int32_t bcl = code >> 4;
                 const uint2 lw = lvs[bcl];
                 const unsigned l0 = lw.x & 0xffffu, l1 = lw.x >> 16, l2 = lw.y & 0xffffu, l3 = lw.y >> 16;
-                Geo<M> g;
-                geo_from_vertices<M>(xyz + l0 * NP, xyz + l1 * NP, xyz + l2 * NP, xyz + l3 * NP, g);
+                Geo<M, N> g;
+                geo_from_vertices<M, N>(xyz + l0 * NP, xyz + l1 * NP, xyz + l2 * NP, xyz + l3 * NP, g);
                 if constexpr (MASS) {
                     const double cm = 1.0 * 1.0 * g.measure;   // (OPK 2's own formula with coefficient 1)
                     const int il = code & 15;
@@ -940,7 +963,7 @@ static __global__ __launch_bounds__(THREADS) void k_assemble_items(AsmArgs a, De
                     const int64_t bc = bc0 + bcl;
                     const int cell = ((a.fq != nullptr && a.fq_block == 0) || op.needs_rows) ? a.bc_cell[bc] : 0;
                     const double fc = fblk ? a.fq[at] : 0.0;
-                    fval = rounded<R>(element_row<M, R, OPK>(a, op, tb, g, cell, code & 15, want_matrix, [&](int j, double value) { val[j] = rounded<R>(value); }, rt,
+                    fval = rounded<R>(element_row<M, R, OPK, N>(a, op, tb, g, cell, code & 15, want_matrix, [&](int j, double value) { val[j] = rounded<R>(value); }, rt,
                                                              fblk ? bc : (int64_t)-1, fc, fbc ? bc : (int64_t)-1));
                     if constexpr (MASS2 == 1) {   // the mass row from the same geometry: what the second sweep would compute for this item, bit for bit
                         const double cm = 1.0 * 1.0 * g.measure;
@@ -1202,19 +1225,19 @@ static __global__ __launch_bounds__(256) void k_assemble_wave(AsmArgs a, DevOp o
     }
 }
 
-// Integrator::quadrature_nodes (integrator.h:109-121): out row nq*cell_ext + q = J p_q + x0, column-major rows x N
-template <int M>
+// Integrator::quadrature_nodes (integrator.h:109-121): out row nq*cell_ext + q = J p_q + x0, column-major rows x N (on a surface: points of R^3)
+template <int M, int N = M>
 static __global__ void k_quadrature_nodes(AsmArgs a, const int32_t* cell_i2e, int nq, double* out) {
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= a.n_cells * nq) return;
     const int64_t ci = idx / nq;
     const int q = (int)(idx - ci * nq);
-    constexpr int NP = M == 2 ? 2 : 4;
+    constexpr int NP = N == 2 ? 2 : 4;
     const int32_t* cv = a.cverts + ci * (M + 1);
     const double* x0 = a.vcoords + (int64_t)cv[0] * NP;
     const int64_t rows = a.n_cells * nq;
     const int64_t orow = (int64_t)cell_i2e[ci] * nq + q;
-    for (int d = 0; d < M; ++d) {
+    for (int d = 0; d < N; ++d) {
         double v = 0;
         for (int k = 0; k < M; ++k) v += (a.vcoords[(int64_t)cv[k + 1] * NP + d] - x0[d]) * a.tables->qn[q * M + k];
         out[(int64_t)d * rows + orow] = v + x0[d];
@@ -1303,12 +1326,12 @@ static __global__ void k_eval_pointwise(AsmArgs a, int64_t n_locs, const double*
 // per cell (reference numbering): measure and the integrals of the local basis functions,
 //   int_e psi_h = measure * sum_q w_q psi_h(p_q)   (Integrator::integrate_cell, utils/integration/integrator.h:47-63)
 // -- the ingredients of areal_evaluation::eval (basis/lagrangian_basis.h:238-283)
-template <int M>
+template <int M, int N = M>
 static __global__ void k_cell_integrals(AsmArgs a, int nb, int nq, const int32_t* cell_i2e, double* measure, double* psi_int) {
     const int64_t ci = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (ci >= a.n_cells) return;
-    Geo<M> g;
-    cell_geometry<M>(a, (int)ci, g);
+    Geo<M, N> g;
+    cell_geometry<M, N>(a, (int)ci, g);
     const int64_t ce = cell_i2e[ci];
     measure[ce] = g.measure;
     for (int h = 0; h < nb; ++h) {

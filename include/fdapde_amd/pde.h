@@ -5,7 +5,7 @@
 //
 //   reference (fdaPDE/...)                                           here (namespace fdapde::amd)
 //   ---------------------------------------------------------------  -------------------------------------------------
-//   Triangulation<M,N>(nodes, cells, boundary)  geometry/triangulation.h:49   Triangulation<M,N>
+//   Triangulation<M,N>(nodes, cells, boundary)  geometry/triangulation.h:49   Triangulation<M,N>: (2,2), (3,3), and (2,3) surfaces
 //   laplacian<FEM>() diffusion<FEM>(K) advection<FEM>(b) reaction<FEM>(c) dt<FEM>()
 //       pde/differential_operators.h:27-52, finite_elements/operators/*.h       same names, tag FEM_HIP
 //   operator algebra  -L, L1 + L2, L1 - L2, c * L  pde/differential_expressions.h:49,95-118   same
@@ -108,7 +108,8 @@ template <int M, int N> class Triangulation {
     // nodes: n_nodes x N; cells: n_cells x (M+1), 0-based node ids; boundary: n_nodes x 1 (0/1)
     Triangulation(const DMatrix<double>& nodes, const DMatrix<int>& cells, const DMatrix<int>& boundary) :
         nodes_(nodes), cells_(cells), boundary_(boundary) {
-        static_assert((M == 2 && N == 2) || (M == 3 && N == 3), "only Triangulation<2,2> and <3,3> are on the accelerated path");
+        static_assert((M == 2 && N == 2) || (M == 2 && N == 3) || (M == 3 && N == 3),
+                      "only Triangulation<2,2>, Triangulation<2,3> (surfaces in R^3) and Triangulation<3,3> are on the accelerated path");
         if (nodes.cols() != N || cells.cols() != M + 1 || boundary.rows() != nodes.rows())
             throw std::runtime_error("Triangulation: inconsistent matrix shapes");
     }
@@ -176,6 +177,11 @@ template <int M, int N> class Triangulation {
     DMatrix<int> cells_, boundary_;
     mutable std::shared_ptr<const Topology> topo_;   // lazily built, like the reference's location policy (triangulation.h:267)
 };
+
+// ---- fixed-size coefficients (reference: SVector<N> / SMatrix<N>, utils/symbols.h): a vector of R^N, an N x N matrix stored row-major -----
+// (advection<FEM_HIP>(SVector<3>{...}) and diffusion<FEM_HIP>(SMatrix<3>{...}) on a surface: b in R^3, K 3 x 3, as the reference's weak forms take them)
+template <int N> using SVector = std::array<double, (size_t)N>;
+template <int N> using SMatrix = std::array<double, (size_t)(N * N)>;
 
 // ---- forcing as a callable (reference: ScalarField<N, F>, fields/scalar_field.h) -----------------------------------------
 template <int N> struct ScalarField {

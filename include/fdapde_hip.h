@@ -184,6 +184,13 @@ const char *fdapde_last_error(const fdapde_ctx *ctx);
 const char *fdapde_status_string(int status);
 
 /* ---- domain: Triangulation<M,N>(nodes, cells, boundary)  (fdaPDE/geometry/triangulation.h:49-60,143,319) ------- */
+/* (M, N) = (2, 2) triangles, (3, 3) tetrahedra, or (2, 3): a triangulated SURFACE in R^3 (cortical surfaces, domes, shells).  On a surface the
+ * per-cell geometry is the reference's manifold branch (geometry/simplex.h:184-195): J = [x1 - x0, x2 - x0] (3 x 2), invJ = (J^T J)^{-1} J^T
+ * (2 x 3), |e| = |(x1 - x0) x (x2 - x0)| / 2, and the weak forms use invJ as on planar cells (operators/laplacian.h:43, diffusion.h:54,
+ * advection.h:55): gradients are 3-vectors, a diffusion tensor is 3 x 3 (9 values per row of a field), an advection vector has 3 components.
+ * Surfaces take orders 1 and 2 on a single-device context, the default assembly (FDAPDE_ASSEMBLY_ROWS) and every solver.  FDAPDE_EUNSUPPORTED:
+ * fdapde_eval_pointwise (point location would need a projection onto the surface), the assembly variants 1-4, fdapde_partition_build, and
+ * a surface in a multi-device context (fdapde_ctx_create_multi).  Every other (M, N) returns FDAPDE_EUNSUPPORTED. */
 int fdapde_mesh_upload(fdapde_ctx *ctx, int M, int N, int64_t n_nodes, const double *nodes_colmajor, int64_t n_cells,
                        const int32_t *cells_rowmajor, const uint8_t *boundary_nodes);
 
