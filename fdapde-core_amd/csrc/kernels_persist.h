@@ -39,6 +39,8 @@
 #ifndef FDAPDE_SYM_U
 #define FDAPDE_SYM_U 1
 #endif
+//   FDAPDE_STAMP_EXPORT  (diagnostic builds, tools/c3_export_build.sh) stats[2] / stats[3] carry the time from the iteration's start to the export
+//                        stores issued / to the first entry step of phase 0 multiplied (thread 0) instead of the all-gather and update phases
 
 namespace fdapde_hip {
 
@@ -324,7 +326,10 @@ static __global__ __launch_bounds__(kPersistT) void k_cg_persist(PersistArgs a) 
         }
     }
     const int nsl = a.nsl;
-    const int H = a.imp_off[g + 1] - a.imp_off[g], E = a.exp_off[g + 1] - a.exp_off[g];
+    const int H = a.imp_off[g + 1] - a.imp_off[g], exp0 = a.exp_off[g], E = a.exp_off[g + 1] - exp0;
+    // (the board section of the exports, in registers: read through a.exp_off behind every export store -- the stores' asm clobbers memory --
+    //  it cost each store a global load, and its vmcnt wait, the acknowledgement of the store before: the stores went out one round trip apart)
+    unsigned long long* const exp_board = a.pboard + 2 * (size_t)exp0;
     double* p_tab = lds;                                                                  // [S + imp_cap]
     long long* y_tab = reinterpret_cast<long long*>(p_tab + (S + a.imp_cap));             // [S] transposed sums, fixed point (SYM)
     double2* ev = reinterpret_cast<double2*>(y_tab + (SYM ? S : 0));                      // [lds_cap / 2] entry pairs (resident form)
@@ -343,14 +348,16 @@ static __global__ __launch_bounds__(kPersistT) void k_cg_persist(PersistArgs a) 
     // ---- stage the workgroup's tables (and, resident form, its block of the matrix)
     const int32_t* impl = PLDS ? a.imp_pos + a.imp_off[g] : impl_l;
     const uint16_t* expl = PLDS ? a.exp_slot + a.exp_off[g] : expl_l;
+    bool expl_in_lds = !PLDS;   // (then read through an LDS pointer: a generic one makes them flat loads, waited for with vmcnt too)
     if constexpr (SYM && STREAM && !DIST) {
         // the export list behind the accumulator table where the host found room (C3: 5.4 KB of the 6 KB the workgroup had left): the global re-read
         // of the codes put a round trip in front of the export stores of every iteration, and those sit in front of the matrix stream (vmcnt is in
         // order) -- a fit of the operator-phase stamps priced an export at 3.8 stored entries
         if (a.exp_lds) {
             uint16_t* expl_s = reinterpret_cast<uint16_t*>(y_tab + S);
-            for (int i = tid; i < E; i += T) expl_s[i] = a.exp_slot[a.exp_off[g] + i];
+            for (int i = tid; i < E; i += T) expl_s[i] = a.exp_slot[exp0 + i];
             expl = expl_s;   // (visible to all threads after the barrier that follows the staging of the tables)
+            expl_in_lds = true;
         }
     }
     if constexpr (!PLDS) {
@@ -463,24 +470,37 @@ static __global__ __launch_bounds__(kPersistT) void k_cg_persist(PersistArgs a) 
 #pragma unroll
             for (int j = 0; j < R; ++j) psj[j] = P(j) * tscale;
         }
-        for (int i0 = tid; i0 < E; i0 += 4 * T) {   // four per thread at a time: slot codes, then table reads, then the stores
-            unsigned code[4];
-            double pe[4];
+        [[maybe_unused]] long long c_exp = 0, c_first = 0;   // (FDAPDE_STAMP_EXPORT builds: export stores issued / first entry step returned)
+        {
+            auto publish = [&](auto codes) {
+                for (int i0 = tid; i0 < E; i0 += 4 * T) {   // four per thread at a time: slot codes, then table reads, then the stores
+                    unsigned code[4];
+                    double pe[4];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) code[k] = expl[min(i0 + k * T, E - 1)];
+                    for (int k = 0; k < 4; ++k) code[k] = codes[min(i0 + k * T, E - 1)];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) pe[k] = p_tab[code[k]];
+                    for (int k = 0; k < 4; ++k) pe[k] = p_tab[code[k]];
 #pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (i0 + k * T < E) publish_f64_x4(a.pboard + 2 * (size_t)(a.exp_off[g] + i0 + k * T), epoch, pe[k]);
-        }
-        if constexpr (DIST) {   // entries other ranks import: pushed into their boards
-            const int re0 = a.rexp_off[g], RE = a.rexp_off[g + 1] - re0;
-            for (int i = tid; i < RE; i += T) {
-                const unsigned slot = a.rexp_slot[re0 + i];
-                publish_f64_x4_sys(a.peer_pboard[a.rexp_peer[re0 + i]] + 2 * (size_t)a.rexp_pos[re0 + i], epoch, p_tab[slot]);
+                    for (int k = 0; k < 4; ++k)
+                        if (i0 + k * T < E) publish_f64_x4(exp_board + 2 * (size_t)(i0 + k * T), epoch, pe[k]);
+                }
+            };
+            if (expl_in_lds) publish((const __attribute__((address_space(3))) uint16_t*)expl);
+            else publish(expl);
+            if constexpr (DIST) {   // entries other ranks import: pushed into their boards
+                const int re0 = a.rexp_off[g], RE = a.rexp_off[g + 1] - re0;
+                for (int i = tid; i < RE; i += T) {
+                    const unsigned slot = a.rexp_slot[re0 + i];
+                    publish_f64_x4_sys(a.peer_pboard[a.rexp_peer[re0 + i]] + 2 * (size_t)a.rexp_pos[re0 + i], epoch, p_tab[slot]);
+                }
             }
+#ifdef FDAPDE_STAMP_EXPORT
+            if (stamper) c_exp = wall_clock64();
+#endif
         }
+        // (measured and dropped, C3, us per iteration, this form 28.7: the stores issued behind the first entry step of phase 0, loaded and waited
+        //  for first, so that the stream's first use does not wait for their acknowledgements 29.0; phase 0 -- whose rows import nothing --
+        //  compiled without the target test of the transposed products 29.3)
         // ---- y = (I + At_offdiag) p: the passes without imports first, the others once the neighbours' entries have arrived
         double yv[R];
 #pragma unroll
@@ -612,6 +632,9 @@ static __global__ __launch_bounds__(kPersistT) void k_cg_persist(PersistArgs a) 
                         uint32_t c[NJ];
                         load(v, c, J0, e);
                         compute(v, c, J0, e);
+#ifdef FDAPDE_STAMP_EXPORT
+                        if (stamper && e == 0 && J0 == 0) c_first = wall_clock64();
+#endif
                     }
                 } else {
                     for (int e = 0; e < mw; e += U) {
@@ -939,7 +962,12 @@ static __global__ __launch_bounds__(kPersistT) void k_cg_persist(PersistArgs a) 
         ++it;
         if (stamper) {
             const long long c3 = wall_clock64();
+#ifdef FDAPDE_STAMP_EXPORT
+            t_spmv += c1 - c0, t_gather += c_exp - c0, t_update += (c_first > 0 ? c_first : c_exp) - c0, ++n_stamped;
+            (void)c2, (void)c3;
+#else
             t_spmv += c1 - c0, t_gather += c2 - c1, t_update += c3 - c2, ++n_stamped;
+#endif
         }
     }
     if constexpr (STREAM) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (touches of an iteration that did not come)
