@@ -6,7 +6,7 @@ followed by PDE::solve (Dirichlet reduction + Jacobi-PCG to rtol 1e-10), all on 
 samples, Dirichlet data) are resident in HBM when the timed region starts; nothing but the solver's convergence flag
 crosses PCIe inside it.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--nx 119] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--nx 119] [--dump-outputs DIR] [--full]
 
 N = 1: the whole C3 mesh (119^3 x 6 = 10 110 954 tetrahedra, 1 728 000 DOFs) on one MI355X.
 N > 1: the same mesh, element-partitioned over N ranks, one per GPU (strong scaling).  Started either by
@@ -23,8 +23,13 @@ devices, host-staged transports over torch.distributed/gloo, imported AFTER the 
 Prints ONE JSON line (rank 0).  `roofline` describes the dominant kernel -- on one GPU the single launch that runs the whole CG
 (k_cg_persist): bytes it streams per launch (its layout x iterations) over the launch duration measured with HIP events on the
 solver's stream; `effective_*` are the same time on the algorithmic bytes of the CSR operator the caller sees
-(12 nnz + 4 (n+1) + 16 n per application).  `cpu_baseline` is the CPU oracle (oracle/fem_oracle.c, the single-threaded port of the
-reference algorithm) timed on the same workload at the same size; `cpu_baseline_all_cores` the same restatement with OpenMP.
+(12 nnz + 4 (n+1) + 16 n per application).
+
+N = 1 without --full: set-up, warm-up, the timed steps, --dump-outputs, the line -- nothing the headline figure does not need.  --full
+then runs, after the line's own timed region, what takes minutes of its own: the other single-GPU BASELINE configurations as `extra`
+(--no-extra drops them), and the CPU oracle with the entry-level parity of the device path against it (--no-cpu-baseline drops them).
+`cpu_baseline` is the CPU oracle (oracle/fem_oracle.c, the single-threaded port of the reference algorithm) timed on the same workload at
+the same size; `cpu_baseline_all_cores` the same restatement with OpenMP; a missed parity bar fails the run (exit code 3).
 """
 import argparse
 import json
@@ -62,10 +67,15 @@ def parse():
     ap.add_argument("--scaling", choices=("strong", "weak"), default="strong",
                     help="N > 1: strong (default) = the C3 mesh split over the N GPUs; weak = the mesh grown with N so that every GPU keeps about C3's "
                          "1.73 M rows (nx = round((N 120^3)^(1/3)) - 1: 150 / 189 / 239 cubes per axis at N = 2 / 4 / 8)")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: after the line's own timed steps, also run the secondary single-GPU results (`extra`), the CPU baselines and the "
+                         "parity of the device path against the CPU oracle (`cpu_baseline`, `cpu_baseline_all_cores`, `parity`)")
     ap.add_argument("--cpu-nx", type=int, default=119,
-                    help="cubes per axis of the CPU-baseline sample (119 = the GPU line's own workload: ~25 s on 1 core + ~6 s on all cores)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary single-GPU results (BASELINE configs C2 and C5) appended as `extra`")
+                    help="--full: cubes per axis of the CPU-baseline sample (119 = the GPU line's own workload: ~25 s on 1 core + ~6 s on all cores)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines and the parity against the oracle")
+    ap.add_argument("--no-extra", action="store_true",
+                    help="--full without the secondary single-GPU results appended as `extra` (BASELINE configs C1, C2 and C5, the 2.35 M and 8.1 M "
+                         "DOF runs, the multi-device context)")
     ap.add_argument("--time-spmv", type=int, default=32,
                     help="multi-launch path: SpMV launches per step timed with dispatch-attached HIP events (each costs a ~6 us bubble)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -452,7 +462,7 @@ def roofline_of(info_list, alg_bytes, streamed_bytes, nx, world, n_int=None, nnz
         ic = 256 * 1024 * 1024
         r["residency"] = (f"{streamed_bytes / 1e6:.0f} MB streamed per iteration " + ("< " if streamed_bytes < ic else ">= ") + "the 256 MiB Infinity Cache: " +
                           ("the stream is Infinity-Cache resident from the second iteration on, so `frac` (of the HBM peak) is nominal for this size; the "
-                           "HBM-resident evidence is extra.wide_2p35M" if streamed_bytes < ic else "an HBM-resident stream"))
+                           "HBM-resident evidence is extra.wide_2p35M of a --full run" if streamed_bytes < ic else "an HBM-resident stream"))
     # HBM bytes per launch from counters: NOT measured in this run (PMC needs rocprofv3 around the process) -- taken from the committed
     # PMC passes of the same workload (tools/profile_gpu.sh -> profiles/spmv_pmc.json) when they match it, and labelled so
     r["traffic"], r["traffic_source"] = None, None
@@ -490,6 +500,8 @@ def run_single(args):
 
     if capi.load().fdapde_device_count() < 1:
         raise SystemExit("bench.py needs a HIP device; there is no CPU fallback")
+    run_extra = args.full and not args.no_extra
+    run_cpu = args.full and not args.no_cpu_baseline
     device_index = int(os.environ.get("LOCAL_RANK", "0")) % max(int(capi.load().fdapde_device_count()), 1)
     t_gen = time.perf_counter()
     nodes, cells, bnd = meshgen.unit_cube(args.nx)
@@ -553,7 +565,7 @@ def run_single(args):
     _, alg_bytes = ctx.bench_spmv(reps=1)
     n_int, nnz_int, streamed_bytes = ctx.solver_layout(True)
     layout = ctx.solver_layout_kind(True)
-    want_parity = not args.no_cpu_baseline and args.cpu_nx == args.nx   # (the CPU leg runs the oracle on this very workload: compare entry by entry)
+    want_parity = run_cpu and args.cpu_nx == args.nx   # (the CPU leg runs the oracle on this very workload: compare entry by entry)
     c3_arrays = None
     if want_parity:
         from fdapde_core_amd import workloads as _w
@@ -596,7 +608,7 @@ def run_single(args):
         },
         "roofline": roofline_of(infos, alg_bytes, streamed_bytes, args.nx, 1, n_int, nnz_int, layout),
     }
-    if not args.no_extra:
+    if run_extra:
         # secondary results, after the C3 line's own timed region: the other single-GPU BASELINE configurations
         from fdapde_core_amd import workloads
 
@@ -604,7 +616,7 @@ def run_single(args):
         # (the wide run BEFORE C5: measured right after C5's seconds of full-HBM BiCGStab the same launch took 101 instead of 74 us per iteration)
         for name, fn in (("c2", workloads.run_c2), ("wide_2p35M", workloads.run_wide), ("large_8p1M", workloads.run_large), ("c5", workloads.run_c5)):
             try:
-                kw = {"keep_arrays": True} if name == "c2" and not args.no_cpu_baseline else {}
+                kw = {"keep_arrays": True} if name == "c2" and run_cpu else {}
                 extra[name] = fn(capi, meshgen, device=device_index, hbm_peak_gbps=HBM_PEAK_GBPS, **kw)
             except Exception as e:   # never let a secondary result take the bench line down
                 extra[name] = {"error": f"{type(e).__name__}: {e}"[:300]}
@@ -619,13 +631,13 @@ def run_single(args):
         out["extra"] = extra
     c2_arrays = out.get("extra", {}).get("c2", {}).pop("_arrays", None) if isinstance(out.get("extra", {}).get("c2"), dict) else None
     parity_ok = True
-    if not args.no_cpu_baseline:
+    if run_cpu:
         out["cpu_baseline"], out["cpu_baseline_all_cores"], c3_parity = cpu_baseline(args.cpu_nx, c3_arrays)
         del c3_arrays
         # entry-level parity with the oracle at the sizes the numbers are quoted on (bars: SURVEY 8d); a missed bar fails the bench (exit code 3)
         out["parity"] = {"c3": c3_parity if c3_parity is not None else
                          {"ok": None, "skipped": f"the CPU sample (--cpu-nx {args.cpu_nx}) is not this line's workload (--nx {args.nx})"}}
-        if not args.no_extra:   # CPU columns beside the secondary results: direct solves where the reference's own solve is feasible (C1, C2)
+        if run_extra:   # CPU columns beside the secondary results: direct solves where the reference's own solve is feasible (C1, C2)
             cols = cpu_columns(c2_gpu=c2_arrays)
             for name in ("c1", "c2", "c5"):
                 if isinstance(out["extra"].get(name), dict):

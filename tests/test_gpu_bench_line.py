@@ -12,11 +12,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_single_gpu_line_has_first_call_and_hygiene_fields(tmp_path):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--nx", "40", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extra",
-                          "--dump-outputs", str(tmp_path)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, cwd=ROOT)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--nx", "40", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                         stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert rec["n_gpus"] == 1 and rec["scaling"] == "strong" and rec["dtype"] == "f64" and rec["vs_baseline"] is None
+    # a plain run is the headline line alone: the secondary results, the CPU baselines and the parity run with --full only
+    assert not {"extra", "cpu_baseline", "cpu_baseline_all_cores", "parity"} & rec.keys(), sorted(rec)
     assert rec["steps"] == 2 and rec["ms_per_step"] > 0
     # --dump-outputs: what the last timed step handed its caller, whole at this size
     import numpy as np
@@ -61,7 +63,8 @@ def test_single_gpu_line_carries_oracle_parity():
     """the CPU leg compares what the oracle computes with what the device path produced for the same workload -- pattern, DOF table,
     boundary DOFs bit-exact, stiff_ / mass_ / force_ entries and the solution within the bars of SURVEY 8(d) -- and the line says so (`parity`).
     Reduced mesh here (the fields and the mechanism; the driver's run carries the full-size figures)."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--nx", "24", "--cpu-nx", "24", "--steps", "1", "--warmup", "1", "--no-extra"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--nx", "24", "--cpu-nx", "24", "--steps", "1", "--warmup", "1", "--full",
+                          "--no-extra"],
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
