@@ -251,8 +251,11 @@ class Context:
 
     # ---- domain / space
     def mesh_upload(self, nodes, cells, boundary):
-        """nodes (n_nodes, N) any order; cells (n_cells, M+1) int32 0-based; boundary (n_nodes,) 0/1"""
+        """nodes (n_nodes, N) any order; cells (n_cells, M+1) int32 0-based; boundary (n_nodes,) 0/1.  (M, N) comes from the shapes: 2-column
+        cells are segments (M = 1) of an interval (nodes (n_nodes,) or (n_nodes, 1)) or of a network in the plane (nodes (n_nodes, 2))"""
         nodes = np.asarray(nodes, dtype=float)
+        if nodes.ndim == 1:
+            nodes = nodes.reshape(-1, 1)
         cells = np.ascontiguousarray(cells, dtype=np.int32)
         boundary = np.ascontiguousarray(boundary, dtype=np.uint8).reshape(-1)
         colmajor = np.ascontiguousarray(nodes.T).reshape(-1)
@@ -396,6 +399,8 @@ class Context:
         import scipy.sparse as sp
 
         locs = np.asarray(locs, dtype=float)
+        if locs.ndim == 1:
+            locs = locs.reshape(-1, 1)
         nl, s = locs.shape[0], self.sizes()
         flat = np.ascontiguousarray(locs.T).reshape(-1)
         cells = np.zeros(nl, dtype=np.int32)

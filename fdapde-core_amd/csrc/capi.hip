@@ -149,6 +149,9 @@ int fdapde_mesh_upload(fdapde_ctx* c, int M, int N, int64_t n_nodes, const doubl
     if (c->group && M == 2 && N == 3)
         return fail(c, FDAPDE_EUNSUPPORTED, "fdapde_mesh_upload: a surface mesh (Triangulation<2,3>) takes a one-GPU context; the multi-device partitioner "
                                             "and its ranks are built for planar and volume meshes");
+    if (c->group && M == 1)
+        return fail(c, FDAPDE_EUNSUPPORTED, "fdapde_mesh_upload: a 1-D mesh (interval or linear network, Triangulation<1,N>) takes a one-GPU context; the "
+                                            "multi-device partitioner and its ranks are built for planar and volume meshes");
     c->space_ready = c->dev_ready = c->colour_ready = c->fq_blk_ready = c->fq_bc_ready = c->stiff_stat_valid = false;
     c->assembled[0] = c->assembled[1] = c->force_ready = c->solved = c->dirichlet_applied = false;
     c->op.clear(), c->coef_of_op = false, c->fq_i.clear(), c->fq_cols = 0, c->g_i.clear(), c->have_g = false;

@@ -45,7 +45,8 @@ struct DevBinGrid {
     double lo[3] = {0, 0, 0}, inv_h[3] = {0, 0, 0};
     int32_t dims[3] = {1, 1, 1};
 };
-int dev_build_bin_grid(int M, int64_t n_nodes, int64_t n_cells, const double* d_vcoords, const int32_t* d_cverts, void* stream, DevBinGrid* out,
+// M: the dimension binned over (the embedding dimension N of the mesh), NV: vertices per cell (M + 1; 2 for the segments of a network in R^2)
+int dev_build_bin_grid(int M, int NV, int64_t n_nodes, int64_t n_cells, const double* d_vcoords, const int32_t* d_cverts, void* stream, DevBinGrid* out,
                        std::string& err);
 
 void dev_setup_preload();      // loads this unit's code object (hipFuncGetAttributes of one of its kernels)

@@ -117,7 +117,7 @@ __global__ void k_morton_keys(int N, int64_t n, const double* pts, const double*
         const double w = hi > lo ? (pts[(int64_t)d * n + i] - lo) / (hi - lo) : 0.0;
         q[d] = (uint64_t)llround(fmin(1.0, fmax(0.0, w)) * span);
     }
-    key[i] = N == 3 ? (d_spread3(q[0]) | d_spread3(q[1]) << 1 | d_spread3(q[2]) << 2) : (d_spread2(q[0]) | d_spread2(q[1]) << 1);
+    key[i] = N == 3 ? (d_spread3(q[0]) | d_spread3(q[1]) << 1 | d_spread3(q[2]) << 2) : N == 2 ? (d_spread2(q[0]) | d_spread2(q[1]) << 1) : q[0];
     idx[i] = (int32_t)i;
 }
 __global__ void k_invert(int64_t n, const int32_t* p, int32_t* inv) {
@@ -503,17 +503,19 @@ template <typename In, typename Out> int exclusive_sum(Scratch& sc, In* in, Out*
 }
 
 // ---- bin grid for point location (dev_build_bin_grid) ----------------------------------------------------------------------------------
+// M: the binning dimension = the embedding dimension N (1 for an interval, 2 for a plane mesh or a network in R^2, 3); NV: vertices per cell
+// (M + 1, or 2 for the segments of a network in R^2)
 template <int M> struct BinGeo {
     double lo[M], inv_h[M];
     int32_t dims[M];
 };
 // bins [b0, b1] a cell's bounding box overlaps along axis d (the expressions of the former host loop, operation for operation)
-template <int M>
+template <int M, int NV = M + 1>
 __device__ __forceinline__ void bin_range(const BinGeo<M>& G, const double* vcoords, const int32_t* cv, int d, int& b0, int& b1) {
-    constexpr int NP = M == 2 ? 2 : 4;
+    constexpr int NP = M <= 2 ? 2 : 4;
     double mn = 1e300, mx = -1e300;
 #pragma unroll
-    for (int v = 0; v <= M; ++v) {
+    for (int v = 0; v < NV; ++v) {
         const double x = vcoords[(size_t)cv[v] * NP + d];
         mn = x < mn ? x : mn, mx = x > mx ? x : mx;
     }
@@ -521,19 +523,19 @@ __device__ __forceinline__ void bin_range(const BinGeo<M>& G, const double* vcoo
     b0 = b0 < 0 ? 0 : b0, b1 = b1 >= G.dims[d] ? G.dims[d] - 1 : b1;
 }
 // FILL = false: cnt[bin] += 1 per (cell, bin) overlap; FILL = true: the cell into the bin's list at the next free position
-template <int M, bool FILL>
+template <int M, bool FILL, int NV = M + 1>
 __global__ __launch_bounds__(256) void k_bin_cells(BinGeo<M> G, int64_t n_cells, const double* vcoords, const int32_t* cverts, int32_t* cnt_or_cursor,
                                                    int32_t* bin_cells) {
     const int64_t cell = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (cell >= n_cells) return;
-    const int32_t* cv = cverts + cell * (M + 1);
+    const int32_t* cv = cverts + cell * NV;
     int b0[3] = {0, 0, 0}, b1[3] = {0, 0, 0};
 #pragma unroll
-    for (int d = 0; d < M; ++d) bin_range<M>(G, vcoords, cv, d, b0[d], b1[d]);
+    for (int d = 0; d < M; ++d) bin_range<M, NV>(G, vcoords, cv, d, b0[d], b1[d]);
     for (int z = b0[2]; z <= b1[2]; ++z)
         for (int y = b0[1]; y <= b1[1]; ++y)
             for (int x = b0[0]; x <= b1[0]; ++x) {
-                const int64_t bin = M == 2 ? (int64_t)y * G.dims[0] + x : ((int64_t)z * G.dims[1] + y) * G.dims[0] + x;
+                const int64_t bin = M <= 2 ? (int64_t)y * G.dims[0] + x : ((int64_t)z * G.dims[1] + y) * G.dims[0] + x;   // (M = 1: y = 0)
                 const int32_t at = atomicAdd(cnt_or_cursor + bin, 1);
                 if constexpr (FILL) bin_cells[at] = (int32_t)cell;
             }
@@ -600,11 +602,11 @@ int morton_order(Scratch& sc, int N, int64_t n, const double* d_pts, int bits, h
 
 }  // namespace
 
-int dev_build_bin_grid(int M, int64_t n_nodes, int64_t n_cells, const double* d_vcoords, const int32_t* d_cverts, void* stream, DevBinGrid* out,
+int dev_build_bin_grid(int M, int NV, int64_t n_nodes, int64_t n_cells, const double* d_vcoords, const int32_t* d_cverts, void* stream, DevBinGrid* out,
                        std::string& err) {
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (!out || (M != 2 && M != 3) || n_nodes < 1 || n_cells < 1) return FDAPDE_EINVAL;
-    const int NP = M == 2 ? 2 : 4;
+    if (!out || M < 1 || M > 3 || !(NV == M + 1 || (M == 2 && NV == 2)) || n_nodes < 1 || n_cells < 1) return FDAPDE_EINVAL;
+    const int NP = M <= 2 ? 2 : 4;
     Scratch sc;
     // bounding box
     const int nblk = (int)std::min<int64_t>(256, (n_nodes + 255) / 256);
@@ -641,10 +643,25 @@ int dev_build_bin_grid(int M, int64_t n_nodes, int64_t n_cells, const double* d_
     do {                                                                                                                       \
         BinGeo<MM> G;                                                                                                          \
         for (int d = 0; d < MM; ++d) G.lo[d] = g.lo[d], G.inv_h[d] = g.inv_h[d], G.dims[d] = g.dims[d];                        \
-        hipLaunchKernelGGL((k_bin_cells<MM, FILL_>), dim3(grid_of(n_cells)), dim3(256), 0, st, G, n_cells, d_vcoords, d_cverts, CNT_, CELLS_); \
+        hipLaunchKernelGGL((k_bin_cells<MM, FILL_, NV_>), dim3(grid_of(n_cells)), dim3(256), 0, st, G, n_cells, d_vcoords, d_cverts, CNT_, CELLS_); \
     } while (0)
-    if (M == 2) BIN_GO(2, false, cnt.p, (int32_t*)nullptr);
-    else BIN_GO(3, false, cnt.p, (int32_t*)nullptr);
+#define BIN_ALL(FILL_, CNT_, CELLS_)                                         \
+    do {                                                                     \
+        if (M == 1) {                                                        \
+            constexpr int NV_ = 2;                                           \
+            BIN_GO(1, FILL_, CNT_, CELLS_);                                  \
+        } else if (M == 2 && NV == 2) {   /* segments of a network in R^2 */ \
+            constexpr int NV_ = 2;                                           \
+            BIN_GO(2, FILL_, CNT_, CELLS_);                                  \
+        } else if (M == 2) {                                                 \
+            constexpr int NV_ = 3;                                           \
+            BIN_GO(2, FILL_, CNT_, CELLS_);                                  \
+        } else {                                                             \
+            constexpr int NV_ = 4;                                           \
+            BIN_GO(3, FILL_, CNT_, CELLS_);                                  \
+        }                                                                    \
+    } while (0)
+    BIN_ALL(false, cnt.p, (int32_t*)nullptr);
     if (int rc = exclusive_sum(sc, cnt.p, g.bin_ptr, g.n_bins + 1, st, err)) return fail_free(rc);
     int32_t total = 0;
     if (hipMemcpyAsync(&total, g.bin_ptr + g.n_bins, sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
@@ -658,8 +675,8 @@ int dev_build_bin_grid(int M, int64_t n_nodes, int64_t n_cells, const double* d_
     }
     // cursors = the offsets; the fill pass advances them
     if (hipMemcpyAsync(cnt.p, g.bin_ptr, sizeof(int32_t) * ((size_t)g.n_bins + 1), hipMemcpyDeviceToDevice, st) != hipSuccess) return fail_free(FDAPDE_EHIP);
-    if (M == 2) BIN_GO(2, true, cnt.p, g.bin_cells);
-    else BIN_GO(3, true, cnt.p, g.bin_cells);
+    BIN_ALL(true, cnt.p, g.bin_cells);
+#undef BIN_ALL
 #undef BIN_GO
     hipLaunchKernelGGL(k_bin_sort, dim3(grid_of(g.n_bins)), dim3(256), 0, st, g.n_bins, g.bin_ptr, g.bin_cells);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {   // (the temporaries of this scope are freed on return)
@@ -730,7 +747,7 @@ int dev_build_space(HostSpace& hs, const double* d_nodes, const int32_t* d_cells
         hipLaunchKernelGGL(k_invert, dim3(grid_of(nd)), dim3(256), 0, st, nd, s.dof_i2e, s.dof_e2i);
     }
     DS_ALLOC(s.cell_i2e, int32_t, nc);
-    const int NP = N == 2 ? 2 : 4;
+    const int NP = N <= 2 ? 2 : 4;   // (host_setup.cpp: N = 1 pads to 2 doubles per node)
     Tmp<double> npack;
     DS_CHK(npack.alloc((size_t)nn * NP));
     hipLaunchKernelGGL(k_pack_nodes, dim3(grid_of(nn)), dim3(256), 0, st, nn, N, NP, d_nodes, npack.p);
@@ -975,8 +992,8 @@ int dev_build_space(HostSpace& hs, const double* d_nodes, const int32_t* d_cells
     DS_CHK(hipStreamSynchronize(st));
     hs.max_slice_width = h_max[4];
     hs.nnz = nnz, hs.max_row = h_max[0], hs.max_blk_nnz = h_max[1], hs.max_blk_cells = h_max[2], hs.max_blk_nodes = h_max[3], hs.nbw = nbw;
-    if (hs.max_row > 65535 || hs.max_row > kSpmvNnz) {
-        err = "row too long for the uint16 slot map / SpMV row block";
+    if (hs.max_row > 65535) {   // (rows longer than kSpmvNnz -- network hubs -- are SpMV row blocks of their own)
+        err = "row too long for the uint16 slot map";
         return FDAPDE_EUNSUPPORTED;
     }
     if (hs.max_blk_nodes > 65535) {
@@ -989,7 +1006,7 @@ int dev_build_space(HostSpace& hs, const double* d_nodes, const int32_t* d_cells
     for (int64_t r = 0; want_rb && r < nd;) {   // SpMV row blocks: consecutive rows with at most kSpmvNnz nonzeros
         int64_t e = r;
         const int32_t base = hs.rowptr_i[(size_t)r];
-        while (e < nd && hs.rowptr_i[(size_t)e + 1] - base <= kSpmvNnz && e - r < 1024) ++e;
+        while (e < nd && (e == r || hs.rowptr_i[(size_t)e + 1] - base <= kSpmvNnz) && e - r < 1024) ++e;
         hs.rb_row.push_back((int32_t)e);
         r = e;
     }

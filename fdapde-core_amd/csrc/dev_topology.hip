@@ -192,6 +192,13 @@ struct RefNodes {
     double v[10 * 3];
 };
 // the edge DOF's coordinates from the first cell that visits it: acc = sum_k (x_{k+1} - x_0) ref_k (in this order, no contraction), + x_0
+// 1-D (Triangulation<1,N>): a segment is its own edge -- DOF row [v0, v1, n_nodes + c] (the numbering the reference's edge rule would give if
+// a segment were listed as its own edge, lagrangian_basis.h:107-127); boundary DOFs = boundary nodes, midpoints interior
+__global__ void k_p2_dofs_1d(int64_t nc, int64_t nn, const int32_t* cells, const uint8_t* node_bnd, int32_t* dofs, uint8_t* bnd) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < nc) dofs[i * 3] = cells[i * 2], dofs[i * 3 + 1] = cells[i * 2 + 1], dofs[i * 3 + 2] = (int32_t)(nn + i);
+    if (i < nn + nc) bnd[i] = i < nn ? node_bnd[i] : (uint8_t)0;
+}
 template <int M>
 __global__ void k_p2_coords(int64_t nn, int64_t ne, int N, int nb, const double* nodes, const int32_t* cells, const int32_t* dofs,
                             const int32_t* first_cell_of /* 2-D: facet_cells (stride 2); 3-D: edge_face */, const int32_t* facet_cells,
@@ -204,7 +211,7 @@ __global__ void k_p2_coords(int64_t nn, int64_t ne, int N, int nb, const double*
     }
     if (i >= nd) return;
     const int64_t e = i - nn;
-    const int64_t c = M == 2 ? first_cell_of[2 * e] : facet_cells[2 * (int64_t)first_cell_of[e]];
+    const int64_t c = M == 1 ? e : M == 2 ? first_cell_of[2 * e] : facet_cells[2 * (int64_t)first_cell_of[e]];
     const int32_t dof = (int32_t)i;
     int j = M + 1;
     while (j < nb - 1 && dofs[c * nb + j] != dof) ++j;
@@ -368,7 +375,32 @@ int dev_build_p2_dofs(int M, int N, int64_t n_nodes, int64_t n_cells, const doub
                       const double* refnodes, void* stream, int32_t** d_dofs, uint8_t** d_dof_bnd, double** d_dof_coords, int64_t* n_edges,
                       std::string& err) {
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if ((M != 2 && M != 3) || (N != M && !(M == 2 && N == 3))) return FDAPDE_EUNSUPPORTED;
+    if ((M < 1 || M > 3) || (N != M && !(M == 2 && N == 3) && !(M == 1 && N == 2))) return FDAPDE_EUNSUPPORTED;
+    if (M == 1) {   // no topology needed: the segment is the edge
+        const int64_t nd = n_nodes + n_cells;
+        if (nd > INT32_MAX) {
+            err = "too many DOFs";
+            return FDAPDE_EUNSUPPORTED;
+        }
+        int32_t* dofs = nullptr;
+        uint8_t* bnd = nullptr;
+        double* coords = nullptr;
+        TOPO_CHK(hipMalloc(reinterpret_cast<void**>(&dofs), sizeof(int32_t) * (size_t)n_cells * 3));
+        TOPO_CHK(hipMalloc(reinterpret_cast<void**>(&bnd), (size_t)nd));
+        TOPO_CHK(hipMalloc(reinterpret_cast<void**>(&coords), sizeof(double) * (size_t)nd * N));
+        RefNodes ref{};
+        for (int i = 0; i < 3; ++i) ref.v[i] = refnodes[i];
+        hipLaunchKernelGGL(k_p2_dofs_1d, dim3(grid_of(nd)), dim3(256), 0, st, n_cells, n_nodes, d_cells, d_node_bnd, dofs, bnd);
+        hipLaunchKernelGGL(k_p2_coords<1>, dim3(grid_of(nd)), dim3(256), 0, st, n_nodes, n_cells, N, 3, d_nodes, d_cells, dofs, (const int32_t*)nullptr,
+                           (const int32_t*)nullptr, ref, coords);
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+            (void)hipFree(dofs), (void)hipFree(bnd), (void)hipFree(coords);
+            err = "order-2 DOF kernels failed";
+            return FDAPDE_EHIP;
+        }
+        *d_dofs = dofs, *d_dof_bnd = bnd, *d_dof_coords = coords, *n_edges = n_cells;
+        return FDAPDE_OK;
+    }
     DevTopology t;
     if (int rc = dev_build_topology(M, n_nodes, n_cells, d_cells, d_node_bnd, stream, &t, err)) return rc;
     struct Guard {

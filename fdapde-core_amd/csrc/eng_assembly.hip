@@ -149,11 +149,11 @@ int check_terms(fdapde_ctx* c, int32_t n_terms, const fdapde_term* terms, std::v
     return FDAPDE_OK;
 }
 
-// N: the embedding dimension (M, or 3 for a surface mesh: launch_assembly sends surfaces to the row-owner sweep only)
+// N: the embedding dimension (M, or 3 for a surface mesh; M = 1: 1 or 2 -- launch_assembly sends surfaces and 1-D meshes to the row-owner sweep only)
 template <int M, int R, int N = M>
 int launch_assembly_t(fdapde_ctx* c, AsmArgs a, const DevOp& op, int assembly) {
     const HostSpace& hs = c->hs;
-    constexpr int NB = (M == 2) ? (R == 1 ? 3 : 6) : (R == 1 ? 4 : 10);
+    constexpr int NB = kNB<M, R>;
     if (assembly == FDAPDE_ASSEMBLY_ROWS) {
         // specialised integrands (see element_row): the two operators FEMSolverBase::init always assembles, and any other
         // constant-coefficient expression through the reference tensors
@@ -164,18 +164,19 @@ int launch_assembly_t(fdapde_ctx* c, AsmArgs a, const DevOp& op, int assembly) {
         if (!op.needs_rows) opk = 3;
         if (op.n == 1 && op.t[0].kind == FDAPDE_LAPLACIAN) opk = 1;
         if (op.n == 1 && op.t[0].kind == FDAPDE_REACTION && !op.t[0].space_varying) opk = 2;
-        // (the generic integrand -- a measurement knob -- on planar and volume meshes only: its surface instantiation would be one more kernel with a
-        //  scratch copy of the operator; GEN stands in for it where the code must name a kernel)
-        constexpr int GEN = N == M ? 0 : 4;
+        // (the generic integrand -- a measurement knob -- on planar and volume meshes only: its surface and 1-D instantiations would be more kernels
+        //  with a scratch copy of the operator; GEN stands in for it where the code must name a kernel)
+        constexpr bool kGeneric = N == M && M >= 2;
+        constexpr int GEN = kGeneric ? 0 : 4;
         if (std::getenv("FDAPDE_ASM_GENERIC")) {
-            if (N == M) opk = 0;
-            else std::fprintf(stderr, "FDAPDE_ASM_GENERIC: ignored on a surface mesh (no generic-integrand instantiation for Triangulation<2,3>): "
-                                      "the specialised integrand OPK %d runs\n", opk);
+            if (kGeneric) opk = 0;
+            else std::fprintf(stderr, "FDAPDE_ASM_GENERIC: ignored on a %s (no generic-integrand instantiation for Triangulation<%d,%d>): "
+                                      "the specialised integrand OPK %d runs\n", M == 1 ? "1-D mesh" : "surface mesh", M, N, opk);
         }
         if (op.kt_sym) a.reftab = reinterpret_cast<const DevRefTensors*>(c->reftab_sym.p), a.ref_doubles = kRefSymDoubles;   // (the compact tensors)
         else a.reftab = c->reftab.p, a.ref_doubles = kRefDoubles;
         const size_t tab = sizeof(DevTables) + (opk == 3 || opk == 5 ? sizeof(double) * (size_t)a.ref_doubles : 0) +
-                           (size_t)hs.max_blk_nodes * (N == 2 ? 2 : 3) * sizeof(double);
+                           (size_t)hs.max_blk_nodes * (N <= 2 ? 2 : 3) * sizeof(double);
         size_t acc = (size_t)hs.max_blk_nnz * sizeof(double);
         // operator + mass in one sweep (a.vals2): both accumulator ranges of every block must fit the LDS, else two sweeps as before
         // ... and the second range must not cost occupancy: measured (tools/asm_fuse_ab.py) 2-D P1 C2 0.073 -> 0.046 ms (40 KB per workgroup), but
@@ -315,6 +316,8 @@ int launch_assembly_t(fdapde_ctx* c, AsmArgs a, const DevOp& op, int assembly) {
             hipLaunchKernelGGL((k_assemble_rows<M, R, 2, 0, N>), dim3(grid), dim3(kAsmBlock), lds, c->stream, a, op);
         else
             hipLaunchKernelGGL((k_assemble_rows<M, R, GEN, 0, N>), dim3(grid), dim3(kAsmBlock), lds, c->stream, a, op);
+    } else if constexpr (M == 1 || N != M) {   // (launch_assembly refuses the other variants on these meshes: nothing is instantiated for them)
+        return FDAPDE_EUNSUPPORTED;
     } else {
         if (a.vals) HIPCHK(c, hipMemsetAsync(a.vals, 0, sizeof(double) * (size_t)hs.nnz, c->stream));
         if (a.force) HIPCHK(c, hipMemsetAsync(a.force, 0, sizeof(double) * (size_t)hs.n_dofs, c->stream));
@@ -419,6 +422,13 @@ int launch_assembly(fdapde_ctx* c, const AsmArgs& a, const DevOp& op, int assemb
             return fail(c, FDAPDE_EUNSUPPORTED, "surface meshes (Triangulation<2,3>) are assembled by the row-owner sweep (FDAPDE_ASSEMBLY_ROWS) only: "
                                                 "the atomic, coloured, partitioned and wave variants have no surface geometry");
         return R == 1 ? launch_assembly_t<2, 1, 3>(c, a, op, assembly) : launch_assembly_t<2, 2, 3>(c, a, op, assembly);
+    }
+    if (M == 1) {   // an interval (Triangulation<1,1>) or a linear network in the plane (Triangulation<1,2>): the same two sweeps only
+        if (assembly != FDAPDE_ASSEMBLY_ROWS)
+            return fail(c, FDAPDE_EUNSUPPORTED, "1-D meshes (Triangulation<1,N>) are assembled by the row-owner sweep (FDAPDE_ASSEMBLY_ROWS) only: "
+                                                "the atomic, coloured, partitioned and wave variants have no segment geometry");
+        if (c->hs.N == 1) return R == 1 ? launch_assembly_t<1, 1, 1>(c, a, op, assembly) : launch_assembly_t<1, 2, 1>(c, a, op, assembly);
+        return R == 1 ? launch_assembly_t<1, 1, 2>(c, a, op, assembly) : launch_assembly_t<1, 2, 2>(c, a, op, assembly);
     }
     if (M == 2 && R == 1) return launch_assembly_t<2, 1>(c, a, op, assembly);
     if (M == 2 && R == 2) return launch_assembly_t<2, 2>(c, a, op, assembly);
@@ -647,7 +657,7 @@ int e_eval_pointwise(fdapde_ctx* c, int64_t n_locs, const double* locs_colmajor,
     HIPCHK(c, hipSetDevice(c->device));
     const HostSpace& hs = c->hs;
     const int M = hs.M;
-    if (hs.N != M)
+    if (hs.N != M && M != 1)
         return fail(c, FDAPDE_EUNSUPPORTED, "fdapde_eval_pointwise on a surface mesh (Triangulation<2,3>): locating a point needs its projection onto the surface, "
                                             "which is not built");
     hipStream_t st = c->stream;
@@ -656,7 +666,8 @@ int e_eval_pointwise(fdapde_ctx* c, int64_t n_locs, const double* locs_colmajor,
     fdapde_ctx::EvalGrid& eg = c->eval_grid;
     if (!eg.ready) {
         DevBinGrid g;
-        if (int rc = dev_build_bin_grid(M, hs.n_nodes, hs.n_cells, c->vcoords.p, c->cverts.p, st, &g, c->err)) return rc;
+        // (bins span the embedding space: a network in R^2 is binned over the plane)
+        if (int rc = dev_build_bin_grid(hs.N, M + 1, hs.n_nodes, hs.n_cells, c->vcoords.p, c->cverts.p, st, &g, c->err)) return rc;
         adopt(eg.ptr, g.bin_ptr, (size_t)g.n_bins + 1), adopt(eg.cells, g.bin_cells, (size_t)g.n_entries + 1);
         HIPCHK(c, eg.dims.upload(g.dims, 3, st));
         HIPCHK(c, eg.lo.upload(g.lo, 3, st));
@@ -664,19 +675,25 @@ int e_eval_pointwise(fdapde_ctx* c, int64_t n_locs, const double* locs_colmajor,
         HIPCHK(c, hipStreamSynchronize(st));   // (g's small arrays live on this stack frame)
         eg.ready = true;
     }
-    HIPCHK(c, c->eval_locs.upload(locs_colmajor, (size_t)n_locs * M, st));
+    HIPCHK(c, c->eval_locs.upload(locs_colmajor, (size_t)n_locs * hs.N, st));
     HIPCHK(c, c->eval_out.alloc((size_t)n_locs));
     HIPCHK(c, c->eval_vals.alloc((size_t)n_locs * hs.nb));
     AsmArgs a = asm_args(c);
     const double tol = 1e-12;
     const dim3 grid(g1(n_locs)), block(256);
-#define EVAL_GO(MM, RR)                                                                                                  \
-    hipLaunchKernelGGL((k_eval_pointwise<MM, RR>), grid, block, 0, st, a, n_locs, c->eval_locs.p, eg.lo.p, eg.invh.p, eg.dims.p, eg.ptr.p, \
+#define EVAL_GO(MM, RR, NN)                                                                                              \
+    hipLaunchKernelGGL((k_eval_pointwise<MM, RR, NN>), grid, block, 0, st, a, n_locs, c->eval_locs.p, eg.lo.p, eg.invh.p, eg.dims.p, eg.ptr.p, \
                        eg.cells.p, c->cell_i2e.p, tol, c->eval_out.p, c->eval_vals.p)
-    if (M == 2 && hs.order == 1) EVAL_GO(2, 1);
-    else if (M == 2) EVAL_GO(2, 2);
-    else if (hs.order == 1) EVAL_GO(3, 1);
-    else EVAL_GO(3, 2);
+    if (M == 1 && hs.N == 1) {
+        if (hs.order == 1) EVAL_GO(1, 1, 1);
+        else EVAL_GO(1, 2, 1);
+    } else if (M == 1) {
+        if (hs.order == 1) EVAL_GO(1, 1, 2);
+        else EVAL_GO(1, 2, 2);
+    } else if (M == 2 && hs.order == 1) EVAL_GO(2, 1, 2);
+    else if (M == 2) EVAL_GO(2, 2, 2);
+    else if (hs.order == 1) EVAL_GO(3, 1, 3);
+    else EVAL_GO(3, 2, 3);
 #undef EVAL_GO
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(cell_ids, c->eval_out.p, sizeof(int32_t) * (size_t)n_locs, hipMemcpyDeviceToHost, st));
@@ -696,7 +713,11 @@ int e_cell_integrals(fdapde_ctx* c, double* measure, double* psi_int) {
     HIPCHK(c, d_m.alloc((size_t)hs.n_cells));
     HIPCHK(c, d_p.alloc((size_t)hs.n_cells * hs.nb));
     AsmArgs a = asm_args(c);
-    if (hs.M == 2 && hs.N == 3)
+    if (hs.M == 1 && hs.N == 1)
+        hipLaunchKernelGGL((k_cell_integrals<1, 1>), dim3(g1(hs.n_cells)), dim3(256), 0, c->stream, a, hs.nb, hs.nq, c->cell_i2e.p, d_m.p, d_p.p);
+    else if (hs.M == 1)
+        hipLaunchKernelGGL((k_cell_integrals<1, 2>), dim3(g1(hs.n_cells)), dim3(256), 0, c->stream, a, hs.nb, hs.nq, c->cell_i2e.p, d_m.p, d_p.p);
+    else if (hs.M == 2 && hs.N == 3)
         hipLaunchKernelGGL((k_cell_integrals<2, 3>), dim3(g1(hs.n_cells)), dim3(256), 0, c->stream, a, hs.nb, hs.nq, c->cell_i2e.p, d_m.p, d_p.p);
     else if (hs.M == 2)
         hipLaunchKernelGGL(k_cell_integrals<2>, dim3(g1(hs.n_cells)), dim3(256), 0, c->stream, a, hs.nb, hs.nq, c->cell_i2e.p, d_m.p, d_p.p);
@@ -720,7 +741,11 @@ int e_quadrature_nodes(fdapde_ctx* c, double* out) {
     DBuf<double> d;
     HIPCHK(c, d.alloc((size_t)rows * hs.N));
     AsmArgs a = asm_args(c);
-    if (hs.M == 2 && hs.N == 3)
+    if (hs.M == 1 && hs.N == 1)
+        hipLaunchKernelGGL((k_quadrature_nodes<1, 1>), dim3(g1(rows)), dim3(256), 0, c->stream, a, c->cell_i2e.p, hs.nq, d.p);
+    else if (hs.M == 1)
+        hipLaunchKernelGGL((k_quadrature_nodes<1, 2>), dim3(g1(rows)), dim3(256), 0, c->stream, a, c->cell_i2e.p, hs.nq, d.p);
+    else if (hs.M == 2 && hs.N == 3)
         hipLaunchKernelGGL((k_quadrature_nodes<2, 3>), dim3(g1(rows)), dim3(256), 0, c->stream, a, c->cell_i2e.p, hs.nq, d.p);
     else if (hs.M == 2)
         hipLaunchKernelGGL(k_quadrature_nodes<2>, dim3(g1(rows)), dim3(256), 0, c->stream, a, c->cell_i2e.p, hs.nq, d.p);

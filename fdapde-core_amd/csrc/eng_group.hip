@@ -1062,9 +1062,9 @@ int e_partition_build(fdapde_ctx* c, int32_t world, int32_t form) {
     if (!c) return FDAPDE_EINVAL;
     if (int rc = need_device(c)) return rc;
     if (c->hs.n_cells == 0) return fail(c, FDAPDE_ENOTINIT, "call fdapde_mesh_upload first");
-    if (c->hs.N != c->hs.M)
-        return fail(c, FDAPDE_EUNSUPPORTED, "fdapde_partition_build: surface meshes (Triangulation<2,3>) are not partitioned (the partitioner bins planar and "
-                                            "volume meshes; a surface takes a one-GPU context)");
+    if (c->hs.N != c->hs.M || c->hs.M == 1)
+        return fail(c, FDAPDE_EUNSUPPORTED, "fdapde_partition_build: surface meshes (Triangulation<2,3>) and 1-D meshes (Triangulation<1,N>) are not partitioned "
+                                            "(the partitioner bins planar and volume meshes; surfaces, intervals and networks take a one-GPU context)");
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->mesh_on_dev) {
         const HostSpace& hs = c->hs;

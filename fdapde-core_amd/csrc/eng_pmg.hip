@@ -41,6 +41,7 @@ namespace {
 using namespace fdapde_hip;
 
 // local edge slot -> its two local vertices (csrc/tables.cpp EDGE2 / EDGE3; reference_element.h:60-62, 93-96)
+const int kEdge1[1][2] = {{0, 1}};   // a segment's midpoint (ReferenceElement<1,2> node 2): the mean of its two ends
 const int kEdge2[3][2] = {{0, 1}, {0, 2}, {1, 2}};
 const int kEdge3[6][2] = {{1, 2}, {0, 2}, {0, 1}, {1, 3}, {2, 3}, {0, 3}};
 
@@ -444,7 +445,7 @@ static int pmg_tables_host(fdapde_ctx* c, fdapde_ctx* cc, std::vector<int32_t>& 
             if (pass == 0)
                 for (int k = 0; k < nv; ++k) pa[(size_t)h2.dof_e2i[(size_t)d2[k]]] = h1.dof_e2i[(size_t)d1[k]], bnd1[(size_t)d1[k]] = h2.dof_bnd[(size_t)d2[k]];
             for (int k = nv; k < nb2; ++k) {
-                const int* ed = h2.M == 2 ? kEdge2[k - nv] : kEdge3[k - nv];
+                const int* ed = h2.M == 1 ? kEdge1[k - nv] : h2.M == 2 ? kEdge2[k - nv] : kEdge3[k - nv];
                 if (pass == 0) {
                     const size_t fi = (size_t)h2.dof_e2i[(size_t)d2[k]];
                     const int32_t x = h1.dof_e2i[(size_t)d1[ed[0]]], y = h1.dof_e2i[(size_t)d1[ed[1]]];
@@ -520,7 +521,10 @@ static int pmg_setup(fdapde_ctx* c) {
     // whatever its end nodes are (triangulation.h:150-193 / fe_space DOF marking), and a coarse function that does not vanish at those nodes prolongs to a zig-zag
     // the coarse operator takes for a smooth mode (100 - 300 outer iterations on such masks; tools/fuzz_pmg.py)
     PmgEdges ed{};
-    for (int k = 0; k < nb2 - nv; ++k) ed.a[k] = h2.M == 2 ? kEdge2[k][0] : kEdge3[k][0], ed.b[k] = h2.M == 2 ? kEdge2[k][1] : kEdge3[k][1];
+    for (int k = 0; k < nb2 - nv; ++k) {
+        const int* e = h2.M == 1 ? kEdge1[k] : h2.M == 2 ? kEdge2[k] : kEdge3[k];
+        ed.a[k] = e[0], ed.b[k] = e[1];
+    }
     HIPCHK(c, m.pa.alloc((size_t)n2));
     HIPCHK(c, m.pb.alloc((size_t)n2));
     HIPCHK(c, bnd1.alloc((size_t)n1));

@@ -130,7 +130,7 @@ int ensure_host(fdapde_ctx* c, int what) {
 int adopt_dev_space(fdapde_ctx* c, DevSpace& s) {
     const HostSpace& hs = c->hs;
     const size_t nd = (size_t)hs.n_dofs, nc = (size_t)hs.n_cells, nnz = (size_t)hs.nnz, nv = (size_t)hs.M + 1, nb = (size_t)hs.nb;
-    adopt(c->cverts, s.cverts, nc * nv), adopt(c->cdofs, s.cdofs, nc * nb), adopt(c->vcoords, s.vcoords, (size_t)hs.n_nodes * (hs.N == 2 ? 2 : 4));
+    adopt(c->cverts, s.cverts, nc * nv), adopt(c->cdofs, s.cdofs, nc * nb), adopt(c->vcoords, s.vcoords, (size_t)hs.n_nodes * (hs.N <= 2 ? 2 : 4));
     adopt(c->adj, s.adj, (size_t)s.n_adj), adopt(c->slotw, s.slotw, (size_t)s.n_adj * hs.nbw), adopt(c->sl_off, s.sl_off, (size_t)s.n_slices + 1);
     if (s.dealt) adopt(c->lane_row, s.lane_row, (size_t)s.n_blk * kAsmBlock);
     else c->lane_row.release();
@@ -428,6 +428,9 @@ int e_topology_build(fdapde_ctx* c, int64_t* n_facets, int64_t* n_edges) {
     if (int rc = need_device(c)) return rc;
     const HostSpace& hs = c->hs;
     if (hs.n_cells < 1) return fail(c, FDAPDE_ENOTINIT, "call fdapde_mesh_upload first");
+    if (hs.M == 1)
+        return fail(c, FDAPDE_EUNSUPPORTED, "fdapde_topology_build on a 1-D mesh (Triangulation<1,N>): the reference's 1-D neighbour structures differ in kind "
+                                            "(an n_cells x 2 matrix for intervals, a sparse cell-cell matrix for networks) and are not built; assembly does not need them");
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->topo_ready) {
         preload_wait(3);

@@ -248,7 +248,8 @@ hvec<int32_t> morton_order(int N, int64_t n, const double* pts_colmajor, int bit
                 q[d] = (uint64_t)std::llround(std::min(1.0, std::max(0.0, w)) * span);
             }
             key[(size_t)i] = N == 3 ? (spread3(q[0]) | spread3(q[1]) << 1 | spread3(q[2]) << 2)
-                                    : (spread2(q[0]) | spread2(q[1]) << 1);
+                           : N == 2 ? (spread2(q[0]) | spread2(q[1]) << 1)
+                                    : q[0];   // (N = 1: the quantised coordinate itself)
         }
     });
     radix_sort_pairs(key, idx);
@@ -399,9 +400,11 @@ int enumerate_edges(HostSpace& hs, hvec<int32_t>& cell_edge /* n_cells x (3|6), 
 int host_set_mesh(HostSpace& hs, int M, int N, int64_t n_nodes, const double* nodes, int64_t n_cells,
                   const int32_t* cells, const uint8_t* bnd, std::string& err) {
     // Triangulation<2,3>: triangles of a surface in R^3.  Topology, DOF numbering and every index structure below depend on the connectivity (M) only;
-    // coordinates (DOF coordinates, locality keys, barycentres) are N-vectors throughout
-    if (!((M == 2 && N == 2) || (M == 2 && N == 3) || (M == 3 && N == 3))) {
-        err = "only Triangulation<2,2>, Triangulation<2,3> (surfaces) and Triangulation<3,3> are on the accelerated path";
+    // coordinates (DOF coordinates, locality keys, barycentres) are N-vectors throughout.  Triangulation<1,1> / <1,2>: segments of an interval or
+    // of a linear network in the plane (cells of 2 node ids)
+    if (!((M == 1 && N == 1) || (M == 1 && N == 2) || (M == 2 && N == 2) || (M == 2 && N == 3) || (M == 3 && N == 3))) {
+        err = "only Triangulation<1,1> (intervals), Triangulation<1,2> (linear networks), Triangulation<2,2>, Triangulation<2,3> (surfaces) and "
+              "Triangulation<3,3> are on the accelerated path";
         return FDAPDE_EUNSUPPORTED;
     }
     if (n_nodes <= 0 || n_cells <= 0 || !nodes || !cells || !bnd) {
@@ -417,6 +420,35 @@ int host_set_mesh(HostSpace& hs, int M, int N, int64_t n_nodes, const double* no
             err = "cell references a node id out of range";
             return FDAPDE_EINVAL;
         }
+    if (M == 1)   // a segment of zero length has no invJ (Jt / |J|^2)
+        for (int64_t c = 0; c < n_cells; ++c) {
+            const int32_t a = cells[2 * c], b = cells[2 * c + 1];
+            bool same = true;
+            for (int d = 0; d < N; ++d) same = same && nodes[(int64_t)d * n_nodes + a] == nodes[(int64_t)d * n_nodes + b];
+            if (same) {
+                err = "segment " + std::to_string(c) + " has zero length (its two nodes coincide): it has no inverse Jacobian";
+                return FDAPDE_EINVAL;
+            }
+        }
+    if (M == 1) {   // a linear network is a simple graph on its nodes: every node on a segment, no segment listed twice
+        std::vector<uint64_t> key((size_t)n_cells);
+        std::vector<uint8_t> used((size_t)n_nodes, 0);
+        for (int64_t c = 0; c < n_cells; ++c) {
+            const uint32_t a = (uint32_t)cells[2 * c], b = (uint32_t)cells[2 * c + 1];
+            key[(size_t)c] = a < b ? (uint64_t)a << 32 | b : (uint64_t)b << 32 | a;
+            used[a] = used[b] = 1;
+        }
+        for (int64_t i = 0; i < n_nodes; ++i)
+            if (!used[(size_t)i]) {
+                err = "node " + std::to_string(i) + " lies on no segment: isolated nodes of a 1-D mesh (Triangulation<1,N>) are not supported";
+                return FDAPDE_EUNSUPPORTED;
+            }
+        std::sort(key.begin(), key.end());
+        if (std::adjacent_find(key.begin(), key.end()) != key.end()) {
+            err = "a segment is listed twice (two cells on the same pair of nodes): repeated segments of a 1-D mesh (Triangulation<1,N>) are not supported";
+            return FDAPDE_EUNSUPPORTED;
+        }
+    }
     hs = HostSpace{};
     hs.M = M, hs.N = N, hs.n_nodes = n_nodes, hs.n_cells = n_cells;
     hs.nodes.resize((size_t)(n_nodes * N)), hs.cells.resize((size_t)(n_cells * (M + 1)));
@@ -467,9 +499,17 @@ int host_build_space(HostSpace& hs, int order, std::string& err, int stop_after)
     if (order == 2) {
         hvec<int32_t> cell_edge;
         std::vector<uint8_t> edge_bnd;
-        int rc = enumerate_edges(hs, cell_edge, edge_bnd, edge_first_cell, err);
+        if (M == 1) {   // a segment is its own (only) edge: DOF row [v0, v1, n_nodes + c]; midpoints are interior DOFs
+            hs.n_edges = nc;
+            edge_first_cell.resize((size_t)nc);
+            parallel_for(nc, [&](int64_t c0, int64_t c1, unsigned) {
+                for (int64_t c = c0; c < c1; ++c) hs.dofs[(size_t)c * nb + 2] = (int32_t)(nn + c), edge_first_cell[(size_t)c] = (int32_t)c;
+            }, 1 << 16);
+            hs.dof_bnd.resize((size_t)(nn + nc), 0);
+        }
+        int rc = M == 1 ? FDAPDE_OK : enumerate_edges(hs, cell_edge, edge_bnd, edge_first_cell, err);
         if (rc) return rc;
-        const int epc = M == 2 ? 3 : 6;
+        const int epc = M == 1 ? 0 : M == 2 ? 3 : 6;
         constexpr int P3[6][2] = {{0, 1}, {0, 2}, {0, 3}, {1, 2}, {1, 3}, {2, 3}};
         parallel_for(nc, [&](int64_t c0, int64_t c1, unsigned) {
             for (int64_t c = c0; c < c1; ++c)
@@ -540,7 +580,7 @@ int host_build_space(HostSpace& hs, int order, std::string& err, int stop_after)
         hs.cell_e2i = invert(hs.cell_i2e);
     }
     phase("  numbering: cells");
-    const int NP = N == 2 ? 2 : 4;
+    const int NP = N <= 2 ? 2 : 4;   // (N = 1 pads to 2 doubles per node as N = 2 does: the second is 0)
     hs.vcoords_i.resize((size_t)nn * NP);
     parallel_for(nn, [&](int64_t b, int64_t e, unsigned) {
         for (int64_t i = b; i < e; ++i)
@@ -653,8 +693,8 @@ int host_build_space(HostSpace& hs, int order, std::string& err, int stop_after)
             std::fclose(fp);
         }
     }
-    if (hs.max_row > 65535 || hs.max_row > kSpmvNnz) {
-        err = "row too long for the uint16 slot map / SpMV row block";
+    if (hs.max_row > 65535) {   // (rows longer than kSpmvNnz -- network hubs -- are SpMV row blocks of their own)
+        err = "row too long for the uint16 slot map";
         return FDAPDE_EUNSUPPORTED;
     }
     hs.diag_i.resize((size_t)nd);
@@ -856,7 +896,7 @@ int host_build_space(HostSpace& hs, int order, std::string& err, int stop_after)
     for (int64_t r = 0; r < nd;) {
         int64_t e = r;
         const int32_t base = hs.rowptr_i[(size_t)r];
-        while (e < nd && hs.rowptr_i[(size_t)e + 1] - base <= kSpmvNnz && e - r < 1024) ++e;
+        while (e < nd && (e == r || hs.rowptr_i[(size_t)e + 1] - base <= kSpmvNnz) && e - r < 1024) ++e;
         hs.rb_row.push_back((int32_t)e);
         r = e;
     }

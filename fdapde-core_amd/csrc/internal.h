@@ -98,7 +98,7 @@ struct HostSpace {
     int n_colours = 0;
     std::vector<int32_t> colour_off;  // n_colours + 1
     std::vector<int32_t> colour_cells;// internal cell ids grouped by colour
-    // ---- SpMV row blocks (CSR-stream): rows [rb_row[b], rb_row[b+1]) hold <= kSpmvNnz nonzeros
+    // ---- SpMV row blocks (CSR-stream): rows [rb_row[b], rb_row[b+1]) hold <= kSpmvNnz nonzeros, or are one longer row
     std::vector<int32_t> rb_row;
     double setup_ms = 0;
 };

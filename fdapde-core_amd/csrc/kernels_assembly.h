@@ -131,7 +131,12 @@ template <int NB, int NBW> __device__ __forceinline__ void add_row_lds(double* a
     for (int j = 0; j < NB; ++j) lds_add(acc_row + ((sw[j >> 1] >> ((j & 1) * 16)) & 0xffffu), val[j]);
 }
 
-// N: the embedding dimension.  N == M: a planar / volume cell; M == 2, N == 3: a triangle of a surface in R^3 (Triangulation<2,3>).
+// local basis functions and quadrature nodes of a cell of dimension M at order R (tables.cpp n_basis_of / n_quadrature_of)
+template <int M, int R> constexpr int kNB = M == 1 ? (R == 1 ? 2 : 3) : M == 2 ? (R == 1 ? 3 : 6) : (R == 1 ? 4 : 10);
+template <int M, int R> constexpr int kNQ = M == 1 ? (R == 1 ? 2 : 3) : M == 2 ? (R == 1 ? 3 : 6) : (R == 1 ? 4 : 5);
+
+// N: the embedding dimension.  N == M: a planar / volume cell (or a segment of an interval); M == 2, N == 3: a triangle of a surface in R^3
+// (Triangulation<2,3>); M == 1, N == 2: a segment of a linear network in the plane (Triangulation<1,2>).
 template <int M, int N = M> struct Geo {
     double invJ[M][N];   // J^{-1}; on a surface the pseudo-inverse (J^T J)^{-1} J^T (2 x 3)
     double measure;      // |det J| / M!; on a surface |(x1 - x0) x (x2 - x0)| / 2
@@ -142,9 +147,24 @@ template <int M, int N = M> struct Geo {
 // Surface cells (M = 2, N = 3, the branch embed_dim != local_dim there): J = [a, b] is 3 x 2, invJ = (J^T J)^{-1} J^T, measure = |a x b| / 2.
 // Every weak form then sees invJ exactly as on a planar cell -- gradients are 3-vectors, K is 3 x 3, b a 3-vector -- and the
 // contractions below pull the cell back to the local dimension once (Gp = invJ K invJ^T is 2 x 2, beta = invJ b a 2-vector).
+// Segments (M = 1, N = 1 or 2): J = x1 - x0 (N x 1), invJ = (J^T J)^{-1} J^T = J^T / |J|^2 (1 x N), measure = |J| (simplex.h:186-192, the
+// local_dim == 1 branch; for N = 1 this is 1 / h and |h|).
 template <int M, int N = M>
 __device__ __forceinline__ void geo_from_vertices(const double* p0, const double* p1, const double* p2, const double* p3, Geo<M, N>& g) {
-    if constexpr (M == 2 && N == 3) {
+    if constexpr (M == 1) {
+        double j[N], l2 = 0;
+#pragma unroll
+        for (int d = 0; d < N; ++d) j[d] = p1[d] - p0[d], l2 += j[d] * j[d];
+        if constexpr (N == 1) {
+            g.invJ[0][0] = 1.0 / j[0];   // (J.inverse(), the reference's embed_dim == local_dim branch)
+        } else {
+            const double il2 = 1.0 / l2;
+#pragma unroll
+            for (int d = 0; d < N; ++d) g.invJ[0][d] = j[d] * il2;
+        }
+        g.measure = N == 1 ? fabs(j[0]) : sqrt(l2);
+        (void)p2, (void)p3;
+    } else if constexpr (M == 2 && N == 3) {
         const double a0 = p1[0] - p0[0], a1 = p1[1] - p0[1], a2 = p1[2] - p0[2];
         const double b0 = p2[0] - p0[0], b1 = p2[1] - p0[1], b2 = p2[2] - p0[2];
         const double gaa = a0 * a0 + a1 * a1 + a2 * a2, gab = a0 * b0 + a1 * b1 + a2 * b2, gbb = b0 * b0 + b1 * b1 + b2 * b2;
@@ -180,7 +200,12 @@ __device__ __forceinline__ void geo_from_vertices(const double* p0, const double
     }
 }
 template <int M, int N = M> __device__ __forceinline__ void cell_geometry(const AsmArgs& a, int cell, Geo<M, N>& g) {
-    if constexpr (M == 2 && N == 3) {   // (the coordinate table of a 3-D embedding is padded to 4 doubles per node)
+    if constexpr (M == 1) {   // (N = 1 and N = 2 both keep 2 doubles per node)
+        const int32_t* cv = a.cverts + (int64_t)cell * 2;
+        const double2 x0 = *reinterpret_cast<const double2*>(a.vcoords + (int64_t)cv[0] * 2);
+        const double2 x1 = *reinterpret_cast<const double2*>(a.vcoords + (int64_t)cv[1] * 2);
+        geo_from_vertices<1, N>(&x0.x, &x1.x, nullptr, nullptr, g);
+    } else if constexpr (M == 2 && N == 3) {   // (the coordinate table of a 3-D embedding is padded to 4 doubles per node)
         const int32_t* cv = a.cverts + (int64_t)cell * 3;
         const double4 x0 = *reinterpret_cast<const double4*>(a.vcoords + (int64_t)cv[0] * 4);
         const double4 x1 = *reinterpret_cast<const double4*>(a.vcoords + (int64_t)cv[1] * 4);
@@ -294,8 +319,8 @@ __device__ __forceinline__ double element_row(const AsmArgs& a, const DevOp& op,
                                               int64_t fcell = -1 /* >= 0: a.fq holds load coefficients per visit ... */,
                                               double fcoef = 0.0 /* ... and this is the visit's, loaded ahead by the caller */,
                                               int64_t frow = -1 /* >= 0: row group of the cell's samples in a.fq (block-cell order) */) {
-    constexpr int NB = (M == 2) ? (R == 1 ? 3 : 6) : (R == 1 ? 4 : 10);
-    constexpr int NQ = (M == 2) ? (R == 1 ? 3 : 6) : (R == 1 ? 4 : 5);
+    constexpr int NB = kNB<M, R>;
+    constexpr int NQ = kNQ<M, R>;
     const int64_t qrow0 = (int64_t)NQ * cell;                                 // rows of space-varying coefficient data
     const int64_t frow0 = frow >= 0 ? (int64_t)NQ * frow : qrow0;             // rows of the forcing samples
     double fsum = 0;
@@ -611,9 +636,9 @@ __device__ __forceinline__ const DevTables* stage_tables(const DevTables* gsrc, 
 // N: embedding dimension (3 for the triangles of a surface, M otherwise): it sets the staged coordinates and the cell geometry only.
 template <int M, int R, int OPK, int MASS2 = 0, int N = M>
 static __global__ __launch_bounds__(kAsmBlock) void k_assemble_rows(AsmArgs a, DevOp op) {
-    constexpr int NB = (M == 2) ? (R == 1 ? 3 : 6) : (R == 1 ? 4 : 10);
+    constexpr int NB = kNB<M, R>;
     constexpr int NBW = (NB * 2 + 3) / 4;
-    constexpr int NP = N == 2 ? 2 : 3;   // doubles per staged vertex in LDS (unpadded: C3 blocks then fit three to a CU, not two)
+    constexpr int NP = N <= 2 ? 2 : 3;   // doubles per staged vertex in LDS (unpadded: C3 blocks then fit three to a CU, not two)
     extern __shared__ double lds[];
     // XCD-aware block order: workgroups are dealt round-robin to the 8 XCDs (own L2 each), so workgroup b serves block
     // (b % 8) * band + b / 8 -- an XCD walks a contiguous range of blocks, and what neighbouring blocks share (vertex coordinates
@@ -652,7 +677,7 @@ static __global__ __launch_bounds__(kAsmBlock) void k_assemble_rows(AsmArgs a, D
     const int64_t bn0 = a.bn_off[blk], nbn = a.bn_off[blk + 1] - bn0;
     for (int i = threadIdx.x; i < nbn; i += kAsmBlock) {
         const int64_t node = a.bn_node[bn0 + i];
-        if constexpr (N == 2) {
+        if constexpr (N <= 2) {
             *reinterpret_cast<double2*>(xyz + i * 2) = *reinterpret_cast<const double2*>(a.vcoords + node * 2);
         } else {
             const double4 v = *reinterpret_cast<const double4*>(a.vcoords + node * 4);   // global copy stays padded to 32 B
@@ -844,9 +869,9 @@ static __global__ __launch_bounds__(kAsmBlock) void k_assemble_rows(AsmArgs a, D
 constexpr int kItemsMaxVisits = 64;   // visit lists longer than this keep the row-walking kernel (the host checks)
 template <int M, int R, int OPK, int MASS2, int THREADS, int N = M>
 static __global__ __launch_bounds__(THREADS) void k_assemble_items(AsmArgs a, DevOp op) {
-    constexpr int NB = (M == 2) ? (R == 1 ? 3 : 6) : (R == 1 ? 4 : 10);
+    constexpr int NB = kNB<M, R>;
     constexpr int NBW = (NB * 2 + 3) / 4;
-    constexpr int NP = N == 2 ? 2 : 3;
+    constexpr int NP = N <= 2 ? 2 : 3;
     constexpr int NW = THREADS / 64, RW = kAsmBlock / NW;   // wavefronts; rows (lane positions) a wavefront owns: w, w + NW, w + 2 NW, ...
     static_assert(RW <= 64 && RW * NW == kAsmBlock, "a wavefront owns at most 64 rows");
     extern __shared__ double lds[];
@@ -882,7 +907,7 @@ static __global__ __launch_bounds__(THREADS) void k_assemble_items(AsmArgs a, De
     const int64_t bn0 = a.bn_off[blk], nbn = a.bn_off[blk + 1] - bn0;
     for (int i = tid; i < nbn; i += THREADS) {
         const int64_t node = a.bn_node[bn0 + i];
-        if constexpr (N == 2) {
+        if constexpr (N <= 2) {
             *reinterpret_cast<double2*>(xyz + i * 2) = *reinterpret_cast<const double2*>(a.vcoords + node * 2);
         } else {
             const double4 v = *reinterpret_cast<const double4*>(a.vcoords + node * 4);
@@ -1102,7 +1127,7 @@ static __global__ __launch_bounds__(512) void k_visit_load_coeffs(int64_t n_slic
 // ---------------------------------------------------------------------------------------------------------------
 template <int M, int R, bool ATOMIC>
 static __global__ __launch_bounds__(256) void k_assemble_scatter(AsmArgs a, DevOp op, const int32_t* cell_list, int64_t n_list) {
-    constexpr int NB = (M == 2) ? (R == 1 ? 3 : 6) : (R == 1 ? 4 : 10);
+    constexpr int NB = kNB<M, R>;
     extern __shared__ double lds[];
     const DevTables* tb = stage_tables(a.tables, lds);
     __syncthreads();
@@ -1148,7 +1173,7 @@ static __global__ __launch_bounds__(256) void k_assemble_scatter(AsmArgs a, DevO
 template <int M, int R, int OPK>
 static __global__ __launch_bounds__(256) void k_assemble_part(AsmArgs a, DevOp op, const int32_t* cell_list, const int32_t* colour_off,
                                                         int max_colours, const uint8_t* dof_shared, const int32_t* slot_map) {
-    constexpr int NB = (M == 2) ? (R == 1 ? 3 : 6) : (R == 1 ? 4 : 10);
+    constexpr int NB = kNB<M, R>;
     extern __shared__ double lds[];
     const DevTables* tb = stage_tables(a.tables, lds);
     const DevRefTensors* rt = nullptr;
@@ -1192,8 +1217,8 @@ static __global__ __launch_bounds__(256) void k_assemble_part(AsmArgs a, DevOp o
 template <int M, int R>
 static __global__ __launch_bounds__(256) void k_assemble_wave(AsmArgs a, DevOp op, const int32_t* cell_list, const int32_t* slot_map,
                                                         int64_t n_list) {
-    constexpr int NB = (M == 2) ? (R == 1 ? 3 : 6) : (R == 1 ? 4 : 10);
-    constexpr int NQ = (M == 2) ? (R == 1 ? 3 : 6) : (R == 1 ? 4 : 5);
+    constexpr int NB = kNB<M, R>;
+    constexpr int NQ = kNQ<M, R>;
     constexpr int NQP = NQ <= 4 ? 4 : 8, PP = 64 / NQP;   // node lanes per pair (a power of two), pairs per pass
     extern __shared__ double lds[];
     const DevTables* tb = stage_tables(a.tables, lds);
@@ -1232,7 +1257,7 @@ static __global__ void k_quadrature_nodes(AsmArgs a, const int32_t* cell_i2e, in
     if (idx >= a.n_cells * nq) return;
     const int64_t ci = idx / nq;
     const int q = (int)(idx - ci * nq);
-    constexpr int NP = N == 2 ? 2 : 4;
+    constexpr int NP = N <= 2 ? 2 : 4;
     const int32_t* cv = a.cverts + ci * (M + 1);
     const double* x0 = a.vcoords + (int64_t)cv[0] * NP;
     const int64_t rows = a.n_cells * nq;
@@ -1260,7 +1285,9 @@ template <int M, int R> __device__ __forceinline__ void eval_ref_basis(const dou
     } else {
 #pragma unroll
         for (int i = 0; i <= M; ++i) out[i] = lam[i] * (2.0 * lam[i] - 1.0);
-        if constexpr (M == 2) {
+        if constexpr (M == 1) {   // ReferenceElement<1,2> node 2 = the midpoint
+            out[2] = 4.0 * lam[0] * lam[1];
+        } else if constexpr (M == 2) {
             out[3] = 4.0 * lam[0] * lam[1], out[4] = 4.0 * lam[0] * lam[2], out[5] = 4.0 * lam[1] * lam[2];
         } else {   // ReferenceElement<3,2> nodes 4..9 = m12, m02, m01, m13, m23, m03
             out[4] = 4.0 * lam[1] * lam[2], out[5] = 4.0 * lam[0] * lam[2], out[6] = 4.0 * lam[0] * lam[1];
@@ -1272,35 +1299,58 @@ template <int M, int R> __device__ __forceinline__ void eval_ref_basis(const dou
 // (geometry/tree_search.h:73-90) done through a uniform bin grid: one lane per location scans the cells registered in its
 // bin and takes the first one whose barycentric coordinates are all >= -tol (Simplex::contains, geometry/simplex.h:118-131).
 // cell_out: reference cell id or -1; values: n_basis basis values psi_h(invJ (p - x0)) per location.
-template <int M, int R>
-static __global__ void k_eval_pointwise(AsmArgs a, int64_t n_locs, const double* locs /*col-major n_locs x M*/, const double* lo,
+// Segments (M = 1, the bins span the N-dimensional bounding box): p is on segment [x0, x1] when its distance to the segment's line is at most
+// tol * max(1, |x1 - x0|) and both barycentric coordinates xi = invJ (p - x0), 1 - xi are >= -tol -- the 2-D rule's tolerance,
+// not the reference's machine epsilon.  The segment of lowest reference id that contains p wins (at a junction: the lowest id meeting there).
+template <int M, int R, int N = M>
+static __global__ void k_eval_pointwise(AsmArgs a, int64_t n_locs, const double* locs /*col-major n_locs x N*/, const double* lo,
                                  const double* inv_h, const int32_t* dims, const int32_t* bin_ptr, const int32_t* bin_cells,
                                  const int32_t* cell_i2e, double tol, int32_t* cell_out, double* values) {
-    constexpr int NB = (M == 2) ? (R == 1 ? 3 : 6) : (R == 1 ? 4 : 10);
-    constexpr int NP = M == 2 ? 2 : 4;
+    constexpr int NB = kNB<M, R>;
+    constexpr int NP = N <= 2 ? 2 : 4;
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_locs) return;
-    double p[M];
+    double p[N];
     int64_t bin = 0;
     bool inside_box = true;
 #pragma unroll
-    for (int d = M - 1; d >= 0; --d) {
+    for (int d = N - 1; d >= 0; --d) {
         p[d] = locs[(int64_t)d * n_locs + i];
         const double t = (p[d] - lo[d]) * inv_h[d];
         int b = (int)floor(t);
         if (b == dims[d] && t <= dims[d] + 1e-9) b = dims[d] - 1;   // points on the upper face of the bounding box
+        if constexpr (M == 1) {
+            if (b == -1 && t >= -1e-9) b = 0;   // ... and, on segments, on the lower face (within the cells' own 1e-9 bin slack)
+        }
         inside_box &= b >= 0 && b < dims[d];
         bin = bin * dims[d] + (b < 0 ? 0 : (b >= dims[d] ? dims[d] - 1 : b));
     }
     int found = -1;
     double xi[M];
     if (inside_box) {
-        for (int32_t k = bin_ptr[bin]; k < bin_ptr[bin + 1] && found < 0; ++k) {
+        for (int32_t k = bin_ptr[bin]; k < bin_ptr[bin + 1] && (M == 1 || found < 0); ++k) {
             const int32_t cell = bin_cells[k];
             const int32_t* cv = a.cverts + (int64_t)cell * (M + 1);
             const double* x0 = a.vcoords + (int64_t)cv[0] * NP;
-            Geo<M> g;
-            if constexpr (M == 2)
+            Geo<M, N> g;
+            if constexpr (M == 1) {
+                const double* x1 = a.vcoords + (int64_t)cv[1] * NP;
+                geo_from_vertices<1, N>(x0, x1, nullptr, nullptr, g);
+                double t = 0;
+#pragma unroll
+                for (int c = 0; c < N; ++c) t += g.invJ[0][c] * (p[c] - x0[c]);
+                double dist2 = 0;
+#pragma unroll
+                for (int c = 0; c < N; ++c) {
+                    const double r = (p[c] - x0[c]) - t * (x1[c] - x0[c]);
+                    dist2 += r * r;
+                }
+                const double dtol = tol * fmax(1.0, g.measure);
+                // (every segment of the bin is looked at: the lowest REFERENCE id wins, and the bin lists are in internal order)
+                if ((N == 1 || sqrt(dist2) <= dtol) && t >= -tol && 1.0 - t >= -tol && (found < 0 || cell_i2e[cell] < cell_i2e[found]))
+                    found = cell, xi[0] = t;
+                continue;
+            } else if constexpr (M == 2)
                 geo_from_vertices<2>(x0, a.vcoords + (int64_t)cv[1] * NP, a.vcoords + (int64_t)cv[2] * NP, nullptr, g);
             else
                 geo_from_vertices<3>(x0, a.vcoords + (int64_t)cv[1] * NP, a.vcoords + (int64_t)cv[2] * NP,

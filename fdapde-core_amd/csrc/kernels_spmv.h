@@ -12,7 +12,7 @@
 namespace fdapde_hip {
 
 // ---------------------------------------------------------------------------------------------------------------
-// CSR SpMV, "stream" form: a workgroup takes a row block (consecutive rows, <= kSpmvNnz nonzeros), streams its
+// CSR SpMV, "stream" form: a workgroup takes a row block (consecutive rows, <= kSpmvNnz nonzeros, or one longer row), streams its
 // contiguous val/colidx range with unit stride, multiplies by the gathered x[col] into LDS, then one lane per row
 // adds up that row's products (ascending column order, like the scalar oracle).  Fused: y = A x and the partial of
 // dot(w, y) with w = x (CG's p.Ap) or w = a second vector (BiCGStab's r0.v, t.s) and of dot(y, y).
@@ -54,6 +54,15 @@ static __global__ __launch_bounds__(256) void k_spmv(SpmvArgs s) {
     for (int rb = band * s.rb_per_band + lb; rb < rb_end; rb += bpx) {
         const int r0 = s.rb_row[rb], r1 = s.rb_row[rb + 1];
         const int k0 = s.rowptr[r0], k1 = s.rowptr[r1];
+        if (k1 - k0 > kSpmvNnz) {   // a row longer than the LDS stage (a network hub) is a block of its own: one lane sums it in column order
+            if (threadIdx.x == 0) {
+                double acc = 0;
+                for (int i = k0; i < k1; ++i) acc += s.vals[i] * s.x[s.colidx[i]];
+                s.y[r0] = acc;
+                if (s.w) d_wy += s.w[r0] * acc, d_yy += spmv_dot2(s, r0, s.w[r0], acc);
+            }
+            continue;   // (workgroup-uniform: the whole workgroup serves this block)
+        }
         int k = k0 + threadIdx.x;
         for (; k + 3 * 256 < k1; k += 4 * 256) {   // 4 independent streams per lane in flight
             const double v0 = s.vals[k], v1 = s.vals[k + 256], v2 = s.vals[k + 512], v3 = s.vals[k + 768];

@@ -17,17 +17,24 @@
 namespace fdapde_hip {
 
 int n_basis_of(int M, int R) {
+    if (M == 1) return R == 1 ? 2 : 3;
     if (M == 2) return R == 1 ? 3 : 6;
     if (M == 3) return R == 1 ? 4 : 10;
     return 0;
 }
 int n_quadrature_of(int M, int R) {
+    if (M == 1) return R == 1 ? 2 : 3;   // standard_fem_quadrature_rule, dim 1: the 2- and 3-point rules
     if (M == 2) return R == 1 ? 3 : 6;
     if (M == 3) return R == 1 ? 4 : 5;
     return 0;
 }
 
 namespace {
+// 1-D rules, IntegratorTable<1,2> and IntegratorTable<1,3> (integrator_tables.h:63-93): Gauss points printed to 15 digits, as there
+const double Q12n[] = {0.211324865405187, 0.788675134594812};
+const double Q12w[] = {0.500000000000000, 0.500000000000000};
+const double Q13n[] = {0.112701665379258, 0.500000000000000, 0.887298334620741};
+const double Q13w[] = {0.277777777777778, 0.444444444444444, 0.277777777777778};
 const double Q23n[] = {0.166666666666667, 0.166666666666667, 0.666666666666667,
                        0.166666666666667, 0.166666666666667, 0.666666666666667};
 const double Q23w[] = {0.333333333333333, 0.333333333333333, 0.333333333333333};
@@ -46,18 +53,22 @@ const double Q35n[] = {0.250000000000000, 0.250000000000000, 0.250000000000000, 
 const double Q35w[] = {-0.80000000000000, 0.450000000000000, 0.450000000000000, 0.450000000000000, 0.450000000000000};
 
 // local edge slot -> its two local vertices, in the reference element's node order
+// 1-D (reference_element.h:41-48): node 2 = (.5), the segment's midpoint                 -> (0,1)
 // 2-D (reference_element.h:60-62): nodes 3,4,5 = (.5,0), (0,.5), (.5,.5)            -> (0,1), (0,2), (1,2)
 // 3-D (reference_element.h:93-96): nodes 4..9 = m12, m02, m01, m13, m23, m03
+const int EDGE1[1][2] = {{0, 1}};
 const int EDGE2[3][2] = {{0, 1}, {0, 2}, {1, 2}};
 const int EDGE3[6][2] = {{1, 2}, {0, 2}, {0, 1}, {1, 3}, {2, 3}, {0, 3}};
 }  // namespace
 
 int build_basis_tables(int M, int R, BasisTables* t) {
     *t = BasisTables{};
-    if ((M != 2 && M != 3) || (R != 1 && R != 2)) return FDAPDE_EUNSUPPORTED;
+    if ((M < 1 || M > 3) || (R != 1 && R != 2)) return FDAPDE_EUNSUPPORTED;
     t->M = M, t->R = R, t->nb = n_basis_of(M, R), t->nq = n_quadrature_of(M, R);
     const double *qn, *qw;
-    if (M == 2)
+    if (M == 1)
+        qn = R == 1 ? Q12n : Q13n, qw = R == 1 ? Q12w : Q13w;
+    else if (M == 2)
         qn = R == 1 ? Q23n : Q26n, qw = R == 1 ? Q23w : Q26w;
     else
         qn = R == 1 ? Q34n : Q35n, qw = R == 1 ? Q34w : Q35w;
@@ -68,7 +79,7 @@ int build_basis_tables(int M, int R, BasisTables* t) {
     for (int v = 0; v < nv; ++v)
         for (int k = 0; k < M; ++k) t->refnodes[v * M + k] = (v == k + 1) ? 1.0 : 0.0;
     for (int s = nv; s < t->nb; ++s) {
-        const int* e = M == 2 ? EDGE2[s - nv] : EDGE3[s - nv];
+        const int* e = M == 1 ? EDGE1[s - nv] : M == 2 ? EDGE2[s - nv] : EDGE3[s - nv];
         for (int k = 0; k < M; ++k) t->refnodes[s * M + k] = 0.5 * (t->refnodes[e[0] * M + k] + t->refnodes[e[1] * M + k]);
     }
     for (int q = 0; q < t->nq; ++q) {
@@ -86,7 +97,7 @@ int build_basis_tables(int M, int R, BasisTables* t) {
                 val = lam[i] * (2.0 * lam[i] - 1.0);
                 for (int k = 0; k < M; ++k) d[k] = (4.0 * lam[i] - 1.0) * dlam[i][k];
             } else {
-                const int* e = M == 2 ? EDGE2[i - nv] : EDGE3[i - nv];
+                const int* e = M == 1 ? EDGE1[i - nv] : M == 2 ? EDGE2[i - nv] : EDGE3[i - nv];
                 val = 4.0 * lam[e[0]] * lam[e[1]];
                 for (int k = 0; k < M; ++k) d[k] = 4.0 * (lam[e[0]] * dlam[e[1]][k] + lam[e[1]] * dlam[e[0]][k]);
             }

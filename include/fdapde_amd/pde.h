@@ -5,7 +5,8 @@
 //
 //   reference (fdaPDE/...)                                           here (namespace fdapde::amd)
 //   ---------------------------------------------------------------  -------------------------------------------------
-//   Triangulation<M,N>(nodes, cells, boundary)  geometry/triangulation.h:49   Triangulation<M,N>: (2,2), (3,3), and (2,3) surfaces
+//   Triangulation<M,N>(nodes, cells, boundary)  geometry/triangulation.h:49   Triangulation<M,N>: (2,2), (3,3), (2,3) surfaces, (1,1) intervals
+//   Triangulation<1,1>(a, b, n), (nodes)        geometry/interval.h:37-62       and (1,2) linear networks
 //   laplacian<FEM>() diffusion<FEM>(K) advection<FEM>(b) reaction<FEM>(c) dt<FEM>()
 //       pde/differential_operators.h:27-52, finite_elements/operators/*.h       same names, tag FEM_HIP
 //   operator algebra  -L, L1 + L2, L1 - L2, c * L  pde/differential_expressions.h:49,95-118   same
@@ -108,34 +109,62 @@ template <int M, int N> class Triangulation {
     // nodes: n_nodes x N; cells: n_cells x (M+1), 0-based node ids; boundary: n_nodes x 1 (0/1)
     Triangulation(const DMatrix<double>& nodes, const DMatrix<int>& cells, const DMatrix<int>& boundary) :
         nodes_(nodes), cells_(cells), boundary_(boundary) {
-        static_assert((M == 2 && N == 2) || (M == 2 && N == 3) || (M == 3 && N == 3),
-                      "only Triangulation<2,2>, Triangulation<2,3> (surfaces in R^3) and Triangulation<3,3> are on the accelerated path");
+        static_assert((M == 1 && N == 1) || (M == 1 && N == 2) || (M == 2 && N == 2) || (M == 2 && N == 3) || (M == 3 && N == 3),
+                      "only Triangulation<1,1> (intervals), Triangulation<1,2> (linear networks), Triangulation<2,2>, Triangulation<2,3> (surfaces in "
+                      "R^3) and Triangulation<3,3> are on the accelerated path");
         if (nodes.cols() != N || cells.cols() != M + 1 || boundary.rows() != nodes.rows())
             throw std::runtime_error("Triangulation: inconsistent matrix shapes");
     }
+    // intervals (geometry/interval.h:37-62): nodes x_0 < ... < x_n, cells (i, i + 1), the first and the last node on the boundary
+    explicit Triangulation(const DVector<double>& nodes)
+        requires(M == 1 && N == 1)
+        : Triangulation(nodes, interval_cells(nodes.rows()), interval_boundary(nodes.rows())) { }
+    // [a, b] split into n subintervals of equal length (LinSpaced(n + 1, a, b))
+    Triangulation(double a, double b, int n)
+        requires(M == 1 && N == 1)
+        : Triangulation(linspaced(a, b, n)) { }
     const DMatrix<double>& nodes() const { return nodes_; }
     const DMatrix<int>& cells() const { return cells_; }
     const DMatrix<int>& boundary_nodes() const { return boundary_; }
     int64_t n_nodes() const { return nodes_.rows(); }
     int64_t n_cells() const { return cells_.rows(); }
     // ---- the rest of the reference constructor (geometry/triangulation.h:143-196, 319-399), built on the device at first use
-    //      (fdapde_topology_build: facets = edges of triangles / faces of tetrahedra in first-seen numbering)
-    const DMatrix<int>& neighbors() const { return topo().neighbors; }       // n_cells x (M+1), -1 = none (triangulation.h:65, 402)
-    const DMatrix<int>& facets() const { return topo().facet_nodes; }        // edges() for triangles, faces() for tetrahedra
-    const DMatrix<int>& facet_to_cells() const { return topo().facet_cells; }
-    const DMatrix<int>& cell_to_facets() const { return topo().cell_facets; }
-    bool is_facet_on_boundary(int64_t id) const { return topo().facet_bnd[(size_t)id] != 0; }
-    int64_t n_facets() const { return topo().facet_nodes.rows(); }
-    int64_t n_edges() const { return M == 2 ? n_facets() : topo().edge_nodes.rows(); }
-    const DMatrix<int>& edges() const { return M == 2 ? topo().facet_nodes : topo().edge_nodes; }
-    bool is_edge_on_boundary(int64_t id) const { return (M == 2 ? topo().facet_bnd : topo().edge_bnd)[(size_t)id] != 0; }
-    const DMatrix<int>& face_to_edges() const { return topo().face_edges; }  // tetrahedra only
+    //      (fdapde_topology_build: facets = edges of triangles / faces of tetrahedra in first-seen numbering).  Not on 1-D meshes: the
+    //      reference's neighbour structures there differ in kind (interval.h, linear_network.h) and are not built -- a compile-time error
+    const DMatrix<int>& neighbors() const requires(M >= 2) { return topo().neighbors; }   // n_cells x (M+1), -1 = none (triangulation.h:65, 402)
+    const DMatrix<int>& facets() const requires(M >= 2) { return topo().facet_nodes; }    // edges() for triangles, faces() for tetrahedra
+    const DMatrix<int>& facet_to_cells() const requires(M >= 2) { return topo().facet_cells; }
+    const DMatrix<int>& cell_to_facets() const requires(M >= 2) { return topo().cell_facets; }
+    bool is_facet_on_boundary(int64_t id) const requires(M >= 2) { return topo().facet_bnd[(size_t)id] != 0; }
+    int64_t n_facets() const requires(M >= 2) { return topo().facet_nodes.rows(); }
+    int64_t n_edges() const requires(M >= 2) { return M == 2 ? n_facets() : topo().edge_nodes.rows(); }
+    const DMatrix<int>& edges() const requires(M >= 2) { return M == 2 ? topo().facet_nodes : topo().edge_nodes; }
+    bool is_edge_on_boundary(int64_t id) const requires(M >= 2) { return (M == 2 ? topo().facet_bnd : topo().edge_bnd)[(size_t)id] != 0; }
+    const DMatrix<int>& face_to_edges() const requires(M >= 2) { return topo().face_edges; }  // tetrahedra only
    private:
+    static DVector<double> linspaced(double a, double b, int n) {
+        if (n < 1) throw std::runtime_error("Triangulation<1,1>(a, b, n): n must be >= 1");
+        DVector<double> x(n + 1, 1);
+        const double step = (b - a) / n;   // (Eigen's LinSpaced: low + i step, the last node exactly b)
+        for (int i = 0; i <= n; ++i) x(i) = i == n ? b : a + i * step;
+        return x;
+    }
+    static DMatrix<int> interval_cells(int64_t n_nodes) {
+        if (n_nodes < 2) throw std::runtime_error("Triangulation<1,1>(nodes): at least two nodes");
+        DMatrix<int> c(n_nodes - 1, 2);
+        for (int64_t i = 0; i + 1 < n_nodes; ++i) c(i, 0) = (int)i, c(i, 1) = (int)(i + 1);
+        return c;
+    }
+    static DMatrix<int> interval_boundary(int64_t n_nodes) {
+        DMatrix<int> bd(n_nodes, 1, 0);
+        if (n_nodes > 0) bd(0) = 1, bd(n_nodes - 1) = 1;
+        return bd;
+    }
     struct Topology {
         DMatrix<int> neighbors, cell_facets, facet_nodes, facet_cells, edge_nodes, face_edges;
         std::vector<uint8_t> facet_bnd, edge_bnd;
     };
-    const Topology& topo() const {
+    const Topology& topo() const requires(M >= 2) {
         if (topo_) return *topo_;
         fdapde_ctx* ctx = nullptr;
         if (fdapde_ctx_create(0, &ctx) != FDAPDE_OK) throw std::runtime_error("Triangulation: no HIP device for the topology tables (there is no CPU fallback)");

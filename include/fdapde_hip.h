@@ -190,7 +190,18 @@ const char *fdapde_status_string(int status);
  * advection.h:55): gradients are 3-vectors, a diffusion tensor is 3 x 3 (9 values per row of a field), an advection vector has 3 components.
  * Surfaces take orders 1 and 2 on a single-device context, the default assembly (FDAPDE_ASSEMBLY_ROWS) and every solver.  FDAPDE_EUNSUPPORTED:
  * fdapde_eval_pointwise (point location would need a projection onto the surface), the assembly variants 1-4, fdapde_partition_build, and
- * a surface in a multi-device context (fdapde_ctx_create_multi).  Every other (M, N) returns FDAPDE_EUNSUPPORTED. */
+ * a surface in a multi-device context (fdapde_ctx_create_multi).
+ * (M, N) = (1, 1): an INTERVAL; (1, 2): a LINEAR NETWORK in the plane (cells of 2 node ids).  Per segment J = x1 - x0, invJ = J^T / |J|^2 (1 / h
+ * for N = 1), measure |J| (simplex.h:186-193); quadrature IntegratorTable<1,2> / <1,3> as printed in the reference (15 digits).  A diffusion
+ * tensor is N x N, an advection vector has N components.  DOFs: order 1 the nodes; order 2 the row of cell c is [v0, v1, n_nodes + c] (the
+ * reference has no edge iterator on Triangulation<1,*>: the segment is taken as its own edge), the midpoint at J 0.5 + x0, boundary DOFs =
+ * boundary nodes.  Coordinates sit on the device as 2 doubles per node for N = 1 and N = 2 (the second 0 for an interval), 4 for N = 3.
+ * fdapde_eval_pointwise on a segment: distance to its line <= 1e-12 max(1, |x1 - x0|) and barycentric coordinates >= -1e-12 (the tolerance
+ * of the 2-D rule, not the reference's machine epsilon); the lowest reference cell id containing the point wins, -1 if none.  (A point within
+ * the rule but more than 1e-9 of a bin width outside the bins its segment was entered in -- bins narrower than about 1e-3 -- may get -1.)
+ * 1-D meshes take orders 1 and 2 on a single-device context, FDAPDE_ASSEMBLY_ROWS and every solver (PMG prolongs a midpoint as the mean of
+ * its two ends); junction rows up to 65 535 entries.  FDAPDE_EINVAL: a zero-length segment.  FDAPDE_EUNSUPPORTED: a node on no segment, a segment listed twice, fdapde_topology_build,
+ * the assembly variants 1-4, fdapde_partition_build, a multi-device context.  Every other (M, N) returns FDAPDE_EUNSUPPORTED. */
 int fdapde_mesh_upload(fdapde_ctx *ctx, int M, int N, int64_t n_nodes, const double *nodes_colmajor, int64_t n_cells,
                        const int32_t *cells_rowmajor, const uint8_t *boundary_nodes);
 
