@@ -66,7 +66,7 @@ int dense_build_csr(fdapde_ctx* c, int64_t n, const int32_t* rowptr, const int32
     hipStream_t st = c->stream;
     D.ready = false, D.failed = true, D.n = n, D.use_bnd = use_bnd, D.A = A, D.rowptr = rowptr, D.colidx = colidx, D.bnd = bnd;
     const auto t0 = std::chrono::steady_clock::now();
-    DBuf<double> S;
+    DBuf<double> S, rs;
     DBuf<int32_t> perm, status;
     DBuf<unsigned long long> cand, worst;
     int G = (int)std::max<int64_t>(1, std::min<int64_t>(c->n_cu > 0 ? c->n_cu : 64, (n + 7) / 8));   // (pivot by pivot: row i lives with workgroup i mod G)
@@ -90,13 +90,14 @@ int dense_build_csr(fdapde_ctx* c, int64_t n, const int32_t* rowptr, const int32
     HIPCHK(c, S.alloc((size_t)n * (size_t)ld));
     HIPCHK(c, D.X.alloc((size_t)n * n));
     HIPCHK(c, perm.alloc((size_t)n));
+    HIPCHK(c, rs.alloc((size_t)n));
     HIPCHK(c, cand.alloc(2 * (size_t)G));
     HIPCHK(c, status.alloc(4));
     HIPCHK(c, worst.alloc(2));
     HIPCHK(c, hipMemsetAsync(cand.p, 0, 2 * (size_t)G * sizeof(unsigned long long), st));
     HIPCHK(c, hipMemsetAsync(status.p, 0, 4 * sizeof(int32_t), st));
     HIPCHK(c, hipMemsetAsync(worst.p, 0, 2 * sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(k_dense_fill, dim3((unsigned)n), dim3(256), 0, st, n, ld, rowptr, colidx, A, bnd, use_bnd, S.p);
+    hipLaunchKernelGGL(k_dense_fill, dim3((unsigned)n), dim3(256), 0, st, n, ld, rowptr, colidx, A, bnd, use_bnd, S.p, rs.p);
     const double* result = S.p;
     if (blocked) {
         HIPCHK(c, S1.alloc((size_t)n * (size_t)ld));
@@ -146,8 +147,8 @@ int dense_build_csr(fdapde_ctx* c, int64_t n, const int32_t* rowptr, const int32
         HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dense_invert), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(k_dense_invert, dim3((unsigned)G), dim3(kDenseT), lds, st, a);
     }
-    hipLaunchKernelGGL(k_dense_unpermute, dim3((unsigned)n), dim3(256), 0, st, n, ld, result, perm.p, D.X.p);
-    hipLaunchKernelGGL(k_dense_check, dim3((unsigned)n), dim3(256), 0, st, n, rowptr, colidx, A, bnd, use_bnd, D.X.p, worst.p);
+    hipLaunchKernelGGL(k_dense_unpermute, dim3((unsigned)n), dim3(256), 0, st, n, ld, result, perm.p, rs.p, D.X.p);
+    hipLaunchKernelGGL(k_dense_check, dim3((unsigned)n), dim3(256), 0, st, n, rowptr, colidx, A, bnd, use_bnd, D.X.p, rs.p, worst.p);
     HIPCHK(c, hipGetLastError());
     int32_t h_status[4] = {0, 0, 0, 0};
     unsigned long long h_worst = 0;

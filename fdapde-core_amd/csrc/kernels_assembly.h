@@ -1299,9 +1299,15 @@ template <int M, int R> __device__ __forceinline__ void eval_ref_basis(const dou
 // (geometry/tree_search.h:73-90) done through a uniform bin grid: one lane per location scans the cells registered in its
 // bin and takes the first one whose barycentric coordinates are all >= -tol (Simplex::contains, geometry/simplex.h:118-131).
 // cell_out: reference cell id or -1; values: n_basis basis values psi_h(invJ (p - x0)) per location.
+// The tolerance allows for the rounding of the coordinates that are subtracted: a location given in float64 is only known to u |p| (u = 2^-53),
+// which is worth u max(|p|, |x_i|) ||invJ||_inf in barycentric units, so a cell is accepted from -(tol + 4 u max(|p|, |x_i|) ||invJ||_inf) on
+// (|.| the largest absolute coordinate of p and of the cell's vertices, ||invJ||_inf the largest absolute row sum over the M + 1 barycentric
+// gradients).  With coordinates of O(1) and cells no smaller than 1e-3 the second term is below tol; on a mesh shifted by 1e6 it is what lets
+// a point of a shared edge be found by at least one of the two neighbours.
 // Segments (M = 1, the bins span the N-dimensional bounding box): p is on segment [x0, x1] when its distance to the segment's line is at most
-// tol * max(1, |x1 - x0|) and both barycentric coordinates xi = invJ (p - x0), 1 - xi are >= -tol -- the 2-D rule's tolerance,
-// not the reference's machine epsilon.  The segment of lowest reference id that contains p wins (at a junction: the lowest id meeting there).
+// tol * max(1, |x1 - x0|) + 4 u max(|p|, |x_i|) and both barycentric coordinates xi = invJ (p - x0), 1 - xi are >= -(tol + 4 u max(|p|, |x_i|)
+// ||invJ||_1) -- the 2-D rule's tolerance, not the reference's machine epsilon.  The segment of lowest reference id that
+// contains p wins (at a junction: the lowest id meeting there).
 template <int M, int R, int N = M>
 static __global__ void k_eval_pointwise(AsmArgs a, int64_t n_locs, const double* locs /*col-major n_locs x N*/, const double* lo,
                                  const double* inv_h, const int32_t* dims, const int32_t* bin_ptr, const int32_t* bin_cells,
@@ -1327,6 +1333,10 @@ static __global__ void k_eval_pointwise(AsmArgs a, int64_t n_locs, const double*
     }
     int found = -1;
     double xi[M];
+    constexpr double kCoordSlack = 4.0 * 1.1102230246251565e-16;   // 4 u: what the rounding of p and of the vertices is worth, per unit of |coordinate|
+    double pmax = 0;
+#pragma unroll
+    for (int d = 0; d < N; ++d) pmax = fmax(pmax, fabs(p[d]));
     if (inside_box) {
         for (int32_t k = bin_ptr[bin]; k < bin_ptr[bin + 1] && (M == 1 || found < 0); ++k) {
             const int32_t cell = bin_cells[k];
@@ -1345,9 +1355,13 @@ static __global__ void k_eval_pointwise(AsmArgs a, int64_t n_locs, const double*
                     const double r = (p[c] - x0[c]) - t * (x1[c] - x0[c]);
                     dist2 += r * r;
                 }
-                const double dtol = tol * fmax(1.0, g.measure);
+                double cmax = pmax, jn = 0;
+#pragma unroll
+                for (int c = 0; c < N; ++c) cmax = fmax(cmax, fmax(fabs(x0[c]), fabs(x1[c]))), jn += fabs(g.invJ[0][c]);
+                const double dtol = tol * fmax(1.0, g.measure) + kCoordSlack * cmax;
+                const double btol = tol + kCoordSlack * cmax * jn;
                 // (every segment of the bin is looked at: the lowest REFERENCE id wins, and the bin lists are in internal order)
-                if ((N == 1 || sqrt(dist2) <= dtol) && t >= -tol && 1.0 - t >= -tol && (found < 0 || cell_i2e[cell] < cell_i2e[found]))
+                if ((N == 1 || sqrt(dist2) <= dtol) && t >= -btol && 1.0 - t >= -btol && (found < 0 || cell_i2e[cell] < cell_i2e[found]))
                     found = cell, xi[0] = t;
                 continue;
             } else if constexpr (M == 2)
@@ -1355,6 +1369,25 @@ static __global__ void k_eval_pointwise(AsmArgs a, int64_t n_locs, const double*
             else
                 geo_from_vertices<3>(x0, a.vcoords + (int64_t)cv[1] * NP, a.vcoords + (int64_t)cv[2] * NP,
                                      a.vcoords + (int64_t)cv[3] * NP, g);
+            double cmax = pmax, jn = 0;
+#pragma unroll
+            for (int v = 0; v <= M; ++v) {
+#pragma unroll
+                for (int c = 0; c < M; ++c) cmax = fmax(cmax, fabs(a.vcoords[(int64_t)cv[v] * NP + c]));
+            }
+#pragma unroll
+            for (int r = 0; r <= M; ++r) {   // (row M: the gradient of lambda_0 = minus the sum of the others)
+                double rs = 0;
+#pragma unroll
+                for (int c = 0; c < M; ++c) {
+                    double e = 0;
+#pragma unroll
+                    for (int k = 0; k < M; ++k) e += (r == M || r == k) ? g.invJ[k][c] : 0.0;
+                    rs += fabs(e);
+                }
+                jn = fmax(jn, rs);
+            }
+            const double btol = tol + kCoordSlack * cmax * jn;
             double z0 = 1.0;
             bool in = true;
 #pragma unroll
@@ -1362,9 +1395,9 @@ static __global__ void k_eval_pointwise(AsmArgs a, int64_t n_locs, const double*
                 double v = 0;
 #pragma unroll
                 for (int c = 0; c < M; ++c) v += g.invJ[r][c] * (p[c] - x0[c]);
-                xi[r] = v, z0 -= v, in &= v >= -tol;
+                xi[r] = v, z0 -= v, in &= v >= -btol;
             }
-            if (in && z0 >= -tol) found = cell;
+            if (in && z0 >= -btol) found = cell;
         }
     }
     cell_out[i] = found >= 0 ? cell_i2e[found] : -1;

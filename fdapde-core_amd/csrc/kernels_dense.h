@@ -40,16 +40,31 @@ constexpr int kDenseMaxRows = 8192; // pivot row in LDS: 64 KB
 typedef __attribute__((address_space(1))) unsigned int dn_u32;
 typedef __attribute__((address_space(1))) unsigned long long dn_u64;
 
-static __global__ void k_dense_fill(int64_t n, int64_t ld, const int32_t* rowptr, const int32_t* colidx, const double* vals, const uint8_t* bnd, int use_bnd, double* D) {
+// Every row is equilibrated by a power of two (exact): rs[i] = 2^-e with 2^e <= max_j |A_ij| < 2^(e+1), D row i = rs[i] A row i.  The inverse of the
+// scaled matrix, its columns scaled by rs (k_dense_unpermute), is the inverse of A; and the residual that decides about refinement and failure
+// (k_dense_check) is that of the scaled system.  Without it both depend on the units of the mesh: a Dirichlet row is a unit vector whatever the
+// units, a stiffness row of a 1-D mesh in micrometres holds entries of 1e8, and max |I - A X| of such a matrix is 1e8 times its rounding.
+static __global__ void k_dense_fill(int64_t n, int64_t ld, const int32_t* rowptr, const int32_t* colidx, const double* vals, const uint8_t* bnd, int use_bnd, double* D,
+                                    double* rs) {
     const int64_t i = blockIdx.x;
     double* row = D + i * ld;
+    __shared__ double red[16];
     for (int64_t j = threadIdx.x; j < n; j += blockDim.x) row[j] = 0.0;
     __syncthreads();
     if (use_bnd && bnd[i]) {
-        if (threadIdx.x == 0) row[i] = 1.0;
+        if (threadIdx.x == 0) row[i] = 1.0, rs[i] = 1.0;
         return;
     }
-    for (int32_t k = rowptr[i] + (int32_t)threadIdx.x; k < rowptr[i + 1]; k += (int32_t)blockDim.x) row[colidx[k]] = vals[k];
+    double mx = 0.0;
+    for (int32_t k = rowptr[i] + (int32_t)threadIdx.x; k < rowptr[i + 1]; k += (int32_t)blockDim.x) mx = fmax(mx, fabs(vals[k]));
+    for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    mx = 0.0;
+    for (int w = 0; w < (int)((blockDim.x + 63) >> 6); ++w) mx = fmax(mx, red[w]);
+    const double sc = (mx > 0.0 && isfinite(mx)) ? ldexp(1.0, -max(-1000, min(1000, ilogb(mx)))) : 1.0;   // (a zero or non-finite row stays as it is: the inversion reports it)
+    for (int32_t k = rowptr[i] + (int32_t)threadIdx.x; k < rowptr[i + 1]; k += (int32_t)blockDim.x) row[colidx[k]] = vals[k] * sc;
+    if (threadIdx.x == 0) rs[i] = sc;
 }
 
 struct DenseInvArgs {
@@ -815,17 +830,20 @@ template <int RPT, int NBT, bool MULTI> static __global__ __launch_bounds__(kDen
 }
 
 
-// X[k][perm[j]] = S[perm[k]][j]
-static __global__ void k_dense_unpermute(int64_t n, int64_t ld, const double* S, const int32_t* perm, double* X) {
+// X[k][perm[j]] = S[perm[k]][j] rs[perm[j]]   (the inverse of the row-scaled matrix, its columns scaled back: k_dense_fill)
+static __global__ void k_dense_unpermute(int64_t n, int64_t ld, const double* S, const int32_t* perm, const double* rs, double* X) {
     const int64_t k = blockIdx.x;
     const double* src = S + (int64_t)perm[k] * ld;
     double* dst = X + k * n;
-    for (int64_t j = threadIdx.x; j < n; j += blockDim.x) dst[perm[j]] = src[j];
+    for (int64_t j = threadIdx.x; j < n; j += blockDim.x) {
+        const int32_t c = perm[j];
+        dst[c] = src[j] * rs[c];
+    }
 }
 
-// out[0] = bits of max |delta_ic - sum_t A[i][t] X[t][c]| (A: the same rows k_dense_fill wrote)
+// out[0] = bits of max |delta_ic - sum_t A[i][t] X[t][c]| rs[i] / rs[c]: the residual of the row-scaled system k_dense_fill wrote, (rs A) (X / rs)
 static __global__ void k_dense_check(int64_t n, const int32_t* rowptr, const int32_t* colidx, const double* vals, const uint8_t* bnd, int use_bnd, const double* X,
-                                     unsigned long long* out) {
+                                     const double* rs, unsigned long long* out) {
     const int64_t i = blockIdx.x;
     const bool unit = use_bnd && bnd[i];
     double worst = 0.0;
@@ -834,7 +852,7 @@ static __global__ void k_dense_check(int64_t n, const int32_t* rowptr, const int
         if (unit) s = X[i * n + c];
         else
             for (int32_t k = rowptr[i]; k < rowptr[i + 1]; ++k) s += vals[k] * X[(int64_t)colidx[k] * n + c];
-        const double e = fabs((c == i ? 1.0 : 0.0) - s);
+        const double e = fabs((c == i ? 1.0 : 0.0) - s) * (rs[i] / rs[c]);
         worst = e > worst || !(e == e) ? (e == e ? e : 1e300) : worst;
     }
     for (int o = 32; o > 0; o >>= 1) worst = fmax(worst, __shfl_xor(worst, o));

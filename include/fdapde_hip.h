@@ -196,8 +196,12 @@ const char *fdapde_status_string(int status);
  * tensor is N x N, an advection vector has N components.  DOFs: order 1 the nodes; order 2 the row of cell c is [v0, v1, n_nodes + c] (the
  * reference has no edge iterator on Triangulation<1,*>: the segment is taken as its own edge), the midpoint at J 0.5 + x0, boundary DOFs =
  * boundary nodes.  Coordinates sit on the device as 2 doubles per node for N = 1 and N = 2 (the second 0 for an interval), 4 for N = 3.
- * fdapde_eval_pointwise on a segment: distance to its line <= 1e-12 max(1, |x1 - x0|) and barycentric coordinates >= -1e-12 (the tolerance
- * of the 2-D rule, not the reference's machine epsilon); the lowest reference cell id containing the point wins, -1 if none.  (A point within
+ * fdapde_eval_pointwise on a segment: distance to its line <= 1e-12 max(1, |x1 - x0|) + rho_x and barycentric coordinates >= -(1e-12 + rho)
+ * (the tolerance of the 2-D rule, not the reference's machine epsilon), where rho_x = 4 u max(|p|, |x0|, |x1|) (u = 2^-53, |.| the largest absolute
+ * coordinate) is what the float64 rounding of the location and of the nodes is worth in length units and rho = rho_x ||invJ||_1 in barycentric
+ * units: negligible next to 1e-12 for coordinates of O(1), and what keeps a point of a segment found on a network given in projected metres.
+ * Triangles and tetrahedra use the same rule: all barycentric coordinates >= -(1e-12 + 4 u max(|p|, |x_i|) ||invJ||_inf), the norm taken
+ * over the M + 1 barycentric gradients.  The lowest reference cell id containing the point wins on segments, -1 if none.  (A point within
  * the rule but more than 1e-9 of a bin width outside the bins its segment was entered in -- bins narrower than about 1e-3 -- may get -1.)
  * 1-D meshes take orders 1 and 2 on a single-device context, FDAPDE_ASSEMBLY_ROWS and every solver (PMG prolongs a midpoint as the mean of
  * its two ends); junction rows up to 65 535 entries.  FDAPDE_EINVAL: a zero-length segment.  FDAPDE_EUNSUPPORTED: a node on no segment, a segment listed twice, fdapde_topology_build,
