@@ -47,7 +47,7 @@ SYMBOLS = [
     "fdapde_info_get", "fdapde_spmv", "fdapde_bench_spmv", "fdapde_tune", "fdapde_stream", "fdapde_synchronize",
     "fdapde_comm_unique_id", "fdapde_comm_init", "fdapde_halo_setup", "fdapde_solve_parabolic",
     "fdapde_lin_compute", "fdapde_lin_solve", "fdapde_eval_pointwise", "fdapde_cell_integrals", "fdapde_comm_init_callback", "fdapde_comm_set_exchange_callback", "fdapde_halo_setup_peers",
-    "fdapde_solver_layout", "fdapde_topology_build", "fdapde_topology_get", "fdapde_comm_allreduce", "fdapde_comm_library", "fdapde_solver_layout_kind", "fdapde_rowdist_setup", "fdapde_ctx_clone", "fdapde_comm_count",
+    "fdapde_solver_layout", "fdapde_topology_build", "fdapde_topology_get", "fdapde_comm_allreduce", "fdapde_comm_library", "fdapde_solver_layout_kind", "fdapde_solver_layout_partition", "fdapde_rowdist_setup", "fdapde_ctx_clone", "fdapde_comm_count",
     "fdapde_ctx_create_multi", "fdapde_ctx_devices", "fdapde_partition_build", "fdapde_partition_sizes", "fdapde_partition_get", "fdapde_partition_whole",
     "fdapde_partition_peers",
 ]
@@ -487,6 +487,12 @@ class Context:
         k, sy, g, r = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
         self._check(self.lib.fdapde_solver_layout_kind(self._ctx, 1 if with_dirichlet else 0, C.byref(k), C.byref(sy), C.byref(g), C.byref(r)))
         return dict(kind=k.value, sym=sy.value, workgroups=g.value, rows_per_thread=r.value)
+
+    def solver_layout_partition(self, with_dirichlet=True):
+        """0: the single launch's blocks are chunks of the internal order, 1: cut by coordinate bisection, -1: no single-launch layout"""
+        p = C.c_int32()
+        self._check(self.lib.fdapde_solver_layout_partition(self._ctx, 1 if with_dirichlet else 0, C.byref(p)))
+        return p.value
 
     # ---- multi-GPU
     @staticmethod

@@ -263,6 +263,13 @@ int fdapde_solver_layout_kind(fdapde_ctx* c, int32_t with_dirichlet, int32_t* ki
     if (c->group) return fdapde_engine::g_layout_kind(c, with_dirichlet, kind, symmetric_storage, workgroups, rows_per_thread);
     return fdapde_engine::e_solver_layout_kind(c, with_dirichlet, kind, symmetric_storage, workgroups, rows_per_thread);
 }
+int fdapde_solver_layout_partition(fdapde_ctx* c, int32_t with_dirichlet, int32_t* partition) {
+    int32_t kind = 0;
+    if (int rc = fdapde_solver_layout_kind(c, with_dirichlet, &kind, nullptr, nullptr, nullptr)) return rc;   // (builds the layout if need be)
+    const fdapde_ctx::Persist& ps = c->ps[with_dirichlet ? 1 : 0];
+    if (partition) *partition = (kind == 2 || kind == 3) && ps.ok ? (ps.meta.bisect ? 1 : 0) : -1;
+    return FDAPDE_OK;
+}
 int fdapde_solve(fdapde_ctx* c, const fdapde_options* opt, fdapde_info* info) {
     if (!c) return FDAPDE_EINVAL;
     if (c->group && opt && opt->method == FDAPDE_SOLVER_AMG) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_AMG takes one-GPU contexts, not a multi-device context");
@@ -477,6 +484,10 @@ int fdapde_tune(fdapde_ctx* c, const char* key, int32_t value) {
     else if (k == "persist_direct_spin_us" && value >= 0 && value <= 1000000) c->persist_direct_spin_us = value;
     else if (k == "persist_single_rows" && value >= 0 && value <= 8192) {
         c->persist_single_rows = value;
+        for (auto& ps : c->ps) ps.tried = ps.ok = ps.filled = false;
+    }
+    else if (k == "persist_partition" && value >= 0 && value <= 2) {   // 0 chunks of the internal order, 1 coordinate bisection, 2 auto
+        c->persist_partition = value;
         for (auto& ps : c->ps) ps.tried = ps.ok = ps.filled = false;
     }
     else if (k == "persist_late" && (value == 0 || value == 1)) {

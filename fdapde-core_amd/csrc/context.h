@@ -428,6 +428,8 @@ struct fdapde_ctx {
                                              // last kernel (the outcome is read behind a wait of its own; the rest is ordered by the stream)
     int persist_single_rows = 2048;          // knob: systems of up to that many interior rows run as ONE workgroup (no hand-off in the iteration)
     int persist_prefetch = 1;                // knob: entry steps of the next operator application touched during the dot all-gather (streaming forms)
+    int persist_partition = 2;               // knob: blocks of the single-launch layouts: 0 chunks of the internal order, 1 coordinate bisection, 2 auto
+                                             // (bisection where its layout fits like the chunks' and moves fewer bytes per iteration: persist_engine.hip)
     int persist_late = 0;                    // knob: CG layouts with late-import workgroups (host builder) instead of doubled rows per thread
     int persist_plain = 0;                   // the system being prepared is non-symmetric: plain storage, BiCGStab kernel
     int persist_bicg = 1;                    // tuning knob: 0 = non-symmetric systems always take the multi-launch BiCGStab

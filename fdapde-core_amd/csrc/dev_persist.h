@@ -4,6 +4,7 @@
 
 #include <cstdint>
 #include <string>
+#include <vector>
 
 #include "internal.h"
 
@@ -28,6 +29,14 @@ void dev_persist_release(DevPersist* p);
 int dev_build_persist_layout(int64_t nd, int32_t max_row, const int32_t* d_rowptr, const int32_t* d_colidx, const uint8_t* d_bnd, bool use_bnd,
                              int n_wg, int lds_entries, int blocked_rows, const int32_t* block_rows, int sym_mode, bool balance, void* stream, PersistLayout& pl, DevPersist* out,
                              std::string& err);
+
+// The layout on exactly G blocks cut by recursive coordinate bisection (internal.h, host_bisect.cpp) instead of chunks of the internal order.
+// M, N: dimension of the mesh and of its embedding space; d_coords: the DOF coordinates, column-major nd x N, in the reference numbering; d_i2e: internal -> reference DOF id (nullptr: identity).
+// The builder above runs on the system in the partition's numbering; slot_dof and ell_src come back in the real one, so everything that
+// reads the layout sees what it sees for chunks.  perm_out / rows_out (optional): the partition itself, for FDAPDE_SETUP_CHECK.
+int dev_build_persist_layout_bisect(int64_t nd, int32_t max_row, const int32_t* d_rowptr, const int32_t* d_colidx, const uint8_t* d_bnd, bool use_bnd, int M,
+                                    int N, const double* d_coords, const int32_t* d_i2e, int G, int lds_entries, int sym_mode, void* stream, PersistLayout& pl,
+                                    DevPersist* out, std::vector<int32_t>* perm_out, std::vector<int32_t>* rows_out, std::string& err);
 
 void dev_persist_preload();    // loads this unit's code object
 }  // namespace fdapde_hip

@@ -736,6 +736,282 @@ int dev_build_persist_layout(int64_t nd, int32_t max_row, const int32_t* d_rowpt
     return FDAPDE_OK;
 }
 
+// =====================================================================================================================================
+// Blocks by recursive coordinate bisection (host_bisect.cpp has the rule in plain words; internal.h the contract).  Per level ONE stable radix
+// sort of (segment, integer coordinate along the segment's longest axis) keys -- a segmented sort, the segments being contiguous and in
+// order --, ONE scan of the costs in the new order and ONE small kernel that cuts every segment that still holds two or more workgroups.
+// How many workgroups each segment holds does not depend on the data: the host follows that list, the bounds stay on the device.
+// =====================================================================================================================================
+namespace {
+
+__global__ void k_bis_rows(int64_t nd, int64_t n_int, int N, const uint8_t* keep, const int32_t* irow_scan, const int32_t* len, const int32_t* i2e,
+                           const double* coords, const double* bb /* lo[3], hi[3] */, double span, int32_t* cost, uint32_t* q, int32_t* ord) {
+    const int64_t d = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (d >= nd || !keep[d]) return;
+    const int64_t i = irow_scan[d], e = i2e ? i2e[d] : d;
+    cost[i] = len[d] + 2, ord[i] = (int32_t)i;
+    for (int a = 0; a < 3; ++a) {
+        uint32_t v = 0;
+        if (a < N) {
+            const double lo = bb[a], hi = bb[3 + a];
+            const double w = hi > lo ? (coords[(int64_t)a * nd + e] - lo) / (hi - lo) : 0.0;
+            v = (uint32_t)llround(fmin(1.0, fmax(0.0, w)) * span);
+        }
+        q[(int64_t)a * n_int + i] = v;
+    }
+}
+// extent of every segment along the three axes (lo: start 0xffffffff, hi: start 0).  A workgroup covers 256 x kBisPer consecutive positions; a
+// thread keeps the minima / maxima of the segment it is in and hands them over when the segment changes; at the end a wave whose lanes all
+// stopped in ONE segment (nearly all: a segment holds thousands of rows) merges through shuffles in front of its six atomics
+constexpr int kBisPer = 16;
+__global__ __launch_bounds__(256) void k_bis_extent(int64_t n_int, const int32_t* ord, const int32_t* segb, int nseg, const uint32_t* q, uint32_t* ext_lo, uint32_t* ext_hi) {
+    const int64_t base = (int64_t)blockIdx.x * (256 * kBisPer);
+    int32_t cur = -1;
+    uint32_t lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};
+    for (int it = 0; it < kBisPer; ++it) {
+        const int64_t p = base + (int64_t)it * 256 + threadIdx.x;
+        if (p >= n_int) break;
+        const int32_t seg = wg_of_irow(segb, nseg, p);
+        if (seg != cur) {
+            if (cur >= 0)
+                for (int a = 0; a < 3; ++a) atomicMin(&ext_lo[cur * 3 + a], lo[a]), atomicMax(&ext_hi[cur * 3 + a], hi[a]);
+            cur = seg;
+            for (int a = 0; a < 3; ++a) lo[a] = 0xffffffffu, hi[a] = 0u;
+        }
+        const int64_t row = ord[p];
+        for (int a = 0; a < 3; ++a) {
+            const uint32_t v = q[(int64_t)a * n_int + row];
+            lo[a] = min(lo[a], v), hi[a] = max(hi[a], v);
+        }
+    }
+    const int32_t c0 = __shfl(cur, 0);
+    const bool one = __ballot(cur != c0) == 0ull;   // (every lane of the wave arrives here)
+    if (one) {
+        for (int a = 0; a < 3; ++a)
+            for (int o = 32; o >= 1; o >>= 1) lo[a] = min(lo[a], (uint32_t)__shfl_xor((int)lo[a], o)), hi[a] = max(hi[a], (uint32_t)__shfl_xor((int)hi[a], o));
+        if ((threadIdx.x & 63) != 0) cur = -1;
+    }
+    if (cur >= 0)
+        for (int a = 0; a < 3; ++a) atomicMin(&ext_lo[cur * 3 + a], lo[a]), atomicMax(&ext_hi[cur * 3 + a], hi[a]);
+}
+__global__ void k_bis_keys(int64_t n_int, const int32_t* ord, const int32_t* segb, const int32_t* segg, int nseg, const uint32_t* q, const uint32_t* ext_lo,
+                           const uint32_t* ext_hi, uint64_t* key) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_int) return;
+    const int32_t seg = wg_of_irow(segb, nseg, p);
+    uint64_t c = 0;
+    if (segg[seg] > 1) {   // (a settled segment keeps its order: one key for all of its rows)
+        int axis = 0;      // largest extent, ties to the lowest axis
+        uint32_t best = 0;
+        for (int a = 0; a < 3; ++a) {
+            const uint32_t ext = ext_hi[seg * 3 + a] - ext_lo[seg * 3 + a];
+            if (ext > best) best = ext, axis = a;
+        }
+        c = q[(int64_t)axis * n_int + ord[p]];
+    }
+    key[p] = ((uint64_t)(uint32_t)seg << 31) | c;
+}
+__global__ void k_bis_gather_cost(int64_t n_int, const int32_t* ord, const int32_t* cost, int64_t* out) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p <= n_int) out[p] = p < n_int ? cost[ord[p]] : 0;
+}
+// one thread per segment (at most kPersistT of them): the right half starts at the first row whose exclusive cost prefix reaches the left half's share
+__global__ __launch_bounds__(512) void k_bis_split(int nseg, const int32_t* segb, const int32_t* segg, const int64_t* pre, int32_t* nb, int32_t* ng) {
+    __shared__ int32_t sg[512];
+    const int s = threadIdx.x;
+    if (s < nseg) sg[s] = segg[s];
+    __syncthreads();
+    if (s >= nseg) return;
+    int off = 0;   // segments of the next level in front of this one's
+    for (int t = 0; t < s; ++t) off += sg[t] > 1 ? 2 : 1;
+    const int32_t b = segb[s], e = segb[s + 1], g = sg[s];
+    if (s == 0) nb[0] = 0;
+    if (g == 1) {
+        nb[off + 1] = e, ng[off] = 1;
+        return;
+    }
+    const int32_t gl = g / 2, gr = g - gl;
+    const int64_t share = (pre[e] - pre[b]) * gl / g;
+    int32_t lo = b, hi = e;
+    while (lo < hi) {
+        const int32_t mid = (lo + hi) >> 1;
+        if (pre[mid] - pre[b] >= share) hi = mid; else lo = mid + 1;
+    }
+    const int32_t split = max(b + gl, min(e - gr, lo));   // neither half with fewer rows than workgroups
+    nb[off + 1] = split, ng[off] = gl, nb[off + 2] = e, ng[off + 1] = gr;
+}
+// the partition's numbering of ALL DOFs: interior rows in partition order, the dropped ones behind them in internal order
+__global__ void k_bis_numbering(int64_t nd, int64_t n_int, const uint8_t* keep, const int32_t* irow_scan, const int32_t* pos_of_row, const int32_t* rowptr,
+                                int32_t* new_of_old, int32_t* old_of_new, int32_t* len_new) {
+    const int64_t d = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (d >= nd) return;
+    const int64_t np = keep[d] ? pos_of_row[irow_scan[d]] : n_int + (d - irow_scan[d]);
+    new_of_old[d] = (int32_t)np, old_of_new[np] = (int32_t)d, len_new[np] = rowptr[d + 1] - rowptr[d];
+}
+__global__ void k_bis_invert(int64_t n, const int32_t* p, int32_t* inv) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) inv[p[i]] = (int32_t)i;
+}
+__global__ void k_bis_entries(int64_t nd, const int32_t* rowptr, const int32_t* colidx, const int32_t* new_of_old, const int32_t* rowptr_new, uint64_t* key,
+                              int32_t* val) {
+    const int64_t d = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (d >= nd) return;
+    const int32_t np = new_of_old[d];
+    int64_t at = rowptr_new[np];
+    for (int32_t k = rowptr[d]; k < rowptr[d + 1]; ++k, ++at) key[at] = ((uint64_t)(uint32_t)np << 32) | (uint32_t)new_of_old[colidx[k]], val[at] = k;
+}
+// the builder's output back in the real numbering: rows by DOF id, entries by their place in the real pattern
+__global__ void k_bis_map_back(int64_t n, const int32_t* map, int32_t* v) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && v[i] >= 0) v[i] = map[v[i]];
+}
+inline int bits_for(int64_t n) {   // key bits that hold 0 .. n - 1
+    int b = 1;
+    while ((int64_t(1) << b) < n) ++b;
+    return b;
+}
+
+}  // namespace
+
+int dev_build_persist_layout_bisect(int64_t nd, int32_t max_row, const int32_t* d_rowptr, const int32_t* d_colidx, const uint8_t* d_bnd, bool use_bnd, int M,
+                                    int N, const double* d_coords, const int32_t* d_i2e, int G, int lds_entries, int sym_mode, void* stream, PersistLayout& pl,
+                                    DevPersist* out, std::vector<int32_t>* perm_out, std::vector<int32_t>* rows_out, std::string& err) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (G < 2 || G > kPersistT || nd < 1 || max_row > 255 || N < 1 || N > 3) return FDAPDE_EUNSUPPORTED;
+    Arena arena;   // (declared before everything that allocates from it: released last)
+    ArenaScope arena_scope(&arena);
+    Scratch sc;
+    Tmp<uint8_t> keep;
+    Tmp<int32_t> keep32, irow_scan, len;
+    DP_CHK(keep.alloc((size_t)nd));
+    DP_CHK(keep32.alloc((size_t)nd + 1));
+    DP_CHK(irow_scan.alloc((size_t)nd + 1));
+    DP_CHK(len.alloc((size_t)nd));
+    DP_CHK(hipMemsetAsync(keep32.p + nd, 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(k_keep_flags, dim3(grid_of(nd)), dim3(256), 0, st, nd, d_bnd, use_bnd ? 1 : 0, keep.p, keep32.p);
+    if (int rc = exclusive_sum(sc, keep32.p, irow_scan.p, nd + 1, st, err)) return rc;
+    hipLaunchKernelGGL(k_row_lengths, dim3(grid_of(nd)), dim3(256), 0, st, nd, d_rowptr, d_colidx, keep.p, len.p);
+    int32_t h_nint = 0, h_nnz = 0;
+    DP_CHK(hipMemcpyAsync(&h_nint, irow_scan.p + nd, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    DP_CHK(hipMemcpyAsync(&h_nnz, d_rowptr + nd, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    DP_CHK(hipStreamSynchronize(st));
+    const int64_t n_int = h_nint, nnz = h_nnz;
+    if (n_int < (int64_t)G) return FDAPDE_EUNSUPPORTED;
+    // ---- integer coordinates (the Morton keys' quantisation -- bounding box of all DOFs -- at the resolution of internal.h persist_bisect_span), costs
+    Tmp<double> bb;
+    DP_CHK(bb.alloc(6));
+    for (int a = 0; a < N; ++a) {
+        size_t need = 0;
+        DP_CHK(hipcub::DeviceReduce::Min(nullptr, need, d_coords + (int64_t)a * nd, bb.p + a, (int)nd, st));
+        DP_CHK(sc.need(need));
+        DP_CHK(hipcub::DeviceReduce::Min(sc.p, need, d_coords + (int64_t)a * nd, bb.p + a, (int)nd, st));
+        DP_CHK(hipcub::DeviceReduce::Max(sc.p, need, d_coords + (int64_t)a * nd, bb.p + 3 + a, (int)nd, st));
+    }
+    Tmp<int32_t> cost, ord_a, ord_b, seg_a, seg_b, sgg_a, sgg_b;
+    Tmp<uint32_t> q, ext;
+    Tmp<uint64_t> key_a, key_b;
+    Tmp<int64_t> c2, pre;
+    DP_CHK(cost.alloc((size_t)n_int));
+    DP_CHK(ord_a.alloc((size_t)n_int));
+    DP_CHK(ord_b.alloc((size_t)n_int));
+    DP_CHK(q.alloc(3 * (size_t)n_int));
+    DP_CHK(key_a.alloc((size_t)n_int));
+    DP_CHK(key_b.alloc((size_t)n_int));
+    DP_CHK(c2.alloc((size_t)n_int + 1));
+    DP_CHK(pre.alloc((size_t)n_int + 1));
+    DP_CHK(seg_a.alloc((size_t)G + 1));
+    DP_CHK(seg_b.alloc((size_t)G + 1));
+    DP_CHK(sgg_a.alloc((size_t)G));
+    DP_CHK(sgg_b.alloc((size_t)G));
+    DP_CHK(ext.alloc(6 * (size_t)G));
+    const double span = persist_bisect_span(M, N, nd);
+    hipLaunchKernelGGL(k_bis_rows, dim3(grid_of(nd)), dim3(256), 0, st, nd, n_int, N, keep.p, irow_scan.p, len.p, d_i2e, d_coords, bb.p, span, cost.p, q.p, ord_a.p);
+    std::vector<int32_t> segg{G};   // workgroups of the segments, in position order
+    {
+        const int32_t b0[2] = {0, (int32_t)n_int};
+        DP_CHK(hipMemcpyAsync(seg_a.p, b0, sizeof(b0), hipMemcpyHostToDevice, st));
+        DP_CHK(hipMemcpyAsync(sgg_a.p, segg.data(), sizeof(int32_t), hipMemcpyHostToDevice, st));
+        DP_CHK(hipStreamSynchronize(st));   // (b0 leaves scope)
+    }
+    int32_t *ord = ord_a.p, *ord_n = ord_b.p, *segb = seg_a.p, *segb_n = seg_b.p, *sgg = sgg_a.p, *sgg_n = sgg_b.p;
+    while (*std::max_element(segg.begin(), segg.end()) > 1) {
+        const int nseg = (int)segg.size();
+        DP_CHK(hipMemsetAsync(ext.p, 0xff, sizeof(uint32_t) * 3 * (size_t)nseg, st));
+        DP_CHK(hipMemsetAsync(ext.p + 3 * (size_t)G, 0, sizeof(uint32_t) * 3 * (size_t)nseg, st));
+        hipLaunchKernelGGL(k_bis_extent, dim3((unsigned)((n_int + 256 * kBisPer - 1) / (256 * kBisPer))), dim3(256), 0, st, n_int, ord, segb, nseg, q.p, ext.p, ext.p + 3 * (size_t)G);
+        hipLaunchKernelGGL(k_bis_keys, dim3(grid_of(n_int)), dim3(256), 0, st, n_int, ord, segb, sgg, nseg, q.p, ext.p, ext.p + 3 * (size_t)G, key_a.p);
+        if (int rc = sort_pairs(sc, key_a.p, key_b.p, ord, ord_n, n_int, 31 + bits_for(nseg), st, err)) return rc;
+        hipLaunchKernelGGL(k_bis_gather_cost, dim3(grid_of(n_int + 1)), dim3(256), 0, st, n_int, ord_n, cost.p, c2.p);
+        if (int rc = exclusive_sum(sc, c2.p, pre.p, n_int + 1, st, err)) return rc;
+        hipLaunchKernelGGL(k_bis_split, dim3(1), dim3(512), 0, st, nseg, segb, sgg, pre.p, segb_n, sgg_n);
+        std::swap(ord, ord_n), std::swap(segb, segb_n), std::swap(sgg, sgg_n);
+        std::vector<int32_t> ng;
+        for (int32_t g : segg) {
+            if (g > 1) ng.push_back(g / 2), ng.push_back(g - g / 2);
+            else ng.push_back(1);
+        }
+        segg.swap(ng);
+    }
+    DP_CHK(hipGetLastError());
+    std::vector<int32_t> h_b((size_t)G + 1), h_rows((size_t)G);
+    DP_CHK(hipMemcpyAsync(h_b.data(), segb, sizeof(int32_t) * ((size_t)G + 1), hipMemcpyDeviceToHost, st));
+    DP_CHK(hipStreamSynchronize(st));
+    for (int g = 0; g < G; ++g) {
+        h_rows[(size_t)g] = h_b[(size_t)g + 1] - h_b[(size_t)g];
+        if (h_rows[(size_t)g] < 1) return FDAPDE_EUNSUPPORTED;
+    }
+    if (perm_out) {
+        perm_out->resize((size_t)n_int);
+        DP_CHK(hipMemcpyAsync(perm_out->data(), ord, sizeof(int32_t) * (size_t)n_int, hipMemcpyDeviceToHost, st));
+        DP_CHK(hipStreamSynchronize(st));
+    }
+    // ---- the system in the partition's numbering: rowptr', colidx' (columns sorted) with the real entry index alongside, bnd'
+    Tmp<int32_t> pos_of_row, new_of_old, old_of_new, len_new, rowptr_new, colidx_new, src_a, src_new;
+    Tmp<uint8_t> bnd_new;
+    Tmp<uint64_t> ek_a, ek_b;
+    DP_CHK(pos_of_row.alloc((size_t)n_int));
+    DP_CHK(new_of_old.alloc((size_t)nd));
+    DP_CHK(old_of_new.alloc((size_t)nd));
+    DP_CHK(len_new.alloc((size_t)nd + 1));
+    DP_CHK(rowptr_new.alloc((size_t)nd + 1));
+    DP_CHK(colidx_new.alloc((size_t)nnz + 2));
+    DP_CHK(src_a.alloc((size_t)nnz));
+    DP_CHK(src_new.alloc((size_t)nnz));
+    DP_CHK(ek_a.alloc((size_t)nnz));
+    DP_CHK(ek_b.alloc((size_t)nnz));
+    DP_CHK(bnd_new.alloc((size_t)nd));
+    hipLaunchKernelGGL(k_bis_invert, dim3(grid_of(n_int)), dim3(256), 0, st, n_int, ord, pos_of_row.p);
+    DP_CHK(hipMemsetAsync(len_new.p + nd, 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(k_bis_numbering, dim3(grid_of(nd)), dim3(256), 0, st, nd, n_int, keep.p, irow_scan.p, pos_of_row.p, d_rowptr, new_of_old.p, old_of_new.p,
+                       len_new.p);
+    if (int rc = exclusive_sum(sc, len_new.p, rowptr_new.p, nd + 1, st, err)) return rc;
+    hipLaunchKernelGGL(k_bis_entries, dim3(grid_of(nd)), dim3(256), 0, st, nd, d_rowptr, d_colidx, new_of_old.p, rowptr_new.p, ek_a.p, src_a.p);
+    if (nnz > 0) {
+        if (int rc = sort_pairs(sc, ek_a.p, ek_b.p, src_a.p, src_new.p, nnz, 32 + bits_for(nd), st, err)) return rc;
+        hipLaunchKernelGGL(k_low32, dim3(grid_of(nnz)), dim3(256), 0, st, nnz, ek_b.p, colidx_new.p);
+    }
+    DP_CHK(hipMemsetAsync(colidx_new.p + nnz, 0, 2 * sizeof(int32_t), st));
+    DP_CHK(hipMemsetAsync(bnd_new.p, 0, (size_t)n_int, st));
+    if (nd > n_int) DP_CHK(hipMemsetAsync(bnd_new.p + n_int, 1, (size_t)(nd - n_int), st));
+    DP_CHK(hipGetLastError());
+    // ---- the builder on that system, exactly these blocks; then rows and entries back in the real numbering
+    DevPersist o;
+    if (int rc = dev_build_persist_layout(nd, max_row, rowptr_new.p, colidx_new.p, bnd_new.p, true, G, lds_entries, 0, h_rows.data(), sym_mode, false, stream, pl, &o,
+                                          err))
+        return rc;
+    const int64_t n_slots = (int64_t)pl.G * pl.R * kPersistT, n_ent = pl.n_entries + 256;
+    hipLaunchKernelGGL(k_bis_map_back, dim3(grid_of(n_slots)), dim3(256), 0, st, n_slots, old_of_new.p, o.slot_dof);
+    hipLaunchKernelGGL(k_bis_map_back, dim3(grid_of(n_ent)), dim3(256), 0, st, n_ent, src_new.p, o.ell_src);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+        dev_persist_release(&o);
+        err = "bisection layout: mapping back failed";
+        return FDAPDE_EHIP;
+    }
+    if (rows_out) *rows_out = std::move(h_rows);
+    *out = o;
+    return FDAPDE_OK;
+}
+
 void dev_persist_preload() {
     hipFuncAttributes attr;
     (void)hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(&k_keep_flags));

@@ -2,6 +2,7 @@
 #ifndef FDAPDE_INTERNAL_H
 #define FDAPDE_INTERNAL_H
 
+#include <cmath>
 #include <cstdint>
 #include <memory>
 #include <new>
@@ -195,6 +196,7 @@ struct PersistLayout {
     int32_t single_rows = 2048;       // IN (set before the builder is called): systems of up to that many interior rows get ONE workgroup -- its
                                       // iteration needs no hand-off at all (kernels_persist.h, a.G == 1); 0: the general rule only
     bool sym = false;                 // in-block pairs stored once (persist_sym_owner)
+    bool bisect = false;              // blocks cut by coordinate bisection (host_bisect.cpp), not chunks of the internal order
     int G = 0, R = 0, nsl = 0;        // workgroups; rows per thread (2, 4, 8, 16); slices of 64 slots per workgroup = R * T / 64.
                                       // Slots [0, T R / 2): rows that import nothing; [T R / 2, T R): the others
     int64_t n_int = 0;                // interior (non-Dirichlet) rows
@@ -229,6 +231,36 @@ struct PersistLayout {
 // owned by other ranks: by owner, then by global key): such a DOF has no row here and is imported from the board's remote section.
 int host_build_persist_layout(const HostSpace& hs, bool use_bnd, int n_wg, int lds_entries, PersistLayout& pl, const int32_t* block_rows = nullptr,
                               int sym_mode = 0, bool balance = false, const int32_t* ghost_order = nullptr, bool allow_late = false);
+
+// ---- blocks by recursive coordinate bisection instead of chunks of the internal order (host_bisect.cpp; dev_persist.hip dev_build_persist_layout_bisect on the device).
+//      A segment of rows that holds g workgroups is cut into floor(g / 2) and ceil(g / 2), the cost (kept entries + 2 per row) shared in
+//      proportion: rows ordered along the axis of the segment's largest extent (ties: the lowest axis) by their integer coordinate, equal
+//      coordinates in their previous order (stable, starting from the internal order); the right half starts at the first row whose
+//      exclusive cost prefix reaches the left half's share, moved where needed so that neither half has fewer rows than workgroups.
+// Resolution of the integer coordinates: the quantisation of the Morton keys of the internal numbering (host_setup.cpp morton_order: position
+// in the bounding box of all DOFs, rounded), but with about as many levels per axis as the space has points along an axis -- n^(1 / M) - 1 for
+// a mesh of dimension M -- instead of 2^21 / 2^31.  Coordinates resolved finer than the points' spacing would order a LAYER of points (the
+// nodes of one lattice plane of a jittered structured mesh, one front of an advancing-front mesh) by their noise: a cut that falls inside such
+// a layer then deals its points to the two halves at random and the boundary between them is as rough as a boundary can be (C3, cut at the
+// keys' resolution: board -9 % against the chunks where the unjittered model has -23 %).  Points that tie keep their previous order, i.e. the
+// locality order: the layer is cut along the space-filling curve.
+// Every axis is scaled by its OWN extent (as in the keys): "largest extent" is counted in levels, not in length -- a flat or elongated domain is cut
+// along its short axes as readily as along its long ones.  The automatic choice's byte comparison (persist_engine.hip) decides whether the result is kept.
+inline double persist_bisect_span(int M, int N, int64_t n) {
+    const double key_span = (double)((uint64_t(1) << (N == 3 ? 21 : 31)) - 1);
+    double levels = std::floor(std::pow((double)(n > 1 ? n : 1), 1.0 / (double)(M >= 1 ? M : 1)) + 0.5) - 1.0;
+    return levels < 1.0 ? 1.0 : (levels > key_span ? key_span : levels);
+}
+// q: 3 x n (axis-major; axes >= N zero): point i2e[i] (i2e == nullptr: point i) of pts (column-major n x N) on the integer grid 0 .. span of its bounding box
+void host_bisect_quantise(int N, int64_t n, const double* pts_colmajor, const int32_t* i2e, double span, std::vector<uint32_t>& q);
+// n_int rows with cost[] and coordinates qx / qy / qz -> perm (position -> row, the rows of block g contiguous) and the blocks' row counts;
+// FDAPDE_EUNSUPPORTED: fewer rows than workgroups
+int host_bisect_partition(int64_t n_int, const int32_t* cost, const uint32_t* qx, const uint32_t* qy, const uint32_t* qz, int G, std::vector<int32_t>& perm,
+                          std::vector<int32_t>& block_rows);
+// host_build_persist_layout on exactly G bisection blocks: the builder sees the system in the partition's numbering (interior rows in perm
+// order, the dropped rows behind them; columns sorted), slot_dof and ell_src come back in the real numbering.  q: 3 x n_dofs, internal order.
+int host_build_persist_layout_bisect(const HostSpace& hs, bool use_bnd, int G, int lds_entries, PersistLayout& pl, int sym_mode, const uint32_t* q,
+                                     std::vector<int32_t>* perm_out = nullptr, std::vector<int32_t>* rows_out = nullptr);
 
 }  // namespace fdapde_hip
 #endif

@@ -18,12 +18,33 @@ static inline size_t dboard_offset(int64_t n_board) { return (2 * (size_t)n_boar
 namespace fdapde_engine {
 
 // FDAPDE_SETUP_CHECK: the device-built persistent layout against the host builder's
+static int compare_dev_persist(fdapde_ctx* c, const PersistLayout& pl, const DevPersist& dp, const PersistLayout& ref);
 int check_dev_persist(fdapde_ctx* c, int v, const PersistLayout& pl, const DevPersist& dp, const std::vector<int32_t>* block_rows, bool balance, int n_wg) {
     if (int rc = ensure_host(c, kHostPattern)) return rc;
     PersistLayout ref;
     ref.single_rows = pl.single_rows;
     if (host_build_persist_layout(c->hs, v == 1, n_wg, 12000, ref, block_rows ? block_rows->data() : nullptr,
                                   pl.sym ? 1 : 0, balance) != FDAPDE_OK) return fail(c, FDAPDE_EHIP, "set-up check: host persistent layout failed");
+    return compare_dev_persist(c, pl, dp, ref);
+}
+// ... and the device-built bisection layout (dev_persist.hip dev_build_persist_layout_bisect) against host_bisect.cpp's: the partition itself
+// (permutation of the interior rows, row counts of the blocks), then every array of the layout
+int check_dev_persist_bisect(fdapde_ctx* c, int v, const PersistLayout& pl, const DevPersist& dp, const std::vector<int32_t>& perm, const std::vector<int32_t>& rows) {
+    if (int rc = ensure_host(c, kHostPattern | kHostDofs)) return rc;
+    std::vector<uint32_t> q;
+    host_bisect_quantise(c->hs.N, c->hs.n_dofs, c->hs.dof_coords.data(), c->hs.dof_i2e.data(), persist_bisect_span(c->hs.M, c->hs.N, c->hs.n_dofs), q);
+    PersistLayout ref;
+    ref.single_rows = pl.single_rows;
+    std::vector<int32_t> perm_h, rows_h;
+    if (host_build_persist_layout_bisect(c->hs, v == 1, pl.G, 12000, ref, pl.sym ? 1 : 0, q.data(), &perm_h, &rows_h) != FDAPDE_OK)
+        return fail(c, FDAPDE_EHIP, "set-up check: host bisection layout failed");
+    const bool same_perm = perm == perm_h, same_rows = rows == rows_h;
+    std::fprintf(stderr, "persist check %-9s: %s (%zu elements)\n", "bis_perm", same_perm ? "ok" : "MISMATCH", perm_h.size());
+    std::fprintf(stderr, "persist check %-9s: %s (%zu elements)\n", "bis_rows", same_rows ? "ok" : "MISMATCH", rows_h.size());
+    if (!same_perm || !same_rows) return fail(c, FDAPDE_EHIP, "FDAPDE_SETUP_CHECK: the device-built bisection differs from the host's (see stderr)");
+    return compare_dev_persist(c, pl, dp, ref);
+}
+static int compare_dev_persist(fdapde_ctx* c, const PersistLayout& pl, const DevPersist& dp, const PersistLayout& ref) {
     int bad = 0;
     auto scalar = [&](const char* name, int64_t a, int64_t b) {
         if (a != b) std::fprintf(stderr, "persist check %-9s: MISMATCH %lld vs %lld\n", name, (long long)a, (long long)b), ++bad;
@@ -50,6 +71,25 @@ int check_dev_persist(fdapde_ctx* c, int v, const PersistLayout& pl, const DevPe
     }
     if (bad) return fail(c, FDAPDE_EHIP, "FDAPDE_SETUP_CHECK: the device-built persistent layout differs from the host builder's (see stderr)");
     return FDAPDE_OK;
+}
+
+// what a layout needs of a workgroup's LDS: slots, list capacities, the fixed part (vectors, tables, lists) and the largest block (ELL entries, with the
+// pair row of zeros behind it: slices narrower than their pass's widest re-read it through clamped loads)
+struct PersistNeeds {
+    int S = 0, imp_cap = 0, exp_cap = 0;
+    size_t fixed = 0;
+    int64_t need = 0;
+};
+static PersistNeeds persist_needs(const PersistLayout& pl, bool host_built) {
+    PersistNeeds n;
+    n.S = pl.R * kPersistT;
+    n.imp_cap = (pl.max_imp + 63) & ~63, n.exp_cap = (pl.max_exp + 63) & ~63;
+    n.fixed = pl.sym ? 8 * (size_t)(n.S + n.imp_cap) + 8 * (size_t)n.S + 64 : 8 * (size_t)(n.S + n.imp_cap) + 4 * (size_t)n.imp_cap + 2 * (size_t)n.exp_cap + 64;
+    if (pl.R > kPersistRmax) n.fixed = 8 * (size_t)(n.S + n.imp_cap) + 64;   // wide form: the p table and the imports (lists stay in global memory)
+    n.need = pl.max_block;   // largest workgroup block
+    for (int g = 0; g < pl.G && host_built; ++g) n.need = std::max<int64_t>(n.need, pl.ell_off[(size_t)g + 1] - pl.ell_off[(size_t)g]);
+    n.need += 128;
+    return n;
 }
 
 // resident layout of the persistent CG for boundary variant v (kernels_persist.h): host index work + uploads, once per function
@@ -121,13 +161,10 @@ int build_persist_once(fdapde_ctx* c, int v, const std::vector<int32_t>* block_r
             dev_persist_release(&dp);
             return FDAPDE_OK;
         }
-        S = pl.R * kPersistT;
-        imp_cap = (pl.max_imp + 63) & ~63, exp_cap = (pl.max_exp + 63) & ~63;
-        fixed = pl.sym ? 8 * (size_t)(S + imp_cap) + 8 * (size_t)S + 64 : 8 * (size_t)(S + imp_cap) + 4 * (size_t)imp_cap + 2 * (size_t)exp_cap + 64;
-        if (pl.R > kPersistRmax) fixed = 8 * (size_t)(S + imp_cap) + 64;   // wide form: the p table and the imports (lists stay in global memory)
-        need = pl.max_block;   // largest workgroup block
-        for (int g = 0; g < pl.G && !on_device; ++g) need = std::max<int64_t>(need, pl.ell_off[(size_t)g + 1] - pl.ell_off[(size_t)g]);
-        need += 128;        // one pair row of zeros behind the block: slices narrower than their pass's widest re-read it (clamped loads)
+        {
+            const PersistNeeds pn = persist_needs(pl, !on_device);
+            S = pn.S, imp_cap = pn.imp_cap, exp_cap = pn.exp_cap, fixed = pn.fixed, need = pn.need;
+        }
         if (pl.sym && fixed > lds_total && attempt == 0) {   // no room for the accumulator table: the plain form
             dev_persist_release(&dp);
             sym_mode = 0;
@@ -162,6 +199,81 @@ int build_persist_once(fdapde_ctx* c, int v, const std::vector<int32_t>* block_r
         dev_persist_release(&dp);
         return FDAPDE_OK;
     }
+    // ---- blocks by coordinate bisection (knob persist_partition; host_bisect.cpp / dev_persist.hip): the same number of workgroups and the same
+    //      storage as the chunk layout above, cut along coordinate planes instead of along the internal order.  Auto keeps it only if it fits
+    //      everything the chunk layout fits, ends in the same form or a better one (storage, rows per thread, resident / streaming) and moves
+    //      fewer bytes per iteration (e_solver_layout's figure: blocks + board); otherwise the chunk layout stays exactly as it is.  No size
+    //      class is left out: the A/B of DESIGN 4.0 (tools/persist_partition_ab.py) has no form that loses.
+    const int part = c->persist_partition;
+    const bool check = on_device && std::getenv("FDAPDE_SETUP_CHECK") != nullptr;
+    if (check) {   // the chunk layout is compared here, whether or not the bisection layout replaces it below
+        if (int rc2 = check_dev_persist(c, v, pl, dp, block_rows, balance, n_wg)) {
+            dev_persist_release(&dp);
+            return rc2;
+        }
+    }
+    if (part != 0 && block_rows == nullptr && !late_ok && pl.G >= 2) {
+        PersistLayout pl2;
+        DevPersist dp2;
+        pl2.single_rows = c->persist_single_rows;
+        std::vector<int32_t> perm2, rows2;
+        // the bisection layout is optional: whatever goes wrong while it is built (no coordinates, an allocation of its temporaries, a launch) leaves the
+        // chunk layout, which passed its checks, in place -- except a mismatch under FDAPDE_SETUP_CHECK, which is what that variable is there to report
+        int rc2 = FDAPDE_EUNSUPPORTED;
+        const size_t n_co = (size_t)c->hs.n_dofs * c->hs.N;
+        if (on_device) {
+            DBuf<double> coords_tmp;
+            const double* coords = nullptr;
+            if (c->hs.order == 1 && c->mesh_on_dev && c->mesh_nodes.n == n_co) coords = c->mesh_nodes.p;
+            else if (c->coords_e.p && c->coords_e.n == n_co) coords = c->coords_e.p;
+            else if (ensure_host(c, kHostDofs) == FDAPDE_OK && c->hs.dof_coords.size() == n_co &&
+                     coords_tmp.upload(c->hs.dof_coords.data(), n_co, c->stream) == hipSuccess)
+                coords = coords_tmp.p;
+            if (coords)
+                rc2 = dev_build_persist_layout_bisect(c->hs.n_dofs, c->hs.max_row, c->rowptr.p, c->colidx.p, c->bnd.p, v == 1, c->hs.M, c->hs.N, coords, c->dof_i2e.p, pl.G, 12000,
+                                                      pl.sym ? 1 : 0, c->stream, pl2, &dp2, check ? &perm2 : nullptr, check ? &rows2 : nullptr, c->err);
+            if (coords_tmp.p) (void)hipStreamSynchronize(c->stream);   // (the upload's source and target outlive the copy)
+        } else if (ensure_host(c, kHostPattern | kHostDofs) == FDAPDE_OK && c->hs.dof_coords.size() == n_co) {
+            std::vector<uint32_t> q;
+            host_bisect_quantise(c->hs.N, c->hs.n_dofs, c->hs.dof_coords.data(), c->hs.dof_i2e.data(), persist_bisect_span(c->hs.M, c->hs.N, c->hs.n_dofs), q);
+            rc2 = host_build_persist_layout_bisect(c->hs, v == 1, pl.G, 12000, pl2, pl.sym ? 1 : 0, q.data());
+        }
+        if (rc2 != FDAPDE_OK) {
+            (void)hipGetLastError();
+            c->err.clear();
+        }
+        if (rc2 == FDAPDE_OK && check)
+            if (int rc3 = check_dev_persist_bisect(c, v, pl2, dp2, perm2, rows2)) {
+                dev_persist_release(&dp), dev_persist_release(&dp2);
+                return rc3;
+            }
+        bool take = false;
+        PersistNeeds pn2;
+        bool stream2 = false;
+        if (rc2 == FDAPDE_OK) {
+            pn2 = persist_needs(pl2, !on_device);
+            stream2 = pn2.fixed + 10 * (size_t)pn2.need > lds_total;
+            auto bytes = [](const PersistLayout& l) {   // (e_solver_layout's figure)
+                return 10.0 * (double)l.n_entries + 32.0 * (double)l.n_board + (l.R > kPersistRmax ? 16.0 * (double)l.n_int : 0.0);
+            };
+            const bool fits = 10.0 * (double)pl2.n_entries <= max_mb * 1e6 && pn2.fixed <= lds_total && !(pl2.R >= 16 && !stream2) &&
+                              !(pl2.R > kPersistRmax && (c->persist_plain || !c->persist_wide));
+            const bool same_form = pl2.sym == pl.sym && pl2.R <= pl.R && (!stream2 || ps.stream);
+            take = fits && same_form && (part == 1 || bytes(pl2) < bytes(pl));
+            if (std::getenv("FDAPDE_DEBUG_SETUP"))
+                std::fprintf(stderr, "persistent CG layout %d: bisection %s: %.0f bytes per iteration against %.0f (entries %lld / %lld, board %lld / %lld, imports <= %d / %d, R %d / %d)\n",
+                             v, take ? "taken" : "not taken", bytes(pl2), bytes(pl), (long long)pl2.n_entries, (long long)pl.n_entries, (long long)pl2.n_board,
+                             (long long)pl.n_board, pl2.max_imp, pl.max_imp, pl2.R, pl.R);
+        }
+        if (take) {
+            dev_persist_release(&dp);
+            pl = std::move(pl2), dp = dp2;
+            S = pn2.S, imp_cap = pn2.imp_cap, exp_cap = pn2.exp_cap, fixed = pn2.fixed, need = pn2.need, ps.stream = stream2;
+            pl.bisect = true;
+        } else
+            dev_persist_release(&dp2);
+        clk.mark("build_persist: bisection layout");
+    }
     ps.lds_cap = ps.stream ? 0 : (int32_t)need, ps.imp_cap = imp_cap;
     ps.lds_bytes = fixed + (ps.stream ? 0 : 10 * (size_t)need);
     // symmetric streaming form: the export list too, where the workgroup has room left (the kernel's static arrays take ~0.6 KB of the 160)
@@ -169,12 +281,6 @@ int build_persist_once(fdapde_ctx* c, int v, const std::vector<int32_t>* block_r
     if (ps.exp_lds) ps.lds_bytes += 2 * (size_t)exp_cap;
     hipStream_t st = c->stream;
     if (on_device) {
-        if (std::getenv("FDAPDE_SETUP_CHECK")) {
-            if (int rc2 = check_dev_persist(c, v, pl, dp, block_rows, balance, n_wg)) {
-                dev_persist_release(&dp);
-                return rc2;
-            }
-        }
         const size_t GS = (size_t)pl.G * S, n_alloc = (size_t)pl.n_entries + 256;
         adopt(ps.slot_dof, dp.slot_dof, GS), adopt(ps.ell_off, dp.ell_off, (size_t)pl.G + 1), adopt(ps.sl_off, dp.sl_off, (size_t)pl.G * (pl.nsl + 1));
         adopt(ps.ell_code, dp.ell_code, n_alloc), adopt(ps.ell_src, dp.ell_src, n_alloc), adopt(ps.exp_off, dp.exp_off, (size_t)pl.G + 1);
@@ -210,7 +316,7 @@ int build_persist_once(fdapde_ctx* c, int v, const std::vector<int32_t>* block_r
                      "LDS %zu B (%s%s, largest block %lld), imports <= %d, exports <= %d, board %lld\n", v, on_device ? "device" : "host", pl.G, pl.R,
                      (long long)pl.n_int, (long long)pl.n_entries, (long long)pl.nnz,
                      100.0 * (double)(pl.n_entries - pl.nnz) / (double)(pl.n_entries > 0 ? pl.n_entries : 1), ps.lds_bytes,
-                     ps.stream ? "blocks stream" : "blocks resident", pl.sym ? ", symmetric storage" : "", (long long)need, pl.max_imp, pl.max_exp, (long long)pl.n_board);
+                     ps.stream ? "blocks stream" : "blocks resident", pl.sym ? (pl.bisect ? ", symmetric storage, bisection blocks" : ", symmetric storage") : (pl.bisect ? ", bisection blocks" : ""), (long long)need, pl.max_imp, pl.max_exp, (long long)pl.n_board);
     // keep the sizes, drop the big host arrays
     pl.slot_dof = {}, pl.ell_code = {}, pl.ell_src = {}, pl.exp_slot = {}, pl.imp_pos = {}, pl.sl_off = {}, pl.ell_off = {};
     ps.meta = std::move(pl);

@@ -312,6 +312,9 @@ int fdapde_solver_layout(fdapde_ctx *ctx, int32_t with_dirichlet, int64_t *n_int
  * the launch stages once, and an iteration moves the exchanged granules only); symmetric storage, workgroups, rows per thread. */
 int fdapde_solver_layout_kind(fdapde_ctx *ctx, int32_t with_dirichlet, int32_t *kind, int32_t *symmetric_storage,
                               int32_t *workgroups, int32_t *rows_per_thread);
+/* How the rows of a single persistent launch are dealt to its workgroups: 0 contiguous chunks of the internal order, 1 recursive coordinate
+ * bisection (fdapde_tune "persist_partition"; with 1 or 2 the chunks remain where the bisection layout does not fit); -1: no such layout. */
+int fdapde_solver_layout_partition(fdapde_ctx *ctx, int32_t with_dirichlet, int32_t *partition);
 /* ---- multi-GPU: element-partitioned meshes, one context (= one rank) per GPU --------------------------------------------
  * No reference counterpart (the reference is single-threaded, single address space).  Each rank uploads the sub-mesh of
  * its own cells (local node numbering), assembles its sub-assembled operator with the calls above, and the solve sums the
@@ -423,7 +426,9 @@ int fdapde_partition_peers(fdapde_ctx *ctx, int32_t rank, int32_t *n_peers, int3
  *                 reads b and writes x and its outcome through pinned host memory itself), "persist_direct_spin_us" (host spin on that outcome),
  *                 "persist_single_rows" (systems of up to that many interior rows run as one workgroup, without hand-offs),
  *                 "persist_prefetch" (0: the streaming forms do not touch the next operator application's first lines during the dot all-gather),
- *                 "persist_exp_lds" (0: the symmetric streaming form re-reads its export list from global memory every iteration)
+ *                 "persist_exp_lds" (0: the symmetric streaming form re-reads its export list from global memory every iteration),
+ *                 "persist_partition" (blocks of the single launch: 0 contiguous chunks of the internal order, 1 recursive coordinate bisection, 2 auto: bisection
+ *                 where its layout fits like the chunk layout and moves fewer bytes per iteration)
  *   solve         "dense_rows" (systems of up to that many DOFs may take the dense inverse; 0: never), "dense_after" (columns / steps before it is built),
  *                 "dense_block" (0: the pivot-by-pivot inversion), "dense_multi" (0: above 2 048 rows ONE panel workgroup with a panel of 8 / 4 columns instead of several with 16),
  *                 "dense_fold" (0: the stepper's dense loop as four launches per step instead of one product),
