@@ -83,7 +83,7 @@ void fdapde_ctx_destroy(fdapde_ctx* c) {
         (void)hipStreamSynchronize(c->stream);
         drop_graph(c);
         for (DBuf<int32_t>* b : {&c->cverts, &c->cdofs, &c->adj, &c->rowptr, &c->colidx, &c->diag, &c->slot_i2e, &c->dof_i2e,
-                                 &c->dof_e2i, &c->cell_i2e, &c->rb_row, &c->colour_cells, &c->ctl, &c->rowptr_e, &c->colidx_e, &c->dofs_e})
+                                 &c->dof_e2i, &c->cell_i2e, &c->colour_cells, &c->ctl, &c->rowptr_e, &c->colidx_e, &c->dofs_e})
             b->release();
         for (DBuf<double>* b : {&c->vcoords, &c->vals[0], &c->vals[1], &c->force, &c->fq, &c->g, &c->sval, &c->scale, &c->gt,
                                 &c->x, &c->r, &c->p, &c->y, &c->s, &c->t, &c->r0, &c->u, &c->part_a, &c->part_b, &c->sc,
@@ -410,16 +410,11 @@ int fdapde_tune(fdapde_ctx* c, const char* key, int32_t value) {
     if (c->group) return fdapde_engine::g_tune(c, key, value);
     const std::string k(key);
     drop_graph(c);
-    if (k == "spmv_variant" && value >= 0 && value <= 2) c->spmv_variant = value;
-    else if (k == "spmv_team" && (value == 2 || value == 4 || value == 8 || value == 16 || value == 32 || value == 64)) {
+    if (k == "spmv_team" && (value == 2 || value == 4 || value == 8 || value == 16 || value == 32)) {
         if (value != c->spmv_team) c->sp_built[0] = c->sp_built[1] = false, c->sp_cur = -1, c->solved = false, c->scaled_owner = fdapde_ctx::kScaledNone;   // segmented patterns depend on it
         c->spmv_team = value;
     }
-    else if (k == "spmv_unroll" && value >= 1 && value <= 8) c->spmv_unroll = value;
-    else if (k == "spmv_ablate") c->spmv_ablate = value;
     else if (k == "spmv_c16" && (value == 0 || value == 1)) c->spmv_c16 = value;
-    else if (k == "spmv_deep" && (value == 0 || value == 1)) c->spmv_deep = value;
-    else if (k == "cgf_split" && (value == 0 || value == 1)) c->cgf_split = value;
     else if (k == "cgf_v" && (value == 1 || value == 2 || value == 4 || value == 8)) c->cgf_v = value;
     else if (k == "use_graph" && (value == 0 || value == 1)) c->use_graph = value;
     else if (k == "cgf_band" && (value == 0 || value == 1)) c->cgf_band = value;

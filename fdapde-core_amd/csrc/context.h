@@ -158,7 +158,7 @@ struct GraphKey {
     const void* rowptr;
     int64_t n;
     double tol2;
-    int chunk, v, grid, team, ablate, c16, deep, unroll, sp_cur, bk_cur, bk_G;
+    int chunk, v, grid, team, c16, sp_cur, bk_cur, bk_G;
     const void* bk_val;
 };
 
@@ -199,7 +199,7 @@ struct fdapde_ctx {
     bool have_g = false, g_zero = false;   // Dirichlet data set; all of it zero (homogeneous: the lift A g~ vanishes)
     fdapde_info info{};
     // device buffers
-    DBuf<int32_t> cverts, cdofs, adj, rowptr, colidx, diag, slot_i2e, dof_i2e, dof_e2i, cell_i2e, rb_row, colour_cells;
+    DBuf<int32_t> cverts, cdofs, adj, rowptr, colidx, diag, slot_i2e, dof_i2e, dof_e2i, cell_i2e, colour_cells;
     DBuf<int32_t> rowptr_e, colidx_e;   // reference-numbering pattern (device-built spaces: fetched by fdapde_pattern_get on demand)
     DBuf<int32_t> dofs_e;               // order 2, device-built: the DOF table in the reference numbering (host mirror on demand)
     DBuf<double> coords_e;              // ... and the DOF coordinates
@@ -256,10 +256,8 @@ struct fdapde_ctx {
     int persist_direct_spin_us = 2000; // how long the host spins on the record's status word before it waits for the stream (0: never spins)
     int32_t* h_ctl = nullptr;   // pinned: ctl[3]
     double* h_sc = nullptr;     // pinned: sc[0..3]
-    int spmv_grid = 0, rb_per_band = 0, vec_grid = 0, n_rb = 0, cg_grid = 0;
-    int spmv_variant = 2;   // 2: team form, 2 entries per lane (default); 0: team form, 1 entry per lane
-                            // (FDAPDE_SPMV=team); 1: stream form (FDAPDE_SPMV=stream) -- kept for A/B measurements
-    int spmv_team = 16, spmv_unroll = 4, spmv_ablate = 0;
+    int spmv_grid = 0, vec_grid = 0, cg_grid = 0;
+    int spmv_team = 16;   // lanes per row of k_spmv_team2 (2 entries per lane), by mean row length
     int lds_limit = 96 * 1024;   // per assembly workgroup: tables + staged vertices + row accumulators
     // compact solver pattern (no diagonal; [1]: also no Dirichlet rows / columns), built on first use
     DBuf<int32_t> sp_rowptr[2], sp_colidx[2], sp_map[2], sp_tbase[2], sp_vrow[2];
@@ -276,9 +274,7 @@ struct fdapde_ctx {
     int cgf_lazy = 1;                        // tuning knob: x updated every second launch of k_cgf_update (C3 solve 33.3 -> 32.5 ms, same iterations)
     int cgf_nt = 7;                          // tuning knob, bit set: nontemporal y (1), x (2), r (4), p load (8) in k_cgf_update
     int cgf_band = 1;                        // tuning knob: XCD-aware mapping + nontemporal x / r / y in k_cgf_update (C3 solve 41.80 -> 41.10 ms)
-    int cgf_split = 0;                       // k_cgf_update requests the second half of its elements after the scalars (diagnostic)
     int cgf_v = 8;                           // double2 elements per lane of k_cgf_update (1, 2, 4, 8); C3 solve: 47.2 / 41.8 / 41.3 / 40.9 ms
-    int spmv_deep = 0;                       // tuning knob: 1 = k_spmv_c16p (gathers one tile ahead; measured slower: 3 waves / SIMD)
     int64_t sp_nnz[2] = {0, 0};
     bool sp_built[2] = {false, false};
     int sp_cur = -1;   // which compact pattern c->sval currently holds (-1: full pattern)

@@ -29,7 +29,7 @@ void dev_space_release(DevSpace* s);
 
 // Inputs on the device: nodes (column-major n_nodes x N), cells (row-major n_cells x (M+1)), and the DOF table in the reference's
 // numbering (dofs n_cells x nb, dof_bnd, dof_coords column-major n_dofs x N).  Fills `out` and the small host-side members of `hs`
-// the rest of the library reads (permutations, boundary flags in internal order, rowptr_i, sizes, rb_row); the big host arrays
+// the rest of the library reads (permutations, boundary flags in internal order, rowptr_i, sizes); the big host arrays
 // (colidx_i, cdofs_i, cverts_i, vcoords_i, colidx_e, rowptr_e) are left empty and fetched on demand by the caller.
 int dev_build_space(HostSpace& hs, const double* d_nodes, const int32_t* d_cells, const int32_t* d_dofs, const uint8_t* d_dof_bnd,
                     const double* d_dof_coords, void* stream, DevSpace* out, std::string& err);

@@ -979,36 +979,19 @@ int dev_build_space(HostSpace& hs, const double* d_nodes, const int32_t* d_cells
     DS_CHK(hipMemcpyAsync(h_max, maxes.p, sizeof h_max, hipMemcpyDeviceToHost, st));
     // (the permutations and the boundary flags in internal order stay on the device until host code asks: ensure_host, kHostPerm)
     hs.dof_i2e.clear(), hs.dof_e2i.clear(), hs.cell_i2e.clear(), hs.dof_bnd_i.clear();
-    // the row-block list of the CSR-stream SpMV (FDAPDE_SPMV=stream, a diagnostic variant) is host index work on the row pointers: only then
-    // are they fetched here; otherwise they come with the pattern's host mirror (ensure_host, kHostPattern)
-    const char* spmv_env = std::getenv("FDAPDE_SPMV");
-    const bool want_rb = spmv_env && std::string(spmv_env) == "stream";
+    // (the row pointers come with the pattern's host mirror: ensure_host, kHostPattern)
     hs.rowptr_i.clear(), hs.sl_off.clear();   // (sl_off: n_slices and the widest slice are all host code reads of it)
     hs.n_slices = n_slices;
-    if (want_rb) {
-        hs.rowptr_i.resize((size_t)nd + 1);
-        DS_CHK(hipMemcpyAsync(hs.rowptr_i.data(), s.rowptr, sizeof(int32_t) * ((size_t)nd + 1), hipMemcpyDeviceToHost, st));
-    }
     DS_CHK(hipStreamSynchronize(st));
     hs.max_slice_width = h_max[4];
     hs.nnz = nnz, hs.max_row = h_max[0], hs.max_blk_nnz = h_max[1], hs.max_blk_cells = h_max[2], hs.max_blk_nodes = h_max[3], hs.nbw = nbw;
-    if (hs.max_row > 65535) {   // (rows longer than kSpmvNnz -- network hubs -- are SpMV row blocks of their own)
+    if (hs.max_row > 65535) {   // (the SpMV itself takes rows of any length -- network hubs -- in further team passes)
         err = "row too long for the uint16 slot map";
         return FDAPDE_EUNSUPPORTED;
     }
     if (hs.max_blk_nodes > 65535) {
         err = "assembly block touches more than 65535 nodes";
         return FDAPDE_EUNSUPPORTED;
-    }
-    hs.rb_row.clear();
-    hs.rb_row.push_back(0);
-    if (!want_rb) hs.rb_row.push_back((int32_t)nd);   // (never read by the default SpMV)
-    for (int64_t r = 0; want_rb && r < nd;) {   // SpMV row blocks: consecutive rows with at most kSpmvNnz nonzeros
-        int64_t e = r;
-        const int32_t base = hs.rowptr_i[(size_t)r];
-        while (e < nd && (e == r || hs.rowptr_i[(size_t)e + 1] - base <= kSpmvNnz) && e - r < 1024) ++e;
-        hs.rb_row.push_back((int32_t)e);
-        r = e;
     }
     hs.n_colours = 0, hs.colour_off.clear(), hs.colour_cells.clear();
     phase("host mirrors");

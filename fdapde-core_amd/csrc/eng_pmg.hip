@@ -680,7 +680,7 @@ int pmg_run(fdapde_ctx* c, const double* A, const double* f_dev, const double* g
     // iterate itself (start, warm start, true residual: Dirichlet columns count there) keep the CSR kernel.
     const int fv = use_bnd ? 1 : 0;
     bool fb = false;
-    if (c->pmg_blocked && c->blocked && c->spmv_variant == 2) {
+    if (c->pmg_blocked && c->blocked) {
         if (int rc = build_blocked(c, fv)) return rc;
         if (c->bk[fv].ok) {
             int32_t zero_diag = 0;

@@ -139,7 +139,6 @@ int adopt_dev_space(fdapde_ctx* c, DevSpace& s) {
     adopt(c->rowptr, s.rowptr, nd + 1), adopt(c->colidx, s.colidx, nnz + 2), adopt(c->diag, s.diag, nd), adopt(c->slot_i2e, s.slot_i2e, nnz);
     adopt(c->dof_i2e, s.dof_i2e, nd), adopt(c->dof_e2i, s.dof_e2i, nd), adopt(c->cell_i2e, s.cell_i2e, nc), adopt(c->bnd, s.bnd, nd);
     adopt(c->rowptr_e, s.rowptr_e, nd + 1), adopt(c->colidx_e, s.colidx_e, nnz);
-    HIPCHK(c, c->rb_row.upload(hs.rb_row.data(), hs.rb_row.size(), c->stream));
     dev_space_release(&s);   // what nobody adopted (node_i2e)
     c->dev_built = true;
     return FDAPDE_OK;
@@ -185,7 +184,6 @@ int check_dev_space(fdapde_ctx* c, const DevSpace& s, int order) {
         CMP("bc_off", s.bc_off, ref.bc_off), CMP("bn_off", s.bn_off, ref.bn_off), CMP("bc_cell", s.bc_cell, ref.bc_cell);
         CMP("bn_node", s.bn_node, ref.bn_node), CMP("bc_vert", s.bc_vert, ref.bc_vert), CMP("adj", s.adj, ref.adj), CMP("slotw", s.slotw, ref.slotw);
 #undef CMP
-        if (hs.rb_row.size() > 2 && hs.rb_row != ref.rb_row) std::fprintf(stderr, "set-up check rb_row: MISMATCH\n"), ++bad;   // (built for FDAPDE_SPMV=stream only)
     }
     if (bad) return fail(c, FDAPDE_EHIP, "FDAPDE_SETUP_CHECK: the device-built space differs from the host builder's (see stderr)");
     return FDAPDE_OK;
@@ -215,7 +213,6 @@ int upload_space(fdapde_ctx* c) {
     HIPCHK(c, c->dof_i2e.upload(hs.dof_i2e.data(), hs.dof_i2e.size(), st));
     HIPCHK(c, c->dof_e2i.upload(hs.dof_e2i.data(), hs.dof_e2i.size(), st));
     HIPCHK(c, c->cell_i2e.upload(hs.cell_i2e.data(), hs.cell_i2e.size(), st));
-    HIPCHK(c, c->rb_row.upload(hs.rb_row.data(), hs.rb_row.size(), st));
     HIPCHK(c, c->bnd.upload(hs.dof_bnd_i.data(), hs.dof_bnd_i.size(), st));
     }
     DevTables dt{};
@@ -271,38 +268,17 @@ int upload_space(fdapde_ctx* c) {
     for (DBuf<double>* b : {&c->scale, &c->gt, &c->x, &c->r, &c->p, &c->y, &c->s, &c->t, &c->r0, &c->u, &c->tmp_e, &c->tmp_i, &c->g})
         HIPCHK(c, b->alloc(n));
     HIPCHK(c, c->force.alloc(n));
-    c->n_rb = (int)hs.rb_row.size() - 1;
-    c->rb_per_band = (c->n_rb + 7) / 8;
-    // workgroups per band: 192 (1536 workgroups = 1.5 rounds of the 1024 resident ones) measured best on C3 with the default cache
-    // policy (solve 33.0 ms at 256, 32.6 at 192, 33.5 at 160 / 224); smaller matrices get one workgroup per 4096 nonzeros
-    int bpx = c->rb_per_band < 192 ? c->rb_per_band : 192;
-    if (bpx < 1) bpx = 1;
-    {
-        const char* v = std::getenv("FDAPDE_SPMV");
-        c->spmv_variant = (v && std::strcmp(v, "stream") == 0) ? 1 : ((v && std::strcmp(v, "team") == 0) ? 0 : 2);
+    int bpx;
+    {   // team width: 2 * team entries per pass cover the mean row; workgroups per band: one per tile of a band's rows, at most 256
+        // (knob spmv_bpx; C3 with the default cache policy: solve 33.0 ms at 256, 32.6 at 192, 33.5 at 160 / 224)
         const double mean_row = (double)hs.nnz / (double)(hs.n_dofs > 0 ? hs.n_dofs : 1);
         int t = 4;
         while (t < 64 && t < mean_row) t *= 2;
-        c->spmv_team = t;
-        if (c->spmv_variant == 2) c->spmv_team = t / 2 < 2 ? 2 : (t / 2 > 32 ? 32 : t / 2);
-        if (const char* e = std::getenv("FDAPDE_SPMV_TEAM")) c->spmv_team = std::atoi(e);
-        if (const char* e = std::getenv("FDAPDE_SPMV_ABLATE")) c->spmv_ablate = std::atoi(e);
-        if (c->spmv_variant == 2) {
-            if (const char* e = std::getenv("FDAPDE_SPMV_UNROLL")) c->spmv_unroll = std::atoi(e);
-            const int tt = c->spmv_team, u = tt == 2 ? 1 : (tt == 4 ? 2 : (tt == 8 ? c->spmv_unroll : 4));
-            const int wrows = (64 / tt) * u * 4;
-            const int64_t tiles = ((hs.n_dofs + 7) / 8 + wrows - 1) / wrows;
-            bpx = (int)(tiles < 256 ? (tiles < 1 ? 1 : tiles) : 256);
-            if (const char* e = std::getenv("FDAPDE_SPMV_BPX")) bpx = std::atoi(e);
-        }
-        if (c->spmv_variant == 0) {
-            if (const char* e = std::getenv("FDAPDE_SPMV_UNROLL")) c->spmv_unroll = std::atoi(e);
-            const int u = c->spmv_team == 64 || c->spmv_team == 4 ? 2 : (c->spmv_team == 16 ? c->spmv_unroll : 4);
-            const int wrows = (64 / c->spmv_team) * u * 4;   // rows per workgroup-iteration
-            const int64_t tiles = ((hs.n_dofs + 7) / 8 + wrows - 1) / wrows;
-            bpx = (int)(tiles < 256 ? (tiles < 1 ? 1 : tiles) : 256);
-            if (const char* e = std::getenv("FDAPDE_SPMV_BPX")) bpx = std::atoi(e);
-        }
+        c->spmv_team = t / 2 < 2 ? 2 : (t / 2 > 32 ? 32 : t / 2);
+        const int tt = c->spmv_team, u = tt == 2 ? 1 : (tt == 4 ? 2 : 4);
+        const int wrows = (64 / tt) * u * 4;   // rows per workgroup-iteration
+        const int64_t tiles = ((hs.n_dofs + 7) / 8 + wrows - 1) / wrows;
+        bpx = (int)(tiles < 256 ? (tiles < 1 ? 1 : tiles) : 256);
     }
     c->spmv_grid = 8 * bpx;
     int64_t vg = (hs.n_dofs + 255) / 256;

@@ -39,21 +39,28 @@ void launch_spmv_blocked(fdapde_ctx* c, int v, const double* x, double* y, const
         a.G = bk.meta.G, a.nsl = bk.meta.nsl, a.imp_cap = bk.imp_cap, a.dot2_ww = dot2_ww;
         a.slot_dof = bk.slot_dof.p, a.ell_off = bk.ell_off.p, a.sl_off = bk.sl_off.p, a.ell_code = bk.ell_code.p, a.ell_val = bk.ell_val.p;
         a.imp_off = bk.imp_off.p, a.imp_dof = bk.imp_dof.p, a.drop_dof = bk.drop_dof.p, a.n_drop = (int32_t)bk.meta.n_drop, a.x = x, a.y = y, a.w = partial ? (w ? w : x) : nullptr, a.partial = partial, a.stop = stop;
-#define BLOCKED_GO(R_)                                                                                                          \
-    do {                                                                                                                        \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_spmv_blocked<R_>), hipFuncAttributeMaxDynamicSharedMemorySize,  \
-                                  (int)bk.lds_bytes);                                                                           \
-        if (e0 || e1) hipExtLaunchKernelGGL((k_spmv_blocked<R_>), dim3(a.G), dim3(kPersistT), bk.lds_bytes, c->stream, e0, e1, 0, a); \
-        else hipLaunchKernelGGL((k_spmv_blocked<R_>), dim3(a.G), dim3(kPersistT), bk.lds_bytes, c->stream, a);                  \
-    } while (0)
-        switch (bk.meta.R) {
-        case 2: BLOCKED_GO(2); break;
-        case 4: BLOCKED_GO(4); break;
-        case 8: BLOCKED_GO(8); break;
-        default: BLOCKED_GO(16); break;
-        }
-#undef BLOCKED_GO
+        void (*k)(BlockedSpmvArgs) = bk.meta.R == 2 ? k_spmv_blocked<2> : bk.meta.R == 4 ? k_spmv_blocked<4> : bk.meta.R == 8 ? k_spmv_blocked<8> : k_spmv_blocked<16>;
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bk.lds_bytes);
+        if (e0 || e1) hipExtLaunchKernelGGL(k, dim3(a.G), dim3(kPersistT), bk.lds_bytes, c->stream, e0, e1, 0, a);
+        else hipLaunchKernelGGL(k, dim3(a.G), dim3(kPersistT), bk.lds_bytes, c->stream, a);
     }
+}
+
+// The instantiations of k_spmv_team2 that a size, a pattern or the platform selects, as tables indexed by the two run-time flags
+// [implicit diagonal owner-masked (multi-GPU)][dot operand == x (CG: p.Ap; one row load serves both)].  WX_FORM = false: this team
+// width has no dot-operand-is-x form, the general one serves.
+using spmv_kernel_t = void (*)(SpmvArgs, int64_t, int64_t);
+template <int T, int U, bool C16, bool WX_FORM, bool VROWS = false, bool NTV = false>
+spmv_kernel_t spmv_form(bool dist, bool wx) {
+    static const spmv_kernel_t form[2][2] = {
+        {k_spmv_team2<T, U, C16, false, false, VROWS, NTV>, k_spmv_team2<T, U, C16, false, WX_FORM, VROWS, NTV>},
+        {k_spmv_team2<T, U, C16, true, false, VROWS, NTV>, k_spmv_team2<T, U, C16, true, WX_FORM, VROWS, NTV>}};
+    return form[dist][wx];
+}
+// ... with 16-bit column codes when the pattern has them
+template <int T, int U, bool WX_FORM>
+spmv_kernel_t spmv_plain_form(bool c16, bool dist, bool wx) {
+    return c16 ? spmv_form<T, U, true, WX_FORM>(dist, wx) : spmv_form<T, U, false, WX_FORM>(dist, wx);
 }
 
 void launch_spmv(fdapde_ctx* c, const double* vals, const double* x, double* y, const double* w, double* partial,
@@ -65,7 +72,7 @@ void launch_spmv(fdapde_ctx* c, const double* vals, const double* x, double* y, 
     }
     SpmvArgs s{};
     s.rowptr = c->rowptr.p, s.colidx = c->colidx.p, s.vals = vals, s.x = x, s.y = y;
-    s.rb_row = c->rb_row.p, s.n_rb = c->n_rb, s.rb_per_band = c->rb_per_band, s.nnz = (int32_t)c->hs.nnz;
+    s.nnz = (int32_t)c->hs.nnz;
     s.w = w, s.partial = partial, s.stop = stop, s.dot2_ww = dot2_ww, s.owned = owned, s.unit_diag = 0;
     s.n_cols = (int32_t)c->hs.n_dofs;
     // value-stream policy by size: x and y slices of a row band (16 bytes per row, 8 bands) against the 4 MB L2 of an XCD
@@ -86,127 +93,28 @@ void launch_spmv(fdapde_ctx* c, const double* vals, const double* x, double* y, 
     }
     // eight row bands (one per XCD); band starts on a multiple of 32 rows so that a wavefront tile lies in one code group
     const int64_t rpb = (((n + 7) / 8) + 31) & ~int64_t(31);
-    const dim3 grid(c->spmv_grid), block(256);
-    // dispatch-attached events only where a launch is timed; the plain launch can be captured into a hipGraph
-#define SPMV_GO(...)                                                                                 \
-    do {                                                                                             \
-        if (e0 || e1) hipExtLaunchKernelGGL((__VA_ARGS__), grid, block, 0, c->stream, e0, e1, 0, s, n, rpb); \
-        else hipLaunchKernelGGL((__VA_ARGS__), grid, block, 0, c->stream, s, n, rpb);                \
-    } while (0)
-    if (c->spmv_variant == 1) {
-        if (e0 || e1) hipExtLaunchKernelGGL(k_spmv, grid, block, 0, c->stream, e0, e1, 0, s);
-        else hipLaunchKernelGGL(k_spmv, grid, block, 0, c->stream, s);
-        return;
-    }
-    if (c->spmv_variant == 2) {   // two entries per lane: team = lanes per row, covering 2 * team entries per pass
-        // production forms: 16-byte aligned entry pairs (2048), + 16-bit column codes when the pattern has them (4096),
-        // + unconditional ownership loads when the implicit diagonal is owner-masked (multi-GPU, 8192)
-        const bool c16 = s.col16 != nullptr, dist = s.unit_diag && s.owned != nullptr;
-        const bool wx = s.w == nullptr || s.w == s.x;   // dot operand == x (CG: p.Ap): one row load serves both (16384)
-#define SPMV_PROD_FEW(T_, U_)                                                    \
-    do {                                                                         \
-        if (c16 && dist) SPMV_GO(k_spmv_team2<T_, U_, 2048 | 4096 | 8192>);      \
-        else if (c16) SPMV_GO(k_spmv_team2<T_, U_, 2048 | 4096>);                \
-        else if (dist) SPMV_GO(k_spmv_team2<T_, U_, 2048 | 8192>);               \
-        else SPMV_GO(k_spmv_team2<T_, U_, 2048>);                                \
-    } while (0)
-#define SPMV_PROD(T_, U_)                                                                    \
-    do {                                                                                     \
-        if (!wx) SPMV_PROD_FEW(T_, U_);                                                      \
-        else if (c16 && dist) SPMV_GO(k_spmv_team2<T_, U_, 2048 | 4096 | 8192 | 16384>);     \
-        else if (c16) SPMV_GO(k_spmv_team2<T_, U_, 2048 | 4096 | 16384>);                    \
-        else if (dist) SPMV_GO(k_spmv_team2<T_, U_, 2048 | 8192 | 16384>);                   \
-        else SPMV_GO(k_spmv_team2<T_, U_, 2048 | 16384>);                                    \
-    } while (0)
-        if (vrows) {   // built for this team size (build_solver_pattern); T = 8 or 16
-#define SPMV_VROWS(T_)                                                                                  \
-    do {                                                                                                \
-        if (dist && wx) SPMV_GO(k_spmv_team2<T_, 4, 2048 | 4096 | 131072 | 8192 | 16384>);              \
-        else if (dist) SPMV_GO(k_spmv_team2<T_, 4, 2048 | 4096 | 131072 | 8192>);                       \
-        else if (wx) SPMV_GO(k_spmv_team2<T_, 4, 2048 | 4096 | 131072 | 16384>);                        \
-        else SPMV_GO(k_spmv_team2<T_, 4, 2048 | 4096 | 131072>);                                        \
-    } while (0)
-            if (c->sp_team == 8) SPMV_VROWS(8);
-            else SPMV_VROWS(16);
-#undef SPMV_VROWS
-            return;
-        }
+    // two entries per lane: team = lanes per row, covering 2 * team entries per pass
+    const bool c16 = s.col16 != nullptr, dist = s.unit_diag && s.owned != nullptr;
+    const bool wx = s.w == nullptr || s.w == s.x;
+    spmv_kernel_t k;
+    if (vrows)   // built for this team size (build_solver_pattern); T = 8 or 16
+        k = c->sp_team == 8 ? spmv_form<8, 4, /*C16*/ true, /*WX_FORM*/ true, /*VROWS*/ true>(dist, wx)
+                             : spmv_form<16, 4, /*C16*/ true, /*WX_FORM*/ true, /*VROWS*/ true>(dist, wx);
+    else
         switch (c->spmv_team) {
-        case 2: SPMV_PROD_FEW(2, 1); break;
-        case 4: SPMV_PROD(4, 2); break;
-        case 8:
-            // the diagnostic forms >= 100 exist for the compact coded matrix only: any other product takes the production path
-            switch ((c->spmv_ablate >= 100 && !c16) ? 0 : c->spmv_ablate) {
-            case 1: SPMV_GO(k_spmv_team2<8, 4, 1>); break;
-            case 2: SPMV_GO(k_spmv_team2<8, 4, 2>); break;
-            case 4: SPMV_GO(k_spmv_team2<8, 4, 4>); break;
-            case 5: SPMV_GO(k_spmv_team2<8, 4, 5>); break;
-            case 8: SPMV_GO(k_spmv_team2<8, 4, 8>); break;     // no y store, no w read
-            case 9: SPMV_GO(k_spmv_team2<8, 4, 9>); break;     // + no gather
-            case 16: SPMV_GO(k_spmv_team2<8, 4, 16>); break;   // one band (no XCD banding)
-            case 32: SPMV_GO(k_spmv_team2<8, 4, 32>); break;   // no y store
-            case 64: SPMV_GO(k_spmv_team2<8, 4, 64>); break;   // no w load
-            case 3: SPMV_GO(k_spmv_team2<8, 4>); break;        // unaligned entry pairs, 32-bit columns (the form before)
-            // diagnostics on the production form (16-bit codes, w == x); meaningful only on the compact solver matrix
-            case 101: if (c16) SPMV_GO(k_spmv_team2<8, 4, 2048 | 4096 | 16384 | 1>); break;    // no x gather
-            case 132: if (c16) SPMV_GO(k_spmv_team2<8, 4, 2048 | 4096 | 16384 | 32>); break;   // no y store
-            case 133: if (c16) SPMV_GO(k_spmv_team2<8, 4, 2048 | 4096 | 16384 | 33>); break;   // neither
-            case 140:   // y rows kept in LDS until the wavefront's tile loop ends (needs <= 8 tiles per wavefront)
-                if (c16 && (rpb / 32 + (int64_t)(c->spmv_grid / 8) * 4 - 1) / ((int64_t)(c->spmv_grid / 8) * 4) <= 8)
-                    SPMV_GO(k_spmv_team2<8, 4, 2048 | 4096 | 16384 | 32768>);
-                break;
-            case 150: if (c16) SPMV_GO(k_spmv_team2<8, 4, 2048 | 4096 | 16384 | 262144>); break;   // window bases as a 16-byte broadcast load (the form before)
-            case 151: if (c16) SPMV_GO(k_spmv_team2<8, 4, 2048 | 4096 | 16384 | 524288>); break;             // nontemporal column codes
-            case 152: if (c16) SPMV_GO(k_spmv_team2<8, 4, 2048 | 4096 | 16384 | 524288 | 1048576>); break;   // + nontemporal values (the form before)
-            case 153: if (c16) SPMV_GO(k_spmv_team2<8, 4, 2048 | 4096 | 16384 | 1048576>); break;            // nontemporal values only
-            case 102: if (c16) SPMV_GO(k_spmv_team2<8, 4, 2048 | 4096 | 16384 | 2>); break;       // gathers inside 16 lines
-            case 103: if (c16) SPMV_GO(k_spmv_team2<8, 4, 2048 | 4096 | 16384 | 65536>); break;   // gathers inside 1 line
-            case 2048: SPMV_GO(k_spmv_team2<8, 4, 2048>); break;   // aligned pairs, 32-bit columns
-            default:
-                if (c->spmv_unroll == 2 && c16 && c->spmv_deep)
-                    SPMV_GO(k_spmv_c16p<8, 2, 16384>);
-                else if (c->spmv_unroll == 2 && c16)
-                    SPMV_GO(k_spmv_team2<8, 2, 2048 | 4096 | 16384>);
-                else if (c->spmv_unroll == 2)
-                    SPMV_GO(k_spmv_team2<8, 2>);
-                else if (c->spmv_unroll == 6)
-                    SPMV_GO(k_spmv_team2<8, 6>);
-                else if (c16 && c->spmv_deep) {   // deep-pipelined form: gathers one tile ahead
-                    if (dist && wx) SPMV_GO(k_spmv_c16p<8, 4, 8192 | 16384>);
-                    else if (dist) SPMV_GO(k_spmv_c16p<8, 4, 8192>);
-                    else if (wx) SPMV_GO(k_spmv_c16p<8, 4, 16384>);
-                    else SPMV_GO(k_spmv_c16p<8, 4, 0>);
-                } else if (ntv && c16 && wx) {   // large matrix: hinted value stream (see load_pair)
-                    if (dist) SPMV_GO(k_spmv_team2<8, 4, 2048 | 4096 | 8192 | 16384 | 1048576>);
-                    else SPMV_GO(k_spmv_team2<8, 4, 2048 | 4096 | 16384 | 1048576>);
-                } else if (ntv && c16) {
-                    if (dist) SPMV_GO(k_spmv_team2<8, 4, 2048 | 4096 | 8192 | 1048576>);
-                    else SPMV_GO(k_spmv_team2<8, 4, 2048 | 4096 | 1048576>);
-                } else
-                    SPMV_PROD(8, 4);
-                break;
-            }
+        case 2: k = spmv_plain_form<2, 1, false>(c16, dist, wx); break;
+        case 4: k = spmv_plain_form<4, 2, true>(c16, dist, wx); break;
+        case 8:   // large matrix: hinted value stream (see load_pair)
+            k = (ntv && c16) ? spmv_form<8, 4, /*C16*/ true, /*WX_FORM*/ true, /*VROWS*/ false, /*NTV*/ true>(dist, wx)
+                             : spmv_plain_form<8, 4, true>(c16, dist, wx);
             break;
-        case 16: SPMV_PROD(16, 4); break;
-        default: SPMV_PROD_FEW(32, 4); break;
+        case 16: k = spmv_plain_form<16, 4, true>(c16, dist, wx); break;
+        default: k = spmv_plain_form<32, 4, false>(c16, dist, wx); break;
         }
-#undef SPMV_PROD
-#undef SPMV_PROD_FEW
-        return;
-    }
-    switch (c->spmv_team) {
-    case 4: SPMV_GO(k_spmv_team<4, 2>); break;
-    case 8: SPMV_GO(k_spmv_team<8, 4>); break;
-    case 16:
-        if (c->spmv_unroll == 8)
-            SPMV_GO(k_spmv_team<16, 8>);
-        else
-            SPMV_GO(k_spmv_team<16, 4>);
-        break;
-    case 32: SPMV_GO(k_spmv_team<32, 4>); break;
-    default: SPMV_GO(k_spmv_team<64, 2>); break;
-    }
-#undef SPMV_GO
+    // dispatch-attached events only where a launch is timed; the plain launch can be captured into a hipGraph
+    const dim3 grid(c->spmv_grid), block(256);
+    if (e0 || e1) hipExtLaunchKernelGGL(k, grid, block, 0, c->stream, e0, e1, 0, s, n, rpb);
+    else hipLaunchKernelGGL(k, grid, block, 0, c->stream, s, n, rpb);
 }
 
 // default iteration bound: 10 n capped at 100 000 -- but ONE number for all ranks of a row-distributed solve (the launches stop by it and
@@ -224,7 +132,7 @@ int build_solver_pattern(fdapde_ctx* c, int v) {
     // rows longer than a team pass (P2): segmented pattern, one team pass per chunk; else the plain compact pattern
     const int T = c->spmv_team;
     bool seg = false;
-    if ((T == 8 || T == 16) && c->hs.max_row - 1 > 2 * T && !std::getenv("FDAPDE_SPMV_NOSEG")) {
+    if ((T == 8 || T == 16) && c->hs.max_row - 1 > 2 * T) {
         const int rc = host_build_solver_pattern_seg(c->hs, v == 1, 2 * T, (64 / T) * 4, rp, ci, map, vrow);
         if (rc == FDAPDE_OK) seg = true;
         else if (rc != FDAPDE_EUNSUPPORTED) return rc;
@@ -314,7 +222,7 @@ int solve_prepare(fdapde_ctx* c, const double* A, int use_bnd, SolveState* ss, b
     ss->front_pending = false, ss->front_A = A;
     // ... and the smallest of them (one workgroup): flag reset, scale and fill are left to k_small_front (solve_run), if the layout turns out to be one it takes
     bool front_candidate = ss->diag_deferred && (symmetric || c->persist_bicg) && c->small_front_rows > 0 && n <= c->small_front_rows && A == c->vals[FDAPDE_MAT_STIFF].p &&
-                           c->stiff_stat_valid && c->persist && !c->persist_broken && c->spmv_variant == 2;
+                           c->stiff_stat_valid && c->persist && !c->persist_broken;
     if (!front_candidate) HIPCHK(c, hipMemsetAsync(c->ctl.p, 0, 8 * sizeof(int32_t), st));
     if (front_candidate) {
     } else if (ss->dist) {   // the diagonal is a sum over the ranks sharing a DOF
@@ -372,7 +280,7 @@ int solve_prepare(fdapde_ctx* c, const double* A, int use_bnd, SolveState* ss, b
     // symmetric: the single launch is a CG (kernels_persist.h); non-symmetric: a BiCGStab on the plain storage (kernels_persist_bicg.h: six
     // vectors in registers, so at most 8 rows per thread -- larger systems keep the multi-launch BiCGStab)
     c->persist_plain = symmetric ? 0 : 1;
-    if ((symmetric || c->persist_bicg) && ss->diag_positive && !ss->dist && c->persist && !c->persist_broken && c->spmv_variant == 2) {
+    if ((symmetric || c->persist_bicg) && ss->diag_positive && !ss->dist && c->persist && !c->persist_broken) {
         if (int rc = build_persist(c, use_bnd ? 1 : 0)) return rc;
         const fdapde_ctx::Persist& ps = c->ps[use_bnd ? 1 : 0];
         persist = ps.ok && (symmetric || (!ps.meta.sym && ps.meta.R <= 8));
@@ -397,11 +305,11 @@ int solve_prepare(fdapde_ctx* c, const double* A, int use_bnd, SolveState* ss, b
     // blocked form wins on short rows too -- 3-D P1, 8.1 M DOFs: 238 us against 281 us per SpMV, 0.67 against 0.56 of the HBM peak on the layout's own
     // bytes (tools/large_ab.py, profiles/r6_large_ab.txt).
     const bool long_rows = (double)c->hs.nnz >= 20.0 * (double)n || c->blocked == 2 || n > kBlockedShortRowsAbove;
-    if (!persist && ss->diag_positive && !ss->dist && c->blocked && long_rows && c->spmv_variant == 2) {
+    if (!persist && ss->diag_positive && !ss->dist && c->blocked && long_rows) {
         if (int rc = build_blocked(c, use_bnd ? 1 : 0)) return rc;
         blocked = c->bk[use_bnd ? 1 : 0].ok;
     }
-    const bool compact = !persist && !blocked && ss->diag_positive && c->spmv_variant == 2 && !std::getenv("FDAPDE_SPMV_FULL");
+    const bool compact = !persist && !blocked && ss->diag_positive;
     if (compact) {
         const int v = use_bnd ? 1 : 0;
         if (int rc = build_solver_pattern(c, v)) return rc;
@@ -684,9 +592,7 @@ int solve_run(fdapde_ctx* c, const SolveState& ss, const double* A, const double
     hipLaunchKernelGGL((k_cgf_update<__VA_ARGS__>), dim3(cg), dim3(256), 0, st, n, c->y.p, c->p.p, c->x.p, c->r.p, c->part_a.p, np_spmv, \
                        c->part_b.p + (size_t)((it + 1) & 1) * cg, cg, c->part_b.p + (size_t)(it & 1) * cg, c->sc.p, tol2, c->ctl.p, \
                        cgf_band2, c->cgf_nt, c->cgf_lazy, it & 1)
-        if (c->cgf_split && cgf_V == 8) CGF_GO(8, 1);
-        else if (c->cgf_split && cgf_V == 4) CGF_GO(4, 1);
-        else if (cgf_V == 1) CGF_GO(1);
+        if (cgf_V == 1) CGF_GO(1);
         else if (cgf_V == 2) CGF_GO(2);
         else if (cgf_V == 8) CGF_GO(8);
         else CGF_GO(4);
@@ -709,7 +615,7 @@ int solve_run(fdapde_ctx* c, const SolveState& ss, const double* A, const double
             std::memset(&key, 0, sizeof key);   // padding bytes take part in the memcmp below
             key.sval = c->sval.p, key.rowptr = c->sp_cur >= 0 ? (const void*)c->sp_rowptr[c->sp_cur].p : (const void*)c->rowptr.p;
             key.n = n, key.tol2 = tol2, key.chunk = chunk, key.v = cgf_V, key.grid = c->spmv_grid, key.team = c->spmv_team;
-            key.ablate = c->spmv_ablate, key.c16 = c->spmv_c16, key.deep = c->spmv_deep, key.unroll = c->spmv_unroll, key.sp_cur = c->sp_cur;
+            key.c16 = c->spmv_c16, key.sp_cur = c->sp_cur;
             // the blocked-ELL layout the captured SpMV nodes read from (its arrays and grid are baked into the graph)
             key.bk_cur = c->bk_cur, key.bk_G = c->bk_cur >= 0 ? c->bk[c->bk_cur].meta.G : 0;
             key.bk_val = c->bk_cur >= 0 ? (const void*)c->bk[c->bk_cur].ell_val.p : nullptr;
@@ -970,7 +876,6 @@ int e_solver_prepare(fdapde_ctx* c, int32_t with_dirichlet) {
     if (int rc = need_device(c)) return rc;
     if (!c->dev_ready) return fail(c, FDAPDE_ENOTINIT, "call fdapde_dofs_build first");
     HIPCHK(c, hipSetDevice(c->device));
-    if (c->spmv_variant != 2) return FDAPDE_OK;
     const int v = with_dirichlet ? 1 : 0;
     if (c->persist && !c->persist_broken && c->comm == nullptr && c->ar_fn == nullptr && (c->op_symmetric || c->persist_bicg)) {
         // single GPU: the single-launch solver's layout (CG for a symmetric operator, BiCGStab on the plain storage otherwise); when the
@@ -1000,7 +905,7 @@ int e_solver_layout(fdapde_ctx* c, int32_t with_dirichlet, int64_t* n_interior, 
     const int v = with_dirichlet ? 1 : 0;
     const bool persist = c->persist && !c->persist_broken && c->ps[v].tried && c->ps[v].ok;
     const bool blocked = !persist && c->bk[v].tried && c->bk[v].ok;
-    if (c->spmv_variant == 2 && !persist && !blocked)
+    if (!persist && !blocked)
         if (int rc = build_solver_pattern(c, v)) return rc;
     if (int rc = ensure_host(c, kHostPattern)) return rc;
     const HostSpace& hs = c->hs;
@@ -1021,7 +926,7 @@ int e_solver_layout(fdapde_ctx* c, int32_t with_dirichlet, int64_t* n_interior, 
                               (c->ps[v].meta.R > kPersistRmax ? 16.0 * (double)c->ps[v].meta.n_int : 0.0);   // (wide form: x read and written once per row)
         } else if (blocked) {   // ELL blocks + x staged once per block (own rows and imports) + y written once
             *streamed_bytes = 10.0 * (double)c->bk[v].meta.n_entries + 8.0 * (double)(c->bk[v].meta.n_int + c->bk[v].meta.n_imp) + 8.0 * (double)c->bk[v].meta.n_int;
-        } else if (c->spmv_variant == 2 && c->sp_built[v]) {
+        } else if (c->sp_built[v]) {
             const int64_t n_csr = c->sp_nv[v] > 0 ? c->sp_nv[v] : hs.n_dofs;
             *streamed_bytes = 10.0 * (double)c->sp_nnz[v] + 4.0 * (double)(n_csr + 1) + 16.0 * (double)((n_csr + kCodeRows - 1) / kCodeRows) +
                               (c->sp_nv[v] > 0 ? 8.0 * (double)n_csr : 0.0) + 16.0 * (double)hs.n_dofs +
@@ -1841,55 +1746,6 @@ int e_bench_spmv(fdapde_ctx* c, int32_t reps, double* avg_ms, double* algorithmi
     HIPCHK(c, hipEventSynchronize(c->ev1));
     float ms = 0;
     HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    if (std::getenv("FDAPDE_READ_PROBE")) {   // diagnostic: pure read stream of the matrix arrays, same stream, HIP events
-        const int64_t n16 = ((int64_t)hs.nnz * 8) / 16;
-        for (int grid : {1024, 2048, 4096, 8192}) {
-            hipLaunchKernelGGL(k_read_probe, dim3(grid), dim3(256), 0, c->stream, reinterpret_cast<const double2*>(A), n16, c->tmp_i.p);
-            HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-            for (int i = 0; i < 20; ++i)
-                hipLaunchKernelGGL(k_read_probe, dim3(grid), dim3(256), 0, c->stream, reinterpret_cast<const double2*>(A), n16, c->tmp_i.p);
-            HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-            HIPCHK(c, hipEventSynchronize(c->ev1));
-            float pm = 0;
-            HIPCHK(c, hipEventElapsedTime(&pm, c->ev0, c->ev1));
-            std::fprintf(stderr, "read_probe grid=%d: %.1f MB in %.2f us -> %.0f GB/s\n", grid, n16 * 16 / 1e6, pm / 20 * 1e3,
-                         n16 * 16 / (pm / 20 * 1e-3) / 1e9);
-        }
-    }
-    if (std::getenv("FDAPDE_STREAM_PROBE")) {   // diagnostic: the matrix arrays streamed once, nothing else
-        const int64_t n2 = (int64_t)hs.nnz / 2;
-        for (int grid : {2048, 8192}) {
-            hipLaunchKernelGGL(k_stream_probe, dim3(grid), dim3(256), 0, c->stream, reinterpret_cast<const double2*>(A),
-                               reinterpret_cast<const int2*>(c->colidx.p), n2, c->tmp_i.p);
-            HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-            for (int i = 0; i < 50; ++i)
-                hipLaunchKernelGGL(k_stream_probe, dim3(grid), dim3(256), 0, c->stream, reinterpret_cast<const double2*>(A),
-                                   reinterpret_cast<const int2*>(c->colidx.p), n2, c->tmp_i.p);
-            HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-            HIPCHK(c, hipEventSynchronize(c->ev1));
-            float pm = 0;
-            HIPCHK(c, hipEventElapsedTime(&pm, c->ev0, c->ev1));
-            std::fprintf(stderr, "stream_probe grid=%d: %.1f MB in %.2f us -> %.0f GB/s\n", grid, n2 * 24 / 1e6, pm / 50 * 1e3,
-                         n2 * 24 / (pm / 50 * 1e-3) / 1e9);
-            HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-            for (int i = 0; i < 50; ++i)
-                hipLaunchKernelGGL(k_stream_probe_unaligned, dim3(grid), dim3(256), 0, c->stream, A,
-                                   reinterpret_cast<const int2*>(c->colidx.p), n2, c->tmp_i.p);
-            HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-            HIPCHK(c, hipEventSynchronize(c->ev1));
-            HIPCHK(c, hipEventElapsedTime(&pm, c->ev0, c->ev1));
-            std::fprintf(stderr, "stream_probe_unaligned grid=%d: %.2f us -> %.0f GB/s\n", grid, pm / 50 * 1e3,
-                         n2 * 24 / (pm / 50 * 1e-3) / 1e9);
-            HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-            for (int i = 0; i < 50; ++i)
-                hipLaunchKernelGGL(k_stream_probe_w, dim3(grid), dim3(256), 0, c->stream, reinterpret_cast<const double2*>(A),
-                                   reinterpret_cast<const int2*>(c->colidx.p), n2, c->tmp_v.p);
-            HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-            HIPCHK(c, hipEventSynchronize(c->ev1));
-            HIPCHK(c, hipEventElapsedTime(&pm, c->ev0, c->ev1));
-            std::fprintf(stderr, "stream_probe + %.1f MB of writes grid=%d: %.2f us\n", n2 / 8 * 8 / 1e6, grid, pm / 50 * 1e3);
-        }
-    }
     if (avg_ms) *avg_ms = (double)ms / reps;
     if (algorithmic_bytes) *algorithmic_bytes = 12.0 * (double)hs.nnz + 4.0 * (double)(hs.n_dofs + 1) + 16.0 * (double)hs.n_dofs;
     return FDAPDE_OK;

@@ -693,7 +693,7 @@ int host_build_space(HostSpace& hs, int order, std::string& err, int stop_after)
             std::fclose(fp);
         }
     }
-    if (hs.max_row > 65535) {   // (rows longer than kSpmvNnz -- network hubs -- are SpMV row blocks of their own)
+    if (hs.max_row > 65535) {   // (the SpMV itself takes rows of any length -- network hubs -- in further team passes)
         err = "row too long for the uint16 slot map";
         return FDAPDE_EUNSUPPORTED;
     }
@@ -890,18 +890,7 @@ int host_build_space(HostSpace& hs, int order, std::string& err, int stop_after)
     }
 
     phase("block tables");
-    // ---- SpMV row blocks: consecutive rows with at most kSpmvNnz nonzeros -----------------------------------
-    hs.rb_row.clear();
-    hs.rb_row.push_back(0);
-    for (int64_t r = 0; r < nd;) {
-        int64_t e = r;
-        const int32_t base = hs.rowptr_i[(size_t)r];
-        while (e < nd && (e == r || hs.rowptr_i[(size_t)e + 1] - base <= kSpmvNnz) && e - r < 1024) ++e;
-        hs.rb_row.push_back((int32_t)e);
-        r = e;
-    }
     hs.n_colours = 0, hs.colour_off.clear(), hs.colour_cells.clear();
-    phase("spmv row blocks");
     hs.setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return FDAPDE_OK;
 }
@@ -929,7 +918,6 @@ int host_build_solver_pattern(const HostSpace& hs, bool use_bnd, std::vector<int
     // index at or below the row start, and gathers x for all even positions with one instruction and for all odd positions with
     // another.  The row's columns (ascending) are therefore dealt so that the even positions hold the lower half and the odd
     // positions the upper half: each gather instruction then touches about half as many distinct cache lines of x.
-    const bool split = !std::getenv("FDAPDE_SPMV_NOSPLIT");
     parallel_for(nd, [&](int64_t b, int64_t e, unsigned) {
         for (int64_t r = b; r < e; ++r) {
             const int32_t base = rowptr_s[(size_t)r], m = rowptr_s[(size_t)r + 1] - base;
@@ -939,9 +927,7 @@ int host_build_solver_pattern(const HostSpace& hs, bool use_bnd, std::vector<int
             for (int32_t k = hs.rowptr_i[(size_t)r]; k < hs.rowptr_i[(size_t)r + 1]; ++k) {
                 if (!keep(r, hs.colidx_i[(size_t)k])) continue;
                 int32_t at;
-                if (!split)
-                    at = base + j;
-                else if (j < n_even)
+                if (j < n_even)
                     at = base + first_even + 2 * j;
                 else
                     at = base + (1 - first_even) + 2 * (j - n_even);

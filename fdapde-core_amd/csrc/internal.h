@@ -99,12 +99,8 @@ struct HostSpace {
     int n_colours = 0;
     std::vector<int32_t> colour_off;  // n_colours + 1
     std::vector<int32_t> colour_cells;// internal cell ids grouped by colour
-    // ---- SpMV row blocks (CSR-stream): rows [rb_row[b], rb_row[b+1]) hold <= kSpmvNnz nonzeros, or are one longer row
-    std::vector<int32_t> rb_row;
     double setup_ms = 0;
 };
-
-constexpr int kSpmvNnz = 4096;  // products staged in LDS per row block (32 KiB)
 
 int host_set_mesh(HostSpace& hs, int M, int N, int64_t n_nodes, const double* nodes, int64_t n_cells,
                   const int32_t* cells, const uint8_t* bnd, std::string& err);

@@ -398,12 +398,10 @@ int fdapde_partition_peers(fdapde_ctx *ctx, int32_t rank, int32_t *n_peers, int3
                            uint8_t *owned, int64_t *n_shared);
 
 /* tuning / diagnostic knobs (A/B measurements inside one process; defaults are the measured best):
- *   SpMV launch   "spmv_variant" (2 pair form, 0 team form, 1 stream form), "spmv_team", "spmv_unroll", "spmv_bpx" (workgroups
- *                 per XCD band), "spmv_ablate" (diagnostic instantiations), "spmv_c16" (16-bit column codes), "spmv_deep"
- *                 (gathers one tile ahead), "spmv_ntv" (-1 auto / 0 / 1: nontemporal value stream)
+ *   SpMV launch   "spmv_team" (lanes per row: 2, 4, 8, 16, 32), "spmv_bpx" (workgroups per XCD band), "spmv_c16" (16-bit column
+ *                 codes), "spmv_ntv" (-1 auto / 0 / 1: nontemporal value stream)
  *   fused CG      "cgf_v" (double2 per lane), "cgf_band" (XCD-aware mapping), "cgf_nt" (bit set: y, x, r, p nontemporal),
- *                 "cgf_lazy" (x touched every second launch), "cgf_split" (second half of the loads after the scalars),
- *                 "use_graph" (hipGraph replay of a chunk of iterations)
+ *                 "cgf_lazy" (x touched every second launch), "use_graph" (hipGraph replay of a chunk of iterations)
  *   handle        "multi_rhs" (batched multi-column solves)
  *   assembly      "asm_fq_block" (forcing as per-visit load coefficients computed by a kernel of their own inside init),
  *                 "asm_fq_bc" (0: the sweep gathers the forcing samples by cell id instead of reading their block-cell ordered copy),

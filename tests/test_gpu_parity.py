@@ -257,18 +257,23 @@ def test_init_force_mass_spmv(capi, ctx, oracle, mesh_loader, mesh_name, order):
         assert np.abs(y - yr).max() <= 1e-12 * max(1.0, np.abs(yr).max())
 
 
-@pytest.mark.parametrize("variant", ["stream", "team4", "team8", "team16", "team32", "team64", "pair2", "pair4", "pair8", "pair16", "pair32"])
+SPMV_FORMS = ([(f"pair{t}", t, 0, 1) for t in (2, 4, 8, 16, 32)] + [(f"pair{t}-compact", t, 1, 1) for t in (2, 4, 8, 16, 32)] +
+              [(f"team{t}", t, 1, 0) for t in (4, 8, 16, 32)])
+
+
+@pytest.mark.parametrize("team,compact,codes", [f[1:] for f in SPMV_FORMS], ids=[f[0] for f in SPMV_FORMS])
 @pytest.mark.parametrize("mesh_name,order", [("unit_square", 1), ("unit_sphere", 1), ("unit_sphere", 2), ("c_shaped", 2)])
-def test_spmv_variants(capi, ctx, oracle, mesh_loader, monkeypatch, variant, mesh_name, order):
-    """every SpMV kernel form / team width gives the oracle's y = A x (ragged rows, rows longer than a team, tails)"""
-    if variant == "stream":
-        monkeypatch.setenv("FDAPDE_SPMV", "stream")
-    else:
-        monkeypatch.setenv("FDAPDE_SPMV", "team" if variant.startswith("team") else "pair")
-        monkeypatch.setenv("FDAPDE_SPMV_TEAM", variant[4:])
+def test_spmv_variants(capi, ctx, oracle, mesh_loader, team, compact, codes, mesh_name, order):
+    """every team width of the SpMV kernel gives the oracle's y = A x (ragged rows, rows longer than a team, tails), on the raw
+    matrix and inside a solve: pairN on the plain full-pattern copy, pairN-compact on the compact pattern with 16-bit column codes
+    (segmented for the order-2 meshes at widths 8 and 16), teamN on the compact pattern with its 32-bit columns (knob spmv_c16 0;
+    a segmented pattern always reads its codes)"""
     m = mesh_loader(mesh_name)
     ctx.mesh_upload(m.nodes, m.cells, m.boundary)
-    nd = ctx.dofs_build(order)   # the kernel form is chosen here
+    nd = ctx.dofs_build(order)
+    ctx.tune("spmv_team", team)
+    if compact:
+        ctx.tune("persist", 0), ctx.tune("blocked", 0), ctx.tune("spmv_c16", codes)
     od, _, _, _ = oracle.enumerate_dofs(m, order)
     op = lambda mod: -mod.laplacian() + mod.reaction(0.3)
     ctx.assemble_operator(capi.MAT_STIFF, op(capi))
@@ -284,6 +289,8 @@ def test_spmv_variants(capi, ctx, oracle, mesh_loader, monkeypatch, variant, mes
     info = ctx.solve(method=capi.SOLVER_CG, rtol=1e-11)
     sol = oracle.pde_init_solve(m, order, op(oracle), forcing_q=np.ones(ctx.sizes()["n_quadrature"] * m.n_cells))
     assert info.converged == 1
+    if compact:
+        assert info.persistent == 0
     assert np.linalg.norm(ctx.solution() - sol.solution) / np.linalg.norm(sol.solution) <= SOL_TOL
 
 
@@ -683,31 +690,42 @@ def test_lazy_x_update_matches_eager(capi, ctx, oracle, mesh_loader):
     ctx.tune("cgf_lazy", 1)
 
 
+KNOB_DEFAULTS = dict(use_graph=0, spmv_c16=1, cgf_band=1, cgf_nt=7, cgf_lazy=1, cgf_v=8, spmv_ntv=-1)
+KNOB_WALK = [("use_graph", 1), ("spmv_c16", 0), ("cgf_band", 0), ("cgf_nt", 0), ("cgf_lazy", 0), ("cgf_v", 2), ("spmv_ntv", 0), ("spmv_ntv", 1)]
+
+
 def test_tuning_knobs_do_not_change_results(capi, oracle, mesh_loader):
-    """every fdapde_tune knob selects another measured form of the same computation: same iterations, same
-    solution up to rounding"""
+    """every fdapde_tune knob of the multi-launch solvers selects another measured form of the same computation (DESIGN.md section
+    4): same iterations, same solution up to rounding.  The single-launch solver and the blocked layout are off, so that the solve
+    runs the multi-launch kernels on the compact, coded pattern -- the fused-update CG the symmetric system takes by default, BiCGStab
+    on the same mesh with an advection term (dot operands other than x) and the single-reduction CG (w.w as second dot)."""
     from fdapde_core_amd import meshgen
 
     nodes, cells, bnd = meshgen.unit_cube(16)
     c = capi.Context(device=0)
     c.mesh_upload(nodes, cells, bnd)
-    nd = c.dofs_build(1)
+    c.dofs_build(1)
+    c.tune("persist", 0), c.tune("blocked", 0)
     _, _, coords = c.dofs_get()
     qn = c.quadrature_nodes()
-    c.set_operator(-capi.laplacian() + capi.reaction(0.4))
-    c.set_forcing(np.sin(2 * qn[:, 0]) + qn[:, 2])
-    c.set_dirichlet(0.2 * coords[:, 1])
-    c.init()
-    base = c.solve(rtol=1e-11)
-    u0 = c.solution()
-    defaults = dict(spmv_deep=0, use_graph=0, spmv_c16=1, cgf_band=1, cgf_nt=7, cgf_lazy=1, cgf_v=8, cgf_split=0, spmv_ntv=-1, spmv_bpx=None)
-    for key, value in [("spmv_deep", 1), ("use_graph", 1), ("spmv_c16", 0), ("cgf_band", 0), ("cgf_nt", 0), ("cgf_lazy", 0), ("cgf_v", 2), ("cgf_split", 1),
-                       ("spmv_ntv", 1), ("spmv_ablate", 150), ("spmv_ablate", 151), ("spmv_ablate", 152), ("spmv_ablate", 3)]:
-        c.tune(key, value)
-        info = c.solve(rtol=1e-11)
-        assert info.converged == 1 and abs(info.iters - base.iters) <= 1, (key, value, info.iters, base.iters)
-        assert np.abs(c.solution() - u0).max() <= 1e-10 * np.abs(u0).max(), (key, value)
-        c.tune(key, 0 if key == "spmv_ablate" else defaults[key])
+    sym = -capi.laplacian() + capi.reaction(0.4)
+    for op, method, used in [(sym, capi.SOLVER_AUTO, capi.SOLVER_CG_FUSED),
+                             (sym + capi.advection(np.array([0.7, -0.2, 0.4])), capi.SOLVER_BICGSTAB, capi.SOLVER_BICGSTAB),
+                             (sym, capi.SOLVER_CG_SR, capi.SOLVER_CG_SR)]:
+        c.set_operator(op)
+        c.set_forcing(np.sin(2 * qn[:, 0]) + qn[:, 2])
+        c.set_dirichlet(0.2 * coords[:, 1])
+        c.init()
+        base = c.solve(method=method, rtol=1e-11)
+        assert base.converged == 1 and base.persistent == 0 and base.method_used == used
+        u0 = c.solution()
+        for key, value in KNOB_WALK:
+            c.tune(key, value)
+            info = c.solve(method=method, rtol=1e-11)
+            assert info.persistent == 0 and info.method_used == used
+            assert info.converged == 1 and abs(info.iters - base.iters) <= 1, (used, key, value, info.iters, base.iters)
+            assert np.abs(c.solution() - u0).max() <= 1e-10 * np.abs(u0).max(), (used, key, value)
+            c.tune(key, KNOB_DEFAULTS[key])
     c.close()
 
 

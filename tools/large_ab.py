@@ -44,8 +44,6 @@ fq = f(c0.quadrature_nodes())
 c0.close()
 print(f"3-D P1 Laplacian, nx {nx}: SpMV of the multi-launch CG (fdapde_bench_spmv, 40 launches, HIP events), bytes = the kernel's own layout")
 variant("default", [])
-for key, vals in (("spmv_team", (8,)), ("spmv_unroll", (2, 8)), ("spmv_ntv", (0, 1)), ("spmv_c16", (0,)), ("spmv_deep", (1,)), ("spmv_bpx", (64, 512)),
-                  ("spmv_variant", (0,)), ("blocked", (2,))):
+for key, vals in (("spmv_team", (8,)), ("spmv_ntv", (0, 1)), ("spmv_c16", (0,)), ("spmv_bpx", (64, 512)), ("blocked", (2,))):
     for v in vals:
         variant(f"{key} = {v}", [(key, v)])
-variant("spmv_team = 8, spmv_unroll = 8", [("spmv_team", 8), ("spmv_unroll", 8)])
