@@ -47,7 +47,7 @@ SYMBOLS = [
     "fdapde_info_get", "fdapde_spmv", "fdapde_bench_spmv", "fdapde_tune", "fdapde_stream", "fdapde_synchronize",
     "fdapde_comm_unique_id", "fdapde_comm_init", "fdapde_halo_setup", "fdapde_solve_parabolic",
     "fdapde_lin_compute", "fdapde_lin_solve", "fdapde_eval_pointwise", "fdapde_cell_integrals", "fdapde_comm_init_callback", "fdapde_comm_set_exchange_callback", "fdapde_halo_setup_peers",
-    "fdapde_solver_layout", "fdapde_topology_build", "fdapde_topology_get", "fdapde_comm_allreduce", "fdapde_comm_library", "fdapde_solver_layout_kind", "fdapde_solver_layout_partition", "fdapde_rowdist_setup", "fdapde_ctx_clone", "fdapde_comm_count",
+    "fdapde_solver_layout", "fdapde_topology_build", "fdapde_topology_get", "fdapde_comm_allreduce", "fdapde_comm_library", "fdapde_solver_layout_kind", "fdapde_solver_layout_partition", "fdapde_solver_trace", "fdapde_rowdist_setup", "fdapde_ctx_clone", "fdapde_comm_count",
     "fdapde_ctx_create_multi", "fdapde_ctx_devices", "fdapde_partition_build", "fdapde_partition_sizes", "fdapde_partition_get", "fdapde_partition_whole",
     "fdapde_partition_peers",
 ]
@@ -380,8 +380,9 @@ class Context:
         v = None if values is None else np.ascontiguousarray(values, dtype=float)
         self._check(self.lib.fdapde_lin_compute(self._ctx, which, None if v is None else _dp(v), 1 if symmetric else 0))
 
-    def lin_solve(self, b, method=SOLVER_AUTO, rtol=1e-10, check_every=0, maxit=0):
-        """fdapde::SparseLU::solve(b); b (n_dofs,) or (n_dofs, n_rhs)"""
+    def lin_solve(self, b, method=SOLVER_AUTO, rtol=1e-10, check_every=0, maxit=0, raise_on_noconv=True):
+        """fdapde::SparseLU::solve(b); b (n_dofs,) or (n_dofs, n_rhs).  raise_on_noconv=False: FDAPDE_ENOCONV is reported through
+        info.converged only, and x holds the last iterate of every column (as after solve)"""
         b = np.asarray(b, dtype=float)
         one = b.ndim == 1
         B = b.reshape(b.shape[0], -1)
@@ -389,7 +390,9 @@ class Context:
         out = np.zeros_like(flat)
         opt = Options(method=method, maxit=maxit, rtol=rtol, assembly=0, check_every=check_every, time_spmv=0)
         info = Info()
-        self._check(self.lib.fdapde_lin_solve(self._ctx, C.byref(opt), _dp(flat), B.shape[1], _dp(out), C.byref(info)))
+        rc = self.lib.fdapde_lin_solve(self._ctx, C.byref(opt), _dp(flat), B.shape[1], _dp(out), C.byref(info))
+        if rc != OK and (raise_on_noconv or rc != ENOCONV):
+            self._check(rc)
         X = np.ascontiguousarray(out.reshape(B.shape[1], B.shape[0]).T)
         return (X[:, 0] if one else X), info
 
@@ -493,6 +496,12 @@ class Context:
         p = C.c_int32()
         self._check(self.lib.fdapde_solver_layout_partition(self._ctx, 1 if with_dirichlet else 0, C.byref(p)))
         return p.value
+
+    def solver_trace(self):
+        """dict(small_front: the last solve's front ran as k_small_front, graph_replays: chunks of it replayed from a captured graph)"""
+        f, g = C.c_int32(), C.c_int32()
+        self._check(self.lib.fdapde_solver_trace(self._ctx, C.byref(f), C.byref(g)))
+        return dict(small_front=f.value, graph_replays=g.value)
 
     # ---- multi-GPU
     @staticmethod

@@ -270,6 +270,12 @@ int fdapde_solver_layout_partition(fdapde_ctx* c, int32_t with_dirichlet, int32_
     if (partition) *partition = (kind == 2 || kind == 3) && ps.ok ? (ps.meta.bisect ? 1 : 0) : -1;
     return FDAPDE_OK;
 }
+int fdapde_solver_trace(fdapde_ctx* c, int32_t* small_front, int32_t* graph_replays) {
+    if (!c) return FDAPDE_EINVAL;
+    if (small_front) *small_front = c->front_used ? 1 : 0;
+    if (graph_replays) *graph_replays = c->graph_replays;
+    return FDAPDE_OK;
+}
 int fdapde_solve(fdapde_ctx* c, const fdapde_options* opt, fdapde_info* info) {
     if (!c) return FDAPDE_EINVAL;
     if (c->group && opt && opt->method == FDAPDE_SOLVER_AMG) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_AMG takes one-GPU contexts, not a multi-device context");

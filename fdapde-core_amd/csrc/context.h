@@ -270,6 +270,7 @@ struct fdapde_ctx {
     int spmv_c16 = 1;                        // tuning knob: 0 = always stream the 32-bit columns
     int use_graph = 0;                       // tuning knob: replay full chunks of the fused-update CG as one hipGraph
     hipGraphExec_t cg_graph_exec = nullptr;
+    int graph_replays = 0;                   // chunks of the last solve_run that were replayed from the captured graph (fdapde_solver_trace)
     GraphKey cg_graph_key{};
     int cgf_lazy = 1;                        // tuning knob: x updated every second launch of k_cgf_update (C3 solve 33.3 -> 32.5 ms, same iterations)
     int cgf_nt = 7;                          // tuning knob, bit set: nontemporal y (1), x (2), r (4), p load (8) in k_cgf_update

@@ -427,6 +427,7 @@ int solve_run(fdapde_ctx* c, const SolveState& ss, const double* A, const double
     // nothing of an earlier solve may be read as this one's outcome by a caller that sees an early return (solve_run_restarting)
     c->h_ctl[0] = c->h_ctl[1] = c->h_ctl[2] = c->h_ctl[3] = 0, c->h_ctl_seen = 4;
     c->info.iters = 0, c->info.method_used = method, c->info.relres = 0, c->info.converged = 0;
+    c->graph_replays = 0;
     // partial pairs the SpMV leaves for the vector kernels: one per workgroup of the kernel that applies the scaled operator
     const int np_spmv = (c->bk_cur >= 0 && !dist) ? c->bk[c->bk_cur].meta.G : c->spmv_grid;
     const double* fvec = f_dev;
@@ -634,7 +635,7 @@ int solve_run(fdapde_ctx* c, const SolveState& ss, const double* A, const double
                 }
                 (void)hipGetLastError();
             }
-            if (c->cg_graph_exec && hipGraphLaunch(c->cg_graph_exec, st) == hipSuccess) launched += chunk, graphed = true;
+            if (c->cg_graph_exec && hipGraphLaunch(c->cg_graph_exec, st) == hipSuccess) launched += chunk, graphed = true, ++c->graph_replays;
         }
         for (int it = 0; !graphed && it < chunk; ++it, ++launched) {
             if (cgsr) {
@@ -730,6 +731,17 @@ int solve_run(fdapde_ctx* c, const SolveState& ss, const double* A, const double
         HIPCHK(c, hipMemcpyAsync(c->h_sc, c->sc.p, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));
         stop = c->h_ctl[0] != 0;
+    }
+    if (cgsr && !stop && launched > 0 && !dist) {
+        // single-reduction CG out of iterations: sc[3] is the gamma = r.r its last SpMV measured, the residual BEFORE the last update.  info.relres is
+        // the residual of the x that is handed out: r.r of the last update, summed here (r vanishes on the Dirichlet rows).  A run whose LAST
+        // permitted update meets rtol therefore reports converged = 1 (the stale gamma said 0: the next SpMV would have seen it).  One GPU only:
+        // the element-partitioned form (dist) would need an all-reduce of its own for this and still reports the gamma of before its last update.
+        hipLaunchKernelGGL(k_sq_norm, dim3(c->vec_grid), dim3(256), 0, st, n, c->r.p, c->part_b.p);
+        hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(256), 0, st, c->part_b.p, c->vec_grid, c->sc.p + 3);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(c->h_sc, c->sc.p, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
     }
     if (launched == 0 && !persisted) {   // already converged at the initial guess
         HIPCHK(c, hipMemcpyAsync(c->h_ctl, c->ctl.p, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -1390,7 +1402,8 @@ int lin_solve_batch(fdapde_ctx* c, const double* b_ext, double* x_ext, double rt
     HIPCHK(c, hipMemcpyAsync(h_sc.data(), sc.p, sizeof(double) * 5 * Q, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipMemcpyAsync(c->h_ctl, c->ctl.p, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    *iters = c->h_ctl[1], *converged = c->h_ctl[2] == 0, *relres = 0;
+    // (the scalar pass behind an exhausted budget counts itself where no column has converged: iterations are what was applied to x)
+    *iters = std::min<int>(c->h_ctl[1], launched), *converged = c->h_ctl[2] == 0, *relres = 0;
     for (int q = 0; q < Q; ++q) {
         const double bb = h_sc[(size_t)q], rr = h_sc[(size_t)Q + q];
         const double rel = bb > 0 ? sqrt(rr / bb) : 0.0;

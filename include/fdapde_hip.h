@@ -60,7 +60,9 @@ typedef struct {
 } fdapde_term;
 
 /* CG_SR: single-reduction (Chronopoulos-Gear) CG: same iterates, both dot products fused into the SpMV, two launches and
- * (multi-GPU) one all-reduce per iteration */
+ * (multi-GPU) one all-reduce per iteration.  Out of iterations (opt->maxit) on one GPU, info.relres is r.r of the iterate handed out, summed
+ * once more behind the last update -- so a run whose last permitted update meets rtol reports converged = 1; the element-partitioned
+ * (multi-GPU) form still reports the r.r its last SpMV measured, the residual of the iterate BEFORE its last update */
 /* CG_FUSED: the SpMV carries p.Ap and Ap.Ap, ONE kernel then updates x, r, p: alpha from the explicit r.r, beta from the
  * estimate alpha^2 Ap.Ap - r.r (only the search direction sees the estimate); two launches per iteration, single GPU */
 /* FDAPDE_SOLVER_AUTO: Jacobi-PCG for a symmetric operator with a positive diagonal, Jacobi-BiCGStab otherwise; if CG breaks down (p.Ap <= 0: the
@@ -272,7 +274,11 @@ int fdapde_solve_parabolic(fdapde_ctx *ctx, const fdapde_options *opt, int32_t n
  * pattern; symmetric != 0 allows CG), or NULL to take the assembled matrix `which`.  No Dirichlet reduction is applied.
  * fdapde_lin_solve = ::solve(b): dense right-hand sides, b and x column-major n_dofs x n_rhs.  Several columns are worth handing over
  * together: the columns of a small system run side by side in one launch (6 us instead of 300 us per column for 289 DOFs x 64).
- * x may overlap b (an in-place solve): the call then works from a private copy of the right-hand sides. */
+ * x may overlap b (an in-place solve): the call then works from a private copy of the right-hand sides.
+ * FDAPDE_ENOCONV for an exhausted iteration budget (opt->maxit): x then holds the last iterate of every column, on every path (the direct
+ * launch of one column, columns side by side, column by column, batches of 8 / 4), as fdapde_solution does after fdapde_solve.
+ * info->iters of a call with several columns: columns side by side or one by one add up their own counts; a batch of 8 / 4 counts the
+ * iterations of its slowest column (the finished ones are frozen), and the batches add up.  info->relres is the worst column's. */
 int fdapde_lin_compute(fdapde_ctx *ctx, int32_t which, const double *values, int32_t symmetric);
 int fdapde_lin_solve(fdapde_ctx *ctx, const fdapde_options *opt, const double *b, int32_t n_rhs, double *x, fdapde_info *info);
 
@@ -315,6 +321,10 @@ int fdapde_solver_layout_kind(fdapde_ctx *ctx, int32_t with_dirichlet, int32_t *
 /* How the rows of a single persistent launch are dealt to its workgroups: 0 contiguous chunks of the internal order, 1 recursive coordinate
  * bisection (fdapde_tune "persist_partition"; with 1 or 2 the chunks remain where the bisection layout does not fit); -1: no such layout. */
 int fdapde_solver_layout_partition(fdapde_ctx *ctx, int32_t with_dirichlet, int32_t *partition);
+/* Two paths of the last solve on this context that leave no other trace (the tests assert them): small_front = 1 if everything in front of a
+ * one-workgroup single launch ran as one kernel (fdapde_tune "small_front_rows"; plain storage only), graph_replays = the chunks of the
+ * fused-update CG that were replayed from a captured graph (fdapde_tune "use_graph": a capture that fails falls back to plain launches). */
+int fdapde_solver_trace(fdapde_ctx *ctx, int32_t *small_front, int32_t *graph_replays);
 /* ---- multi-GPU: element-partitioned meshes, one context (= one rank) per GPU --------------------------------------------
  * No reference counterpart (the reference is single-threaded, single address space).  Each rank uploads the sub-mesh of
  * its own cells (local node numbering), assembles its sub-assembled operator with the calls above, and the solve sums the

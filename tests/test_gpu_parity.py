@@ -673,21 +673,26 @@ def test_lazy_x_update_matches_eager(capi, ctx, oracle, mesh_loader):
     ctx.init()
     seen = set()
     cases = [dict(rtol=10.0 ** -k) for k in range(3, 13)] + [dict(rtol=1e-30, maxit=k) for k in (1, 2, 31, 32, 33, 64)]
-    for kw in cases:
-        sol = {}
-        for lazy in (0, 1):
-            ctx.tune("cgf_lazy", lazy)
-            try:
-                info = ctx.solve(method=capi.SOLVER_CG_FUSED, **kw)
-            except capi.FdapdeError as e:
-                assert e.status == capi.ENOCONV
-                info = ctx.info()
-            sol[lazy] = (ctx.solution(), info.iters)
-        assert sol[0][1] == sol[1][1]
-        seen.add(sol[0][1] & 1)
-        assert np.abs(sol[0][0] - sol[1][0]).max() <= 1e-13 * np.abs(sol[0][0]).max(), kw
-    assert seen == {0, 1}          # both parities of the last executed update were exercised
-    ctx.tune("cgf_lazy", 1)
+    ctx.tune("persist", 0)   # (with the single launch on, both arms would run k_cg_persist, which has no lazy form: cgf_lazy would never be compared)
+    try:
+        for kw in cases:
+            sol = {}
+            for lazy in (0, 1):
+                ctx.tune("cgf_lazy", lazy)
+                try:
+                    info = ctx.solve(method=capi.SOLVER_CG_FUSED, **kw)
+                except capi.FdapdeError as e:
+                    assert e.status == capi.ENOCONV
+                    info = ctx.info()
+                assert info.persistent == 0 and info.method_used == capi.SOLVER_CG_FUSED
+                sol[lazy] = (ctx.solution(), info.iters)
+            assert sol[0][1] == sol[1][1]
+            seen.add(sol[0][1] & 1)
+            assert np.abs(sol[0][0] - sol[1][0]).max() <= 1e-13 * np.abs(sol[0][0]).max(), kw
+        assert seen == {0, 1}          # both parities of the last executed update were exercised
+    finally:
+        ctx.tune("cgf_lazy", 1)
+        ctx.tune("persist", 1)   # (the context is shared by the module)
 
 
 KNOB_DEFAULTS = dict(use_graph=0, spmv_c16=1, cgf_band=1, cgf_nt=7, cgf_lazy=1, cgf_v=8, spmv_ntv=-1)
