@@ -46,7 +46,7 @@ SYMBOLS = [
     "fdapde_init", "fdapde_assemble_operator", "fdapde_solver_prepare", "fdapde_solve", "fdapde_matrix_values", "fdapde_lump", "fdapde_force", "fdapde_solution",
     "fdapde_info_get", "fdapde_spmv", "fdapde_bench_spmv", "fdapde_tune", "fdapde_stream", "fdapde_synchronize",
     "fdapde_comm_unique_id", "fdapde_comm_init", "fdapde_halo_setup", "fdapde_solve_parabolic",
-    "fdapde_lin_compute", "fdapde_lin_solve", "fdapde_eval_pointwise", "fdapde_cell_integrals", "fdapde_comm_init_callback", "fdapde_comm_set_exchange_callback", "fdapde_halo_setup_peers",
+    "fdapde_lin_compute", "fdapde_lin_solve", "fdapde_eval_pointwise", "fdapde_project", "fdapde_cell_integrals", "fdapde_comm_init_callback", "fdapde_comm_set_exchange_callback", "fdapde_halo_setup_peers",
     "fdapde_solver_layout", "fdapde_topology_build", "fdapde_topology_get", "fdapde_comm_allreduce", "fdapde_comm_library", "fdapde_solver_layout_kind", "fdapde_solver_layout_partition", "fdapde_solver_trace", "fdapde_rowdist_setup", "fdapde_ctx_clone", "fdapde_comm_count",
     "fdapde_ctx_create_multi", "fdapde_ctx_devices", "fdapde_partition_build", "fdapde_partition_sizes", "fdapde_partition_get", "fdapde_partition_whole",
     "fdapde_partition_peers",
@@ -415,6 +415,29 @@ class Context:
         cols = dofs[cells[ok]].reshape(-1)
         psi = sp.csr_matrix((vals[ok].reshape(-1), (rows, cols)), shape=(nl, s["n_dofs"]))
         return psi, np.ones(nl), cells
+
+    def project(self, points, values=True):
+        """Projection<Triangulation>(points, Exact) -> (Psi csr n_pts x n_dofs, cell ids, projected points n_pts x N, distances): every point
+        onto its nearest cell, Psi the basis at the projected point (None with values=False).  Every row is filled."""
+        import scipy.sparse as sp
+
+        pts = np.asarray(points, dtype=float)
+        if pts.ndim == 1:
+            pts = pts.reshape(-1, 1)
+        n, dim, s = pts.shape[0], pts.shape[1], self.sizes()
+        flat = np.ascontiguousarray(pts.T).reshape(-1)
+        cells = np.zeros(n, dtype=np.int32)
+        proj = np.zeros(n * dim)
+        dist = np.zeros(n)
+        vals = np.zeros((n, s["n_basis"])) if values else None
+        self._check(self.lib.fdapde_project(self._ctx, C.c_int64(n), _dp(flat), _ip(cells), _dp(proj), _dp(dist), _dp(vals) if values else None))
+        projected = np.ascontiguousarray(proj.reshape(dim, n).T)
+        if not values:
+            return None, cells, projected, dist
+        dofs, _, _ = self.dofs_get()
+        rows = np.repeat(np.arange(n), s["n_basis"])
+        psi = sp.csr_matrix((vals.reshape(-1), (rows, dofs[cells].reshape(-1))), shape=(n, s["n_dofs"]))
+        return psi, cells, projected, dist
 
     def eval_areal(self, incidence):
         """areal_evaluation::eval: incidence (n_sub, n_cells) of 0/1 -> (Psi csr n_sub x n_dofs, D = subdomain measures)"""

@@ -89,7 +89,7 @@ void fdapde_ctx_destroy(fdapde_ctx* c) {
                                 &c->x, &c->r, &c->p, &c->y, &c->s, &c->t, &c->r0, &c->u, &c->part_a, &c->part_b, &c->sc,
                                 &c->tmp_e, &c->tmp_i, &c->tmp_v, &c->lin_rhs, &c->cols_b, &c->cols_r, &c->cols_x, &c->cols_sc, &c->cols_part})
             b->release();
-        c->cols_ctl.release(), c->eval_grid.release(), c->eval_locs.release(), c->eval_vals.release(), c->eval_out.release();
+        c->cols_ctl.release(), c->eval_grid.release(), c->eval_locs.release(), c->eval_vals.release(), c->eval_out.release(), c->proj_q.release(), c->proj_d.release();
         for (auto& b : c->coef) b.release();
         c->slotw.release(), c->sl_off.release(), c->lane_row.release(), c->fq_blk.release(), c->bnd.release(), c->tables.release(), c->reftab.release(), c->reftab_sym.release(), c->lin_sq.release();
         c->bc_off.release(), c->bn_off.release(), c->bc_cell.release(), c->bn_node.release(), c->bc_vert.release();
@@ -243,6 +243,10 @@ int fdapde_init(fdapde_ctx* c, const fdapde_options* opt) {
 int fdapde_eval_pointwise(fdapde_ctx* c, int64_t n_locs, const double* locs_colmajor, int32_t* cell_ids, double* values) {
     if (!c) return FDAPDE_EINVAL;
     return fdapde_engine::e_eval_pointwise(c, n_locs, locs_colmajor, cell_ids, values);
+}
+int fdapde_project(fdapde_ctx* c, int64_t n_pts, const double* pts_colmajor, int32_t* cell_ids, double* proj_colmajor, double* dist, double* values) {
+    if (!c) return FDAPDE_EINVAL;
+    return fdapde_engine::e_project(c, n_pts, pts_colmajor, cell_ids, proj_colmajor, dist, values);   // (a multi-device context: its own whole mesh, as above)
 }
 int fdapde_cell_integrals(fdapde_ctx* c, double* measure, double* psi_int) {
     if (!c) return FDAPDE_EINVAL;

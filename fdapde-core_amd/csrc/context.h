@@ -413,6 +413,7 @@ struct fdapde_ctx {
     } eval_grid;
     DBuf<double> eval_locs, eval_vals;   // locations / basis values of a call (kept between calls)
     DBuf<int32_t> eval_out;
+    DBuf<double> proj_q, proj_d;         // fdapde_project: projected points / distances of a call (it shares eval_locs, eval_vals, eval_out)
     std::function<int()> persist_tail;      // what run_persist enqueues behind the launch and its read-backs, before it waits (solve_run's epilogue)
     int h_ctl_seen = 4;                      // how many words of ctl the last outcome read-back fetched into h_ctl
     bool ev1_at_end = false;                 // fdapde_solve: solve_run records ev1 right before its final wait (no event wait of the caller's own)

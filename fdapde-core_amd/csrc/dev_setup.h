@@ -45,7 +45,9 @@ struct DevBinGrid {
     double lo[3] = {0, 0, 0}, inv_h[3] = {0, 0, 0};
     int32_t dims[3] = {1, 1, 1};
 };
-// M: the dimension binned over (the embedding dimension N of the mesh), NV: vertices per cell (M + 1; 2 for the segments of a network in R^2)
+// M: the dimension binned over (the embedding dimension N of the mesh), NV: vertices per cell (M + 1; 2 for the segments of a network in R^2; 3 for the
+// triangles of a surface in R^3, which only fdapde_project searches).  An axis of zero extent (a horizontal sheet, a network on one horizontal line)
+// gets inv_h = 0 and every cell in its bin 0; the other dims[d] - 1 bins of that axis stay empty.
 int dev_build_bin_grid(int M, int NV, int64_t n_nodes, int64_t n_cells, const double* d_vcoords, const int32_t* d_cverts, void* stream, DevBinGrid* out,
                        std::string& err);
 

@@ -504,7 +504,7 @@ template <typename In, typename Out> int exclusive_sum(Scratch& sc, In* in, Out*
 
 // ---- bin grid for point location (dev_build_bin_grid) ----------------------------------------------------------------------------------
 // M: the binning dimension = the embedding dimension N (1 for an interval, 2 for a plane mesh or a network in R^2, 3); NV: vertices per cell
-// (M + 1, or 2 for the segments of a network in R^2)
+// (M + 1, or 2 for the segments of a network in R^2, or 3 for the triangles of a surface in R^3)
 template <int M> struct BinGeo {
     double lo[M], inv_h[M];
     int32_t dims[M];
@@ -605,7 +605,7 @@ int morton_order(Scratch& sc, int N, int64_t n, const double* d_pts, int bits, h
 int dev_build_bin_grid(int M, int NV, int64_t n_nodes, int64_t n_cells, const double* d_vcoords, const int32_t* d_cverts, void* stream, DevBinGrid* out,
                        std::string& err) {
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (!out || M < 1 || M > 3 || !(NV == M + 1 || (M == 2 && NV == 2)) || n_nodes < 1 || n_cells < 1) return FDAPDE_EINVAL;
+    if (!out || M < 1 || M > 3 || !(NV == M + 1 || (M == 2 && NV == 2) || (M == 3 && NV == 3)) || n_nodes < 1 || n_cells < 1) return FDAPDE_EINVAL;
     const int NP = M <= 2 ? 2 : 4;
     Scratch sc;
     // bounding box
@@ -656,6 +656,9 @@ int dev_build_bin_grid(int M, int NV, int64_t n_nodes, int64_t n_cells, const do
         } else if (M == 2) {                                                 \
             constexpr int NV_ = 3;                                           \
             BIN_GO(2, FILL_, CNT_, CELLS_);                                  \
+        } else if (NV == 3) {   /* triangles of a surface in R^3 */          \
+            constexpr int NV_ = 3;                                           \
+            BIN_GO(3, FILL_, CNT_, CELLS_);                                  \
         } else {                                                             \
             constexpr int NV_ = 4;                                           \
             BIN_GO(3, FILL_, CNT_, CELLS_);                                  \

@@ -648,8 +648,27 @@ int e_init(fdapde_ctx* c, const fdapde_options* opt) {
     return FDAPDE_OK;
 }
 
+// uniform bin grid over the mesh, built on the device once per mesh (dev_setup.hip dev_build_bin_grid; it was a serial host loop over
+// the cells on every call: 80 % of a call with 10^6 locations on a 10^6-cell mesh).  Shared by fdapde_eval_pointwise and fdapde_project.
+int ensure_eval_grid(fdapde_ctx* c) {
+    fdapde_ctx::EvalGrid& eg = c->eval_grid;
+    if (eg.ready) return FDAPDE_OK;
+    const HostSpace& hs = c->hs;
+    hipStream_t st = c->stream;
+    DevBinGrid g;
+    // (bins span the embedding space: a network in R^2 is binned over the plane, a surface over R^3)
+    if (int rc = dev_build_bin_grid(hs.N, hs.M + 1, hs.n_nodes, hs.n_cells, c->vcoords.p, c->cverts.p, st, &g, c->err)) return rc;
+    adopt(eg.ptr, g.bin_ptr, (size_t)g.n_bins + 1), adopt(eg.cells, g.bin_cells, (size_t)g.n_entries + 1);
+    HIPCHK(c, eg.dims.upload(g.dims, 3, st));
+    HIPCHK(c, eg.lo.upload(g.lo, 3, st));
+    HIPCHK(c, eg.invh.upload(g.inv_h, 3, st));
+    HIPCHK(c, hipStreamSynchronize(st));   // (g's small arrays live on this stack frame)
+    eg.ready = true;
+    return FDAPDE_OK;
+}
+
 // pointwise_evaluation::eval (basis/lagrangian_basis.h:203-235): locate + evaluate.  The bin grid over the cells' bounding
-// boxes is built on the host per call (index work, like the reference's KD-tree build at first use, tree_search.h:47-62).
+// boxes is built at first use (ensure_eval_grid; like the reference's KD-tree build at first use, tree_search.h:47-62).
 int e_eval_pointwise(fdapde_ctx* c, int64_t n_locs, const double* locs_colmajor, int32_t* cell_ids, double* values) {
     if (!c || n_locs < 1 || !locs_colmajor || !cell_ids || !values) return FDAPDE_EINVAL;
     if (int rc = need_device(c)) return rc;
@@ -658,29 +677,19 @@ int e_eval_pointwise(fdapde_ctx* c, int64_t n_locs, const double* locs_colmajor,
     const HostSpace& hs = c->hs;
     const int M = hs.M;
     if (hs.N != M && M != 1)
-        return fail(c, FDAPDE_EUNSUPPORTED, "fdapde_eval_pointwise on a surface mesh (Triangulation<2,3>): locating a point needs its projection onto the surface, "
-                                            "which is not built");
+        return fail(c, FDAPDE_EUNSUPPORTED, "fdapde_eval_pointwise on a surface mesh (Triangulation<2,3>): a measured location is not on the flat triangles of a "
+                                            "surface; fdapde_project gives its nearest cell, its projection and the basis values there");
     hipStream_t st = c->stream;
-    // uniform bin grid over the mesh, built on the device once per mesh (dev_setup.hip dev_build_bin_grid; it was a serial host loop over
-    // the cells on every call: 80 % of a call with 10^6 locations on a 10^6-cell mesh)
+    if (int rc = ensure_eval_grid(c)) return rc;
     fdapde_ctx::EvalGrid& eg = c->eval_grid;
-    if (!eg.ready) {
-        DevBinGrid g;
-        // (bins span the embedding space: a network in R^2 is binned over the plane)
-        if (int rc = dev_build_bin_grid(hs.N, M + 1, hs.n_nodes, hs.n_cells, c->vcoords.p, c->cverts.p, st, &g, c->err)) return rc;
-        adopt(eg.ptr, g.bin_ptr, (size_t)g.n_bins + 1), adopt(eg.cells, g.bin_cells, (size_t)g.n_entries + 1);
-        HIPCHK(c, eg.dims.upload(g.dims, 3, st));
-        HIPCHK(c, eg.lo.upload(g.lo, 3, st));
-        HIPCHK(c, eg.invh.upload(g.inv_h, 3, st));
-        HIPCHK(c, hipStreamSynchronize(st));   // (g's small arrays live on this stack frame)
-        eg.ready = true;
-    }
     HIPCHK(c, c->eval_locs.upload(locs_colmajor, (size_t)n_locs * hs.N, st));
     HIPCHK(c, c->eval_out.alloc((size_t)n_locs));
     HIPCHK(c, c->eval_vals.alloc((size_t)n_locs * hs.nb));
     AsmArgs a = asm_args(c);
     const double tol = 1e-12;
     const dim3 grid(g1(n_locs)), block(256);
+    static const bool timed = std::getenv("FDAPDE_DEBUG_TIMING") != nullptr;
+    if (timed) HIPCHK(c, hipEventRecord(c->ev0, st));
 #define EVAL_GO(MM, RR, NN)                                                                                              \
     hipLaunchKernelGGL((k_eval_pointwise<MM, RR, NN>), grid, block, 0, st, a, n_locs, c->eval_locs.p, eg.lo.p, eg.invh.p, eg.dims.p, eg.ptr.p, \
                        eg.cells.p, c->cell_i2e.p, tol, c->eval_out.p, c->eval_vals.p)
@@ -696,6 +705,13 @@ int e_eval_pointwise(fdapde_ctx* c, int64_t n_locs, const double* locs_colmajor,
     else EVAL_GO(3, 2, 3);
 #undef EVAL_GO
     HIPCHK(c, hipGetLastError());
+    if (timed) {   // (the kernel alone, on stderr: tools/project_time.py reads it)
+        float ms = 0;
+        HIPCHK(c, hipEventRecord(c->ev1, st));
+        HIPCHK(c, hipEventSynchronize(c->ev1));
+        HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        std::fprintf(stderr, "[timing] %-34s %8.3f ms\n", "k_eval_pointwise", (double)ms);
+    }
     HIPCHK(c, hipMemcpyAsync(cell_ids, c->eval_out.p, sizeof(int32_t) * (size_t)n_locs, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipMemcpyAsync(values, c->eval_vals.p, sizeof(double) * (size_t)n_locs * hs.nb, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));

@@ -66,6 +66,8 @@ int ranks_saying_yes(fdapde_ctx* c, bool mine, int* yes);                // eng_
 int allreduce_sum(fdapde_ctx* c, double* buf, size_t count);               // eng_dist.hip: device buffer summed over the ranks
 int halo_sum(fdapde_ctx* c, double* v, const double* part, int np, bool unpack = true);   // eng_dist.hip: interface entries summed over the sharing ranks
 
+int ensure_eval_grid(fdapde_ctx* c);                                       // eng_assembly.hip: the bin grid of point location and projection, once per mesh
+
 // ---- the bodies behind the C ABI (capi.hip forwards to them; each unit's header comment says what it holds) ----------------------------
 int e_ctx_clone(const fdapde_ctx* src, fdapde_ctx* dst);   // eng_clone.hip
 int clone_state(const fdapde_ctx* src, fdapde_ctx* dst);   // ... its second half: problem data + assembled / solved state onto an identical space
@@ -84,6 +86,7 @@ int e_assemble_operator(fdapde_ctx* c, int32_t which, int32_t n_terms, const fda
 int e_init(fdapde_ctx* c, const fdapde_options* opt);
 int e_eval_pointwise(fdapde_ctx* c, int64_t n_locs, const double* locs_colmajor, int32_t* cell_ids, double* values);
 int e_cell_integrals(fdapde_ctx* c, double* measure, double* psi_int);
+int e_project(fdapde_ctx* c, int64_t n_pts, const double* pts_colmajor, int32_t* cell_ids, double* proj_colmajor, double* dist, double* values);   // eng_project.hip
 int e_solver_prepare(fdapde_ctx* c, int32_t with_dirichlet);
 int e_solver_layout(fdapde_ctx* c, int32_t with_dirichlet, int64_t* n_interior, int64_t* nnz_interior, double* streamed_bytes);
 int e_solver_layout_kind(fdapde_ctx* c, int32_t with_dirichlet, int32_t* kind, int32_t* symmetric_storage, int32_t* workgroups, int32_t* rows_per_thread);

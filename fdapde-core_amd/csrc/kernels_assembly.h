@@ -1274,11 +1274,8 @@ static __global__ void k_quadrature_nodes(AsmArgs a, const int32_t* cell_i2e, in
 // fdaPDE/pde/pde.h:149-158).
 // ---------------------------------------------------------------------------------------------------------------
 // Lagrange basis of order R at reference point xi, the reference's local node order (closed forms of tables.cpp)
-template <int M, int R> __device__ __forceinline__ void eval_ref_basis(const double* xi, double* out) {
-    double lam[M + 1];
-    lam[0] = 1.0;
-#pragma unroll
-    for (int k = 0; k < M; ++k) lam[0] -= xi[k], lam[k + 1] = xi[k];
+// ... at the barycentric coordinates lam[0 .. M] (lam[0] belongs to vertex 0)
+template <int M, int R> __device__ __forceinline__ void eval_basis_bary(const double* lam, double* out) {
     if constexpr (R == 1) {
 #pragma unroll
         for (int i = 0; i <= M; ++i) out[i] = lam[i];
@@ -1294,6 +1291,13 @@ template <int M, int R> __device__ __forceinline__ void eval_ref_basis(const dou
             out[7] = 4.0 * lam[1] * lam[3], out[8] = 4.0 * lam[2] * lam[3], out[9] = 4.0 * lam[0] * lam[3];
         }
     }
+}
+template <int M, int R> __device__ __forceinline__ void eval_ref_basis(const double* xi, double* out) {
+    double lam[M + 1];
+    lam[0] = 1.0;
+#pragma unroll
+    for (int k = 0; k < M; ++k) lam[0] -= xi[k], lam[k + 1] = xi[k];
+    eval_basis_bary<M, R>(lam, out);
 }
 // pointwise_evaluation::eval (basis/lagrangian_basis.h:203-235) with the point location of TreeSearch::locate
 // (geometry/tree_search.h:73-90) done through a uniform bin grid: one lane per location scans the cells registered in its

@@ -520,7 +520,32 @@ template <typename D, typename F, int R> class PDE<D, DifferentialExpr, F, FEM_H
                 for (auto& cv : rows[(size_t)k]) cv.second /= out.D(k);
             }
         }
-        SpMatrix<double>& P = out.Psi;
+        fill_csr(rows, out.Psi);
+        return out;
+    }
+    // eval_basis at locations that are NOT on the mesh (measured positions near a surface or a street network): every location is attached
+    // to its nearest cell and the basis is taken at its projection there (fdapde_project; the reference projects first -- geometry/project.h
+    // -- and then evaluates).  D = ones, no row is empty.  projected (optional): n_locs x N, the projected locations.
+    EvalReturnType eval_basis_nearest(const DMatrix<double>& locs, DMatrix<double>* projected = nullptr) const {
+        if (locs.cols() != N) throw std::runtime_error("eval_basis_nearest: locations need one column per coordinate of the mesh");
+        const int64_t nl = locs.rows(), nb = dofs_.cols();
+        std::vector<int32_t> cell((size_t)nl);
+        std::vector<double> val((size_t)(nl * nb)), dist((size_t)nl);
+        DMatrix<double> q(nl, N);
+        check(fdapde_project(ctx_.get(), nl, locs.data(), cell.data(), q.data(), dist.data(), val.data()));
+        std::vector<std::vector<std::pair<int32_t, double>>> rows((size_t)nl);
+        for (int64_t i = 0; i < nl; ++i)
+            for (int64_t h = 0; h < nb; ++h) rows[(size_t)i].push_back({dofs_(cell[(size_t)i], h), val[(size_t)(i * nb + h)]});
+        EvalReturnType out;
+        out.D = DVector<double>(nl, 1, 1.0);
+        fill_csr(rows, out.Psi);
+        if (projected) *projected = std::move(q);
+        return out;
+    }
+
+   private:
+    // rows of (column, value) pairs -> CSR with sorted columns, duplicates summed like setFromTriplets
+    void fill_csr(std::vector<std::vector<std::pair<int32_t, double>>>& rows, SpMatrix<double>& P) const {
         P.n_rows = (int64_t)rows.size(), P.n_cols = n_dofs_;
         P.rowptr.assign(rows.size() + 1, 0);
         for (size_t i = 0; i < rows.size(); ++i) {
@@ -534,10 +559,7 @@ template <typename D, typename F, int R> class PDE<D, DifferentialExpr, F, FEM_H
             }
             P.rowptr[i + 1] = (int32_t)P.colidx.size();
         }
-        return out;
     }
-
-   private:
     // FEMLinearParabolicSolver::solve (fem_linear_parabolic_solver.h:37-72)
     void solve_parabolic() {
         const int64_t m = time_domain_.rows();

@@ -191,8 +191,8 @@ const char *fdapde_status_string(int status);
  * (2 x 3), |e| = |(x1 - x0) x (x2 - x0)| / 2, and the weak forms use invJ as on planar cells (operators/laplacian.h:43, diffusion.h:54,
  * advection.h:55): gradients are 3-vectors, a diffusion tensor is 3 x 3 (9 values per row of a field), an advection vector has 3 components.
  * Surfaces take orders 1 and 2 on a single-device context, the default assembly (FDAPDE_ASSEMBLY_ROWS) and every solver.  FDAPDE_EUNSUPPORTED:
- * fdapde_eval_pointwise (point location would need a projection onto the surface), the assembly variants 1-4, fdapde_partition_build, and
- * a surface in a multi-device context (fdapde_ctx_create_multi).
+ * fdapde_eval_pointwise (a measured location is not on the flat triangles: fdapde_project attaches it to its nearest cell instead), the assembly
+ * variants 1-4, fdapde_partition_build, and a surface in a multi-device context (fdapde_ctx_create_multi).
  * (M, N) = (1, 1): an INTERVAL; (1, 2): a LINEAR NETWORK in the plane (cells of 2 node ids).  Per segment J = x1 - x0, invJ = J^T / |J|^2 (1 / h
  * for N = 1), measure |J| (simplex.h:186-193); quadrature IntegratorTable<1,2> / <1,3> as printed in the reference (15 digits).  A diffusion
  * tensor is N x N, an advection vector has N components.  DOFs: order 1 the nodes; order 2 the row of cell c is [v0, v1, n_nodes + c] (the
@@ -290,6 +290,18 @@ int fdapde_lin_solve(fdapde_ctx *ctx, const fdapde_options *opt, const double *b
  * incidence matrix they give Psi(k, dofs(e,h)) += psi_int[e][h] / |D_k|, D_k = sum measure (areal_evaluation::eval). */
 int fdapde_eval_pointwise(fdapde_ctx *ctx, int64_t n_locs, const double *locs_colmajor, int32_t *cell_ids, double *values);
 int fdapde_cell_integrals(fdapde_ctx *ctx, double *measure, double *psi_int);
+/* fdapde_project: every point (column-major n_pts x N) onto the mesh -- Projection<Triangulation>::operator()(points, Exact), geometry/project.h,
+ * on every mesh kind (intervals, networks, planar and volume meshes, surfaces).  Per point: cell_ids = the cell minimising the Euclidean distance
+ * from the point to the closed cell (reference cell id; ties in the computed squared distance go to the lowest reference id; the search is global:
+ * a point far from the mesh gets the true minimum over all cells), proj_colmajor (n_pts x N) = the closest point q of that cell, dist = |p - q|, and
+ * values (row-major n_pts x n_basis, may be NULL) = the basis of the space's order at the barycentric coordinates of q as the closest-point
+ * routine produced them (clamped: all >= 0 exactly; a vertex region gives the vertex bit for bit and a unit row).  The closest point is the true one
+ * (segment: clamped parameter; triangle: Voronoi regions; tetrahedron: the point itself if inside, else the best of its faces), not the reference's
+ * Simplex::nearest, which drops the farthest vertex and is off on obtuse cells.  Every row is filled: there is no -1.
+ * Psi(i, dofs(cell_i, h)) = values[i*n_basis + h].  Needs fdapde_dofs_build (FDAPDE_ENOTINIT); FDAPDE_EINVAL for a NULL or empty argument and for a
+ * non-finite coordinate (checked on the host before the launch).  A multi-device context answers from its whole mesh on devices[0]. */
+int fdapde_project(fdapde_ctx *ctx, int64_t n_pts, const double *pts_colmajor, int32_t *cell_ids, double *proj_colmajor, double *dist,
+                   double *values);
 
 /* ---- getters (fem_solver_base.h:50-53) ------------------------------------------------------------------------- */
 /* values[nnz] aligned with fdapde_pattern_get.  After a solve with Dirichlet data, FDAPDE_MAT_STIFF is the
