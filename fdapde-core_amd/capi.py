@@ -50,6 +50,7 @@ SYMBOLS = [
     "fdapde_solver_layout", "fdapde_topology_build", "fdapde_topology_get", "fdapde_comm_allreduce", "fdapde_comm_library", "fdapde_solver_layout_kind", "fdapde_solver_layout_partition", "fdapde_solver_trace", "fdapde_rowdist_setup", "fdapde_ctx_clone", "fdapde_comm_count",
     "fdapde_ctx_create_multi", "fdapde_ctx_devices", "fdapde_partition_build", "fdapde_partition_sizes", "fdapde_partition_get", "fdapde_partition_whole",
     "fdapde_partition_peers",
+    "fdapde_block_compute", "fdapde_block_solve", "fdapde_block_spmv", "fdapde_block_bench_spmv", "fdapde_gram_pointwise",
 ]
 PARTITION_ROWDIST, PARTITION_ELEMENTS = 0, 1
 
@@ -395,6 +396,98 @@ class Context:
             self._check(rc)
         X = np.ascontiguousarray(out.reshape(B.shape[1], B.shape[0]).T)
         return (X[:, 0] if one else X), info
+
+    # ---- 2 x 2 block systems on the FEM pattern (SparseBlockMatrix<double,2,2> under fdapde::SparseLU): the smoothing system's handle
+    def block_compute(self, a11, a12, a21, a22, symmetric=False):
+        """fdapde_block_compute: four blocks of nnz values each, aligned with pattern_get(); None = a zero block"""
+        nnz = self.sizes()["nnz"]
+        keep = []
+        for a in (a11, a12, a21, a22):
+            if a is None:
+                keep.append(None)
+                continue
+            v = np.ascontiguousarray(a, dtype=float).reshape(-1)
+            if v.size != nnz:
+                raise ValueError(f"block_compute(): a block holds {v.size} values, the pattern has {nnz} entries")
+            keep.append(v)
+        self._check(self.lib.fdapde_block_compute(self._ctx, *[None if v is None else _dp(v) for v in keep], 1 if symmetric else 0))
+
+    def block_solve(self, b, method=SOLVER_AUTO, rtol=1e-10, maxit=0, raise_on_noconv=True):
+        """fdapde_block_solve: b (2 n_dofs,) or (2 n_dofs, n_rhs), stacked [first block row; second block row] -> (x, Info).
+        raise_on_noconv=False: FDAPDE_ENOCONV is reported through info.converged only, x holds the last iterate of every column"""
+        b = np.asarray(b, dtype=float)
+        one = b.ndim == 1
+        B = b.reshape(b.shape[0], -1)
+        flat = np.ascontiguousarray(B.T).reshape(-1)
+        out = np.zeros_like(flat)
+        opt = Options(method=method, maxit=maxit, rtol=rtol, assembly=0, check_every=0, time_spmv=0)
+        info = Info()
+        rc = self.lib.fdapde_block_solve(self._ctx, C.byref(opt), _dp(flat), B.shape[1], _dp(out), C.byref(info))
+        if rc != OK and (raise_on_noconv or rc != ENOCONV):
+            self._check(rc)
+        X = np.ascontiguousarray(out.reshape(B.shape[1], B.shape[0]).T)
+        return (X[:, 0] if one else X), info
+
+    def block_solve_inplace(self, bx, method=SOLVER_AUTO, rtol=1e-10, maxit=0):
+        """fdapde_block_solve with x = b: bx (2 n_dofs, n_rhs) Fortran-ordered float64 is overwritten by the solutions -> Info"""
+        assert bx.dtype == np.float64 and bx.ndim == 2 and bx.flags.f_contiguous
+        opt = Options(method=method, maxit=maxit, rtol=rtol, assembly=0, check_every=0, time_spmv=0)
+        info = Info()
+        self._check(self.lib.fdapde_block_solve(self._ctx, C.byref(opt), _dp(bx), bx.shape[1], _dp(bx), C.byref(info)))
+        return info
+
+    def block_spmv(self, x):
+        """y = A x with the unscaled blocks, stacked vectors of 2 n_dofs"""
+        x = np.ascontiguousarray(x, dtype=float).reshape(-1)
+        if x.size != 2 * self.sizes()["n_dofs"]:
+            raise ValueError("block_spmv(): x must hold 2 n_dofs values")
+        y = np.zeros_like(x)
+        self._check(self.lib.fdapde_block_spmv(self._ctx, _dp(x), _dp(y)))
+        return y
+
+    def block_bench_spmv(self, reps=50):
+        """(average ms of k_block_spmv on the scaled blocks, algorithmic bytes per launch)"""
+        ms, by = C.c_double(), C.c_double()
+        self._check(self.lib.fdapde_block_bench_spmv(self._ctx, reps, C.byref(ms), C.byref(by)))
+        return ms.value, by.value
+
+    def gram_pointwise(self, cell_ids, values, weights=None):
+        """Psi^T W Psi on the FEM pattern (nnz values aligned with pattern_get()) from cell ids and row-major n_locs x n_basis values"""
+        s = self.sizes()
+        cells = np.ascontiguousarray(cell_ids, dtype=np.int32).reshape(-1)
+        vals = np.ascontiguousarray(values, dtype=float)
+        if vals.size != cells.size * s["n_basis"]:
+            raise ValueError("gram_pointwise(): values must be n_locs x n_basis")
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=float).reshape(-1)
+        if w is not None and w.size != cells.size:
+            raise ValueError("gram_pointwise(): one weight per location")
+        out = np.zeros(s["nnz"])
+        self._check(self.lib.fdapde_gram_pointwise(self._ctx, C.c_int64(cells.size), _ip(cells), _dp(vals), None if w is None else _dp(w), _dp(out)))
+        return out
+
+    def eval_pointwise_raw(self, locs):
+        """fdapde_eval_pointwise as the C ABI hands it out: (cell ids, values n_locs x n_basis)"""
+        locs = np.asarray(locs, dtype=float)
+        if locs.ndim == 1:
+            locs = locs.reshape(-1, 1)
+        nl, s = locs.shape[0], self.sizes()
+        flat = np.ascontiguousarray(locs.T).reshape(-1)
+        cells = np.zeros(nl, dtype=np.int32)
+        vals = np.zeros((nl, s["n_basis"]))
+        self._check(self.lib.fdapde_eval_pointwise(self._ctx, C.c_int64(nl), _dp(flat), _ip(cells), _dp(vals)))
+        return cells, vals
+
+    def project_raw(self, points):
+        """fdapde_project as the C ABI hands it out: (cell ids, values n_pts x n_basis, projected points n_pts x N, distances)"""
+        pts = np.asarray(points, dtype=float)
+        if pts.ndim == 1:
+            pts = pts.reshape(-1, 1)
+        n, dim, s = pts.shape[0], pts.shape[1], self.sizes()
+        flat = np.ascontiguousarray(pts.T).reshape(-1)
+        cells = np.zeros(n, dtype=np.int32)
+        proj, dist, vals = np.zeros(n * dim), np.zeros(n), np.zeros((n, s["n_basis"]))
+        self._check(self.lib.fdapde_project(self._ctx, C.c_int64(n), _dp(flat), _ip(cells), _dp(proj), _dp(dist), _dp(vals)))
+        return cells, vals, np.ascontiguousarray(proj.reshape(dim, n).T), dist
 
     # ---- basis evaluation (PDE__::eval_basis): Psi as scipy CSR + D
     def eval_pointwise(self, locs):

@@ -76,6 +76,7 @@ void fdapde_ctx_destroy(fdapde_ctx* c) {
     if (c->group) fdapde_engine::g_destroy(c);   // (the rank contexts and their threads first)
     fdapde_engine::pmg_release(c);               // (... and the coarse level's context)
     fdapde_engine::amg_release(c);               // (... and the aggregation hierarchies)
+    fdapde_engine::block_release(c);             // (... and the 2 x 2 block handle)
     if (c->has_device) {
         (void)hipSetDevice(c->device);
         fdapde_engine::partition_free(c);
@@ -302,6 +303,33 @@ int fdapde_lin_solve(fdapde_ctx* c, const fdapde_options* opt, const double* b, 
     if (c->group && opt && opt->method == FDAPDE_SOLVER_AMG) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_AMG takes one-GPU contexts, not a multi-device context");
     if (c->group) return fdapde_engine::g_lin_solve(c, opt, b, n_rhs, x, info);
     return fdapde_engine::e_lin_solve(c, opt, b, n_rhs, x, info);
+}
+// the 2 x 2 block handle (eng_block.hip): single-device contexts only
+static const char* const kBlockNoGroup = "the 2 x 2 block handle takes one-GPU contexts, not a multi-device context";
+int fdapde_block_compute(fdapde_ctx* c, const double* a11, const double* a12, const double* a21, const double* a22, int32_t symmetric) {
+    if (!c) return FDAPDE_EINVAL;
+    if (c->group) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, kBlockNoGroup);
+    return fdapde_engine::e_block_compute(c, a11, a12, a21, a22, symmetric);
+}
+int fdapde_block_solve(fdapde_ctx* c, const fdapde_options* opt, const double* b, int32_t n_rhs, double* x, fdapde_info* info) {
+    if (!c) return FDAPDE_EINVAL;
+    if (c->group) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, kBlockNoGroup);
+    return fdapde_engine::e_block_solve(c, opt, b, n_rhs, x, info);
+}
+int fdapde_block_spmv(fdapde_ctx* c, const double* x, double* y) {
+    if (!c) return FDAPDE_EINVAL;
+    if (c->group) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, kBlockNoGroup);
+    return fdapde_engine::e_block_spmv(c, x, y);
+}
+int fdapde_block_bench_spmv(fdapde_ctx* c, int32_t reps, double* avg_ms, double* algorithmic_bytes) {
+    if (!c) return FDAPDE_EINVAL;
+    if (c->group) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, kBlockNoGroup);
+    return fdapde_engine::e_block_bench_spmv(c, reps, avg_ms, algorithmic_bytes);
+}
+int fdapde_gram_pointwise(fdapde_ctx* c, int64_t n_locs, const int32_t* cell_ids, const double* values, const double* weights, double* out_values) {
+    if (!c) return FDAPDE_EINVAL;
+    if (c->group) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, kBlockNoGroup);
+    return fdapde_engine::e_gram_pointwise(c, n_locs, cell_ids, values, weights, out_values);
 }
 int fdapde_matrix_values(fdapde_ctx* c, int32_t which, double* values) {
     if (!c) return FDAPDE_EINVAL;

@@ -24,6 +24,7 @@
 namespace fdapde_engine {
 struct Group;            // eng_group.hip: the ranks of a multi-device context
 struct AmgHierarchy;     // eng_amg.hip: the aggregation hierarchy of FDAPDE_SOLVER_AMG
+struct BlockHandle;      // eng_block.hip: the 2 x 2 block handle (fdapde_block_compute / fdapde_block_solve)
 }
 namespace fdapde_hip {
 struct DevPartition;     // dev_partition.h
@@ -485,6 +486,7 @@ struct fdapde_ctx {
     // FDAPDE_SOLVER_AMG (eng_amg.hip): the hierarchy of fdapde_solve / fdapde_solve_parabolic, and the factor-once handle's; rebuilt lazily by a clone
     fdapde_engine::AmgHierarchy* amg = nullptr;
     fdapde_engine::AmgHierarchy* amg_lin = nullptr;
+    fdapde_engine::BlockHandle* block = nullptr;   // the 2 x 2 block system's handle (eng_block.hip); not carried by fdapde_ctx_clone
     int64_t amg_lin_epoch = 0;    // fdapde_lin_compute calls: the handle's hierarchy belongs to the matrix of one of them
     int64_t amg_coarse_rows = 1024;   // knob: coarsening stops at a level of at most that many rows, which is inverted once (dense_build_estimate_ms(1024) ~ 2.5 ms)
     int amg_setup_check = 0;      // knob: 1 = host loops also build the aggregates and the coarse matrices, compared bit for bit (an error if they differ)

@@ -1,0 +1,349 @@
+// eng_block.hip -- the 2 x 2 block handle: fdapde::SparseLU on a SparseBlockMatrix<double,2,2> whose four blocks lie on the FEM pattern (the
+// smoothing system the downstream models factor once and solve for many columns: fdaPDE/linear_algebra/sparse_block_matrix.h:29-128,
+// utils/symbols.h:133-160, linear_algebra/smw.h:38-59), and Psi^T W Psi on that pattern (kernels_block.h).
+//   fdapde_block_compute   blocks -> block CSR in the internal order, D^-1 A folded into a second copy (left block-Jacobi)
+//   fdapde_block_solve     restarted GMRES(m) on D^-1 A (kernels_gmres.h, buffers of the handle's own), or the dense inverse of the 2 n-row matrix
+//   fdapde_block_spmv      y = A x with the unscaled blocks
+//   fdapde_gram_pointwise  Psi^T W Psi from what fdapde_eval_pointwise / fdapde_project hand out
+// Independent of the n x n handle of fdapde_lin_compute: nothing here writes a buffer one of the other solves reads back.
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <vector>
+
+#include "context.h"
+#include "engine.h"
+#include "kernels_block.h"
+#include "kernels_dense.h"
+#include "kernels_gmres.h"
+#include "kernels_krylov.h"
+
+namespace fdapde_engine {
+
+struct BlockHandle {
+    bool ready = false, symmetric = false;
+    bool jacobi_ok = false;            // every diagonal block was invertible: the Krylov stage is available
+    int64_t n = 0, nnz = 0;            // the space the handle was computed on
+    DBuf<double> raw, scaled, dinv;    // [4 nnz] unscaled / D^-1-scaled values, [4 n] the inverted diagonal blocks
+    DBuf<double> ext;                  // staging: blocks / stacked columns in the reference numbering
+    DBuf<double> bt, x, r, w, t, sc, gm_V, gm_s, gm_part;
+    DBuf<int32_t> ctl, flag;
+    DBuf<int32_t> rowptr2, colidx2;    // the 2 n-row CSR form (dense stage), built on first use
+    DBuf<double> val2, dn_b, dn_x;
+    bool expanded = false;
+    fdapde_ctx::Dense dense;
+    int64_t cols = 0;                  // columns solved against the current matrix
+    double krylov_ms = 0;              // ... and the host time the Krylov columns among them took
+};
+
+void block_release(fdapde_ctx* c) {
+    if (!c->block) return;
+    if (c->has_device) {
+        (void)hipSetDevice(c->device);
+        (void)hipStreamSynchronize(c->stream);
+    }
+    delete c->block;
+    c->block = nullptr;
+}
+
+namespace {
+
+int block_guard(fdapde_ctx* c) {
+    if (int rc = need_device(c)) return rc;
+    if (c->comm != nullptr || c->ar_fn != nullptr || c->halo_ready || c->rd.ready)
+        return fail(c, FDAPDE_EUNSUPPORTED, "the 2 x 2 block handle takes one-GPU contexts, not a rank of a multi-GPU job");
+    if (!c->dev_ready) return fail(c, FDAPDE_ENOTINIT, "call fdapde_dofs_build first");
+    return FDAPDE_OK;
+}
+
+void launch_block_spmv(fdapde_ctx* c, const double* vals, const double* x, double* y, const int32_t* stop) {
+    const int64_t n = c->hs.n_dofs;
+    constexpr int T = kBlockTeam;
+    hipLaunchKernelGGL(k_block_spmv<T>, dim3(g1(n, 256 / T)), dim3(256), 0, c->stream, n, c->rowptr.p, c->colidx.p, vals, x, y, stop);
+}
+
+int vec_grid2(int64_t n2) { return (int)std::max<int64_t>(1, std::min<int64_t>(1024, (n2 + 255) / 256)); }
+
+// restarted GMRES(m) on D^-1 A z = D^-1 b for the column staged in B.bt: the loop of run_gmres (eng_solve.hip) on the handle's buffers -- the same
+// stop rule (the estimate inside a cycle, the TRUE residual at its end, which the next cycle starts from and relres reports)
+int block_gmres(fdapde_ctx* c, BlockHandle& B, double tol2, int maxit, int32_t h_ctl[4], double h_sc[4]) {
+    const int64_t n2 = 2 * B.n;
+    const int m = c->gmres_m;
+    hipStream_t st = c->stream;
+    const int vg = vec_grid2(n2);
+    HIPCHK(c, B.gm_V.alloc((size_t)(m + 1) * (size_t)n2));
+    HIPCHK(c, B.gm_s.alloc((size_t)gm_state_doubles(m) + (size_t)m + 2));
+    const size_t gm_norm_at = (size_t)(m + 1) * kGmStripes;
+    HIPCHK(c, B.gm_part.alloc(gm_norm_at + (size_t)std::max(vg, kGmStripes)));
+    double* gm_norm = B.gm_part.p + gm_norm_at;
+    double* gs = B.gm_s.p;
+    double* h_pass = gs + gm_state_doubles(m);
+    double* hcol = gs + 3 * m + 1;
+    double* w = B.w.p;
+    hipLaunchKernelGGL(k_block_krylov_init, dim3(vg), dim3(256), 0, st, n2, B.bt.p, B.x.p, B.r.p, B.gm_part.p);
+    hipLaunchKernelGGL(k_block_krylov_init_fin, dim3(1), dim3(64), 0, st, B.gm_part.p, vg, B.sc.p, B.ctl.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h_ctl, B.ctl.p, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(h_sc, B.sc.p, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    bool stop = h_ctl[0] != 0;
+    while (!stop) {
+        hipLaunchKernelGGL(k_gm_cycle_init, dim3(vg), dim3(256), 0, st, n2, m, B.r.p, B.sc.p, gs, B.gm_V.p, B.ctl.p);
+        for (int j = 0; j < m; ++j) {
+            const double* vj = B.gm_V.p + (size_t)j * n2;
+            launch_block_spmv(c, B.scaled.p, vj, w, B.ctl.p);
+            for (int pass = 0; pass < 2; ++pass) {
+                hipLaunchKernelGGL(k_gm_dots, dim3(kGmStripes, j + 1), dim3(256), 0, st, n2, B.gm_V.p, w, B.gm_part.p, B.ctl.p);
+                hipLaunchKernelGGL(k_gm_reduce, dim3(j + 1), dim3(256), 0, st, B.gm_part.p, h_pass, hcol, pass, B.ctl.p);
+                hipLaunchKernelGGL(k_gm_axpy, dim3(vg), dim3(256), 0, st, n2, j + 1, B.gm_V.p, h_pass, w, gm_norm, pass, B.ctl.p);
+            }
+            hipLaunchKernelGGL(k_gm_hess, dim3(1), dim3(256), 0, st, j, m, gm_norm, vg, gs, B.sc.p, B.ctl.p, tol2, maxit);
+            hipLaunchKernelGGL(k_gm_next, dim3(vg), dim3(256), 0, st, n2, w, gs, m, B.gm_V.p + (size_t)(j + 1) * n2, B.ctl.p);
+            if (j % 10 == 9 && j + 1 < m) {
+                HIPCHK(c, hipMemcpyAsync(h_ctl, B.ctl.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+                HIPCHK(c, hipStreamSynchronize(st));
+                if (h_ctl[0] != 0) break;
+            }
+        }
+        hipLaunchKernelGGL(k_gm_solve_y, dim3(1), dim3(1), 0, st, m, gs);
+        hipLaunchKernelGGL(k_gm_update_x, dim3(vg), dim3(256), 0, st, n2, m, B.gm_V.p, gs, B.x.p);
+        launch_block_spmv(c, B.scaled.p, B.x.p, B.t.p, nullptr);
+        hipLaunchKernelGGL(k_gm_residual, dim3(vg), dim3(256), 0, st, n2, B.bt.p, B.t.p, B.r.p, B.gm_part.p);
+        hipLaunchKernelGGL(k_gm_cycle_fin, dim3(1), dim3(256), 0, st, B.gm_part.p, vg, B.sc.p, B.ctl.p, tol2, maxit);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(h_ctl, B.ctl.p, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(h_sc, B.sc.p, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        stop = h_ctl[0] != 0;
+    }
+    return FDAPDE_OK;
+}
+
+bool block_dense_eligible(const fdapde_ctx* c, const BlockHandle& B) {
+    return c->dense_rows > 0 && 2 * B.n <= c->dense_rows && 2 * B.n <= kDenseMaxRows;
+}
+
+int block_dense_build(fdapde_ctx* c, BlockHandle& B) {
+    const int64_t n = B.n;
+    if (!B.expanded) {
+        HIPCHK(c, B.rowptr2.alloc((size_t)(2 * n + 1)));
+        HIPCHK(c, B.colidx2.alloc((size_t)(4 * B.nnz)));
+        HIPCHK(c, B.val2.alloc((size_t)(4 * B.nnz)));
+        hipLaunchKernelGGL(k_block_expand, dim3(g1(n + 1)), dim3(256), 0, c->stream, n, c->rowptr.p, c->colidx.p, B.raw.p, B.rowptr2.p, B.colidx2.p, B.val2.p);
+        HIPCHK(c, hipGetLastError());
+        B.expanded = true;
+    }
+    return dense_build_csr(c, 2 * n, B.rowptr2.p, B.colidx2.p, B.val2.p, nullptr, 0, B.dense);
+}
+
+}   // namespace
+
+int e_block_compute(fdapde_ctx* c, const double* a11, const double* a12, const double* a21, const double* a22, int32_t symmetric) {
+    if (!c) return FDAPDE_EINVAL;
+    if (int rc = block_guard(c)) return rc;
+    if ((!a11 && !a12) || (!a21 && !a22)) return fail(c, FDAPDE_EINVAL, "fdapde_block_compute: a block row without a block (the matrix would be singular)");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const HostSpace& hs = c->hs;
+    const int64_t n = hs.n_dofs, nnz = hs.nnz;
+    if (!c->block) c->block = new BlockHandle();
+    BlockHandle& B = *c->block;
+    B.ready = false, B.expanded = false, B.n = n, B.nnz = nnz, B.symmetric = symmetric != 0;
+    B.dense.ready = B.dense.failed = false, B.cols = 0, B.krylov_ms = 0;
+    HIPCHK(c, B.ext.alloc((size_t)std::max<int64_t>(4 * nnz, 2 * n)));
+    HIPCHK(c, B.raw.alloc((size_t)(4 * nnz)));
+    HIPCHK(c, B.scaled.alloc((size_t)(4 * nnz)));
+    HIPCHK(c, B.dinv.alloc((size_t)(4 * n)));
+    HIPCHK(c, B.flag.alloc(1));
+    HIPCHK(c, B.ctl.alloc(8));
+    HIPCHK(c, B.sc.alloc(32));
+    for (DBuf<double>* v : {&B.bt, &B.x, &B.r, &B.w, &B.t}) HIPCHK(c, v->alloc((size_t)(2 * n)));
+    const double* blocks[4] = {a11, a12, a21, a22};
+    for (int q = 0; q < 4; ++q) {
+        if (blocks[q]) HIPCHK(c, hipMemcpyAsync(B.ext.p + (size_t)q * nnz, blocks[q], sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, st));
+        else HIPCHK(c, hipMemsetAsync(B.ext.p + (size_t)q * nnz, 0, sizeof(double) * (size_t)nnz, st));
+    }
+    HIPCHK(c, hipMemsetAsync(B.flag.p, 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(k_block_pack, dim3(g1(nnz)), dim3(256), 0, st, nnz, c->slot_i2e.p, B.ext.p, B.raw.p);
+    hipLaunchKernelGGL(k_block_diag_inv, dim3(g1(n)), dim3(256), 0, st, n, c->rowptr.p, c->colidx.p, B.raw.p, B.dinv.p, B.flag.p);
+    hipLaunchKernelGGL(k_block_scale, dim3(g1(n, 256 / kBlockTeam)), dim3(256), 0, st, n, c->rowptr.p, B.raw.p, B.dinv.p, B.scaled.p);
+    HIPCHK(c, hipGetLastError());
+    int32_t h_flag = 0;
+    HIPCHK(c, hipMemcpyAsync(&h_flag, B.flag.p, sizeof h_flag, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));   // (the caller's blocks have been read)
+    B.jacobi_ok = h_flag == 0;
+    B.ready = true;
+    return FDAPDE_OK;
+}
+
+int e_block_spmv(fdapde_ctx* c, const double* x, double* y) {
+    if (!c || !x || !y) return FDAPDE_EINVAL;
+    if (int rc = block_guard(c)) return rc;
+    if (!c->block || !c->block->ready || c->block->n != c->hs.n_dofs || c->block->nnz != c->hs.nnz) return fail(c, FDAPDE_ENOTINIT, "call fdapde_block_compute first");
+    HIPCHK(c, hipSetDevice(c->device));
+    BlockHandle& B = *c->block;
+    hipStream_t st = c->stream;
+    const int64_t n = B.n;
+    HIPCHK(c, hipMemcpyAsync(B.ext.p, x, sizeof(double) * (size_t)(2 * n), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_block_stage, dim3(g1(n), 1), dim3(256), 0, st, n, c->dof_i2e.p, B.ext.p, nullptr, B.w.p);
+    launch_block_spmv(c, B.raw.p, B.w.p, B.t.p, nullptr);
+    hipLaunchKernelGGL(k_block_unstage, dim3(g1(n), 1), dim3(256), 0, st, n, c->dof_i2e.p, B.t.p, B.ext.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(y, B.ext.p, sizeof(double) * (size_t)(2 * n), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    return FDAPDE_OK;
+}
+
+// times `reps` launches of k_block_spmv on the scaled values (the launch inside the Krylov stage) with HIP events on the context's stream
+int e_block_bench_spmv(fdapde_ctx* c, int32_t reps, double* avg_ms, double* algorithmic_bytes) {
+    if (!c || reps < 1) return FDAPDE_EINVAL;
+    if (int rc = block_guard(c)) return rc;
+    if (!c->block || !c->block->ready || c->block->n != c->hs.n_dofs || c->block->nnz != c->hs.nnz) return fail(c, FDAPDE_ENOTINIT, "call fdapde_block_compute first");
+    HIPCHK(c, hipSetDevice(c->device));
+    BlockHandle& B = *c->block;
+    const int64_t n = B.n;
+    hipLaunchKernelGGL(k_fill_f64, dim3(g1(2 * n)), dim3(256), 0, c->stream, 2 * n, 1.0, B.w.p);
+    for (int i = 0; i < 3; ++i) launch_block_spmv(c, B.scaled.p, B.w.p, B.t.p, nullptr);
+    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    for (int i = 0; i < reps; ++i) launch_block_spmv(c, B.scaled.p, B.w.p, B.t.p, nullptr);
+    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+    HIPCHK(c, hipEventSynchronize(c->ev1));
+    float ms = 0;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    if (avg_ms) *avg_ms = (double)ms / reps;
+    if (algorithmic_bytes) *algorithmic_bytes = 36.0 * (double)B.nnz + 4.0 * (double)(n + 1) + 32.0 * (double)n;
+    return FDAPDE_OK;
+}
+
+int e_block_solve(fdapde_ctx* c, const fdapde_options* opt, const double* b, int32_t n_rhs, double* x, fdapde_info* info) {
+    if (!c || !b || !x || n_rhs < 1) return FDAPDE_EINVAL;
+    if (int rc = block_guard(c)) return rc;
+    if (!c->block || !c->block->ready || c->block->n != c->hs.n_dofs || c->block->nnz != c->hs.nnz) return fail(c, FDAPDE_ENOTINIT, "call fdapde_block_compute first");
+    HIPCHK(c, hipSetDevice(c->device));
+    BlockHandle& B = *c->block;
+    const int64_t n = B.n, n2 = 2 * n;
+    {   // an in-place solve: finished columns are written to x while later ones still read b
+        const double *b0 = b, *b1 = b + (size_t)n2 * n_rhs, *x0 = x, *x1 = x + (size_t)n2 * n_rhs;
+        if (b0 < x1 && x0 < b1) {
+            std::vector<double> b_copy(b0, b1);
+            return e_block_solve(c, opt, b_copy.data(), n_rhs, x, info);
+        }
+    }
+    hipStream_t st = c->stream;
+    const int method = opt ? opt->method : FDAPDE_SOLVER_AUTO;
+    const bool open = method == FDAPDE_SOLVER_AUTO, dense_named = method == FDAPDE_SOLVER_DENSE;
+    if (!open && !dense_named && method != FDAPDE_SOLVER_GMRES)
+        return fail(c, FDAPDE_EUNSUPPORTED, "fdapde_block_solve runs FDAPDE_SOLVER_GMRES, FDAPDE_SOLVER_DENSE or the open method");
+    const double rtol = (opt && opt->rtol > 0) ? opt->rtol : 1e-10;
+    const int maxit = (opt && opt->maxit > 0) ? opt->maxit : 2000;
+    fdapde_info out{};
+    const auto t_call = std::chrono::steady_clock::now();
+    const bool eligible = block_dense_eligible(c, B);
+    if (dense_named && !eligible) return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_DENSE takes block systems of up to `dense_rows` (at most 8192) rows");
+    if (!dense_named && !eligible && !B.jacobi_ok)
+        return fail(c, FDAPDE_EUNSUPPORTED, "a DOF's diagonal block is singular: no block-Jacobi form for the Krylov stage, and the system is too large for the dense inverse");
+    if (method == FDAPDE_SOLVER_GMRES && !B.jacobi_ok)
+        return fail(c, FDAPDE_EUNSUPPORTED, "a DOF's diagonal block is singular (|det| <= 1e-14 max|entry|^2): no block-Jacobi form for the Krylov stage");
+    HIPCHK(c, B.ext.alloc((size_t)std::max<int64_t>(4 * B.nnz, 2 * n)));
+    if ((open || dense_named) && eligible) {   // the rent-or-buy rule of fdapde_lin_solve, with 2 n as the row count
+        fdapde_ctx::Dense& D = B.dense;
+        if (!D.ready && (!D.failed || dense_named) &&
+            (dense_named || !B.jacobi_ok || c->dense_after == 0 || (B.cols + n_rhs > c->dense_after && B.krylov_ms >= 0.5 * dense_build_estimate_ms(n2))))
+            if (int rc = block_dense_build(c, B)) return rc;
+        if ((dense_named || !B.jacobi_ok) && !D.ready) {
+            out.method_used = FDAPDE_SOLVER_DENSE, out.relres = D.check;
+            c->info = out;
+            if (info) *info = out;
+            c->err = "FDAPDE_SOLVER_DENSE: the block matrix is singular to working precision (no usable pivot, or max |I - A X| beyond 1e-6)";
+            return FDAPDE_ENOCONV;
+        }
+        if (D.ready) {
+            const size_t cnt = (size_t)n2 * (size_t)n_rhs;
+            HIPCHK(c, B.dn_b.alloc(cnt));
+            HIPCHK(c, B.dn_x.alloc(cnt));
+            // the columns cross in slices of the staging buffer's size, every slice one product
+            const int per = (int)std::max<int64_t>(1, (int64_t)(B.ext.n / (size_t)n2));
+            for (int j0 = 0; j0 < n_rhs; j0 += per) {
+                const int q = std::min(per, n_rhs - j0);
+                HIPCHK(c, hipMemcpyAsync(B.ext.p, b + (size_t)j0 * n2, sizeof(double) * (size_t)n2 * q, hipMemcpyHostToDevice, st));
+                hipLaunchKernelGGL(k_block_stage, dim3(g1(n), q), dim3(256), 0, st, n, c->dof_i2e.p, B.ext.p, nullptr, B.dn_b.p + (size_t)j0 * n2);
+            }
+            if (int rc = dense_apply(c, D, n_rhs, B.dn_b.p, B.dn_x.p)) return rc;
+            for (int j0 = 0; j0 < n_rhs; j0 += per) {
+                const int q = std::min(per, n_rhs - j0);
+                hipLaunchKernelGGL(k_block_unstage, dim3(g1(n), q), dim3(256), 0, st, n, c->dof_i2e.p, B.dn_x.p + (size_t)j0 * n2, B.ext.p);
+                HIPCHK(c, hipGetLastError());
+                HIPCHK(c, hipMemcpyAsync(x + (size_t)j0 * n2, B.ext.p, sizeof(double) * (size_t)n2 * q, hipMemcpyDeviceToHost, st));
+                HIPCHK(c, hipStreamSynchronize(st));
+            }
+            B.cols += n_rhs;
+            out.iters = D.refine ? 1 : 0, out.converged = 1, out.relres = D.check, out.method_used = FDAPDE_SOLVER_DENSE;
+            out.t_solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+            c->info = out;
+            if (info) *info = out;
+            return FDAPDE_OK;
+        }
+    }
+    // Krylov stage, the columns one after another
+    B.cols += n_rhs;
+    const double tol2 = rtol * rtol;
+    int total = 0, rc_all = FDAPDE_OK;
+    double worst = 0;
+    bool broke = false;
+    for (int32_t j = 0; j < n_rhs; ++j) {
+        HIPCHK(c, hipMemcpyAsync(B.ext.p, b + (size_t)j * n2, sizeof(double) * (size_t)n2, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_block_stage, dim3(g1(n), 1), dim3(256), 0, st, n, c->dof_i2e.p, B.ext.p, B.dinv.p, B.bt.p);
+        int32_t h_ctl[4] = {0, 0, 0, 0};
+        double h_sc[4] = {0, 0, 0, 0};
+        if (int rc = block_gmres(c, B, tol2, maxit, h_ctl, h_sc)) return rc;
+        const double bb = h_sc[0], rr = h_sc[3];
+        const double rel = bb > 0 ? std::sqrt(rr / bb) : 0.0;
+        if (!(rr <= tol2 * bb && h_ctl[2] == 0)) rc_all = FDAPDE_ENOCONV, broke = broke || h_ctl[2] != 0;
+        total += h_ctl[1], worst = rel > worst ? rel : worst;
+        hipLaunchKernelGGL(k_block_unstage, dim3(g1(n), 1), dim3(256), 0, st, n, c->dof_i2e.p, B.x.p, B.ext.p);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(x + (size_t)j * n2, B.ext.p, sizeof(double) * (size_t)n2, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+    }
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+    B.krylov_ms += ms;
+    out.iters = total, out.relres = worst, out.converged = rc_all == FDAPDE_OK ? 1 : 0, out.method_used = FDAPDE_SOLVER_GMRES, out.t_solve_ms = ms;
+    c->info = out;
+    if (info) *info = out;
+    if (rc_all == FDAPDE_ENOCONV) c->err = broke ? "GMRES stagnated or broke down in at least one column" : "maxit reached in at least one column";
+    return rc_all;
+}
+
+// Psi^T W Psi on the FEM pattern from the rows fdapde_eval_pointwise / fdapde_project hand out: Psi(i, dofs(cell_i, h)) = values[i nb + h]
+int e_gram_pointwise(fdapde_ctx* c, int64_t n_locs, const int32_t* cell_ids, const double* values, const double* weights, double* out_values) {
+    if (!c || n_locs < 1 || !cell_ids || !values || !out_values) return FDAPDE_EINVAL;
+    if (int rc = block_guard(c)) return rc;
+    const HostSpace& hs = c->hs;
+    for (int64_t k = 0; k < n_locs; ++k)
+        if (cell_ids[k] < -1 || cell_ids[k] >= hs.n_cells) {
+            c->err = "fdapde_gram_pointwise: location " + std::to_string(k) + " names cell " + std::to_string(cell_ids[k]) + ", which the mesh does not have";
+            return FDAPDE_EINVAL;
+        }
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const int nb = hs.nb;
+    DBuf<int32_t> d_cells, d_e2i;
+    DBuf<double> d_vals, d_w, d_out, d_ext;
+    HIPCHK(c, d_cells.upload(cell_ids, (size_t)n_locs, st));
+    HIPCHK(c, d_vals.upload(values, (size_t)n_locs * nb, st));
+    if (weights) HIPCHK(c, d_w.upload(weights, (size_t)n_locs, st));
+    HIPCHK(c, d_e2i.alloc((size_t)hs.n_cells));
+    HIPCHK(c, d_out.alloc((size_t)hs.nnz));
+    HIPCHK(c, d_ext.alloc((size_t)hs.nnz));
+    HIPCHK(c, hipMemsetAsync(d_out.p, 0, sizeof(double) * (size_t)hs.nnz, st));
+    hipLaunchKernelGGL(k_block_invert_perm, dim3(g1(hs.n_cells)), dim3(256), 0, st, hs.n_cells, c->cell_i2e.p, d_e2i.p);
+    hipLaunchKernelGGL(k_gram_pointwise, dim3(g1(n_locs * nb * nb)), dim3(256), 0, st, n_locs, nb, d_cells.p, d_e2i.p, c->cdofs.p, d_vals.p, weights ? d_w.p : nullptr,
+                       c->rowptr.p, c->colidx.p, d_out.p);
+    hipLaunchKernelGGL(k_scatter_f64, dim3(g1(hs.nnz)), dim3(256), 0, st, hs.nnz, c->slot_i2e.p, d_out.p, d_ext.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out_values, d_ext.p, sizeof(double) * (size_t)hs.nnz, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    return FDAPDE_OK;
+}
+
+}   // namespace fdapde_engine

@@ -190,6 +190,13 @@ int amg_run(fdapde_ctx* c, AmgHierarchy* h, const double* A, const double* f_dev
 int amg_build(fdapde_ctx* c, AmgHierarchy** slot, const double* A, int use_bnd, bool symmetric);
 int dense_step_loop(fdapde_ctx* c, fdapde_ctx::Dense& D, int32_t n_times, double inv_dt, const double* g_ext_dev, double* u0, double* sol_ext);
 void preload_dense();
+// eng_block.hip: 2 x 2 block systems on the FEM pattern (the smoothing system's handle) and Psi^T W Psi on that pattern
+void block_release(fdapde_ctx* c);
+int e_block_compute(fdapde_ctx* c, const double* a11, const double* a12, const double* a21, const double* a22, int32_t symmetric);
+int e_block_solve(fdapde_ctx* c, const fdapde_options* opt, const double* b, int32_t n_rhs, double* x, fdapde_info* info);
+int e_block_spmv(fdapde_ctx* c, const double* x, double* y);
+int e_block_bench_spmv(fdapde_ctx* c, int32_t reps, double* avg_ms, double* algorithmic_bytes);
+int e_gram_pointwise(fdapde_ctx* c, int64_t n_locs, const int32_t* cell_ids, const double* values, const double* weights, double* out_values);
 
 // code objects of the units loaded up front (fdapde_ctx_create)
 void preload_assembly();

@@ -1,0 +1,196 @@
+// kernels_block.h -- 2 x 2 block systems on the FEM pattern (fdaPDE/linear_algebra/sparse_block_matrix.h:29-128: the smoothing system
+//     [ -Psi^T W Psi   lambda R1^T ] [f]   [ -Psi^T W z ]
+//     [  lambda R1     lambda R0   ] [g] = [  lambda u   ]
+// every block of which lies on the pattern of stiff() / mass()).  Layout: block CSR in the solver's internal DOF order -- the context's
+// rowptr / colidx, ONE column index per pattern entry, four contiguous doubles [a11 a12 a21 a22] per entry (32-byte aligned) -- and vectors
+// interleaved per DOF: z[2 i] = f_i, z[2 i + 1] = g_i.  The Krylov stage works on D^-1 A, D = the 2 x 2 diagonal block of every DOF (left
+// block-Jacobi, folded into the values once per fdapde_block_compute); the Gram matrix Psi^T W Psi is accumulated with fp64 atomics.
+#ifndef FDAPDE_KERNELS_BLOCK_H
+#define FDAPDE_KERNELS_BLOCK_H
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "kernels_reduce.h"
+
+namespace fdapde_hip {
+
+typedef double blk_v2f64_t __attribute__((ext_vector_type(2)));
+
+constexpr int kBlockTeam = 8;   // lanes per block row of k_block_spmv: one pass covers 8 entries (2-D P1 rows: 7, 3-D P1: ~15, P2: 20 - 30)
+
+__device__ __forceinline__ int32_t blk_lower_bound(const int32_t* a, int32_t lo, int32_t hi, int32_t x) {
+    while (lo < hi) {
+        const int32_t mid = lo + ((hi - lo) >> 1);
+        if (a[mid] < x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// y = A x on the interleaved layout.  T lanes share a block row; a lane takes whole entries k = rs + l, rs + l + T, ...: the 32 bytes of values
+// as two 16-byte loads, one column index, one 16-byte gather of the x pair.  Lanes past the row's end issue no load at all (nothing is read
+// out of bounds: the arrays need no padding).  The in-team sum is a fixed butterfly: the same bits every run.  One 16-byte store per row.
+// Algorithmic bytes per launch: 36 nnz + 4 (n + 1) + 32 n.
+template <int T>
+static __global__ __launch_bounds__(256) void k_block_spmv(int64_t n, const int32_t* rowptr, const int32_t* colidx, const double* vals, const double* x, double* y,
+                                                           const int32_t* stop) {
+    if (stop && __syncthreads_or(*stop != 0)) return;
+    constexpr int TEAMS = 256 / T;
+    const int l = threadIdx.x % T;
+    const int64_t row = (int64_t)blockIdx.x * TEAMS + threadIdx.x / T;
+    const bool row_ok = row < n;
+    const int64_t rc = row_ok ? row : n - 1;   // (lanes of a row past the end go through the motions on the last row and do not store)
+    const int rs = rowptr[rc], re = rowptr[rc + 1];
+    double a0 = 0.0, a1 = 0.0;
+    for (int k = rs + l; k < re; k += T) {
+        const blk_v2f64_t* v = reinterpret_cast<const blk_v2f64_t*>(vals + 4 * (int64_t)k);
+        const blk_v2f64_t top = v[0], bot = v[1];
+        const int col = colidx[k];
+        const blk_v2f64_t xp = *reinterpret_cast<const blk_v2f64_t*>(x + 2 * (int64_t)col);
+        a0 += top.x * xp.x + top.y * xp.y;
+        a1 += bot.x * xp.x + bot.y * xp.y;
+    }
+    a0 = team_sum<T>(a0), a1 = team_sum<T>(a1);
+    if (l == 0 && row_ok) *reinterpret_cast<blk_v2f64_t*>(y + 2 * row) = blk_v2f64_t{a0, a1};
+}
+
+// the four blocks as handed over (reference slot order, block q at ext[q * nnz ...], a NULL block as zeros) -> [a11 a12 a21 a22] per internal slot
+static __global__ void k_block_pack(int64_t nnz, const int32_t* slot_i2e, const double* ext, double* raw) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= nnz) return;
+    const int64_t e = slot_i2e[s];
+    blk_v2f64_t* o = reinterpret_cast<blk_v2f64_t*>(raw + 4 * s);
+    o[0] = blk_v2f64_t{ext[e], ext[nnz + e]};
+    o[1] = blk_v2f64_t{ext[2 * nnz + e], ext[3 * nnz + e]};
+}
+
+// D_i^-1 of every DOF's diagonal block; flag raised where |det| <= 1e-14 max|entry|^2 (or the block is missing / not finite): no block-Jacobi form
+static __global__ void k_block_diag_inv(int64_t n, const int32_t* rowptr, const int32_t* colidx, const double* raw, double* dinv, int32_t* flag) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int32_t k0 = rowptr[i], k1 = rowptr[i + 1];
+    const int32_t d = blk_lower_bound(colidx, k0, k1, (int32_t)i);
+    double a = 0, b = 0, cc = 0, e = 0;
+    if (d < k1 && colidx[d] == (int32_t)i) a = raw[4 * (int64_t)d], b = raw[4 * (int64_t)d + 1], cc = raw[4 * (int64_t)d + 2], e = raw[4 * (int64_t)d + 3];
+    const double det = a * e - b * cc;
+    const double mx = fmax(fmax(fabs(a), fabs(b)), fmax(fabs(cc), fabs(e)));
+    double* o = dinv + 4 * i;
+    if (!(fabs(det) > 1e-14 * mx * mx) || !isfinite(det)) {
+        *flag = 1;
+        o[0] = 1.0, o[1] = 0.0, o[2] = 0.0, o[3] = 1.0;
+        return;
+    }
+    const double inv = 1.0 / det;
+    o[0] = e * inv, o[1] = -b * inv, o[2] = -cc * inv, o[3] = a * inv;
+}
+
+// scaled = D_i^-1 times block row i (T lanes per row, as the product walks it)
+static __global__ void k_block_scale(int64_t n, const int32_t* rowptr, const double* raw, const double* dinv, double* scaled) {
+    constexpr int T = kBlockTeam;
+    const int l = threadIdx.x % T;
+    const int64_t row = (int64_t)blockIdx.x * (256 / T) + threadIdx.x / T;
+    if (row >= n) return;
+    const double d0 = dinv[4 * row], d1 = dinv[4 * row + 1], d2 = dinv[4 * row + 2], d3 = dinv[4 * row + 3];
+    for (int k = rowptr[row] + l; k < rowptr[row + 1]; k += T) {
+        const double a = raw[4 * (int64_t)k], b = raw[4 * (int64_t)k + 1], cc = raw[4 * (int64_t)k + 2], e = raw[4 * (int64_t)k + 3];
+        double* o = scaled + 4 * (int64_t)k;
+        o[0] = d0 * a + d1 * cc, o[1] = d0 * b + d1 * e, o[2] = d2 * a + d3 * cc, o[3] = d2 * b + d3 * e;
+    }
+}
+
+// a stacked column in the reference numbering (rows 0 .. n-1 the first block row, n .. 2n-1 the second) -> interleaved internal order, times
+// D^-1 where dinv is given (the Krylov stage's right-hand side); column blockIdx.y of nc
+static __global__ void k_block_stage(int64_t n, const int32_t* i2e, const double* b_ext, const double* dinv, double* z) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const size_t col = blockIdx.y;
+    const int64_t e = i2e[i];
+    const double f = b_ext[col * 2 * (size_t)n + e], g = b_ext[col * 2 * (size_t)n + n + e];
+    double* o = z + col * 2 * (size_t)n + 2 * i;
+    if (dinv) o[0] = dinv[4 * i] * f + dinv[4 * i + 1] * g, o[1] = dinv[4 * i + 2] * f + dinv[4 * i + 3] * g;
+    else o[0] = f, o[1] = g;
+}
+// ... and back
+static __global__ void k_block_unstage(int64_t n, const int32_t* i2e, const double* z, double* x_ext) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const size_t col = blockIdx.y;
+    const int64_t e = i2e[i];
+    const double* s = z + col * 2 * (size_t)n + 2 * i;
+    x_ext[col * 2 * (size_t)n + e] = s[0] + 0.0, x_ext[col * 2 * (size_t)n + n + e] = s[1] + 0.0;
+}
+
+// start of a Krylov column: x = 0, r = bt, |bt|^2 partials ...
+static __global__ __launch_bounds__(256) void k_block_krylov_init(int64_t n2, const double* bt, double* x, double* r, double* part) {
+    __shared__ double red[4];
+    double a = 0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (int64_t)gridDim.x * blockDim.x) {
+        const double v = bt[i];
+        x[i] = 0.0, r[i] = v, a += isfinite(v) ? v * v : 1e300;
+    }
+    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+}
+// ... sc[0] = |b|^2, sc[3] = sc[21] = |r|^2 (the slots the GMRES kernels read), ctl cleared; a zero right-hand side is solved by x = 0
+static __global__ void k_block_krylov_init_fin(const double* part, int np, double* sc, int32_t* ctl) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    double s = 0;
+    for (int i = 0; i < np; ++i) s += part[i];
+    sc[0] = s, sc[3] = s, sc[21] = s;
+    for (int k = 0; k < 8; ++k) ctl[k] = 0;
+    if (!(s > 0.0)) ctl[0] = 1;
+}
+
+// the four blocks as ONE CSR matrix of 2 n rows in the interleaved order (row 2 i + p, column 2 j + q): what the dense inverse is built from
+static __global__ void k_block_expand(int64_t n, const int32_t* rowptr, const int32_t* colidx, const double* raw, int32_t* rowptr2, int32_t* colidx2, double* val2) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > n) return;
+    if (i == n) {
+        rowptr2[2 * n] = 4 * rowptr[n];
+        return;
+    }
+    const int32_t k0 = rowptr[i], len = rowptr[i + 1] - k0;
+    const int32_t r0 = 4 * k0, r1 = 4 * k0 + 2 * len;
+    rowptr2[2 * i] = r0, rowptr2[2 * i + 1] = r1;
+    for (int32_t t = 0; t < len; ++t) {
+        const int64_t k = k0 + t;
+        const int32_t j = colidx[k];
+        colidx2[r0 + 2 * t] = 2 * j, colidx2[r0 + 2 * t + 1] = 2 * j + 1;
+        colidx2[r1 + 2 * t] = 2 * j, colidx2[r1 + 2 * t + 1] = 2 * j + 1;
+        val2[r0 + 2 * t] = raw[4 * k], val2[r0 + 2 * t + 1] = raw[4 * k + 1];
+        val2[r1 + 2 * t] = raw[4 * k + 2], val2[r1 + 2 * t + 1] = raw[4 * k + 3];
+    }
+}
+
+// ---- Psi^T W Psi on the pattern --------------------------------------------------------------------------------------------------------
+static __global__ void k_block_invert_perm(int64_t n, const int32_t* i2e, int32_t* e2i) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) e2i[i2e[i]] = (int32_t)i;
+}
+// one lane per (location, a, b): out[slot(dof_a, dof_b)] += w psi_a psi_b, the slot found by a search in row dof_a (as the element-wise
+// assembly forms do); locations outside the mesh (cell id -1) contribute nothing.  fp64 atomics: the order of the additions is not fixed.
+static __global__ void k_gram_pointwise(int64_t n_locs, int nb, const int32_t* cell_ids, const int32_t* cell_e2i, const int32_t* cdofs, const double* values,
+                                        const double* weights, const int32_t* rowptr, const int32_t* colidx, double* out) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int nb2 = nb * nb;
+    if (t >= n_locs * nb2) return;
+    const int64_t loc = t / nb2;
+    const int ab = (int)(t - loc * nb2), a = ab / nb, b = ab - a * nb;
+    const int32_t ce = cell_ids[loc];
+    if (ce < 0) return;
+    const int64_t ci = cell_e2i[ce];
+    const int32_t i = cdofs[ci * nb + a], j = cdofs[ci * nb + b];
+    const int32_t k1 = rowptr[i + 1];
+    const int32_t k = blk_lower_bound(colidx, rowptr[i], k1, j);
+    if (k >= k1 || colidx[k] != j) return;
+    const double va = values[loc * nb + a], vb = values[loc * nb + b];
+    const double term = weights ? (weights[loc] * va) * vb : va * vb;
+    atomicAdd(out + k, term);
+}
+
+}  // namespace fdapde_hip
+#endif

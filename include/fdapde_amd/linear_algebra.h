@@ -3,6 +3,8 @@
 //   lump(A)              row-sum lumping                    fdaPDE/linear_algebra/lumping.h:30-51
 //   PartialPivLU         small dense LU (q x q)             stands in for Eigen::PartialPivLU<DMatrix<double>>
 //   SMW<SparseSolver>    Sherman-Morrison-Woodbury solve    fdaPDE/linear_algebra/smw.h:38-59
+//   SparseBlockMatrix<double,2,2>   four sparse blocks as one matrix   fdaPDE/linear_algebra/sparse_block_matrix.h:29-128
+//                        (what PDE::BlockSolver factors: SMW<PDE<...>::BlockSolver> solves the smoothing system under a low-rank update)
 // The heavy step of SMW, A^{-1} [b | U] (1 + q right-hand sides against one prepared sparse system), runs on the device as ONE
 // batched multi-column solve through the factor-once handle (PDE::SparseSolver -> fdapde_lin_compute / fdapde_lin_solve);
 // everything dense is q x q or n x q host work.
@@ -10,6 +12,7 @@
 #define FDAPDE_AMD_LINEAR_ALGEBRA_H
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <stdexcept>
 #include <utility>
@@ -65,6 +68,56 @@ template <typename T> SpMatrix<T> lump(const SpMatrix<T>& a) {
     }
     d.rowptr[(size_t)a.rows()] = (int32_t)a.rows();
     return d;
+}
+
+// ---- SparseBlockMatrix<T, 2, 2> (sparse_block_matrix.h:29-128): the blocks in row-major order, as the reference's constructor takes them ----------
+template <typename T, int Rows, int Cols> class SparseBlockMatrix;
+template <typename T> class SparseBlockMatrix<T, 2, 2> {
+   public:
+    SparseBlockMatrix() = default;
+    SparseBlockMatrix(const SpMatrix<T>& m00, const SpMatrix<T>& m01, const SpMatrix<T>& m10, const SpMatrix<T>& m11) : blocks_ {m00, m01, m10, m11} {
+        // blocks of a block row share their rows, blocks of a block column their columns (sparse_block_matrix.h:60-72)
+        if (m00.rows() != m01.rows() || m10.rows() != m11.rows() || m00.cols() != m10.cols() || m01.cols() != m11.cols())
+            throw std::runtime_error("SparseBlockMatrix: the blocks do not fit together");
+        rows_ = m00.rows() + m10.rows(), cols_ = m00.cols() + m01.cols();
+    }
+    const SpMatrix<T>& block(int i, int j) const { return blocks_[(size_t)(2 * i + j)]; }
+    int64_t rows() const { return rows_; }
+    int64_t cols() const { return cols_; }
+    int64_t nonZeros() const {
+        int64_t s = 0;
+        for (const auto& b : blocks_) s += b.nonZeros();
+        return s;
+    }
+    T coeff(int64_t i, int64_t j) const {
+        const int64_t r0 = blocks_[0].rows(), c0 = blocks_[0].cols();
+        return block(i >= r0, j >= c0).coeff(i >= r0 ? i - r0 : i, j >= c0 ? j - c0 : j);
+    }
+    DMatrix<T> operator*(const DMatrix<T>& x) const {   // host-side product (checks)
+        const int64_t r0 = blocks_[0].rows(), c0 = blocks_[0].cols();
+        DMatrix<T> y(rows_, x.cols(), T(0));
+        for (int bi = 0; bi < 2; ++bi)
+            for (int bj = 0; bj < 2; ++bj) {
+                const SpMatrix<T>& b = block(bi, bj);
+                if (b.values.empty()) continue;
+                for (int64_t c = 0; c < x.cols(); ++c)
+                    for (int64_t i = 0; i < b.rows(); ++i) {
+                        T s = 0;
+                        for (int32_t k = b.rowptr[(size_t)i]; k < b.rowptr[(size_t)i + 1]; ++k) s += b.values[(size_t)k] * x((bj ? c0 : 0) + b.colidx[(size_t)k], c);
+                        y((bi ? r0 : 0) + i, c) += s;
+                    }
+            }
+        return y;
+    }
+   private:
+    std::array<SpMatrix<T>, 4> blocks_;
+    int64_t rows_ = 0, cols_ = 0;
+};
+// an n x m sparse matrix without entries (a zero block)
+template <typename T> SpMatrix<T> zero_block(int64_t rows, int64_t cols) {
+    SpMatrix<T> z;
+    z.n_rows = rows, z.n_cols = cols, z.rowptr.assign((size_t)rows + 1, 0);
+    return z;
 }
 
 // ---- small dense LU with partial pivoting (the DenseSolver of SMW; q x q) ----------------------------------------------

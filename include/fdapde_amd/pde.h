@@ -318,6 +318,10 @@ struct device_list {
 struct EvalReturnType {
     SpMatrix<double> Psi;
     DVector<double> D;
+    // point evaluations (eval_basis(0, .), eval_basis_nearest) also keep the rows as the C ABI handed them out -- the cell of every location
+    // (reference id, -1: outside) and its n_basis values, row-major -- which is what PDE::gram takes to the device; empty for areal evaluations
+    std::vector<int32_t> cells;
+    std::vector<double> values;
 };
 
 template <typename D, typename E, typename F, typename S, typename... Ts> class PDE;
@@ -492,11 +496,14 @@ template <typename D, typename F, int R> class PDE<D, DifferentialExpr, F, FEM_H
         if (eval_type != 0 && eval_type != 1) return std::nullopt;
         const int64_t nc = domain_.cells().rows(), nb = dofs_.cols();
         std::vector<std::vector<std::pair<int32_t, double>>> rows;
+        std::vector<int32_t> pw_cell;
+        std::vector<double> pw_val;
         EvalReturnType out;
         if (eval_type == 0) {   // pointwise_evaluation::eval (lagrangian_basis.h:203-235)
             const int64_t nl = locs.rows();
-            std::vector<int32_t> cell((size_t)nl);
-            std::vector<double> val((size_t)(nl * nb));
+            pw_cell.resize((size_t)nl), pw_val.resize((size_t)(nl * nb));
+            std::vector<int32_t>& cell = pw_cell;
+            std::vector<double>& val = pw_val;
             check(fdapde_eval_pointwise(ctx_.get(), nl, locs.data(), cell.data(), val.data()));
             rows.resize((size_t)nl);
             out.D = DVector<double>(nl, 1, 1.0);
@@ -521,6 +528,7 @@ template <typename D, typename F, int R> class PDE<D, DifferentialExpr, F, FEM_H
             }
         }
         fill_csr(rows, out.Psi);
+        if (eval_type == 0) out.cells = std::move(pw_cell), out.values = std::move(pw_val);
         return out;
     }
     // eval_basis at locations that are NOT on the mesh (measured positions near a surface or a street network): every location is attached
@@ -539,9 +547,79 @@ template <typename D, typename F, int R> class PDE<D, DifferentialExpr, F, FEM_H
         EvalReturnType out;
         out.D = DVector<double>(nl, 1, 1.0);
         fill_csr(rows, out.Psi);
+        out.cells = std::move(cell), out.values = std::move(val);
         if (projected) *projected = std::move(q);
         return out;
     }
+
+    // Psi^T W Psi of a point evaluation as a matrix on the pattern of stiff() / mass(), accumulated on the device (fdapde_gram_pointwise): the (1, 1)
+    // block of the smoothing system.  weights: one per location, or empty (W = I).
+    SpMatrix<double> gram(const EvalReturnType& e, const DVector<double>& weights = DVector<double> {}) const {
+        const int64_t nl = (int64_t)e.cells.size();
+        if (nl == 0 || (int64_t)e.values.size() != nl * nb_) throw std::runtime_error("gram: needs a point evaluation (eval_basis(0, locs) or eval_basis_nearest)");
+        if (!is_empty(weights) && weights.size() != nl) throw std::runtime_error("gram: one weight per location");
+        SpMatrix<double> g;
+        g.n_rows = g.n_cols = n_dofs_, g.rowptr = stiff_.rowptr, g.colidx = stiff_.colidx, g.values.assign(stiff_.colidx.size(), 0.0);
+        check(fdapde_gram_pointwise(ctx_.get(), nl, e.cells.data(), e.values.data(), is_empty(weights) ? nullptr : weights.data(), g.values.data()));
+        return g;
+    }
+
+    // "factor once, solve many" on a 2 x 2 block matrix whose blocks lie on this PDE's pattern: fdapde::SparseLU on a SparseBlockMatrix<double,2,2>
+    // (linear_algebra/sparse_block_matrix.h:29-128; include/fdapde_amd/linear_algebra.h) -- the smoothing system.  Right-hand sides and solutions are
+    // stacked as the reference stacks them: rows 0 .. n-1 the first block row, n .. 2n-1 the second.  Context lifetime as SparseSolver.
+    class BlockSolver {
+       public:
+        // m.block(i, j): SpMatrix<double> of n_dofs x n_dofs; no stored entry = a zero block, else entries on the pattern (a sub-pattern is filled up with zeros)
+        template <typename BlockMatrix> void compute(const BlockMatrix& m, bool symmetric = false) {
+            if (m.rows() != 2 * n_ || m.cols() != 2 * n_) throw std::runtime_error("BlockSolver: the block matrix must be 2 n_dofs x 2 n_dofs");
+            std::vector<double> v[4];
+            const double* p[4];
+            for (int q = 0; q < 4; ++q) p[q] = on_pattern(m.block(q / 2, q % 2), v[q]);
+            computed_ = fdapde_block_compute(ctx_.get(), p[0], p[1], p[2], p[3], symmetric ? 1 : 0) == FDAPDE_OK;
+        }
+        DMatrix<double> solve(const DMatrix<double>& b) const {
+            if (!computed_) throw std::runtime_error("BlockSolver: compute() first");
+            if (b.rows() != 2 * n_) throw std::runtime_error("BlockSolver: right-hand sides need 2 n_dofs rows");
+            DMatrix<double> x(b.rows(), b.cols());
+            fdapde_info info;
+            const int rc = fdapde_block_solve(ctx_.get(), &opt_, b.data(), (int32_t)b.cols(), x.data(), &info);
+            if (rc != FDAPDE_OK) throw std::runtime_error(fdapde_last_error(ctx_.get()));
+            return x;
+        }
+        explicit operator bool() const { return computed_; }
+        fdapde_options& solver_options() { return opt_; }
+       private:
+        friend class PDE;
+        BlockSolver(fdapde::hip::context_handle ctx, int64_t n, std::vector<int32_t> rowptr, std::vector<int32_t> colidx) :
+            ctx_(std::move(ctx)), n_(n), rowptr_(std::move(rowptr)), colidx_(std::move(colidx)) { }
+        // values of `a` aligned with the PDE's pattern (nullptr: a zero block)
+        const double* on_pattern(const SpMatrix<double>& a, std::vector<double>& hold) const {
+            if (a.values.empty()) return nullptr;
+            if (a.rows() != n_ || a.cols() != n_) throw std::runtime_error("BlockSolver: every block must be n_dofs x n_dofs");
+            if (a.rowptr == rowptr_ && a.colidx == colidx_) return a.values.data();
+            hold.assign(colidx_.size(), 0.0);
+            for (int64_t i = 0; i < n_; ++i) {
+                int32_t k = rowptr_[(size_t)i];
+                for (int32_t t = a.rowptr[(size_t)i]; t < a.rowptr[(size_t)i + 1]; ++t) {
+                    while (k < rowptr_[(size_t)i + 1] && colidx_[(size_t)k] < a.colidx[(size_t)t]) ++k;
+                    if (k == rowptr_[(size_t)i + 1] || colidx_[(size_t)k] != a.colidx[(size_t)t])
+                        throw std::runtime_error("BlockSolver: a block has an entry off the FEM pattern");
+                    hold[(size_t)k] += a.values[(size_t)t];
+                }
+            }
+            return hold.data();
+        }
+        fdapde::hip::context_handle ctx_;
+        int64_t n_ = 0;
+        std::vector<int32_t> rowptr_, colidx_;
+        bool computed_ = false;
+        fdapde_options opt_ {FDAPDE_SOLVER_AUTO, 0, 0.0, FDAPDE_ASSEMBLY_ROWS, 0, 0};
+    };
+    BlockSolver make_block_solver() {
+        ctx_.unique();   // (as make_solver)
+        return BlockSolver(ctx_.observer(), n_dofs_, stiff_.rowptr, stiff_.colidx);
+    }
+    bool owns_context_of(const BlockSolver& s) const { return s.ctx_.shared_with(ctx_); }
 
    private:
     // rows of (column, value) pairs -> CSR with sorted columns, duplicates summed like setFromTriplets

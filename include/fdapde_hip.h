@@ -282,6 +282,36 @@ int fdapde_solve_parabolic(fdapde_ctx *ctx, const fdapde_options *opt, int32_t n
 int fdapde_lin_compute(fdapde_ctx *ctx, int32_t which, const double *values, int32_t symmetric);
 int fdapde_lin_solve(fdapde_ctx *ctx, const fdapde_options *opt, const double *b, int32_t n_rhs, double *x, fdapde_info *info);
 
+/* ---- 2 x 2 block systems on the FEM pattern: fdapde::SparseLU on a SparseBlockMatrix<double,2,2> (fdaPDE/linear_algebra/sparse_block_matrix.h:29-128,
+ *      utils/symbols.h:133-160) -- the smoothing system [ -Psi^T W Psi, lambda R1^T ; lambda R1, lambda R0 ] the downstream models factor once and solve
+ *      for many columns, directly or under SMW (linear_algebra/smw.h:38-59).  Every block lies on the pattern of stiff() / mass().
+ * fdapde_block_compute: each pointer holds nnz values aligned with fdapde_pattern_get, NULL = a zero block; at least one of a11 / a12 and one of a21 / a22
+ * must be given (FDAPDE_EINVAL).  Needs fdapde_dofs_build (FDAPDE_ENOTINIT); a rank of a multi-GPU job and a multi-device context: FDAPDE_EUNSUPPORTED.
+ * On the device the blocks become ONE block CSR in the solver's internal DOF order (four contiguous doubles per pattern entry, one column index) and the
+ * unknowns are interleaved per DOF; a second copy holds D^-1 A, D = the 2 x 2 diagonal block of every DOF (left block-Jacobi, folded in once).  A
+ * diagonal block with |det| <= 1e-14 max|entry|^2 makes the Krylov stage unavailable for that matrix.  `symmetric` is recorded only.  Independent of
+ * fdapde_lin_compute's handle: both may be live.  fdapde_ctx_clone does NOT carry the block handle (fdapde_block_solve on a clone: FDAPDE_ENOTINIT);
+ * fdapde_dofs_build drops it.
+ * fdapde_block_solve: b and x column-major 2 n_dofs x n_rhs, stacked as the reference stacks them (rows 0 .. n-1 the first block row, n .. 2n-1 the
+ * second, DOF ids); x may overlap b.  FDAPDE_SOLVER_GMRES: restarted GMRES(gmres_m = 50) on D^-1 A, columns one after another, stop rule
+ * |D^-1 (b - A x)| <= rtol |D^-1 b| on the true residual at the end of a cycle (rtol <= 0: 1e-10; maxit <= 0: 2000); FDAPDE_EUNSUPPORTED where a diagonal
+ * block is singular.  FDAPDE_SOLVER_DENSE: 2 n <= dense_rows (8192): the dense inverse of the 2 n-row matrix, built in the call, all columns in one product;
+ * above the limit FDAPDE_EUNSUPPORTED, a singular matrix FDAPDE_ENOCONV.  FDAPDE_SOLVER_AUTO: GMRES, and the rent-or-buy rule of fdapde_lin_solve with 2 n
+ * as the row count (more than `dense_after` columns asked for and half of dense_build_estimate_ms spent on Krylov columns: the inverse from then on; at
+ * once where the Krylov stage is unavailable).  Every other method: FDAPDE_EUNSUPPORTED.  info as fdapde_lin_solve: iters summed over the columns, relres
+ * the worst column's, method_used the stage; FDAPDE_ENOCONV leaves the last iterate of every column in x.
+ * fdapde_block_spmv: y = A x with the unscaled blocks, stacked host vectors of 2 n_dofs (parity tests, the byte figure).
+ * fdapde_block_bench_spmv: times `reps` launches of the Krylov stage's operator kernel (k_block_spmv on D^-1 A) with HIP events; algorithmic bytes per
+ * launch 36 nnz + 4 (n + 1) + 32 n.
+ * fdapde_gram_pointwise: Psi^T W Psi on the FEM pattern (nnz values aligned with fdapde_pattern_get) from what fdapde_eval_pointwise / fdapde_project hand
+ * out: reference cell ids and row-major n_locs x n_basis values; rows with cell id -1 are skipped, weights may be NULL (all ones); a cell id the mesh does
+ * not have: FDAPDE_EINVAL.  Accumulated on the device with fp64 atomics: the order of the additions, hence the last bits, may differ run to run. */
+int fdapde_block_compute(fdapde_ctx *ctx, const double *a11, const double *a12, const double *a21, const double *a22, int32_t symmetric);
+int fdapde_block_solve(fdapde_ctx *ctx, const fdapde_options *opt, const double *b, int32_t n_rhs, double *x, fdapde_info *info);
+int fdapde_block_spmv(fdapde_ctx *ctx, const double *x, double *y);
+int fdapde_block_bench_spmv(fdapde_ctx *ctx, int32_t reps, double *avg_ms, double *algorithmic_bytes);
+int fdapde_gram_pointwise(fdapde_ctx *ctx, int64_t n_locs, const int32_t *cell_ids, const double *values, const double *weights, double *out_values);
+
 /* ---- basis evaluation (PDE__::eval_basis, pde/pde.h:149-158; policies basis/lagrangian_basis.h:203-283) -------------------
  * fdapde_eval_pointwise: for each location (column-major n_locs x N) the containing cell (reference cell id, -1 if outside;
  * TreeSearch::locate, geometry/tree_search.h:73-90) and the n_basis values psi_h(invJ (p - x0)), row-major n_locs x n_basis.
