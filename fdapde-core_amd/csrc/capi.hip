@@ -281,14 +281,17 @@ int fdapde_solver_trace(fdapde_ctx* c, int32_t* small_front, int32_t* graph_repl
     if (graph_replays) *graph_replays = c->graph_replays;
     return FDAPDE_OK;
 }
+static const char* const kBlockAmgOnly = "FDAPDE_SOLVER_BLOCK_AMG is a method of fdapde_block_solve (the 2 x 2 block handle) only";
 int fdapde_solve(fdapde_ctx* c, const fdapde_options* opt, fdapde_info* info) {
     if (!c) return FDAPDE_EINVAL;
+    if (opt && opt->method == FDAPDE_SOLVER_BLOCK_AMG) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, kBlockAmgOnly);
     if (c->group && opt && opt->method == FDAPDE_SOLVER_AMG) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_AMG takes one-GPU contexts, not a multi-device context");
     if (c->group) return fdapde_engine::g_solve(c, opt, info);
     return fdapde_engine::e_solve(c, opt, info);
 }
 int fdapde_solve_parabolic(fdapde_ctx* c, const fdapde_options* opt, int32_t n_times, double delta_t, const double* initial_condition, const double* dirichlet, double* solution, fdapde_info* info) {
     if (!c) return FDAPDE_EINVAL;
+    if (opt && opt->method == FDAPDE_SOLVER_BLOCK_AMG) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, kBlockAmgOnly);
     if (c->group && opt && opt->method == FDAPDE_SOLVER_AMG) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_AMG takes one-GPU contexts, not a multi-device context");
     if (c->group) return fdapde_engine::g_solve_parabolic(c, opt, n_times, delta_t, initial_condition, dirichlet, solution, info);
     return fdapde_engine::e_solve_parabolic(c, opt, n_times, delta_t, initial_condition, dirichlet, solution, info);
@@ -300,6 +303,7 @@ int fdapde_lin_compute(fdapde_ctx* c, int32_t which, const double* values, int32
 }
 int fdapde_lin_solve(fdapde_ctx* c, const fdapde_options* opt, const double* b, int32_t n_rhs, double* x, fdapde_info* info) {
     if (!c) return FDAPDE_EINVAL;
+    if (opt && opt->method == FDAPDE_SOLVER_BLOCK_AMG) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, kBlockAmgOnly);
     if (c->group && opt && opt->method == FDAPDE_SOLVER_AMG) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_AMG takes one-GPU contexts, not a multi-device context");
     if (c->group) return fdapde_engine::g_lin_solve(c, opt, b, n_rhs, x, info);
     return fdapde_engine::e_lin_solve(c, opt, b, n_rhs, x, info);

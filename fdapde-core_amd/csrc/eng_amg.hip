@@ -31,6 +31,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "context.h"
+#include "amg_setup.h"
 #include "engine.h"
 #include "kernels_reduce.h"
 
@@ -366,20 +367,6 @@ template <typename F> void by_team(int T, F&& f) {
 }
 }   // namespace
 
-struct AmgLevel {
-    int64_t n = 0, nnz = 0;
-    DBuf<int32_t> rp_own, ci_own;
-    DBuf<double> a_own;
-    const int32_t *rp = nullptr, *ci = nullptr;   // level 0: the context's pattern and the caller's values; below: the level's own arrays
-    const double* a = nullptr;
-    const uint8_t* excl = nullptr;                // rows that belong to no aggregate (level 0's Dirichlet DOFs)
-    DBuf<double> dinv;
-    double om = 0.0;
-    int team = 4, np = 1;
-    DBuf<int32_t> agg, mptr, midx;                // row -> row of the next level (-1: none); members of each next-level row, ascending
-    DBuf<double> b, zt, cv, v, dv, w, rt, e, part, sc;   // work vectors (b: the restricted right-hand side; e: this level's correction)
-};
-
 struct AmgHierarchy {
     std::vector<std::unique_ptr<AmgLevel>> lv;
     fdapde_ctx::Dense D;                          // the coarsest level's inverse
@@ -397,13 +384,7 @@ struct AmgHierarchy {
     }
 };
 
-namespace {
-// ---- the host loops of the same set-up (knob amg_setup_check): the same arithmetic in the same order ----
-struct HostCsr {
-    int64_t n = 0;
-    std::vector<int32_t> rp, ci;
-    std::vector<double> a;
-};
+// ---- the host loops of the same set-up (knob amg_setup_check): the same arithmetic in the same order (declared in amg_setup.h) ----
 void host_pairwise(const HostCsr& A, const uint8_t* excl, std::vector<int32_t>& agg, int32_t& nc) {
     const int64_t n = A.n;
     std::vector<double> sw(A.a.size());
@@ -448,6 +429,7 @@ void host_galerkin(const HostCsr& A, const std::vector<int32_t>& agg, int32_t nc
     }
     for (int32_t r = 0; r < nc; ++r) C.rp[(size_t)r + 1] += C.rp[(size_t)r];
 }
+namespace {
 template <typename T> bool same_dev(const T* p, size_t n, const std::vector<T>& h) {
     if (h.size() != n) return false;
     std::vector<T> g(n);
@@ -459,6 +441,8 @@ template <typename T> int fetch(fdapde_ctx* c, const T* p, size_t n, std::vector
     if (n) HIPCHK(c, hipMemcpy(h.data(), p, sizeof(T) * n, hipMemcpyDeviceToHost));
     return FDAPDE_OK;
 }
+
+}   // namespace
 
 // one pairwise pass on the device: agg (n words), *nc; scratch kept by the caller
 int dev_pairwise(fdapde_ctx* c, int64_t n, int64_t nnz, const int32_t* rp, const int32_t* ci, const double* a, const uint8_t* excl, DBuf<int32_t>& agg, int32_t* nc) {
@@ -491,13 +475,18 @@ int dev_pairwise(fdapde_ctx* c, int64_t n, int64_t nnz, const int32_t* rp, const
     HIPCHK(c, hipStreamSynchronize(st));
     return FDAPDE_OK;
 }
+namespace {
 inline int key_bits(uint64_t v) {
     int b = 1;
     while (b < 64 && (v >> b) != 0) ++b;
     return b;
 }
+}   // namespace
+
 // the Galerkin product P^T A P of piecewise-constant P (agg) on the device: a stable key sort, a segmented sum in ascending fine-slot order
-int dev_galerkin(fdapde_ctx* c, int64_t n, int64_t nnz, const int32_t* rp, const int32_t* ci, const double* a, const int32_t* agg, int32_t nc, AmgLevel& out) {
+// (keep: the sorted keys and slots stay with the caller, who sums further values per coarse entry in the same order -- eng_block_amg.hip)
+int dev_galerkin(fdapde_ctx* c, int64_t n, int64_t nnz, const int32_t* rp, const int32_t* ci, const double* a, const int32_t* agg, int32_t nc, AmgLevel& out,
+                 AmgGalerkinMap* keep) {
     hipStream_t st = c->stream;
     const dim3 bv(256);
     const uint64_t ncu = (uint64_t)nc, sentinel = ncu * ncu;
@@ -532,6 +521,13 @@ int dev_galerkin(fdapde_ctx* c, int64_t n, int64_t nnz, const int32_t* rp, const
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(st));   // (nnz_c is this frame's; the scratch goes out of scope)
     out.rp = out.rp_own.p, out.ci = out.ci_own.p, out.a = out.a_own.p;
+    if (keep) {
+        std::swap(keep->keys.p, keys_s.p), std::swap(keep->keys.n, keys_s.n);
+        std::swap(keep->idx.p, idx_s.p), std::swap(keep->idx.n, idx_s.n);
+        std::swap(keep->head.p, head.p), std::swap(keep->head.n, head.n);
+        std::swap(keep->pos.p, pos.p), std::swap(keep->pos.n, pos.n);
+        keep->m = nnz, keep->nc = ncu;
+    }
     return FDAPDE_OK;
 }
 // members of each aggregate (CSR, ascending row index)
@@ -557,6 +553,7 @@ int dev_members(fdapde_ctx* c, int64_t n, const int32_t* agg, int32_t nc, DBuf<i
     HIPCHK(c, hipStreamSynchronize(st));
     return FDAPDE_OK;
 }
+namespace {
 // D^-1, the Jacobi damping 1.5 / lambda_max(D^-1 A) (15 power iterations), team width and work vectors of a level
 int level_prepare(fdapde_ctx* c, AmgLevel& L, bool has_next) {
     hipStream_t st = c->stream;
@@ -867,6 +864,15 @@ int e_solve_amg(fdapde_ctx* c, const fdapde_options* opt, fdapde_info* info) {
     c->solved = true, c->dirichlet_applied = c->have_g;
     if (info) *info = c->info;
     return rc;
+}
+
+// the K-cycle's helpers on vectors of any length (the block cycle of eng_block_amg.hip runs them on 2 n_l words)
+void amg_launch_coef(hipStream_t st, const double* part, int np, int stage, double* sc) { hipLaunchKernelGGL(k_amg_coef, dim3(1), dim3(256), 0, st, part, np, stage, sc); }
+void amg_launch_axpy_sc(hipStream_t st, int64_t n, const double* b, const double* v, const double* sc, double* rt) {
+    hipLaunchKernelGGL(k_amg_axpy_sc, dim3(gn(n)), dim3(256), 0, st, n, b, v, sc, rt);
+}
+void amg_launch_comb2(hipStream_t st, int64_t n, const double* cv, const double* dv, const double* sc, double* e) {
+    hipLaunchKernelGGL(k_amg_comb2, dim3(gn(n)), dim3(256), 0, st, n, cv, dv, sc, e);
 }
 
 void amg_forget(fdapde_ctx* c) {

@@ -2,7 +2,8 @@
 // smoothing system the downstream models factor once and solve for many columns: fdaPDE/linear_algebra/sparse_block_matrix.h:29-128,
 // utils/symbols.h:133-160, linear_algebra/smw.h:38-59), and Psi^T W Psi on that pattern (kernels_block.h).
 //   fdapde_block_compute   blocks -> block CSR in the internal order, D^-1 A folded into a second copy (left block-Jacobi)
-//   fdapde_block_solve     restarted GMRES(m) on D^-1 A (kernels_gmres.h, buffers of the handle's own), or the dense inverse of the 2 n-row matrix
+//   fdapde_block_solve     restarted GMRES(m) on D^-1 A (kernels_gmres.h, buffers of the handle's own), or the dense inverse of the 2 n-row matrix, or
+//                          (by name) flexible GMRES around the point-block multilevel cycle of eng_block_amg.hip
 //   fdapde_block_spmv      y = A x with the unscaled blocks
 //   fdapde_gram_pointwise  Psi^T W Psi from what fdapde_eval_pointwise / fdapde_project hand out
 // Independent of the n x n handle of fdapde_lin_compute: nothing here writes a buffer one of the other solves reads back.
@@ -34,6 +35,9 @@ struct BlockHandle {
     fdapde_ctx::Dense dense;
     int64_t cols = 0;                  // columns solved against the current matrix
     double krylov_ms = 0;              // ... and the host time the Krylov columns among them took
+    bool given[4] = {false, false, false, false};   // which of a11 a12 a21 a22 were handed over (not NULL)
+    BlockAmg* amg = nullptr;           // FDAPDE_SOLVER_BLOCK_AMG's hierarchy of the current matrix (eng_block_amg.hip), built by its first solve
+    ~BlockHandle() { block_amg_free(amg); }
 };
 
 void block_release(fdapde_ctx* c) {
@@ -136,6 +140,52 @@ int block_dense_build(fdapde_ctx* c, BlockHandle& B) {
     return dense_build_csr(c, 2 * n, B.rowptr2.p, B.colidx2.p, B.val2.p, nullptr, 0, B.dense);
 }
 
+// FDAPDE_SOLVER_BLOCK_AMG by name: the hierarchy built by the first such solve after fdapde_block_compute, the columns one after another on the UNSCALED
+// system (stop rule: the true residual |b - A x| <= rtol |b| -- not the D^-1-scaled one of the GMRES stage)
+int block_amg_solve(fdapde_ctx* c, BlockHandle& B, const fdapde_options* opt, const double* b, int32_t n_rhs, double* x, fdapde_info* info) {
+    const int64_t n = B.n, n2 = 2 * n;
+    hipStream_t st = c->stream;
+    const double rtol = (opt && opt->rtol > 0) ? opt->rtol : 1e-10;
+    const int maxit = (opt && opt->maxit > 0) ? opt->maxit : 200;
+    fdapde_info out{};
+    out.method_used = FDAPDE_SOLVER_BLOCK_AMG;
+    const auto t_call = std::chrono::steady_clock::now();
+    if (!B.jacobi_ok)
+        return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_BLOCK_AMG: a DOF's diagonal block is singular (|det| <= 1e-14 max|entry|^2): no block-Jacobi smoother");
+    if (!B.amg) {
+        const int strength = B.given[2] ? 2 : B.given[1] ? 1 : B.given[3] ? 3 : 0;   // the (2,1) block, else (1,2), (2,2), (1,1)
+        if (int rc = block_amg_build(c, &B.amg, B.raw.p, strength)) {
+            c->info = out;
+            if (info) *info = out;
+            return rc;
+        }
+    }
+    HIPCHK(c, B.ext.alloc((size_t)std::max<int64_t>(4 * B.nnz, 2 * n)));
+    int total = 0, rc_all = FDAPDE_OK;   // (B.cols and B.krylov_ms stay: the open method's rent-or-buy rule counts its own columns only)
+    double worst = 0;
+    bool broke_any = false;
+    for (int32_t j = 0; j < n_rhs; ++j) {
+        HIPCHK(c, hipMemcpyAsync(B.ext.p, b + (size_t)j * n2, sizeof(double) * (size_t)n2, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_block_stage, dim3(g1(n), 1), dim3(256), 0, st, n, c->dof_i2e.p, B.ext.p, nullptr, B.bt.p);
+        int it = 0;
+        double rel = 0;
+        bool conv = false, broke = false;
+        if (int rc = block_amg_run(c, B.amg, B.raw.p, B.bt.p, B.x.p, rtol, maxit, &it, &rel, &conv, &broke)) return rc;
+        if (!conv) rc_all = FDAPDE_ENOCONV, broke_any = broke_any || broke;
+        total += it, worst = rel > worst || std::isnan(rel) ? rel : worst;
+        hipLaunchKernelGGL(k_block_unstage, dim3(g1(n), 1), dim3(256), 0, st, n, c->dof_i2e.p, B.x.p, B.ext.p);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(x + (size_t)j * n2, B.ext.p, sizeof(double) * (size_t)n2, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+    }
+    out.iters = total, out.relres = worst, out.converged = rc_all == FDAPDE_OK ? 1 : 0, out.persistent = 0;
+    out.t_solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+    c->info = out;
+    if (info) *info = out;
+    if (rc_all == FDAPDE_ENOCONV) c->err = broke_any ? "FDAPDE_SOLVER_BLOCK_AMG: the flexible GMRES broke down in at least one column" : "FDAPDE_SOLVER_BLOCK_AMG: maxit reached in at least one column";
+    return rc_all;
+}
+
 }   // namespace
 
 int e_block_compute(fdapde_ctx* c, const double* a11, const double* a12, const double* a21, const double* a22, int32_t symmetric) {
@@ -150,6 +200,8 @@ int e_block_compute(fdapde_ctx* c, const double* a11, const double* a12, const d
     BlockHandle& B = *c->block;
     B.ready = false, B.expanded = false, B.n = n, B.nnz = nnz, B.symmetric = symmetric != 0;
     B.dense.ready = B.dense.failed = false, B.cols = 0, B.krylov_ms = 0;
+    block_amg_free(B.amg), B.amg = nullptr;   // (the hierarchy belonged to the previous matrix)
+    B.given[0] = a11 != nullptr, B.given[1] = a12 != nullptr, B.given[2] = a21 != nullptr, B.given[3] = a22 != nullptr;
     HIPCHK(c, B.ext.alloc((size_t)std::max<int64_t>(4 * nnz, 2 * n)));
     HIPCHK(c, B.raw.alloc((size_t)(4 * nnz)));
     HIPCHK(c, B.scaled.alloc((size_t)(4 * nnz)));
@@ -232,8 +284,9 @@ int e_block_solve(fdapde_ctx* c, const fdapde_options* opt, const double* b, int
     hipStream_t st = c->stream;
     const int method = opt ? opt->method : FDAPDE_SOLVER_AUTO;
     const bool open = method == FDAPDE_SOLVER_AUTO, dense_named = method == FDAPDE_SOLVER_DENSE;
+    if (method == FDAPDE_SOLVER_BLOCK_AMG) return block_amg_solve(c, B, opt, b, n_rhs, x, info);
     if (!open && !dense_named && method != FDAPDE_SOLVER_GMRES)
-        return fail(c, FDAPDE_EUNSUPPORTED, "fdapde_block_solve runs FDAPDE_SOLVER_GMRES, FDAPDE_SOLVER_DENSE or the open method");
+        return fail(c, FDAPDE_EUNSUPPORTED, "fdapde_block_solve runs FDAPDE_SOLVER_GMRES, FDAPDE_SOLVER_DENSE, FDAPDE_SOLVER_BLOCK_AMG or the open method");
     const double rtol = (opt && opt->rtol > 0) ? opt->rtol : 1e-10;
     const int maxit = (opt && opt->maxit > 0) ? opt->maxit : 2000;
     fdapde_info out{};

@@ -1,0 +1,362 @@
+// eng_block_amg.hip -- FDAPDE_SOLVER_BLOCK_AMG: flexible GMRES around a K-cycle over an aggregation hierarchy of POINT-BLOCK unknowns, for the 2 x 2 block
+// handle of eng_block.hip (the smoothing system [ -Psi^T W Psi, lambda R1^T ; lambda R1, lambda R0 ]).
+//
+// Why: above the dense limit the handle's only stage is GMRES(50) on the block-Jacobi-scaled system, whose iterations grow like 1 / h and each of which
+// costs ten operator applications in Gram-Schmidt.  Short recurrences break down on this symmetric indefinite system; the scheme of
+// FDAPDE_SOLVER_AMG (eng_amg.hip) with the two unknowns of a DOF kept together does not.
+//
+// What:
+//   set-up    level 0 is the handle's unscaled block CSR.  The aggregates come from eng_amg.hip's two pairwise passes (dev_pairwise, unchanged) on a SCALAR
+//             strength matrix on the same pattern: the (2,1) block as given -- (1,2), (2,2), (1,1) where it was NULL --, whose Galerkin product
+//             (dev_galerkin) is the next level's pattern and strength matrix.  The four block values of a coarse entry are summed with the same keys in
+//             ascending fine-slot order (k_bamg_gsum): P = P_scalar (x) I_2, unknowns interleaved on every level, no float atomics.  Levels until one has
+//             at most `amg_coarse_rows` rows (counted in 2 n_l); that one goes through k_block_expand + dense_build_csr.
+//   cycle     0.7 D^-1 (D the 2 x 2 diagonal blocks), the coarse correction, 0.7 D^-1 (kernels_block.h k_bamg_*).  Below the finest level the coarse
+//             correction is always two GCR steps preconditioned by the next level's cycle -- GCR because the system is indefinite (flexible CG may divide
+//             by zero), no early exit (it would need a host read-back inside the cycle).
+//   outer     fgmres_outer (eng_pmg.hip) on the UNSCALED system, right-preconditioned by the cycle; the stop rule is the true residual |b - A x| <= rtol |b|.
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "amg_setup.h"
+#include "context.h"
+#include "engine.h"
+#include "kernels_block.h"
+#include "kernels_dense.h"
+
+namespace fdapde_engine {
+
+namespace {
+using namespace fdapde_hip;
+
+constexpr double kBamgOmega = 0.7;   // the smoother's damping: fixed (the spectrum of D^-1 A is not one-sided: no power iteration)
+constexpr double kBamgStall = 0.8;   // a level that keeps more than this share of its rows ends the hierarchy
+constexpr int kBamgMaxRestart = 64;  // fgmres_outer's Gram-Schmidt kernels hold that many coefficients
+
+struct BamgLevel {
+    int64_t n = 0, nnz = 0;                       // block rows, pattern entries
+    AmgLevel S;                                   // the scalar strength matrix on the level's pattern (level 0: the context's pattern, own values)
+    const int32_t *rp = nullptr, *ci = nullptr;
+    const double* bv = nullptr;                   // four doubles per entry (level 0: the handle's)
+    DBuf<double> bv_own, dinv;
+    int team = 8, np = 1;
+    DBuf<int32_t> agg, mptr, midx;                // row -> row of the next level; members of each next-level row, ascending
+    DBuf<double> b, zt, cv, v, dv, w, rt, e, part, sc;
+};
+}   // namespace
+
+struct BlockAmg {
+    std::vector<std::unique_ptr<BamgLevel>> lv;
+    fdapde_ctx::Dense D;                          // the coarsest level's inverse (2 n_L rows)
+    DBuf<int32_t> rp2, ci2;
+    DBuf<double> val2;
+    DBuf<double> vec, basis, part, dots;          // the outer iteration's x, r, t, b and the flexible GMRES basis
+    double setup_ms = 0.0;
+    ~BlockAmg() { D.X.release(); }
+};
+
+void block_amg_free(BlockAmg* h) { delete h; }
+
+namespace {
+inline unsigned gn(int64_t n) { return (unsigned)((n + 255) / 256); }
+
+template <typename F> void by_team(int T, F&& f) {
+    if (T <= 8) f(std::integral_constant<int, 8>{});
+    else f(std::integral_constant<int, 16>{});
+}
+
+template <typename T> int fetch(fdapde_ctx* c, const T* p, size_t n, std::vector<T>& h) {
+    h.resize(n);
+    if (n) HIPCHK(c, hipMemcpy(h.data(), p, sizeof(T) * n, hipMemcpyDeviceToHost));
+    return FDAPDE_OK;
+}
+
+// the block values of P^T A P by the host loops: host_galerkin's keys and order (eng_amg.hip), four sums per coarse entry
+void host_block_galerkin(const HostCsr& A, const std::vector<double>& bv, const std::vector<int32_t>& agg, int32_t nc, std::vector<double>& out) {
+    std::vector<std::pair<uint64_t, int32_t>> ent;
+    for (int64_t i = 0; i < A.n; ++i)
+        for (int32_t k = A.rp[(size_t)i]; k < A.rp[(size_t)i + 1]; ++k)
+            ent.emplace_back((uint64_t)agg[(size_t)i] * (uint64_t)nc + (uint64_t)agg[(size_t)A.ci[(size_t)k]], k);
+    std::stable_sort(ent.begin(), ent.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
+    out.clear();
+    for (size_t e = 0; e < ent.size();) {
+        const uint64_t key = ent[e].first;
+        double s[4] = {0.0, 0.0, 0.0, 0.0};
+        for (; e < ent.size() && ent[e].first == key; ++e)
+            for (int q = 0; q < 4; ++q) s[q] += bv[4 * (size_t)ent[e].second + q];
+        out.insert(out.end(), s, s + 4);
+    }
+}
+
+// the block values of the coarse entries dev_galerkin just formed (map: what it sorted)
+int block_galerkin(fdapde_ctx* c, const AmgGalerkinMap& map, const double* bv, int64_t nnz_c, DBuf<double>& out) {
+    HIPCHK(c, out.alloc(4 * (size_t)std::max<int64_t>(nnz_c, 1)));
+    hipLaunchKernelGGL(k_bamg_gsum, dim3(gn(map.m)), dim3(256), 0, c->stream, map.m, map.keys.p, map.idx.p, map.head.p, map.pos.p, bv, out.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // (the map is the caller's local)
+    return FDAPDE_OK;
+}
+
+// D^-1 of a level's diagonal blocks (today's 1e-14 rule: k_block_diag_inv); *bad: a block was singular
+int level_dinv(fdapde_ctx* c, BamgLevel& L, bool* bad) {
+    hipStream_t st = c->stream;
+    DBuf<int32_t> flag;
+    HIPCHK(c, flag.alloc(1));
+    HIPCHK(c, hipMemsetAsync(flag.p, 0, sizeof(int32_t), st));
+    HIPCHK(c, L.dinv.alloc(4 * (size_t)L.n));
+    hipLaunchKernelGGL(k_block_diag_inv, dim3(gn(L.n)), dim3(256), 0, st, L.n, L.rp, L.ci, L.bv, L.dinv.p, flag.p);
+    HIPCHK(c, hipGetLastError());
+    int32_t h = 0;
+    HIPCHK(c, hipMemcpyAsync(&h, flag.p, sizeof h, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    *bad = h != 0;
+    return FDAPDE_OK;
+}
+
+int level_vectors(fdapde_ctx* c, BamgLevel& L) {
+    const size_t n2 = 2 * (size_t)std::max<int64_t>(L.n, 1);
+    const double per_row = L.n > 0 ? (double)L.nnz / (double)L.n : 1.0;
+    L.team = per_row <= 12.0 ? 8 : 16;
+    L.np = (int)std::min<int64_t>(1024, std::max<int64_t>(1, (L.n * L.team + 1023) / 1024));
+    for (DBuf<double>* p : {&L.b, &L.zt, &L.cv, &L.v, &L.dv, &L.w, &L.rt, &L.e}) HIPCHK(c, p->alloc(n2));
+    HIPCHK(c, L.part.alloc(3 * (size_t)std::max(L.np, 1024)));
+    HIPCHK(c, L.sc.alloc(8));
+    HIPCHK(c, hipMemsetAsync(L.sc.p, 0, 8 * sizeof(double), c->stream));
+    return FDAPDE_OK;
+}
+
+int bamg_correction(fdapde_ctx* c, BlockAmg& H, size_t m);
+// out = the cycle of level l on r (l < coarsest)
+int bamg_cycle(fdapde_ctx* c, BlockAmg& H, size_t l, const double* r, double* out) {
+    hipStream_t st = c->stream;
+    BamgLevel& L = *H.lv[l];
+    BamgLevel& N = *H.lv[l + 1];
+    by_team(L.team, [&](auto t) {
+        constexpr int T = decltype(t)::value;
+        hipLaunchKernelGGL(k_bamg_pre_restrict<T>, dim3(g1(N.n, 256 / T)), dim3(256), 0, st, N.n, L.mptr.p, L.midx.p, L.rp, L.ci, L.bv, L.dinv.p, kBamgOmega, r, L.zt.p,
+                           N.b.p, (const int32_t*)nullptr);
+    });
+    if (int rc = bamg_correction(c, H, l + 1)) return rc;
+    by_team(L.team, [&](auto t) {
+        constexpr int T = decltype(t)::value;
+        hipLaunchKernelGGL(k_bamg_post<T>, dim3(g1(L.n, 256 / T)), dim3(256), 0, st, L.n, L.rp, L.ci, L.bv, L.dinv.p, kBamgOmega, L.agg.p, N.e.p, r, L.zt.p, out,
+                           (const int32_t*)nullptr);
+    });
+    return FDAPDE_OK;
+}
+// e_m = (level m's matrix)^-1 b_m approximately: the dense inverse on the coarsest level, two GCR steps around the cycle elsewhere (k_amg_coef's GCR
+// reading: rho1 = v.v, alpha1 = v.b; gamma = v.w, rho2 = w.w - gamma^2 / rho1, alpha2 = w.rt)
+int bamg_correction(fdapde_ctx* c, BlockAmg& H, size_t m) {
+    hipStream_t st = c->stream;
+    BamgLevel& L = *H.lv[m];
+    if (m + 1 == H.lv.size()) return dense_apply(c, H.D, 1, L.b.p, L.e.p);
+    const int64_t n = L.n;
+    auto spmv_dots = [&](const double* x, double* y, const double* p0, const double* q0, const double* p1, const double* q1, const double* p2, const double* q2) {
+        by_team(L.team, [&](auto t) {
+            constexpr int T = decltype(t)::value;
+            hipLaunchKernelGGL(k_bamg_spmv_dots<T>, dim3((unsigned)L.np), dim3(256), 0, st, n, L.rp, L.ci, L.bv, x, y, p0, q0, p1, q1, p2, q2, L.part.p,
+                               (const int32_t*)nullptr);
+        });
+    };
+    if (int rc = bamg_cycle(c, H, m, L.b.p, L.cv.p)) return rc;   // c = B b, v = A c
+    spmv_dots(L.cv.p, L.v.p, L.v.p, L.v.p, L.v.p, L.b.p, nullptr, nullptr);
+    amg_launch_coef(st, L.part.p, L.np, 1, L.sc.p);
+    amg_launch_axpy_sc(st, 2 * n, L.b.p, L.v.p, L.sc.p, L.rt.p);
+    if (int rc = bamg_cycle(c, H, m, L.rt.p, L.dv.p)) return rc;  // d = B rt, w = A d
+    spmv_dots(L.dv.p, L.w.p, L.v.p, L.w.p, L.w.p, L.w.p, L.w.p, L.rt.p);
+    amg_launch_coef(st, L.part.p, L.np, 2, L.sc.p);
+    amg_launch_comb2(st, 2 * n, L.cv.p, L.dv.p, L.sc.p, L.e.p);
+    return FDAPDE_OK;
+}
+}   // namespace
+
+// the hierarchy of the handle's matrix: raw = the unscaled block CSR on the context's pattern, strength_block = which of its four blocks the aggregation reads
+int block_amg_build(fdapde_ctx* c, BlockAmg** slot, const double* raw, int strength_block) {
+    delete *slot;
+    *slot = nullptr;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::unique_ptr<BlockAmg> H(new BlockAmg());
+    const int64_t dense_limit = std::min<int64_t>(c->dense_rows, kDenseMaxRows);
+    const int64_t coarse_rows = std::max<int64_t>(2, std::min<int64_t>(c->amg_coarse_rows, kDenseMaxRows));
+    {
+        std::unique_ptr<BamgLevel> L0(new BamgLevel());
+        L0->n = c->hs.n_dofs, L0->nnz = c->hs.nnz, L0->rp = c->rowptr.p, L0->ci = c->colidx.p, L0->bv = raw;
+        AmgLevel& S = L0->S;
+        S.n = L0->n, S.nnz = L0->nnz, S.rp = L0->rp, S.ci = L0->ci;
+        HIPCHK(c, S.a_own.alloc((size_t)std::max<int64_t>(S.nnz, 1)));
+        hipLaunchKernelGGL(k_bamg_pick, dim3(gn(S.nnz)), dim3(256), 0, st, S.nnz, raw, strength_block, S.a_own.p);
+        HIPCHK(c, hipGetLastError());
+        S.a = S.a_own.p;
+        H->lv.push_back(std::move(L0));
+    }
+    while (2 * H->lv.back()->n > coarse_rows) {
+        BamgLevel& F = *H->lv.back();
+        // pass 1 on the level's strength matrix, pass 2 on its Galerkin matrix (the pair graph): aggregates of at most four rows; the block values follow
+        DBuf<int32_t> agg1, agg2;
+        int32_t n1 = 0, n2 = 0;
+        if (int rc = dev_pairwise(c, F.n, F.nnz, F.rp, F.ci, F.S.a, nullptr, agg1, &n1)) return rc;
+        AmgLevel T;
+        DBuf<double> bvT;
+        {
+            AmgGalerkinMap map;
+            if (int rc = dev_galerkin(c, F.n, F.nnz, F.rp, F.ci, F.S.a, agg1.p, n1, T, &map)) return rc;
+            if (int rc = block_galerkin(c, map, F.bv, T.nnz, bvT)) return rc;
+        }
+        if (int rc = dev_pairwise(c, T.n, T.nnz, T.rp, T.ci, T.a, nullptr, agg2, &n2)) return rc;
+        std::unique_ptr<BamgLevel> N(new BamgLevel());
+        {
+            AmgGalerkinMap map;
+            if (int rc = dev_galerkin(c, T.n, T.nnz, T.rp, T.ci, T.a, agg2.p, n2, N->S, &map)) return rc;
+            if (int rc = block_galerkin(c, map, bvT.p, N->S.nnz, N->bv_own)) return rc;
+        }
+        N->n = N->S.n, N->nnz = N->S.nnz, N->rp = N->S.rp, N->ci = N->S.ci, N->bv = N->bv_own.p;
+        HIPCHK(c, F.agg.alloc((size_t)F.n));
+        hipLaunchKernelGGL(k_bamg_compose, dim3(gn(F.n)), dim3(256), 0, st, F.n, agg1.p, agg2.p, F.agg.p);
+        HIPCHK(c, hipGetLastError());
+        if (int rc = dev_members(c, F.n, F.agg.p, n2, F.mptr, F.midx)) return rc;
+        if (c->amg_setup_check) {   // the same level by the host loops, compared bit for bit
+            HostCsr hf, ht, hn;
+            std::vector<double> bf, bt, bn, dev;
+            std::vector<int32_t> a1, a2, dv32;
+            int32_t m1 = 0, m2 = 0;
+            hf.n = F.n;
+            if (int rc = fetch(c, F.rp, (size_t)F.n + 1, hf.rp)) return rc;
+            if (int rc = fetch(c, F.ci, (size_t)F.nnz, hf.ci)) return rc;
+            if (int rc = fetch(c, F.S.a, (size_t)F.nnz, hf.a)) return rc;
+            if (int rc = fetch(c, F.bv, 4 * (size_t)F.nnz, bf)) return rc;
+            host_pairwise(hf, nullptr, a1, m1);
+            host_galerkin(hf, a1, m1, ht);
+            host_block_galerkin(hf, bf, a1, m1, bt);
+            host_pairwise(ht, nullptr, a2, m2);
+            host_galerkin(ht, a2, m2, hn);
+            host_block_galerkin(ht, bt, a2, m2, bn);
+            std::string which;
+            auto same = [&](const auto* p, size_t cnt, const auto& h) {
+                using E = std::decay_t<decltype(h[0])>;
+                std::vector<E> g;
+                return h.size() == cnt && fetch(c, p, cnt, g) == FDAPDE_OK && (cnt == 0 || std::memcmp(g.data(), h.data(), sizeof(E) * cnt) == 0);
+            };
+            if (m1 != n1 || !same(agg1.p, (size_t)F.n, a1)) which += " pass-1 aggregates";
+            else if (m2 != n2 || !same(agg2.p, (size_t)n1, a2)) which += " pass-2 aggregates";
+            else {
+                if (!same(T.rp, (size_t)n1 + 1, ht.rp) || !same(T.ci, (size_t)T.nnz, ht.ci)) which += " pair-graph pattern";
+                else if (!same(T.a, (size_t)T.nnz, ht.a)) which += " pair-graph strength values";
+                else if (!same(bvT.p, 4 * (size_t)T.nnz, bt)) which += " pair-graph block values";
+                if (!same(N->rp, (size_t)n2 + 1, hn.rp) || !same(N->ci, (size_t)N->nnz, hn.ci)) which += " coarse pattern";
+                else if (!same(N->S.a, (size_t)N->nnz, hn.a)) which += " coarse strength values";
+                else if (!same(N->bv, 4 * (size_t)N->nnz, bn)) which += " coarse block values";
+            }
+            if (!which.empty()) {
+                c->err = "amg_setup_check: block level " + std::to_string(H->lv.size() - 1) + ": the device-built hierarchy differs from the host-built one:" + which;
+                return FDAPDE_EHIP;
+            }
+        }
+        if ((double)n2 > kBamgStall * (double)F.n && 2 * (int64_t)n2 > coarse_rows) {   // coarsening stalled: a level the dense inverse takes ends the hierarchy
+            if (2 * F.n > dense_limit)
+                return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_BLOCK_AMG: coarsening stalled above the dense limit (a level kept more than 0.8 of its rows): the strength block has too few strong couplings for pairwise aggregation");
+            F.agg.release(), F.mptr.release(), F.midx.release();
+            break;
+        }
+        H->lv.push_back(std::move(N));
+    }
+    // the smoother of every level that has a next one; a singular diagonal block below level 0 ends the hierarchy one level above
+    for (size_t l = 0; l + 1 < H->lv.size(); ++l) {
+        bool bad = false;
+        if (int rc = level_dinv(c, *H->lv[l], &bad)) return rc;
+        if (!bad) continue;
+        if (l == 0) return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_BLOCK_AMG: a DOF's diagonal block is singular (|det| <= 1e-14 max|entry|^2): no block-Jacobi smoother");
+        if (2 * H->lv[l - 1]->n > dense_limit)
+            return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_BLOCK_AMG: a coarse level has a singular diagonal block and the level above it is too large for the dense inverse");
+        H->lv.resize(l);
+        BamgLevel& E = *H->lv.back();
+        E.agg.release(), E.mptr.release(), E.midx.release(), E.dinv.release();
+        break;
+    }
+    for (auto& L : H->lv)
+        if (int rc = level_vectors(c, *L)) return rc;
+    BamgLevel& C = *H->lv.back();
+    if (2 * C.n > kDenseMaxRows) return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_BLOCK_AMG: the coarsest level is too large for the dense inverse");
+    HIPCHK(c, H->rp2.alloc((size_t)(2 * C.n + 1)));
+    HIPCHK(c, H->ci2.alloc((size_t)std::max<int64_t>(4 * C.nnz, 1)));
+    HIPCHK(c, H->val2.alloc((size_t)std::max<int64_t>(4 * C.nnz, 1)));
+    hipLaunchKernelGGL(k_block_expand, dim3(gn(C.n + 1)), dim3(256), 0, st, C.n, C.rp, C.ci, C.bv, H->rp2.p, H->ci2.p, H->val2.p);
+    HIPCHK(c, hipGetLastError());
+    if (int rc = dense_build_csr(c, 2 * C.n, H->rp2.p, H->ci2.p, H->val2.p, nullptr, 0, H->D)) return rc;
+    if (!H->D.ready) return fail(c, FDAPDE_ENOCONV, "FDAPDE_SOLVER_BLOCK_AMG: the coarsest level is singular to working precision");
+    H->setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (std::getenv("FDAPDE_DEBUG_SETUP")) {
+        std::string rows;
+        for (size_t l = 0; l < H->lv.size(); ++l) rows += (l ? " / " : "") + std::to_string(2 * H->lv[l]->n);
+        std::fprintf(stderr, "block amg: %zu levels, rows %s, set-up %.2f ms\n", H->lv.size(), rows.c_str(), H->setup_ms);
+    }
+    *slot = H.release();
+    return FDAPDE_OK;
+}
+
+// one column: A x = b (both interleaved, internal order, on the device; x is written), raw = the matrix the hierarchy was built from
+int block_amg_run(fdapde_ctx* c, BlockAmg* hp, const double* raw, const double* b_dev, double* x_dev, double rtol, int maxit, int* iters, double* relres,
+                  bool* converged_out, bool* broke_out) {
+    BlockAmg& H = *hp;
+    hipStream_t st = c->stream;
+    BamgLevel& L0 = *H.lv[0];
+    const int64_t n = L0.n, n2 = 2 * n;
+    const int np = (int)std::min<int64_t>(1024, std::max<int64_t>(1, (n2 + 4095) / 4096));
+    const int mk = std::max(1, std::min(std::min(c->gmres_m, kBamgMaxRestart), std::max(maxit, 1)));
+    HIPCHK(c, H.vec.alloc(2 * (size_t)n2));
+    HIPCHK(c, H.basis.alloc((size_t)(2 * mk + 1) * (size_t)n2));
+    HIPCHK(c, H.part.alloc((size_t)(mk + 2) * (size_t)np + 3 * (size_t)np));
+    HIPCHK(c, H.dots.alloc((size_t)(mk + 4)));
+    double *x = x_dev, *r = H.vec.p, *t = r + n2;
+    double h[3] = {0, 0, 0};
+    auto spmv = [&](const double* in, double* out) {
+        hipLaunchKernelGGL(k_block_spmv<kBlockTeam>, dim3(g1(n, 256 / kBlockTeam)), dim3(256), 0, st, n, L0.rp, L0.ci, raw, in, out, (const int32_t*)nullptr);
+    };
+    auto dots = [&](const double* a0) -> int {
+        fixed_dots(st, n2, np, a0, a0, nullptr, nullptr, nullptr, nullptr, H.part.p, H.dots.p);
+        HIPCHK(c, hipMemcpyAsync(h, H.dots.p, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        return FDAPDE_OK;
+    };
+    HIPCHK(c, hipMemsetAsync(x, 0, sizeof(double) * (size_t)n2, st));
+    HIPCHK(c, hipMemcpyAsync(r, b_dev, sizeof(double) * (size_t)n2, hipMemcpyDeviceToDevice, st));
+    if (int rc = dots(r)) return rc;
+    const double bb = h[0];
+    double rr = bb;
+    int it = 0;
+    bool converged = !(bb > 0.0) && std::isfinite(bb), broke = !std::isfinite(bb);
+    const bool one_level = H.lv.size() == 1;
+    auto precond = [&](const double* v, double* z, double* w, bool&) -> int {
+        if (one_level) {
+            if (int rc = dense_apply(c, H.D, 1, v, z)) return rc;
+        } else if (int rc = bamg_cycle(c, H, 0, v, z))
+            return rc;
+        spmv(z, w);
+        return FDAPDE_OK;
+    };
+    auto residual = [&](double& rr_out) -> int {   // the TRUE residual of the iterate
+        spmv(x, t);
+        hipLaunchKernelGGL(k_bamg_residual, dim3(gn(n2)), dim3(256), 0, st, n2, b_dev, t, r);
+        if (int rc = dots(r)) return rc;
+        rr_out = h[0];
+        return FDAPDE_OK;
+    };
+    FgmresSpace fs{n2, mk, H.basis.p, H.basis.p + (size_t)(mk + 1) * (size_t)n2, H.part.p, H.dots.p, np};
+    if (!converged && !broke)
+        if (int rc = fgmres_outer(c, fs, x, r, nullptr, rtol, maxit, bb, precond, residual, rr, it, converged, broke)) return rc;
+    if (bb > 0.0 && std::isfinite(bb)) {   // what is handed out is judged by its own residual, whichever way the loop ended
+        if (int rc = residual(rr)) return rc;
+        converged = std::isfinite(rr) && rr <= rtol * rtol * bb;
+    }
+    HIPCHK(c, hipGetLastError());
+    *iters = it, *relres = bb > 0.0 ? std::sqrt(rr / bb) : 0.0, *converged_out = converged, *broke_out = broke;
+    return FDAPDE_OK;
+}
+
+}   // namespace fdapde_engine

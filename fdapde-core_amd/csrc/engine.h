@@ -197,6 +197,14 @@ int e_block_solve(fdapde_ctx* c, const fdapde_options* opt, const double* b, int
 int e_block_spmv(fdapde_ctx* c, const double* x, double* y);
 int e_block_bench_spmv(fdapde_ctx* c, int32_t reps, double* avg_ms, double* algorithmic_bytes);
 int e_gram_pointwise(fdapde_ctx* c, int64_t n_locs, const int32_t* cell_ids, const double* values, const double* weights, double* out_values);
+// eng_block_amg.hip: FDAPDE_SOLVER_BLOCK_AMG, the point-block multilevel preconditioner of the block handle -- the hierarchy of the unscaled block CSR
+// `raw` on the context's pattern (strength_block: which of a11 a12 a21 a22 the aggregation reads), and one column A x = b against it (b, x: interleaved,
+// internal order, device)
+struct BlockAmg;
+void block_amg_free(BlockAmg* h);
+int block_amg_build(fdapde_ctx* c, BlockAmg** slot, const double* raw, int strength_block);
+int block_amg_run(fdapde_ctx* c, BlockAmg* h, const double* raw, const double* b_dev, double* x_dev, double rtol, int maxit, int* iters, double* relres,
+                  bool* converged, bool* broke);
 
 // code objects of the units loaded up front (fdapde_ctx_create)
 void preload_assembly();

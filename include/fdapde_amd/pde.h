@@ -567,6 +567,7 @@ template <typename D, typename F, int R> class PDE<D, DifferentialExpr, F, FEM_H
     // "factor once, solve many" on a 2 x 2 block matrix whose blocks lie on this PDE's pattern: fdapde::SparseLU on a SparseBlockMatrix<double,2,2>
     // (linear_algebra/sparse_block_matrix.h:29-128; include/fdapde_amd/linear_algebra.h) -- the smoothing system.  Right-hand sides and solutions are
     // stacked as the reference stacks them: rows 0 .. n-1 the first block row, n .. 2n-1 the second.  Context lifetime as SparseSolver.
+    // solver_options().method names the stage: FDAPDE_SOLVER_GMRES, FDAPDE_SOLVER_DENSE, FDAPDE_SOLVER_BLOCK_AMG (the point-block multilevel preconditioner).
     class BlockSolver {
        public:
         // m.block(i, j): SpMatrix<double> of n_dofs x n_dofs; no stored entry = a zero block, else entries on the pattern (a sub-pattern is filled up with zeros)

@@ -104,7 +104,21 @@ enum { FDAPDE_SOLVER_AUTO = 0, FDAPDE_SOLVER_CG = 1, FDAPDE_SOLVER_BICGSTAB = 2,
                                 info.iters counts outer iterations, info.relres is the true relative residual of what is handed out, info.persistent = 0.
                                 rtol 1e-10 and maxit 200 by default; non-convergence is FDAPDE_ENOCONV (success = false), as is a singular coarsest level
                                 (pure Neumann data); coarsening that stalls above the dense limit, a rank of a multi-GPU job and a multi-device context are
-                                FDAPDE_EUNSUPPORTED. */ };
+                                FDAPDE_EUNSUPPORTED. */,
+       FDAPDE_SOLVER_BLOCK_AMG = 9 /* fdapde_block_solve only (fdapde_solve, fdapde_solve_parabolic and fdapde_lin_solve answer FDAPDE_EUNSUPPORTED): flexible
+                                GMRES(gmres_m) on the UNSCALED 2 x 2 block system, right-preconditioned by the multilevel cycle of FDAPDE_SOLVER_AMG on
+                                POINT-BLOCK unknowns -- the two unknowns of a DOF stay together on every level.  Aggregates of at most four DOFs from double
+                                pairwise matching on a scalar strength matrix on the pattern (the (2,1) block as given; (1,2), (2,2), (1,1) where it was
+                                NULL), block Galerkin matrices in a fixed summation order (the same bits every run), smoother 0.7 D^-1 with D the 2 x 2
+                                diagonal blocks, two GCR steps per coarse level always (the system is indefinite), the last level -- at most
+                                `amg_coarse_rows` rows counted as 2 n_l, or where coarsening stalls at no more than `dense_rows` -- inverted once.  The
+                                hierarchy is built by the first such solve after fdapde_block_compute and kept until the next one.  Stop rule:
+                                |b - A x| <= rtol |b| on the true residual -- NOT the D^-1-scaled rule of the handle's FDAPDE_SOLVER_GMRES stage.  rtol 1e-10
+                                and maxit 200 by default; columns one after another, info.iters summed over them, info.relres the worst column's true
+                                relative residual, info.persistent = 0; FDAPDE_ENOCONV leaves the last iterate of every column, and is also the answer to
+                                a singular coarsest level; a singular diagonal block of a DOF (the 1e-14 rule of fdapde_block_compute) and coarsening
+                                that stalls above the dense limit are FDAPDE_EUNSUPPORTED.  Taken by name only: the open method never chooses it.
+                                Order-2 spaces in 3-D are allowed, but pairwise matching serves them poorly (no iteration count is claimed). */ };
 /* ROWS: row-owner sweep (default; no atomics, bitwise reproducible).  The others are element-wise scatter forms kept as measured
  * alternatives and cross-checks: ATOMIC / COLOURED = lane per (cell, row) with a slot search, fp64 atomics / one launch per colour;
  * PARTITIONED = one workgroup per cell partition, colours walked inside the workgroup, atomics only on rows shared between
@@ -298,7 +312,9 @@ int fdapde_lin_solve(fdapde_ctx *ctx, const fdapde_options *opt, const double *b
  * block is singular.  FDAPDE_SOLVER_DENSE: 2 n <= dense_rows (8192): the dense inverse of the 2 n-row matrix, built in the call, all columns in one product;
  * above the limit FDAPDE_EUNSUPPORTED, a singular matrix FDAPDE_ENOCONV.  FDAPDE_SOLVER_AUTO: GMRES, and the rent-or-buy rule of fdapde_lin_solve with 2 n
  * as the row count (more than `dense_after` columns asked for and half of dense_build_estimate_ms spent on Krylov columns: the inverse from then on; at
- * once where the Krylov stage is unavailable).  Every other method: FDAPDE_EUNSUPPORTED.  info as fdapde_lin_solve: iters summed over the columns, relres
+ * once where the Krylov stage is unavailable).  FDAPDE_SOLVER_BLOCK_AMG (by name only): flexible GMRES on the unscaled system around a point-block
+ * multilevel cycle, stop rule |b - A x| <= rtol |b| (rtol <= 0: 1e-10; maxit <= 0: 200); its hierarchy is built by the first such solve after
+ * fdapde_block_compute and dropped with the matrix; see the enumerator.  Every other method: FDAPDE_EUNSUPPORTED.  info as fdapde_lin_solve: iters summed over the columns, relres
  * the worst column's, method_used the stage; FDAPDE_ENOCONV leaves the last iterate of every column in x.
  * fdapde_block_spmv: y = A x with the unscaled blocks, stacked host vectors of 2 n_dofs (parity tests, the byte figure).
  * fdapde_block_bench_spmv: times `reps` launches of the Krylov stage's operator kernel (k_block_spmv on D^-1 A) with HIP events; algorithmic bytes per
@@ -501,7 +517,8 @@ int fdapde_partition_peers(fdapde_ctx *ctx, int32_t rank, int32_t *n_peers, int3
  *                 additive preconditioner, the round's first form), "pmg_smooth" (0: flexible GMRES around the additive preconditioner instead of the V(1,1)
  *                 cycle), "pmg_blocked" (0: the fine operator through the CSR kernel instead of the blocked-ELL SpMV), "pmg_setup_check" (1: the transfer tables
  *                 are also built by host loops and compared; an error if they differ)
- *   multilevel    "amg_coarse_rows" (FDAPDE_SOLVER_AMG coarsens until a level has at most that many rows, 1 .. 8 192; 1 024), "amg_setup_check" (1: the aggregates,
+ *   multilevel    "amg_coarse_rows" (FDAPDE_SOLVER_AMG and FDAPDE_SOLVER_BLOCK_AMG coarsen until a level has at most that many rows -- 2 n_l for the block
+ *                 form --, 1 .. 8 192; 1 024), "amg_setup_check" (1: the aggregates,
  *                 coarse patterns and coarse values are also built by host loops and compared bit for bit; an error if they differ) */
 int fdapde_tune(fdapde_ctx *ctx, const char *key, int32_t value);
 /* the context's HIP stream (hipStream_t) so that callers can bracket work with their own events */

@@ -1,0 +1,253 @@
+"""FDAPDE_SOLVER_BLOCK_AMG (csrc/eng_block_amg.hip, the k_bamg_* kernels of kernels_block.h): flexible GMRES around the point-block multilevel cycle on the
+2 x 2 block handle, against scipy's SuperLU on sp.bmat of the four blocks and against the numpy restatement of the scheme (tests/block_amg_ref.py, which
+tests/test_block_amg_cpu.py holds to HALF of every iteration budget handed over here).  Every context sets `amg_coarse_rows` = 256 -- small systems get
+several levels -- and `amg_setup_check` = 1: the device-built aggregates and coarse block values are compared bit for bit with host loops."""
+import os
+
+import numpy as np
+import pytest
+
+import block_amg_ref as ar
+import block_ref as br
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def env():
+    from fdapde_loader import load_package
+
+    load_package()
+    from fdapde_core_amd import capi, meshgen, workloads
+
+    assert capi.load().fdapde_device_count() >= 1, "no HIP device visible: the GPU tests must not fall back to anything"
+    return capi, meshgen, workloads
+
+
+def _context(env, mesh, order, coarse_rows=ar.COARSE_ROWS):
+    capi, meshgen, workloads = env
+    if isinstance(mesh, str):
+        nodes, cells, bnd = workloads.load_fixture_mesh(os.path.join(ROOT, "tests", "golden", "mesh", mesh))
+    else:
+        nodes, cells, bnd = getattr(meshgen, mesh[0])(mesh[1])
+    c = capi.Context(0)
+    c.mesh_upload(nodes, cells, bnd)
+    nd = c.dofs_build(order)
+    c.tune("amg_coarse_rows", coarse_rows)
+    c.tune("amg_setup_check", 1)
+    return c, nd, nodes
+
+
+def _blocks(env, c, nd, nodes, lam, advection=False):
+    """the smoothing system's blocks from the device's own matrices -> (blocks, rowptr, colidx, observed nodes)"""
+    capi = env[0]
+    op = -capi.laplacian()
+    if advection:
+        op = op + capi.advection([4.0, -2.0] if nodes.shape[1] == 2 else [4.0, -2.0, 1.0])
+    c.set_operator(op)
+    c.set_forcing(np.ones(c.quadrature_nodes().shape[0]))
+    c.init()
+    rp, ci = c.pattern_get()
+    obs = br.observed_nodes(nodes.shape[0])
+    return br.smoothing_blocks(rp, ci, c.matrix_values(capi.MAT_STIFF), c.matrix_values(capi.MAT_MASS), obs, lam, nd), rp, ci, obs
+
+
+_systems = {}
+
+
+def _smoothing(env, case):
+    """-> (context with the block handle computed, A, b, n_dofs, LU solution, blocks, rowptr, colidx); one context and one factorisation per case"""
+    import scipy.sparse.linalg as spl
+
+    if case not in _systems:
+        mesh, order, lam, advection = case
+        c, nd, nodes = _context(env, mesh, order)
+        blocks, rp, ci, obs = _blocks(env, c, nd, nodes, lam, advection)
+        A = br.bmat(rp, ci, blocks, nd)
+        b = br.smoothing_rhs(obs, lam, nd)
+        c.block_compute(*blocks, symmetric=True)
+        _systems[case] = (c, A, b, nd, spl.splu(A.tocsc()).solve(b), blocks, rp, ci)
+    return _systems[case]
+
+
+def _rel(x, ref):
+    return np.linalg.norm(x - ref) / np.linalg.norm(ref)
+
+
+def _against_lu(env, case, budget):
+    capi = env[0]
+    c, A, b, nd, x_lu, blocks, rp, ci = _smoothing(env, case)
+    x_ref, it_ref, ok_ref, rows_ref = ar.solve(rp, ci, blocks, nd, b)
+    assert ok_ref
+    e_ref = _rel(x_ref, x_lu)
+    x, info = c.block_solve(b, method=capi.SOLVER_BLOCK_AMG, rtol=ar.RTOL, maxit=budget, raise_on_noconv=False)
+    err, res = _rel(x, x_lu), np.linalg.norm(b - A @ x) / np.linalg.norm(b)
+    print(f"{ar.case_id(case)}: 2n = {2 * nd}, iterations {info.iters} (restatement {it_ref}, rows {rows_ref}, budget {budget}), relres {info.relres:.2e}, "
+          f"recomputed {res:.2e}, error against LU {err:.2e} (restatement {e_ref:.2e})")
+    assert info.converged == 1 and info.method_used == capi.SOLVER_BLOCK_AMG == 9 and info.persistent == 0
+    assert info.iters <= budget
+    assert info.relres <= ar.RTOL
+    assert res <= 10 * ar.RTOL
+    assert err <= 10 * e_ref
+
+
+@pytest.mark.parametrize("case", ar.LU_CASES, ids=[ar.case_id(c) for c in ar.LU_CASES])
+def test_order_1_against_lu(env, case):
+    """budget 80 (the restatement stays <= 40): converged, relres <= rtol, the unscaled residual recomputed by numpy <= 10 rtol, and the error against LU
+    within 10 times that of the restatement (two correct runs stop at different last iterates: the rule of the GMRES stage's test)"""
+    _against_lu(env, case, ar.BUDGET_P1)
+
+
+@pytest.mark.parametrize("case", ar.P2_2D_CASES, ids=[ar.case_id(c) for c in ar.P2_2D_CASES])
+def test_order_2_in_2d_against_lu(env, case):
+    """budget 120 (the restatement stays <= 60)"""
+    _against_lu(env, case, ar.BUDGET_P2_2D)
+
+
+def test_order_2_in_3d_converges(env):
+    """unit_sphere P2, 2 n = 8 386 -- the matrix FDAPDE_SOLVER_DENSE refuses by name --, lambda 1e-2, budget 200 (the restatement stays <= 100): it converges;
+    no count is claimed for order 2 in 3-D"""
+    capi = env[0]
+    c, A, b, nd, x_lu, *_ = _smoothing(env, ar.P2_3D_CASES[0])
+    assert 2 * nd == 8386
+    x, info = c.block_solve(b, method=capi.SOLVER_BLOCK_AMG, rtol=ar.RTOL, maxit=ar.BUDGET_P2_3D, raise_on_noconv=False)
+    print(f"unit_sphere P2: iterations {info.iters}, relres {info.relres:.2e}, error against LU {_rel(x, x_lu):.2e}")
+    assert info.converged == 1 and info.method_used == capi.SOLVER_BLOCK_AMG and info.relres <= ar.RTOL
+
+
+@pytest.mark.parametrize("meshes,lam", ar.LADDERS, ids=[f"{m[0][0]}-{lam:g}" for m, lam in ar.LADDERS])
+def test_ladder(env, meshes, lam):
+    """outer iterations over a ladder of meshes: every count <= 40, the largest mesh's <= 1.5 x the smallest's + 2 (the ladder rule of FDAPDE_SOLVER_AMG's test)"""
+    capi = env[0]
+    counts = []
+    for mesh in meshes:
+        c, A, b, nd, x_lu, *_ = _smoothing(env, (mesh, 1, lam, False))
+        x, info = c.block_solve(b, method=capi.SOLVER_BLOCK_AMG, rtol=ar.RTOL, maxit=ar.BUDGET_P1, raise_on_noconv=False)
+        assert info.converged == 1 and _rel(x, x_lu) <= 1e-6
+        counts.append(info.iters)
+    print(f"{meshes[0][0]} lambda {lam:g}: iterations {counts}")
+    assert max(counts) <= ar.LADDER_CAP
+    assert counts[-1] <= 1.5 * counts[0] + 2
+
+
+def test_small_system_is_one_dense_level(env):
+    capi = env[0]
+    c, nd, nodes = _context(env, "unit_square_16", 1, coarse_rows=1024)
+    blocks, rp, ci, obs = _blocks(env, c, nd, nodes, 1e-4)
+    c.block_compute(*blocks, symmetric=True)
+    b = br.smoothing_rhs(obs, 1e-4, nd)
+    import scipy.sparse.linalg as spl
+
+    x_lu = spl.splu(br.bmat(rp, ci, blocks, nd).tocsc()).solve(b)
+    x, info = c.block_solve(b, method=capi.SOLVER_BLOCK_AMG)
+    print(f"one level: iterations {info.iters}, error against LU {_rel(x, x_lu):.2e}")
+    assert info.converged == 1 and info.method_used == capi.SOLVER_BLOCK_AMG and info.iters <= 2
+    assert _rel(x, x_lu) <= 1e-7
+    c.close()
+
+
+def test_columns_together_one_by_one_and_in_place(env):
+    capi = env[0]
+    c, A, b, nd, *_ = _smoothing(env, (("unit_square", 32), 1, 1e-4, False))
+    B = np.random.default_rng(5).standard_normal((2 * nd, 8))
+    X, info = c.block_solve(B, method=capi.SOLVER_BLOCK_AMG)
+    assert info.converged == 1
+    total = 0
+    for j in range(8):
+        xj, ij = c.block_solve(B[:, j], method=capi.SOLVER_BLOCK_AMG)
+        assert np.array_equal(X[:, j], xj)
+        total += ij.iters
+    assert info.iters == total
+    inplace = np.asfortranarray(B.copy())
+    ii = c.block_solve_inplace(inplace, method=capi.SOLVER_BLOCK_AMG)
+    assert np.array_equal(inplace, X) and ii.iters == total
+
+
+def test_two_fresh_contexts_give_the_same_bits(env):
+    capi = env[0]
+    out = []
+    for _ in range(2):
+        c, nd, nodes = _context(env, ("unit_square", 32), 1)
+        blocks, rp, ci, obs = _blocks(env, c, nd, nodes, 1e-4)
+        c.block_compute(*blocks, symmetric=True)
+        x, info = c.block_solve(br.smoothing_rhs(obs, 1e-4, nd), method=capi.SOLVER_BLOCK_AMG)
+        out.append((x, info.iters, info.relres))
+        c.close()
+    assert np.array_equal(out[0][0], out[1][0]) and out[0][1:] == out[1][1:]
+
+
+def test_exhausted_budget_leaves_the_last_iterate(env):
+    capi = env[0]
+    c, A, b, nd, x_lu, *_ = _smoothing(env, ("unit_square_16", 1, 1e-2, False))
+    with pytest.raises(capi.FdapdeError) as e:
+        c.block_solve(b, method=capi.SOLVER_BLOCK_AMG, maxit=3)
+    assert e.value.status == capi.ENOCONV
+    x, info = c.block_solve(b, method=capi.SOLVER_BLOCK_AMG, maxit=3, raise_on_noconv=False)
+    res = np.linalg.norm(b - A @ x) / np.linalg.norm(b)
+    assert info.converged == 0 and info.iters == 3 and info.method_used == capi.SOLVER_BLOCK_AMG
+    assert np.all(np.isfinite(x)) and 1e-10 < res < 1.0 and abs(res - info.relres) <= 1e-6 * res
+
+
+def test_lifetime_of_the_hierarchy(env):
+    """a second block_compute rebuilds it; a clone does not carry it; the other solves of the context refuse the id and keep their bits"""
+    import scipy.sparse.linalg as spl
+
+    capi = env[0]
+    c, nd, nodes = _context(env, "unit_square_16", 1)
+    c.set_operator(-capi.laplacian() + capi.reaction(1.0))
+    c.set_forcing(np.ones(c.quadrature_nodes().shape[0]))
+    c.init()
+    rhs = np.random.default_rng(2).standard_normal((nd, 3))
+
+    def others():
+        c.lin_compute(capi.MAT_STIFF)
+        X, _ = c.lin_solve(rhs, rtol=1e-12)
+        c.solve(rtol=1e-12)
+        return X, c.solution()
+
+    X0, u0 = others()
+    rp, ci = c.pattern_get()
+    obs = br.observed_nodes(nodes.shape[0])
+    r1, r0 = c.matrix_values(capi.MAT_STIFF), c.matrix_values(capi.MAT_MASS)
+    for lam in (1e-4, 1e-2):   # the second matrix meets the first one's hierarchy: it must be rebuilt
+        blocks = br.smoothing_blocks(rp, ci, r1, r0, obs, lam, nd)
+        b = br.smoothing_rhs(obs, lam, nd)
+        c.block_compute(*blocks, symmetric=True)
+        x, info = c.block_solve(b, method=capi.SOLVER_BLOCK_AMG)
+        x_lu = spl.splu(br.bmat(rp, ci, blocks, nd).tocsc()).solve(b)
+        assert info.converged == 1 and info.method_used == capi.SOLVER_BLOCK_AMG and _rel(x, x_lu) <= 1e-6
+    X1, u1 = others()
+    assert np.array_equal(X0, X1) and np.array_equal(u0, u1)
+    for call in (lambda: c.solve(method=capi.SOLVER_BLOCK_AMG), lambda: c.lin_solve(rhs, method=capi.SOLVER_BLOCK_AMG),
+                 lambda: c.solve_parabolic(np.linspace(0.0, 0.1, 3), np.zeros(nd), method=capi.SOLVER_BLOCK_AMG)):
+        with pytest.raises(capi.FdapdeError) as e:
+            call()
+        assert e.value.status == capi.EUNSUPPORTED
+    with pytest.raises(capi.FdapdeError) as e:   # (the id of the scalar solver stays refused on the block handle)
+        c.block_solve(b, method=capi.SOLVER_AMG)
+    assert e.value.status == capi.EUNSUPPORTED
+    k = c.clone()
+    with pytest.raises(capi.FdapdeError) as e:
+        k.block_solve(b, method=capi.SOLVER_BLOCK_AMG)
+    assert e.value.status == capi.ENOTINIT
+    k.close()
+    x2, _ = c.block_solve(b, method=capi.SOLVER_BLOCK_AMG)   # ... and the original still answers, with the same bits
+    assert np.array_equal(x, x2)
+    c.close()
+
+
+def test_singular_diagonal_block_on_level_0(env):
+    """the matrix of the GMRES stage's refusal test (a11 = a12 = 0 on the diagonal of one DOF): no block-Jacobi smoother"""
+    capi = env[0]
+    c, nd, nodes = _context(env, "unit_square_16", 1)
+    blocks, rp, ci, obs = _blocks(env, c, nd, nodes, 1e-4)
+    blocks = [v.copy() for v in blocks]
+    d = rp[7] + np.searchsorted(ci[rp[7]:rp[8]], 7)
+    blocks[0][d] = 0.0
+    blocks[1][d] = 0.0
+    c.block_compute(*blocks)
+    with pytest.raises(capi.FdapdeError) as e:
+        c.block_solve(br.smoothing_rhs(obs, 1e-4, nd), method=capi.SOLVER_BLOCK_AMG)
+    assert e.value.status == capi.EUNSUPPORTED
+    c.close()
