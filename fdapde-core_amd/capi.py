@@ -51,7 +51,9 @@ SYMBOLS = [
     "fdapde_ctx_create_multi", "fdapde_ctx_devices", "fdapde_partition_build", "fdapde_partition_sizes", "fdapde_partition_get", "fdapde_partition_whole",
     "fdapde_partition_peers",
     "fdapde_block_compute", "fdapde_block_solve", "fdapde_block_spmv", "fdapde_block_bench_spmv", "fdapde_gram_pointwise",
+    "fdapde_amg_hierarchy",
 ]
+AMG_OF_SOLVE, AMG_OF_HANDLE, AMG_OF_BLOCK = 0, 1, 2   # `which` of fdapde_amg_hierarchy
 PARTITION_ROWDIST, PARTITION_ELEMENTS = 0, 1
 
 _lib = None
@@ -618,6 +620,16 @@ class Context:
         f, g = C.c_int32(), C.c_int32()
         self._check(self.lib.fdapde_solver_trace(self._ctx, C.byref(f), C.byref(g)))
         return dict(small_front=f.value, graph_replays=g.value)
+
+    def amg_hierarchy(self, which=AMG_OF_SOLVE):
+        """fdapde_amg_hierarchy: the live hierarchy of fdapde_solve (0), the factor-once handle (1) or the block handle (2, rows counted as 2 n_l) ->
+        dict(rows, nnz: per level, the last level the inverted one; absorbed; setup_ms).  FdapdeError(ENOTINIT) where none is live"""
+        nl, ab, ms = C.c_int32(), C.c_int32(), C.c_double()
+        self._check(self.lib.fdapde_amg_hierarchy(self._ctx, int(which), 0, C.byref(nl), None, None, None, None))
+        rows, nnz = np.zeros(nl.value, dtype=np.int64), np.zeros(nl.value, dtype=np.int64)
+        self._check(self.lib.fdapde_amg_hierarchy(self._ctx, int(which), nl.value, C.byref(nl), rows.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                  nnz.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(ab), C.byref(ms)))
+        return dict(rows=[int(r) for r in rows], nnz=[int(z) for z in nnz], absorbed=ab.value, setup_ms=ms.value)
 
     # ---- multi-GPU
     @staticmethod

@@ -1,5 +1,6 @@
 // amg_setup.h -- the set-up passes of the aggregation hierarchies (eng_amg.hip), shared by FDAPDE_SOLVER_AMG and the block form of eng_block_amg.hip:
-// pairwise handshake matching, the Galerkin product of piecewise-constant P, the members of every aggregate -- on the device, and as the host loops
+// pairwise handshake matching (absorb: the rows it leaves single join the pair of their most strongly coupled paired neighbour -- aggregates of any size),
+// the Galerkin product of piecewise-constant P, the members of every aggregate -- on the device, and as the host loops
 // the knob amg_setup_check compares them with.
 #ifndef FDAPDE_AMG_SETUP_H
 #define FDAPDE_AMG_SETUP_H
@@ -39,9 +40,10 @@ struct AmgGalerkinMap {
     uint64_t nc = 0;
 };
 
-void host_pairwise(const HostCsr& A, const uint8_t* excl, std::vector<int32_t>& agg, int32_t& nc);
+void host_pairwise(const HostCsr& A, const uint8_t* excl, int absorb, std::vector<int32_t>& agg, int32_t& nc);
 void host_galerkin(const HostCsr& A, const std::vector<int32_t>& agg, int32_t nc, HostCsr& C);
-int dev_pairwise(fdapde_ctx* c, int64_t n, int64_t nnz, const int32_t* rp, const int32_t* ci, const double* a, const uint8_t* excl, DBuf<int32_t>& agg, int32_t* nc);
+int dev_pairwise(fdapde_ctx* c, int64_t n, int64_t nnz, const int32_t* rp, const int32_t* ci, const double* a, const uint8_t* excl, int absorb, DBuf<int32_t>& agg,
+                 int32_t* nc);
 int dev_galerkin(fdapde_ctx* c, int64_t n, int64_t nnz, const int32_t* rp, const int32_t* ci, const double* a, const int32_t* agg, int32_t nc, AmgLevel& out,
                  AmgGalerkinMap* keep = nullptr);
 int dev_members(fdapde_ctx* c, int64_t n, const int32_t* agg, int32_t nc, DBuf<int32_t>& mptr, DBuf<int32_t>& midx);

@@ -437,6 +437,15 @@ int fdapde_partition_peers(fdapde_ctx* c, int32_t rank, int32_t* n_peers, int32_
     return fdapde_engine::e_partition_peers(c, rank, n_peers, peer_rank, peer_off, peer_node, owned, n_shared);
 }
 
+int fdapde_amg_hierarchy(fdapde_ctx* c, int32_t which, int32_t cap, int32_t* n_levels, int64_t* rows, int64_t* nnz, int32_t* absorbed, double* setup_ms) {
+    if (!c || which < 0 || which > 2 || cap < 0 || (cap > 0 && !rows && !nnz)) return FDAPDE_EINVAL;
+    const int rc = which == 0   ? fdapde_engine::amg_describe(c->amg, cap, n_levels, rows, nnz, absorbed, setup_ms)
+                   : which == 1 ? fdapde_engine::amg_describe(c->amg_lin, cap, n_levels, rows, nnz, absorbed, setup_ms)
+                                : fdapde_engine::block_amg_describe_ctx(c, cap, n_levels, rows, nnz, absorbed, setup_ms);
+    if (rc == FDAPDE_ENOTINIT) return fdapde_engine::fail(c, rc, "fdapde_amg_hierarchy: no hierarchy of that kind is live (it is built by the first solve that names the multilevel method)");
+    return rc;
+}
+
 int fdapde_info_get(const fdapde_ctx* c, fdapde_info* info) {
     if (!c || !info) return FDAPDE_EINVAL;
     *info = c->info;
@@ -489,6 +498,10 @@ int fdapde_tune(fdapde_ctx* c, const char* key, int32_t value) {
     else if (k == "pmg_setup_check" && (value == 0 || value == 1)) c->pmg_setup_check = value;
     else if (k == "amg_coarse_rows" && value >= 1 && value <= 8192) c->amg_coarse_rows = value;
     else if (k == "amg_setup_check" && (value == 0 || value == 1)) c->amg_setup_check = value;
+    else if (k == "amg_absorb" && value >= 0 && value <= 2) {   // the hierarchies are built again by the next solve that needs one
+        if (value != c->amg_absorb) fdapde_engine::amg_release(c), fdapde_engine::block_amg_forget(c);
+        c->amg_absorb = value;
+    }
     else if (k == "pmg_restart" && value >= 2 && value <= 50) c->pmg_restart = (int)value;
     else if (k == "pmg_outer" && (value == 0 || value == 1)) c->pmg_outer = value;
     else if (k == "pmg_auto_rows" && value >= 0) c->pmg_auto_rows = value;

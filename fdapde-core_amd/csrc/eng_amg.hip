@@ -10,7 +10,10 @@
 //             their correction is 0 on every level) or the handle's matrix, in the internal (locality) DOF order.  A level's aggregates come from TWO
 //             pairwise passes of handshake matching on the strength graph (-a_ij >= theta max_k -a_ik on the symmetric part; a row without negative
 //             couplings goes by |a_ij|): every free node proposes to its strongest unmatched strong neighbour (ties: a hash of the index pair), mutual proposals
-//             pair, kAmgRounds rounds (from kAmgStrongRounds on weak couplings count too), leftovers stay single -- the second pass on the Galerkin matrix of the first: aggregates of at most 4 nodes.  The
+//             pair, kAmgRounds rounds (from kAmgStrongRounds on weak couplings count too), leftovers stay single -- the second pass on the Galerkin matrix of the first: aggregates of at most 4 nodes
+//             -- unless the pass ABSORBS (knob amg_absorb): a row the rounds left single joins the pair of its most strongly coupled paired neighbour
+//             (k_amg_absorb), so an aggregate is a pair and whatever singles chose it.  The singles are an independent set that pairing alone carries from
+//             level to level -- their neighbours are heavy aggregates that prefer each other -- until they are most of a level and coarsening stalls (3-D).  The
 //             coarse matrix is P^T A P with piecewise-constant P, built as a stable key sort of the (agg(i), agg(j)) pairs and a segmented sum in
 //             ascending fine-slot order: no float atomics, the same bits every run.  Levels until one has at most `amg_coarse_rows` rows; that one is
 //             inverted once (dense_build_csr, kernels_dense.h).
@@ -115,7 +118,36 @@ __device__ __host__ inline int32_t amg_propose_row(int64_t i, const int32_t* rp,
     }
     return best;
 }
-__device__ __host__ inline bool amg_leader(int64_t i, const int32_t* mate) { return mate[i] == kMateFree || (mate[i] >= 0 && (int64_t)mate[i] > i); }
+// absorption, after the last round (mate as it left it: no order of execution matters): a row still free picks the PAIRED neighbour it is most strongly coupled
+// to -- amg_propose_row's relaxed comparison with "paired" in place of "free" -- and joins that pair's aggregate; -1: none (not free, or no paired neighbour)
+__device__ __host__ inline int32_t amg_absorb_row(int64_t i, const int32_t* rp, const int32_t* ci, const double* sw, const int32_t* mate) {
+    if (mate[i] != kMateFree) return -1;
+    int32_t best = -1;
+    double bw = 0.0;
+    uint32_t bh = 0;
+    for (int32_t k = rp[i]; k < rp[i + 1]; ++k) {
+        const int32_t j = ci[k];
+        const double w = sw[k] < 0.0 ? -sw[k] : sw[k];
+        if (!(w > 0.0) || j == (int32_t)i || mate[j] < 0) continue;
+        const uint32_t h = amg_pair_hash((int32_t)i, j);
+        if (w > bw || (w == bw && (h > bh || (h == bh && j < best)))) bw = w, bh = h, best = j;
+    }
+    return best;
+}
+// host: what amg_absorb_row chose per row, or NULL (a pass that does not absorb).  A row with a host leads no aggregate; hosts are paired rows: no chains
+__device__ __host__ inline bool amg_leader(int64_t i, const int32_t* mate, const int32_t* host) {
+    if (host && host[i] >= 0) return false;
+    return mate[i] == kMateFree || (mate[i] >= 0 && (int64_t)mate[i] > i);
+}
+__device__ __host__ inline int32_t amg_aggregate_of(int64_t i, const int32_t* mate, const int32_t* host, const int32_t* id) {
+    const int32_t m = mate[i];
+    if (m == kMateExcluded) return -1;
+    if (host && host[i] >= 0) {
+        const int32_t h = host[i], hm = mate[h];
+        return id[h < hm ? h : hm];
+    }
+    return amg_leader(i, mate, host) ? id[i] : id[m];
+}
 
 __global__ void k_amg_init_mate(int64_t n, const uint8_t* excl, int32_t* mate) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -136,15 +168,17 @@ __global__ void k_amg_accept(int64_t n, const int32_t* prop, int32_t* mate) {
     const int32_t j = prop[i];
     if (j >= 0 && prop[j] == (int32_t)i) mate[i] = j;
 }
-__global__ void k_amg_leaders(int64_t n, const int32_t* mate, int32_t* lead) {
+__global__ void k_amg_absorb(int64_t n, const int32_t* rp, const int32_t* ci, const double* sw, const int32_t* mate, int32_t* host) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) lead[i] = amg_leader(i, mate) ? 1 : 0;
+    if (i < n) host[i] = amg_absorb_row(i, rp, ci, sw, mate);
 }
-__global__ void k_amg_assign(int64_t n, const int32_t* mate, const int32_t* id, int32_t* agg) {
+__global__ void k_amg_leaders(int64_t n, const int32_t* mate, const int32_t* host, int32_t* lead) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int32_t m = mate[i];
-    agg[i] = m == kMateExcluded ? -1 : amg_leader(i, mate) ? id[i] : id[m];
+    if (i < n) lead[i] = amg_leader(i, mate, host) ? 1 : 0;
+}
+__global__ void k_amg_assign(int64_t n, const int32_t* mate, const int32_t* host, const int32_t* id, int32_t* agg) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) agg[i] = amg_aggregate_of(i, mate, host, id);
 }
 __global__ void k_amg_compose(int64_t n, const int32_t* agg1, const int32_t* agg2, int32_t* agg) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -375,6 +409,8 @@ struct AmgHierarchy {
     const double* A = nullptr;
     int64_t key = -1;
     double setup_ms = 0.0, op_complexity = 0.0;
+    int absorbed = 0;                             // its passes absorbed the rows the matching left single (knob amg_absorb)
+    double discarded_ms = 0.0;                    // amg_absorb 2: what the build without absorption cost before it stalled (part of setup_ms)
     DBuf<double> vec, basis, part, dots;          // the outer iteration's vectors (x, r, t) and flexible GMRES basis
     int np = 1, mk = 0;
     ~AmgHierarchy() {
@@ -385,7 +421,7 @@ struct AmgHierarchy {
 };
 
 // ---- the host loops of the same set-up (knob amg_setup_check): the same arithmetic in the same order (declared in amg_setup.h) ----
-void host_pairwise(const HostCsr& A, const uint8_t* excl, std::vector<int32_t>& agg, int32_t& nc) {
+void host_pairwise(const HostCsr& A, const uint8_t* excl, int absorb, std::vector<int32_t>& agg, int32_t& nc) {
     const int64_t n = A.n;
     std::vector<double> sw(A.a.size());
     for (int64_t i = 0; i < n; ++i) amg_strength_row(i, A.rp.data(), A.ci.data(), A.a.data(), excl, sw.data());
@@ -399,17 +435,20 @@ void host_pairwise(const HostCsr& A, const uint8_t* excl, std::vector<int32_t>& 
             if (j >= 0 && prop[(size_t)j] == (int32_t)i) mate[(size_t)i] = j;
         }
     }
+    std::vector<int32_t> host_of;
+    if (absorb) {
+        host_of.resize((size_t)n);
+        for (int64_t i = 0; i < n; ++i) host_of[(size_t)i] = amg_absorb_row(i, A.rp.data(), A.ci.data(), sw.data(), mate.data());
+    }
+    const int32_t* host = absorb ? host_of.data() : nullptr;
     std::vector<int32_t> id((size_t)n);
     nc = 0;
     for (int64_t i = 0; i < n; ++i) {
         id[(size_t)i] = nc;
-        nc += amg_leader(i, mate.data()) ? 1 : 0;
+        nc += amg_leader(i, mate.data(), host) ? 1 : 0;
     }
     agg.assign((size_t)n, -1);
-    for (int64_t i = 0; i < n; ++i) {
-        const int32_t m = mate[(size_t)i];
-        agg[(size_t)i] = m == kMateExcluded ? -1 : amg_leader(i, mate.data()) ? id[(size_t)i] : id[(size_t)m];
-    }
+    for (int64_t i = 0; i < n; ++i) agg[(size_t)i] = amg_aggregate_of(i, mate.data(), host, id.data());
 }
 void host_galerkin(const HostCsr& A, const std::vector<int32_t>& agg, int32_t nc, HostCsr& C) {
     std::vector<std::pair<uint64_t, int32_t>> ent;
@@ -444,12 +483,13 @@ template <typename T> int fetch(fdapde_ctx* c, const T* p, size_t n, std::vector
 
 }   // namespace
 
-// one pairwise pass on the device: agg (n words), *nc; scratch kept by the caller
-int dev_pairwise(fdapde_ctx* c, int64_t n, int64_t nnz, const int32_t* rp, const int32_t* ci, const double* a, const uint8_t* excl, DBuf<int32_t>& agg, int32_t* nc) {
+// one pairwise pass on the device (absorb: followed by the absorption of the rows it left single): agg (n words), *nc
+int dev_pairwise(fdapde_ctx* c, int64_t n, int64_t nnz, const int32_t* rp, const int32_t* ci, const double* a, const uint8_t* excl, int absorb, DBuf<int32_t>& agg,
+                 int32_t* nc) {
     hipStream_t st = c->stream;
     const dim3 bv(256);
     DBuf<double> sw;
-    DBuf<int32_t> mate, prop, lead, id;
+    DBuf<int32_t> mate, prop, lead, id, host;
     DBuf<char> tmp;
     HIPCHK(c, sw.alloc((size_t)nnz));
     HIPCHK(c, mate.alloc((size_t)n));
@@ -463,13 +503,17 @@ int dev_pairwise(fdapde_ctx* c, int64_t n, int64_t nnz, const int32_t* rp, const
         hipLaunchKernelGGL(k_amg_propose, dim3(gn(n)), bv, 0, st, n, rp, ci, sw.p, mate.p, round >= kAmgStrongRounds ? 1 : 0, prop.p);
         hipLaunchKernelGGL(k_amg_accept, dim3(gn(n)), bv, 0, st, n, prop.p, mate.p);
     }
+    if (absorb) {
+        HIPCHK(c, host.alloc((size_t)n));
+        hipLaunchKernelGGL(k_amg_absorb, dim3(gn(n)), bv, 0, st, n, rp, ci, sw.p, mate.p, host.p);
+    }
     HIPCHK(c, hipMemsetAsync(lead.p + n, 0, sizeof(int32_t), st));
-    hipLaunchKernelGGL(k_amg_leaders, dim3(gn(n)), bv, 0, st, n, mate.p, lead.p);
+    hipLaunchKernelGGL(k_amg_leaders, dim3(gn(n)), bv, 0, st, n, mate.p, (const int32_t*)host.p, lead.p);
     size_t need = 0;
     HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, need, lead.p, id.p, (int)(n + 1), st));
     HIPCHK(c, tmp.alloc(need));
     HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(tmp.p, need, lead.p, id.p, (int)(n + 1), st));
-    hipLaunchKernelGGL(k_amg_assign, dim3(gn(n)), bv, 0, st, n, mate.p, id.p, agg.p);
+    hipLaunchKernelGGL(k_amg_assign, dim3(gn(n)), bv, 0, st, n, mate.p, (const int32_t*)host.p, id.p, agg.p);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(nc, id.p + n, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
@@ -612,14 +656,13 @@ void amg_release(fdapde_ctx* c) {
     c->amg = c->amg_lin = nullptr;
 }
 
-// the hierarchy of A (the context's pattern, internal order); use_bnd: level 0's Dirichlet DOFs (c->bnd) belong to no aggregate
-int amg_build(fdapde_ctx* c, AmgHierarchy** slot, const double* A, int use_bnd, bool symmetric) {
-    delete *slot;
-    *slot = nullptr;
-    HIPCHK(c, hipSetDevice(c->device));
+namespace {
+// the hierarchy of A with (absorb) or without absorption on every level; *stalled: the answer is the "coarsening stalled above the dense limit" refusal
+int amg_build_pass(fdapde_ctx* c, AmgHierarchy** slot, const double* A, int use_bnd, bool symmetric, int absorb, bool* stalled) {
+    *stalled = false;
     const auto t0 = std::chrono::steady_clock::now();
     std::unique_ptr<AmgHierarchy> H(new AmgHierarchy());
-    H->sym = symmetric, H->use_bnd = use_bnd, H->A = A;
+    H->sym = symmetric, H->use_bnd = use_bnd, H->A = A, H->absorbed = absorb;
     const int64_t coarse_rows = std::max<int64_t>(1, std::min<int64_t>(c->amg_coarse_rows, kAmgMaxCoarse));
     {
         std::unique_ptr<AmgLevel> L0(new AmgLevel());
@@ -635,11 +678,11 @@ int amg_build(fdapde_ctx* c, AmgHierarchy** slot, const double* A, int use_bnd, 
         // pass 1 on the level, pass 2 on the Galerkin matrix of pass 1 (the pair graph): aggregates of at most four rows
         DBuf<int32_t> agg1, agg2;
         int32_t n1 = 0, n2 = 0;
-        if (int rc = dev_pairwise(c, F.n, F.nnz, F.rp, F.ci, F.a, F.excl, agg1, &n1)) return rc;
+        if (int rc = dev_pairwise(c, F.n, F.nnz, F.rp, F.ci, F.a, F.excl, absorb, agg1, &n1)) return rc;
         if (n1 == 0) return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_AMG: a level above the dense limit has no free rows to aggregate");
         AmgLevel T;
         if (int rc = dev_galerkin(c, F.n, F.nnz, F.rp, F.ci, F.a, agg1.p, n1, T)) return rc;
-        if (int rc = dev_pairwise(c, T.n, T.nnz, T.rp, T.ci, T.a, nullptr, agg2, &n2)) return rc;
+        if (int rc = dev_pairwise(c, T.n, T.nnz, T.rp, T.ci, T.a, nullptr, absorb, agg2, &n2)) return rc;
         std::unique_ptr<AmgLevel> N(new AmgLevel());
         if (int rc = dev_galerkin(c, T.n, T.nnz, T.rp, T.ci, T.a, agg2.p, n2, *N)) return rc;
         HIPCHK(c, F.agg.alloc((size_t)F.n));
@@ -653,9 +696,9 @@ int amg_build(fdapde_ctx* c, AmgHierarchy** slot, const double* A, int use_bnd, 
             if (int rc = fetch(c, F.a, (size_t)F.nnz, hf.a)) return rc;
             std::vector<int32_t> a1, a2, comp((size_t)F.n), mptr((size_t)n2 + 1, 0), midx;
             int32_t m1 = 0, m2 = 0;
-            host_pairwise(hf, H->lv.size() == 1 && use_bnd ? excl_h.data() : nullptr, a1, m1);
+            host_pairwise(hf, H->lv.size() == 1 && use_bnd ? excl_h.data() : nullptr, absorb, a1, m1);
             host_galerkin(hf, a1, m1, ht);
-            host_pairwise(ht, nullptr, a2, m2);
+            host_pairwise(ht, nullptr, absorb, a2, m2);
             host_galerkin(ht, a2, m2, hn);
             for (int64_t i = 0; i < F.n; ++i) comp[(size_t)i] = a1[(size_t)i] < 0 ? -1 : a2[(size_t)a1[(size_t)i]];
             for (int64_t i = 0; i < F.n; ++i)
@@ -684,8 +727,10 @@ int amg_build(fdapde_ctx* c, AmgHierarchy** slot, const double* A, int use_bnd, 
             }
         }
         if ((double)n2 > kAmgStall * (double)F.n && n2 > coarse_rows) {   // coarsening stalled: a level the dense inverse takes ends the hierarchy
-            if (F.n > kAmgMaxCoarse)
+            if (F.n > kAmgMaxCoarse) {
+                *stalled = true;
                 return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_AMG: coarsening stalled above the dense limit (a level kept more than 0.8 of its rows): the matrix has too few strong couplings for pairwise aggregation");
+            }
             F.agg.release(), F.mptr.release(), F.midx.release();
             break;
         }
@@ -704,6 +749,37 @@ int amg_build(fdapde_ctx* c, AmgHierarchy** slot, const double* A, int use_bnd, 
         return fail(c, FDAPDE_ENOCONV, "FDAPDE_SOLVER_AMG: the coarsest level is singular to working precision (a pure Neumann problem has no unique solution)");
     H->setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     *slot = H.release();
+    return FDAPDE_OK;
+}
+}   // namespace
+
+// the hierarchy of A (the context's pattern, internal order); use_bnd: level 0's Dirichlet DOFs (c->bnd) belong to no aggregate.  Knob amg_absorb: 0 pairs
+// only, 1 absorbs on every level, 2 pairs only and -- where that ends in the stall refusal -- builds again from level 0 with absorption on every level
+int amg_build(fdapde_ctx* c, AmgHierarchy** slot, const double* A, int use_bnd, bool symmetric) {
+    delete *slot;
+    *slot = nullptr;
+    HIPCHK(c, hipSetDevice(c->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    bool stalled = false;
+    int rc = amg_build_pass(c, slot, A, use_bnd, symmetric, c->amg_absorb == 1 ? 1 : 0, &stalled);
+    if (rc != FDAPDE_OK && stalled && c->amg_absorb == 2) {
+        const double first = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        rc = amg_build_pass(c, slot, A, use_bnd, symmetric, 1, &stalled);
+        if (rc == FDAPDE_OK) (*slot)->discarded_ms = first, (*slot)->setup_ms += first;
+    }
+    return rc;
+}
+
+// fdapde_amg_hierarchy for a scalar hierarchy: rows and entries per level
+int amg_describe(const AmgHierarchy* H, int32_t cap, int32_t* n_levels, int64_t* rows, int64_t* nnz, int32_t* absorbed, double* setup_ms) {
+    if (!H) return FDAPDE_ENOTINIT;
+    if (n_levels) *n_levels = (int32_t)H->lv.size();
+    for (size_t l = 0; l < H->lv.size() && (int64_t)l < (int64_t)cap; ++l) {
+        if (rows) rows[l] = H->lv[l]->n;
+        if (nnz) nnz[l] = H->lv[l]->nnz;
+    }
+    if (absorbed) *absorbed = H->absorbed;
+    if (setup_ms) *setup_ms = H->setup_ms;
     return FDAPDE_OK;
 }
 
@@ -831,8 +907,8 @@ int amg_run(fdapde_ctx* c, AmgHierarchy* hp, const double* A, const double* f_de
     if (std::getenv("FDAPDE_DEBUG_SETUP")) {
         std::string rows;
         for (size_t l = 0; l < H.lv.size(); ++l) rows += (l ? " / " : "") + std::to_string(H.lv[l]->n);
-        std::fprintf(stderr, "amg: %zu levels, rows %s, operator complexity %.3f, set-up %.2f ms, solve %.2f ms, %d iterations, true relres %.2e\n", H.lv.size(),
-                     rows.c_str(), H.op_complexity, H.setup_ms, c->info.t_solve_ms, it, true_rel);
+        std::fprintf(stderr, "amg: %zu levels, rows %s, operator complexity %.3f, set-up %.2f ms, solve %.2f ms, %d iterations, true relres %.2e, absorbed %d, discarded build %.2f ms\n",
+                     H.lv.size(), rows.c_str(), H.op_complexity, H.setup_ms, c->info.t_solve_ms, it, true_rel, H.absorbed, H.discarded_ms);
     }
     if (!converged) {
         c->err = broke ? "FDAPDE_SOLVER_AMG: the flexible GMRES broke down" : "FDAPDE_SOLVER_AMG: maxit reached";

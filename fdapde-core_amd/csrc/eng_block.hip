@@ -50,6 +50,18 @@ void block_release(fdapde_ctx* c) {
     c->block = nullptr;
 }
 
+void block_amg_forget(fdapde_ctx* c) {
+    if (!c->block || !c->block->amg) return;
+    if (c->has_device) {
+        (void)hipSetDevice(c->device);
+        (void)hipStreamSynchronize(c->stream);
+    }
+    block_amg_free(c->block->amg), c->block->amg = nullptr;
+}
+int block_amg_describe_ctx(const fdapde_ctx* c, int32_t cap, int32_t* n_levels, int64_t* rows, int64_t* nnz, int32_t* absorbed, double* setup_ms) {
+    return block_amg_describe(c->block ? c->block->amg : nullptr, cap, n_levels, rows, nnz, absorbed, setup_ms);
+}
+
 namespace {
 
 int block_guard(fdapde_ctx* c) {

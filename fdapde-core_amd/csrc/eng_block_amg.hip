@@ -6,7 +6,8 @@
 // FDAPDE_SOLVER_AMG (eng_amg.hip) with the two unknowns of a DOF kept together does not.
 //
 // What:
-//   set-up    level 0 is the handle's unscaled block CSR.  The aggregates come from eng_amg.hip's two pairwise passes (dev_pairwise, unchanged) on a SCALAR
+//   set-up    level 0 is the handle's unscaled block CSR.  The aggregates come from eng_amg.hip's two pairwise passes (dev_pairwise, with its absorption of
+//             the rows left single under the knob amg_absorb) on a SCALAR
 //             strength matrix on the same pattern: the (2,1) block as given -- (1,2), (2,2), (1,1) where it was NULL --, whose Galerkin product
 //             (dev_galerkin) is the next level's pattern and strength matrix.  The four block values of a coarse entry are summed with the same keys in
 //             ascending fine-slot order (k_bamg_gsum): P = P_scalar (x) I_2, unknowns interleaved on every level, no float atomics.  Levels until one has
@@ -56,7 +57,8 @@ struct BlockAmg {
     DBuf<int32_t> rp2, ci2;
     DBuf<double> val2;
     DBuf<double> vec, basis, part, dots;          // the outer iteration's x, r, t, b and the flexible GMRES basis
-    double setup_ms = 0.0;
+    double setup_ms = 0.0, discarded_ms = 0.0;    // (discarded_ms: amg_absorb 2, the build without absorption that stalled -- part of setup_ms)
+    int absorbed = 0;
     ~BlockAmg() { D.X.release(); }
 };
 
@@ -175,14 +177,14 @@ int bamg_correction(fdapde_ctx* c, BlockAmg& H, size_t m) {
 }
 }   // namespace
 
-// the hierarchy of the handle's matrix: raw = the unscaled block CSR on the context's pattern, strength_block = which of its four blocks the aggregation reads
-int block_amg_build(fdapde_ctx* c, BlockAmg** slot, const double* raw, int strength_block) {
-    delete *slot;
-    *slot = nullptr;
-    HIPCHK(c, hipSetDevice(c->device));
+namespace {
+// the hierarchy with (absorb) or without absorption on every level; *stalled: the answer is the "coarsening stalled above the dense limit" refusal
+int block_amg_build_pass(fdapde_ctx* c, BlockAmg** slot, const double* raw, int strength_block, int absorb, bool* stalled) {
+    *stalled = false;
     hipStream_t st = c->stream;
     const auto t0 = std::chrono::steady_clock::now();
     std::unique_ptr<BlockAmg> H(new BlockAmg());
+    H->absorbed = absorb;
     const int64_t dense_limit = std::min<int64_t>(c->dense_rows, kDenseMaxRows);
     const int64_t coarse_rows = std::max<int64_t>(2, std::min<int64_t>(c->amg_coarse_rows, kDenseMaxRows));
     {
@@ -201,7 +203,7 @@ int block_amg_build(fdapde_ctx* c, BlockAmg** slot, const double* raw, int stren
         // pass 1 on the level's strength matrix, pass 2 on its Galerkin matrix (the pair graph): aggregates of at most four rows; the block values follow
         DBuf<int32_t> agg1, agg2;
         int32_t n1 = 0, n2 = 0;
-        if (int rc = dev_pairwise(c, F.n, F.nnz, F.rp, F.ci, F.S.a, nullptr, agg1, &n1)) return rc;
+        if (int rc = dev_pairwise(c, F.n, F.nnz, F.rp, F.ci, F.S.a, nullptr, absorb, agg1, &n1)) return rc;
         AmgLevel T;
         DBuf<double> bvT;
         {
@@ -209,7 +211,7 @@ int block_amg_build(fdapde_ctx* c, BlockAmg** slot, const double* raw, int stren
             if (int rc = dev_galerkin(c, F.n, F.nnz, F.rp, F.ci, F.S.a, agg1.p, n1, T, &map)) return rc;
             if (int rc = block_galerkin(c, map, F.bv, T.nnz, bvT)) return rc;
         }
-        if (int rc = dev_pairwise(c, T.n, T.nnz, T.rp, T.ci, T.a, nullptr, agg2, &n2)) return rc;
+        if (int rc = dev_pairwise(c, T.n, T.nnz, T.rp, T.ci, T.a, nullptr, absorb, agg2, &n2)) return rc;
         std::unique_ptr<BamgLevel> N(new BamgLevel());
         {
             AmgGalerkinMap map;
@@ -231,10 +233,10 @@ int block_amg_build(fdapde_ctx* c, BlockAmg** slot, const double* raw, int stren
             if (int rc = fetch(c, F.ci, (size_t)F.nnz, hf.ci)) return rc;
             if (int rc = fetch(c, F.S.a, (size_t)F.nnz, hf.a)) return rc;
             if (int rc = fetch(c, F.bv, 4 * (size_t)F.nnz, bf)) return rc;
-            host_pairwise(hf, nullptr, a1, m1);
+            host_pairwise(hf, nullptr, absorb, a1, m1);
             host_galerkin(hf, a1, m1, ht);
             host_block_galerkin(hf, bf, a1, m1, bt);
-            host_pairwise(ht, nullptr, a2, m2);
+            host_pairwise(ht, nullptr, absorb, a2, m2);
             host_galerkin(ht, a2, m2, hn);
             host_block_galerkin(ht, bt, a2, m2, bn);
             std::string which;
@@ -259,8 +261,10 @@ int block_amg_build(fdapde_ctx* c, BlockAmg** slot, const double* raw, int stren
             }
         }
         if ((double)n2 > kBamgStall * (double)F.n && 2 * (int64_t)n2 > coarse_rows) {   // coarsening stalled: a level the dense inverse takes ends the hierarchy
-            if (2 * F.n > dense_limit)
+            if (2 * F.n > dense_limit) {
+                *stalled = true;
                 return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_BLOCK_AMG: coarsening stalled above the dense limit (a level kept more than 0.8 of its rows): the strength block has too few strong couplings for pairwise aggregation");
+            }
             F.agg.release(), F.mptr.release(), F.midx.release();
             break;
         }
@@ -294,9 +298,39 @@ int block_amg_build(fdapde_ctx* c, BlockAmg** slot, const double* raw, int stren
     if (std::getenv("FDAPDE_DEBUG_SETUP")) {
         std::string rows;
         for (size_t l = 0; l < H->lv.size(); ++l) rows += (l ? " / " : "") + std::to_string(2 * H->lv[l]->n);
-        std::fprintf(stderr, "block amg: %zu levels, rows %s, set-up %.2f ms\n", H->lv.size(), rows.c_str(), H->setup_ms);
+        std::fprintf(stderr, "block amg: %zu levels, rows %s, set-up %.2f ms, absorbed %d\n", H->lv.size(), rows.c_str(), H->setup_ms, H->absorbed);
     }
     *slot = H.release();
+    return FDAPDE_OK;
+}
+}   // namespace
+
+// the hierarchy of the handle's matrix: raw = the unscaled block CSR on the context's pattern, strength_block = which of its four blocks the aggregation reads.
+// Knob amg_absorb as in amg_build (eng_amg.hip): 2 builds without absorption and, where that ends in the stall refusal, again from level 0 with it
+int block_amg_build(fdapde_ctx* c, BlockAmg** slot, const double* raw, int strength_block) {
+    delete *slot;
+    *slot = nullptr;
+    HIPCHK(c, hipSetDevice(c->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    bool stalled = false;
+    int rc = block_amg_build_pass(c, slot, raw, strength_block, c->amg_absorb == 1 ? 1 : 0, &stalled);
+    if (rc != FDAPDE_OK && stalled && c->amg_absorb == 2) {
+        const double first = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        rc = block_amg_build_pass(c, slot, raw, strength_block, 1, &stalled);
+        if (rc == FDAPDE_OK) (*slot)->discarded_ms = first, (*slot)->setup_ms += first;
+    }
+    return rc;
+}
+
+int block_amg_describe(const BlockAmg* H, int32_t cap, int32_t* n_levels, int64_t* rows, int64_t* nnz, int32_t* absorbed, double* setup_ms) {
+    if (!H) return FDAPDE_ENOTINIT;
+    if (n_levels) *n_levels = (int32_t)H->lv.size();
+    for (size_t l = 0; l < H->lv.size() && (int64_t)l < (int64_t)cap; ++l) {
+        if (rows) rows[l] = 2 * H->lv[l]->n;
+        if (nnz) nnz[l] = 4 * H->lv[l]->nnz;
+    }
+    if (absorbed) *absorbed = H->absorbed;
+    if (setup_ms) *setup_ms = H->setup_ms;
     return FDAPDE_OK;
 }
 

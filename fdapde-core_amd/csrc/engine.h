@@ -188,10 +188,14 @@ int e_solve_amg(fdapde_ctx* c, const fdapde_options* opt, fdapde_info* info);
 int amg_run(fdapde_ctx* c, AmgHierarchy* h, const double* A, const double* f_dev, const double* g_dev, int use_bnd, const double* x0_dev, double rtol, int maxit);
 // (re)build hierarchy *slot for A on the context's pattern (use_bnd: the Dirichlet DOFs belong to no aggregate)
 int amg_build(fdapde_ctx* c, AmgHierarchy** slot, const double* A, int use_bnd, bool symmetric);
+// fdapde_amg_hierarchy: levels, rows and entries per level (the first `cap` of them), whether the passes absorbed, what the set-up cost; FDAPDE_ENOTINIT for NULL
+int amg_describe(const AmgHierarchy* h, int32_t cap, int32_t* n_levels, int64_t* rows, int64_t* nnz, int32_t* absorbed, double* setup_ms);
 int dense_step_loop(fdapde_ctx* c, fdapde_ctx::Dense& D, int32_t n_times, double inv_dt, const double* g_ext_dev, double* u0, double* sol_ext);
 void preload_dense();
 // eng_block.hip: 2 x 2 block systems on the FEM pattern (the smoothing system's handle) and Psi^T W Psi on that pattern
 void block_release(fdapde_ctx* c);
+void block_amg_forget(fdapde_ctx* c);   // the block handle's hierarchy is built again by its next solve (a set-up knob changed)
+int block_amg_describe_ctx(const fdapde_ctx* c, int32_t cap, int32_t* n_levels, int64_t* rows, int64_t* nnz, int32_t* absorbed, double* setup_ms);
 int e_block_compute(fdapde_ctx* c, const double* a11, const double* a12, const double* a21, const double* a22, int32_t symmetric);
 int e_block_solve(fdapde_ctx* c, const fdapde_options* opt, const double* b, int32_t n_rhs, double* x, fdapde_info* info);
 int e_block_spmv(fdapde_ctx* c, const double* x, double* y);
@@ -203,6 +207,7 @@ int e_gram_pointwise(fdapde_ctx* c, int64_t n_locs, const int32_t* cell_ids, con
 struct BlockAmg;
 void block_amg_free(BlockAmg* h);
 int block_amg_build(fdapde_ctx* c, BlockAmg** slot, const double* raw, int strength_block);
+int block_amg_describe(const BlockAmg* h, int32_t cap, int32_t* n_levels, int64_t* rows, int64_t* nnz, int32_t* absorbed, double* setup_ms);   // rows: 2 n_l
 int block_amg_run(fdapde_ctx* c, BlockAmg* h, const double* raw, const double* b_dev, double* x_dev, double rtol, int maxit, int* iters, double* relres,
                   bool* converged, bool* broke);
 

@@ -96,18 +96,21 @@ enum { FDAPDE_SOLVER_AUTO = 0, FDAPDE_SOLVER_CG = 1, FDAPDE_SOLVER_BICGSTAB = 2,
                                 form), pmg_smooth 0 = flexible GMRES around that additive form, pmg_blocked 0 = the fine operator through the CSR kernel. */,
        FDAPDE_SOLVER_AMG = 8 /* any order, any dimension, symmetric or not, one-GPU contexts: flexible GMRES with an ALGEBRAIC multilevel preconditioner --
                                 a K-cycle (damped Jacobi, two flexible CG / GCR steps on the next level, damped Jacobi) over aggregates of at most four DOFs
-                                from double pairwise matching on the matrix's strong couplings, Galerkin coarse matrices P^T A P (piecewise-constant P, a fixed
+                                from double pairwise matching on the matrix's strong couplings (larger where the passes absorb: a row the matching left single
+                                joins the pair of its most strongly coupled paired neighbour -- knob `amg_absorb`: by default only a hierarchy that would
+                                otherwise stall above the dense limit is built again that way, which is what coarsens 3-D systems of millions of rows), Galerkin coarse matrices P^T A P (piecewise-constant P, a fixed
                                 summation order: the same bits every run), the last level -- at most `amg_coarse_rows` (1 024) rows, or where coarsening
                                 stalls below 8 192 rows -- inverted once on the device.  The hierarchy is built from the matrix alone: fdapde_solve (kept while the operator and the Dirichlet variant
                                 stay), fdapde_solve_parabolic (once per call, on K = M / dt + A; a step starts from the previous column) and the factor-once
                                 handle (once per fdapde_lin_compute; columns one after the other).  Taken by name only: the open method never chooses it.
                                 info.iters counts outer iterations, info.relres is the true relative residual of what is handed out, info.persistent = 0.
                                 rtol 1e-10 and maxit 200 by default; non-convergence is FDAPDE_ENOCONV (success = false), as is a singular coarsest level
-                                (pure Neumann data); coarsening that stalls above the dense limit, a rank of a multi-GPU job and a multi-device context are
+                                (pure Neumann data); coarsening that stalls above the dense limit with absorption too (or with `amg_absorb` 0), a rank of a multi-GPU job and a multi-device context are
                                 FDAPDE_EUNSUPPORTED. */,
        FDAPDE_SOLVER_BLOCK_AMG = 9 /* fdapde_block_solve only (fdapde_solve, fdapde_solve_parabolic and fdapde_lin_solve answer FDAPDE_EUNSUPPORTED): flexible
                                 GMRES(gmres_m) on the UNSCALED 2 x 2 block system, right-preconditioned by the multilevel cycle of FDAPDE_SOLVER_AMG on
-                                POINT-BLOCK unknowns -- the two unknowns of a DOF stay together on every level.  Aggregates of at most four DOFs from double
+                                POINT-BLOCK unknowns -- the two unknowns of a DOF stay together on every level.  Aggregates of at most four DOFs (larger where
+                                the passes absorb the rows left single: knob `amg_absorb`, as for FDAPDE_SOLVER_AMG) from double
                                 pairwise matching on a scalar strength matrix on the pattern (the (2,1) block as given; (1,2), (2,2), (1,1) where it was
                                 NULL), block Galerkin matrices in a fixed summation order (the same bits every run), smoother 0.7 D^-1 with D the 2 x 2
                                 diagonal blocks, two GCR steps per coarse level always (the system is indefinite), the last level -- at most
@@ -117,7 +120,7 @@ enum { FDAPDE_SOLVER_AUTO = 0, FDAPDE_SOLVER_CG = 1, FDAPDE_SOLVER_BICGSTAB = 2,
                                 and maxit 200 by default; columns one after another, info.iters summed over them, info.relres the worst column's true
                                 relative residual, info.persistent = 0; FDAPDE_ENOCONV leaves the last iterate of every column, and is also the answer to
                                 a singular coarsest level; a singular diagonal block of a DOF (the 1e-14 rule of fdapde_block_compute) and coarsening
-                                that stalls above the dense limit are FDAPDE_EUNSUPPORTED.  Taken by name only: the open method never chooses it.
+                                that stalls above the dense limit with absorption too (or with `amg_absorb` 0) are FDAPDE_EUNSUPPORTED.  Taken by name only: the open method never chooses it.
                                 Order-2 spaces in 3-D are allowed, but pairwise matching serves them poorly (no iteration count is claimed). */ };
 /* ROWS: row-owner sweep (default; no atomics, bitwise reproducible).  The others are element-wise scatter forms kept as measured
  * alternatives and cross-checks: ATOMIC / COLOURED = lane per (cell, row) with a slot search, fp64 atomics / one launch per colour;
@@ -519,8 +522,18 @@ int fdapde_partition_peers(fdapde_ctx *ctx, int32_t rank, int32_t *n_peers, int3
  *                 are also built by host loops and compared; an error if they differ)
  *   multilevel    "amg_coarse_rows" (FDAPDE_SOLVER_AMG and FDAPDE_SOLVER_BLOCK_AMG coarsen until a level has at most that many rows -- 2 n_l for the block
  *                 form --, 1 .. 8 192; 1 024), "amg_setup_check" (1: the aggregates,
- *                 coarse patterns and coarse values are also built by host loops and compared bit for bit; an error if they differ) */
+ *                 coarse patterns and coarse values are also built by host loops and compared bit for bit; an error if they differ),
+ *                 "amg_absorb" (both set-ups: 0 = pairwise matching only; 1 = every pass of every level also lets each row it left single join the pair
+ *                 of its most strongly coupled paired neighbour; 2, the default = as 0, and where that build ends in "coarsening stalled above the dense
+ *                 limit" the whole hierarchy is built again as 1 -- a system that is solved under 0 keeps its hierarchy, its count and its bits; setting
+ *                 another value drops the live hierarchies) */
 int fdapde_tune(fdapde_ctx *ctx, const char *key, int32_t value);
+/* The live hierarchy of a multilevel solver as data.  which: 0 = fdapde_solve's (FDAPDE_SOLVER_AMG; fdapde_solve_parabolic builds its own per call and
+ * drops it when it returns), 1 = the factor-once handle's, 2 = the 2 x 2 block handle's (FDAPDE_SOLVER_BLOCK_AMG).  *n_levels: its levels, the last one the
+ * inverted one; rows[l] / nnz[l] for the first min(cap, *n_levels) of them: rows and stored entries of level l (the block handle's counted as scalars:
+ * 2 n_l and 4 nnz_l); *absorbed: 1 if its passes absorbed the rows left single ("amg_absorb"); *setup_ms: host time of the set-up, the discarded
+ * first build of "amg_absorb" 2 included.  Any output pointer may be NULL.  FDAPDE_ENOTINIT where no such hierarchy is live. */
+int fdapde_amg_hierarchy(fdapde_ctx *ctx, int32_t which, int32_t cap, int32_t *n_levels, int64_t *rows, int64_t *nnz, int32_t *absorbed, double *setup_ms);
 /* the context's HIP stream (hipStream_t) so that callers can bracket work with their own events */
 void *fdapde_stream(fdapde_ctx *ctx);
 int fdapde_synchronize(fdapde_ctx *ctx);

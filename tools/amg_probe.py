@@ -2,9 +2,11 @@
 operator complexity), set-up ms (first solve minus second), solve ms and iterations, and the same system through FDAPDE_SOLVER_AUTO (or, for C5's P2 operator,
 FDAPDE_SOLVER_PMG; for the handle, the handle's existing path per column).  Wall-clock host times around each call.  -> profiles/amg_probe.txt
 
-    python tools/amg_probe.py [--cases all | c2,c3,...]
+    python tools/amg_probe.py [--cases all | c2,c3,...] [--absorb 2 | 0,1 | ...]
 
-The hierarchy's line comes from FDAPDE_DEBUG_SETUP (stderr of the library, caught per call)."""
+--absorb: the values of the knob `amg_absorb` to run every elliptic case with, one context per value in the same process; the timed solves of the arms
+alternate, five each (median, smallest, largest).  The hierarchy comes from fdapde_amg_hierarchy; the cost of the build `amg_absorb` 2 discards comes from the
+FDAPDE_DEBUG_SETUP line (stderr of the library, caught per call)."""
 import argparse
 import os
 import re
@@ -45,56 +47,83 @@ def timed(fn):
     return r, 1e3 * (time.perf_counter() - t0)
 
 
-def amg_line(text):
-    m = re.findall(r"amg: (\d+) levels, rows ([\d / ]+), operator complexity ([\d.]+)", text)
-    return f"{m[-1][0]} levels, rows {m[-1][1]}, op. complexity {m[-1][2]}" if m else "-"
+ABSORB = [2]   # --absorb
+
+
+def amg_line(h):
+    return (f"{len(h['rows'])} levels, rows {' / '.join(str(r) for r in h['rows'])}, op. complexity {sum(h['nnz']) / h['nnz'][0]:.3f}, "
+            f"absorbed {h['absorbed']}")
 
 
 def elliptic(name, dim, nx, order, op, compare=capi.SOLVER_AUTO):
     nodes, cells, bnd = meshgen.unit_square(nx) if dim == 2 else meshgen.unit_cube(nx)
-    c = capi.Context(0)
-    c.mesh_upload(nodes, cells, bnd)
-    nd = c.dofs_build(order)
+    arms = {}
+    for absorb in ABSORB:
+        c = capi.Context(0)
+        c.mesh_upload(nodes, cells, bnd)
+        nd = c.dofs_build(order)
+        c.tune("amg_absorb", absorb)
+        c.set_operator(op)
+        c.set_forcing(np.ones(c.quadrature_nodes().shape[0]))
+        c.set_dirichlet(np.zeros(nd))
+        c.init()
+        arms[absorb] = c
     del nodes, cells
-    c.set_operator(op)
-    c.set_forcing(np.ones(c.quadrature_nodes().shape[0]))
-    c.set_dirichlet(np.zeros(nd))
-    c.init()
-    os.environ["FDAPDE_DEBUG_SETUP"] = "1"
-    try:
-        with CaptureStderr() as cap:
-            first, t_first = timed(lambda: c.solve(method=capi.SOLVER_AMG, raise_on_noconv=False))
-    finally:
-        del os.environ["FDAPDE_DEBUG_SETUP"]
-    second, t_second = timed(lambda: c.solve(method=capi.SOLVER_AMG, raise_on_noconv=False))
-    u = c.solution()
+    built, u = {}, None
+    for absorb, c in arms.items():
+        os.environ["FDAPDE_DEBUG_SETUP"] = "1"
+        try:
+            with CaptureStderr() as cap:
+                first, t_first = timed(lambda: c.solve(method=capi.SOLVER_AMG, raise_on_noconv=False))
+        except capi.FdapdeError as e:   # (a case the solver refuses is a result too)
+            print(f"{name:<34} {nd:>9} | amg_absorb {absorb} | refused: {e}", flush=True)
+            continue
+        finally:
+            del os.environ["FDAPDE_DEBUG_SETUP"]
+        _, t_second = timed(lambda: c.solve(method=capi.SOLVER_AMG, raise_on_noconv=False))
+        discarded = re.findall(r"discarded build ([\d.]+) ms", cap.text)
+        built[absorb] = (c.amg_hierarchy(), t_first - t_second, float(discarded[-1]) if discarded else 0.0)
+        u = c.solution()
+    times, last = {absorb: [] for absorb in built}, {}
+    for _ in range(5):   # the arms alternate
+        for absorb in built:
+            last[absorb], t = timed(lambda: arms[absorb].solve(method=capi.SOLVER_AMG, raise_on_noconv=False))
+            times[absorb].append(t)
+    c = next(iter(arms.values()))
     c.solve(method=compare, raise_on_noconv=False)   # (warm: its own layouts, the two-level solver's coarse level)
     other, t_other = timed(lambda: c.solve(method=compare, raise_on_noconv=False))
-    diff = np.linalg.norm(c.solution() - u) / max(np.linalg.norm(u), 1e-300)
-    c.close()
+    diff = np.linalg.norm(c.solution() - u) / max(np.linalg.norm(u), 1e-300) if u is not None else float("nan")
     cmp_name = {capi.SOLVER_AUTO: "open method", capi.SOLVER_PMG: "PMG"}[compare]
-    print(f"{name:<34} {nd:>9} | {amg_line(cap.text):<62} | set-up {t_first - t_second:8.1f} ms  solve {t_second:8.1f} ms  {second.iters:>4} it "
-          f"{'ok' if second.converged else 'NO CONV'} | {cmp_name} (method {other.method_used}) {t_other:8.1f} ms {other.iters:>5} it "
-          f"{'ok' if other.converged else 'NO CONV'} | rel. diff {diff:.1e}", flush=True)
+    for absorb, (h, t_setup, discarded) in built.items():
+        t, info = times[absorb], last[absorb]
+        print(f"{name:<34} {nd:>9} | amg_absorb {absorb} | {amg_line(h):<76} | set-up {t_setup:8.1f} ms (of it the discarded build {discarded:6.1f})  "
+              f"solve {np.median(t):8.1f} ms (smallest {min(t):.1f}, largest {max(t):.1f})  {info.iters:>4} it {'ok' if info.converged else 'NO CONV'}", flush=True)
+    print(f"{name:<34} {nd:>9} | {cmp_name} (method {other.method_used}) {t_other:8.1f} ms {other.iters:>5} it {'ok' if other.converged else 'NO CONV'} | "
+          f"rel. diff to the last multilevel arm {diff:.1e}", flush=True)
+    for c in arms.values():
+        c.close()
 
 
 def handle(nx, cols=8):
     nodes, cells, bnd = meshgen.unit_square(nx)
-    c = capi.Context(0)
-    c.mesh_upload(nodes, cells, bnd)
-    nd = c.dofs_build(1)
-    c.set_operator(-capi.laplacian() + capi.reaction(1.0))
-    c.set_forcing(np.ones(3 * cells.shape[0]))
-    c.init()
-    B = np.random.default_rng(3).standard_normal((nd, cols))
-    c.lin_compute(capi.MAT_STIFF)
-    (_, i1), t1 = timed(lambda: c.lin_solve(B[:, 0], method=capi.SOLVER_AMG))   # (builds the hierarchy)
-    (_, ia), ta = timed(lambda: c.lin_solve(B, method=capi.SOLVER_AMG))
-    c.lin_solve(B[:, 0])
-    (_, ib), tb = timed(lambda: c.lin_solve(B))
-    c.close()
-    print(f"{'handle, 2-D P1 -Lap + 1':<34} {nd:>9} | set-up + 1st column {t1:8.2f} ms | AMG {ta / cols:7.3f} ms per column ({ia.iters / cols:.1f} it) | "
-          f"existing handle path (method {ib.method_used}) {tb / cols:7.3f} ms per column", flush=True)
+    for absorb in ABSORB:   # (one arm after the other: every column is a solve of its own)
+        c = capi.Context(0)
+        c.mesh_upload(nodes, cells, bnd)
+        nd = c.dofs_build(1)
+        c.tune("amg_absorb", absorb)
+        c.set_operator(-capi.laplacian() + capi.reaction(1.0))
+        c.set_forcing(np.ones(3 * cells.shape[0]))
+        c.init()
+        B = np.random.default_rng(3).standard_normal((nd, cols))
+        c.lin_compute(capi.MAT_STIFF)
+        (_, i1), t1 = timed(lambda: c.lin_solve(B[:, 0], method=capi.SOLVER_AMG))   # (builds the hierarchy)
+        (_, ia), ta = timed(lambda: c.lin_solve(B, method=capi.SOLVER_AMG))
+        h = c.amg_hierarchy(capi.AMG_OF_HANDLE)
+        c.lin_solve(B[:, 0])
+        (_, ib), tb = timed(lambda: c.lin_solve(B))
+        c.close()
+        print(f"{'handle, 2-D P1 -Lap + 1':<34} {nd:>9} | amg_absorb {absorb} | {amg_line(h)} | set-up + 1st column {t1:8.2f} ms | AMG {ta / cols:7.3f} ms per column "
+              f"({ia.iters / cols:.1f} it) | existing handle path (method {ib.method_used}) {tb / cols:7.3f} ms per column", flush=True)
 
 
 CASES = {
@@ -116,9 +145,11 @@ CASES = {
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--cases", default="all")
+    ap.add_argument("--absorb", default="2")
     a = ap.parse_args()
+    ABSORB[:] = [int(v) for v in a.absorb.split(",")]
     names = list(CASES) if a.cases == "all" else a.cases.split(",")
-    print("case                                    DOFs | hierarchy | FDAPDE_SOLVER_AMG (set-up = first solve - second) | today's path | |u_amg - u_other| / |u_amg|")
+    print("case                                    DOFs | knob | hierarchy | FDAPDE_SOLVER_AMG (set-up = first solve - second; five solves) -- then today's path and |u_amg - u_other| / |u_amg|")
     for n in names:
         try:
             CASES[n]()

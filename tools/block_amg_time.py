@@ -4,8 +4,8 @@ had measured this before.
 
   * 2-D P1, unit_square(708): 502 681 DOFs; 3-D P1, unit_cube(118): 1 685 159 DOFs; observations at half of the nodes, lambda 1e-4 and 1e-2, rtol 1e-10.
   * per case: the hierarchy's rows per level (2 n_l) and set-up time (first BLOCK_AMG solve - second), then the host clock around one solve (it ends in a
-    stream synchronise) by FDAPDE_SOLVER_BLOCK_AMG and by FDAPDE_SOLVER_GMRES on the same handle in the same process, alternating, five times each -> median,
-    smallest, largest, and the iterations of each.  GMRES(50) is the stage the handle had before, untouched: the baseline.
+    stream synchronise) by FDAPDE_SOLVER_BLOCK_AMG under `amg_absorb` 0 and 1 (a context each) and by FDAPDE_SOLVER_GMRES in the same process, alternating,
+    five times each -> median, smallest, largest, and the iterations of each.  GMRES(50) is the stage the handle had before, untouched: the baseline.
   * --trace: the 2-D case, lambda 1e-4, one set-up and three solves, nothing else -- what a `rocprofv3 --kernel-trace --stats -- python tools/block_amg_time.py
     --trace` run wraps (the script does not start the profiler itself); --stats DIR OUT appends the top kernels of that run's *kernel_stats.csv to OUT.
 
@@ -15,10 +15,8 @@ usage: block_amg_time.py [OUT]      (OUT defaults to profiles/block_amg_time.txt
 import csv
 import glob
 import os
-import re
 import socket
 import sys
-import tempfile
 import time
 
 import numpy as np
@@ -45,11 +43,12 @@ def smoothing_blocks(c, capi, n_nodes, lam):
     return (a11, lam * r1, lam * r1, lam * r0), b, nd
 
 
-def space(capi, mesh):
+def space(capi, mesh, absorb=2):
     nodes, cells, bnd = mesh
     c = capi.Context(0)
     c.mesh_upload(nodes, cells, bnd)
     c.dofs_build(1)
+    c.tune("amg_absorb", absorb)
     c.set_operator(-capi.laplacian())
     c.set_forcing(np.zeros(c.quadrature_nodes().shape[0]))
     c.init()
@@ -66,51 +65,40 @@ def timed(fn):
     return r, 1e3 * (time.perf_counter() - t0)
 
 
-def with_setup_report(fn):
-    """fn() with FDAPDE_DEBUG_SETUP on and the process's stderr in a file -> (result, what the library wrote)"""
-    os.environ["FDAPDE_DEBUG_SETUP"] = "1"
-    sys.stderr.flush()
-    saved = os.dup(2)
-    with tempfile.TemporaryFile(mode="w+b") as tmp:
-        os.dup2(tmp.fileno(), 2)
+def case(capi, arms, n_nodes, lam, out):
+    """arms: {amg_absorb: context}; the GMRES stage runs on the first of them"""
+    amg, live = {}, {}
+    for absorb, c in arms.items():
+        blocks, b, nd = smoothing_blocks(c, capi, n_nodes, lam)
+        c.block_compute(*blocks, symmetric=True)
+        amg[absorb] = lambda c=c, b=b: c.block_solve(b, method=capi.SOLVER_BLOCK_AMG, rtol=1e-10, raise_on_noconv=False)
+    c0 = next(iter(arms.values()))
+    gm = lambda: c0.block_solve(b, method=capi.SOLVER_GMRES, rtol=1e-10, maxit=2000, raise_on_noconv=False)
+    out.append(f"  lambda {lam:g}:")
+    for absorb, c in arms.items():
         try:
-            r = fn()
-        finally:
-            os.dup2(saved, 2)
-            os.close(saved)
-            del os.environ["FDAPDE_DEBUG_SETUP"]
-        tmp.seek(0)
-        return r, tmp.read().decode(errors="replace")
-
-
-def case(capi, c, n_nodes, lam, out):
-    blocks, b, nd = smoothing_blocks(c, capi, n_nodes, lam)
-    c.block_compute(*blocks, symmetric=True)
-    amg = lambda: c.block_solve(b, method=capi.SOLVER_BLOCK_AMG, rtol=1e-10, raise_on_noconv=False)
-    gm = lambda: c.block_solve(b, method=capi.SOLVER_GMRES, rtol=1e-10, maxit=2000, raise_on_noconv=False)
-    try:
-        ((_, i_first), t_first), report = with_setup_report(lambda: timed(amg))
-    except capi.FdapdeError as e:   # (a refusal is a result too: the GMRES stage alone, then)
-        gm()
-        (_, i_gm), t = timed(gm)
-        out.append(f"  lambda {lam:g}: FDAPDE_SOLVER_BLOCK_AMG refused: {e}")
-        out.append(f"    FDAPDE_SOLVER_GMRES       {i_gm.iters} iterations, converged {i_gm.converged}, relres {i_gm.relres:.2e} (D^-1-scaled), {t:.1f} ms")
-        return
-    (_, i_amg), t_second = timed(amg)
-    rows = re.search(r"rows ([0-9 /]+),", report)
+            _, t_first = timed(amg[absorb])
+        except capi.FdapdeError as e:   # (a refusal is a result too)
+            out.append(f"    amg_absorb {absorb}: FDAPDE_SOLVER_BLOCK_AMG refused: {e}")
+            continue
+        _, t_second = timed(amg[absorb])
+        h = c.amg_hierarchy(capi.AMG_OF_BLOCK)
+        live[absorb] = f"rows per level {' / '.join(str(r) for r in h['rows'])}; set-up {t_first - t_second:.1f} ms (first solve {t_first:.1f} - second {t_second:.1f})"
     gm()   # (its buffers are allocated by the first call)
-    t_amg, t_gm, i_gm = [], [], None
+    t_amg, i_amg, t_gm, i_gm = {absorb: [] for absorb in live}, {}, [], None
     for _ in range(5):
-        (_, i_amg), t = timed(amg)
-        t_amg.append(t)
+        for absorb in live:
+            (_, i_amg[absorb]), t = timed(amg[absorb])
+            t_amg[absorb].append(t)
         (_, i_gm), t = timed(gm)
         t_gm.append(t)
-    out.append(f"  lambda {lam:g}: rows per level {rows.group(1).strip() if rows else '?'}; set-up {t_first - t_second:.1f} ms (first solve {t_first:.1f} - second {t_second:.1f})")
-    out.append(f"    FDAPDE_SOLVER_BLOCK_AMG   {i_amg.iters} iterations, converged {i_amg.converged}, relres {i_amg.relres:.2e} (unscaled), {spread(t_amg)}, "
-               f"{np.median(t_amg) / max(i_amg.iters, 1):.2f} ms per iteration")
+    for absorb in live:
+        i, t = i_amg[absorb], t_amg[absorb]
+        out.append(f"    amg_absorb {absorb}: {live[absorb]}")
+        out.append(f"      FDAPDE_SOLVER_BLOCK_AMG {i.iters} iterations, converged {i.converged}, relres {i.relres:.2e} (unscaled), {spread(t)}, "
+                   f"{np.median(t) / max(i.iters, 1):.2f} ms per iteration; against GMRES {np.median(t) / np.median(t_gm):.2f} x the time")
     out.append(f"    FDAPDE_SOLVER_GMRES       {i_gm.iters} iterations, converged {i_gm.converged}, relres {i_gm.relres:.2e} (D^-1-scaled), {spread(t_gm)}, "
                f"{np.median(t_gm) / max(i_gm.iters, 1):.2f} ms per iteration")
-    out.append(f"    BLOCK_AMG / GMRES         {np.median(t_amg) / np.median(t_gm):.2f} x the time, {i_amg.iters / max(i_gm.iters, 1):.2f} x the iterations")
 
 
 def append_stats(directory, out_path, top=10):
@@ -150,12 +138,17 @@ def main():
     out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "block_amg_time.txt")
     out = [f"tools/block_amg_time.py on {socket.gethostname()} (MI355X), {time.strftime('%Y-%m-%d %H:%M:%S')}", ""]
     for label, mesh in (("2-D P1, unit_square(708) (C2's size)", lambda: meshgen.unit_square(708)), ("3-D P1, unit_cube(118)", lambda: meshgen.unit_cube(118))):
-        c, n_nodes = space(capi, mesh())
-        out.append(f"{label}: {c.sizes()['n_dofs']} DOFs, 2 n = {2 * c.sizes()['n_dofs']}")
+        m = mesh()
+        arms = {absorb: space(capi, m, absorb)[0] for absorb in (0, 1)}
+        n_nodes = m[0].shape[0]
+        del m
+        out.append(f"{label}: {arms[0].sizes()['n_dofs']} DOFs, 2 n = {2 * arms[0].sizes()['n_dofs']}")
         for lam in (1e-4, 1e-2):
-            case(capi, c, n_nodes, lam, out)
-            print("\n".join(out[-4:]), flush=True)
-        c.close()
+            at = len(out)
+            case(capi, arms, n_nodes, lam, out)
+            print("\n".join(out[at:]), flush=True)
+        for c in arms.values():
+            c.close()
         out.append("")
     text = "\n".join(out)
     os.makedirs(os.path.dirname(out_path), exist_ok=True)
