@@ -51,7 +51,7 @@ SYMBOLS = [
     "fdapde_ctx_create_multi", "fdapde_ctx_devices", "fdapde_partition_build", "fdapde_partition_sizes", "fdapde_partition_get", "fdapde_partition_whole",
     "fdapde_partition_peers",
     "fdapde_block_compute", "fdapde_block_solve", "fdapde_block_spmv", "fdapde_block_bench_spmv", "fdapde_gram_pointwise",
-    "fdapde_amg_hierarchy",
+    "fdapde_amg_hierarchy", "fdapde_amg_aggregates",
 ]
 AMG_OF_SOLVE, AMG_OF_HANDLE, AMG_OF_BLOCK = 0, 1, 2   # `which` of fdapde_amg_hierarchy
 PARTITION_ROWDIST, PARTITION_ELEMENTS = 0, 1
@@ -630,6 +630,17 @@ class Context:
         self._check(self.lib.fdapde_amg_hierarchy(self._ctx, int(which), nl.value, C.byref(nl), rows.ctypes.data_as(C.POINTER(C.c_int64)),
                                                   nnz.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(ab), C.byref(ms)))
         return dict(rows=[int(r) for r in rows], nnz=[int(z) for z in nnz], absorbed=ab.value, setup_ms=ms.value)
+
+    def amg_aggregates(self, which, level):
+        """fdapde_amg_aggregates: for the block handle (which = 2) and a level that has a next one, the row of level + 1 every block row of `level` belongs
+        to (level 0 in the reference DOF numbering) -> int32 array.  FdapdeError(ENOTINIT) where no hierarchy is live, (EUNSUPPORTED) for which 0 / 1"""
+        n = C.c_int64(0)
+        rc = self.lib.fdapde_amg_aggregates(self._ctx, int(which), int(level), C.c_int64(0), None, C.byref(n))
+        if rc != EINVAL or n.value <= 0:   # (a valid level answers EINVAL to the empty buffer and leaves its row count)
+            self._check(rc)
+        agg = np.full(n.value, -1, dtype=np.int32)
+        self._check(self.lib.fdapde_amg_aggregates(self._ctx, int(which), int(level), C.c_int64(agg.size), _ip(agg), C.byref(n)))
+        return agg
 
     # ---- multi-GPU
     @staticmethod

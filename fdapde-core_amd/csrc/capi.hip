@@ -446,6 +446,16 @@ int fdapde_amg_hierarchy(fdapde_ctx* c, int32_t which, int32_t cap, int32_t* n_l
     return rc;
 }
 
+int fdapde_amg_aggregates(fdapde_ctx* c, int32_t which, int32_t level, int64_t cap, int32_t* agg, int64_t* n_rows) {
+    if (!c || which < 0 || which > 2) return FDAPDE_EINVAL;
+    if (c->group) return fail(c, FDAPDE_EUNSUPPORTED, "fdapde_amg_aggregates: one-device contexts only");
+    if (which != 2) return fail(c, FDAPDE_EUNSUPPORTED, "fdapde_amg_aggregates: only the block handle's hierarchy (which = 2) hands its aggregates out");
+    const int rc = fdapde_engine::block_amg_aggregates_ctx(c, level, cap, agg, n_rows);
+    if (rc == FDAPDE_ENOTINIT) return fail(c, rc, "fdapde_amg_aggregates: no block hierarchy is live (it is built by the first solve that names FDAPDE_SOLVER_BLOCK_AMG)");
+    if (rc == FDAPDE_EINVAL) return fail(c, rc, "fdapde_amg_aggregates: `level` must have a next level, and `agg` room for the level's block rows (`cap`)");
+    return rc;
+}
+
 int fdapde_info_get(const fdapde_ctx* c, fdapde_info* info) {
     if (!c || !info) return FDAPDE_EINVAL;
     *info = c->info;

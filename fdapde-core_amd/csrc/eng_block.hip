@@ -61,6 +61,9 @@ void block_amg_forget(fdapde_ctx* c) {
 int block_amg_describe_ctx(const fdapde_ctx* c, int32_t cap, int32_t* n_levels, int64_t* rows, int64_t* nnz, int32_t* absorbed, double* setup_ms) {
     return block_amg_describe(c->block ? c->block->amg : nullptr, cap, n_levels, rows, nnz, absorbed, setup_ms);
 }
+int block_amg_aggregates_ctx(fdapde_ctx* c, int32_t level, int64_t cap, int32_t* agg, int64_t* n_rows) {
+    return block_amg_aggregates(c, c->block ? c->block->amg : nullptr, level, cap, agg, n_rows);
+}
 
 namespace {
 

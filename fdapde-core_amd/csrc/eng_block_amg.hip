@@ -334,6 +334,27 @@ int block_amg_describe(const BlockAmg* H, int32_t cap, int32_t* n_levels, int64_
     return FDAPDE_OK;
 }
 
+// fdapde_amg_aggregates for the block handle: agg[i] = the row of level + 1 that block row i of `level` belongs to (level 0: i in the reference DOF
+// numbering, through dof_i2e; deeper levels in the level's own numbering).  The resident maps copied out, no kernel
+int block_amg_aggregates(fdapde_ctx* c, const BlockAmg* H, int32_t level, int64_t cap, int32_t* agg, int64_t* n_rows) {
+    if (!H) return FDAPDE_ENOTINIT;
+    if (level < 0 || (size_t)level + 1 >= H->lv.size()) return FDAPDE_EINVAL;
+    const BamgLevel& L = *H->lv[(size_t)level];
+    if (n_rows) *n_rows = L.n;
+    if (!agg || cap < L.n) return FDAPDE_EINVAL;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::vector<int32_t> own, i2e;
+    if (int rc = fetch(c, L.agg.p, (size_t)L.n, own)) return rc;
+    if (level > 0) {
+        std::copy(own.begin(), own.end(), agg);
+        return FDAPDE_OK;
+    }
+    if (int rc = fetch(c, c->dof_i2e.p, (size_t)L.n, i2e)) return rc;
+    for (int64_t i = 0; i < L.n; ++i) agg[i2e[(size_t)i]] = own[(size_t)i];
+    return FDAPDE_OK;
+}
+
 // one column: A x = b (both interleaved, internal order, on the device; x is written), raw = the matrix the hierarchy was built from
 int block_amg_run(fdapde_ctx* c, BlockAmg* hp, const double* raw, const double* b_dev, double* x_dev, double rtol, int maxit, int* iters, double* relres,
                   bool* converged_out, bool* broke_out) {

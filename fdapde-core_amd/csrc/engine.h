@@ -196,6 +196,7 @@ void preload_dense();
 void block_release(fdapde_ctx* c);
 void block_amg_forget(fdapde_ctx* c);   // the block handle's hierarchy is built again by its next solve (a set-up knob changed)
 int block_amg_describe_ctx(const fdapde_ctx* c, int32_t cap, int32_t* n_levels, int64_t* rows, int64_t* nnz, int32_t* absorbed, double* setup_ms);
+int block_amg_aggregates_ctx(fdapde_ctx* c, int32_t level, int64_t cap, int32_t* agg, int64_t* n_rows);
 int e_block_compute(fdapde_ctx* c, const double* a11, const double* a12, const double* a21, const double* a22, int32_t symmetric);
 int e_block_solve(fdapde_ctx* c, const fdapde_options* opt, const double* b, int32_t n_rhs, double* x, fdapde_info* info);
 int e_block_spmv(fdapde_ctx* c, const double* x, double* y);
@@ -208,6 +209,7 @@ struct BlockAmg;
 void block_amg_free(BlockAmg* h);
 int block_amg_build(fdapde_ctx* c, BlockAmg** slot, const double* raw, int strength_block);
 int block_amg_describe(const BlockAmg* h, int32_t cap, int32_t* n_levels, int64_t* rows, int64_t* nnz, int32_t* absorbed, double* setup_ms);   // rows: 2 n_l
+int block_amg_aggregates(fdapde_ctx* c, const BlockAmg* h, int32_t level, int64_t cap, int32_t* agg, int64_t* n_rows);   // fdapde_amg_aggregates, which 2
 int block_amg_run(fdapde_ctx* c, BlockAmg* h, const double* raw, const double* b_dev, double* x_dev, double rtol, int maxit, int* iters, double* relres,
                   bool* converged, bool* broke);
 

@@ -534,6 +534,13 @@ int fdapde_tune(fdapde_ctx *ctx, const char *key, int32_t value);
  * 2 n_l and 4 nnz_l); *absorbed: 1 if its passes absorbed the rows left single ("amg_absorb"); *setup_ms: host time of the set-up, the discarded
  * first build of "amg_absorb" 2 included.  Any output pointer may be NULL.  FDAPDE_ENOTINIT where no such hierarchy is live. */
 int fdapde_amg_hierarchy(fdapde_ctx *ctx, int32_t which, int32_t cap, int32_t *n_levels, int64_t *rows, int64_t *nnz, int32_t *absorbed, double *setup_ms);
+/* The aggregates of a live hierarchy as data (diagnostic, like fdapde_amg_hierarchy: what a test needs to restate everything numerical that is built on
+ * them).  which = 2, the block handle's, and level < *n_levels - 1 of fdapde_amg_hierarchy: agg[i] = the row of level + 1 that block row i of `level`
+ * belongs to, *n_rows = the level's block rows (rows[level] / 2).  Level 0 is given in the reference DOF numbering, deeper levels in the level's own row
+ * numbering.  cap: the room of agg in entries.  FDAPDE_ENOTINIT where no hierarchy is live; FDAPDE_EINVAL for a level outside that range, a NULL agg or
+ * cap < *n_rows (*n_rows is set where the level is valid); FDAPDE_EUNSUPPORTED for which = 0 and 1 (the scalar hierarchies do not hand theirs out) and
+ * for multi-device contexts. */
+int fdapde_amg_aggregates(fdapde_ctx *ctx, int32_t which, int32_t level, int64_t cap, int32_t *agg, int64_t *n_rows);
 /* the context's HIP stream (hipStream_t) so that callers can bracket work with their own events */
 void *fdapde_stream(fdapde_ctx *ctx);
 int fdapde_synchronize(fdapde_ctx *ctx);

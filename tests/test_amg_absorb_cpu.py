@@ -147,4 +147,10 @@ def test_the_query_is_exported_and_a_host_only_context_has_no_hierarchy():
     with pytest.raises(capi.FdapdeError) as e:
         c.amg_hierarchy(3)
     assert e.value.status == capi.EINVAL
+    # ... and fdapde_amg_aggregates likewise: no block hierarchy, the scalar ones do not hand theirs out, no fourth kind
+    assert "fdapde_amg_aggregates" in capi.SYMBOLS and hasattr(capi.load(), "fdapde_amg_aggregates")
+    for which, status in ((2, capi.ENOTINIT), (0, capi.EUNSUPPORTED), (1, capi.EUNSUPPORTED), (3, capi.EINVAL)):
+        with pytest.raises(capi.FdapdeError) as e:
+            c.amg_aggregates(which, 0)
+        assert e.value.status == status, which
     c.close()
