@@ -1,56 +1,103 @@
-// amg_setup.h -- the set-up passes of the aggregation hierarchies (eng_amg.hip), shared by FDAPDE_SOLVER_AMG and the block form of eng_block_amg.hip:
-// pairwise handshake matching (absorb: the rows it leaves single join the pair of their most strongly coupled paired neighbour -- aggregates of any size),
-// the Galerkin product of piecewise-constant P, the members of every aggregate -- on the device, and as the host loops
-// the knob amg_setup_check compares them with.
+// amg_setup.h -- what FDAPDE_SOLVER_AMG (eng_amg.hip) and the block form of eng_block_amg.hip share: a level, a hierarchy, the level step of the set-up
+// (pairwise handshake matching twice -- absorb: the rows it leaves single join the pair of their most strongly coupled paired neighbour --, the Galerkin
+// products of piecewise-constant P, the members of every aggregate; compared with the host loops of host_amg.cpp under the knob amg_setup_check), the
+// stall rule, the retry with absorption, and the K-cycle's recursion.
 #ifndef FDAPDE_AMG_SETUP_H
 #define FDAPDE_AMG_SETUP_H
 
+#include <chrono>
 #include <cstdint>
+#include <memory>
 #include <vector>
 
+#include "amg_rows.h"
 #include "context.h"
 
 namespace fdapde_engine {
+
+constexpr double kAmgStall = 0.8;   // a level that keeps more than this share of its rows ends the hierarchy (inverted if the dense limit allows: else unsupported)
 
 struct AmgLevel {
     int64_t n = 0, nnz = 0;
     DBuf<int32_t> rp_own, ci_own;
     DBuf<double> a_own;
     const int32_t *rp = nullptr, *ci = nullptr;   // level 0: the context's pattern and the caller's values; below: the level's own arrays
-    const double* a = nullptr;
+    const double* a = nullptr;                    // (the block form: the scalar strength matrix on the level's pattern)
     const uint8_t* excl = nullptr;                // rows that belong to no aggregate (level 0's Dirichlet DOFs)
     DBuf<double> dinv;
     double om = 0.0;
     int team = 4, np = 1;
     DBuf<int32_t> agg, mptr, midx;                // row -> row of the next level (-1: none); members of each next-level row, ascending
     DBuf<double> b, zt, cv, v, dv, w, rt, e, part, sc;   // work vectors (b: the restricted right-hand side; e: this level's correction)
+    virtual ~AmgLevel() = default;                // (the block form's levels carry their block values: eng_block_amg.hip)
 };
 
-
-struct HostCsr {
-    int64_t n = 0;
-    std::vector<int32_t> rp, ci;
-    std::vector<double> a;
-};
-// what dev_galerkin sorted: entry e of the m sorted ones has key keys[e] and fine slot idx[e]; head[e] = 1 where a coarse entry starts, pos[e] its slot
-struct AmgGalerkinMap {
-    DBuf<uint64_t> keys;
-    DBuf<int32_t> idx, head, pos;
-    int64_t m = 0;
-    uint64_t nc = 0;
+struct AmgHierarchy;
+// the launches of a cycle that differ between the two solvers (L: the level, N: the next one)
+struct AmgCycleOps {
+    void (*pre_restrict)(hipStream_t st, AmgLevel& L, AmgLevel& N, const double* r);              // L.zt = the smoothed r, N.b = the restricted residual
+    void (*post)(hipStream_t st, AmgLevel& L, AmgLevel& N, const double* r, double* out);         // out = L.zt + P N.e, smoothed once more
+    void (*spmv_dots)(hipStream_t st, AmgLevel& L, const double* x, double* y, const double* p0, const double* q0, const double* p1, const double* q1,
+                      const double* p2, const double* q2);                                        // y = A x, L.part = the partials of p_q . q_q
 };
 
-void host_pairwise(const HostCsr& A, const uint8_t* excl, int absorb, std::vector<int32_t>& agg, int32_t& nc);
-void host_galerkin(const HostCsr& A, const std::vector<int32_t>& agg, int32_t nc, HostCsr& C);
-int dev_pairwise(fdapde_ctx* c, int64_t n, int64_t nnz, const int32_t* rp, const int32_t* ci, const double* a, const uint8_t* excl, int absorb, DBuf<int32_t>& agg,
-                 int32_t* nc);
-int dev_galerkin(fdapde_ctx* c, int64_t n, int64_t nnz, const int32_t* rp, const int32_t* ci, const double* a, const int32_t* agg, int32_t nc, AmgLevel& out,
-                 AmgGalerkinMap* keep = nullptr);
-int dev_members(fdapde_ctx* c, int64_t n, const int32_t* agg, int32_t nc, DBuf<int32_t>& mptr, DBuf<int32_t>& midx);
-// the K-cycle's scalar helpers (k_amg_coef, k_amg_axpy_sc, k_amg_comb2) on vectors of any length
-void amg_launch_coef(hipStream_t st, const double* part, int np, int stage, double* sc);
-void amg_launch_axpy_sc(hipStream_t st, int64_t n, const double* b, const double* v, const double* sc, double* rt);
-void amg_launch_comb2(hipStream_t st, int64_t n, const double* cv, const double* dv, const double* sc, double* e);
+struct AmgHierarchy {
+    std::vector<std::unique_ptr<AmgLevel>> lv;
+    fdapde_ctx::Dense D;                          // the coarsest level's inverse
+    const AmgCycleOps* ops = nullptr;
+    int per = 1;                                  // rows per node: vectors hold per * n_l words (the block form: 2, interleaved)
+    bool sym = true;                              // the coarse corrections are flexible CG steps (false: GCR)
+    int use_bnd = 0;
+    const double* A = nullptr;
+    int64_t key = -1;
+    double setup_ms = 0.0, op_complexity = 0.0;
+    int absorbed = 0;                             // its passes absorbed the rows the matching left single (knob amg_absorb)
+    double discarded_ms = 0.0;                    // amg_absorb 2: what the build without absorption cost before it stalled (part of setup_ms)
+    DBuf<double> vec, basis, part, dots;          // the outer iteration's vectors and flexible GMRES basis
+    int np = 1, mk = 0;
+    virtual ~AmgHierarchy() { D.X.release(); }
+};
+
+inline unsigned gn(int64_t n) { return (unsigned)((n + 255) / 256); }
+template <typename T> int fetch(fdapde_ctx* c, const T* p, size_t n, std::vector<T>& h) {
+    h.resize(n);
+    if (n) HIPCHK(c, hipMemcpy(h.data(), p, sizeof(T) * n, hipMemcpyDeviceToHost));
+    return FDAPDE_OK;
+}
+
+// what a level step leaves besides the fine level's agg / mptr / midx and the coarse level
+struct AmgCoarse {
+    DBuf<int32_t> agg1, agg2;   // row -> pair-graph row (-1: excluded), pair-graph row -> coarse row
+    int32_t n1 = 0, n2 = 0;
+    AmgLevel T;                 // the pair graph: the Galerkin matrix of pass 1
+    DBuf<double> payT;          // the payload on its entries
+};
+enum AmgVerdict { kAmgNext, kAmgEnd, kAmgStalled, kAmgNoFreeRows };
+// One level step on the device.  F: the fine level (pattern, strength values F.a, F.excl or NULL); pay: `width` doubles per entry that follow the strength
+// values through both Galerkin products, or NULL.  Pass 1 on F, pass 2 on the pair graph K.T: aggregates of at most four rows (any size if absorb).  Out:
+// K, the coarse level N with payN, and F.agg / F.mptr / F.midx.  n1 == 0 (every row excluded): only K.agg1 is built.
+int amg_coarsen(fdapde_ctx* c, AmgLevel& F, int absorb, const double* pay, int width, AmgCoarse& K, AmgLevel& N, DBuf<double>* payN);
+// amg_coarsen, the comparison with host_coarsen under amg_setup_check (errors as "amg_setup_check: <tag>level <level>: ..."), and the stall rule: a step that
+// keeps more than kAmgStall of F's rows (and more than coarse_rows) ends the hierarchy at F -- kAmgEnd, F.agg / mptr / midx released -- unless F is above
+// dense_limit: kAmgStalled.  All three counts in rows, per of them to a node.  kAmgNoFreeRows: n1 == 0
+int amg_next_level(fdapde_ctx* c, AmgLevel& F, int absorb, const double* pay, int width, int per, int64_t coarse_rows, int64_t dense_limit, const char* tag,
+                   size_t level, AmgLevel& N, DBuf<double>* payN, AmgVerdict* verdict);
+// The knob amg_absorb around a build `pass(absorb, &stalled)` that leaves its hierarchy in *slot: 0 pairs only, 1 absorbs on every level, 2 pairs only and --
+// where that ends in the stall refusal -- builds again from level 0 with absorption on every level, the first attempt booked under discarded_ms
+template <typename H, typename Pass> int amg_build_retry(fdapde_ctx* c, H** slot, Pass&& pass) {
+    const auto t0 = std::chrono::steady_clock::now();
+    bool stalled = false;
+    int rc = pass(c->amg_absorb == 1 ? 1 : 0, &stalled);
+    if (rc != FDAPDE_OK && stalled && c->amg_absorb == 2) {
+        const double first = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        rc = pass(1, &stalled);
+        if (rc == FDAPDE_OK) (*slot)->discarded_ms = first, (*slot)->setup_ms += first;
+    }
+    return rc;
+}
+// out = the cycle of level l on r (l < coarsest): smoothing, the coarse correction -- below the finest level two flexible CG / GCR steps around the next
+// level's cycle (the K-cycle), the dense inverse on the last level --, smoothing
+int amg_cycle(fdapde_ctx* c, AmgHierarchy& H, size_t l, const double* r, double* out);
 
 }   // namespace fdapde_engine
 #endif

@@ -36,6 +36,7 @@
 #include "context.h"
 #include "amg_setup.h"
 #include "engine.h"
+#include "kernels_dense.h"
 #include "kernels_reduce.h"
 
 namespace fdapde_engine {
@@ -43,112 +44,7 @@ namespace fdapde_engine {
 namespace {
 using namespace fdapde_hip;
 
-constexpr double kAmgTheta = 0.25;   // strength threshold of a coupling, relative to the row's strongest
-constexpr int kAmgRounds = 10;       // handshake rounds per pairwise pass ...
-constexpr int kAmgStrongRounds = 3;  // ... the first of them on strong couplings only
-constexpr double kAmgStall = 0.8;    // a level that keeps more than this share of its rows ends the hierarchy (inverted if the dense limit allows: else unsupported)
-constexpr int kMateFree = -1, kMateExcluded = -2;
-constexpr int64_t kAmgMaxCoarse = 8192;   // the dense inverse's limit (kernels_dense.h kDenseMaxRows)
-
-inline unsigned gn(int64_t n) { return (unsigned)((n + 255) / 256); }
-
-// ---- set-up kernels (one thread per row: a set-up pass, not a hot path) ----
-// the coupling of (i, j) in the symmetric part, as a positive number for an M-matrix entry: -(a_ij + a_ji) -- a_ji looked up even where the matrix is
-// symmetric (an assembled a_ji need not carry a_ij's last bit): the same word from both ends, which the matching's order of the edges relies on
-__device__ __host__ inline double amg_sym_coupling(const int32_t* rp, const int32_t* ci, const double* a, int32_t k, int32_t i, int32_t j) {
-    double at = 0.0;
-    for (int32_t q = rp[j]; q < rp[j + 1]; ++q)
-        if (ci[q] == i) {
-            at = a[q];
-            break;
-        }
-    return -(a[k] + at);
-}
-// sw[k] = the strength of entry k: > 0 a strong coupling, < 0 (minus its strength) a weak one, 0 none (the diagonal, excluded rows and columns)
-__device__ __host__ inline void amg_strength_row(int64_t i, const int32_t* rp, const int32_t* ci, const double* a, const uint8_t* excl, double* sw) {
-    const int32_t b = rp[i], e = rp[i + 1];
-    if (excl && excl[i]) {
-        for (int32_t k = b; k < e; ++k) sw[k] = 0.0;
-        return;
-    }
-    double mneg = 0.0, mabs = 0.0;
-    for (int32_t k = b; k < e; ++k) {
-        const int32_t j = ci[k];
-        if (j == (int32_t)i || (excl && excl[j])) continue;
-        const double s = amg_sym_coupling(rp, ci, a, k, (int32_t)i, j);
-        mneg = s > mneg ? s : mneg;
-        const double sa = s < 0.0 ? -s : s;
-        mabs = sa > mabs ? sa : mabs;
-    }
-    const bool neg = mneg > 0.0;
-    const double thr = kAmgTheta * (neg ? mneg : mabs);
-    for (int32_t k = b; k < e; ++k) {
-        const int32_t j = ci[k];
-        double w = 0.0;
-        if (j != (int32_t)i && !(excl && excl[j]) && (neg || mabs > 0.0)) {
-            const double s = amg_sym_coupling(rp, ci, a, k, (int32_t)i, j);
-            const double v = neg ? s : (s < 0.0 ? -s : s);
-            if (v > 0.0) w = v >= thr ? v : -v;   // (negative: a weak coupling, for the relaxed rounds)
-        }
-        sw[k] = w;
-    }
-}
-// a tie between equally strong couplings is broken by a hash of the index pair -- the same word from both ends: a total order on the edges, so that a
-// coupling that is the best of both its ends is proposed from both (breaking ties by the smaller index alone pairs almost nothing on a uniform stencil:
-// every node proposes to its smallest neighbour, which proposes further down)
-__device__ __host__ inline uint32_t amg_pair_hash(int32_t i, int32_t j) {
-    const uint32_t lo = (uint32_t)(i < j ? i : j), hi = (uint32_t)(i < j ? j : i);
-    uint64_t z = ((uint64_t)hi << 32 | lo) * 0x9E3779B97F4A7C15ull;
-    z ^= z >> 29, z *= 0xBF58476D1CE4E5B9ull, z ^= z >> 32;
-    return (uint32_t)z;
-}
-// relaxed (the rounds from kAmgStrongRounds on): weak couplings count too -- a node whose strong neighbours have all been taken pairs along a weaker one
-// instead of staying single (3-D P1 -Lap, the 250 k interior rows of unit_cube(64): strong couplings only, every round, stalled at 3 829 rows four levels down)
-__device__ __host__ inline int32_t amg_propose_row(int64_t i, const int32_t* rp, const int32_t* ci, const double* sw, const int32_t* mate, int relaxed) {
-    if (mate[i] != kMateFree) return -1;
-    int32_t best = -1;
-    double bw = 0.0;
-    uint32_t bh = 0;
-    for (int32_t k = rp[i]; k < rp[i + 1]; ++k) {
-        const int32_t j = ci[k];
-        const double w = relaxed ? (sw[k] < 0.0 ? -sw[k] : sw[k]) : sw[k];
-        if (!(w > 0.0) || j == (int32_t)i || mate[j] != kMateFree) continue;
-        const uint32_t h = amg_pair_hash((int32_t)i, j);
-        if (w > bw || (w == bw && (h > bh || (h == bh && j < best)))) bw = w, bh = h, best = j;
-    }
-    return best;
-}
-// absorption, after the last round (mate as it left it: no order of execution matters): a row still free picks the PAIRED neighbour it is most strongly coupled
-// to -- amg_propose_row's relaxed comparison with "paired" in place of "free" -- and joins that pair's aggregate; -1: none (not free, or no paired neighbour)
-__device__ __host__ inline int32_t amg_absorb_row(int64_t i, const int32_t* rp, const int32_t* ci, const double* sw, const int32_t* mate) {
-    if (mate[i] != kMateFree) return -1;
-    int32_t best = -1;
-    double bw = 0.0;
-    uint32_t bh = 0;
-    for (int32_t k = rp[i]; k < rp[i + 1]; ++k) {
-        const int32_t j = ci[k];
-        const double w = sw[k] < 0.0 ? -sw[k] : sw[k];
-        if (!(w > 0.0) || j == (int32_t)i || mate[j] < 0) continue;
-        const uint32_t h = amg_pair_hash((int32_t)i, j);
-        if (w > bw || (w == bw && (h > bh || (h == bh && j < best)))) bw = w, bh = h, best = j;
-    }
-    return best;
-}
-// host: what amg_absorb_row chose per row, or NULL (a pass that does not absorb).  A row with a host leads no aggregate; hosts are paired rows: no chains
-__device__ __host__ inline bool amg_leader(int64_t i, const int32_t* mate, const int32_t* host) {
-    if (host && host[i] >= 0) return false;
-    return mate[i] == kMateFree || (mate[i] >= 0 && (int64_t)mate[i] > i);
-}
-__device__ __host__ inline int32_t amg_aggregate_of(int64_t i, const int32_t* mate, const int32_t* host, const int32_t* id) {
-    const int32_t m = mate[i];
-    if (m == kMateExcluded) return -1;
-    if (host && host[i] >= 0) {
-        const int32_t h = host[i], hm = mate[h];
-        return id[h < hm ? h : hm];
-    }
-    return amg_leader(i, mate, host) ? id[i] : id[m];
-}
-
+// ---- set-up kernels (one thread per row: a set-up pass, not a hot path; the row rules are amg_rows.h's) ----
 __global__ void k_amg_init_mate(int64_t n, const uint8_t* excl, int32_t* mate) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) mate[i] = (excl && excl[i]) ? kMateExcluded : kMateFree;
@@ -211,6 +107,19 @@ __global__ void k_amg_gsum(int64_t m, const uint64_t* keys, const int32_t* idx, 
     const uint64_t row = key / nc;
     a_c[p] = s, ci_c[p] = (int32_t)(key - row * nc);
     if (e == 0 || keys[e - 1] / nc != row) rp_c[row] = p;
+}
+// ... and the payload of the block form, four doubles per entry, summed over the same fine entries in the same order
+__global__ void k_bamg_gsum(int64_t m, const uint64_t* keys, const int32_t* idx, const int32_t* head, const int32_t* pos, const double* bv, double* bv_c) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= m || !head[e]) return;
+    const uint64_t key = keys[e];
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    for (int64_t q = e; q < m && keys[q] == key; ++q) {
+        const double* v = bv + 4 * (int64_t)idx[q];
+        s0 += v[0], s1 += v[1], s2 += v[2], s3 += v[3];
+    }
+    double* o = bv_c + 4 * (int64_t)pos[e];
+    o[0] = s0, o[1] = s1, o[2] = s2, o[3] = s3;
 }
 // members of every aggregate, ascending: keys agg(i) (nc for none), sorted stably with the row index
 __global__ void k_amg_mkeys(int64_t n, const int32_t* agg, uint32_t nc, uint32_t* keys, int32_t* idx) {
@@ -399,89 +308,12 @@ template <typename F> void by_team(int T, F&& f) {
     else if (T <= 8) f(std::integral_constant<int, 8>{});
     else f(std::integral_constant<int, 16>{});
 }
-}   // namespace
-
-struct AmgHierarchy {
-    std::vector<std::unique_ptr<AmgLevel>> lv;
-    fdapde_ctx::Dense D;                          // the coarsest level's inverse
-    bool sym = true;
-    int use_bnd = 0;
-    const double* A = nullptr;
-    int64_t key = -1;
-    double setup_ms = 0.0, op_complexity = 0.0;
-    int absorbed = 0;                             // its passes absorbed the rows the matching left single (knob amg_absorb)
-    double discarded_ms = 0.0;                    // amg_absorb 2: what the build without absorption cost before it stalled (part of setup_ms)
-    DBuf<double> vec, basis, part, dots;          // the outer iteration's vectors (x, r, t) and flexible GMRES basis
-    int np = 1, mk = 0;
-    ~AmgHierarchy() {
-        D.X.release();
-        for (auto& l : lv)
-            for (DBuf<double>* p : {&l->a_own, &l->dinv, &l->b, &l->zt, &l->cv, &l->v, &l->dv, &l->w, &l->rt, &l->e, &l->part, &l->sc}) p->release();
-    }
-};
-
-// ---- the host loops of the same set-up (knob amg_setup_check): the same arithmetic in the same order (declared in amg_setup.h) ----
-void host_pairwise(const HostCsr& A, const uint8_t* excl, int absorb, std::vector<int32_t>& agg, int32_t& nc) {
-    const int64_t n = A.n;
-    std::vector<double> sw(A.a.size());
-    for (int64_t i = 0; i < n; ++i) amg_strength_row(i, A.rp.data(), A.ci.data(), A.a.data(), excl, sw.data());
-    std::vector<int32_t> mate((size_t)n), prop((size_t)n);
-    for (int64_t i = 0; i < n; ++i) mate[(size_t)i] = (excl && excl[i]) ? kMateExcluded : kMateFree;
-    for (int round = 0; round < kAmgRounds; ++round) {
-        for (int64_t i = 0; i < n; ++i) prop[(size_t)i] = amg_propose_row(i, A.rp.data(), A.ci.data(), sw.data(), mate.data(), round >= kAmgStrongRounds ? 1 : 0);
-        for (int64_t i = 0; i < n; ++i) {
-            if (mate[(size_t)i] != kMateFree) continue;
-            const int32_t j = prop[(size_t)i];
-            if (j >= 0 && prop[(size_t)j] == (int32_t)i) mate[(size_t)i] = j;
-        }
-    }
-    std::vector<int32_t> host_of;
-    if (absorb) {
-        host_of.resize((size_t)n);
-        for (int64_t i = 0; i < n; ++i) host_of[(size_t)i] = amg_absorb_row(i, A.rp.data(), A.ci.data(), sw.data(), mate.data());
-    }
-    const int32_t* host = absorb ? host_of.data() : nullptr;
-    std::vector<int32_t> id((size_t)n);
-    nc = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        id[(size_t)i] = nc;
-        nc += amg_leader(i, mate.data(), host) ? 1 : 0;
-    }
-    agg.assign((size_t)n, -1);
-    for (int64_t i = 0; i < n; ++i) agg[(size_t)i] = amg_aggregate_of(i, mate.data(), host, id.data());
-}
-void host_galerkin(const HostCsr& A, const std::vector<int32_t>& agg, int32_t nc, HostCsr& C) {
-    std::vector<std::pair<uint64_t, int32_t>> ent;
-    for (int64_t i = 0; i < A.n; ++i)
-        for (int32_t k = A.rp[(size_t)i]; k < A.rp[(size_t)i + 1]; ++k) {
-            const int32_t ai = agg[(size_t)i], aj = agg[(size_t)A.ci[(size_t)k]];
-            if (ai >= 0 && aj >= 0) ent.emplace_back((uint64_t)ai * (uint64_t)nc + (uint64_t)aj, k);
-        }
-    std::stable_sort(ent.begin(), ent.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
-    C.n = nc, C.rp.assign((size_t)nc + 1, 0), C.ci.clear(), C.a.clear();
-    for (size_t e = 0; e < ent.size();) {
-        const uint64_t key = ent[e].first;
-        double s = 0.0;
-        for (; e < ent.size() && ent[e].first == key; ++e) s += A.a[(size_t)ent[e].second];
-        const uint64_t row = key / (uint64_t)nc;
-        C.ci.push_back((int32_t)(key - row * (uint64_t)nc)), C.a.push_back(s), ++C.rp[(size_t)row + 1];
-    }
-    for (int32_t r = 0; r < nc; ++r) C.rp[(size_t)r + 1] += C.rp[(size_t)r];
-}
-namespace {
 template <typename T> bool same_dev(const T* p, size_t n, const std::vector<T>& h) {
     if (h.size() != n) return false;
     std::vector<T> g(n);
     if (n && hipMemcpy(g.data(), p, sizeof(T) * n, hipMemcpyDeviceToHost) != hipSuccess) return false;
     return n == 0 || std::memcmp(g.data(), h.data(), sizeof(T) * n) == 0;
 }
-template <typename T> int fetch(fdapde_ctx* c, const T* p, size_t n, std::vector<T>& h) {
-    h.resize(n);
-    if (n) HIPCHK(c, hipMemcpy(h.data(), p, sizeof(T) * n, hipMemcpyDeviceToHost));
-    return FDAPDE_OK;
-}
-
-}   // namespace
 
 // one pairwise pass on the device (absorb: followed by the absorption of the rows it left single): agg (n words), *nc
 int dev_pairwise(fdapde_ctx* c, int64_t n, int64_t nnz, const int32_t* rp, const int32_t* ci, const double* a, const uint8_t* excl, int absorb, DBuf<int32_t>& agg,
@@ -519,18 +351,17 @@ int dev_pairwise(fdapde_ctx* c, int64_t n, int64_t nnz, const int32_t* rp, const
     HIPCHK(c, hipStreamSynchronize(st));
     return FDAPDE_OK;
 }
-namespace {
 inline int key_bits(uint64_t v) {
     int b = 1;
     while (b < 64 && (v >> b) != 0) ++b;
     return b;
 }
-}   // namespace
 
-// the Galerkin product P^T A P of piecewise-constant P (agg) on the device: a stable key sort, a segmented sum in ascending fine-slot order
-// (keep: the sorted keys and slots stay with the caller, who sums further values per coarse entry in the same order -- eng_block_amg.hip)
+// the Galerkin product P^T A P of piecewise-constant P (agg) on the device: a stable key sort, a segmented sum in ascending fine-slot order.  pay (or
+// NULL): the block form's four doubles per entry, summed per coarse entry over the same sorted slots into pay_c
 int dev_galerkin(fdapde_ctx* c, int64_t n, int64_t nnz, const int32_t* rp, const int32_t* ci, const double* a, const int32_t* agg, int32_t nc, AmgLevel& out,
-                 AmgGalerkinMap* keep) {
+                 const double* pay, int width, DBuf<double>* pay_c) {
+    if (pay && width != 4) return fail(c, FDAPDE_EINVAL, "dev_galerkin: the device sums payloads of four doubles per entry only");
     hipStream_t st = c->stream;
     const dim3 bv(256);
     const uint64_t ncu = (uint64_t)nc, sentinel = ncu * ncu;
@@ -560,18 +391,13 @@ int dev_galerkin(fdapde_ctx* c, int64_t n, int64_t nnz, const int32_t* rp, const
     HIPCHK(c, out.rp_own.alloc((size_t)nc + 1));
     HIPCHK(c, out.ci_own.alloc((size_t)std::max(nnz_c, 1)));
     HIPCHK(c, out.a_own.alloc((size_t)std::max(nnz_c, 1) + 2));
+    if (pay) HIPCHK(c, pay_c->alloc(4 * (size_t)std::max(nnz_c, 1)));
     HIPCHK(c, hipMemcpyAsync(out.rp_own.p + nc, &nnz_c, sizeof(int32_t), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_amg_gsum, dim3(gn(nnz)), bv, 0, st, nnz, keys_s.p, idx_s.p, a, head.p, pos.p, ncu, out.rp_own.p, out.ci_own.p, out.a_own.p);
+    if (pay) hipLaunchKernelGGL(k_bamg_gsum, dim3(gn(nnz)), bv, 0, st, nnz, keys_s.p, idx_s.p, head.p, pos.p, pay, pay_c->p);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(st));   // (nnz_c is this frame's; the scratch goes out of scope)
     out.rp = out.rp_own.p, out.ci = out.ci_own.p, out.a = out.a_own.p;
-    if (keep) {
-        std::swap(keep->keys.p, keys_s.p), std::swap(keep->keys.n, keys_s.n);
-        std::swap(keep->idx.p, idx_s.p), std::swap(keep->idx.n, idx_s.n);
-        std::swap(keep->head.p, head.p), std::swap(keep->head.n, head.n);
-        std::swap(keep->pos.p, pos.p), std::swap(keep->pos.n, pos.n);
-        keep->m = nnz, keep->nc = ncu;
-    }
     return FDAPDE_OK;
 }
 // members of each aggregate (CSR, ascending row index)
@@ -597,6 +423,71 @@ int dev_members(fdapde_ctx* c, int64_t n, const int32_t* agg, int32_t nc, DBuf<i
     HIPCHK(c, hipStreamSynchronize(st));
     return FDAPDE_OK;
 }
+// the level step of F by the host loops (host_amg.cpp), compared bit for bit with what amg_coarsen built
+int amg_check_level(fdapde_ctx* c, const AmgLevel& F, int absorb, const double* pay, int width, const char* tag, size_t level, const AmgCoarse& K, const AmgLevel& N,
+                    const DBuf<double>* payN) {
+    HostCsr hf;
+    std::vector<uint8_t> excl;
+    std::vector<double> hpay;
+    hf.n = F.n;
+    if (int rc = fetch(c, F.rp, (size_t)F.n + 1, hf.rp)) return rc;
+    if (int rc = fetch(c, F.ci, (size_t)F.nnz, hf.ci)) return rc;
+    if (int rc = fetch(c, F.a, (size_t)F.nnz, hf.a)) return rc;
+    if (F.excl)
+        if (int rc = fetch(c, F.excl, (size_t)F.n, excl)) return rc;
+    if (pay)
+        if (int rc = fetch(c, pay, (size_t)width * (size_t)F.nnz, hpay)) return rc;
+    HostCoarse h;
+    host_coarsen(hf, F.excl ? excl.data() : nullptr, absorb, pay ? hpay.data() : nullptr, width, h);
+    const std::string vals = pay ? " strength values" : " values";
+    std::string which;
+    if (h.n1 != K.n1 || !same_dev(K.agg1.p, (size_t)F.n, h.agg1)) which += " pass-1 aggregates";
+    if (h.n2 != K.n2 || (h.n1 == K.n1 && !same_dev(K.agg2.p, (size_t)K.n1, h.agg2))) which += " pass-2 aggregates";
+    if (which.empty()) {
+        if (!same_dev(K.T.rp, (size_t)K.n1 + 1, h.T.rp) || !same_dev(K.T.ci, (size_t)K.T.nnz, h.T.ci)) which += " pair-graph pattern";
+        else if (!same_dev(K.T.a, (size_t)K.T.nnz, h.T.a)) which += " pair-graph" + vals;
+        else if (pay && !same_dev(K.payT.p, (size_t)width * (size_t)K.T.nnz, h.payT)) which += " pair-graph block values";
+        if (!same_dev(N.rp, (size_t)K.n2 + 1, h.N.rp) || !same_dev(N.ci, (size_t)N.nnz, h.N.ci)) which += " coarse pattern";
+        else if (!same_dev(N.a, (size_t)N.nnz, h.N.a)) which += " coarse" + vals;
+        else if (pay && !same_dev(payN->p, (size_t)width * (size_t)N.nnz, h.payN)) which += " coarse block values";
+        if (!same_dev(F.agg.p, (size_t)F.n, h.agg)) which += " composite aggregates";
+        if (!same_dev(F.mptr.p, (size_t)K.n2 + 1, h.mptr) || !same_dev(F.midx.p, h.midx.size(), h.midx)) which += " members";
+    }
+    if (which.empty()) return FDAPDE_OK;
+    c->err = std::string("amg_setup_check: ") + tag + "level " + std::to_string(level) + ": the device-built hierarchy differs from the host-built one:" + which;
+    return FDAPDE_EHIP;
+}
+}   // namespace
+
+int amg_coarsen(fdapde_ctx* c, AmgLevel& F, int absorb, const double* pay, int width, AmgCoarse& K, AmgLevel& N, DBuf<double>* payN) {
+    if (int rc = dev_pairwise(c, F.n, F.nnz, F.rp, F.ci, F.a, F.excl, absorb, K.agg1, &K.n1)) return rc;
+    if (K.n1 == 0) return FDAPDE_OK;
+    AmgLevel& T = K.T;
+    if (int rc = dev_galerkin(c, F.n, F.nnz, F.rp, F.ci, F.a, K.agg1.p, K.n1, T, pay, width, &K.payT)) return rc;
+    if (int rc = dev_pairwise(c, T.n, T.nnz, T.rp, T.ci, T.a, nullptr, absorb, K.agg2, &K.n2)) return rc;
+    if (int rc = dev_galerkin(c, T.n, T.nnz, T.rp, T.ci, T.a, K.agg2.p, K.n2, N, pay ? K.payT.p : nullptr, width, payN)) return rc;
+    HIPCHK(c, F.agg.alloc((size_t)F.n));
+    hipLaunchKernelGGL(k_amg_compose, dim3(gn(F.n)), dim3(256), 0, c->stream, F.n, K.agg1.p, K.agg2.p, F.agg.p);
+    HIPCHK(c, hipGetLastError());
+    return dev_members(c, F.n, F.agg.p, K.n2, F.mptr, F.midx);
+}
+
+int amg_next_level(fdapde_ctx* c, AmgLevel& F, int absorb, const double* pay, int width, int per, int64_t coarse_rows, int64_t dense_limit, const char* tag,
+                   size_t level, AmgLevel& N, DBuf<double>* payN, AmgVerdict* verdict) {
+    AmgCoarse K;
+    if (int rc = amg_coarsen(c, F, absorb, pay, width, K, N, payN)) return rc;
+    *verdict = kAmgNoFreeRows;
+    if (K.n1 == 0) return FDAPDE_OK;
+    if (c->amg_setup_check)
+        if (int rc = amg_check_level(c, F, absorb, pay, width, tag, level, K, N, payN)) return rc;
+    *verdict = kAmgNext;
+    if ((double)K.n2 > kAmgStall * (double)F.n && per * (int64_t)K.n2 > coarse_rows) {   // coarsening stalled: a level the dense inverse takes ends the hierarchy
+        *verdict = per * F.n > dense_limit ? kAmgStalled : kAmgEnd;
+        F.agg.release(), F.mptr.release(), F.midx.release();
+    }
+    return FDAPDE_OK;
+}
+
 namespace {
 // D^-1, the Jacobi damping 1.5 / lambda_max(D^-1 A) (15 power iterations), team width and work vectors of a level
 int level_prepare(fdapde_ctx* c, AmgLevel& L, bool has_next) {
@@ -657,83 +548,53 @@ void amg_release(fdapde_ctx* c) {
 }
 
 namespace {
+// the scalar cycle's launches: damped Jacobi (L.om D^-1) as the smoother
+void scalar_pre_restrict(hipStream_t st, AmgLevel& L, AmgLevel& N, const double* r) {
+    by_team(L.team, [&](auto t) {
+        constexpr int T = decltype(t)::value;
+        hipLaunchKernelGGL(k_amg_pre_restrict<T>, dim3(gn(N.n * T)), dim3(256), 0, st, N.n, L.mptr.p, L.midx.p, L.rp, L.ci, L.a, L.dinv.p, L.om, r, L.zt.p, N.b.p);
+    });
+}
+void scalar_post(hipStream_t st, AmgLevel& L, AmgLevel& N, const double* r, double* out) {
+    by_team(L.team, [&](auto t) {
+        constexpr int T = decltype(t)::value;
+        hipLaunchKernelGGL(k_amg_post<T>, dim3(gn(L.n * T)), dim3(256), 0, st, L.n, L.rp, L.ci, L.a, L.dinv.p, L.om, L.agg.p, N.e.p, r, L.zt.p, out);
+    });
+}
+void scalar_spmv_dots(hipStream_t st, AmgLevel& L, const double* x, double* y, const double* p0, const double* q0, const double* p1, const double* q1, const double* p2,
+                      const double* q2) {
+    by_team(L.team, [&](auto t) {
+        constexpr int T = decltype(t)::value;
+        hipLaunchKernelGGL(k_amg_spmv_dots<T>, dim3((unsigned)L.np), dim3(256), 0, st, L.n, L.rp, L.ci, L.a, x, y, p0, q0, p1, q1, p2, q2, L.part.p);
+    });
+}
+constexpr AmgCycleOps kScalarOps{scalar_pre_restrict, scalar_post, scalar_spmv_dots};
+
 // the hierarchy of A with (absorb) or without absorption on every level; *stalled: the answer is the "coarsening stalled above the dense limit" refusal
 int amg_build_pass(fdapde_ctx* c, AmgHierarchy** slot, const double* A, int use_bnd, bool symmetric, int absorb, bool* stalled) {
     *stalled = false;
     const auto t0 = std::chrono::steady_clock::now();
     std::unique_ptr<AmgHierarchy> H(new AmgHierarchy());
-    H->sym = symmetric, H->use_bnd = use_bnd, H->A = A, H->absorbed = absorb;
-    const int64_t coarse_rows = std::max<int64_t>(1, std::min<int64_t>(c->amg_coarse_rows, kAmgMaxCoarse));
+    H->ops = &kScalarOps, H->sym = symmetric, H->use_bnd = use_bnd, H->A = A, H->absorbed = absorb;
+    const int64_t coarse_rows = std::max<int64_t>(1, std::min<int64_t>(c->amg_coarse_rows, kDenseMaxRows));
     {
         std::unique_ptr<AmgLevel> L0(new AmgLevel());
         L0->n = c->hs.n_dofs, L0->nnz = c->hs.nnz, L0->rp = c->rowptr.p, L0->ci = c->colidx.p, L0->a = A, L0->excl = use_bnd ? c->bnd.p : nullptr;
         H->lv.push_back(std::move(L0));
     }
-    std::vector<uint8_t> excl_h;
-    if (c->amg_setup_check && use_bnd) {
-        if (int rc = fetch(c, c->bnd.p, (size_t)c->hs.n_dofs, excl_h)) return rc;
-    }
     while (H->lv.back()->n > coarse_rows) {
         AmgLevel& F = *H->lv.back();
-        // pass 1 on the level, pass 2 on the Galerkin matrix of pass 1 (the pair graph): aggregates of at most four rows
-        DBuf<int32_t> agg1, agg2;
-        int32_t n1 = 0, n2 = 0;
-        if (int rc = dev_pairwise(c, F.n, F.nnz, F.rp, F.ci, F.a, F.excl, absorb, agg1, &n1)) return rc;
-        if (n1 == 0) return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_AMG: a level above the dense limit has no free rows to aggregate");
-        AmgLevel T;
-        if (int rc = dev_galerkin(c, F.n, F.nnz, F.rp, F.ci, F.a, agg1.p, n1, T)) return rc;
-        if (int rc = dev_pairwise(c, T.n, T.nnz, T.rp, T.ci, T.a, nullptr, absorb, agg2, &n2)) return rc;
         std::unique_ptr<AmgLevel> N(new AmgLevel());
-        if (int rc = dev_galerkin(c, T.n, T.nnz, T.rp, T.ci, T.a, agg2.p, n2, *N)) return rc;
-        HIPCHK(c, F.agg.alloc((size_t)F.n));
-        hipLaunchKernelGGL(k_amg_compose, dim3(gn(F.n)), dim3(256), 0, c->stream, F.n, agg1.p, agg2.p, F.agg.p);
-        if (int rc = dev_members(c, F.n, F.agg.p, n2, F.mptr, F.midx)) return rc;
-        if (c->amg_setup_check) {   // the same level by the host loops, compared bit for bit
-            HostCsr hf, ht, hn;
-            hf.n = F.n;
-            if (int rc = fetch(c, F.rp, (size_t)F.n + 1, hf.rp)) return rc;
-            if (int rc = fetch(c, F.ci, (size_t)F.nnz, hf.ci)) return rc;
-            if (int rc = fetch(c, F.a, (size_t)F.nnz, hf.a)) return rc;
-            std::vector<int32_t> a1, a2, comp((size_t)F.n), mptr((size_t)n2 + 1, 0), midx;
-            int32_t m1 = 0, m2 = 0;
-            host_pairwise(hf, H->lv.size() == 1 && use_bnd ? excl_h.data() : nullptr, absorb, a1, m1);
-            host_galerkin(hf, a1, m1, ht);
-            host_pairwise(ht, nullptr, absorb, a2, m2);
-            host_galerkin(ht, a2, m2, hn);
-            for (int64_t i = 0; i < F.n; ++i) comp[(size_t)i] = a1[(size_t)i] < 0 ? -1 : a2[(size_t)a1[(size_t)i]];
-            for (int64_t i = 0; i < F.n; ++i)
-                if (comp[(size_t)i] >= 0) ++mptr[(size_t)comp[(size_t)i] + 1];
-            for (int32_t q = 0; q < m2; ++q) mptr[(size_t)q + 1] += mptr[(size_t)q];
-            midx.resize((size_t)mptr[(size_t)m2]);
-            {
-                std::vector<int32_t> fill(mptr.begin(), mptr.end() - 1);
-                for (int64_t i = 0; i < F.n; ++i)
-                    if (comp[(size_t)i] >= 0) midx[(size_t)fill[(size_t)comp[(size_t)i]]++] = (int32_t)i;
-            }
-            std::string which;
-            if (m1 != n1 || !same_dev(agg1.p, (size_t)F.n, a1)) which += " pass-1 aggregates";
-            if (m2 != n2 || (m1 == n1 && !same_dev(agg2.p, (size_t)n1, a2))) which += " pass-2 aggregates";
-            if (which.empty()) {
-                if (!same_dev(T.rp, (size_t)n1 + 1, ht.rp) || !same_dev(T.ci, (size_t)T.nnz, ht.ci)) which += " pair-graph pattern";
-                else if (!same_dev(T.a, (size_t)T.nnz, ht.a)) which += " pair-graph values";
-                if (!same_dev(N->rp, (size_t)n2 + 1, hn.rp) || !same_dev(N->ci, (size_t)N->nnz, hn.ci)) which += " coarse pattern";
-                else if (!same_dev(N->a, (size_t)N->nnz, hn.a)) which += " coarse values";
-                if (!same_dev(F.agg.p, (size_t)F.n, comp)) which += " composite aggregates";
-                if (!same_dev(F.mptr.p, (size_t)n2 + 1, mptr) || !same_dev(F.midx.p, midx.size(), midx)) which += " members";
-            }
-            if (!which.empty()) {
-                c->err = "amg_setup_check: level " + std::to_string(H->lv.size() - 1) + ": the device-built hierarchy differs from the host-built one:" + which;
-                return FDAPDE_EHIP;
-            }
+        AmgVerdict verdict;
+        // (the dense limit: this solver refuses a stalled level above kDenseMaxRows whatever the knob dense_rows says; the block form of eng_block_amg.hip
+        // above min(dense_rows, kDenseMaxRows), counted in 2 n -- two rules nobody has decided between, hence a parameter)
+        if (int rc = amg_next_level(c, F, absorb, nullptr, 0, 1, coarse_rows, kDenseMaxRows, "", H->lv.size() - 1, *N, nullptr, &verdict)) return rc;
+        if (verdict == kAmgNoFreeRows) return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_AMG: a level above the dense limit has no free rows to aggregate");
+        if (verdict == kAmgStalled) {
+            *stalled = true;
+            return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_AMG: coarsening stalled above the dense limit (a level kept more than 0.8 of its rows): the matrix has too few strong couplings for pairwise aggregation");
         }
-        if ((double)n2 > kAmgStall * (double)F.n && n2 > coarse_rows) {   // coarsening stalled: a level the dense inverse takes ends the hierarchy
-            if (F.n > kAmgMaxCoarse) {
-                *stalled = true;
-                return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_AMG: coarsening stalled above the dense limit (a level kept more than 0.8 of its rows): the matrix has too few strong couplings for pairwise aggregation");
-            }
-            F.agg.release(), F.mptr.release(), F.midx.release();
-            break;
-        }
+        if (verdict == kAmgEnd) break;
         H->lv.push_back(std::move(N));
     }
     double nnz_all = 0.0;
@@ -753,30 +614,21 @@ int amg_build_pass(fdapde_ctx* c, AmgHierarchy** slot, const double* A, int use_
 }
 }   // namespace
 
-// the hierarchy of A (the context's pattern, internal order); use_bnd: level 0's Dirichlet DOFs (c->bnd) belong to no aggregate.  Knob amg_absorb: 0 pairs
-// only, 1 absorbs on every level, 2 pairs only and -- where that ends in the stall refusal -- builds again from level 0 with absorption on every level
+// the hierarchy of A (the context's pattern, internal order); use_bnd: level 0's Dirichlet DOFs (c->bnd) belong to no aggregate.  Knob amg_absorb: amg_build_retry
 int amg_build(fdapde_ctx* c, AmgHierarchy** slot, const double* A, int use_bnd, bool symmetric) {
     delete *slot;
     *slot = nullptr;
     HIPCHK(c, hipSetDevice(c->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    bool stalled = false;
-    int rc = amg_build_pass(c, slot, A, use_bnd, symmetric, c->amg_absorb == 1 ? 1 : 0, &stalled);
-    if (rc != FDAPDE_OK && stalled && c->amg_absorb == 2) {
-        const double first = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        rc = amg_build_pass(c, slot, A, use_bnd, symmetric, 1, &stalled);
-        if (rc == FDAPDE_OK) (*slot)->discarded_ms = first, (*slot)->setup_ms += first;
-    }
-    return rc;
+    return amg_build_retry(c, slot, [&](int absorb, bool* stalled) { return amg_build_pass(c, slot, A, use_bnd, symmetric, absorb, stalled); });
 }
 
-// fdapde_amg_hierarchy for a scalar hierarchy: rows and entries per level
+// fdapde_amg_hierarchy: rows and entries per level, counted in scalar unknowns (H->per of them to a node)
 int amg_describe(const AmgHierarchy* H, int32_t cap, int32_t* n_levels, int64_t* rows, int64_t* nnz, int32_t* absorbed, double* setup_ms) {
     if (!H) return FDAPDE_ENOTINIT;
     if (n_levels) *n_levels = (int32_t)H->lv.size();
     for (size_t l = 0; l < H->lv.size() && (int64_t)l < (int64_t)cap; ++l) {
-        if (rows) rows[l] = H->lv[l]->n;
-        if (nnz) nnz[l] = H->lv[l]->nnz;
+        if (rows) rows[l] = H->per * H->lv[l]->n;
+        if (nnz) nnz[l] = H->per * H->per * H->lv[l]->nnz;
     }
     if (absorbed) *absorbed = H->absorbed;
     if (setup_ms) *setup_ms = H->setup_ms;
@@ -784,51 +636,37 @@ int amg_describe(const AmgHierarchy* H, int32_t cap, int32_t* n_levels, int64_t*
 }
 
 namespace {
-// e_m = (level m's system)^-1 b_m approximately: the dense inverse on the coarsest level, two flexible CG / GCR steps around the cycle elsewhere
-int amg_correction(fdapde_ctx* c, AmgHierarchy& H, size_t m);
-// out = the cycle of level l on r (l < coarsest): Jacobi, the coarse correction, Jacobi
-int amg_cycle(fdapde_ctx* c, AmgHierarchy& H, size_t l, const double* r, double* out) {
-    hipStream_t st = c->stream;
-    AmgLevel& L = *H.lv[l];
-    AmgLevel& N = *H.lv[l + 1];
-    by_team(L.team, [&](auto t) {
-        constexpr int T = decltype(t)::value;
-        hipLaunchKernelGGL(k_amg_pre_restrict<T>, dim3(gn(N.n * T)), dim3(256), 0, st, N.n, L.mptr.p, L.midx.p, L.rp, L.ci, L.a, L.dinv.p, L.om, r, L.zt.p, N.b.p);
-    });
-    if (int rc = amg_correction(c, H, l + 1)) return rc;
-    by_team(L.team, [&](auto t) {
-        constexpr int T = decltype(t)::value;
-        hipLaunchKernelGGL(k_amg_post<T>, dim3(gn(L.n * T)), dim3(256), 0, st, L.n, L.rp, L.ci, L.a, L.dinv.p, L.om, L.agg.p, N.e.p, r, L.zt.p, out);
-    });
-    return FDAPDE_OK;
-}
+// e_m = (level m's system)^-1 b_m approximately: the dense inverse on the coarsest level, two flexible CG / GCR steps around the cycle elsewhere.  The dots
+// k_amg_coef reads, (p0.q0, p1.q1[, p2.q2]): flexible CG c.v, c.b then d.v, d.w, d.rt; GCR v.v, v.b then v.w, w.w, w.rt
 int amg_correction(fdapde_ctx* c, AmgHierarchy& H, size_t m) {
     hipStream_t st = c->stream;
     AmgLevel& L = *H.lv[m];
     if (m + 1 == H.lv.size()) return dense_apply(c, H.D, 1, L.b.p, L.e.p);
-    const int64_t n = L.n;
-    const bool fcg = H.sym;
-    auto spmv_dots = [&](const double* x, double* y, const double* p0, const double* q0, const double* p1, const double* q1, const double* p2, const double* q2) {
-        by_team(L.team, [&](auto t) {
-            constexpr int T = decltype(t)::value;
-            hipLaunchKernelGGL(k_amg_spmv_dots<T>, dim3((unsigned)L.np), dim3(256), 0, st, n, L.rp, L.ci, L.a, x, y, p0, q0, p1, q1, p2, q2, L.part.p);
-        });
-    };
+    const int64_t n = H.per * L.n;
+    double *b = L.b.p, *cv = L.cv.p, *v = L.v.p, *rt = L.rt.p, *dv = L.dv.p, *w = L.w.p;
     // step 1: c = B b, v = A c
-    if (int rc = amg_cycle(c, H, m, L.b.p, L.cv.p)) return rc;
-    if (fcg) spmv_dots(L.cv.p, L.v.p, L.cv.p, L.v.p, L.cv.p, L.b.p, nullptr, nullptr);
-    else spmv_dots(L.cv.p, L.v.p, L.v.p, L.v.p, L.v.p, L.b.p, nullptr, nullptr);
+    if (int rc = amg_cycle(c, H, m, b, cv)) return rc;
+    if (H.sym) H.ops->spmv_dots(st, L, cv, v, cv, v, cv, b, nullptr, nullptr);
+    else H.ops->spmv_dots(st, L, cv, v, v, v, v, b, nullptr, nullptr);
     hipLaunchKernelGGL(k_amg_coef, dim3(1), dim3(256), 0, st, L.part.p, L.np, 1, L.sc.p);
-    hipLaunchKernelGGL(k_amg_axpy_sc, dim3(gn(n)), dim3(256), 0, st, n, L.b.p, L.v.p, L.sc.p, L.rt.p);
+    hipLaunchKernelGGL(k_amg_axpy_sc, dim3(gn(n)), dim3(256), 0, st, n, b, v, L.sc.p, rt);
     // step 2: d = B rt, w = A d
-    if (int rc = amg_cycle(c, H, m, L.rt.p, L.dv.p)) return rc;
-    if (fcg) spmv_dots(L.dv.p, L.w.p, L.dv.p, L.v.p, L.dv.p, L.w.p, L.dv.p, L.rt.p);
-    else spmv_dots(L.dv.p, L.w.p, L.v.p, L.w.p, L.w.p, L.w.p, L.w.p, L.rt.p);
+    if (int rc = amg_cycle(c, H, m, rt, dv)) return rc;
+    if (H.sym) H.ops->spmv_dots(st, L, dv, w, dv, v, dv, w, dv, rt);
+    else H.ops->spmv_dots(st, L, dv, w, v, w, w, w, w, rt);
     hipLaunchKernelGGL(k_amg_coef, dim3(1), dim3(256), 0, st, L.part.p, L.np, 2, L.sc.p);
-    hipLaunchKernelGGL(k_amg_comb2, dim3(gn(n)), dim3(256), 0, st, n, L.cv.p, L.dv.p, L.sc.p, L.e.p);
+    hipLaunchKernelGGL(k_amg_comb2, dim3(gn(n)), dim3(256), 0, st, n, cv, dv, L.sc.p, L.e.p);
     return FDAPDE_OK;
 }
 }   // namespace
+
+int amg_cycle(fdapde_ctx* c, AmgHierarchy& H, size_t l, const double* r, double* out) {
+    AmgLevel &L = *H.lv[l], &N = *H.lv[l + 1];
+    H.ops->pre_restrict(c->stream, L, N, r);
+    if (int rc = amg_correction(c, H, l + 1)) return rc;
+    H.ops->post(c->stream, L, N, r, out);
+    return FDAPDE_OK;
+}
 
 int amg_run(fdapde_ctx* c, AmgHierarchy* hp, const double* A, const double* f_dev, const double* g_dev, int use_bnd, const double* x0_dev, double rtol, int maxit) {
     AmgHierarchy& H = *hp;
@@ -940,15 +778,6 @@ int e_solve_amg(fdapde_ctx* c, const fdapde_options* opt, fdapde_info* info) {
     c->solved = true, c->dirichlet_applied = c->have_g;
     if (info) *info = c->info;
     return rc;
-}
-
-// the K-cycle's helpers on vectors of any length (the block cycle of eng_block_amg.hip runs them on 2 n_l words)
-void amg_launch_coef(hipStream_t st, const double* part, int np, int stage, double* sc) { hipLaunchKernelGGL(k_amg_coef, dim3(1), dim3(256), 0, st, part, np, stage, sc); }
-void amg_launch_axpy_sc(hipStream_t st, int64_t n, const double* b, const double* v, const double* sc, double* rt) {
-    hipLaunchKernelGGL(k_amg_axpy_sc, dim3(gn(n)), dim3(256), 0, st, n, b, v, sc, rt);
-}
-void amg_launch_comb2(hipStream_t st, int64_t n, const double* cv, const double* dv, const double* sc, double* e) {
-    hipLaunchKernelGGL(k_amg_comb2, dim3(gn(n)), dim3(256), 0, st, n, cv, dv, sc, e);
 }
 
 void amg_forget(fdapde_ctx* c) {

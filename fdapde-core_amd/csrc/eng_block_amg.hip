@@ -6,12 +6,12 @@
 // FDAPDE_SOLVER_AMG (eng_amg.hip) with the two unknowns of a DOF kept together does not.
 //
 // What:
-//   set-up    level 0 is the handle's unscaled block CSR.  The aggregates come from eng_amg.hip's two pairwise passes (dev_pairwise, with its absorption of
-//             the rows left single under the knob amg_absorb) on a SCALAR
-//             strength matrix on the same pattern: the (2,1) block as given -- (1,2), (2,2), (1,1) where it was NULL --, whose Galerkin product
-//             (dev_galerkin) is the next level's pattern and strength matrix.  The four block values of a coarse entry are summed with the same keys in
-//             ascending fine-slot order (k_bamg_gsum): P = P_scalar (x) I_2, unknowns interleaved on every level, no float atomics.  Levels until one has
-//             at most `amg_coarse_rows` rows (counted in 2 n_l); that one goes through k_block_expand + dense_build_csr.
+//   set-up    level 0 is the handle's unscaled block CSR.  The aggregates come from eng_amg.hip's level step (amg_next_level: two pairwise passes, with
+//             their absorption of the rows left single under the knob amg_absorb) on a SCALAR strength matrix on the same pattern: the (2,1) block as
+//             given -- (1,2), (2,2), (1,1) where it was NULL --, whose Galerkin product is the next level's pattern and strength matrix.  The four block
+//             values ride along as the step's payload: summed per coarse entry with the same keys in ascending fine-slot order (k_bamg_gsum):
+//             P = P_scalar (x) I_2, unknowns interleaved on every level, no float atomics.  Levels until one has at most `amg_coarse_rows` rows (counted
+//             in 2 n_l); that one goes through k_block_expand + dense_build_csr.
 //   cycle     0.7 D^-1 (D the 2 x 2 diagonal blocks), the coarse correction, 0.7 D^-1 (kernels_block.h k_bamg_*).  Below the finest level the coarse
 //             correction is always two GCR steps preconditioned by the next level's cycle -- GCR because the system is indefinite (flexible CG may divide
 //             by zero), no early exit (it would need a host read-back inside the cycle).
@@ -36,72 +36,27 @@ namespace {
 using namespace fdapde_hip;
 
 constexpr double kBamgOmega = 0.7;   // the smoother's damping: fixed (the spectrum of D^-1 A is not one-sided: no power iteration)
-constexpr double kBamgStall = 0.8;   // a level that keeps more than this share of its rows ends the hierarchy
 constexpr int kBamgMaxRestart = 64;  // fgmres_outer's Gram-Schmidt kernels hold that many coefficients
 
-struct BamgLevel {
-    int64_t n = 0, nnz = 0;                       // block rows, pattern entries
-    AmgLevel S;                                   // the scalar strength matrix on the level's pattern (level 0: the context's pattern, own values)
-    const int32_t *rp = nullptr, *ci = nullptr;
+// a level: the scalar level (n block rows; a = the strength matrix on the pattern; agg, mptr, midx; team, np; the work vectors at 2 n words) and its blocks
+struct BamgLevel : AmgLevel {
     const double* bv = nullptr;                   // four doubles per entry (level 0: the handle's)
-    DBuf<double> bv_own, dinv;
-    int team = 8, np = 1;
-    DBuf<int32_t> agg, mptr, midx;                // row -> row of the next level; members of each next-level row, ascending
-    DBuf<double> b, zt, cv, v, dv, w, rt, e, part, sc;
+    DBuf<double> bv_own, dinv4;                   // (dinv4: the inverted 2 x 2 diagonal blocks, four doubles per row)
 };
+inline BamgLevel& blk(AmgLevel& L) { return static_cast<BamgLevel&>(L); }
 }   // namespace
 
-struct BlockAmg {
-    std::vector<std::unique_ptr<BamgLevel>> lv;
-    fdapde_ctx::Dense D;                          // the coarsest level's inverse (2 n_L rows)
+struct BlockAmg : AmgHierarchy {   // (D: 2 n_L rows; the coarse corrections are GCR steps)
     DBuf<int32_t> rp2, ci2;
     DBuf<double> val2;
-    DBuf<double> vec, basis, part, dots;          // the outer iteration's x, r, t, b and the flexible GMRES basis
-    double setup_ms = 0.0, discarded_ms = 0.0;    // (discarded_ms: amg_absorb 2, the build without absorption that stalled -- part of setup_ms)
-    int absorbed = 0;
-    ~BlockAmg() { D.X.release(); }
 };
 
 void block_amg_free(BlockAmg* h) { delete h; }
 
 namespace {
-inline unsigned gn(int64_t n) { return (unsigned)((n + 255) / 256); }
-
 template <typename F> void by_team(int T, F&& f) {
     if (T <= 8) f(std::integral_constant<int, 8>{});
     else f(std::integral_constant<int, 16>{});
-}
-
-template <typename T> int fetch(fdapde_ctx* c, const T* p, size_t n, std::vector<T>& h) {
-    h.resize(n);
-    if (n) HIPCHK(c, hipMemcpy(h.data(), p, sizeof(T) * n, hipMemcpyDeviceToHost));
-    return FDAPDE_OK;
-}
-
-// the block values of P^T A P by the host loops: host_galerkin's keys and order (eng_amg.hip), four sums per coarse entry
-void host_block_galerkin(const HostCsr& A, const std::vector<double>& bv, const std::vector<int32_t>& agg, int32_t nc, std::vector<double>& out) {
-    std::vector<std::pair<uint64_t, int32_t>> ent;
-    for (int64_t i = 0; i < A.n; ++i)
-        for (int32_t k = A.rp[(size_t)i]; k < A.rp[(size_t)i + 1]; ++k)
-            ent.emplace_back((uint64_t)agg[(size_t)i] * (uint64_t)nc + (uint64_t)agg[(size_t)A.ci[(size_t)k]], k);
-    std::stable_sort(ent.begin(), ent.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
-    out.clear();
-    for (size_t e = 0; e < ent.size();) {
-        const uint64_t key = ent[e].first;
-        double s[4] = {0.0, 0.0, 0.0, 0.0};
-        for (; e < ent.size() && ent[e].first == key; ++e)
-            for (int q = 0; q < 4; ++q) s[q] += bv[4 * (size_t)ent[e].second + q];
-        out.insert(out.end(), s, s + 4);
-    }
-}
-
-// the block values of the coarse entries dev_galerkin just formed (map: what it sorted)
-int block_galerkin(fdapde_ctx* c, const AmgGalerkinMap& map, const double* bv, int64_t nnz_c, DBuf<double>& out) {
-    HIPCHK(c, out.alloc(4 * (size_t)std::max<int64_t>(nnz_c, 1)));
-    hipLaunchKernelGGL(k_bamg_gsum, dim3(gn(map.m)), dim3(256), 0, c->stream, map.m, map.keys.p, map.idx.p, map.head.p, map.pos.p, bv, out.p);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));   // (the map is the caller's local)
-    return FDAPDE_OK;
 }
 
 // D^-1 of a level's diagonal blocks (today's 1e-14 rule: k_block_diag_inv); *bad: a block was singular
@@ -110,8 +65,8 @@ int level_dinv(fdapde_ctx* c, BamgLevel& L, bool* bad) {
     DBuf<int32_t> flag;
     HIPCHK(c, flag.alloc(1));
     HIPCHK(c, hipMemsetAsync(flag.p, 0, sizeof(int32_t), st));
-    HIPCHK(c, L.dinv.alloc(4 * (size_t)L.n));
-    hipLaunchKernelGGL(k_block_diag_inv, dim3(gn(L.n)), dim3(256), 0, st, L.n, L.rp, L.ci, L.bv, L.dinv.p, flag.p);
+    HIPCHK(c, L.dinv4.alloc(4 * (size_t)L.n));
+    hipLaunchKernelGGL(k_block_diag_inv, dim3(gn(L.n)), dim3(256), 0, st, L.n, L.rp, L.ci, L.bv, L.dinv4.p, flag.p);
     HIPCHK(c, hipGetLastError());
     int32_t h = 0;
     HIPCHK(c, hipMemcpyAsync(&h, flag.p, sizeof h, hipMemcpyDeviceToHost, st));
@@ -120,7 +75,7 @@ int level_dinv(fdapde_ctx* c, BamgLevel& L, bool* bad) {
     return FDAPDE_OK;
 }
 
-int level_vectors(fdapde_ctx* c, BamgLevel& L) {
+int level_vectors(fdapde_ctx* c, AmgLevel& L) {
     const size_t n2 = 2 * (size_t)std::max<int64_t>(L.n, 1);
     const double per_row = L.n > 0 ? (double)L.nnz / (double)L.n : 1.0;
     L.team = per_row <= 12.0 ? 8 : 16;
@@ -132,160 +87,80 @@ int level_vectors(fdapde_ctx* c, BamgLevel& L) {
     return FDAPDE_OK;
 }
 
-int bamg_correction(fdapde_ctx* c, BlockAmg& H, size_t m);
-// out = the cycle of level l on r (l < coarsest)
-int bamg_cycle(fdapde_ctx* c, BlockAmg& H, size_t l, const double* r, double* out) {
-    hipStream_t st = c->stream;
-    BamgLevel& L = *H.lv[l];
-    BamgLevel& N = *H.lv[l + 1];
+// the block cycle's launches: 0.7 D^-1 with the 2 x 2 diagonal blocks as the smoother (kernels_block.h)
+void block_pre_restrict(hipStream_t st, AmgLevel& L, AmgLevel& N, const double* r) {
     by_team(L.team, [&](auto t) {
         constexpr int T = decltype(t)::value;
-        hipLaunchKernelGGL(k_bamg_pre_restrict<T>, dim3(g1(N.n, 256 / T)), dim3(256), 0, st, N.n, L.mptr.p, L.midx.p, L.rp, L.ci, L.bv, L.dinv.p, kBamgOmega, r, L.zt.p,
-                           N.b.p, (const int32_t*)nullptr);
+        hipLaunchKernelGGL(k_bamg_pre_restrict<T>, dim3(g1(N.n, 256 / T)), dim3(256), 0, st, N.n, L.mptr.p, L.midx.p, L.rp, L.ci, blk(L).bv, blk(L).dinv4.p, kBamgOmega, r,
+                           L.zt.p, N.b.p, (const int32_t*)nullptr);
     });
-    if (int rc = bamg_correction(c, H, l + 1)) return rc;
+}
+void block_post(hipStream_t st, AmgLevel& L, AmgLevel& N, const double* r, double* out) {
     by_team(L.team, [&](auto t) {
         constexpr int T = decltype(t)::value;
-        hipLaunchKernelGGL(k_bamg_post<T>, dim3(g1(L.n, 256 / T)), dim3(256), 0, st, L.n, L.rp, L.ci, L.bv, L.dinv.p, kBamgOmega, L.agg.p, N.e.p, r, L.zt.p, out,
+        hipLaunchKernelGGL(k_bamg_post<T>, dim3(g1(L.n, 256 / T)), dim3(256), 0, st, L.n, L.rp, L.ci, blk(L).bv, blk(L).dinv4.p, kBamgOmega, L.agg.p, N.e.p, r, L.zt.p, out,
                            (const int32_t*)nullptr);
     });
-    return FDAPDE_OK;
 }
-// e_m = (level m's matrix)^-1 b_m approximately: the dense inverse on the coarsest level, two GCR steps around the cycle elsewhere (k_amg_coef's GCR
-// reading: rho1 = v.v, alpha1 = v.b; gamma = v.w, rho2 = w.w - gamma^2 / rho1, alpha2 = w.rt)
-int bamg_correction(fdapde_ctx* c, BlockAmg& H, size_t m) {
-    hipStream_t st = c->stream;
-    BamgLevel& L = *H.lv[m];
-    if (m + 1 == H.lv.size()) return dense_apply(c, H.D, 1, L.b.p, L.e.p);
-    const int64_t n = L.n;
-    auto spmv_dots = [&](const double* x, double* y, const double* p0, const double* q0, const double* p1, const double* q1, const double* p2, const double* q2) {
-        by_team(L.team, [&](auto t) {
-            constexpr int T = decltype(t)::value;
-            hipLaunchKernelGGL(k_bamg_spmv_dots<T>, dim3((unsigned)L.np), dim3(256), 0, st, n, L.rp, L.ci, L.bv, x, y, p0, q0, p1, q1, p2, q2, L.part.p,
-                               (const int32_t*)nullptr);
-        });
-    };
-    if (int rc = bamg_cycle(c, H, m, L.b.p, L.cv.p)) return rc;   // c = B b, v = A c
-    spmv_dots(L.cv.p, L.v.p, L.v.p, L.v.p, L.v.p, L.b.p, nullptr, nullptr);
-    amg_launch_coef(st, L.part.p, L.np, 1, L.sc.p);
-    amg_launch_axpy_sc(st, 2 * n, L.b.p, L.v.p, L.sc.p, L.rt.p);
-    if (int rc = bamg_cycle(c, H, m, L.rt.p, L.dv.p)) return rc;  // d = B rt, w = A d
-    spmv_dots(L.dv.p, L.w.p, L.v.p, L.w.p, L.w.p, L.w.p, L.w.p, L.rt.p);
-    amg_launch_coef(st, L.part.p, L.np, 2, L.sc.p);
-    amg_launch_comb2(st, 2 * n, L.cv.p, L.dv.p, L.sc.p, L.e.p);
-    return FDAPDE_OK;
+void block_spmv_dots(hipStream_t st, AmgLevel& L, const double* x, double* y, const double* p0, const double* q0, const double* p1, const double* q1, const double* p2,
+                     const double* q2) {
+    by_team(L.team, [&](auto t) {
+        constexpr int T = decltype(t)::value;
+        hipLaunchKernelGGL(k_bamg_spmv_dots<T>, dim3((unsigned)L.np), dim3(256), 0, st, L.n, L.rp, L.ci, blk(L).bv, x, y, p0, q0, p1, q1, p2, q2, L.part.p,
+                           (const int32_t*)nullptr);
+    });
 }
-}   // namespace
+constexpr AmgCycleOps kBlockOps{block_pre_restrict, block_post, block_spmv_dots};
 
-namespace {
 // the hierarchy with (absorb) or without absorption on every level; *stalled: the answer is the "coarsening stalled above the dense limit" refusal
 int block_amg_build_pass(fdapde_ctx* c, BlockAmg** slot, const double* raw, int strength_block, int absorb, bool* stalled) {
     *stalled = false;
     hipStream_t st = c->stream;
     const auto t0 = std::chrono::steady_clock::now();
     std::unique_ptr<BlockAmg> H(new BlockAmg());
-    H->absorbed = absorb;
+    // (GCR, not flexible CG, because the system is indefinite)
+    H->ops = &kBlockOps, H->per = 2, H->sym = false, H->absorbed = absorb;
     const int64_t dense_limit = std::min<int64_t>(c->dense_rows, kDenseMaxRows);
     const int64_t coarse_rows = std::max<int64_t>(2, std::min<int64_t>(c->amg_coarse_rows, kDenseMaxRows));
     {
         std::unique_ptr<BamgLevel> L0(new BamgLevel());
         L0->n = c->hs.n_dofs, L0->nnz = c->hs.nnz, L0->rp = c->rowptr.p, L0->ci = c->colidx.p, L0->bv = raw;
-        AmgLevel& S = L0->S;
-        S.n = L0->n, S.nnz = L0->nnz, S.rp = L0->rp, S.ci = L0->ci;
-        HIPCHK(c, S.a_own.alloc((size_t)std::max<int64_t>(S.nnz, 1)));
-        hipLaunchKernelGGL(k_bamg_pick, dim3(gn(S.nnz)), dim3(256), 0, st, S.nnz, raw, strength_block, S.a_own.p);
+        HIPCHK(c, L0->a_own.alloc((size_t)std::max<int64_t>(L0->nnz, 1)));
+        hipLaunchKernelGGL(k_bamg_pick, dim3(gn(L0->nnz)), dim3(256), 0, st, L0->nnz, raw, strength_block, L0->a_own.p);
         HIPCHK(c, hipGetLastError());
-        S.a = S.a_own.p;
+        L0->a = L0->a_own.p;
         H->lv.push_back(std::move(L0));
     }
     while (2 * H->lv.back()->n > coarse_rows) {
-        BamgLevel& F = *H->lv.back();
-        // pass 1 on the level's strength matrix, pass 2 on its Galerkin matrix (the pair graph): aggregates of at most four rows; the block values follow
-        DBuf<int32_t> agg1, agg2;
-        int32_t n1 = 0, n2 = 0;
-        if (int rc = dev_pairwise(c, F.n, F.nnz, F.rp, F.ci, F.S.a, nullptr, absorb, agg1, &n1)) return rc;
-        AmgLevel T;
-        DBuf<double> bvT;
-        {
-            AmgGalerkinMap map;
-            if (int rc = dev_galerkin(c, F.n, F.nnz, F.rp, F.ci, F.S.a, agg1.p, n1, T, &map)) return rc;
-            if (int rc = block_galerkin(c, map, F.bv, T.nnz, bvT)) return rc;
-        }
-        if (int rc = dev_pairwise(c, T.n, T.nnz, T.rp, T.ci, T.a, nullptr, absorb, agg2, &n2)) return rc;
+        BamgLevel& F = blk(*H->lv.back());
         std::unique_ptr<BamgLevel> N(new BamgLevel());
-        {
-            AmgGalerkinMap map;
-            if (int rc = dev_galerkin(c, T.n, T.nnz, T.rp, T.ci, T.a, agg2.p, n2, N->S, &map)) return rc;
-            if (int rc = block_galerkin(c, map, bvT.p, N->S.nnz, N->bv_own)) return rc;
+        AmgVerdict verdict;
+        // the level step on the strength matrix; the block values follow as its payload (the dense limit: see amg_build_pass, eng_amg.hip)
+        if (int rc = amg_next_level(c, F, absorb, F.bv, 4, 2, coarse_rows, dense_limit, "block ", H->lv.size() - 1, *N, &N->bv_own, &verdict)) return rc;
+        if (verdict == kAmgStalled) {
+            *stalled = true;
+            return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_BLOCK_AMG: coarsening stalled above the dense limit (a level kept more than 0.8 of its rows): the strength block has too few strong couplings for pairwise aggregation");
         }
-        N->n = N->S.n, N->nnz = N->S.nnz, N->rp = N->S.rp, N->ci = N->S.ci, N->bv = N->bv_own.p;
-        HIPCHK(c, F.agg.alloc((size_t)F.n));
-        hipLaunchKernelGGL(k_bamg_compose, dim3(gn(F.n)), dim3(256), 0, st, F.n, agg1.p, agg2.p, F.agg.p);
-        HIPCHK(c, hipGetLastError());
-        if (int rc = dev_members(c, F.n, F.agg.p, n2, F.mptr, F.midx)) return rc;
-        if (c->amg_setup_check) {   // the same level by the host loops, compared bit for bit
-            HostCsr hf, ht, hn;
-            std::vector<double> bf, bt, bn, dev;
-            std::vector<int32_t> a1, a2, dv32;
-            int32_t m1 = 0, m2 = 0;
-            hf.n = F.n;
-            if (int rc = fetch(c, F.rp, (size_t)F.n + 1, hf.rp)) return rc;
-            if (int rc = fetch(c, F.ci, (size_t)F.nnz, hf.ci)) return rc;
-            if (int rc = fetch(c, F.S.a, (size_t)F.nnz, hf.a)) return rc;
-            if (int rc = fetch(c, F.bv, 4 * (size_t)F.nnz, bf)) return rc;
-            host_pairwise(hf, nullptr, absorb, a1, m1);
-            host_galerkin(hf, a1, m1, ht);
-            host_block_galerkin(hf, bf, a1, m1, bt);
-            host_pairwise(ht, nullptr, absorb, a2, m2);
-            host_galerkin(ht, a2, m2, hn);
-            host_block_galerkin(ht, bt, a2, m2, bn);
-            std::string which;
-            auto same = [&](const auto* p, size_t cnt, const auto& h) {
-                using E = std::decay_t<decltype(h[0])>;
-                std::vector<E> g;
-                return h.size() == cnt && fetch(c, p, cnt, g) == FDAPDE_OK && (cnt == 0 || std::memcmp(g.data(), h.data(), sizeof(E) * cnt) == 0);
-            };
-            if (m1 != n1 || !same(agg1.p, (size_t)F.n, a1)) which += " pass-1 aggregates";
-            else if (m2 != n2 || !same(agg2.p, (size_t)n1, a2)) which += " pass-2 aggregates";
-            else {
-                if (!same(T.rp, (size_t)n1 + 1, ht.rp) || !same(T.ci, (size_t)T.nnz, ht.ci)) which += " pair-graph pattern";
-                else if (!same(T.a, (size_t)T.nnz, ht.a)) which += " pair-graph strength values";
-                else if (!same(bvT.p, 4 * (size_t)T.nnz, bt)) which += " pair-graph block values";
-                if (!same(N->rp, (size_t)n2 + 1, hn.rp) || !same(N->ci, (size_t)N->nnz, hn.ci)) which += " coarse pattern";
-                else if (!same(N->S.a, (size_t)N->nnz, hn.a)) which += " coarse strength values";
-                else if (!same(N->bv, 4 * (size_t)N->nnz, bn)) which += " coarse block values";
-            }
-            if (!which.empty()) {
-                c->err = "amg_setup_check: block level " + std::to_string(H->lv.size() - 1) + ": the device-built hierarchy differs from the host-built one:" + which;
-                return FDAPDE_EHIP;
-            }
-        }
-        if ((double)n2 > kBamgStall * (double)F.n && 2 * (int64_t)n2 > coarse_rows) {   // coarsening stalled: a level the dense inverse takes ends the hierarchy
-            if (2 * F.n > dense_limit) {
-                *stalled = true;
-                return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_BLOCK_AMG: coarsening stalled above the dense limit (a level kept more than 0.8 of its rows): the strength block has too few strong couplings for pairwise aggregation");
-            }
-            F.agg.release(), F.mptr.release(), F.midx.release();
-            break;
-        }
+        if (verdict != kAmgNext) break;   // (kAmgNoFreeRows does not arise: no row is excluded)
+        N->bv = N->bv_own.p;
         H->lv.push_back(std::move(N));
     }
     // the smoother of every level that has a next one; a singular diagonal block below level 0 ends the hierarchy one level above
     for (size_t l = 0; l + 1 < H->lv.size(); ++l) {
         bool bad = false;
-        if (int rc = level_dinv(c, *H->lv[l], &bad)) return rc;
+        if (int rc = level_dinv(c, blk(*H->lv[l]), &bad)) return rc;
         if (!bad) continue;
         if (l == 0) return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_BLOCK_AMG: a DOF's diagonal block is singular (|det| <= 1e-14 max|entry|^2): no block-Jacobi smoother");
         if (2 * H->lv[l - 1]->n > dense_limit)
             return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_BLOCK_AMG: a coarse level has a singular diagonal block and the level above it is too large for the dense inverse");
         H->lv.resize(l);
-        BamgLevel& E = *H->lv.back();
-        E.agg.release(), E.mptr.release(), E.midx.release(), E.dinv.release();
+        BamgLevel& E = blk(*H->lv.back());
+        E.agg.release(), E.mptr.release(), E.midx.release(), E.dinv4.release();
         break;
     }
     for (auto& L : H->lv)
         if (int rc = level_vectors(c, *L)) return rc;
-    BamgLevel& C = *H->lv.back();
+    BamgLevel& C = blk(*H->lv.back());
     if (2 * C.n > kDenseMaxRows) return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_BLOCK_AMG: the coarsest level is too large for the dense inverse");
     HIPCHK(c, H->rp2.alloc((size_t)(2 * C.n + 1)));
     HIPCHK(c, H->ci2.alloc((size_t)std::max<int64_t>(4 * C.nnz, 1)));
@@ -306,32 +181,16 @@ int block_amg_build_pass(fdapde_ctx* c, BlockAmg** slot, const double* raw, int 
 }   // namespace
 
 // the hierarchy of the handle's matrix: raw = the unscaled block CSR on the context's pattern, strength_block = which of its four blocks the aggregation reads.
-// Knob amg_absorb as in amg_build (eng_amg.hip): 2 builds without absorption and, where that ends in the stall refusal, again from level 0 with it
+// Knob amg_absorb: amg_build_retry (amg_setup.h)
 int block_amg_build(fdapde_ctx* c, BlockAmg** slot, const double* raw, int strength_block) {
     delete *slot;
     *slot = nullptr;
     HIPCHK(c, hipSetDevice(c->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    bool stalled = false;
-    int rc = block_amg_build_pass(c, slot, raw, strength_block, c->amg_absorb == 1 ? 1 : 0, &stalled);
-    if (rc != FDAPDE_OK && stalled && c->amg_absorb == 2) {
-        const double first = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        rc = block_amg_build_pass(c, slot, raw, strength_block, 1, &stalled);
-        if (rc == FDAPDE_OK) (*slot)->discarded_ms = first, (*slot)->setup_ms += first;
-    }
-    return rc;
+    return amg_build_retry(c, slot, [&](int absorb, bool* stalled) { return block_amg_build_pass(c, slot, raw, strength_block, absorb, stalled); });
 }
 
 int block_amg_describe(const BlockAmg* H, int32_t cap, int32_t* n_levels, int64_t* rows, int64_t* nnz, int32_t* absorbed, double* setup_ms) {
-    if (!H) return FDAPDE_ENOTINIT;
-    if (n_levels) *n_levels = (int32_t)H->lv.size();
-    for (size_t l = 0; l < H->lv.size() && (int64_t)l < (int64_t)cap; ++l) {
-        if (rows) rows[l] = 2 * H->lv[l]->n;
-        if (nnz) nnz[l] = 4 * H->lv[l]->nnz;
-    }
-    if (absorbed) *absorbed = H->absorbed;
-    if (setup_ms) *setup_ms = H->setup_ms;
-    return FDAPDE_OK;
+    return amg_describe(H, cap, n_levels, rows, nnz, absorbed, setup_ms);   // (rows 2 n_l, entries 4 nnz_l: per = 2)
 }
 
 // fdapde_amg_aggregates for the block handle: agg[i] = the row of level + 1 that block row i of `level` belongs to (level 0: i in the reference DOF
@@ -339,7 +198,7 @@ int block_amg_describe(const BlockAmg* H, int32_t cap, int32_t* n_levels, int64_
 int block_amg_aggregates(fdapde_ctx* c, const BlockAmg* H, int32_t level, int64_t cap, int32_t* agg, int64_t* n_rows) {
     if (!H) return FDAPDE_ENOTINIT;
     if (level < 0 || (size_t)level + 1 >= H->lv.size()) return FDAPDE_EINVAL;
-    const BamgLevel& L = *H->lv[(size_t)level];
+    const AmgLevel& L = *H->lv[(size_t)level];
     if (n_rows) *n_rows = L.n;
     if (!agg || cap < L.n) return FDAPDE_EINVAL;
     HIPCHK(c, hipSetDevice(c->device));
@@ -360,7 +219,7 @@ int block_amg_run(fdapde_ctx* c, BlockAmg* hp, const double* raw, const double* 
                   bool* converged_out, bool* broke_out) {
     BlockAmg& H = *hp;
     hipStream_t st = c->stream;
-    BamgLevel& L0 = *H.lv[0];
+    AmgLevel& L0 = *H.lv[0];
     const int64_t n = L0.n, n2 = 2 * n;
     const int np = (int)std::min<int64_t>(1024, std::max<int64_t>(1, (n2 + 4095) / 4096));
     const int mk = std::max(1, std::min(std::min(c->gmres_m, kBamgMaxRestart), std::max(maxit, 1)));
@@ -390,7 +249,7 @@ int block_amg_run(fdapde_ctx* c, BlockAmg* hp, const double* raw, const double* 
     auto precond = [&](const double* v, double* z, double* w, bool&) -> int {
         if (one_level) {
             if (int rc = dense_apply(c, H.D, 1, v, z)) return rc;
-        } else if (int rc = bamg_cycle(c, H, 0, v, z))
+        } else if (int rc = amg_cycle(c, H, 0, v, z))
             return rc;
         spmv(z, w);
         return FDAPDE_OK;

@@ -271,28 +271,10 @@ static __global__ void k_bamg_residual(int64_t n2, const double* b, const double
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n2) r[i] = b[i] - t[i];
 }
-// ---- ... and its set-up: the scalar strength matrix, the block Galerkin sums --------------------------------------------------------------------------
+// ---- ... and its set-up: the scalar strength matrix (the block Galerkin sums are k_bamg_gsum's, beside k_amg_gsum in eng_amg.hip) ------------------------
 static __global__ void k_bamg_pick(int64_t nnz, const double* bv, int q, double* out) {   // block q of every entry
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k < nnz) out[k] = bv[4 * k + q];
-}
-static __global__ void k_bamg_compose(int64_t n, const int32_t* agg1, const int32_t* agg2, int32_t* agg) {   // row -> pair -> aggregate
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) agg[i] = agg2[agg1[i]];
-}
-// one thread per coarse entry: the four block values summed over its fine entries in ascending slot order (the order dev_galerkin's stable sort left
-// them in: keys / idx / head / pos are its AmgGalerkinMap) -- no float atomics, the same bits every run
-static __global__ void k_bamg_gsum(int64_t m, const uint64_t* keys, const int32_t* idx, const int32_t* head, const int32_t* pos, const double* bv, double* bv_c) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= m || !head[e]) return;
-    const uint64_t key = keys[e];
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-    for (int64_t q = e; q < m && keys[q] == key; ++q) {
-        const double* v = bv + 4 * (int64_t)idx[q];
-        s0 += v[0], s1 += v[1], s2 += v[2], s3 += v[3];
-    }
-    double* o = bv_c + 4 * (int64_t)pos[e];
-    o[0] = s0, o[1] = s1, o[2] = s2, o[3] = s3;
 }
 
 // ---- Psi^T W Psi on the pattern --------------------------------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 """Reference side of the absorption tests (tests/test_amg_absorb_cpu.py, tests/test_gpu_amg_absorb.py): a numpy / scipy restatement of the multilevel set-up
 with the knob `amg_absorb`, on top of tests/block_amg_ref.py --
-  * the handshake matching of block_amg_ref.pairwise, kept as `mate`, and the ABSORPTION pass of csrc/eng_amg.hip (amg_absorb_row): every row the ten rounds
+  * the handshake matching of block_amg_ref.pairwise, kept as `mate`, and the ABSORPTION pass (amg_absorb_row, csrc/amg_rows.h; k_amg_absorb of csrc/eng_amg.hip): every row the ten rounds
     left single looks along its row at the entries with a coupling (strong or weak) to a PAIRED row, takes the one with the largest |coupling| (ties: the
     larger hash of the index pair, then the smaller index) and joins that pair's aggregate; a single without a paired neighbour stays a singleton;
   * the SCALAR K-cycle of csrc/eng_amg.hip: damped Jacobi 1.5 / lambda_max(D^-1 A) by 15 power steps, the coarse correction, damped Jacobi;
@@ -17,7 +17,7 @@ import block_amg_ref as ar
 
 COARSE_ROWS = 256          # what the GPU test sets `amg_coarse_rows` to for the scalar cases
 KEEP = 0.35                # every level of a hierarchy built with absorption keeps at most this share of the rows above it (the restatement: <= 0.23)
-SCALAR_DENSE_LIMIT = 8192  # kAmgMaxCoarse
+SCALAR_DENSE_LIMIT = 8192  # kDenseMaxRows
 # iteration caps the GPU test hands over: conditions with a factor 2 to spare over this restatement (tests/test_amg_absorb_cpu.py holds it to HALF of each)
 CAP_3D, CAP_2D, CAP_BLOCK = 40, 50, ar.BUDGET_P1
 LADDER_3D = [("unit_cube", nx) for nx in (8, 16, 32)]
@@ -59,7 +59,7 @@ def matching(rp, ci, a, n):
 
 
 def absorb(ci, sw, rows, h, mate):
-    """amg_absorb_row for every row: the paired row a single joins, -1 for none"""
+    """amg_absorb_row (csrc/amg_rows.h) for every row: the paired row a single joins, -1 for none"""
     w = np.abs(sw)
     k = np.flatnonzero((w > 0.0) & (rows != ci) & (mate[rows] < 0) & (mate[ci] >= 0))
     order = k[np.lexsort((-ci[k], h[k], w[k], rows[k]))]   # per row ascending (w, hash, -j): the best candidate comes last

@@ -1,5 +1,5 @@
 """Reference side of the FDAPDE_SOLVER_BLOCK_AMG tests (tests/test_block_amg_cpu.py, tests/test_gpu_block_amg.py): a numpy / scipy restatement of
-csrc/eng_block_amg.hip with the device's rules --
+csrc/eng_block_amg.hip with the device's rules (the row rules of csrc/amg_rows.h; tests/test_host_amg.py holds their host loops to `pairwise` and `galerkin`) --
   * aggregation: handshake matching on a SCALAR strength matrix on the pattern (the (2,1) block), theta 0.25, ten rounds of which the first three on strong
     couplings only, ties broken by the device's hash of the index pair; two pairwise passes per level, the second on the Galerkin matrix of the first;
   * block Galerkin matrices with P = P_scalar (x) I_2 (the four blocks summed per coarse entry in ascending fine-slot order);
@@ -34,7 +34,7 @@ def case_id(case):
 
 
 def pair_hash(i, j):
-    """amg_pair_hash (csrc/eng_amg.hip): the same word from both ends of an edge"""
+    """amg_pair_hash (csrc/amg_rows.h): the same word from both ends of an edge"""
     lo, hi = np.minimum(i, j).astype(np.uint64), np.maximum(i, j).astype(np.uint64)
     with np.errstate(over="ignore"):
         z = ((hi << np.uint64(32)) | lo) * np.uint64(0x9E3779B97F4A7C15)
@@ -52,7 +52,7 @@ def _transposed_values(rp, ci, a, n):
 
 
 def strength(rp, ci, a, n):
-    """amg_strength_row: > 0 a strong coupling, < 0 (minus its strength) a weak one, 0 none"""
+    """amg_strength_row (csrc/amg_rows.h): > 0 a strong coupling, < 0 (minus its strength) a weak one, 0 none"""
     rows = np.repeat(np.arange(n), np.diff(rp))
     off = rows != ci
     s = np.where(off, -(a + _transposed_values(rp, ci, a, n)), 0.0)
