@@ -51,7 +51,7 @@ SYMBOLS = [
     "fdapde_ctx_create_multi", "fdapde_ctx_devices", "fdapde_partition_build", "fdapde_partition_sizes", "fdapde_partition_get", "fdapde_partition_whole",
     "fdapde_partition_peers",
     "fdapde_block_compute", "fdapde_block_solve", "fdapde_block_spmv", "fdapde_block_bench_spmv", "fdapde_gram_pointwise",
-    "fdapde_amg_hierarchy", "fdapde_amg_aggregates",
+    "fdapde_amg_hierarchy", "fdapde_amg_aggregates", "fdapde_amg_cols_trace",
 ]
 AMG_OF_SOLVE, AMG_OF_HANDLE, AMG_OF_BLOCK = 0, 1, 2   # `which` of fdapde_amg_hierarchy
 PARTITION_ROWDIST, PARTITION_ELEMENTS = 0, 1
@@ -630,6 +630,13 @@ class Context:
         self._check(self.lib.fdapde_amg_hierarchy(self._ctx, int(which), nl.value, C.byref(nl), rows.ctypes.data_as(C.POINTER(C.c_int64)),
                                                   nnz.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(ab), C.byref(ms)))
         return dict(rows=[int(r) for r in rows], nnz=[int(z) for z in nnz], absorbed=ab.value, setup_ms=ms.value)
+
+    def amg_cols_trace(self, which):
+        """fdapde_amg_cols_trace: since the hierarchy of the factor-once handle (which = 1) or the block handle (2) was built ->
+        dict(batches: runs of 2, 4 or 8 columns side by side; batched_cols: the columns they took; single_cols: the columns solved one by one)"""
+        b, q, s = C.c_int32(), C.c_int32(), C.c_int32()
+        self._check(self.lib.fdapde_amg_cols_trace(self._ctx, int(which), C.byref(b), C.byref(q), C.byref(s)))
+        return dict(batches=b.value, batched_cols=q.value, single_cols=s.value)
 
     def amg_aggregates(self, which, level):
         """fdapde_amg_aggregates: for the block handle (which = 2) and a level that has a next one, the row of level + 1 every block row of `level` belongs

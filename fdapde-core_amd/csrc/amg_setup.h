@@ -5,6 +5,7 @@
 #ifndef FDAPDE_AMG_SETUP_H
 #define FDAPDE_AMG_SETUP_H
 
+#include <algorithm>
 #include <chrono>
 #include <cstdint>
 #include <memory>
@@ -29,6 +30,10 @@ struct AmgLevel {
     int team = 4, np = 1;
     DBuf<int32_t> agg, mptr, midx;                // row -> row of the next level (-1: none); members of each next-level row, ascending
     DBuf<double> b, zt, cv, v, dv, w, rt, e, part, sc;   // work vectors (b: the restricted right-hand side; e: this level's correction)
+    // ... and for a batch of qcols interleaved columns (allocated by the first batch of that width: amg_cols_prepare): qcols times the words, qsc 8 per column,
+    // qpart 3 np per column; on the coarsest level qb / qecm are column-major (what dense_apply takes), qe the correction interleaved again
+    DBuf<double> qb, qzt, qcv, qv, qdv, qw, qrt, qe, qecm, qpart, qsc;
+    int qcols = 0;
     virtual ~AmgLevel() = default;                // (the block form's levels carry their block values: eng_block_amg.hip)
 };
 
@@ -39,6 +44,12 @@ struct AmgCycleOps {
     void (*post)(hipStream_t st, AmgLevel& L, AmgLevel& N, const double* r, double* out);         // out = L.zt + P N.e, smoothed once more
     void (*spmv_dots)(hipStream_t st, AmgLevel& L, const double* x, double* y, const double* p0, const double* q0, const double* p1, const double* q1,
                       const double* p2, const double* q2);                                        // y = A x, L.part = the partials of p_q . q_q
+    // the same launches for Q interleaved columns (work vectors L.q*): rc = the restricted residual, word w of column q at rc[w * rs + q * cs] (interleaved, or
+    // column-major for the dense inverse of the coarsest level); dot d of column q in L.qpart[(d Q + q) np ..]
+    void (*pre_restrict_cols)(hipStream_t st, int Q, AmgLevel& L, AmgLevel& N, const double* r, double* rc, int64_t rs, int64_t cs);
+    void (*post_cols)(hipStream_t st, int Q, AmgLevel& L, AmgLevel& N, const double* r, double* out);
+    void (*spmv_dots_cols)(hipStream_t st, int Q, AmgLevel& L, const double* x, double* y, const double* p0, const double* q0, const double* p1, const double* q1,
+                           const double* p2, const double* q2);
 };
 
 struct AmgHierarchy {
@@ -54,6 +65,8 @@ struct AmgHierarchy {
     int absorbed = 0;                             // its passes absorbed the rows the matching left single (knob amg_absorb)
     double discarded_ms = 0.0;                    // amg_absorb 2: what the build without absorption cost before it stalled (part of setup_ms)
     DBuf<double> vec, basis, part, dots;          // the outer iteration's vectors and flexible GMRES basis
+    DBuf<double> qvec, qio;                       // a batch's iterate, residual, right-hand side (interleaved) and staging vectors; its columns in the reference numbering
+    int64_t batches = 0, batched_cols = 0, single_cols = 0;   // fdapde_amg_cols_trace: Q-column runs, the columns they took, the columns solved one by one
     int np = 1, mk = 0;
     virtual ~AmgHierarchy() { D.X.release(); }
 };
@@ -98,6 +111,20 @@ template <typename H, typename Pass> int amg_build_retry(fdapde_ctx* c, H** slot
 // out = the cycle of level l on r (l < coarsest): smoothing, the coarse correction -- below the finest level two flexible CG / GCR steps around the next
 // level's cycle (the K-cycle), the dense inverse on the last level --, smoothing
 int amg_cycle(fdapde_ctx* c, AmgHierarchy& H, size_t l, const double* r, double* out);
+// ... for Q in {2, 4, 8} interleaved columns (the same recursion; per column the arithmetic of amg_cycle in the same order).  amg_cols_prepare: the levels'
+// work vectors for batches of that width, on first use
+int amg_cols_prepare(fdapde_ctx* c, AmgHierarchy& H, int Q);
+int amg_cycle_cols(fdapde_ctx* c, AmgHierarchy& H, size_t l, int Q, const double* r, double* out);
+// the coarsest level alone as the preconditioner: z = D^-1 v for Q interleaved columns (through the column-major layout dense_apply takes)
+int amg_dense_cols(fdapde_ctx* c, AmgHierarchy& H, int Q, const double* v, double* z);
+// the restart length of FDAPDE_SOLVER_AMG's outer iteration on n unknowns: at most 50 vectors, at most ~16 GB of basis, never more than maxit.  The single-column
+// run and a batch must use the same one (a batch's iterates are the single-column run's)
+inline int amg_restart_len(int64_t n, int maxit) {
+    const int mk = (int)std::min<int64_t>(50, std::max<int64_t>(5, (int64_t)(16e9 / (16.0 * (double)n))));
+    return std::max(1, std::min(mk, std::max(maxit, 1)));
+}
+// the widest batch the basis budget allows: Q (2 mk + 1) n words within 16 GB, else 4, 2, 1 (the restart length is never shortened)
+int amg_cols_width(int want, int64_t n_words, int mk);
 
 }   // namespace fdapde_engine
 #endif

@@ -446,6 +446,14 @@ int fdapde_amg_hierarchy(fdapde_ctx* c, int32_t which, int32_t cap, int32_t* n_l
     return rc;
 }
 
+int fdapde_amg_cols_trace(fdapde_ctx* c, int32_t which, int32_t* batches, int32_t* batched_cols, int32_t* single_cols) {
+    if (!c || which < 0 || which > 2) return FDAPDE_EINVAL;
+    if (which == 0) return fail(c, FDAPDE_EUNSUPPORTED, "fdapde_amg_cols_trace: fdapde_solve has one column; the factor-once handle (which = 1) and the block handle (which = 2) batch theirs");
+    const int rc = which == 1 ? fdapde_engine::amg_lin_cols_trace(c, batches, batched_cols, single_cols) : fdapde_engine::block_amg_cols_trace_ctx(c, batches, batched_cols, single_cols);
+    if (rc == FDAPDE_ENOTINIT) return fail(c, rc, "fdapde_amg_cols_trace: no hierarchy of that kind is live (it is built by the first solve that names the multilevel method)");
+    return rc;
+}
+
 int fdapde_amg_aggregates(fdapde_ctx* c, int32_t which, int32_t level, int64_t cap, int32_t* agg, int64_t* n_rows) {
     if (!c || which < 0 || which > 2) return FDAPDE_EINVAL;
     if (c->group) return fail(c, FDAPDE_EUNSUPPORTED, "fdapde_amg_aggregates: one-device contexts only");
@@ -508,6 +516,7 @@ int fdapde_tune(fdapde_ctx* c, const char* key, int32_t value) {
     else if (k == "pmg_setup_check" && (value == 0 || value == 1)) c->pmg_setup_check = value;
     else if (k == "amg_coarse_rows" && value >= 1 && value <= 8192) c->amg_coarse_rows = value;
     else if (k == "amg_setup_check" && (value == 0 || value == 1)) c->amg_setup_check = value;
+    else if (k == "amg_cols" && (value == 1 || value == 2 || value == 4 || value == 8)) c->amg_cols = value;
     else if (k == "amg_absorb" && value >= 0 && value <= 2) {   // the hierarchies are built again by the next solve that needs one
         if (value != c->amg_absorb) fdapde_engine::amg_release(c), fdapde_engine::block_amg_forget(c);
         c->amg_absorb = value;

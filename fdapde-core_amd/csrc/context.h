@@ -491,6 +491,7 @@ struct fdapde_ctx {
     int64_t amg_coarse_rows = 1024;   // knob: coarsening stops at a level of at most that many rows, which is inverted once (dense_build_estimate_ms(1024) ~ 2.5 ms)
     int amg_absorb = 2;           // knob: 0 = the multilevel set-ups pair only, 1 = every pass also absorbs the rows it left single, 2 = pair only and, where that ends in
                                   // the "coarsening stalled above the dense limit" refusal, build again with absorption on every level (what is solved without it keeps its bits)
+    int amg_cols = 8;             // knob: the widest batch of columns the two multilevel handles solve side by side (8, 4, 2; 1 = column by column)
     int amg_setup_check = 0;      // knob: 1 = host loops also build the aggregates and the coarse matrices, compared bit for bit (an error if they differ)
     int64_t init_count = 0;       // the assembled stiffness matrix's EPOCH: fdapde_init calls that may have changed its values (who caches something derived from them compares).
                                   // A repeated fdapde_init of the SAME operator with the row-owner sweep reproduces the matrix bit for bit (only the load vector is new): same epoch

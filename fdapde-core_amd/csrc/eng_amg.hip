@@ -36,6 +36,7 @@
 #include "context.h"
 #include "amg_setup.h"
 #include "engine.h"
+#include "kernels_cols.h"
 #include "kernels_dense.h"
 #include "kernels_reduce.h"
 
@@ -303,6 +304,232 @@ __global__ void k_amg_scatter(int64_t n, const int32_t* idx, const double* src, 
     if (i < n) dst[idx[i]] = src[i];
 }
 
+// ---- the cycle kernels for Q interleaved columns (kernels_cols.h): word i of column q at [i * Q + q].  Per column the arithmetic of the kernel of the same name
+// above, in the same order -- the same team width, the same entries to the same lanes, the same team_sum / wave_sum / block_sum, the same grid of partials --
+// with Q accumulators per lane; the matrix and its indices are read once for all columns, a gathered operand is Q contiguous doubles.  No column reads another.
+// These kernels (and k_pmg_*_cols of eng_pmg.hip) write each expression as the single-column kernel does and leave its contraction to the compiler, which fuses
+// the unrolled per-column copies as it fuses the original (s += a x, r - om s, z + om d (r - s), w -= h v): that is a property of this compiler, not of the
+// language -- the block forms in kernels_block.h needed theirs spelled out.  tests/test_gpu_amg_cols.py holds every column to the single-column run's bits
+// for Q = 2, 4, 8 on 2-D and 3-D, P1 and P2 hierarchies; if a toolchain changes a width's fusion that test fails, and the remedy is kernels_block.h's.
+template <int T, int Q>
+__global__ __launch_bounds__(256) void k_amg_pre_restrict_cols(int64_t nc, const int32_t* mptr, const int32_t* midx, const int32_t* rp, const int32_t* ci, const double* a,
+                                                               const double* dinv, double om, const double* r, double* zt, double* rc, int64_t rs, int64_t cs) {
+    const int lane = threadIdx.x & (T - 1);
+    const int64_t ag = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / T;
+    if (ag >= nc) return;
+    double acc[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) acc[q] = 0.0;
+    for (int32_t m = mptr[ag]; m < mptr[ag + 1]; ++m) {
+        const int32_t i = midx[m];
+        double s[Q];
+#pragma unroll
+        for (int q = 0; q < Q; ++q) s[q] = 0.0;
+        for (int32_t k = rp[i] + lane; k < rp[i + 1]; k += T) {
+            const int32_t j = ci[k];
+            const double ak = a[k], dj = dinv[j];
+            double rj[Q];
+            ld_cols<Q>(r + (int64_t)j * Q, rj);
+#pragma unroll
+            for (int q = 0; q < Q; ++q) s[q] += ak * (dj * rj[q]);
+        }
+#pragma unroll
+        for (int q = 0; q < Q; ++q) s[q] = team_sum<T>(s[q]);
+        double ri[Q];
+        ld_cols<Q>(r + (int64_t)i * Q, ri);
+        if (lane == 0) {
+            double z[Q];
+#pragma unroll
+            for (int q = 0; q < Q; ++q) z[q] = om * dinv[i] * ri[q];
+            st_cols<Q>(zt + (int64_t)i * Q, z);
+        }
+#pragma unroll
+        for (int q = 0; q < Q; ++q) acc[q] += ri[q] - om * s[q];
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < Q; ++q) rc[ag * rs + q * cs] = acc[q];
+    }
+}
+template <int T, int Q>
+__global__ __launch_bounds__(256) void k_amg_post_cols(int64_t n, const int32_t* rp, const int32_t* ci, const double* a, const double* dinv, double om, const int32_t* agg,
+                                                       const double* e, const double* r, const double* zt, double* out) {
+    const int lane = threadIdx.x & (T - 1);
+    const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / T;
+    if (i >= n) return;
+    double s[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) s[q] = 0.0;
+    for (int32_t k = rp[i] + lane; k < rp[i + 1]; k += T) {
+        const int32_t j = ci[k], g = agg[j];
+        const double ak = a[k];
+        double zj[Q], eg[Q];
+        ld_cols<Q>(zt + (int64_t)j * Q, zj);
+        if (g >= 0) ld_cols<Q>(e + (int64_t)g * Q, eg);
+        else {
+#pragma unroll
+            for (int q = 0; q < Q; ++q) eg[q] = 0.0;
+        }
+#pragma unroll
+        for (int q = 0; q < Q; ++q) s[q] += ak * (zj[q] + eg[q]);
+    }
+#pragma unroll
+    for (int q = 0; q < Q; ++q) s[q] = team_sum<T>(s[q]);
+    if (lane == 0) {
+        const int32_t g = agg[i];
+        double zi[Q], eg[Q], ri[Q], o[Q];
+        ld_cols<Q>(zt + i * Q, zi), ld_cols<Q>(r + i * Q, ri);
+        if (g >= 0) ld_cols<Q>(e + (int64_t)g * Q, eg);
+        else {
+#pragma unroll
+            for (int q = 0; q < Q; ++q) eg[q] = 0.0;
+        }
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            const double z = zi[q] + eg[q];
+            o[q] = z + om * dinv[i] * (ri[q] - s[q]);
+        }
+        st_cols<Q>(out + i * Q, o);
+    }
+}
+// y = A x and up to three dot products per column: part[(d Q + q) gridDim.x + block]
+template <int T, int Q>
+__global__ __launch_bounds__(256) void k_amg_spmv_dots_cols(int64_t n, const int32_t* rp, const int32_t* ci, const double* a, const double* x, double* y, const double* p0,
+                                                            const double* q0, const double* p1, const double* q1, const double* p2, const double* q2, double* part) {
+    __shared__ double red[3 * Q][4];
+    const int lane = threadIdx.x & (T - 1);
+    double d0[Q], d1[Q], d2[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) d0[q] = d1[q] = d2[q] = 0.0;
+    const int64_t teams = (int64_t)gridDim.x * blockDim.x / T;
+    for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / T; i < n; i += teams) {
+        double s[Q];
+#pragma unroll
+        for (int q = 0; q < Q; ++q) s[q] = 0.0;
+        for (int32_t k = rp[i] + lane; k < rp[i + 1]; k += T) {
+            const double ak = a[k];
+            double xj[Q];
+            ld_cols<Q>(x + (int64_t)ci[k] * Q, xj);
+#pragma unroll
+            for (int q = 0; q < Q; ++q) s[q] += ak * xj[q];
+        }
+#pragma unroll
+        for (int q = 0; q < Q; ++q) s[q] = team_sum<T>(s[q]);
+        if (lane == 0) {
+            st_cols<Q>(y + i * Q, s);
+            auto dot = [&](const double* u, const double* v, double (&d)[Q]) {
+                double uv[Q], vv[Q];
+#pragma unroll
+                for (int q = 0; q < Q; ++q) uv[q] = vv[q] = s[q];
+                if (u != y) ld_cols<Q>(u + i * Q, uv);
+                if (v != y) ld_cols<Q>(v + i * Q, vv);
+#pragma unroll
+                for (int q = 0; q < Q; ++q) d[q] += uv[q] * vv[q];
+            };
+            dot(p0, q0, d0), dot(p1, q1, d1);
+            if (p2) dot(p2, q2, d2);
+        }
+    }
+    const int w = threadIdx.x >> 6;
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+        const double t0 = wave_sum(d0[q]), t1 = wave_sum(d1[q]), t2 = wave_sum(d2[q]);
+        if ((threadIdx.x & 63) == 0) red[q][w] = t0, red[Q + q][w] = t1, red[2 * Q + q][w] = t2;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3 * Q) part[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
+}
+// k_amg_coef for column blockIdx.x of Q: the partials part[(d Q + q) np ..], the scalars sc[8 q ..]; the guards are the column's own
+__global__ __launch_bounds__(256) void k_amg_coef_cols(const double* part, int np, int Q, int stage, double* sc_all) {
+    __shared__ double red[5];
+    const int col = blockIdx.x;
+    double* sc = sc_all + 8 * col;
+    double t[3];
+    for (int q = 0; q < 3; ++q) {
+        double s = 0.0;
+        for (int i = threadIdx.x; i < np; i += 256) s += part[((size_t)q * Q + col) * np + i];
+        t[q] = block_sum(s, red);
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    if (stage == 1) {
+        const double rho1 = t[0], a1 = rho1 > 0.0 && isfinite(rho1) ? t[1] / rho1 : 0.0;
+        sc[0] = rho1, sc[1] = isfinite(a1) ? a1 : 0.0;
+    } else {
+        const double rho1 = sc[0], gamma = t[0];
+        const double rho2 = rho1 > 0.0 ? t[1] - gamma * gamma / rho1 : 0.0;
+        double cd = rho2 > 0.0 && isfinite(rho2) ? t[2] / rho2 : 0.0;
+        double cc = sc[1] - (rho1 > 0.0 ? cd * gamma / rho1 : 0.0);
+        if (!isfinite(cd) || !isfinite(cc)) cd = 0.0, cc = sc[1];
+        sc[2] = cc, sc[3] = cd;
+    }
+}
+template <int Q> __global__ void k_amg_axpy_sc_cols(int64_t n, const double* b, const double* v, const double* sc, double* rt) {   // rt_q = b_q - sc[8 q + 1] v_q
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double bi[Q], vi[Q], o[Q];
+    ld_cols<Q>(b + i * Q, bi), ld_cols<Q>(v + i * Q, vi);
+#pragma unroll
+    for (int q = 0; q < Q; ++q) o[q] = bi[q] - sc[8 * q + 1] * vi[q];
+    st_cols<Q>(rt + i * Q, o);
+}
+template <int Q> __global__ void k_amg_comb2_cols(int64_t n, const double* cv, const double* dv, const double* sc, double* e) {   // e_q = sc[8 q + 2] c_q + sc[8 q + 3] d_q
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double ci[Q], di[Q], o[Q];
+    ld_cols<Q>(cv + i * Q, ci), ld_cols<Q>(dv + i * Q, di);
+#pragma unroll
+    for (int q = 0; q < Q; ++q) o[q] = sc[8 * q + 2] * ci[q] + sc[8 * q + 3] * di[q];
+    st_cols<Q>(e + i * Q, o);
+}
+template <int T, int Q>
+__global__ __launch_bounds__(256) void k_amg_apply_K_cols(int64_t n, const int32_t* rp, const int32_t* ci, const double* a, const uint8_t* bnd, int use_bnd, const double* x,
+                                                          const double* f, const double* g, double* y) {
+    const int lane = threadIdx.x & (T - 1);
+    const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / T;
+    if (i >= n) return;
+    const bool unit = use_bnd && bnd[i];
+    double s[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) s[q] = 0.0;
+    if (!unit)
+        for (int32_t k = rp[i] + lane; k < rp[i + 1]; k += T) {
+            const double ak = a[k];
+            double xj[Q];
+            ld_cols<Q>(x + (int64_t)ci[k] * Q, xj);
+#pragma unroll
+            for (int q = 0; q < Q; ++q) s[q] += ak * xj[q];
+        }
+#pragma unroll
+    for (int q = 0; q < Q; ++q) s[q] = team_sum<T>(s[q]);
+    if (lane == 0) {
+        double o[Q];
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            const double kx = unit ? x[i * Q + q] : s[q];
+            o[q] = f ? (unit ? g[i * Q + q] : f[i * Q + q]) - kx : kx;
+        }
+        st_cols<Q>(y + i * Q, o);
+    }
+}
+// x = g on the Dirichlet rows; elsewhere x0 or 0 (any layout: elementwise over the n Q words, row = e / Q)
+__global__ void k_amg_start_cols(int64_t n, int Q, const uint8_t* bnd, int use_bnd, const double* g, const double* x0, double* x) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < n * Q) x[e] = (use_bnd && bnd[e / Q]) ? g[e] : (x0 ? x0[e] : 0.0);
+}
+// the handle's columns between the reference numbering (column-major n x Q) and the internal order (interleaved)
+__global__ void k_amg_gather_cols(int64_t n, int Q, const int32_t* idx, const double* src, double* dst) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n * Q) return;
+    const int64_t i = e / Q, q = e - i * Q;
+    dst[e] = src[q * n + idx[i]];
+}
+__global__ void k_amg_scatter_cols(int64_t n, int Q, const int32_t* idx, const double* src, double* dst) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n * Q) return;
+    const int64_t i = e / Q, q = e - i * Q;
+    dst[q * n + idx[i]] = src[e];
+}
 template <typename F> void by_team(int T, F&& f) {
     if (T <= 4) f(std::integral_constant<int, 4>{});
     else if (T <= 8) f(std::integral_constant<int, 8>{});
@@ -568,7 +795,26 @@ void scalar_spmv_dots(hipStream_t st, AmgLevel& L, const double* x, double* y, c
         hipLaunchKernelGGL(k_amg_spmv_dots<T>, dim3((unsigned)L.np), dim3(256), 0, st, L.n, L.rp, L.ci, L.a, x, y, p0, q0, p1, q1, p2, q2, L.part.p);
     });
 }
-constexpr AmgCycleOps kScalarOps{scalar_pre_restrict, scalar_post, scalar_spmv_dots};
+void scalar_pre_restrict_cols(hipStream_t st, int Q, AmgLevel& L, AmgLevel& N, const double* r, double* rc, int64_t rs, int64_t cs) {
+    by_team_cols<4>(L.team, Q, [&](auto t, auto q) {
+        constexpr int T = decltype(t)::value, QC = decltype(q)::value;
+        hipLaunchKernelGGL((k_amg_pre_restrict_cols<T, QC>), dim3(gn(N.n * T)), dim3(256), 0, st, N.n, L.mptr.p, L.midx.p, L.rp, L.ci, L.a, L.dinv.p, L.om, r, L.qzt.p, rc, rs, cs);
+    });
+}
+void scalar_post_cols(hipStream_t st, int Q, AmgLevel& L, AmgLevel& N, const double* r, double* out) {
+    by_team_cols<4>(L.team, Q, [&](auto t, auto q) {
+        constexpr int T = decltype(t)::value, QC = decltype(q)::value;
+        hipLaunchKernelGGL((k_amg_post_cols<T, QC>), dim3(gn(L.n * T)), dim3(256), 0, st, L.n, L.rp, L.ci, L.a, L.dinv.p, L.om, L.agg.p, N.qe.p, r, L.qzt.p, out);
+    });
+}
+void scalar_spmv_dots_cols(hipStream_t st, int Q, AmgLevel& L, const double* x, double* y, const double* p0, const double* q0, const double* p1, const double* q1,
+                           const double* p2, const double* q2) {
+    by_team_cols<4>(L.team, Q, [&](auto t, auto q) {
+        constexpr int T = decltype(t)::value, QC = decltype(q)::value;
+        hipLaunchKernelGGL((k_amg_spmv_dots_cols<T, QC>), dim3((unsigned)L.np), dim3(256), 0, st, L.n, L.rp, L.ci, L.a, x, y, p0, q0, p1, q1, p2, q2, L.qpart.p);
+    });
+}
+constexpr AmgCycleOps kScalarOps{scalar_pre_restrict, scalar_post, scalar_spmv_dots, scalar_pre_restrict_cols, scalar_post_cols, scalar_spmv_dots_cols};
 
 // the hierarchy of A with (absorb) or without absorption on every level; *stalled: the answer is the "coarsening stalled above the dense limit" refusal
 int amg_build_pass(fdapde_ctx* c, AmgHierarchy** slot, const double* A, int use_bnd, bool symmetric, int absorb, bool* stalled) {
@@ -622,6 +868,20 @@ int amg_build(fdapde_ctx* c, AmgHierarchy** slot, const double* A, int use_bnd, 
     return amg_build_retry(c, slot, [&](int absorb, bool* stalled) { return amg_build_pass(c, slot, A, use_bnd, symmetric, absorb, stalled); });
 }
 
+// fdapde_amg_cols_trace: since the hierarchy was built, the Q-column runs, the columns they took and the columns solved one by one
+int amg_cols_trace(const AmgHierarchy* H, int32_t* batches, int32_t* batched_cols, int32_t* single_cols) {
+    if (!H) return FDAPDE_ENOTINIT;
+    if (batches) *batches = (int32_t)H->batches;
+    if (batched_cols) *batched_cols = (int32_t)H->batched_cols;
+    if (single_cols) *single_cols = (int32_t)H->single_cols;
+    return FDAPDE_OK;
+}
+
+// (a hierarchy fdapde_lin_compute has outlived is not live: the next solve builds the new matrix's, and its trace starts at zero)
+int amg_lin_cols_trace(const fdapde_ctx* c, int32_t* batches, int32_t* batched_cols, int32_t* single_cols) {
+    return amg_cols_trace(c->amg_lin && c->amg_lin->key == c->amg_lin_epoch ? c->amg_lin : nullptr, batches, batched_cols, single_cols);
+}
+
 // fdapde_amg_hierarchy: rows and entries per level, counted in scalar unknowns (H->per of them to a node)
 int amg_describe(const AmgHierarchy* H, int32_t cap, int32_t* n_levels, int64_t* rows, int64_t* nnz, int32_t* absorbed, double* setup_ms) {
     if (!H) return FDAPDE_ENOTINIT;
@@ -668,6 +928,139 @@ int amg_cycle(fdapde_ctx* c, AmgHierarchy& H, size_t l, const double* r, double*
     return FDAPDE_OK;
 }
 
+// ---- the recursion for Q interleaved columns: the launches of amg_correction / amg_cycle in the same order, every one for all columns at once
+int amg_cols_width(int want, int64_t n_words, int mk) {
+    int Q = want >= 8 ? 8 : want >= 4 ? 4 : want >= 2 ? 2 : 1;
+    while (Q > 1 && (double)Q * (double)(2 * mk + 1) * (double)n_words * 8.0 > 16e9) Q /= 2;
+    return Q;
+}
+
+int amg_cols_prepare(fdapde_ctx* c, AmgHierarchy& H, int Q) {
+    hipStream_t st = c->stream;
+    for (size_t l = 0; l < H.lv.size(); ++l) {
+        AmgLevel& L = *H.lv[l];
+        if (L.qcols == Q) continue;
+        const size_t nw = (size_t)H.per * (size_t)std::max<int64_t>(L.n, 1) * (size_t)Q;
+        const bool last = l + 1 == H.lv.size();
+        for (DBuf<double>* p : {&L.qb, &L.qzt, &L.qcv, &L.qv, &L.qdv, &L.qw, &L.qrt, &L.qe}) HIPCHK(c, p->alloc(nw));
+        if (last) HIPCHK(c, L.qecm.alloc(nw));
+        HIPCHK(c, hipMemsetAsync(L.qzt.p, 0, sizeof(double) * nw, st));   // (rows of no aggregate are never written: their 0 stays -- in this width's layout)
+        HIPCHK(c, L.qpart.alloc(3 * (size_t)Q * (size_t)std::max(L.np, 1024)));
+        HIPCHK(c, L.qsc.alloc(8 * (size_t)kAmgColsMax));
+        HIPCHK(c, hipMemsetAsync(L.qsc.p, 0, 8 * (size_t)kAmgColsMax * sizeof(double), st));
+        L.qcols = Q;
+    }
+    return FDAPDE_OK;
+}
+
+int amg_dense_cols(fdapde_ctx* c, AmgHierarchy& H, int Q, const double* v, double* z) {
+    AmgLevel& L = *H.lv.back();
+    const int64_t nw = H.per * L.n;
+    hipLaunchKernelGGL(k_amg_il2cm, dim3(gn(nw * Q)), dim3(256), 0, c->stream, nw, Q, v, L.qb.p);
+    if (int rc = dense_apply(c, H.D, Q, L.qb.p, L.qecm.p)) return rc;
+    hipLaunchKernelGGL(k_amg_cm2il, dim3(gn(nw * Q)), dim3(256), 0, c->stream, nw, Q, (const double*)L.qecm.p, z);
+    return FDAPDE_OK;
+}
+
+namespace {
+int amg_correction_cols(fdapde_ctx* c, AmgHierarchy& H, size_t m, int Q) {
+    hipStream_t st = c->stream;
+    AmgLevel& L = *H.lv[m];
+    const int64_t n = H.per * L.n;
+    if (m + 1 == H.lv.size()) {   // (qb arrived column-major: amg_cycle_cols)
+        if (int rc = dense_apply(c, H.D, Q, L.qb.p, L.qecm.p)) return rc;
+        hipLaunchKernelGGL(k_amg_cm2il, dim3(gn(n * Q)), dim3(256), 0, st, n, Q, (const double*)L.qecm.p, L.qe.p);
+        return FDAPDE_OK;
+    }
+    double *b = L.qb.p, *cv = L.qcv.p, *v = L.qv.p, *rt = L.qrt.p, *dv = L.qdv.p, *w = L.qw.p;
+    if (int rc = amg_cycle_cols(c, H, m, Q, b, cv)) return rc;
+    if (H.sym) H.ops->spmv_dots_cols(st, Q, L, cv, v, cv, v, cv, b, nullptr, nullptr);
+    else H.ops->spmv_dots_cols(st, Q, L, cv, v, v, v, v, b, nullptr, nullptr);
+    hipLaunchKernelGGL(k_amg_coef_cols, dim3((unsigned)Q), dim3(256), 0, st, L.qpart.p, L.np, Q, 1, L.qsc.p);
+    by_cols(Q, [&](auto q) {
+        constexpr int QC = decltype(q)::value;
+        hipLaunchKernelGGL(k_amg_axpy_sc_cols<QC>, dim3(gn(n)), dim3(256), 0, st, n, b, v, L.qsc.p, rt);
+    });
+    if (int rc = amg_cycle_cols(c, H, m, Q, rt, dv)) return rc;
+    if (H.sym) H.ops->spmv_dots_cols(st, Q, L, dv, w, dv, v, dv, w, dv, rt);
+    else H.ops->spmv_dots_cols(st, Q, L, dv, w, v, w, w, w, w, rt);
+    hipLaunchKernelGGL(k_amg_coef_cols, dim3((unsigned)Q), dim3(256), 0, st, L.qpart.p, L.np, Q, 2, L.qsc.p);
+    by_cols(Q, [&](auto q) {
+        constexpr int QC = decltype(q)::value;
+        hipLaunchKernelGGL(k_amg_comb2_cols<QC>, dim3(gn(n)), dim3(256), 0, st, n, cv, dv, L.qsc.p, L.qe.p);
+    });
+    return FDAPDE_OK;
+}
+}   // namespace
+
+int amg_cycle_cols(fdapde_ctx* c, AmgHierarchy& H, size_t l, int Q, const double* r, double* out) {
+    AmgLevel &L = *H.lv[l], &N = *H.lv[l + 1];
+    const bool dense_next = l + 2 == H.lv.size();   // the coarsest level's right-hand side goes out column-major: what dense_apply takes
+    H.ops->pre_restrict_cols(c->stream, Q, L, N, r, N.qb.p, dense_next ? 1 : Q, dense_next ? H.per * N.n : 1);
+    if (int rc = amg_correction_cols(c, H, l + 1, Q)) return rc;
+    H.ops->post_cols(c->stream, Q, L, N, r, out);
+    return FDAPDE_OK;
+}
+
+namespace {
+// amg_run for Q columns of the handle (no Dirichlet rows, no warm start): f, x interleaved on the device (x is written).  Per column what amg_run does, the
+// outer iteration in lockstep (fgmres_outer_cols); relres: the true relative residuals of what is handed out
+int amg_run_cols(fdapde_ctx* c, AmgHierarchy& H, const double* A, int Q, const double* f, double* x, double* r, double* t, double rtol, int maxit, int mk, FgmresCols& S,
+                 double* relres) {
+    hipStream_t st = c->stream;
+    AmgLevel& L0 = *H.lv[0];
+    const int64_t n = L0.n;
+    H.np = (int)std::min<int64_t>(1024, std::max<int64_t>(1, (n + 4095) / 4096));
+    if (int rc = amg_cols_prepare(c, H, Q)) return rc;
+    HIPCHK(c, H.basis.alloc((size_t)Q * (size_t)(2 * mk + 1) * (size_t)n));
+    HIPCHK(c, H.part.alloc((size_t)Q * (size_t)(mk + 2) * (size_t)H.np));
+    HIPCHK(c, H.dots.alloc((size_t)Q * (size_t)(mk + 4)));
+    double h[kAmgColsMax];
+    auto dots = [&](const double* a0) -> int {
+        fixed_dots_cols(st, n, H.np, Q, a0, a0, H.part.p, H.dots.p);
+        HIPCHK(c, hipMemcpyAsync(h, H.dots.p, sizeof(double) * (size_t)Q, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        return FDAPDE_OK;
+    };
+    auto apply_K = [&](const double* in, const double* rhs, double* out) {
+        by_team_cols<4>(L0.team, Q, [&](auto tt, auto q) {
+            constexpr int T = decltype(tt)::value, QC = decltype(q)::value;
+            hipLaunchKernelGGL((k_amg_apply_K_cols<T, QC>), dim3(gn(n * T)), dim3(256), 0, st, n, L0.rp, L0.ci, A, (const uint8_t*)nullptr, 0, in, rhs, (const double*)nullptr, out);
+        });
+    };
+    hipLaunchKernelGGL(k_amg_start_cols, dim3(gn(n * Q)), dim3(256), 0, st, n, Q, (const uint8_t*)nullptr, 0, (const double*)nullptr, (const double*)nullptr, x);
+    apply_K(x, f, r);
+    if (int rc = dots(r)) return rc;
+    for (int q = 0; q < Q; ++q) S.bb[q] = S.rr[q] = h[q], S.converged[q] = S.rr[q] <= rtol * rtol * S.bb[q], S.broke[q] = false;
+    const bool one_level = H.lv.size() == 1;
+    auto precond = [&](const double* v, double* z, double* w) -> int {
+        if (one_level) {
+            if (int rc = amg_dense_cols(c, H, Q, v, z)) return rc;
+        } else if (int rc = amg_cycle_cols(c, H, 0, Q, v, z))
+            return rc;
+        apply_K(z, nullptr, w);
+        return FDAPDE_OK;
+    };
+    auto residual = [&](double* rr_out) -> int {
+        apply_K(x, f, r);
+        if (int rc = dots(r)) return rc;
+        std::copy(h, h + Q, rr_out);
+        return FDAPDE_OK;
+    };
+    FgmresSpace fs{n, mk, H.basis.p, H.basis.p + (size_t)(mk + 1) * (size_t)n * (size_t)Q, H.part.p, H.dots.p, H.np};
+    if (int rc = fgmres_outer_cols(c, fs, Q, x, r, rtol, maxit, precond, residual, S)) return rc;
+    // the TRUE residuals of what is handed out
+    apply_K(x, f, t);
+    if (int rc = dots(t)) return rc;
+    for (int q = 0; q < Q; ++q) {
+        relres[q] = S.bb[q] > 0 ? std::sqrt(h[q] / S.bb[q]) : 0.0;
+        if (S.converged[q] && !(relres[q] <= 10.0 * rtol)) S.converged[q] = false;
+    }
+    HIPCHK(c, hipGetLastError());
+    return FDAPDE_OK;
+}
+}   // namespace
+
 int amg_run(fdapde_ctx* c, AmgHierarchy* hp, const double* A, const double* f_dev, const double* g_dev, int use_bnd, const double* x0_dev, double rtol, int maxit) {
     AmgHierarchy& H = *hp;
     HIPCHK(c, hipSetDevice(c->device));
@@ -677,8 +1070,7 @@ int amg_run(fdapde_ctx* c, AmgHierarchy* hp, const double* A, const double* f_de
     const auto t_begin = std::chrono::steady_clock::now();
     const dim3 gv(gn(n)), bv(256);
     H.np = (int)std::min<int64_t>(1024, std::max<int64_t>(1, (n + 4095) / 4096));
-    int mk = (int)std::min<int64_t>(50, std::max<int64_t>(5, (int64_t)(16e9 / (16.0 * (double)n))));   // (at most ~16 GB of basis)
-    mk = std::max(1, std::min(mk, std::max(maxit, 1)));
+    const int mk = amg_restart_len(n, maxit);
     HIPCHK(c, H.vec.alloc(3 * (size_t)n));
     HIPCHK(c, H.basis.alloc((size_t)(2 * mk + 1) * (size_t)n));
     HIPCHK(c, H.part.alloc((size_t)(mk + 2) * (size_t)H.np));
@@ -786,7 +1178,7 @@ void amg_forget(fdapde_ctx* c) {
 }
 
 // fdapde_lin_solve with FDAPDE_SOLVER_AMG: the hierarchy of the handle's matrix (no Dirichlet reduction), built by the first solve after fdapde_lin_compute and
-// shared by every later column; columns one after the other
+// shared by every later column; the columns in batches of 8, 4 and 2 side by side (amg_run_cols; knob amg_cols), a last one alone
 int amg_lin_solve(fdapde_ctx* c, const fdapde_options* opt, const double* b, int32_t n_rhs, double* x, fdapde_info* info) {
     if (!amg_eligible(c)) return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_AMG takes one-GPU contexts");
     const double rtol = (opt && opt->rtol > 0) ? opt->rtol : 1e-10;
@@ -808,7 +1200,46 @@ int amg_lin_solve(fdapde_ctx* c, const fdapde_options* opt, const double* b, int
     HIPCHK(c, rhs.alloc((size_t)n));
     int total = 0, rc_all = FDAPDE_OK;
     double worst = 0.0;
-    for (int32_t j = 0; j < n_rhs; ++j) {
+    AmgHierarchy& H = *c->amg_lin;
+    const int mk = amg_restart_len(n, maxit);   // (amg_run's restart length: a batch keeps it)
+    for (int32_t j = 0; j < n_rhs;) {
+        // batches of 8, then 4, then 2 columns (knob amg_cols: the widest; narrower where the basis budget asks for it); a last single column as before
+        const int32_t left = n_rhs - j;
+        const int Q = amg_cols_width(std::min<int32_t>(left, c->amg_cols), n, mk);
+        if (Q > 1) {
+            const size_t nq = (size_t)n * (size_t)Q;
+            HIPCHK(c, H.qio.alloc(nq));
+            HIPCHK(c, H.qvec.alloc(4 * nq));
+            double *f = H.qvec.p, *xq = f + nq, *r = xq + nq, *t = r + nq;
+            HIPCHK(c, hipMemcpyAsync(H.qio.p, b + (size_t)j * n, sizeof(double) * nq, hipMemcpyHostToDevice, st));   // (one copy per batch)
+            hipLaunchKernelGGL(k_amg_gather_cols, dim3(gn(n * Q)), dim3(256), 0, st, n, Q, c->dof_i2e.p, (const double*)H.qio.p, f);
+            FgmresCols S{};
+            double rel[kAmgColsMax];
+            if (int rc = amg_run_cols(c, H, c->lin_mat.p, Q, f, xq, r, t, rtol, maxit, mk, S, rel)) return rc;
+            ++H.batches, H.batched_cols += Q;
+            for (int q = 0; q < Q; ++q) {
+                bool conv = S.converged[q];
+                int its = S.it[q];
+                if (S.handed[q]) {   // the recurrence and the true residual disagreed: the rest of this column on the single-column path, from its iterate
+                    hipLaunchKernelGGL(k_amg_col_get, dim3(gn(n)), dim3(256), 0, st, n, Q, q, (const double*)f, rhs.p);
+                    hipLaunchKernelGGL(k_amg_col_get, dim3(gn(n)), dim3(256), 0, st, n, Q, q, (const double*)xq, c->tmp_e.p);
+                    const int rc = amg_run(c, c->amg_lin, c->lin_mat.p, rhs.p, nullptr, 0, c->tmp_e.p, rtol, maxit - its);
+                    if (rc != FDAPDE_OK && rc != FDAPDE_ENOCONV) return rc;
+                    hipLaunchKernelGGL(k_amg_col_put, dim3(gn(n)), dim3(256), 0, st, n, Q, q, (const double*)c->u.p, xq);
+                    conv = rc == FDAPDE_OK, its += c->info.iters, rel[q] = c->info.relres;
+                    ++H.single_cols;
+                }
+                if (!conv) rc_all = FDAPDE_ENOCONV;
+                total += its, worst = std::max(worst, rel[q]);
+            }
+            hipLaunchKernelGGL(k_amg_scatter_cols, dim3(gn(n * Q)), dim3(256), 0, st, n, Q, c->dof_i2e.p, (const double*)xq, H.qio.p);
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipMemcpyAsync(x + (size_t)j * n, H.qio.p, sizeof(double) * nq, hipMemcpyDeviceToHost, st));
+            HIPCHK(c, hipStreamSynchronize(st));
+            j += Q;
+            continue;
+        }
+        ++H.single_cols;
         HIPCHK(c, hipMemcpyAsync(c->tmp_e.p, b + (size_t)j * n, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_amg_gather, dim3(gn(n)), dim3(256), 0, st, n, c->dof_i2e.p, c->tmp_e.p, rhs.p);
         const int rc = amg_run(c, c->amg_lin, c->lin_mat.p, rhs.p, nullptr, 0, nullptr, rtol, maxit);
@@ -818,7 +1249,11 @@ int amg_lin_solve(fdapde_ctx* c, const fdapde_options* opt, const double* b, int
         hipLaunchKernelGGL(k_amg_scatter, dim3(gn(n)), dim3(256), 0, st, n, c->dof_i2e.p, c->u.p, c->tmp_e.p);
         HIPCHK(c, hipMemcpyAsync(x + (size_t)j * n, c->tmp_e.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));   // (tmp_e is reused by the next column)
+        ++j;
     }
+    const double t_asm = c->info.t_assemble_ms;
+    c->info = fdapde_info{};
+    c->info.t_assemble_ms = t_asm;
     c->info.iters = total, c->info.relres = worst, c->info.converged = rc_all == FDAPDE_OK ? 1 : 0, c->info.method_used = FDAPDE_SOLVER_AMG, c->info.persistent = 0;
     c->info.t_solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (rc_all != FDAPDE_OK) c->err = "FDAPDE_SOLVER_AMG: maxit reached in at least one column";

@@ -61,6 +61,9 @@ void block_amg_forget(fdapde_ctx* c) {
 int block_amg_describe_ctx(const fdapde_ctx* c, int32_t cap, int32_t* n_levels, int64_t* rows, int64_t* nnz, int32_t* absorbed, double* setup_ms) {
     return block_amg_describe(c->block ? c->block->amg : nullptr, cap, n_levels, rows, nnz, absorbed, setup_ms);
 }
+int block_amg_cols_trace_ctx(const fdapde_ctx* c, int32_t* batches, int32_t* batched_cols, int32_t* single_cols) {
+    return block_amg_cols_trace(c->block ? c->block->amg : nullptr, batches, batched_cols, single_cols);
+}
 int block_amg_aggregates_ctx(fdapde_ctx* c, int32_t level, int64_t cap, int32_t* agg, int64_t* n_rows) {
     return block_amg_aggregates(c, c->block ? c->block->amg : nullptr, level, cap, agg, n_rows);
 }
@@ -155,7 +158,7 @@ int block_dense_build(fdapde_ctx* c, BlockHandle& B) {
     return dense_build_csr(c, 2 * n, B.rowptr2.p, B.colidx2.p, B.val2.p, nullptr, 0, B.dense);
 }
 
-// FDAPDE_SOLVER_BLOCK_AMG by name: the hierarchy built by the first such solve after fdapde_block_compute, the columns one after another on the UNSCALED
+// FDAPDE_SOLVER_BLOCK_AMG by name: the hierarchy built by the first such solve after fdapde_block_compute, the columns in batches side by side (knob amg_cols) on the UNSCALED
 // system (stop rule: the true residual |b - A x| <= rtol |b| -- not the D^-1-scaled one of the GMRES stage)
 int block_amg_solve(fdapde_ctx* c, BlockHandle& B, const fdapde_options* opt, const double* b, int32_t n_rhs, double* x, fdapde_info* info) {
     const int64_t n = B.n, n2 = 2 * n;
@@ -175,11 +178,25 @@ int block_amg_solve(fdapde_ctx* c, BlockHandle& B, const fdapde_options* opt, co
             return rc;
         }
     }
-    HIPCHK(c, B.ext.alloc((size_t)std::max<int64_t>(4 * B.nnz, 2 * n)));
+    HIPCHK(c, B.ext.alloc((size_t)std::max<int64_t>(4 * B.nnz, n2 * kAmgColsMax)));
     int total = 0, rc_all = FDAPDE_OK;   // (B.cols and B.krylov_ms stay: the open method's rent-or-buy rule counts its own columns only)
     double worst = 0;
     bool broke_any = false;
     for (int32_t j = 0; j < n_rhs; ++j) {
+        // batches of 8, then 4, then 2 columns side by side (knob amg_cols; one host <-> device copy per batch), a last single column as before
+        const int Q = block_amg_width(c, B.amg, n_rhs - j, maxit);
+        if (Q > 1) {
+            const size_t cnt = (size_t)n2 * (size_t)Q;
+            HIPCHK(c, hipMemcpyAsync(B.ext.p, b + (size_t)j * n2, sizeof(double) * cnt, hipMemcpyHostToDevice, st));
+            bool not_conv = false;
+            if (int rc = block_amg_batch(c, B.amg, B.raw.p, Q, B.ext.p, B.bt.p, B.x.p, rtol, maxit, &total, &worst, &not_conv, &broke_any)) return rc;
+            if (not_conv) rc_all = FDAPDE_ENOCONV;
+            HIPCHK(c, hipMemcpyAsync(x + (size_t)j * n2, B.ext.p, sizeof(double) * cnt, hipMemcpyDeviceToHost, st));
+            HIPCHK(c, hipStreamSynchronize(st));
+            j += Q - 1;
+            continue;
+        }
+        block_amg_count_single(B.amg);
         HIPCHK(c, hipMemcpyAsync(B.ext.p, b + (size_t)j * n2, sizeof(double) * (size_t)n2, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_block_stage, dim3(g1(n), 1), dim3(256), 0, st, n, c->dof_i2e.p, B.ext.p, nullptr, B.bt.p);
         int it = 0;

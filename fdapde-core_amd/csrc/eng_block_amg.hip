@@ -37,6 +37,8 @@ using namespace fdapde_hip;
 
 constexpr double kBamgOmega = 0.7;   // the smoother's damping: fixed (the spectrum of D^-1 A is not one-sided: no power iteration)
 constexpr int kBamgMaxRestart = 64;  // fgmres_outer's Gram-Schmidt kernels hold that many coefficients
+// the restart length of the outer iteration: the knob gmres_m, never more than maxit -- one rule for the single-column run and for a batch
+inline int block_restart_len(const fdapde_ctx* c, int maxit) { return std::max(1, std::min(std::min(c->gmres_m, kBamgMaxRestart), std::max(maxit, 1))); }
 
 // a level: the scalar level (n block rows; a = the strength matrix on the pattern; agg, mptr, midx; team, np; the work vectors at 2 n words) and its blocks
 struct BamgLevel : AmgLevel {
@@ -110,7 +112,28 @@ void block_spmv_dots(hipStream_t st, AmgLevel& L, const double* x, double* y, co
                            (const int32_t*)nullptr);
     });
 }
-constexpr AmgCycleOps kBlockOps{block_pre_restrict, block_post, block_spmv_dots};
+void block_pre_restrict_cols(hipStream_t st, int Q, AmgLevel& L, AmgLevel& N, const double* r, double* rc, int64_t rs, int64_t cs) {
+    by_team_cols<8>(L.team, Q, [&](auto t, auto q) {
+        constexpr int T = decltype(t)::value, QC = decltype(q)::value;
+        hipLaunchKernelGGL((k_bamg_pre_restrict_cols<T, QC>), dim3(g1(N.n, 256 / T)), dim3(256), 0, st, N.n, L.mptr.p, L.midx.p, L.rp, L.ci, blk(L).bv, blk(L).dinv4.p, kBamgOmega,
+                           r, L.qzt.p, rc, rs, cs);
+    });
+}
+void block_post_cols(hipStream_t st, int Q, AmgLevel& L, AmgLevel& N, const double* r, double* out) {
+    by_team_cols<8>(L.team, Q, [&](auto t, auto q) {
+        constexpr int T = decltype(t)::value, QC = decltype(q)::value;
+        hipLaunchKernelGGL((k_bamg_post_cols<T, QC>), dim3(g1(L.n, 256 / T)), dim3(256), 0, st, L.n, L.rp, L.ci, blk(L).bv, blk(L).dinv4.p, kBamgOmega, L.agg.p, N.qe.p, r,
+                           L.qzt.p, out);
+    });
+}
+void block_spmv_dots_cols(hipStream_t st, int Q, AmgLevel& L, const double* x, double* y, const double* p0, const double* q0, const double* p1, const double* q1,
+                          const double* p2, const double* q2) {
+    by_team_cols<8>(L.team, Q, [&](auto t, auto q) {
+        constexpr int T = decltype(t)::value, QC = decltype(q)::value;
+        hipLaunchKernelGGL((k_bamg_spmv_dots_cols<T, QC>), dim3((unsigned)L.np), dim3(256), 0, st, L.n, L.rp, L.ci, blk(L).bv, x, y, p0, q0, p1, q1, p2, q2, L.qpart.p);
+    });
+}
+constexpr AmgCycleOps kBlockOps{block_pre_restrict, block_post, block_spmv_dots, block_pre_restrict_cols, block_post_cols, block_spmv_dots_cols};
 
 // the hierarchy with (absorb) or without absorption on every level; *stalled: the answer is the "coarsening stalled above the dense limit" refusal
 int block_amg_build_pass(fdapde_ctx* c, BlockAmg** slot, const double* raw, int strength_block, int absorb, bool* stalled) {
@@ -214,15 +237,19 @@ int block_amg_aggregates(fdapde_ctx* c, const BlockAmg* H, int32_t level, int64_
     return FDAPDE_OK;
 }
 
-// one column: A x = b (both interleaved, internal order, on the device; x is written), raw = the matrix the hierarchy was built from
+int block_amg_cols_trace(const BlockAmg* H, int32_t* batches, int32_t* batched_cols, int32_t* single_cols) { return amg_cols_trace(H, batches, batched_cols, single_cols); }
+void block_amg_count_single(BlockAmg* H) { ++H->single_cols; }
+
+// one column: A x = b (both interleaved, internal order, on the device; x is written -- warm: x holds the iterate to start from), raw = the matrix the
+// hierarchy was built from
 int block_amg_run(fdapde_ctx* c, BlockAmg* hp, const double* raw, const double* b_dev, double* x_dev, double rtol, int maxit, int* iters, double* relres,
-                  bool* converged_out, bool* broke_out) {
+                  bool* converged_out, bool* broke_out, bool warm) {
     BlockAmg& H = *hp;
     hipStream_t st = c->stream;
     AmgLevel& L0 = *H.lv[0];
     const int64_t n = L0.n, n2 = 2 * n;
     const int np = (int)std::min<int64_t>(1024, std::max<int64_t>(1, (n2 + 4095) / 4096));
-    const int mk = std::max(1, std::min(std::min(c->gmres_m, kBamgMaxRestart), std::max(maxit, 1)));
+    const int mk = block_restart_len(c, maxit);
     HIPCHK(c, H.vec.alloc(2 * (size_t)n2));
     HIPCHK(c, H.basis.alloc((size_t)(2 * mk + 1) * (size_t)n2));
     HIPCHK(c, H.part.alloc((size_t)(mk + 2) * (size_t)np + 3 * (size_t)np));
@@ -238,13 +265,20 @@ int block_amg_run(fdapde_ctx* c, BlockAmg* hp, const double* raw, const double* 
         HIPCHK(c, hipStreamSynchronize(st));
         return FDAPDE_OK;
     };
-    HIPCHK(c, hipMemsetAsync(x, 0, sizeof(double) * (size_t)n2, st));
+    if (!warm) HIPCHK(c, hipMemsetAsync(x, 0, sizeof(double) * (size_t)n2, st));
     HIPCHK(c, hipMemcpyAsync(r, b_dev, sizeof(double) * (size_t)n2, hipMemcpyDeviceToDevice, st));
     if (int rc = dots(r)) return rc;
     const double bb = h[0];
     double rr = bb;
     int it = 0;
     bool converged = !(bb > 0.0) && std::isfinite(bb), broke = !std::isfinite(bb);
+    if (warm && !converged && !broke) {   // (a column a batch handed back: the residual of its iterate starts the first cycle)
+        spmv(x, t);
+        hipLaunchKernelGGL(k_bamg_residual, dim3(gn(n2)), dim3(256), 0, st, n2, b_dev, t, r);
+        if (int rc = dots(r)) return rc;
+        rr = h[0];
+        if (!std::isfinite(rr)) broke = true;
+    }
     const bool one_level = H.lv.size() == 1;
     auto precond = [&](const double* v, double* z, double* w, bool&) -> int {
         if (one_level) {
@@ -270,6 +304,95 @@ int block_amg_run(fdapde_ctx* c, BlockAmg* hp, const double* raw, const double* 
     }
     HIPCHK(c, hipGetLastError());
     *iters = it, *relres = bb > 0.0 ? std::sqrt(rr / bb) : 0.0, *converged_out = converged, *broke_out = broke;
+    return FDAPDE_OK;
+}
+
+// the widest batch for `left` columns under the knob amg_cols and the basis budget (amg_cols_width); block_amg_run's restart length is kept
+int block_amg_width(const fdapde_ctx* c, const BlockAmg* H, int32_t left, int maxit) {
+    const int mk = block_restart_len(c, maxit);
+    return amg_cols_width(std::min<int32_t>(left, c->amg_cols), 2 * H->lv[0]->n, mk);
+}
+
+// Q columns side by side: ext (device) holds them stacked in the reference numbering, column q at ext + 2 n q, and receives the solutions.  Per column what
+// block_amg_run does, the outer iteration in lockstep (fgmres_outer_cols); a column handed back is finished by block_amg_run itself from its iterate (col_b,
+// col_x: one column of scratch each).  iters is added to, worst / not_conv / broke_any follow block_amg_solve's rules
+int block_amg_batch(fdapde_ctx* c, BlockAmg* hp, const double* raw, int Q, double* ext, double* col_b, double* col_x, double rtol, int maxit, int* iters, double* worst,
+                    bool* not_conv, bool* broke_any) {
+    BlockAmg& H = *hp;
+    hipStream_t st = c->stream;
+    AmgLevel& L0 = *H.lv[0];
+    const int64_t n = L0.n, n2 = 2 * n;
+    const size_t nq = (size_t)n2 * (size_t)Q;
+    const int np = (int)std::min<int64_t>(1024, std::max<int64_t>(1, (n2 + 4095) / 4096));
+    const int mk = block_restart_len(c, maxit);
+    if (int rc = amg_cols_prepare(c, H, Q)) return rc;
+    HIPCHK(c, H.qvec.alloc(4 * nq));
+    HIPCHK(c, H.basis.alloc((size_t)(2 * mk + 1) * nq));
+    HIPCHK(c, H.part.alloc((size_t)Q * ((size_t)(mk + 2) * (size_t)np + 3 * (size_t)np)));
+    HIPCHK(c, H.dots.alloc((size_t)Q * (size_t)(mk + 4)));
+    double *b = H.qvec.p, *x = b + nq, *r = x + nq, *t = r + nq;
+    hipLaunchKernelGGL(k_block_stage_cols, dim3(gn(n * Q)), dim3(256), 0, st, n, Q, c->dof_i2e.p, (const double*)ext, b);
+    double h[kAmgColsMax];
+    auto spmv = [&](const double* in, double* out) {
+        by_cols(Q, [&](auto q) {
+            constexpr int QC = decltype(q)::value;
+            hipLaunchKernelGGL((k_block_spmv_cols<kBlockTeam, QC>), dim3(g1(n, 256 / kBlockTeam)), dim3(256), 0, st, n, L0.rp, L0.ci, raw, in, out);
+        });
+    };
+    auto dots = [&](const double* a0) -> int {
+        fixed_dots_cols(st, n2, np, Q, a0, a0, H.part.p, H.dots.p);
+        HIPCHK(c, hipMemcpyAsync(h, H.dots.p, sizeof(double) * (size_t)Q, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        return FDAPDE_OK;
+    };
+    HIPCHK(c, hipMemsetAsync(x, 0, sizeof(double) * nq, st));
+    HIPCHK(c, hipMemcpyAsync(r, b, sizeof(double) * nq, hipMemcpyDeviceToDevice, st));
+    if (int rc = dots(r)) return rc;
+    FgmresCols S{};
+    for (int q = 0; q < Q; ++q) S.bb[q] = S.rr[q] = h[q], S.converged[q] = !(h[q] > 0.0) && std::isfinite(h[q]), S.broke[q] = !std::isfinite(h[q]);
+    const bool one_level = H.lv.size() == 1;
+    auto precond = [&](const double* v, double* z, double* w) -> int {
+        if (one_level) {
+            if (int rc = amg_dense_cols(c, H, Q, v, z)) return rc;
+        } else if (int rc = amg_cycle_cols(c, H, 0, Q, v, z))
+            return rc;
+        spmv(z, w);
+        return FDAPDE_OK;
+    };
+    auto residual = [&](double* rr_out) -> int {   // the TRUE residuals of the iterates
+        spmv(x, t);
+        hipLaunchKernelGGL(k_bamg_residual, dim3(gn((int64_t)nq)), dim3(256), 0, st, (int64_t)nq, (const double*)b, (const double*)t, r);
+        if (int rc = dots(r)) return rc;
+        std::copy(h, h + Q, rr_out);
+        return FDAPDE_OK;
+    };
+    FgmresSpace fs{n2, mk, H.basis.p, H.basis.p + (size_t)(mk + 1) * nq, H.part.p, H.dots.p, np};
+    if (int rc = fgmres_outer_cols(c, fs, Q, x, r, rtol, maxit, precond, residual, S)) return rc;
+    double rr[kAmgColsMax];
+    if (int rc = residual(rr)) return rc;   // what is handed out is judged by its own residual, whichever way the loop ended
+    HIPCHK(c, hipGetLastError());
+    ++H.batches, H.batched_cols += Q;
+    for (int q = 0; q < Q; ++q) {
+        int it = S.it[q];
+        bool conv = S.converged[q], broke = S.broke[q];
+        double rel = 0.0;
+        if (S.handed[q]) {   // the recurrence and the true residual disagreed: the rest of this column by block_amg_run, from its iterate
+            hipLaunchKernelGGL(k_amg_col_get, dim3(gn(n2)), dim3(256), 0, st, n2, Q, q, (const double*)b, col_b);
+            hipLaunchKernelGGL(k_amg_col_get, dim3(gn(n2)), dim3(256), 0, st, n2, Q, q, (const double*)x, col_x);
+            int it1 = 0;
+            if (int rc = block_amg_run(c, hp, raw, col_b, col_x, rtol, maxit - it, &it1, &rel, &conv, &broke, true)) return rc;
+            hipLaunchKernelGGL(k_amg_col_put, dim3(gn(n2)), dim3(256), 0, st, n2, Q, q, (const double*)col_x, x);
+            it += it1, ++H.single_cols;
+        } else if (S.bb[q] > 0.0 && std::isfinite(S.bb[q])) {
+            conv = std::isfinite(rr[q]) && rr[q] <= rtol * rtol * S.bb[q];
+            rel = std::sqrt(rr[q] / S.bb[q]);
+        } else
+            rel = S.bb[q] > 0.0 ? std::sqrt(S.rr[q] / S.bb[q]) : 0.0;
+        if (!conv) *not_conv = true, *broke_any = *broke_any || broke;
+        *iters += it, *worst = rel > *worst || std::isnan(rel) ? rel : *worst;
+    }
+    hipLaunchKernelGGL(k_block_unstage_cols, dim3(gn(n * Q)), dim3(256), 0, st, n, Q, c->dof_i2e.p, (const double*)x, ext);
+    HIPCHK(c, hipGetLastError());
     return FDAPDE_OK;
 }
 

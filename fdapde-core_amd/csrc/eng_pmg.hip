@@ -29,6 +29,7 @@
 
 #include "context.h"
 #include "engine.h"
+#include "kernels_cols.h"
 #include "kernels_reduce.h"
 
 namespace fdapde_engine {
@@ -231,6 +232,138 @@ __global__ __launch_bounds__(256) void k_pmg_comb(int64_t n, const double* Z, in
     for (int q = 0; q < k; ++q) s += ys[q] * Z[(int64_t)q * stride + i];
     x[i] += dinv ? s * dinv[i] : s;
 }
+// ---- the same kernels for Q interleaved columns (kernels_cols.h): Q independent Krylov spaces side by side, basis vector b at V + b * stride with
+// stride = n Q.  A column's sums run over the same elements in the same order as in the single-column kernel above it (the same grid, the same wave_sum,
+// the same four-wave sum, the same k_pmg_mreduce behind it): the column's bits are those of a single-column run.  Value (b, q) of a launch: part[(b Q + q) np ..]
+template <int Q> __global__ __launch_bounds__(256) void k_pmg_dots_cols(int64_t n, const double* a, const double* b, double* part) {
+    __shared__ double red[Q][4];
+    double s[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) s[q] = 0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        double av[Q], bv[Q];
+        ld_cols<Q>(a + i * Q, av), ld_cols<Q>(b + i * Q, bv);
+#pragma unroll
+        for (int q = 0; q < Q; ++q) s[q] += av[q] * bv[q];
+    }
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+        const double t = wave_sum(s[q]);
+        if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = t;
+    }
+    __syncthreads();
+    if (threadIdx.x < Q) part[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
+}
+// h_(b,q) = V_b,q . w_q for b < k, and w_q . w_q behind them; 16 / Q basis vectors per sweep (sixteen accumulators)
+template <int Q> __global__ __launch_bounds__(256) void k_pmg_mdot_cols(int64_t n, const double* V, int64_t stride, int k, const double* w, double* part) {
+    constexpr int CB = 16 / Q;
+    __shared__ double red[CB * Q + Q][4];
+    const int wv = threadIdx.x >> 6;
+    for (int c0 = 0; c0 < k || c0 == 0; c0 += CB) {
+        double sq[CB][Q], sw[Q];
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            sw[q] = 0;
+#pragma unroll
+            for (int b = 0; b < CB; ++b) sq[b][q] = 0;
+        }
+        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+            double wi[Q];
+            ld_cols<Q>(w + i * Q, wi);
+#pragma unroll
+            for (int b = 0; b < CB; ++b)
+                if (c0 + b < k) {
+                    double v[Q];
+                    ld_cols<Q>(V + (int64_t)(c0 + b) * stride + i * Q, v);
+#pragma unroll
+                    for (int q = 0; q < Q; ++q) sq[b][q] += v[q] * wi[q];
+                }
+            if (c0 == 0) {
+#pragma unroll
+                for (int q = 0; q < Q; ++q) sw[q] += wi[q] * wi[q];
+            }
+        }
+#pragma unroll
+        for (int b = 0; b < CB; ++b) {
+#pragma unroll
+            for (int q = 0; q < Q; ++q) {
+                const double r = wave_sum(sq[b][q]);
+                if ((threadIdx.x & 63) == 0) red[b * Q + q][wv] = r;
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            const double r = wave_sum(sw[q]);
+            if ((threadIdx.x & 63) == 0) red[CB * Q + q][wv] = r;
+        }
+        __syncthreads();
+        const int t = threadIdx.x;
+        if (t < CB * Q && c0 + t / Q < k) part[((size_t)(c0 + t / Q) * Q + t % Q) * gridDim.x + blockIdx.x] = red[t][0] + red[t][1] + red[t][2] + red[t][3];
+        if (t >= CB * Q && t < CB * Q + Q && c0 == 0) part[((size_t)k * Q + (t - CB * Q)) * gridDim.x + blockIdx.x] = red[t][0] + red[t][1] + red[t][2] + red[t][3];
+        __syncthreads();
+    }
+}
+// w_q -= sum_b h_(b,q) V_b,q, and the partials of what is left: |w_q|^2 to part[q np + block]
+template <int Q> __global__ __launch_bounds__(256) void k_pmg_msub_cols(int64_t n, const double* V, int64_t stride, int k, const double* h, double* w, double* part) {
+    __shared__ double hs[64 * Q];
+    __shared__ double red[Q][4];
+    for (int t = threadIdx.x; t < k * Q; t += 256) hs[t] = h[t];
+    __syncthreads();
+    double sw[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) sw[q] = 0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        double wi[Q];
+        ld_cols<Q>(w + i * Q, wi);
+        for (int b = 0; b < k; ++b) {
+            double v[Q];
+            ld_cols<Q>(V + (int64_t)b * stride + i * Q, v);
+#pragma unroll
+            for (int q = 0; q < Q; ++q) wi[q] -= hs[b * Q + q] * v[q];
+        }
+        st_cols<Q>(w + i * Q, wi);
+#pragma unroll
+        for (int q = 0; q < Q; ++q) sw[q] += wi[q] * wi[q];
+    }
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+        const double r = wave_sum(sw[q]);
+        if ((threadIdx.x & 63) == 0) red[q][threadIdx.x >> 6] = r;
+    }
+    __syncthreads();
+    if (threadIdx.x < Q) part[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
+}
+// out_q = f_q a_q for the columns of the mask, 0 for the others: a column that does not run (a zero right-hand side, a frozen column, one that left the cycle) goes
+// through the batch's launches as zeros -- its slot of the basis is work space, and the cycle must not chew on whatever the allocation held
+template <int Q> __global__ void k_pmg_scale_cols(int64_t n, const double* a, ColScal f, double* out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double v[Q];
+    ld_cols<Q>(a + i * Q, v);
+#pragma unroll
+    for (int q = 0; q < Q; ++q) v[q] = ((f.mask >> q) & 1u) ? f.f[q] * v[q] : 0.0;
+    st_cols<Q>(out + i * Q, v);
+}
+// x_q += sum_b y_(b,q) Z_b,q for the columns of the mask: nothing writes to a column outside it
+template <int Q> __global__ __launch_bounds__(256) void k_pmg_comb_cols(int64_t n, const double* Z, int64_t stride, int k, const double* y, unsigned mask, double* x) {
+    __shared__ double ys[64 * Q];
+    for (int t = threadIdx.x; t < k * Q; t += 256) ys[t] = y[t];
+    __syncthreads();
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double s[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) s[q] = 0;
+    for (int b = 0; b < k; ++b) {
+        double z[Q];
+        ld_cols<Q>(Z + (int64_t)b * stride + i * Q, z);
+#pragma unroll
+        for (int q = 0; q < Q; ++q) s[q] += ys[b * Q + q] * z[q];
+    }
+#pragma unroll
+    for (int q = 0; q < Q; ++q)
+        if ((mask >> q) & 1u) x[i * Q + q] += s[q];
+}
 // a coefficient field of the fine level -- nq2 samples per cell at the order-2 rule's nodes, `width` values each -- for the coarse level: every cell's
 // weighted mean at each of the nq1 nodes of the P1 rule (a preconditioner needs the coarse OPERATOR only approximately)
 __global__ void k_pmg_cell_mean(int64_t n_cells, int nq2, int nq1, int width, const double* qw2, const int32_t* fine_cell, const double* in, double* out) {
@@ -351,6 +484,184 @@ int fgmres_outer(fdapde_ctx* c, const FgmresSpace& s, double* x, double* r, cons
             break;
         }
     }
+    return FDAPDE_OK;
+}
+
+// a_q . b_q of Q interleaved columns into out[0 .. Q-1] (device): per column the sums of fixed_dots' first product
+void fixed_dots_cols(hipStream_t st, int64_t n, int np, int Q, const double* a, const double* b, double* part, double* out) {
+    by_cols(Q, [&](auto qq) {
+        constexpr int QC = decltype(qq)::value;
+        hipLaunchKernelGGL(k_pmg_dots_cols<QC>, dim3((unsigned)np), dim3(256), 0, st, n, a, b, part);
+    });
+    hipLaunchKernelGGL(k_pmg_mreduce, dim3((unsigned)Q), dim3(256), 0, st, part, np, out);
+}
+
+// ---- fgmres_outer for Q columns side by side (the multilevel handles' batches: eng_amg.hip, eng_block_amg.hip).  Q INDEPENDENT Krylov spaces -- not a block
+// method --, vectors interleaved (kernels_cols.h), s.n words per column, basis vectors s.n Q apart; the host keeps a Hessenberg matrix and the rotations per
+// column.  The columns run in lockstep and share the cycle position: one preconditioner launch sequence, one read-back per Gram-Schmidt pass for all of them.
+// What happens to a column is what fgmres_outer does to it -- the same kernels' sums in the same order, the same host arithmetic -- so its iterate is the
+// single-column run's, bit for bit.  A column whose recurrence says "converged" (or whose new vector vanished) gets its x update and its true residual at
+// once; if that agrees the column is FROZEN (nothing writes to it any more), if not it is handed back (S.handed): fgmres_outer would restart that column alone,
+// and so does the caller, on the single-column path from the column's iterate.  A restart at s.mk vectors and maxit end all columns still running at once.
+// On entry r holds the residuals, S.rr their squares, S.bb the squared norms the stop rule is relative to, S.converged / S.broke the columns that do not
+// start; precond(v, z, w) leaves z = M^-1 v and w = A z for all Q columns, residual(rr) r = rhs - A x and its squared norms.
+int fgmres_outer_cols(fdapde_ctx* c, const FgmresSpace& s, int Q, double* x, double* r, double rtol, int maxit,
+                      const std::function<int(const double*, double*, double*)>& precond, const std::function<int(double*)>& residual, FgmresCols& S) {
+    hipStream_t st = c->stream;
+    const int64_t n = s.n, nq = s.n * Q;
+    const int mk = s.mk;
+    const dim3 gv(g1n(n)), bv(256);
+    const unsigned gnp = (unsigned)s.np;
+    double* V = s.V;
+    double* Z = s.Z;
+    struct Col {
+        std::vector<double> H, cs, sn, gg, yy;
+    };
+    std::vector<Col> col((size_t)Q);
+    for (Col& C : col) C.H.assign((size_t)(mk + 1) * mk, 0.0), C.cs.resize((size_t)mk), C.sn.resize((size_t)mk), C.gg.resize((size_t)mk + 1), C.yy.resize((size_t)mk);
+    auto Hat = [&](Col& C, int i, int j) -> double& { return C.H[(size_t)j * (mk + 1) + i]; };
+    std::vector<double> hj((size_t)(mk + 4) * Q), ybuf((size_t)mk * Q), rrv((size_t)Q), wn2((size_t)Q);
+    const double tol2 = rtol * rtol;
+    unsigned live = 0;
+    for (int q = 0; q < Q; ++q) {
+        S.it[q] = 0, S.handed[q] = false;
+        if (!S.converged[q] && !S.broke[q]) live |= 1u << q;
+    }
+    int it = 0;
+    auto scale = [&](const double* a, const ColScal& f, double* out) {
+        by_cols(Q, [&](auto qq) {
+            constexpr int QC = decltype(qq)::value;
+            hipLaunchKernelGGL(k_pmg_scale_cols<QC>, gv, bv, 0, st, n, a, f, out);
+        });
+    };
+    // x += Z y for the columns of mask, every one from its own triangular system of k columns
+    auto comb = [&](unsigned mask, int k) -> int {
+        if (!mask || k <= 0) return FDAPDE_OK;
+        std::fill(ybuf.begin(), ybuf.end(), 0.0);
+        for (int q = 0; q < Q; ++q) {
+            if (!((mask >> q) & 1u)) continue;
+            Col& C = col[(size_t)q];
+            for (int i = k - 1; i >= 0; --i) {
+                double sacc = C.gg[(size_t)i];
+                for (int p = i + 1; p < k; ++p) sacc -= Hat(C, i, p) * C.yy[(size_t)p];
+                C.yy[(size_t)i] = sacc / Hat(C, i, i);
+                ybuf[(size_t)i * Q + q] = C.yy[(size_t)i];
+            }
+        }
+        HIPCHK(c, hipMemcpyAsync(s.dots, ybuf.data(), sizeof(double) * (size_t)k * Q, hipMemcpyHostToDevice, st));
+        by_cols(Q, [&](auto qq) {
+            constexpr int QC = decltype(qq)::value;
+            hipLaunchKernelGGL(k_pmg_comb_cols<QC>, gv, bv, 0, st, n, Z, nq, k, s.dots, mask, x);
+        });
+        HIPCHK(c, hipStreamSynchronize(st));   // (ybuf is the host's)
+        return FDAPDE_OK;
+    };
+    while (live && it < maxit) {
+        // (r holds the residuals of x, S.rr their squares)
+        ColScal f0{};
+        for (int q = 0; q < Q; ++q) {
+            if (!((live >> q) & 1u)) continue;
+            const double beta = std::sqrt(S.rr[q]);
+            if (!(beta > 0.0) || !std::isfinite(beta)) {
+                S.broke[q] = !std::isfinite(beta), S.converged[q] = !S.broke[q], S.it[q] = it;
+                live &= ~(1u << q);
+                continue;
+            }
+            f0.f[q] = 1.0 / beta, f0.mask |= 1u << q;
+            Col& C = col[(size_t)q];
+            std::fill(C.gg.begin(), C.gg.end(), 0.0);
+            C.gg[0] = beta;
+        }
+        if (!live) break;
+        scale(r, f0, V);
+        int k = 0;             // columns of this cycle
+        unsigned cyc = live;   // the columns still in it
+        while (cyc && k < mk && it < maxit) {
+            const int j = k;
+            double* zj = Z + (size_t)j * (size_t)nq;
+            double* w = V + (size_t)(j + 1) * (size_t)nq;
+            const double* vj = V + (size_t)j * (size_t)nq;
+            if (int rc = precond(vj, zj, w)) return rc;
+            for (int pass = 0; pass < 2; ++pass) {   // Gram-Schmidt, twice; ONE read-back per pass for all columns
+                by_cols(Q, [&](auto qq) {
+                    constexpr int QC = decltype(qq)::value;
+                    hipLaunchKernelGGL(k_pmg_mdot_cols<QC>, dim3(gnp), bv, 0, st, n, V, nq, j + 1, w, s.part);
+                    hipLaunchKernelGGL(k_pmg_mreduce, dim3((unsigned)((j + 2) * Q)), bv, 0, st, s.part, s.np, s.dots);
+                    hipLaunchKernelGGL(k_pmg_msub_cols<QC>, dim3(gnp), bv, 0, st, n, V, nq, j + 1, s.dots, w, s.part);
+                    hipLaunchKernelGGL(k_pmg_mreduce, dim3((unsigned)Q), bv, 0, st, s.part, s.np, s.dots + (size_t)(j + 2) * Q);
+                });
+                HIPCHK(c, hipMemcpyAsync(hj.data(), s.dots, sizeof(double) * (size_t)(j + 3) * Q, hipMemcpyDeviceToHost, st));
+                HIPCHK(c, hipStreamSynchronize(st));
+                for (int q = 0; q < Q; ++q) {
+                    if (!((cyc >> q) & 1u)) continue;
+                    Col& C = col[(size_t)q];
+                    for (int i = 0; i <= j; ++i) Hat(C, i, j) = pass == 0 ? hj[(size_t)i * Q + q] : Hat(C, i, j) + hj[(size_t)i * Q + q];
+                    wn2[(size_t)q] = hj[(size_t)(j + 2) * Q + q];
+                }
+            }
+            unsigned done = 0, brk = 0;
+            ColScal fw{};
+            for (int q = 0; q < Q; ++q) {
+                if (!((cyc >> q) & 1u)) continue;
+                Col& C = col[(size_t)q];
+                const double hn = std::sqrt(wn2[(size_t)q]);
+                if (!std::isfinite(hn)) {
+                    brk |= 1u << q;
+                    continue;
+                }
+                Hat(C, j + 1, j) = hn;
+                for (int i = 0; i < j; ++i) {
+                    const double a0 = Hat(C, i, j), a1 = Hat(C, i + 1, j);
+                    Hat(C, i, j) = C.cs[(size_t)i] * a0 + C.sn[(size_t)i] * a1, Hat(C, i + 1, j) = -C.sn[(size_t)i] * a0 + C.cs[(size_t)i] * a1;
+                }
+                const double d = std::hypot(Hat(C, j, j), Hat(C, j + 1, j));
+                if (!(d > 0.0)) {   // (a zero column: M^-1 v_j = 0 -- nothing this basis can do)
+                    brk |= 1u << q;
+                    continue;
+                }
+                C.cs[(size_t)j] = Hat(C, j, j) / d, C.sn[(size_t)j] = Hat(C, j + 1, j) / d;
+                Hat(C, j, j) = d, Hat(C, j + 1, j) = 0.0;
+                C.gg[(size_t)j + 1] = -C.sn[(size_t)j] * C.gg[(size_t)j], C.gg[(size_t)j] = C.cs[(size_t)j] * C.gg[(size_t)j];
+                S.rr[q] = C.gg[(size_t)j + 1] * C.gg[(size_t)j + 1];
+                if (S.rr[q] <= tol2 * S.bb[q] || !(hn > 1e-300)) done |= 1u << q;   // (hn = 0: the exact solution lies in this basis)
+                else fw.f[q] = 1.0 / hn, fw.mask |= 1u << q;
+            }
+            if (brk) {   // a column that broke down leaves with the k vectors it had
+                if (int rc = comb(brk, k)) return rc;
+                for (int q = 0; q < Q; ++q)
+                    if ((brk >> q) & 1u) S.broke[q] = true, S.it[q] = it;
+                live &= ~brk, cyc &= ~brk;
+            }
+            ++k, ++it;
+            scale(w, fw, w);   // (the next basis vector; zeros in the columns that have just left the cycle)
+            if (done) {   // the recurrence's word is not taken for convergence: the column's x update and its true residual, as at the end of a cycle
+                if (int rc = comb(done, k)) return rc;
+                if (int rc = residual(rrv.data())) return rc;
+                for (int q = 0; q < Q; ++q) {
+                    if (!((done >> q) & 1u)) continue;
+                    S.rr[q] = rrv[(size_t)q], S.it[q] = it;
+                    if (!std::isfinite(S.rr[q])) S.broke[q] = true;
+                    else if (S.rr[q] <= tol2 * S.bb[q]) S.converged[q] = true;
+                    else if (it < maxit) S.handed[q] = true;   // (fgmres_outer would restart this column alone: the single-column path does)
+                }
+                live &= ~done, cyc &= ~done;
+            }
+        }
+        if (cyc) {   // a restart after mk vectors, or maxit: all the columns still in the cycle at once
+            if (int rc = comb(cyc, k)) return rc;
+            if (int rc = residual(rrv.data())) return rc;
+            for (int q = 0; q < Q; ++q) {
+                if (!((cyc >> q) & 1u)) continue;
+                S.rr[q] = rrv[(size_t)q];
+                if (!std::isfinite(S.rr[q])) S.broke[q] = true;
+                else if (S.rr[q] <= tol2 * S.bb[q]) S.converged[q] = true;
+                else continue;
+                S.it[q] = it, live &= ~(1u << q);
+            }
+        }
+    }
+    for (int q = 0; q < Q; ++q)
+        if ((live >> q) & 1u) S.it[q] = it;   // maxit
     return FDAPDE_OK;
 }
 

@@ -177,6 +177,17 @@ int fgmres_outer(fdapde_ctx* c, const FgmresSpace& s, double* x, double* r, cons
                  bool& converged, bool& broke);
 void fixed_dots(hipStream_t st, int64_t n, int np, const double* a0, const double* b0, const double* a1, const double* b1, const double* a2, const double* b2,
                 double* part, double* out);
+// the same loop for Q <= 8 columns in lockstep (interleaved vectors: kernels_cols.h; s.n words per column, basis vectors s.n Q apart, part >= (mk + 2) Q np,
+// dots >= (mk + 4) Q).  Per column: in rr / bb / converged / broke, out also it and handed (the recurrence said "converged", the true residual did not: the
+// caller finishes that column on the single-column path from its iterate)
+struct FgmresCols {
+    double rr[8], bb[8];
+    int it[8];
+    bool converged[8], broke[8], handed[8];
+};
+int fgmres_outer_cols(fdapde_ctx* c, const FgmresSpace& s, int Q, double* x, double* r, double rtol, int maxit,
+                      const std::function<int(const double*, double*, double*)>& precond, const std::function<int(double*)>& residual, FgmresCols& S);
+void fixed_dots_cols(hipStream_t st, int64_t n, int np, int Q, const double* a, const double* b, double* part, double* out);
 // eng_amg.hip: FDAPDE_SOLVER_AMG
 bool amg_eligible(const fdapde_ctx* c);
 void amg_release(fdapde_ctx* c);
@@ -190,6 +201,10 @@ int amg_run(fdapde_ctx* c, AmgHierarchy* h, const double* A, const double* f_dev
 int amg_build(fdapde_ctx* c, AmgHierarchy** slot, const double* A, int use_bnd, bool symmetric);
 // fdapde_amg_hierarchy: levels, rows and entries per level (the first `cap` of them), whether the passes absorbed, what the set-up cost; FDAPDE_ENOTINIT for NULL
 int amg_describe(const AmgHierarchy* h, int32_t cap, int32_t* n_levels, int64_t* rows, int64_t* nnz, int32_t* absorbed, double* setup_ms);
+// fdapde_amg_cols_trace: the hierarchy's Q-column runs, the columns they took, the columns solved one by one; FDAPDE_ENOTINIT for NULL
+int amg_cols_trace(const AmgHierarchy* h, int32_t* batches, int32_t* batched_cols, int32_t* single_cols);
+int amg_lin_cols_trace(const fdapde_ctx* c, int32_t* batches, int32_t* batched_cols, int32_t* single_cols);   // the handle's (none once fdapde_lin_compute has outlived it)
+int block_amg_cols_trace_ctx(const fdapde_ctx* c, int32_t* batches, int32_t* batched_cols, int32_t* single_cols);
 int dense_step_loop(fdapde_ctx* c, fdapde_ctx::Dense& D, int32_t n_times, double inv_dt, const double* g_ext_dev, double* u0, double* sol_ext);
 void preload_dense();
 // eng_block.hip: 2 x 2 block systems on the FEM pattern (the smoothing system's handle) and Psi^T W Psi on that pattern
@@ -211,7 +226,14 @@ int block_amg_build(fdapde_ctx* c, BlockAmg** slot, const double* raw, int stren
 int block_amg_describe(const BlockAmg* h, int32_t cap, int32_t* n_levels, int64_t* rows, int64_t* nnz, int32_t* absorbed, double* setup_ms);   // rows: 2 n_l
 int block_amg_aggregates(fdapde_ctx* c, const BlockAmg* h, int32_t level, int64_t cap, int32_t* agg, int64_t* n_rows);   // fdapde_amg_aggregates, which 2
 int block_amg_run(fdapde_ctx* c, BlockAmg* h, const double* raw, const double* b_dev, double* x_dev, double rtol, int maxit, int* iters, double* relres,
-                  bool* converged, bool* broke);
+                  bool* converged, bool* broke, bool warm = false);   // warm: x_dev holds the iterate to start from (a column a batch handed back)
+// Q in {2, 4, 8} columns side by side (knob amg_cols; block_amg_width: the widest batch for `left` columns): ext (device) holds the stacked columns in the
+// reference numbering and receives the solutions; col_b, col_x: a column of scratch each.  Adds to *iters, follows block_amg_solve's rules for the rest
+int block_amg_width(const fdapde_ctx* c, const BlockAmg* h, int32_t left, int maxit);
+int block_amg_batch(fdapde_ctx* c, BlockAmg* h, const double* raw, int Q, double* ext, double* col_b, double* col_x, double rtol, int maxit, int* iters, double* worst,
+                    bool* not_conv, bool* broke_any);
+int block_amg_cols_trace(const BlockAmg* h, int32_t* batches, int32_t* batched_cols, int32_t* single_cols);   // fdapde_amg_cols_trace, which 2
+void block_amg_count_single(BlockAmg* h);   // a column went through block_amg_run alone
 
 // code objects of the units loaded up front (fdapde_ctx_create)
 void preload_assembly();

@@ -12,6 +12,7 @@
 
 #include <cstdint>
 
+#include "kernels_cols.h"
 #include "kernels_reduce.h"
 
 namespace fdapde_hip {
@@ -270,6 +271,219 @@ static __global__ __launch_bounds__(256) void k_bamg_spmv_dots(int64_t n, const 
 static __global__ void k_bamg_residual(int64_t n2, const double* b, const double* t, double* r) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n2) r[i] = b[i] - t[i];
+}
+// ---- ... for Q interleaved columns (kernels_cols.h): unknown u of DOF i, column q at [(2 i + u) Q + q].  Per column the arithmetic of the kernel of the same
+// name above, in the same order (the same team, the same entries to the same lanes, blk_mul, team_sum, the same grid of partials), Q accumulator pairs per
+// lane; the blocks and indices are read once for all columns, a gathered DOF is 2 Q contiguous doubles.  (The outer iteration's r = b - t is k_bamg_residual
+// itself over the 2 n Q words.)
+// The arithmetic is spelled out with contraction off: the single-column kernels are compiled with the default contraction, which turns blk_mul's and the dot
+// products' a.x b.x + a.y b.y into fma(a.x, b.x, a.y b.y), r - om s into fma(-om, s, r) and z + om d into fma(om, d, z), and leaves every accumulation a plain
+// addition; left to itself the compiler fuses the unrolled column forms differently at some widths, and a column's last bits would depend on its batch.
+__device__ __forceinline__ blk_v2f64_t blk_mul_cols(const blk_v2f64_t top, const blk_v2f64_t bot, const blk_v2f64_t v) {
+#pragma clang fp contract(off)
+    return blk_v2f64_t{__builtin_fma(top.x, v.x, top.y * v.y), __builtin_fma(bot.x, v.x, bot.y * v.y)};
+}
+__device__ __forceinline__ double blk_dot_cols(const blk_v2f64_t u, const blk_v2f64_t w) {
+#pragma clang fp contract(off)
+    return __builtin_fma(u.x, w.x, u.y * w.y);
+}
+template <int Q> __device__ __forceinline__ void blk_ld_cols(const double* p, blk_v2f64_t (&v)[Q]) {   // p = base + 2 i Q
+    double a[Q], b[Q];
+    ld_cols<Q>(p, a), ld_cols<Q>(p + Q, b);
+#pragma unroll
+    for (int q = 0; q < Q; ++q) v[q] = blk_v2f64_t{a[q], b[q]};
+}
+template <int Q> __device__ __forceinline__ void blk_st_cols(double* p, const blk_v2f64_t (&v)[Q]) {
+    double a[Q], b[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) a[q] = v[q].x, b[q] = v[q].y;
+    st_cols<Q>(p, a), st_cols<Q>(p + Q, b);
+}
+template <int T, int Q>
+static __global__ __launch_bounds__(256) void k_block_spmv_cols(int64_t n, const int32_t* rowptr, const int32_t* colidx, const double* vals, const double* x, double* y) {
+#pragma clang fp contract(off)
+    constexpr int TEAMS = 256 / T;
+    const int l = threadIdx.x % T;
+    const int64_t row = (int64_t)blockIdx.x * TEAMS + threadIdx.x / T;
+    const bool row_ok = row < n;
+    const int64_t rc = row_ok ? row : n - 1;
+    const int rs = rowptr[rc], re = rowptr[rc + 1];
+    double a0[Q], a1[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) a0[q] = 0.0, a1[q] = 0.0;
+    for (int k = rs + l; k < re; k += T) {
+        const blk_v2f64_t* v = reinterpret_cast<const blk_v2f64_t*>(vals + 4 * (int64_t)k);
+        const blk_v2f64_t top = v[0], bot = v[1];
+        const int col = colidx[k];
+        blk_v2f64_t xp[Q];
+        blk_ld_cols<Q>(x + 2 * (int64_t)col * Q, xp);
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            const blk_v2f64_t t = blk_mul_cols(top, bot, xp[q]);
+            a0[q] += t.x, a1[q] += t.y;
+        }
+    }
+    blk_v2f64_t o[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) o[q] = blk_v2f64_t{team_sum<T>(a0[q]), team_sum<T>(a1[q])};
+    if (l == 0 && row_ok) blk_st_cols<Q>(y + 2 * row * Q, o);
+}
+// rc: unknown u of aggregate a, column q at rc[(2 a + u) rs + q cs] (interleaved, or column-major for the dense inverse of the coarsest level)
+template <int T, int Q>
+static __global__ __launch_bounds__(256) void k_bamg_pre_restrict_cols(int64_t nc, const int32_t* mptr, const int32_t* midx, const int32_t* rp, const int32_t* ci,
+                                                                       const double* bv, const double* dinv, double om, const double* r, double* zt, double* rc,
+                                                                       int64_t rs, int64_t cs) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x % T;
+    const int64_t ag = (int64_t)blockIdx.x * (256 / T) + threadIdx.x / T;
+    if (ag >= nc) return;
+    double c0[Q], c1[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) c0[q] = 0.0, c1[q] = 0.0;
+    for (int32_t m = mptr[ag]; m < mptr[ag + 1]; ++m) {
+        const int32_t i = midx[m];
+        double s0[Q], s1[Q];
+#pragma unroll
+        for (int q = 0; q < Q; ++q) s0[q] = 0.0, s1[q] = 0.0;
+        for (int32_t k = rp[i] + lane; k < rp[i + 1]; k += T) {
+            const blk_v2f64_t top = blk_ld2(bv + 4 * (int64_t)k), bot = blk_ld2(bv + 4 * (int64_t)k + 2);
+            const int64_t j = ci[k];
+            const blk_v2f64_t dt = blk_ld2(dinv + 4 * j), db = blk_ld2(dinv + 4 * j + 2);
+            blk_v2f64_t rj[Q];
+            blk_ld_cols<Q>(r + 2 * j * Q, rj);
+#pragma unroll
+            for (int q = 0; q < Q; ++q) {
+                const blk_v2f64_t y = blk_mul_cols(dt, db, rj[q]);
+                const blk_v2f64_t t = blk_mul_cols(top, bot, y);
+                s0[q] += t.x, s1[q] += t.y;
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < Q; ++q) s0[q] = team_sum<T>(s0[q]), s1[q] = team_sum<T>(s1[q]);
+        blk_v2f64_t ri[Q];
+        blk_ld_cols<Q>(r + 2 * (int64_t)i * Q, ri);
+        if (lane == 0) {
+            const blk_v2f64_t dt = blk_ld2(dinv + 4 * (int64_t)i), db = blk_ld2(dinv + 4 * (int64_t)i + 2);
+            blk_v2f64_t z[Q];
+#pragma unroll
+            for (int q = 0; q < Q; ++q) {
+                const blk_v2f64_t y = blk_mul_cols(dt, db, ri[q]);
+                z[q] = blk_v2f64_t{om * y.x, om * y.y};
+            }
+            blk_st_cols<Q>(zt + 2 * (int64_t)i * Q, z);
+        }
+#pragma unroll
+        for (int q = 0; q < Q; ++q) c0[q] += __builtin_fma(-om, s0[q], ri[q].x), c1[q] += __builtin_fma(-om, s1[q], ri[q].y);
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < Q; ++q) rc[2 * ag * rs + q * cs] = c0[q], rc[(2 * ag + 1) * rs + q * cs] = c1[q];
+    }
+}
+template <int T, int Q>
+static __global__ __launch_bounds__(256) void k_bamg_post_cols(int64_t n, const int32_t* rp, const int32_t* ci, const double* bv, const double* dinv, double om,
+                                                               const int32_t* agg, const double* e, const double* r, const double* zt, double* out) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x % T;
+    const int64_t i = (int64_t)blockIdx.x * (256 / T) + threadIdx.x / T;
+    if (i >= n) return;
+    double s0[Q], s1[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) s0[q] = 0.0, s1[q] = 0.0;
+    for (int32_t k = rp[i] + lane; k < rp[i + 1]; k += T) {
+        const blk_v2f64_t top = blk_ld2(bv + 4 * (int64_t)k), bot = blk_ld2(bv + 4 * (int64_t)k + 2);
+        const int64_t j = ci[k];
+        blk_v2f64_t zj[Q], eg[Q];
+        blk_ld_cols<Q>(zt + 2 * j * Q, zj), blk_ld_cols<Q>(e + 2 * (int64_t)agg[j] * Q, eg);
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            const blk_v2f64_t z = zj[q] + eg[q];
+            const blk_v2f64_t t = blk_mul_cols(top, bot, z);
+            s0[q] += t.x, s1[q] += t.y;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < Q; ++q) s0[q] = team_sum<T>(s0[q]), s1[q] = team_sum<T>(s1[q]);
+    if (lane == 0) {
+        const blk_v2f64_t dt = blk_ld2(dinv + 4 * i), db = blk_ld2(dinv + 4 * i + 2);
+        blk_v2f64_t zi[Q], eg[Q], ri[Q], o[Q];
+        blk_ld_cols<Q>(zt + 2 * i * Q, zi), blk_ld_cols<Q>(e + 2 * (int64_t)agg[i] * Q, eg), blk_ld_cols<Q>(r + 2 * i * Q, ri);
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            const blk_v2f64_t z = zi[q] + eg[q];
+            const blk_v2f64_t d = blk_mul_cols(dt, db, blk_v2f64_t{ri[q].x - s0[q], ri[q].y - s1[q]});
+            o[q] = blk_v2f64_t{__builtin_fma(om, d.x, z.x), __builtin_fma(om, d.y, z.y)};
+        }
+        blk_st_cols<Q>(out + 2 * i * Q, o);
+    }
+}
+// dot d of column q: part[(d Q + q) gridDim.x + block]
+template <int T, int Q>
+static __global__ __launch_bounds__(256) void k_bamg_spmv_dots_cols(int64_t n, const int32_t* rp, const int32_t* ci, const double* bv, const double* x, double* y,
+                                                                    const double* p0, const double* q0, const double* p1, const double* q1, const double* p2,
+                                                                    const double* q2, double* part) {
+#pragma clang fp contract(off)
+    __shared__ double red[3 * Q][4];
+    const int lane = threadIdx.x % T;
+    double d0[Q], d1[Q], d2[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) d0[q] = d1[q] = d2[q] = 0.0;
+    const int64_t teams = (int64_t)gridDim.x * (256 / T);
+    for (int64_t i = (int64_t)blockIdx.x * (256 / T) + threadIdx.x / T; i < n; i += teams) {
+        double s0[Q], s1[Q];
+#pragma unroll
+        for (int q = 0; q < Q; ++q) s0[q] = 0.0, s1[q] = 0.0;
+        for (int32_t k = rp[i] + lane; k < rp[i + 1]; k += T) {
+            const blk_v2f64_t top = blk_ld2(bv + 4 * (int64_t)k), bot = blk_ld2(bv + 4 * (int64_t)k + 2);
+            blk_v2f64_t xj[Q];
+            blk_ld_cols<Q>(x + 2 * (int64_t)ci[k] * Q, xj);
+#pragma unroll
+            for (int q = 0; q < Q; ++q) {
+                const blk_v2f64_t t = blk_mul_cols(top, bot, xj[q]);
+                s0[q] += t.x, s1[q] += t.y;
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < Q; ++q) s0[q] = team_sum<T>(s0[q]), s1[q] = team_sum<T>(s1[q]);
+        if (lane == 0) {
+            blk_v2f64_t yi[Q];
+#pragma unroll
+            for (int q = 0; q < Q; ++q) yi[q] = blk_v2f64_t{s0[q], s1[q]};
+            blk_st_cols<Q>(y + 2 * i * Q, yi);
+            auto dots = [&](const double* a, const double* b, double (&d)[Q]) {
+                blk_v2f64_t u[Q], w[Q];
+#pragma unroll
+                for (int q = 0; q < Q; ++q) u[q] = w[q] = yi[q];
+                if (a != y) blk_ld_cols<Q>(a + 2 * i * Q, u);
+                if (b != y) blk_ld_cols<Q>(b + 2 * i * Q, w);
+#pragma unroll
+                for (int q = 0; q < Q; ++q) d[q] += blk_dot_cols(u[q], w[q]);
+            };
+            dots(p0, q0, d0), dots(p1, q1, d1);
+            if (p2) dots(p2, q2, d2);
+        }
+    }
+    const int w = threadIdx.x >> 6;
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+        const double t0 = wave_sum(d0[q]), t1 = wave_sum(d1[q]), t2 = wave_sum(d2[q]);
+        if ((threadIdx.x & 63) == 0) red[q][w] = t0, red[Q + q][w] = t1, red[2 * Q + q][w] = t2;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3 * Q) part[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
+}
+// Q stacked columns in the reference numbering (column q at b_ext + 2 n q) <-> interleaved internal order
+static __global__ void k_block_stage_cols(int64_t n, int Q, const int32_t* i2e, const double* b_ext, double* z) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n * Q) return;
+    const int64_t i = t / Q, q = t - i * Q, e = i2e[i];
+    z[2 * i * Q + q] = b_ext[q * 2 * n + e], z[(2 * i + 1) * Q + q] = b_ext[q * 2 * n + n + e];
+}
+static __global__ void k_block_unstage_cols(int64_t n, int Q, const int32_t* i2e, const double* z, double* x_ext) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n * Q) return;
+    const int64_t i = t / Q, q = t - i * Q, e = i2e[i];
+    x_ext[q * 2 * n + e] = z[2 * i * Q + q] + 0.0, x_ext[q * 2 * n + n + e] = z[(2 * i + 1) * Q + q] + 0.0;
 }
 // ---- ... and its set-up: the scalar strength matrix (the block Galerkin sums are k_bamg_gsum's, beside k_amg_gsum in eng_amg.hip) ------------------------
 static __global__ void k_bamg_pick(int64_t nnz, const double* bv, int q, double* out) {   // block q of every entry

@@ -526,7 +526,10 @@ int fdapde_partition_peers(fdapde_ctx *ctx, int32_t rank, int32_t *n_peers, int3
  *                 "amg_absorb" (both set-ups: 0 = pairwise matching only; 1 = every pass of every level also lets each row it left single join the pair
  *                 of its most strongly coupled paired neighbour; 2, the default = as 0, and where that build ends in "coarsening stalled above the dense
  *                 limit" the whole hierarchy is built again as 1 -- a system that is solved under 0 keeps its hierarchy, its count and its bits; setting
- *                 another value drops the live hierarchies) */
+ *                 another value drops the live hierarchies), "amg_cols" (the widest batch of columns fdapde_lin_solve under FDAPDE_SOLVER_AMG and
+ *                 fdapde_block_solve under FDAPDE_SOLVER_BLOCK_AMG solve side by side -- n_rhs columns go in batches of 8, then 4, then 2, a last one
+ *                 alone; every column's iterates are those of a column-by-column run, bit for bit --: 1, 2, 4 or 8; 8.  1 = column by column.  The
+ *                 hierarchy stays) */
 int fdapde_tune(fdapde_ctx *ctx, const char *key, int32_t value);
 /* The live hierarchy of a multilevel solver as data.  which: 0 = fdapde_solve's (FDAPDE_SOLVER_AMG; fdapde_solve_parabolic builds its own per call and
  * drops it when it returns), 1 = the factor-once handle's, 2 = the 2 x 2 block handle's (FDAPDE_SOLVER_BLOCK_AMG).  *n_levels: its levels, the last one the
@@ -541,6 +544,11 @@ int fdapde_amg_hierarchy(fdapde_ctx *ctx, int32_t which, int32_t cap, int32_t *n
  * cap < *n_rows (*n_rows is set where the level is valid); FDAPDE_EUNSUPPORTED for which = 0 and 1 (the scalar hierarchies do not hand theirs out) and
  * for multi-device contexts. */
 int fdapde_amg_aggregates(fdapde_ctx *ctx, int32_t which, int32_t level, int64_t cap, int32_t *agg, int64_t *n_rows);
+/* How the columns of a multilevel handle's solves were run since its hierarchy was built.  which as in fdapde_amg_hierarchy: 1 = the factor-once handle's
+ * (FDAPDE_SOLVER_AMG), 2 = the block handle's (FDAPDE_SOLVER_BLOCK_AMG); 0, fdapde_solve's own, is FDAPDE_EUNSUPPORTED (one column).  *batches: runs of
+ * 2, 4 or 8 columns side by side ("amg_cols"); *batched_cols: the columns they took; *single_cols: the columns solved one by one -- a column a batch
+ * handed back to the single-column path counts here too.  Any output pointer may be NULL.  FDAPDE_ENOTINIT where no such hierarchy is live. */
+int fdapde_amg_cols_trace(fdapde_ctx *ctx, int32_t which, int32_t *batches, int32_t *batched_cols, int32_t *single_cols);
 /* the context's HIP stream (hipStream_t) so that callers can bracket work with their own events */
 void *fdapde_stream(fdapde_ctx *ctx);
 int fdapde_synchronize(fdapde_ctx *ctx);
