@@ -29,27 +29,25 @@ struct AmgLevel {
     double om = 0.0;
     int team = 4, np = 1;
     DBuf<int32_t> agg, mptr, midx;                // row -> row of the next level (-1: none); members of each next-level row, ascending
-    DBuf<double> b, zt, cv, v, dv, w, rt, e, part, sc;   // work vectors (b: the restricted right-hand side; e: this level's correction)
-    // ... and for a batch of qcols interleaved columns (allocated by the first batch of that width: amg_cols_prepare): qcols times the words, qsc 8 per column,
-    // qpart 3 np per column; on the coarsest level qb / qecm are column-major (what dense_apply takes), qe the correction interleaved again
-    DBuf<double> qb, qzt, qcv, qv, qdv, qw, qrt, qe, qecm, qpart, qsc;
-    int qcols = 0;
+    // work vectors (b: the restricted right-hand side; e: this level's correction), laid out for `cols` interleaved columns -- one from the build on, wider from
+    // the first batch of that width (amg_cols_prepare: they only grow): cols times the words, sc 8 per column, part 3 np per column; on the coarsest level b / ecm
+    // are column-major (what dense_apply takes), e the correction interleaved again
+    DBuf<double> b, zt, cv, v, dv, w, rt, e, ecm, part, sc;
+    int cols = 0;
     virtual ~AmgLevel() = default;                // (the block form's levels carry their block values: eng_block_amg.hip)
 };
 
 struct AmgHierarchy;
-// the launches of a cycle that differ between the two solvers (L: the level, N: the next one)
+// the launches of a cycle that differ between the two solvers (L: the level, N: the next one),
+// for Q in {1, 2, 4, 8} interleaved columns
 struct AmgCycleOps {
-    void (*pre_restrict)(hipStream_t st, AmgLevel& L, AmgLevel& N, const double* r);              // L.zt = the smoothed r, N.b = the restricted residual
-    void (*post)(hipStream_t st, AmgLevel& L, AmgLevel& N, const double* r, double* out);         // out = L.zt + P N.e, smoothed once more
-    void (*spmv_dots)(hipStream_t st, AmgLevel& L, const double* x, double* y, const double* p0, const double* q0, const double* p1, const double* q1,
-                      const double* p2, const double* q2);                                        // y = A x, L.part = the partials of p_q . q_q
-    // the same launches for Q interleaved columns (work vectors L.q*): rc = the restricted residual, word w of column q at rc[w * rs + q * cs] (interleaved, or
-    // column-major for the dense inverse of the coarsest level); dot d of column q in L.qpart[(d Q + q) np ..]
-    void (*pre_restrict_cols)(hipStream_t st, int Q, AmgLevel& L, AmgLevel& N, const double* r, double* rc, int64_t rs, int64_t cs);
-    void (*post_cols)(hipStream_t st, int Q, AmgLevel& L, AmgLevel& N, const double* r, double* out);
-    void (*spmv_dots_cols)(hipStream_t st, int Q, AmgLevel& L, const double* x, double* y, const double* p0, const double* q0, const double* p1, const double* q1,
-                           const double* p2, const double* q2);
+    // L.zt = the smoothed r, rc = the restricted residual: word w of column q at rc[w * rs + q * cs] (interleaved, or column-major for the dense inverse of the
+    // coarsest level)
+    void (*pre_restrict)(hipStream_t st, int Q, AmgLevel& L, AmgLevel& N, const double* r, double* rc, int64_t rs, int64_t cs);
+    void (*post)(hipStream_t st, int Q, AmgLevel& L, AmgLevel& N, const double* r, double* out);   // out = L.zt + P N.e, smoothed once more
+    // y = A x, the partials of p_d . q_d: dot d of column q in L.part[(d Q + q) np ..]
+    void (*spmv_dots)(hipStream_t st, int Q, AmgLevel& L, const double* x, double* y, const double* p0, const double* q0, const double* p1, const double* q1,
+                      const double* p2, const double* q2);
 };
 
 struct AmgHierarchy {
@@ -108,14 +106,12 @@ template <typename H, typename Pass> int amg_build_retry(fdapde_ctx* c, H** slot
     }
     return rc;
 }
-// out = the cycle of level l on r (l < coarsest): smoothing, the coarse correction -- below the finest level two flexible CG / GCR steps around the next
-// level's cycle (the K-cycle), the dense inverse on the last level --, smoothing
-int amg_cycle(fdapde_ctx* c, AmgHierarchy& H, size_t l, const double* r, double* out);
-// ... for Q in {2, 4, 8} interleaved columns (the same recursion; per column the arithmetic of amg_cycle in the same order).  amg_cols_prepare: the levels'
-// work vectors for batches of that width, on first use
+// out = the cycle of level l on r (l < coarsest) for Q in {1, 2, 4, 8} interleaved columns: smoothing, the coarse correction -- below the finest level two
+// flexible CG / GCR steps around the next level's cycle (the K-cycle), the dense inverse on the last level --, smoothing.  A column's arithmetic and order do
+// not depend on Q.  The levels' work vectors must be laid out for Q: amg_cols_prepare (before a run's first cycle; it costs nothing while the width stays)
 int amg_cols_prepare(fdapde_ctx* c, AmgHierarchy& H, int Q);
-int amg_cycle_cols(fdapde_ctx* c, AmgHierarchy& H, size_t l, int Q, const double* r, double* out);
-// the coarsest level alone as the preconditioner: z = D^-1 v for Q interleaved columns (through the column-major layout dense_apply takes)
+int amg_cycle(fdapde_ctx* c, AmgHierarchy& H, size_t l, int Q, const double* r, double* out);
+// the coarsest level alone as the preconditioner: z = D^-1 v for Q interleaved columns (Q >= 2: through the column-major layout dense_apply takes)
 int amg_dense_cols(fdapde_ctx* c, AmgHierarchy& H, int Q, const double* v, double* z);
 // the restart length of FDAPDE_SOLVER_AMG's outer iteration on n unknowns: at most 50 vectors, at most ~16 GB of basis, never more than maxit.  The single-column
 // run and a batch must use the same one (a batch's iterates are the single-column run's)

@@ -168,152 +168,21 @@ __global__ void k_amg_scale(int64_t n, const double* a, double f, double* out) {
     if (i < n) out[i] = f * a[i];
 }
 
-// ---- cycle kernels: a team of T lanes per row (coarse levels are latency-bound: few launches, each fused as far as the data flow allows) ----
+// ---- cycle kernels: a team of T lanes per row (coarse levels are latency-bound: few launches, each fused as far as the data flow allows), for Q interleaved
+// columns (kernels_cols.h): word i of column q at [i * Q + q].  A column's arithmetic does not depend on Q -- the same team width, the same entries to the same
+// lanes, the same team_sum / wave_sum / block_sum, the same grid of partials -- with Q accumulators per lane; the matrix and its indices are read once for all
+// columns, a gathered operand is Q contiguous doubles.  No column reads another.  The single-column solve runs the Q = 1 instantiations.
+// These kernels (and k_pmg_*_cols of eng_pmg.hip) write each expression once and leave its contraction to the compiler, which fuses the unrolled per-column
+// copies of every width, Q = 1 included, alike (s += a x, r - om s, z + om d (r - s), w -= h v): that is a property of this compiler, not of the language -- the
+// block forms in kernels_block.h needed theirs spelled out.  tests/test_gpu_amg_cols.py holds every column of Q = 2, 4, 8 to the Q = 1 run's bits on 2-D and
+// 3-D, P1 and P2 hierarchies; if a toolchain changes a width's fusion that test fails, and the remedy is kernels_block.h's.
+
 // pre-smoothing from zero and the restricted residual in one pass, a team per aggregate: zt_i = om d_i r_i for its members, and
-// rc_a = sum over members i of (r_i - sum_j a_ij om d_j r_j)
-template <int T>
-__global__ __launch_bounds__(256) void k_amg_pre_restrict(int64_t nc, const int32_t* mptr, const int32_t* midx, const int32_t* rp, const int32_t* ci,
-                                                          const double* a, const double* dinv, double om, const double* r, double* zt, double* rc) {
-    const int lane = threadIdx.x & (T - 1);
-    const int64_t ag = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / T;
-    if (ag >= nc) return;   // (whole teams leave together: T divides the wavefront)
-    double acc = 0.0;
-    for (int32_t q = mptr[ag]; q < mptr[ag + 1]; ++q) {
-        const int32_t i = midx[q];
-        double s = 0.0;
-        for (int32_t k = rp[i] + lane; k < rp[i + 1]; k += T) {
-            const int32_t j = ci[k];
-            s += a[k] * (dinv[j] * r[j]);
-        }
-        s = team_sum<T>(s);
-        const double ri = r[i];
-        if (lane == 0) zt[i] = om * dinv[i] * ri;
-        acc += ri - om * s;
-    }
-    if (lane == 0) rc[ag] = acc;
-}
-// out_i = z_i + om d_i (r_i - sum_j a_ij z_j) with z = zt + P e (the coarse correction prolongated on the fly)
-template <int T>
-__global__ __launch_bounds__(256) void k_amg_post(int64_t n, const int32_t* rp, const int32_t* ci, const double* a, const double* dinv, double om, const int32_t* agg,
-                                                  const double* e, const double* r, const double* zt, double* out) {
-    const int lane = threadIdx.x & (T - 1);
-    const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / T;
-    if (i >= n) return;
-    double s = 0.0;
-    for (int32_t k = rp[i] + lane; k < rp[i + 1]; k += T) {
-        const int32_t j = ci[k], g = agg[j];
-        s += a[k] * (zt[j] + (g >= 0 ? e[g] : 0.0));
-    }
-    s = team_sum<T>(s);
-    if (lane == 0) {
-        const int32_t g = agg[i];
-        const double zi = zt[i] + (g >= 0 ? e[g] : 0.0);
-        out[i] = zi + om * dinv[i] * (r[i] - s);
-    }
-}
-// y = A x and up to three dot products p_q . q_q (any of them may be y itself) as per-workgroup partials: a fixed grid, the same bits every run
-template <int T>
-__global__ __launch_bounds__(256) void k_amg_spmv_dots(int64_t n, const int32_t* rp, const int32_t* ci, const double* a, const double* x, double* y, const double* p0,
-                                                       const double* q0, const double* p1, const double* q1, const double* p2, const double* q2, double* part) {
-    __shared__ double red[3][4];
-    const int lane = threadIdx.x & (T - 1);
-    double d0 = 0.0, d1 = 0.0, d2 = 0.0;
-    const int64_t teams = (int64_t)gridDim.x * blockDim.x / T;
-    for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / T; i < n; i += teams) {
-        double s = 0.0;
-        for (int32_t k = rp[i] + lane; k < rp[i + 1]; k += T) s += a[k] * x[ci[k]];
-        s = team_sum<T>(s);
-        if (lane == 0) {
-            y[i] = s;
-            auto val = [&](const double* v) { return v == y ? s : v[i]; };
-            d0 += val(p0) * val(q0);
-            d1 += val(p1) * val(q1);
-            if (p2) d2 += val(p2) * val(q2);
-        }
-    }
-    d0 = wave_sum(d0), d1 = wave_sum(d1), d2 = wave_sum(d2);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) red[0][w] = d0, red[1][w] = d1, red[2][w] = d2;
-    __syncthreads();
-    if (threadIdx.x < 3) part[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
-}
-// the K-cycle's scalars from the partials of k_amg_spmv_dots (one workgroup).  Stage 1 (c = B b, v = A c): FCG rho1 = c.v, alpha1 = c.b; GCR rho1 = v.v,
-// alpha1 = v.b; sc[0] = rho1, sc[1] = alpha1 / rho1.  Stage 2 (rt = b - sc[1] v, d = B rt, w = A d): FCG gamma = d.v, rho2 = d.w - gamma^2 / rho1,
-// alpha2 = d.rt; GCR gamma = v.w, rho2 = w.w - gamma^2 / rho1, alpha2 = w.rt; the correction e = sc[2] c + sc[3] d.  A step that cannot be taken
-// (rho <= 0, not finite) contributes nothing.
-__global__ __launch_bounds__(256) void k_amg_coef(const double* part, int np, int stage, double* sc) {
-    __shared__ double red[5];
-    double t[3];
-    for (int q = 0; q < 3; ++q) {
-        double s = 0.0;
-        for (int i = threadIdx.x; i < np; i += 256) s += part[(size_t)q * np + i];
-        t[q] = block_sum(s, red);
-        __syncthreads();
-    }
-    if (threadIdx.x != 0) return;
-    if (stage == 1) {
-        const double rho1 = t[0], a1 = rho1 > 0.0 && isfinite(rho1) ? t[1] / rho1 : 0.0;
-        sc[0] = rho1, sc[1] = isfinite(a1) ? a1 : 0.0;
-    } else {
-        const double rho1 = sc[0], gamma = t[0];
-        const double rho2 = rho1 > 0.0 ? t[1] - gamma * gamma / rho1 : 0.0;
-        double cd = rho2 > 0.0 && isfinite(rho2) ? t[2] / rho2 : 0.0;
-        double cc = sc[1] - (rho1 > 0.0 ? cd * gamma / rho1 : 0.0);
-        if (!isfinite(cd) || !isfinite(cc)) cd = 0.0, cc = sc[1];
-        sc[2] = cc, sc[3] = cd;
-    }
-}
-__global__ void k_amg_axpy_sc(int64_t n, const double* b, const double* v, const double* sc, double* rt) {   // rt = b - sc[1] v
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) rt[i] = b[i] - sc[1] * v[i];
-}
-__global__ void k_amg_comb2(int64_t n, const double* cv, const double* dv, const double* sc, double* e) {   // e = sc[2] c + sc[3] d
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) e[i] = sc[2] * cv[i] + sc[3] * dv[i];
-}
-// the finest level's system: y = K x (the Dirichlet rows as unit rows if use_bnd); with f: r = rhs - K x (rhs = f, g on the Dirichlet rows)
-template <int T>
-__global__ __launch_bounds__(256) void k_amg_apply_K(int64_t n, const int32_t* rp, const int32_t* ci, const double* a, const uint8_t* bnd, int use_bnd, const double* x,
-                                                     const double* f, const double* g, double* y) {
-    const int lane = threadIdx.x & (T - 1);
-    const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / T;
-    if (i >= n) return;
-    const bool unit = use_bnd && bnd[i];
-    double s = 0.0;
-    if (!unit)
-        for (int32_t k = rp[i] + lane; k < rp[i + 1]; k += T) s += a[k] * x[ci[k]];
-    s = team_sum<T>(s);
-    if (lane == 0) {
-        const double kx = unit ? x[i] : s;
-        y[i] = f ? (unit ? g[i] : f[i]) - kx : kx;
-    }
-}
-// x = g on the Dirichlet rows; elsewhere x0 (a warm start) or 0
-__global__ void k_amg_start(int64_t n, const uint8_t* bnd, int use_bnd, const double* g, const double* x0, double* x) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) x[i] = (use_bnd && bnd[i]) ? g[i] : (x0 ? x0[i] : 0.0);
-}
-
-// the handle's columns between the reference numbering and the internal order
-__global__ void k_amg_gather(int64_t n, const int32_t* idx, const double* src, double* dst) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = src[idx[i]];
-}
-__global__ void k_amg_scatter(int64_t n, const int32_t* idx, const double* src, double* dst) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[idx[i]] = src[i];
-}
-
-// ---- the cycle kernels for Q interleaved columns (kernels_cols.h): word i of column q at [i * Q + q].  Per column the arithmetic of the kernel of the same name
-// above, in the same order -- the same team width, the same entries to the same lanes, the same team_sum / wave_sum / block_sum, the same grid of partials --
-// with Q accumulators per lane; the matrix and its indices are read once for all columns, a gathered operand is Q contiguous doubles.  No column reads another.
-// These kernels (and k_pmg_*_cols of eng_pmg.hip) write each expression as the single-column kernel does and leave its contraction to the compiler, which fuses
-// the unrolled per-column copies as it fuses the original (s += a x, r - om s, z + om d (r - s), w -= h v): that is a property of this compiler, not of the
-// language -- the block forms in kernels_block.h needed theirs spelled out.  tests/test_gpu_amg_cols.py holds every column to the single-column run's bits
-// for Q = 2, 4, 8 on 2-D and 3-D, P1 and P2 hierarchies; if a toolchain changes a width's fusion that test fails, and the remedy is kernels_block.h's.
+// rc_a = sum over members i of (r_i - sum_j a_ij om d_j r_j); word w of column q of rc at rc[w * rs + q * cs] (interleaved, or column-major for the dense
+// inverse of the coarsest level)
 template <int T, int Q>
-__global__ __launch_bounds__(256) void k_amg_pre_restrict_cols(int64_t nc, const int32_t* mptr, const int32_t* midx, const int32_t* rp, const int32_t* ci, const double* a,
-                                                               const double* dinv, double om, const double* r, double* zt, double* rc, int64_t rs, int64_t cs) {
+__global__ __launch_bounds__(256) void k_amg_pre_restrict(int64_t nc, const int32_t* mptr, const int32_t* midx, const int32_t* rp, const int32_t* ci, const double* a,
+                                                          const double* dinv, double om, const double* r, double* zt, double* rc, int64_t rs, int64_t cs) {
     const int lane = threadIdx.x & (T - 1);
     const int64_t ag = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / T;
     if (ag >= nc) return;
@@ -351,9 +220,10 @@ __global__ __launch_bounds__(256) void k_amg_pre_restrict_cols(int64_t nc, const
         for (int q = 0; q < Q; ++q) rc[ag * rs + q * cs] = acc[q];
     }
 }
+// out_i = z_i + om d_i (r_i - sum_j a_ij z_j) with z = zt + P e (the coarse correction prolongated on the fly)
 template <int T, int Q>
-__global__ __launch_bounds__(256) void k_amg_post_cols(int64_t n, const int32_t* rp, const int32_t* ci, const double* a, const double* dinv, double om, const int32_t* agg,
-                                                       const double* e, const double* r, const double* zt, double* out) {
+__global__ __launch_bounds__(256) void k_amg_post(int64_t n, const int32_t* rp, const int32_t* ci, const double* a, const double* dinv, double om, const int32_t* agg,
+                                                  const double* e, const double* r, const double* zt, double* out) {
     const int lane = threadIdx.x & (T - 1);
     const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / T;
     if (i >= n) return;
@@ -392,10 +262,11 @@ __global__ __launch_bounds__(256) void k_amg_post_cols(int64_t n, const int32_t*
         st_cols<Q>(out + i * Q, o);
     }
 }
-// y = A x and up to three dot products per column: part[(d Q + q) gridDim.x + block]
+// y = A x and up to three dot products p_d . q_d per column (any of them may be y itself) as per-workgroup partials part[(d Q + q) gridDim.x + block]: a fixed
+// grid, the same bits every run
 template <int T, int Q>
-__global__ __launch_bounds__(256) void k_amg_spmv_dots_cols(int64_t n, const int32_t* rp, const int32_t* ci, const double* a, const double* x, double* y, const double* p0,
-                                                            const double* q0, const double* p1, const double* q1, const double* p2, const double* q2, double* part) {
+__global__ __launch_bounds__(256) void k_amg_spmv_dots(int64_t n, const int32_t* rp, const int32_t* ci, const double* a, const double* x, double* y, const double* p0,
+                                                       const double* q0, const double* p1, const double* q1, const double* p2, const double* q2, double* part) {
     __shared__ double red[3 * Q][4];
     const int lane = threadIdx.x & (T - 1);
     double d0[Q], d1[Q], d2[Q];
@@ -439,8 +310,11 @@ __global__ __launch_bounds__(256) void k_amg_spmv_dots_cols(int64_t n, const int
     __syncthreads();
     if (threadIdx.x < 3 * Q) part[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
 }
-// k_amg_coef for column blockIdx.x of Q: the partials part[(d Q + q) np ..], the scalars sc[8 q ..]; the guards are the column's own
-__global__ __launch_bounds__(256) void k_amg_coef_cols(const double* part, int np, int Q, int stage, double* sc_all) {
+// the K-cycle's scalars from the partials of k_amg_spmv_dots, a workgroup per column: column blockIdx.x of Q reads part[(d Q + q) np ..] and keeps its scalars
+// in sc[8 q ..].  Stage 1 (c = B b, v = A c): FCG rho1 = c.v, alpha1 = c.b; GCR rho1 = v.v, alpha1 = v.b; sc[0] = rho1, sc[1] = alpha1 / rho1.  Stage 2
+// (rt = b - sc[1] v, d = B rt, w = A d): FCG gamma = d.v, rho2 = d.w - gamma^2 / rho1, alpha2 = d.rt; GCR gamma = v.w, rho2 = w.w - gamma^2 / rho1,
+// alpha2 = w.rt; the correction e = sc[2] c + sc[3] d.  A step that cannot be taken (rho <= 0, not finite) contributes nothing: the guards are the column's own
+__global__ __launch_bounds__(256) void k_amg_coef(const double* part, int np, int Q, int stage, double* sc_all) {
     __shared__ double red[5];
     const int col = blockIdx.x;
     double* sc = sc_all + 8 * col;
@@ -464,7 +338,7 @@ __global__ __launch_bounds__(256) void k_amg_coef_cols(const double* part, int n
         sc[2] = cc, sc[3] = cd;
     }
 }
-template <int Q> __global__ void k_amg_axpy_sc_cols(int64_t n, const double* b, const double* v, const double* sc, double* rt) {   // rt_q = b_q - sc[8 q + 1] v_q
+template <int Q> __global__ void k_amg_axpy_sc(int64_t n, const double* b, const double* v, const double* sc, double* rt) {   // rt_q = b_q - sc[8 q + 1] v_q
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     double bi[Q], vi[Q], o[Q];
@@ -473,7 +347,7 @@ template <int Q> __global__ void k_amg_axpy_sc_cols(int64_t n, const double* b, 
     for (int q = 0; q < Q; ++q) o[q] = bi[q] - sc[8 * q + 1] * vi[q];
     st_cols<Q>(rt + i * Q, o);
 }
-template <int Q> __global__ void k_amg_comb2_cols(int64_t n, const double* cv, const double* dv, const double* sc, double* e) {   // e_q = sc[8 q + 2] c_q + sc[8 q + 3] d_q
+template <int Q> __global__ void k_amg_comb2(int64_t n, const double* cv, const double* dv, const double* sc, double* e) {   // e_q = sc[8 q + 2] c_q + sc[8 q + 3] d_q
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     double ci[Q], di[Q], o[Q];
@@ -482,9 +356,10 @@ template <int Q> __global__ void k_amg_comb2_cols(int64_t n, const double* cv, c
     for (int q = 0; q < Q; ++q) o[q] = sc[8 * q + 2] * ci[q] + sc[8 * q + 3] * di[q];
     st_cols<Q>(e + i * Q, o);
 }
+// the finest level's system: y = K x (the Dirichlet rows as unit rows if use_bnd); with f: r = rhs - K x (rhs = f, g on the Dirichlet rows)
 template <int T, int Q>
-__global__ __launch_bounds__(256) void k_amg_apply_K_cols(int64_t n, const int32_t* rp, const int32_t* ci, const double* a, const uint8_t* bnd, int use_bnd, const double* x,
-                                                          const double* f, const double* g, double* y) {
+__global__ __launch_bounds__(256) void k_amg_apply_K(int64_t n, const int32_t* rp, const int32_t* ci, const double* a, const uint8_t* bnd, int use_bnd, const double* x,
+                                                     const double* f, const double* g, double* y) {
     const int lane = threadIdx.x & (T - 1);
     const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / T;
     if (i >= n) return;
@@ -512,28 +387,23 @@ __global__ __launch_bounds__(256) void k_amg_apply_K_cols(int64_t n, const int32
         st_cols<Q>(y + i * Q, o);
     }
 }
-// x = g on the Dirichlet rows; elsewhere x0 or 0 (any layout: elementwise over the n Q words, row = e / Q)
-__global__ void k_amg_start_cols(int64_t n, int Q, const uint8_t* bnd, int use_bnd, const double* g, const double* x0, double* x) {
+// x = g on the Dirichlet rows; elsewhere x0 (a warm start) or 0 (any layout: elementwise over the n Q words, row = e / Q)
+__global__ void k_amg_start(int64_t n, int Q, const uint8_t* bnd, int use_bnd, const double* g, const double* x0, double* x) {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e < n * Q) x[e] = (use_bnd && bnd[e / Q]) ? g[e] : (x0 ? x0[e] : 0.0);
 }
 // the handle's columns between the reference numbering (column-major n x Q) and the internal order (interleaved)
-__global__ void k_amg_gather_cols(int64_t n, int Q, const int32_t* idx, const double* src, double* dst) {
+__global__ void k_amg_gather(int64_t n, int Q, const int32_t* idx, const double* src, double* dst) {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n * Q) return;
     const int64_t i = e / Q, q = e - i * Q;
     dst[e] = src[q * n + idx[i]];
 }
-__global__ void k_amg_scatter_cols(int64_t n, int Q, const int32_t* idx, const double* src, double* dst) {
+__global__ void k_amg_scatter(int64_t n, int Q, const int32_t* idx, const double* src, double* dst) {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n * Q) return;
     const int64_t i = e / Q, q = e - i * Q;
     dst[q * n + idx[i]] = src[e];
-}
-template <typename F> void by_team(int T, F&& f) {
-    if (T <= 4) f(std::integral_constant<int, 4>{});
-    else if (T <= 8) f(std::integral_constant<int, 8>{});
-    else f(std::integral_constant<int, 16>{});
 }
 template <typename T> bool same_dev(const T* p, size_t n, const std::vector<T>& h) {
     if (h.size() != n) return false;
@@ -716,6 +586,22 @@ int amg_next_level(fdapde_ctx* c, AmgLevel& F, int absorb, const double* pay, in
 }
 
 namespace {
+// a level's work vectors laid out for Q interleaved columns (L.np is set); they only grow.  On the coarsest level b / ecm are column-major (what dense_apply
+// takes), e the correction interleaved again -- one column is both.  zt is zeroed whenever the width changes: rows of no aggregate are never written, and the
+// cycle reads their 0 in the current width's layout (no other vector has a row the cycle does not write before it reads it)
+int level_width(fdapde_ctx* c, AmgLevel& L, int per, bool last, int Q) {
+    if (L.cols == Q) return FDAPDE_OK;
+    const size_t nw = (size_t)per * (size_t)std::max<int64_t>(L.n, 1) * (size_t)Q;
+    for (DBuf<double>* p : {&L.b, &L.zt, &L.cv, &L.v, &L.dv, &L.w, &L.rt, &L.e}) HIPCHK(c, p->alloc(nw));
+    if (last && Q > 1) HIPCHK(c, L.ecm.alloc(nw));
+    HIPCHK(c, hipMemsetAsync(L.zt.p, 0, sizeof(double) * nw, c->stream));
+    HIPCHK(c, L.part.alloc(3 * (size_t)Q * (size_t)std::max(L.np, 1024)));
+    HIPCHK(c, L.sc.alloc(8 * (size_t)kAmgColsMax));
+    HIPCHK(c, hipMemsetAsync(L.sc.p, 0, 8 * (size_t)kAmgColsMax * sizeof(double), c->stream));
+    L.cols = Q;
+    return FDAPDE_OK;
+}
+
 // D^-1, the Jacobi damping 1.5 / lambda_max(D^-1 A) (15 power iterations), team width and work vectors of a level
 int level_prepare(fdapde_ctx* c, AmgLevel& L, bool has_next) {
     hipStream_t st = c->stream;
@@ -733,11 +619,7 @@ int level_prepare(fdapde_ctx* c, AmgLevel& L, bool has_next) {
     const double per_row = n > 0 ? (double)L.nnz / (double)n : 1.0;
     L.team = per_row <= 10.0 ? 4 : per_row <= 24.0 ? 8 : 16;
     L.np = (int)std::min<int64_t>(1024, std::max<int64_t>(1, (n * L.team + 1023) / 1024));
-    for (DBuf<double>* p : {&L.b, &L.zt, &L.cv, &L.v, &L.dv, &L.w, &L.rt, &L.e}) HIPCHK(c, p->alloc((size_t)std::max<int64_t>(n, 1)));
-    HIPCHK(c, hipMemsetAsync(L.zt.p, 0, sizeof(double) * (size_t)std::max<int64_t>(n, 1), st));   // (rows of no aggregate are never written: their 0 stays)
-    HIPCHK(c, L.part.alloc(3 * (size_t)std::max(L.np, 1024)));
-    HIPCHK(c, L.sc.alloc(8));
-    HIPCHK(c, hipMemsetAsync(L.sc.p, 0, 8 * sizeof(double), st));
+    if (int rc = level_width(c, L, 1, !has_next, 1)) return rc;
     L.om = 0.0;
     if (!has_next) return FDAPDE_OK;   // (the coarsest level is inverted, not smoothed)
     // lambda_max(D^-1 A) by the power iteration (as the two-level solver's); the dots in a fixed order
@@ -776,45 +658,26 @@ void amg_release(fdapde_ctx* c) {
 
 namespace {
 // the scalar cycle's launches: damped Jacobi (L.om D^-1) as the smoother
-void scalar_pre_restrict(hipStream_t st, AmgLevel& L, AmgLevel& N, const double* r) {
-    by_team(L.team, [&](auto t) {
-        constexpr int T = decltype(t)::value;
-        hipLaunchKernelGGL(k_amg_pre_restrict<T>, dim3(gn(N.n * T)), dim3(256), 0, st, N.n, L.mptr.p, L.midx.p, L.rp, L.ci, L.a, L.dinv.p, L.om, r, L.zt.p, N.b.p);
-    });
-}
-void scalar_post(hipStream_t st, AmgLevel& L, AmgLevel& N, const double* r, double* out) {
-    by_team(L.team, [&](auto t) {
-        constexpr int T = decltype(t)::value;
-        hipLaunchKernelGGL(k_amg_post<T>, dim3(gn(L.n * T)), dim3(256), 0, st, L.n, L.rp, L.ci, L.a, L.dinv.p, L.om, L.agg.p, N.e.p, r, L.zt.p, out);
-    });
-}
-void scalar_spmv_dots(hipStream_t st, AmgLevel& L, const double* x, double* y, const double* p0, const double* q0, const double* p1, const double* q1, const double* p2,
-                      const double* q2) {
-    by_team(L.team, [&](auto t) {
-        constexpr int T = decltype(t)::value;
-        hipLaunchKernelGGL(k_amg_spmv_dots<T>, dim3((unsigned)L.np), dim3(256), 0, st, L.n, L.rp, L.ci, L.a, x, y, p0, q0, p1, q1, p2, q2, L.part.p);
-    });
-}
-void scalar_pre_restrict_cols(hipStream_t st, int Q, AmgLevel& L, AmgLevel& N, const double* r, double* rc, int64_t rs, int64_t cs) {
+void scalar_pre_restrict(hipStream_t st, int Q, AmgLevel& L, AmgLevel& N, const double* r, double* rc, int64_t rs, int64_t cs) {
     by_team_cols<4>(L.team, Q, [&](auto t, auto q) {
         constexpr int T = decltype(t)::value, QC = decltype(q)::value;
-        hipLaunchKernelGGL((k_amg_pre_restrict_cols<T, QC>), dim3(gn(N.n * T)), dim3(256), 0, st, N.n, L.mptr.p, L.midx.p, L.rp, L.ci, L.a, L.dinv.p, L.om, r, L.qzt.p, rc, rs, cs);
+        hipLaunchKernelGGL((k_amg_pre_restrict<T, QC>), dim3(gn(N.n * T)), dim3(256), 0, st, N.n, L.mptr.p, L.midx.p, L.rp, L.ci, L.a, L.dinv.p, L.om, r, L.zt.p, rc, rs, cs);
     });
 }
-void scalar_post_cols(hipStream_t st, int Q, AmgLevel& L, AmgLevel& N, const double* r, double* out) {
+void scalar_post(hipStream_t st, int Q, AmgLevel& L, AmgLevel& N, const double* r, double* out) {
     by_team_cols<4>(L.team, Q, [&](auto t, auto q) {
         constexpr int T = decltype(t)::value, QC = decltype(q)::value;
-        hipLaunchKernelGGL((k_amg_post_cols<T, QC>), dim3(gn(L.n * T)), dim3(256), 0, st, L.n, L.rp, L.ci, L.a, L.dinv.p, L.om, L.agg.p, N.qe.p, r, L.qzt.p, out);
+        hipLaunchKernelGGL((k_amg_post<T, QC>), dim3(gn(L.n * T)), dim3(256), 0, st, L.n, L.rp, L.ci, L.a, L.dinv.p, L.om, L.agg.p, N.e.p, r, L.zt.p, out);
     });
 }
-void scalar_spmv_dots_cols(hipStream_t st, int Q, AmgLevel& L, const double* x, double* y, const double* p0, const double* q0, const double* p1, const double* q1,
-                           const double* p2, const double* q2) {
+void scalar_spmv_dots(hipStream_t st, int Q, AmgLevel& L, const double* x, double* y, const double* p0, const double* q0, const double* p1, const double* q1,
+                      const double* p2, const double* q2) {
     by_team_cols<4>(L.team, Q, [&](auto t, auto q) {
         constexpr int T = decltype(t)::value, QC = decltype(q)::value;
-        hipLaunchKernelGGL((k_amg_spmv_dots_cols<T, QC>), dim3((unsigned)L.np), dim3(256), 0, st, L.n, L.rp, L.ci, L.a, x, y, p0, q0, p1, q1, p2, q2, L.qpart.p);
+        hipLaunchKernelGGL((k_amg_spmv_dots<T, QC>), dim3((unsigned)L.np), dim3(256), 0, st, L.n, L.rp, L.ci, L.a, x, y, p0, q0, p1, q1, p2, q2, L.part.p);
     });
 }
-constexpr AmgCycleOps kScalarOps{scalar_pre_restrict, scalar_post, scalar_spmv_dots, scalar_pre_restrict_cols, scalar_post_cols, scalar_spmv_dots_cols};
+constexpr AmgCycleOps kScalarOps{scalar_pre_restrict, scalar_post, scalar_spmv_dots};
 
 // the hierarchy of A with (absorb) or without absorption on every level; *stalled: the answer is the "coarsening stalled above the dense limit" refusal
 int amg_build_pass(fdapde_ctx* c, AmgHierarchy** slot, const double* A, int use_bnd, bool symmetric, int absorb, bool* stalled) {
@@ -896,39 +759,50 @@ int amg_describe(const AmgHierarchy* H, int32_t cap, int32_t* n_levels, int64_t*
 }
 
 namespace {
-// e_m = (level m's system)^-1 b_m approximately: the dense inverse on the coarsest level, two flexible CG / GCR steps around the cycle elsewhere.  The dots
-// k_amg_coef reads, (p0.q0, p1.q1[, p2.q2]): flexible CG c.v, c.b then d.v, d.w, d.rt; GCR v.v, v.b then v.w, w.w, w.rt
-int amg_correction(fdapde_ctx* c, AmgHierarchy& H, size_t m) {
+// e_m = (level m's system)^-1 b_m approximately, for Q interleaved columns: the dense inverse on the coarsest level, two flexible CG / GCR steps around the cycle
+// elsewhere.  The dots k_amg_coef reads, (p0.q0, p1.q1[, p2.q2]): flexible CG c.v, c.b then d.v, d.w, d.rt; GCR v.v, v.b then v.w, w.w, w.rt
+int amg_correction(fdapde_ctx* c, AmgHierarchy& H, size_t m, int Q) {
     hipStream_t st = c->stream;
     AmgLevel& L = *H.lv[m];
-    if (m + 1 == H.lv.size()) return dense_apply(c, H.D, 1, L.b.p, L.e.p);
     const int64_t n = H.per * L.n;
+    if (m + 1 == H.lv.size()) {   // (b arrived column-major: amg_cycle)
+        if (Q == 1) return dense_apply(c, H.D, 1, L.b.p, L.e.p);
+        if (int rc = dense_apply(c, H.D, Q, L.b.p, L.ecm.p)) return rc;
+        hipLaunchKernelGGL(k_amg_cm2il, dim3(gn(n * Q)), dim3(256), 0, st, n, Q, (const double*)L.ecm.p, L.e.p);
+        return FDAPDE_OK;
+    }
     double *b = L.b.p, *cv = L.cv.p, *v = L.v.p, *rt = L.rt.p, *dv = L.dv.p, *w = L.w.p;
     // step 1: c = B b, v = A c
-    if (int rc = amg_cycle(c, H, m, b, cv)) return rc;
-    if (H.sym) H.ops->spmv_dots(st, L, cv, v, cv, v, cv, b, nullptr, nullptr);
-    else H.ops->spmv_dots(st, L, cv, v, v, v, v, b, nullptr, nullptr);
-    hipLaunchKernelGGL(k_amg_coef, dim3(1), dim3(256), 0, st, L.part.p, L.np, 1, L.sc.p);
-    hipLaunchKernelGGL(k_amg_axpy_sc, dim3(gn(n)), dim3(256), 0, st, n, b, v, L.sc.p, rt);
+    if (int rc = amg_cycle(c, H, m, Q, b, cv)) return rc;
+    if (H.sym) H.ops->spmv_dots(st, Q, L, cv, v, cv, v, cv, b, nullptr, nullptr);
+    else H.ops->spmv_dots(st, Q, L, cv, v, v, v, v, b, nullptr, nullptr);
+    hipLaunchKernelGGL(k_amg_coef, dim3((unsigned)Q), dim3(256), 0, st, L.part.p, L.np, Q, 1, L.sc.p);
+    by_cols(Q, [&](auto q) {
+        constexpr int QC = decltype(q)::value;
+        hipLaunchKernelGGL(k_amg_axpy_sc<QC>, dim3(gn(n)), dim3(256), 0, st, n, b, v, L.sc.p, rt);
+    });
     // step 2: d = B rt, w = A d
-    if (int rc = amg_cycle(c, H, m, rt, dv)) return rc;
-    if (H.sym) H.ops->spmv_dots(st, L, dv, w, dv, v, dv, w, dv, rt);
-    else H.ops->spmv_dots(st, L, dv, w, v, w, w, w, w, rt);
-    hipLaunchKernelGGL(k_amg_coef, dim3(1), dim3(256), 0, st, L.part.p, L.np, 2, L.sc.p);
-    hipLaunchKernelGGL(k_amg_comb2, dim3(gn(n)), dim3(256), 0, st, n, cv, dv, L.sc.p, L.e.p);
+    if (int rc = amg_cycle(c, H, m, Q, rt, dv)) return rc;
+    if (H.sym) H.ops->spmv_dots(st, Q, L, dv, w, dv, v, dv, w, dv, rt);
+    else H.ops->spmv_dots(st, Q, L, dv, w, v, w, w, w, w, rt);
+    hipLaunchKernelGGL(k_amg_coef, dim3((unsigned)Q), dim3(256), 0, st, L.part.p, L.np, Q, 2, L.sc.p);
+    by_cols(Q, [&](auto q) {
+        constexpr int QC = decltype(q)::value;
+        hipLaunchKernelGGL(k_amg_comb2<QC>, dim3(gn(n)), dim3(256), 0, st, n, cv, dv, L.sc.p, L.e.p);
+    });
     return FDAPDE_OK;
 }
 }   // namespace
 
-int amg_cycle(fdapde_ctx* c, AmgHierarchy& H, size_t l, const double* r, double* out) {
+int amg_cycle(fdapde_ctx* c, AmgHierarchy& H, size_t l, int Q, const double* r, double* out) {
     AmgLevel &L = *H.lv[l], &N = *H.lv[l + 1];
-    H.ops->pre_restrict(c->stream, L, N, r);
-    if (int rc = amg_correction(c, H, l + 1)) return rc;
-    H.ops->post(c->stream, L, N, r, out);
+    const bool dense_next = l + 2 == H.lv.size();   // the coarsest level's right-hand side goes out column-major: what dense_apply takes
+    H.ops->pre_restrict(c->stream, Q, L, N, r, N.b.p, dense_next ? 1 : Q, dense_next ? H.per * N.n : 1);
+    if (int rc = amg_correction(c, H, l + 1, Q)) return rc;
+    H.ops->post(c->stream, Q, L, N, r, out);
     return FDAPDE_OK;
 }
 
-// ---- the recursion for Q interleaved columns: the launches of amg_correction / amg_cycle in the same order, every one for all columns at once
 int amg_cols_width(int want, int64_t n_words, int mk) {
     int Q = want >= 8 ? 8 : want >= 4 ? 4 : want >= 2 ? 2 : 1;
     while (Q > 1 && (double)Q * (double)(2 * mk + 1) * (double)n_words * 8.0 > 16e9) Q /= 2;
@@ -936,69 +810,18 @@ int amg_cols_width(int want, int64_t n_words, int mk) {
 }
 
 int amg_cols_prepare(fdapde_ctx* c, AmgHierarchy& H, int Q) {
-    hipStream_t st = c->stream;
-    for (size_t l = 0; l < H.lv.size(); ++l) {
-        AmgLevel& L = *H.lv[l];
-        if (L.qcols == Q) continue;
-        const size_t nw = (size_t)H.per * (size_t)std::max<int64_t>(L.n, 1) * (size_t)Q;
-        const bool last = l + 1 == H.lv.size();
-        for (DBuf<double>* p : {&L.qb, &L.qzt, &L.qcv, &L.qv, &L.qdv, &L.qw, &L.qrt, &L.qe}) HIPCHK(c, p->alloc(nw));
-        if (last) HIPCHK(c, L.qecm.alloc(nw));
-        HIPCHK(c, hipMemsetAsync(L.qzt.p, 0, sizeof(double) * nw, st));   // (rows of no aggregate are never written: their 0 stays -- in this width's layout)
-        HIPCHK(c, L.qpart.alloc(3 * (size_t)Q * (size_t)std::max(L.np, 1024)));
-        HIPCHK(c, L.qsc.alloc(8 * (size_t)kAmgColsMax));
-        HIPCHK(c, hipMemsetAsync(L.qsc.p, 0, 8 * (size_t)kAmgColsMax * sizeof(double), st));
-        L.qcols = Q;
-    }
+    for (size_t l = 0; l < H.lv.size(); ++l)
+        if (int rc = level_width(c, *H.lv[l], H.per, l + 1 == H.lv.size(), Q)) return rc;
     return FDAPDE_OK;
 }
 
 int amg_dense_cols(fdapde_ctx* c, AmgHierarchy& H, int Q, const double* v, double* z) {
+    if (Q == 1) return dense_apply(c, H.D, 1, v, z);
     AmgLevel& L = *H.lv.back();
     const int64_t nw = H.per * L.n;
-    hipLaunchKernelGGL(k_amg_il2cm, dim3(gn(nw * Q)), dim3(256), 0, c->stream, nw, Q, v, L.qb.p);
-    if (int rc = dense_apply(c, H.D, Q, L.qb.p, L.qecm.p)) return rc;
-    hipLaunchKernelGGL(k_amg_cm2il, dim3(gn(nw * Q)), dim3(256), 0, c->stream, nw, Q, (const double*)L.qecm.p, z);
-    return FDAPDE_OK;
-}
-
-namespace {
-int amg_correction_cols(fdapde_ctx* c, AmgHierarchy& H, size_t m, int Q) {
-    hipStream_t st = c->stream;
-    AmgLevel& L = *H.lv[m];
-    const int64_t n = H.per * L.n;
-    if (m + 1 == H.lv.size()) {   // (qb arrived column-major: amg_cycle_cols)
-        if (int rc = dense_apply(c, H.D, Q, L.qb.p, L.qecm.p)) return rc;
-        hipLaunchKernelGGL(k_amg_cm2il, dim3(gn(n * Q)), dim3(256), 0, st, n, Q, (const double*)L.qecm.p, L.qe.p);
-        return FDAPDE_OK;
-    }
-    double *b = L.qb.p, *cv = L.qcv.p, *v = L.qv.p, *rt = L.qrt.p, *dv = L.qdv.p, *w = L.qw.p;
-    if (int rc = amg_cycle_cols(c, H, m, Q, b, cv)) return rc;
-    if (H.sym) H.ops->spmv_dots_cols(st, Q, L, cv, v, cv, v, cv, b, nullptr, nullptr);
-    else H.ops->spmv_dots_cols(st, Q, L, cv, v, v, v, v, b, nullptr, nullptr);
-    hipLaunchKernelGGL(k_amg_coef_cols, dim3((unsigned)Q), dim3(256), 0, st, L.qpart.p, L.np, Q, 1, L.qsc.p);
-    by_cols(Q, [&](auto q) {
-        constexpr int QC = decltype(q)::value;
-        hipLaunchKernelGGL(k_amg_axpy_sc_cols<QC>, dim3(gn(n)), dim3(256), 0, st, n, b, v, L.qsc.p, rt);
-    });
-    if (int rc = amg_cycle_cols(c, H, m, Q, rt, dv)) return rc;
-    if (H.sym) H.ops->spmv_dots_cols(st, Q, L, dv, w, dv, v, dv, w, dv, rt);
-    else H.ops->spmv_dots_cols(st, Q, L, dv, w, v, w, w, w, w, rt);
-    hipLaunchKernelGGL(k_amg_coef_cols, dim3((unsigned)Q), dim3(256), 0, st, L.qpart.p, L.np, Q, 2, L.qsc.p);
-    by_cols(Q, [&](auto q) {
-        constexpr int QC = decltype(q)::value;
-        hipLaunchKernelGGL(k_amg_comb2_cols<QC>, dim3(gn(n)), dim3(256), 0, st, n, cv, dv, L.qsc.p, L.qe.p);
-    });
-    return FDAPDE_OK;
-}
-}   // namespace
-
-int amg_cycle_cols(fdapde_ctx* c, AmgHierarchy& H, size_t l, int Q, const double* r, double* out) {
-    AmgLevel &L = *H.lv[l], &N = *H.lv[l + 1];
-    const bool dense_next = l + 2 == H.lv.size();   // the coarsest level's right-hand side goes out column-major: what dense_apply takes
-    H.ops->pre_restrict_cols(c->stream, Q, L, N, r, N.qb.p, dense_next ? 1 : Q, dense_next ? H.per * N.n : 1);
-    if (int rc = amg_correction_cols(c, H, l + 1, Q)) return rc;
-    H.ops->post_cols(c->stream, Q, L, N, r, out);
+    hipLaunchKernelGGL(k_amg_il2cm, dim3(gn(nw * Q)), dim3(256), 0, c->stream, nw, Q, v, L.b.p);
+    if (int rc = dense_apply(c, H.D, Q, L.b.p, L.ecm.p)) return rc;
+    hipLaunchKernelGGL(k_amg_cm2il, dim3(gn(nw * Q)), dim3(256), 0, c->stream, nw, Q, (const double*)L.ecm.p, z);
     return FDAPDE_OK;
 }
 
@@ -1025,10 +848,10 @@ int amg_run_cols(fdapde_ctx* c, AmgHierarchy& H, const double* A, int Q, const d
     auto apply_K = [&](const double* in, const double* rhs, double* out) {
         by_team_cols<4>(L0.team, Q, [&](auto tt, auto q) {
             constexpr int T = decltype(tt)::value, QC = decltype(q)::value;
-            hipLaunchKernelGGL((k_amg_apply_K_cols<T, QC>), dim3(gn(n * T)), dim3(256), 0, st, n, L0.rp, L0.ci, A, (const uint8_t*)nullptr, 0, in, rhs, (const double*)nullptr, out);
+            hipLaunchKernelGGL((k_amg_apply_K<T, QC>), dim3(gn(n * T)), dim3(256), 0, st, n, L0.rp, L0.ci, A, (const uint8_t*)nullptr, 0, in, rhs, (const double*)nullptr, out);
         });
     };
-    hipLaunchKernelGGL(k_amg_start_cols, dim3(gn(n * Q)), dim3(256), 0, st, n, Q, (const uint8_t*)nullptr, 0, (const double*)nullptr, (const double*)nullptr, x);
+    hipLaunchKernelGGL(k_amg_start, dim3(gn(n * Q)), dim3(256), 0, st, n, Q, (const uint8_t*)nullptr, 0, (const double*)nullptr, (const double*)nullptr, x);
     apply_K(x, f, r);
     if (int rc = dots(r)) return rc;
     for (int q = 0; q < Q; ++q) S.bb[q] = S.rr[q] = h[q], S.converged[q] = S.rr[q] <= rtol * rtol * S.bb[q], S.broke[q] = false;
@@ -1036,7 +859,7 @@ int amg_run_cols(fdapde_ctx* c, AmgHierarchy& H, const double* A, int Q, const d
     auto precond = [&](const double* v, double* z, double* w) -> int {
         if (one_level) {
             if (int rc = amg_dense_cols(c, H, Q, v, z)) return rc;
-        } else if (int rc = amg_cycle_cols(c, H, 0, Q, v, z))
+        } else if (int rc = amg_cycle(c, H, 0, Q, v, z))
             return rc;
         apply_K(z, nullptr, w);
         return FDAPDE_OK;
@@ -1071,6 +894,7 @@ int amg_run(fdapde_ctx* c, AmgHierarchy* hp, const double* A, const double* f_de
     const dim3 gv(gn(n)), bv(256);
     H.np = (int)std::min<int64_t>(1024, std::max<int64_t>(1, (n + 4095) / 4096));
     const int mk = amg_restart_len(n, maxit);
+    if (int rc = amg_cols_prepare(c, H, 1)) return rc;
     HIPCHK(c, H.vec.alloc(3 * (size_t)n));
     HIPCHK(c, H.basis.alloc((size_t)(2 * mk + 1) * (size_t)n));
     HIPCHK(c, H.part.alloc((size_t)(mk + 2) * (size_t)H.np));
@@ -1085,19 +909,19 @@ int amg_run(fdapde_ctx* c, AmgHierarchy* hp, const double* A, const double* f_de
         return FDAPDE_OK;
     };
     auto apply_K = [&](const double* in, const double* f, double* out) {   // out = K in, or (f given) rhs - K in
-        by_team(L0.team, [&](auto tt) {
-            constexpr int T = decltype(tt)::value;
-            hipLaunchKernelGGL(k_amg_apply_K<T>, dim3(gn(n * T)), bv, 0, st, n, L0.rp, L0.ci, A, bnd, use_bnd, in, f, g_dev, out);
+        by_team_cols<4>(L0.team, 1, [&](auto tt, auto q) {
+            constexpr int T = decltype(tt)::value, QC = decltype(q)::value;
+            hipLaunchKernelGGL((k_amg_apply_K<T, QC>), dim3(gn(n * T)), bv, 0, st, n, L0.rp, L0.ci, A, bnd, use_bnd, in, f, g_dev, out);
         });
     };
     // the lift of the Dirichlet data: the stop rule is relative to its residual (as the two-level solver's)
-    hipLaunchKernelGGL(k_amg_start, gv, bv, 0, st, n, bnd, use_bnd, g_dev, (const double*)nullptr, x);
+    hipLaunchKernelGGL(k_amg_start, gv, bv, 0, st, n, 1, bnd, use_bnd, g_dev, (const double*)nullptr, x);
     apply_K(x, f_dev, r);
     if (int rc = dots(r, r)) return rc;
     const double bb = h[0];
     double rr = h[0];
     if (x0_dev) {
-        hipLaunchKernelGGL(k_amg_start, gv, bv, 0, st, n, bnd, use_bnd, g_dev, x0_dev, x);
+        hipLaunchKernelGGL(k_amg_start, gv, bv, 0, st, n, 1, bnd, use_bnd, g_dev, x0_dev, x);
         apply_K(x, f_dev, r);
         if (int rc = dots(r, r)) return rc;
         rr = h[0];
@@ -1107,8 +931,8 @@ int amg_run(fdapde_ctx* c, AmgHierarchy* hp, const double* A, const double* f_de
     const bool one_level = H.lv.size() == 1;
     auto precond = [&](const double* v, double* z, double* w, bool&) -> int {
         if (one_level) {
-            if (int rc = dense_apply(c, H.D, 1, v, z)) return rc;
-        } else if (int rc = amg_cycle(c, H, 0, v, z))
+            if (int rc = amg_dense_cols(c, H, 1, v, z)) return rc;
+        } else if (int rc = amg_cycle(c, H, 0, 1, v, z))
             return rc;
         apply_K(z, nullptr, w);
         return FDAPDE_OK;
@@ -1212,7 +1036,7 @@ int amg_lin_solve(fdapde_ctx* c, const fdapde_options* opt, const double* b, int
             HIPCHK(c, H.qvec.alloc(4 * nq));
             double *f = H.qvec.p, *xq = f + nq, *r = xq + nq, *t = r + nq;
             HIPCHK(c, hipMemcpyAsync(H.qio.p, b + (size_t)j * n, sizeof(double) * nq, hipMemcpyHostToDevice, st));   // (one copy per batch)
-            hipLaunchKernelGGL(k_amg_gather_cols, dim3(gn(n * Q)), dim3(256), 0, st, n, Q, c->dof_i2e.p, (const double*)H.qio.p, f);
+            hipLaunchKernelGGL(k_amg_gather, dim3(gn(n * Q)), dim3(256), 0, st, n, Q, c->dof_i2e.p, (const double*)H.qio.p, f);
             FgmresCols S{};
             double rel[kAmgColsMax];
             if (int rc = amg_run_cols(c, H, c->lin_mat.p, Q, f, xq, r, t, rtol, maxit, mk, S, rel)) return rc;
@@ -1232,7 +1056,7 @@ int amg_lin_solve(fdapde_ctx* c, const fdapde_options* opt, const double* b, int
                 if (!conv) rc_all = FDAPDE_ENOCONV;
                 total += its, worst = std::max(worst, rel[q]);
             }
-            hipLaunchKernelGGL(k_amg_scatter_cols, dim3(gn(n * Q)), dim3(256), 0, st, n, Q, c->dof_i2e.p, (const double*)xq, H.qio.p);
+            hipLaunchKernelGGL(k_amg_scatter, dim3(gn(n * Q)), dim3(256), 0, st, n, Q, c->dof_i2e.p, (const double*)xq, H.qio.p);
             HIPCHK(c, hipGetLastError());
             HIPCHK(c, hipMemcpyAsync(x + (size_t)j * n, H.qio.p, sizeof(double) * nq, hipMemcpyDeviceToHost, st));
             HIPCHK(c, hipStreamSynchronize(st));
@@ -1241,12 +1065,12 @@ int amg_lin_solve(fdapde_ctx* c, const fdapde_options* opt, const double* b, int
         }
         ++H.single_cols;
         HIPCHK(c, hipMemcpyAsync(c->tmp_e.p, b + (size_t)j * n, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_amg_gather, dim3(gn(n)), dim3(256), 0, st, n, c->dof_i2e.p, c->tmp_e.p, rhs.p);
+        hipLaunchKernelGGL(k_amg_gather, dim3(gn(n)), dim3(256), 0, st, n, 1, c->dof_i2e.p, (const double*)c->tmp_e.p, rhs.p);
         const int rc = amg_run(c, c->amg_lin, c->lin_mat.p, rhs.p, nullptr, 0, nullptr, rtol, maxit);
         if (rc != FDAPDE_OK && rc != FDAPDE_ENOCONV) return rc;
         if (rc == FDAPDE_ENOCONV) rc_all = rc;
         total += c->info.iters, worst = std::max(worst, c->info.relres);
-        hipLaunchKernelGGL(k_amg_scatter, dim3(gn(n)), dim3(256), 0, st, n, c->dof_i2e.p, c->u.p, c->tmp_e.p);
+        hipLaunchKernelGGL(k_amg_scatter, dim3(gn(n)), dim3(256), 0, st, n, 1, c->dof_i2e.p, (const double*)c->u.p, c->tmp_e.p);
         HIPCHK(c, hipMemcpyAsync(x + (size_t)j * n, c->tmp_e.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));   // (tmp_e is reused by the next column)
         ++j;

@@ -56,11 +56,6 @@ struct BlockAmg : AmgHierarchy {   // (D: 2 n_L rows; the coarse corrections are
 void block_amg_free(BlockAmg* h) { delete h; }
 
 namespace {
-template <typename F> void by_team(int T, F&& f) {
-    if (T <= 8) f(std::integral_constant<int, 8>{});
-    else f(std::integral_constant<int, 16>{});
-}
-
 // D^-1 of a level's diagonal blocks (today's 1e-14 rule: k_block_diag_inv); *bad: a block was singular
 int level_dinv(fdapde_ctx* c, BamgLevel& L, bool* bad) {
     hipStream_t st = c->stream;
@@ -77,63 +72,36 @@ int level_dinv(fdapde_ctx* c, BamgLevel& L, bool* bad) {
     return FDAPDE_OK;
 }
 
-int level_vectors(fdapde_ctx* c, AmgLevel& L) {
-    const size_t n2 = 2 * (size_t)std::max<int64_t>(L.n, 1);
+// a level's team width and its grid of partials (its work vectors are amg_cols_prepare's)
+void level_team(AmgLevel& L) {
     const double per_row = L.n > 0 ? (double)L.nnz / (double)L.n : 1.0;
     L.team = per_row <= 12.0 ? 8 : 16;
     L.np = (int)std::min<int64_t>(1024, std::max<int64_t>(1, (L.n * L.team + 1023) / 1024));
-    for (DBuf<double>* p : {&L.b, &L.zt, &L.cv, &L.v, &L.dv, &L.w, &L.rt, &L.e}) HIPCHK(c, p->alloc(n2));
-    HIPCHK(c, L.part.alloc(3 * (size_t)std::max(L.np, 1024)));
-    HIPCHK(c, L.sc.alloc(8));
-    HIPCHK(c, hipMemsetAsync(L.sc.p, 0, 8 * sizeof(double), c->stream));
-    return FDAPDE_OK;
 }
 
 // the block cycle's launches: 0.7 D^-1 with the 2 x 2 diagonal blocks as the smoother (kernels_block.h)
-void block_pre_restrict(hipStream_t st, AmgLevel& L, AmgLevel& N, const double* r) {
-    by_team(L.team, [&](auto t) {
-        constexpr int T = decltype(t)::value;
-        hipLaunchKernelGGL(k_bamg_pre_restrict<T>, dim3(g1(N.n, 256 / T)), dim3(256), 0, st, N.n, L.mptr.p, L.midx.p, L.rp, L.ci, blk(L).bv, blk(L).dinv4.p, kBamgOmega, r,
-                           L.zt.p, N.b.p, (const int32_t*)nullptr);
-    });
-}
-void block_post(hipStream_t st, AmgLevel& L, AmgLevel& N, const double* r, double* out) {
-    by_team(L.team, [&](auto t) {
-        constexpr int T = decltype(t)::value;
-        hipLaunchKernelGGL(k_bamg_post<T>, dim3(g1(L.n, 256 / T)), dim3(256), 0, st, L.n, L.rp, L.ci, blk(L).bv, blk(L).dinv4.p, kBamgOmega, L.agg.p, N.e.p, r, L.zt.p, out,
-                           (const int32_t*)nullptr);
-    });
-}
-void block_spmv_dots(hipStream_t st, AmgLevel& L, const double* x, double* y, const double* p0, const double* q0, const double* p1, const double* q1, const double* p2,
-                     const double* q2) {
-    by_team(L.team, [&](auto t) {
-        constexpr int T = decltype(t)::value;
-        hipLaunchKernelGGL(k_bamg_spmv_dots<T>, dim3((unsigned)L.np), dim3(256), 0, st, L.n, L.rp, L.ci, blk(L).bv, x, y, p0, q0, p1, q1, p2, q2, L.part.p,
-                           (const int32_t*)nullptr);
-    });
-}
-void block_pre_restrict_cols(hipStream_t st, int Q, AmgLevel& L, AmgLevel& N, const double* r, double* rc, int64_t rs, int64_t cs) {
+void block_pre_restrict(hipStream_t st, int Q, AmgLevel& L, AmgLevel& N, const double* r, double* rc, int64_t rs, int64_t cs) {
     by_team_cols<8>(L.team, Q, [&](auto t, auto q) {
         constexpr int T = decltype(t)::value, QC = decltype(q)::value;
-        hipLaunchKernelGGL((k_bamg_pre_restrict_cols<T, QC>), dim3(g1(N.n, 256 / T)), dim3(256), 0, st, N.n, L.mptr.p, L.midx.p, L.rp, L.ci, blk(L).bv, blk(L).dinv4.p, kBamgOmega,
-                           r, L.qzt.p, rc, rs, cs);
+        hipLaunchKernelGGL((k_bamg_pre_restrict<T, QC>), dim3(g1(N.n, 256 / T)), dim3(256), 0, st, N.n, L.mptr.p, L.midx.p, L.rp, L.ci, blk(L).bv, blk(L).dinv4.p, kBamgOmega,
+                           r, L.zt.p, rc, rs, cs);
     });
 }
-void block_post_cols(hipStream_t st, int Q, AmgLevel& L, AmgLevel& N, const double* r, double* out) {
+void block_post(hipStream_t st, int Q, AmgLevel& L, AmgLevel& N, const double* r, double* out) {
     by_team_cols<8>(L.team, Q, [&](auto t, auto q) {
         constexpr int T = decltype(t)::value, QC = decltype(q)::value;
-        hipLaunchKernelGGL((k_bamg_post_cols<T, QC>), dim3(g1(L.n, 256 / T)), dim3(256), 0, st, L.n, L.rp, L.ci, blk(L).bv, blk(L).dinv4.p, kBamgOmega, L.agg.p, N.qe.p, r,
-                           L.qzt.p, out);
+        hipLaunchKernelGGL((k_bamg_post<T, QC>), dim3(g1(L.n, 256 / T)), dim3(256), 0, st, L.n, L.rp, L.ci, blk(L).bv, blk(L).dinv4.p, kBamgOmega, L.agg.p, N.e.p, r,
+                           L.zt.p, out);
     });
 }
-void block_spmv_dots_cols(hipStream_t st, int Q, AmgLevel& L, const double* x, double* y, const double* p0, const double* q0, const double* p1, const double* q1,
-                          const double* p2, const double* q2) {
+void block_spmv_dots(hipStream_t st, int Q, AmgLevel& L, const double* x, double* y, const double* p0, const double* q0, const double* p1, const double* q1,
+                     const double* p2, const double* q2) {
     by_team_cols<8>(L.team, Q, [&](auto t, auto q) {
         constexpr int T = decltype(t)::value, QC = decltype(q)::value;
-        hipLaunchKernelGGL((k_bamg_spmv_dots_cols<T, QC>), dim3((unsigned)L.np), dim3(256), 0, st, L.n, L.rp, L.ci, blk(L).bv, x, y, p0, q0, p1, q1, p2, q2, L.qpart.p);
+        hipLaunchKernelGGL((k_bamg_spmv_dots<T, QC>), dim3((unsigned)L.np), dim3(256), 0, st, L.n, L.rp, L.ci, blk(L).bv, x, y, p0, q0, p1, q1, p2, q2, L.part.p);
     });
 }
-constexpr AmgCycleOps kBlockOps{block_pre_restrict, block_post, block_spmv_dots, block_pre_restrict_cols, block_post_cols, block_spmv_dots_cols};
+constexpr AmgCycleOps kBlockOps{block_pre_restrict, block_post, block_spmv_dots};
 
 // the hierarchy with (absorb) or without absorption on every level; *stalled: the answer is the "coarsening stalled above the dense limit" refusal
 int block_amg_build_pass(fdapde_ctx* c, BlockAmg** slot, const double* raw, int strength_block, int absorb, bool* stalled) {
@@ -181,8 +149,8 @@ int block_amg_build_pass(fdapde_ctx* c, BlockAmg** slot, const double* raw, int 
         E.agg.release(), E.mptr.release(), E.midx.release(), E.dinv4.release();
         break;
     }
-    for (auto& L : H->lv)
-        if (int rc = level_vectors(c, *L)) return rc;
+    for (auto& L : H->lv) level_team(*L);
+    if (int rc = amg_cols_prepare(c, *H, 1)) return rc;   // (the work vectors: one column until a batch asks for more)
     BamgLevel& C = blk(*H->lv.back());
     if (2 * C.n > kDenseMaxRows) return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_BLOCK_AMG: the coarsest level is too large for the dense inverse");
     HIPCHK(c, H->rp2.alloc((size_t)(2 * C.n + 1)));
@@ -250,6 +218,7 @@ int block_amg_run(fdapde_ctx* c, BlockAmg* hp, const double* raw, const double* 
     const int64_t n = L0.n, n2 = 2 * n;
     const int np = (int)std::min<int64_t>(1024, std::max<int64_t>(1, (n2 + 4095) / 4096));
     const int mk = block_restart_len(c, maxit);
+    if (int rc = amg_cols_prepare(c, H, 1)) return rc;
     HIPCHK(c, H.vec.alloc(2 * (size_t)n2));
     HIPCHK(c, H.basis.alloc((size_t)(2 * mk + 1) * (size_t)n2));
     HIPCHK(c, H.part.alloc((size_t)(mk + 2) * (size_t)np + 3 * (size_t)np));
@@ -282,8 +251,8 @@ int block_amg_run(fdapde_ctx* c, BlockAmg* hp, const double* raw, const double* 
     const bool one_level = H.lv.size() == 1;
     auto precond = [&](const double* v, double* z, double* w, bool&) -> int {
         if (one_level) {
-            if (int rc = dense_apply(c, H.D, 1, v, z)) return rc;
-        } else if (int rc = amg_cycle(c, H, 0, v, z))
+            if (int rc = amg_dense_cols(c, H, 1, v, z)) return rc;
+        } else if (int rc = amg_cycle(c, H, 0, 1, v, z))
             return rc;
         spmv(z, w);
         return FDAPDE_OK;
@@ -354,7 +323,7 @@ int block_amg_batch(fdapde_ctx* c, BlockAmg* hp, const double* raw, int Q, doubl
     auto precond = [&](const double* v, double* z, double* w) -> int {
         if (one_level) {
             if (int rc = amg_dense_cols(c, H, Q, v, z)) return rc;
-        } else if (int rc = amg_cycle_cols(c, H, 0, Q, v, z))
+        } else if (int rc = amg_cycle(c, H, 0, Q, v, z))
             return rc;
         spmv(z, w);
         return FDAPDE_OK;

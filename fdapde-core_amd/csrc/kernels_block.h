@@ -170,115 +170,20 @@ static __global__ void k_block_expand(int64_t n, const int32_t* rowptr, const in
 // ---- the multilevel cycle of FDAPDE_SOLVER_BLOCK_AMG (eng_block_amg.hip): block forms of eng_amg.hip's cycle kernels ------------------------------
 // A level is a block CSR matrix (rp / ci / four doubles per entry), the inverted 2 x 2 diagonal blocks dinv (four doubles per row) and vectors
 // interleaved per row; the smoother is om D^-1.  The access pattern is k_block_spmv's: a team of T lanes per row (or aggregate), a lane takes whole
-// entries (two 16-byte loads, one index, 16-byte gathers), no load past a row's end, the fixed team_sum butterfly, the stop flag first.
+// entries (two 16-byte loads, one index, 16-byte gathers), no load past a row's end, the fixed team_sum butterfly.
 __device__ __forceinline__ blk_v2f64_t blk_ld2(const double* p) { return *reinterpret_cast<const blk_v2f64_t*>(p); }
-__device__ __forceinline__ blk_v2f64_t blk_mul(const blk_v2f64_t top, const blk_v2f64_t bot, const blk_v2f64_t v) {
-    return blk_v2f64_t{top.x * v.x + top.y * v.y, bot.x * v.x + bot.y * v.y};
-}
-
-// pre-smoothing from zero and the restricted residual in one pass, a team per aggregate: zt_i = om D_i^-1 r_i for its members i, and
-// rc_a = sum over members of (r_i - om sum_j A_ij D_j^-1 r_j)
-template <int T>
-static __global__ __launch_bounds__(256) void k_bamg_pre_restrict(int64_t nc, const int32_t* mptr, const int32_t* midx, const int32_t* rp, const int32_t* ci,
-                                                                  const double* bv, const double* dinv, double om, const double* r, double* zt, double* rc,
-                                                                  const int32_t* stop) {
-    if (stop && __syncthreads_or(*stop != 0)) return;
-    const int lane = threadIdx.x % T;
-    const int64_t ag = (int64_t)blockIdx.x * (256 / T) + threadIdx.x / T;
-    if (ag >= nc) return;   // (whole teams leave together: T divides the wavefront)
-    double c0 = 0.0, c1 = 0.0;
-    for (int32_t q = mptr[ag]; q < mptr[ag + 1]; ++q) {
-        const int32_t i = midx[q];
-        double s0 = 0.0, s1 = 0.0;
-        for (int32_t k = rp[i] + lane; k < rp[i + 1]; k += T) {
-            const blk_v2f64_t top = blk_ld2(bv + 4 * (int64_t)k), bot = blk_ld2(bv + 4 * (int64_t)k + 2);
-            const int64_t j = ci[k];
-            const blk_v2f64_t y = blk_mul(blk_ld2(dinv + 4 * j), blk_ld2(dinv + 4 * j + 2), blk_ld2(r + 2 * j));
-            const blk_v2f64_t t = blk_mul(top, bot, y);
-            s0 += t.x, s1 += t.y;
-        }
-        s0 = team_sum<T>(s0), s1 = team_sum<T>(s1);
-        const blk_v2f64_t ri = blk_ld2(r + 2 * (int64_t)i);
-        if (lane == 0) {
-            const blk_v2f64_t y = blk_mul(blk_ld2(dinv + 4 * (int64_t)i), blk_ld2(dinv + 4 * (int64_t)i + 2), ri);
-            *reinterpret_cast<blk_v2f64_t*>(zt + 2 * (int64_t)i) = blk_v2f64_t{om * y.x, om * y.y};
-        }
-        c0 += ri.x - om * s0, c1 += ri.y - om * s1;
-    }
-    if (lane == 0) *reinterpret_cast<blk_v2f64_t*>(rc + 2 * ag) = blk_v2f64_t{c0, c1};
-}
-// out_i = z_i + om D_i^-1 (r_i - sum_j A_ij z_j) with z = zt + P e: prolongation (every row has an aggregate), residual and post-smoothing in one pass
-template <int T>
-static __global__ __launch_bounds__(256) void k_bamg_post(int64_t n, const int32_t* rp, const int32_t* ci, const double* bv, const double* dinv, double om,
-                                                          const int32_t* agg, const double* e, const double* r, const double* zt, double* out, const int32_t* stop) {
-    if (stop && __syncthreads_or(*stop != 0)) return;
-    const int lane = threadIdx.x % T;
-    const int64_t i = (int64_t)blockIdx.x * (256 / T) + threadIdx.x / T;
-    if (i >= n) return;
-    double s0 = 0.0, s1 = 0.0;
-    for (int32_t k = rp[i] + lane; k < rp[i + 1]; k += T) {
-        const blk_v2f64_t top = blk_ld2(bv + 4 * (int64_t)k), bot = blk_ld2(bv + 4 * (int64_t)k + 2);
-        const int64_t j = ci[k];
-        const blk_v2f64_t z = blk_ld2(zt + 2 * j) + blk_ld2(e + 2 * (int64_t)agg[j]);
-        const blk_v2f64_t t = blk_mul(top, bot, z);
-        s0 += t.x, s1 += t.y;
-    }
-    s0 = team_sum<T>(s0), s1 = team_sum<T>(s1);
-    if (lane == 0) {
-        const blk_v2f64_t zi = blk_ld2(zt + 2 * i) + blk_ld2(e + 2 * (int64_t)agg[i]), ri = blk_ld2(r + 2 * i);
-        const blk_v2f64_t d = blk_mul(blk_ld2(dinv + 4 * i), blk_ld2(dinv + 4 * i + 2), blk_v2f64_t{ri.x - s0, ri.y - s1});
-        *reinterpret_cast<blk_v2f64_t*>(out + 2 * i) = blk_v2f64_t{zi.x + om * d.x, zi.y + om * d.y};
-    }
-}
-// y = A x and the three dot products p_q . q_q of a GCR step (any of the vectors may be y itself) as per-workgroup partials part[q * gridDim.x + block]:
-// a fixed grid, every team strides over the rows, the same bits every run
-template <int T>
-static __global__ __launch_bounds__(256) void k_bamg_spmv_dots(int64_t n, const int32_t* rp, const int32_t* ci, const double* bv, const double* x, double* y,
-                                                               const double* p0, const double* q0, const double* p1, const double* q1, const double* p2,
-                                                               const double* q2, double* part, const int32_t* stop) {
-    if (stop && __syncthreads_or(*stop != 0)) return;
-    __shared__ double red[3][4];
-    const int lane = threadIdx.x % T;
-    double d0 = 0.0, d1 = 0.0, d2 = 0.0;
-    const int64_t teams = (int64_t)gridDim.x * (256 / T);
-    for (int64_t i = (int64_t)blockIdx.x * (256 / T) + threadIdx.x / T; i < n; i += teams) {
-        double s0 = 0.0, s1 = 0.0;
-        for (int32_t k = rp[i] + lane; k < rp[i + 1]; k += T) {
-            const blk_v2f64_t top = blk_ld2(bv + 4 * (int64_t)k), bot = blk_ld2(bv + 4 * (int64_t)k + 2);
-            const blk_v2f64_t t = blk_mul(top, bot, blk_ld2(x + 2 * (int64_t)ci[k]));
-            s0 += t.x, s1 += t.y;
-        }
-        s0 = team_sum<T>(s0), s1 = team_sum<T>(s1);
-        if (lane == 0) {
-            const blk_v2f64_t yi{s0, s1};
-            *reinterpret_cast<blk_v2f64_t*>(y + 2 * i) = yi;
-            auto val = [&](const double* v) { return v == y ? yi : blk_ld2(v + 2 * i); };
-            auto dot = [&](const double* a, const double* b) {
-                const blk_v2f64_t u = val(a), w = val(b);
-                return u.x * w.x + u.y * w.y;
-            };
-            d0 += dot(p0, q0), d1 += dot(p1, q1);
-            if (p2) d2 += dot(p2, q2);
-        }
-    }
-    d0 = wave_sum(d0), d1 = wave_sum(d1), d2 = wave_sum(d2);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) red[0][w] = d0, red[1][w] = d1, red[2][w] = d2;
-    __syncthreads();
-    if (threadIdx.x < 3) part[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
-}
 // r = b - t (the outer iteration's true residual, t = A x)
 static __global__ void k_bamg_residual(int64_t n2, const double* b, const double* t, double* r) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n2) r[i] = b[i] - t[i];
 }
-// ---- ... for Q interleaved columns (kernels_cols.h): unknown u of DOF i, column q at [(2 i + u) Q + q].  Per column the arithmetic of the kernel of the same
-// name above, in the same order (the same team, the same entries to the same lanes, blk_mul, team_sum, the same grid of partials), Q accumulator pairs per
-// lane; the blocks and indices are read once for all columns, a gathered DOF is 2 Q contiguous doubles.  (The outer iteration's r = b - t is k_bamg_residual
-// itself over the 2 n Q words.)
-// The arithmetic is spelled out with contraction off: the single-column kernels are compiled with the default contraction, which turns blk_mul's and the dot
-// products' a.x b.x + a.y b.y into fma(a.x, b.x, a.y b.y), r - om s into fma(-om, s, r) and z + om d into fma(om, d, z), and leaves every accumulation a plain
-// addition; left to itself the compiler fuses the unrolled column forms differently at some widths, and a column's last bits would depend on its batch.
+// ---- The cycle kernels take Q in {1, 2, 4, 8} interleaved columns (kernels_cols.h): unknown u of DOF i, column q at [(2 i + u) Q + q]; the single-column solve
+// runs their Q = 1 instantiations.  A column's arithmetic does not depend on Q (the same team, the same entries to the same lanes, blk_mul_cols, team_sum, the same
+// grid of partials), Q accumulator pairs per lane; the blocks and indices are read once for all columns, a gathered DOF is 2 Q contiguous doubles.  (The outer
+// iteration's r = b - t is k_bamg_residual over the 2 n Q words.)
+// The arithmetic is spelled out with contraction off: a.x b.x + a.y b.y as fma(a.x, b.x, a.y b.y), r - om s as fma(-om, s, r), z + om d as fma(om, d, z), every
+// accumulation a plain addition; left to itself the compiler fuses the unrolled column forms differently at some widths, and a column's last bits would depend
+// on its batch.
 __device__ __forceinline__ blk_v2f64_t blk_mul_cols(const blk_v2f64_t top, const blk_v2f64_t bot, const blk_v2f64_t v) {
 #pragma clang fp contract(off)
     return blk_v2f64_t{__builtin_fma(top.x, v.x, top.y * v.y), __builtin_fma(bot.x, v.x, bot.y * v.y)};
@@ -299,6 +204,7 @@ template <int Q> __device__ __forceinline__ void blk_st_cols(double* p, const bl
     for (int q = 0; q < Q; ++q) a[q] = v[q].x, b[q] = v[q].y;
     st_cols<Q>(p, a), st_cols<Q>(p + Q, b);
 }
+// k_block_spmv for the Q >= 2 columns of a batch's outer iteration (no stop flag)
 template <int T, int Q>
 static __global__ __launch_bounds__(256) void k_block_spmv_cols(int64_t n, const int32_t* rowptr, const int32_t* colidx, const double* vals, const double* x, double* y) {
 #pragma clang fp contract(off)
@@ -328,11 +234,13 @@ static __global__ __launch_bounds__(256) void k_block_spmv_cols(int64_t n, const
     for (int q = 0; q < Q; ++q) o[q] = blk_v2f64_t{team_sum<T>(a0[q]), team_sum<T>(a1[q])};
     if (l == 0 && row_ok) blk_st_cols<Q>(y + 2 * row * Q, o);
 }
-// rc: unknown u of aggregate a, column q at rc[(2 a + u) rs + q cs] (interleaved, or column-major for the dense inverse of the coarsest level)
+// pre-smoothing from zero and the restricted residual in one pass, a team per aggregate: zt_i = om D_i^-1 r_i for its members i, and
+// rc_a = sum over members of (r_i - om sum_j A_ij D_j^-1 r_j); unknown u of aggregate a, column q at rc[(2 a + u) rs + q cs] (interleaved, or column-major for
+// the dense inverse of the coarsest level)
 template <int T, int Q>
-static __global__ __launch_bounds__(256) void k_bamg_pre_restrict_cols(int64_t nc, const int32_t* mptr, const int32_t* midx, const int32_t* rp, const int32_t* ci,
-                                                                       const double* bv, const double* dinv, double om, const double* r, double* zt, double* rc,
-                                                                       int64_t rs, int64_t cs) {
+static __global__ __launch_bounds__(256) void k_bamg_pre_restrict(int64_t nc, const int32_t* mptr, const int32_t* midx, const int32_t* rp, const int32_t* ci,
+                                                                  const double* bv, const double* dinv, double om, const double* r, double* zt, double* rc,
+                                                                  int64_t rs, int64_t cs) {
 #pragma clang fp contract(off)
     const int lane = threadIdx.x % T;
     const int64_t ag = (int64_t)blockIdx.x * (256 / T) + threadIdx.x / T;
@@ -380,9 +288,10 @@ static __global__ __launch_bounds__(256) void k_bamg_pre_restrict_cols(int64_t n
         for (int q = 0; q < Q; ++q) rc[2 * ag * rs + q * cs] = c0[q], rc[(2 * ag + 1) * rs + q * cs] = c1[q];
     }
 }
+// out_i = z_i + om D_i^-1 (r_i - sum_j A_ij z_j) with z = zt + P e: prolongation (every row has an aggregate), residual and post-smoothing in one pass
 template <int T, int Q>
-static __global__ __launch_bounds__(256) void k_bamg_post_cols(int64_t n, const int32_t* rp, const int32_t* ci, const double* bv, const double* dinv, double om,
-                                                               const int32_t* agg, const double* e, const double* r, const double* zt, double* out) {
+static __global__ __launch_bounds__(256) void k_bamg_post(int64_t n, const int32_t* rp, const int32_t* ci, const double* bv, const double* dinv, double om,
+                                                          const int32_t* agg, const double* e, const double* r, const double* zt, double* out) {
 #pragma clang fp contract(off)
     const int lane = threadIdx.x % T;
     const int64_t i = (int64_t)blockIdx.x * (256 / T) + threadIdx.x / T;
@@ -417,11 +326,12 @@ static __global__ __launch_bounds__(256) void k_bamg_post_cols(int64_t n, const 
         blk_st_cols<Q>(out + 2 * i * Q, o);
     }
 }
-// dot d of column q: part[(d Q + q) gridDim.x + block]
+// y = A x and the three dot products p_d . q_d of a GCR step per column (any of the vectors may be y itself) as per-workgroup partials
+// part[(d Q + q) gridDim.x + block]: a fixed grid, every team strides over the rows, the same bits every run
 template <int T, int Q>
-static __global__ __launch_bounds__(256) void k_bamg_spmv_dots_cols(int64_t n, const int32_t* rp, const int32_t* ci, const double* bv, const double* x, double* y,
-                                                                    const double* p0, const double* q0, const double* p1, const double* q1, const double* p2,
-                                                                    const double* q2, double* part) {
+static __global__ __launch_bounds__(256) void k_bamg_spmv_dots(int64_t n, const int32_t* rp, const int32_t* ci, const double* bv, const double* x, double* y,
+                                                               const double* p0, const double* q0, const double* p1, const double* q1, const double* p2,
+                                                               const double* q2, double* part) {
 #pragma clang fp contract(off)
     __shared__ double red[3 * Q][4];
     const int lane = threadIdx.x % T;

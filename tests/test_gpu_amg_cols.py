@@ -1,7 +1,7 @@
-"""The columns of fdapde_lin_solve under FDAPDE_SOLVER_AMG side by side (knob `amg_cols`; csrc/eng_amg.hip: the k_amg_*_cols kernels, amg_cycle_cols; csrc/eng_pmg.hip:
-fgmres_outer_cols), against the column-by-column path (`amg_cols` = 1) on the same hierarchy.
+"""The columns of fdapde_lin_solve under FDAPDE_SOLVER_AMG side by side (knob `amg_cols`; csrc/eng_amg.hip: the cycle kernels at Q = 2, 4, 8 columns, amg_cycle; csrc/eng_pmg.hip:
+fgmres_outer_cols), against the column-by-column path (`amg_cols` = 1: the same kernels at Q = 1) on the same hierarchy.
 
-With the hierarchy fixed the k-th iterate of a column is ONE vector, and every kernel of the batch orders a column's sums as its single-column form does: a batch
+With the hierarchy fixed the k-th iterate of a column is ONE vector, and every cycle kernel orders a column's sums in the same way at every width: a batch
 must hand out the column-by-column run's BITS -- np.array_equal per column at `rtol = 1e-30, maxit = k` (k = 1, 2, 5) and at convergence.  Right-hand sides of
 different difficulty stop at different iterations: a smooth column, a unit vector, a column of zeros, a column scaled by 1e-150, random columns; n_rhs = 11 goes as
 8 + 2 + 1, n_rhs = 7 under `amg_cols` = 4 as 4 + 2 + 1.  `amg_coarse_rows` = 256 and `amg_setup_check` = 1 throughout, as tests/test_gpu_amg.py."""

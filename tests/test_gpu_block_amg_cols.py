@@ -1,4 +1,4 @@
-"""The columns of fdapde_block_solve under FDAPDE_SOLVER_BLOCK_AMG side by side (knob `amg_cols`; the k_bamg_*_cols kernels and k_block_spmv_cols of
+"""The columns of fdapde_block_solve under FDAPDE_SOLVER_BLOCK_AMG side by side (knob `amg_cols`; the k_bamg_* kernels at Q = 2, 4, 8 columns and k_block_spmv_cols of
 csrc/kernels_block.h, block_amg_batch of csrc/eng_block_amg.hip, fgmres_outer_cols of csrc/eng_pmg.hip), against the column-by-column path (`amg_cols` = 1) on
 the same hierarchy: np.array_equal per column at the k-th iterate (`rtol = 1e-30, maxit = k`, k = 1, 2, 5) and at convergence.
 
