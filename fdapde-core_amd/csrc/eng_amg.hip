@@ -172,7 +172,7 @@ __global__ void k_amg_scale(int64_t n, const double* a, double f, double* out) {
 // columns (kernels_cols.h): word i of column q at [i * Q + q].  A column's arithmetic does not depend on Q -- the same team width, the same entries to the same
 // lanes, the same team_sum / wave_sum / block_sum, the same grid of partials -- with Q accumulators per lane; the matrix and its indices are read once for all
 // columns, a gathered operand is Q contiguous doubles.  No column reads another.  The single-column solve runs the Q = 1 instantiations.
-// These kernels (and k_pmg_*_cols of eng_pmg.hip) write each expression once and leave its contraction to the compiler, which fuses the unrolled per-column
+// These kernels (and the Gram-Schmidt kernels of eng_pmg.hip) write each expression once and leave its contraction to the compiler, which fuses the unrolled per-column
 // copies of every width, Q = 1 included, alike (s += a x, r - om s, z + om d (r - s), w -= h v): that is a property of this compiler, not of the language -- the
 // block forms in kernels_block.h needed theirs spelled out.  tests/test_gpu_amg_cols.py holds every column of Q = 2, 4, 8 to the Q = 1 run's bits on 2-D and
 // 3-D, P1 and P2 hierarchies; if a toolchain changes a width's fusion that test fails, and the remedy is kernels_block.h's.
@@ -826,10 +826,11 @@ int amg_dense_cols(fdapde_ctx* c, AmgHierarchy& H, int Q, const double* v, doubl
 }
 
 namespace {
-// amg_run for Q columns of the handle (no Dirichlet rows, no warm start): f, x interleaved on the device (x is written).  Per column what amg_run does, the
-// outer iteration in lockstep (fgmres_outer_cols); relres: the true relative residuals of what is handed out
-int amg_run_cols(fdapde_ctx* c, AmgHierarchy& H, const double* A, int Q, const double* f, double* x, double* r, double* t, double rtol, int maxit, int mk, FgmresCols& S,
-                 double* relres) {
+// One run against the hierarchy H for Q interleaved columns: K u = rhs per column (K: A with the Dirichlet rows as unit rows if use_bnd; rhs = f on the free rows,
+// g on the Dirichlet rows), from x0 or from g / 0; f, g, x0, x interleaved on the device (x is written; g, x0 may be null).  The outer iteration is
+// fgmres_outer at width Q; relres: the true relative residuals of what is handed out.  amg_run is the call at Q = 1, a batch of the handle one at Q = 2, 4, 8
+int amg_run_cols(fdapde_ctx* c, AmgHierarchy& H, const double* A, int Q, const uint8_t* bnd, int use_bnd, const double* f, const double* g, const double* x0, double* x,
+                 double* r, double* t, double rtol, int maxit, int mk, FgmresCols& S, double* relres) {
     hipStream_t st = c->stream;
     AmgLevel& L0 = *H.lv[0];
     const int64_t n = L0.n;
@@ -845,18 +846,26 @@ int amg_run_cols(fdapde_ctx* c, AmgHierarchy& H, const double* A, int Q, const d
         HIPCHK(c, hipStreamSynchronize(st));
         return FDAPDE_OK;
     };
-    auto apply_K = [&](const double* in, const double* rhs, double* out) {
+    auto apply_K = [&](const double* in, const double* rhs, double* out) {   // out = K in, or (rhs given) rhs - K in
         by_team_cols<4>(L0.team, Q, [&](auto tt, auto q) {
             constexpr int T = decltype(tt)::value, QC = decltype(q)::value;
-            hipLaunchKernelGGL((k_amg_apply_K<T, QC>), dim3(gn(n * T)), dim3(256), 0, st, n, L0.rp, L0.ci, A, (const uint8_t*)nullptr, 0, in, rhs, (const double*)nullptr, out);
+            hipLaunchKernelGGL((k_amg_apply_K<T, QC>), dim3(gn(n * T)), dim3(256), 0, st, n, L0.rp, L0.ci, A, bnd, use_bnd, in, rhs, g, out);
         });
     };
-    hipLaunchKernelGGL(k_amg_start, dim3(gn(n * Q)), dim3(256), 0, st, n, Q, (const uint8_t*)nullptr, 0, (const double*)nullptr, (const double*)nullptr, x);
+    // the lift of the Dirichlet data: the stop rule is relative to its residual (as the two-level solver's)
+    hipLaunchKernelGGL(k_amg_start, dim3(gn(n * Q)), dim3(256), 0, st, n, Q, bnd, use_bnd, g, (const double*)nullptr, x);
     apply_K(x, f, r);
     if (int rc = dots(r)) return rc;
-    for (int q = 0; q < Q; ++q) S.bb[q] = S.rr[q] = h[q], S.converged[q] = S.rr[q] <= rtol * rtol * S.bb[q], S.broke[q] = false;
+    for (int q = 0; q < Q; ++q) S.bb[q] = S.rr[q] = h[q];
+    if (x0) {
+        hipLaunchKernelGGL(k_amg_start, dim3(gn(n * Q)), dim3(256), 0, st, n, Q, bnd, use_bnd, g, x0, x);
+        apply_K(x, f, r);
+        if (int rc = dots(r)) return rc;
+        std::copy(h, h + Q, S.rr);
+    }
+    for (int q = 0; q < Q; ++q) S.converged[q] = S.rr[q] <= rtol * rtol * S.bb[q], S.broke[q] = false;
     const bool one_level = H.lv.size() == 1;
-    auto precond = [&](const double* v, double* z, double* w) -> int {
+    auto precond = [&](const double* v, double* z, double* w, bool&) -> int {
         if (one_level) {
             if (int rc = amg_dense_cols(c, H, Q, v, z)) return rc;
         } else if (int rc = amg_cycle(c, H, 0, Q, v, z))
@@ -871,7 +880,7 @@ int amg_run_cols(fdapde_ctx* c, AmgHierarchy& H, const double* A, int Q, const d
         return FDAPDE_OK;
     };
     FgmresSpace fs{n, mk, H.basis.p, H.basis.p + (size_t)(mk + 1) * (size_t)n * (size_t)Q, H.part.p, H.dots.p, H.np};
-    if (int rc = fgmres_outer_cols(c, fs, Q, x, r, rtol, maxit, precond, residual, S)) return rc;
+    if (int rc = fgmres_outer(c, fs, Q, x, r, nullptr, rtol, maxit, precond, residual, S)) return rc;
     // the TRUE residuals of what is handed out
     apply_K(x, f, t);
     if (int rc = dots(t)) return rc;
@@ -884,72 +893,20 @@ int amg_run_cols(fdapde_ctx* c, AmgHierarchy& H, const double* A, int Q, const d
 }
 }   // namespace
 
+// the single column: amg_run_cols at Q = 1 on the hierarchy's own vectors, the context's Dirichlet mask, its result and its record
 int amg_run(fdapde_ctx* c, AmgHierarchy* hp, const double* A, const double* f_dev, const double* g_dev, int use_bnd, const double* x0_dev, double rtol, int maxit) {
     AmgHierarchy& H = *hp;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
-    AmgLevel& L0 = *H.lv[0];
-    const int64_t n = L0.n;
+    const int64_t n = H.lv[0]->n;
     const auto t_begin = std::chrono::steady_clock::now();
-    const dim3 gv(gn(n)), bv(256);
-    H.np = (int)std::min<int64_t>(1024, std::max<int64_t>(1, (n + 4095) / 4096));
-    const int mk = amg_restart_len(n, maxit);
-    if (int rc = amg_cols_prepare(c, H, 1)) return rc;
     HIPCHK(c, H.vec.alloc(3 * (size_t)n));
-    HIPCHK(c, H.basis.alloc((size_t)(2 * mk + 1) * (size_t)n));
-    HIPCHK(c, H.part.alloc((size_t)(mk + 2) * (size_t)H.np));
-    HIPCHK(c, H.dots.alloc((size_t)(mk + 4)));
     double *x = H.vec.p, *r = x + n, *t = r + n;
-    const uint8_t* bnd = c->bnd.p;
-    double h[3] = {0, 0, 0};
-    auto dots = [&](const double* a0, const double* b0) -> int {
-        fixed_dots(st, n, H.np, a0, b0, nullptr, nullptr, nullptr, nullptr, H.part.p, H.dots.p);
-        HIPCHK(c, hipMemcpyAsync(h, H.dots.p, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        return FDAPDE_OK;
-    };
-    auto apply_K = [&](const double* in, const double* f, double* out) {   // out = K in, or (f given) rhs - K in
-        by_team_cols<4>(L0.team, 1, [&](auto tt, auto q) {
-            constexpr int T = decltype(tt)::value, QC = decltype(q)::value;
-            hipLaunchKernelGGL((k_amg_apply_K<T, QC>), dim3(gn(n * T)), bv, 0, st, n, L0.rp, L0.ci, A, bnd, use_bnd, in, f, g_dev, out);
-        });
-    };
-    // the lift of the Dirichlet data: the stop rule is relative to its residual (as the two-level solver's)
-    hipLaunchKernelGGL(k_amg_start, gv, bv, 0, st, n, 1, bnd, use_bnd, g_dev, (const double*)nullptr, x);
-    apply_K(x, f_dev, r);
-    if (int rc = dots(r, r)) return rc;
-    const double bb = h[0];
-    double rr = h[0];
-    if (x0_dev) {
-        hipLaunchKernelGGL(k_amg_start, gv, bv, 0, st, n, 1, bnd, use_bnd, g_dev, x0_dev, x);
-        apply_K(x, f_dev, r);
-        if (int rc = dots(r, r)) return rc;
-        rr = h[0];
-    }
-    int it = 0;
-    bool converged = rr <= rtol * rtol * bb, broke = false;
-    const bool one_level = H.lv.size() == 1;
-    auto precond = [&](const double* v, double* z, double* w, bool&) -> int {
-        if (one_level) {
-            if (int rc = amg_dense_cols(c, H, 1, v, z)) return rc;
-        } else if (int rc = amg_cycle(c, H, 0, 1, v, z))
-            return rc;
-        apply_K(z, nullptr, w);
-        return FDAPDE_OK;
-    };
-    auto residual = [&](double& rr_out) -> int {
-        apply_K(x, f_dev, r);
-        if (int rc = dots(r, r)) return rc;
-        rr_out = h[0];
-        return FDAPDE_OK;
-    };
-    FgmresSpace fs{n, mk, H.basis.p, H.basis.p + (size_t)(mk + 1) * (size_t)n, H.part.p, H.dots.p, H.np};
-    if (int rc = fgmres_outer(c, fs, x, r, nullptr, rtol, maxit, bb, precond, residual, rr, it, converged, broke)) return rc;
-    // the TRUE residual of what is handed out
-    apply_K(x, f_dev, t);
-    if (int rc = dots(t, t)) return rc;
-    const double true_rel = bb > 0 ? std::sqrt(h[0] / bb) : 0.0;
-    if (converged && !(true_rel <= 10.0 * rtol)) converged = false;
+    FgmresCols S{};
+    double true_rel = 0.0;
+    if (int rc = amg_run_cols(c, H, A, 1, c->bnd.p, use_bnd, f_dev, g_dev, x0_dev, x, r, t, rtol, maxit, amg_restart_len(n, maxit), S, &true_rel)) return rc;
+    const int it = S.it[0];
+    const bool converged = S.converged[0], broke = S.broke[0];
     HIPCHK(c, c->u.alloc((size_t)n));
     HIPCHK(c, hipMemcpyAsync(c->u.p, x, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
     HIPCHK(c, hipStreamSynchronize(st));
@@ -1039,12 +996,12 @@ int amg_lin_solve(fdapde_ctx* c, const fdapde_options* opt, const double* b, int
             hipLaunchKernelGGL(k_amg_gather, dim3(gn(n * Q)), dim3(256), 0, st, n, Q, c->dof_i2e.p, (const double*)H.qio.p, f);
             FgmresCols S{};
             double rel[kAmgColsMax];
-            if (int rc = amg_run_cols(c, H, c->lin_mat.p, Q, f, xq, r, t, rtol, maxit, mk, S, rel)) return rc;
+            if (int rc = amg_run_cols(c, H, c->lin_mat.p, Q, nullptr, 0, f, nullptr, nullptr, xq, r, t, rtol, maxit, mk, S, rel)) return rc;
             ++H.batches, H.batched_cols += Q;
             for (int q = 0; q < Q; ++q) {
                 bool conv = S.converged[q];
                 int its = S.it[q];
-                if (S.handed[q]) {   // the recurrence and the true residual disagreed: the rest of this column on the single-column path, from its iterate
+                if (S.handed[q]) {   // the recurrence and the true residual disagreed: the rest of this column alone, from its iterate
                     hipLaunchKernelGGL(k_amg_col_get, dim3(gn(n)), dim3(256), 0, st, n, Q, q, (const double*)f, rhs.p);
                     hipLaunchKernelGGL(k_amg_col_get, dim3(gn(n)), dim3(256), 0, st, n, Q, q, (const double*)xq, c->tmp_e.p);
                     const int rc = amg_run(c, c->amg_lin, c->lin_mat.p, rhs.p, nullptr, 0, c->tmp_e.p, rtol, maxit - its);

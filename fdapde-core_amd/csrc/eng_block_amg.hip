@@ -208,71 +208,92 @@ int block_amg_aggregates(fdapde_ctx* c, const BlockAmg* H, int32_t level, int64_
 int block_amg_cols_trace(const BlockAmg* H, int32_t* batches, int32_t* batched_cols, int32_t* single_cols) { return amg_cols_trace(H, batches, batched_cols, single_cols); }
 void block_amg_count_single(BlockAmg* H) { ++H->single_cols; }
 
-// one column: A x = b (both interleaved, internal order, on the device; x is written -- warm: x holds the iterate to start from), raw = the matrix the
-// hierarchy was built from
-int block_amg_run(fdapde_ctx* c, BlockAmg* hp, const double* raw, const double* b_dev, double* x_dev, double rtol, int maxit, int* iters, double* relres,
-                  bool* converged_out, bool* broke_out, bool warm) {
-    BlockAmg& H = *hp;
+namespace {
+// One run against the hierarchy for Q columns side by side: A x = b per column (b, x: 2 n Q words, the columns interleaved as in kernels_cols.h, internal order,
+// on the device; x is written -- warm: x holds the iterates to start from; r, t: scratch of the same size), raw = the matrix the hierarchy was built from.  The
+// outer iteration is fgmres_outer at width Q; what is handed out is judged by its own residual: S.converged, and rel = |b - A x| / |b| per column.
+// block_amg_run is the call at Q = 1, block_amg_batch drives those at Q = 2, 4, 8
+int block_amg_cols(fdapde_ctx* c, BlockAmg& H, const double* raw, int Q, const double* b, double* x, double* r, double* t, bool warm, double rtol, int maxit,
+                   FgmresCols& S, double* rel) {
     hipStream_t st = c->stream;
     AmgLevel& L0 = *H.lv[0];
     const int64_t n = L0.n, n2 = 2 * n;
+    const size_t nq = (size_t)n2 * (size_t)Q;
     const int np = (int)std::min<int64_t>(1024, std::max<int64_t>(1, (n2 + 4095) / 4096));
     const int mk = block_restart_len(c, maxit);
-    if (int rc = amg_cols_prepare(c, H, 1)) return rc;
-    HIPCHK(c, H.vec.alloc(2 * (size_t)n2));
-    HIPCHK(c, H.basis.alloc((size_t)(2 * mk + 1) * (size_t)n2));
-    HIPCHK(c, H.part.alloc((size_t)(mk + 2) * (size_t)np + 3 * (size_t)np));
-    HIPCHK(c, H.dots.alloc((size_t)(mk + 4)));
-    double *x = x_dev, *r = H.vec.p, *t = r + n2;
-    double h[3] = {0, 0, 0};
-    auto spmv = [&](const double* in, double* out) {
-        hipLaunchKernelGGL(k_block_spmv<kBlockTeam>, dim3(g1(n, 256 / kBlockTeam)), dim3(256), 0, st, n, L0.rp, L0.ci, raw, in, out, (const int32_t*)nullptr);
+    if (int rc = amg_cols_prepare(c, H, Q)) return rc;
+    HIPCHK(c, H.basis.alloc((size_t)(2 * mk + 1) * nq));
+    HIPCHK(c, H.part.alloc((size_t)Q * ((size_t)(mk + 2) * (size_t)np + 3 * (size_t)np)));
+    HIPCHK(c, H.dots.alloc((size_t)Q * (size_t)(mk + 4)));
+    double h[kAmgColsMax];
+    auto spmv = [&](const double* in, double* out) {   // (one column: the block handle's own kernel)
+        if (Q == 1) {
+            hipLaunchKernelGGL(k_block_spmv<kBlockTeam>, dim3(g1(n, 256 / kBlockTeam)), dim3(256), 0, st, n, L0.rp, L0.ci, raw, in, out, (const int32_t*)nullptr);
+            return;
+        }
+        by_cols(Q, [&](auto q) {
+            constexpr int QC = decltype(q)::value;
+            if constexpr (QC > 1)
+                hipLaunchKernelGGL((k_block_spmv_cols<kBlockTeam, QC>), dim3(g1(n, 256 / kBlockTeam)), dim3(256), 0, st, n, L0.rp, L0.ci, raw, in, out);
+        });
     };
     auto dots = [&](const double* a0) -> int {
-        fixed_dots(st, n2, np, a0, a0, nullptr, nullptr, nullptr, nullptr, H.part.p, H.dots.p);
-        HIPCHK(c, hipMemcpyAsync(h, H.dots.p, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+        fixed_dots_cols(st, n2, np, Q, a0, a0, H.part.p, H.dots.p);
+        HIPCHK(c, hipMemcpyAsync(h, H.dots.p, sizeof(double) * (size_t)Q, hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));
         return FDAPDE_OK;
     };
-    if (!warm) HIPCHK(c, hipMemsetAsync(x, 0, sizeof(double) * (size_t)n2, st));
-    HIPCHK(c, hipMemcpyAsync(r, b_dev, sizeof(double) * (size_t)n2, hipMemcpyDeviceToDevice, st));
-    if (int rc = dots(r)) return rc;
-    const double bb = h[0];
-    double rr = bb;
-    int it = 0;
-    bool converged = !(bb > 0.0) && std::isfinite(bb), broke = !std::isfinite(bb);
-    if (warm && !converged && !broke) {   // (a column a batch handed back: the residual of its iterate starts the first cycle)
+    auto residual = [&](double* rr_out) -> int {   // the TRUE residuals of the iterates
         spmv(x, t);
-        hipLaunchKernelGGL(k_bamg_residual, dim3(gn(n2)), dim3(256), 0, st, n2, b_dev, t, r);
+        hipLaunchKernelGGL(k_bamg_residual, dim3(gn((int64_t)nq)), dim3(256), 0, st, (int64_t)nq, b, (const double*)t, r);
         if (int rc = dots(r)) return rc;
-        rr = h[0];
-        if (!std::isfinite(rr)) broke = true;
+        std::copy(h, h + Q, rr_out);
+        return FDAPDE_OK;
+    };
+    if (!warm) HIPCHK(c, hipMemsetAsync(x, 0, sizeof(double) * nq, st));
+    HIPCHK(c, hipMemcpyAsync(r, b, sizeof(double) * nq, hipMemcpyDeviceToDevice, st));
+    if (int rc = dots(r)) return rc;
+    bool live = false;   // a column that starts (0 < |b|^2 < inf), and is judged by its own residual at the end
+    for (int q = 0; q < Q; ++q) {
+        S.bb[q] = S.rr[q] = h[q], S.converged[q] = !(h[q] > 0.0) && std::isfinite(h[q]), S.broke[q] = !std::isfinite(h[q]);
+        live = live || (h[q] > 0.0 && std::isfinite(h[q]));
+    }
+    if (warm && live) {   // (a column a batch handed back: the residual of its iterate starts the first cycle)
+        if (int rc = residual(S.rr)) return rc;
+        for (int q = 0; q < Q; ++q)
+            if (!std::isfinite(S.rr[q])) S.broke[q] = true;
     }
     const bool one_level = H.lv.size() == 1;
     auto precond = [&](const double* v, double* z, double* w, bool&) -> int {
         if (one_level) {
-            if (int rc = amg_dense_cols(c, H, 1, v, z)) return rc;
-        } else if (int rc = amg_cycle(c, H, 0, 1, v, z))
+            if (int rc = amg_dense_cols(c, H, Q, v, z)) return rc;
+        } else if (int rc = amg_cycle(c, H, 0, Q, v, z))
             return rc;
         spmv(z, w);
         return FDAPDE_OK;
     };
-    auto residual = [&](double& rr_out) -> int {   // the TRUE residual of the iterate
-        spmv(x, t);
-        hipLaunchKernelGGL(k_bamg_residual, dim3(gn(n2)), dim3(256), 0, st, n2, b_dev, t, r);
-        if (int rc = dots(r)) return rc;
-        rr_out = h[0];
-        return FDAPDE_OK;
-    };
-    FgmresSpace fs{n2, mk, H.basis.p, H.basis.p + (size_t)(mk + 1) * (size_t)n2, H.part.p, H.dots.p, np};
-    if (!converged && !broke)
-        if (int rc = fgmres_outer(c, fs, x, r, nullptr, rtol, maxit, bb, precond, residual, rr, it, converged, broke)) return rc;
-    if (bb > 0.0 && std::isfinite(bb)) {   // what is handed out is judged by its own residual, whichever way the loop ended
+    FgmresSpace fs{n2, mk, H.basis.p, H.basis.p + (size_t)(mk + 1) * nq, H.part.p, H.dots.p, np};
+    if (int rc = fgmres_outer(c, fs, Q, x, r, nullptr, rtol, maxit, precond, residual, S)) return rc;
+    double rr[kAmgColsMax];
+    if (live)   // what is handed out is judged by its own residual, whichever way the loop ended
         if (int rc = residual(rr)) return rc;
-        converged = std::isfinite(rr) && rr <= rtol * rtol * bb;
+    for (int q = 0; q < Q; ++q) {
+        if (S.bb[q] > 0.0 && std::isfinite(S.bb[q])) S.rr[q] = rr[q], S.converged[q] = std::isfinite(rr[q]) && rr[q] <= rtol * rtol * S.bb[q];
+        rel[q] = S.bb[q] > 0.0 ? std::sqrt(S.rr[q] / S.bb[q]) : 0.0;
     }
     HIPCHK(c, hipGetLastError());
-    *iters = it, *relres = bb > 0.0 ? std::sqrt(rr / bb) : 0.0, *converged_out = converged, *broke_out = broke;
+    return FDAPDE_OK;
+}
+}   // namespace
+
+// one column: A x = b (both interleaved, internal order, on the device; x is written -- warm: x holds the iterate to start from)
+int block_amg_run(fdapde_ctx* c, BlockAmg* hp, const double* raw, const double* b_dev, double* x_dev, double rtol, int maxit, int* iters, double* relres,
+                  bool* converged_out, bool* broke_out, bool warm) {
+    const size_t n2 = 2 * (size_t)hp->lv[0]->n;
+    HIPCHK(c, hp->vec.alloc(2 * n2));
+    FgmresCols S{};
+    if (int rc = block_amg_cols(c, *hp, raw, 1, b_dev, x_dev, hp->vec.p, hp->vec.p + n2, warm, rtol, maxit, S, relres)) return rc;
+    *iters = S.it[0], *converged_out = S.converged[0], *broke_out = S.broke[0];
     return FDAPDE_OK;
 }
 
@@ -282,69 +303,26 @@ int block_amg_width(const fdapde_ctx* c, const BlockAmg* H, int32_t left, int ma
     return amg_cols_width(std::min<int32_t>(left, c->amg_cols), 2 * H->lv[0]->n, mk);
 }
 
-// Q columns side by side: ext (device) holds them stacked in the reference numbering, column q at ext + 2 n q, and receives the solutions.  Per column what
-// block_amg_run does, the outer iteration in lockstep (fgmres_outer_cols); a column handed back is finished by block_amg_run itself from its iterate (col_b,
-// col_x: one column of scratch each).  iters is added to, worst / not_conv / broke_any follow block_amg_solve's rules
+// Q columns side by side: ext (device) holds them stacked in the reference numbering, column q at ext + 2 n q, and receives the solutions.  One run of
+// block_amg_cols at width Q; a column handed back is finished by block_amg_run from its iterate (col_b, col_x: one column of scratch each).  iters is added to,
+// worst / not_conv / broke_any follow block_amg_solve's rules
 int block_amg_batch(fdapde_ctx* c, BlockAmg* hp, const double* raw, int Q, double* ext, double* col_b, double* col_x, double rtol, int maxit, int* iters, double* worst,
                     bool* not_conv, bool* broke_any) {
     BlockAmg& H = *hp;
     hipStream_t st = c->stream;
-    AmgLevel& L0 = *H.lv[0];
-    const int64_t n = L0.n, n2 = 2 * n;
+    const int64_t n = H.lv[0]->n, n2 = 2 * n;
     const size_t nq = (size_t)n2 * (size_t)Q;
-    const int np = (int)std::min<int64_t>(1024, std::max<int64_t>(1, (n2 + 4095) / 4096));
-    const int mk = block_restart_len(c, maxit);
-    if (int rc = amg_cols_prepare(c, H, Q)) return rc;
     HIPCHK(c, H.qvec.alloc(4 * nq));
-    HIPCHK(c, H.basis.alloc((size_t)(2 * mk + 1) * nq));
-    HIPCHK(c, H.part.alloc((size_t)Q * ((size_t)(mk + 2) * (size_t)np + 3 * (size_t)np)));
-    HIPCHK(c, H.dots.alloc((size_t)Q * (size_t)(mk + 4)));
     double *b = H.qvec.p, *x = b + nq, *r = x + nq, *t = r + nq;
     hipLaunchKernelGGL(k_block_stage_cols, dim3(gn(n * Q)), dim3(256), 0, st, n, Q, c->dof_i2e.p, (const double*)ext, b);
-    double h[kAmgColsMax];
-    auto spmv = [&](const double* in, double* out) {
-        by_cols(Q, [&](auto q) {
-            constexpr int QC = decltype(q)::value;
-            hipLaunchKernelGGL((k_block_spmv_cols<kBlockTeam, QC>), dim3(g1(n, 256 / kBlockTeam)), dim3(256), 0, st, n, L0.rp, L0.ci, raw, in, out);
-        });
-    };
-    auto dots = [&](const double* a0) -> int {
-        fixed_dots_cols(st, n2, np, Q, a0, a0, H.part.p, H.dots.p);
-        HIPCHK(c, hipMemcpyAsync(h, H.dots.p, sizeof(double) * (size_t)Q, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        return FDAPDE_OK;
-    };
-    HIPCHK(c, hipMemsetAsync(x, 0, sizeof(double) * nq, st));
-    HIPCHK(c, hipMemcpyAsync(r, b, sizeof(double) * nq, hipMemcpyDeviceToDevice, st));
-    if (int rc = dots(r)) return rc;
     FgmresCols S{};
-    for (int q = 0; q < Q; ++q) S.bb[q] = S.rr[q] = h[q], S.converged[q] = !(h[q] > 0.0) && std::isfinite(h[q]), S.broke[q] = !std::isfinite(h[q]);
-    const bool one_level = H.lv.size() == 1;
-    auto precond = [&](const double* v, double* z, double* w) -> int {
-        if (one_level) {
-            if (int rc = amg_dense_cols(c, H, Q, v, z)) return rc;
-        } else if (int rc = amg_cycle(c, H, 0, Q, v, z))
-            return rc;
-        spmv(z, w);
-        return FDAPDE_OK;
-    };
-    auto residual = [&](double* rr_out) -> int {   // the TRUE residuals of the iterates
-        spmv(x, t);
-        hipLaunchKernelGGL(k_bamg_residual, dim3(gn((int64_t)nq)), dim3(256), 0, st, (int64_t)nq, (const double*)b, (const double*)t, r);
-        if (int rc = dots(r)) return rc;
-        std::copy(h, h + Q, rr_out);
-        return FDAPDE_OK;
-    };
-    FgmresSpace fs{n2, mk, H.basis.p, H.basis.p + (size_t)(mk + 1) * nq, H.part.p, H.dots.p, np};
-    if (int rc = fgmres_outer_cols(c, fs, Q, x, r, rtol, maxit, precond, residual, S)) return rc;
-    double rr[kAmgColsMax];
-    if (int rc = residual(rr)) return rc;   // what is handed out is judged by its own residual, whichever way the loop ended
-    HIPCHK(c, hipGetLastError());
+    double rels[kAmgColsMax];
+    if (int rc = block_amg_cols(c, H, raw, Q, b, x, r, t, false, rtol, maxit, S, rels)) return rc;
     ++H.batches, H.batched_cols += Q;
     for (int q = 0; q < Q; ++q) {
         int it = S.it[q];
         bool conv = S.converged[q], broke = S.broke[q];
-        double rel = 0.0;
+        double rel = rels[q];
         if (S.handed[q]) {   // the recurrence and the true residual disagreed: the rest of this column by block_amg_run, from its iterate
             hipLaunchKernelGGL(k_amg_col_get, dim3(gn(n2)), dim3(256), 0, st, n2, Q, q, (const double*)b, col_b);
             hipLaunchKernelGGL(k_amg_col_get, dim3(gn(n2)), dim3(256), 0, st, n2, Q, q, (const double*)x, col_x);
@@ -352,11 +330,7 @@ int block_amg_batch(fdapde_ctx* c, BlockAmg* hp, const double* raw, int Q, doubl
             if (int rc = block_amg_run(c, hp, raw, col_b, col_x, rtol, maxit - it, &it1, &rel, &conv, &broke, true)) return rc;
             hipLaunchKernelGGL(k_amg_col_put, dim3(gn(n2)), dim3(256), 0, st, n2, Q, q, (const double*)col_x, x);
             it += it1, ++H.single_cols;
-        } else if (S.bb[q] > 0.0 && std::isfinite(S.bb[q])) {
-            conv = std::isfinite(rr[q]) && rr[q] <= rtol * rtol * S.bb[q];
-            rel = std::sqrt(rr[q] / S.bb[q]);
-        } else
-            rel = S.bb[q] > 0.0 ? std::sqrt(S.rr[q] / S.bb[q]) : 0.0;
+        }
         if (!conv) *not_conv = true, *broke_any = *broke_any || broke;
         *iters += it, *worst = rel > *worst || std::isnan(rel) ? rel : *worst;
     }

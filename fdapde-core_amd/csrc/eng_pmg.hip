@@ -163,35 +163,6 @@ __global__ void k_pmg_x(int64_t n, double alpha, const double* ph, double omega,
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;   // (dinv: ph, sh are D M^-1 p, D M^-1 s)
     if (i < n) x[i] += (alpha * ph[i] + (sh ? omega * sh[i] : 0.0)) * (dinv ? dinv[i] : 1.0);
 }
-// ---- flexible GMRES (the outer method): Gram-Schmidt against the basis V_0 .. V_{k-1} (vectors `stride` apart), twice per new vector ----
-// h_q = V_q . w for q < k, and w . w behind them: per-workgroup partials part[q * np + block] (fixed order: the same bits every run); eight basis vectors per
-// sweep over the workgroup's elements (w is read again per sweep: one extra vector per eight)
-__global__ __launch_bounds__(256) void k_pmg_mdot(int64_t n, const double* V, int64_t stride, int k, const double* w, double* part) {
-    __shared__ double red[9][4];
-    const int wv = threadIdx.x >> 6;
-    for (int c0 = 0; c0 < k || c0 == 0; c0 += 8) {
-        double sq[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sw = 0;
-        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-            const double wi = w[i];
-#pragma unroll
-            for (int q = 0; q < 8; ++q)
-                if (c0 + q < k) sq[q] += V[(int64_t)(c0 + q) * stride + i] * wi;
-            if (c0 == 0) sw += wi * wi;
-        }
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const double r = wave_sum(sq[q]);
-            if ((threadIdx.x & 63) == 0) red[q][wv] = r;
-        }
-        sw = wave_sum(sw);
-        if ((threadIdx.x & 63) == 0) red[8][wv] = sw;
-        __syncthreads();
-        if (threadIdx.x < 8 && c0 + (int)threadIdx.x < k)
-            part[(size_t)(c0 + threadIdx.x) * gridDim.x + blockIdx.x] = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
-        if (threadIdx.x == 8 && c0 == 0) part[(size_t)k * gridDim.x + blockIdx.x] = red[8][0] + red[8][1] + red[8][2] + red[8][3];
-        __syncthreads();
-    }
-}
 // out[q] = sum of part[q * np ..] for q < cnt: one workgroup per value
 __global__ __launch_bounds__(256) void k_pmg_mreduce(const double* part, int np, double* out) {
     __shared__ double red[5];
@@ -200,41 +171,10 @@ __global__ __launch_bounds__(256) void k_pmg_mreduce(const double* part, int np,
     s = block_sum(s, red);
     if (threadIdx.x == 0) out[blockIdx.x] = s;
 }
-// w -= sum_q h_q V_q, and the partials of what is left: |w|^2 to part[block]
-__global__ __launch_bounds__(256) void k_pmg_msub(int64_t n, const double* V, int64_t stride, int k, const double* h, double* w, double* part) {
-    __shared__ double hs[64];
-    __shared__ double red[4];
-    if ((int)threadIdx.x < k) hs[threadIdx.x] = h[threadIdx.x];
-    __syncthreads();
-    double sw = 0;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        double wi = w[i];
-        for (int q = 0; q < k; ++q) wi -= hs[q] * V[(int64_t)q * stride + i];
-        w[i] = wi, sw += wi * wi;
-    }
-    sw = wave_sum(sw);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sw;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
-__global__ void k_pmg_scale(int64_t n, const double* a, double f, double* out) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = f * a[i];
-}
-// x += (sum_q y_q Z_q) [* dinv: the Z_q are D M^-1 v_q]
-__global__ __launch_bounds__(256) void k_pmg_comb(int64_t n, const double* Z, int64_t stride, int k, const double* y, const double* dinv, double* x) {
-    __shared__ double ys[64];
-    if ((int)threadIdx.x < k) ys[threadIdx.x] = y[threadIdx.x];
-    __syncthreads();
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    double s = 0;
-    for (int q = 0; q < k; ++q) s += ys[q] * Z[(int64_t)q * stride + i];
-    x[i] += dinv ? s * dinv[i] : s;
-}
-// ---- the same kernels for Q interleaved columns (kernels_cols.h): Q independent Krylov spaces side by side, basis vector b at V + b * stride with
-// stride = n Q.  A column's sums run over the same elements in the same order as in the single-column kernel above it (the same grid, the same wave_sum,
-// the same four-wave sum, the same k_pmg_mreduce behind it): the column's bits are those of a single-column run.  Value (b, q) of a launch: part[(b Q + q) np ..]
+// ---- flexible GMRES (the outer method) for Q in {1, 2, 4, 8} interleaved columns (kernels_cols.h): Q independent Krylov spaces side by side, basis vector b at
+// V + b * stride with stride = n Q; Gram-Schmidt against V_0 .. V_{k-1}, twice per new vector.  A column's sums run over the same elements in the same order at
+// every Q (the same grid, the same wave_sum, the same four-wave sum, the same k_pmg_mreduce behind it -- per-workgroup partials in a fixed order: the same bits
+// every run): the column's bits are those of a one-column run.  Value (b, q) of a launch: part[(b Q + q) np ..]
 template <int Q> __global__ __launch_bounds__(256) void k_pmg_dots_cols(int64_t n, const double* a, const double* b, double* part) {
     __shared__ double red[Q][4];
     double s[Q];
@@ -254,9 +194,10 @@ template <int Q> __global__ __launch_bounds__(256) void k_pmg_dots_cols(int64_t 
     __syncthreads();
     if (threadIdx.x < Q) part[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
 }
-// h_(b,q) = V_b,q . w_q for b < k, and w_q . w_q behind them; 16 / Q basis vectors per sweep (sixteen accumulators)
-template <int Q> __global__ __launch_bounds__(256) void k_pmg_mdot_cols(int64_t n, const double* V, int64_t stride, int k, const double* w, double* part) {
-    constexpr int CB = 16 / Q;
+// h_(b,q) = V_b,q . w_q for b < k, and w_q . w_q behind them; CB basis vectors per sweep over the workgroup's elements (w is read again per sweep): sixteen
+// accumulators for Q >= 2, eight for one column (which basis vectors share a sweep changes no sum's order)
+template <int Q> __global__ __launch_bounds__(256) void k_pmg_mdot(int64_t n, const double* V, int64_t stride, int k, const double* w, double* part) {
+    constexpr int CB = Q == 1 ? 8 : 16 / Q;
     __shared__ double red[CB * Q + Q][4];
     const int wv = threadIdx.x >> 6;
     for (int c0 = 0; c0 < k || c0 == 0; c0 += CB) {
@@ -304,7 +245,7 @@ template <int Q> __global__ __launch_bounds__(256) void k_pmg_mdot_cols(int64_t 
     }
 }
 // w_q -= sum_b h_(b,q) V_b,q, and the partials of what is left: |w_q|^2 to part[q np + block]
-template <int Q> __global__ __launch_bounds__(256) void k_pmg_msub_cols(int64_t n, const double* V, int64_t stride, int k, const double* h, double* w, double* part) {
+template <int Q> __global__ __launch_bounds__(256) void k_pmg_msub(int64_t n, const double* V, int64_t stride, int k, const double* h, double* w, double* part) {
     __shared__ double hs[64 * Q];
     __shared__ double red[Q][4];
     for (int t = threadIdx.x; t < k * Q; t += 256) hs[t] = h[t];
@@ -335,7 +276,7 @@ template <int Q> __global__ __launch_bounds__(256) void k_pmg_msub_cols(int64_t 
 }
 // out_q = f_q a_q for the columns of the mask, 0 for the others: a column that does not run (a zero right-hand side, a frozen column, one that left the cycle) goes
 // through the batch's launches as zeros -- its slot of the basis is work space, and the cycle must not chew on whatever the allocation held
-template <int Q> __global__ void k_pmg_scale_cols(int64_t n, const double* a, ColScal f, double* out) {
+template <int Q> __global__ void k_pmg_scale(int64_t n, const double* a, ColScal f, double* out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     double v[Q];
@@ -344,8 +285,9 @@ template <int Q> __global__ void k_pmg_scale_cols(int64_t n, const double* a, Co
     for (int q = 0; q < Q; ++q) v[q] = ((f.mask >> q) & 1u) ? f.f[q] * v[q] : 0.0;
     st_cols<Q>(out + i * Q, v);
 }
-// x_q += sum_b y_(b,q) Z_b,q for the columns of the mask: nothing writes to a column outside it
-template <int Q> __global__ __launch_bounds__(256) void k_pmg_comb_cols(int64_t n, const double* Z, int64_t stride, int k, const double* y, unsigned mask, double* x) {
+// x_q += (sum_b y_(b,q) Z_b,q) [* dinv, one value per row for all columns: the Z are D M^-1 v] for the columns of the mask: nothing writes to a column outside it
+template <int Q>
+__global__ __launch_bounds__(256) void k_pmg_comb(int64_t n, const double* Z, int64_t stride, int k, const double* y, const double* dinv, unsigned mask, double* x) {
     __shared__ double ys[64 * Q];
     for (int t = threadIdx.x; t < k * Q; t += 256) ys[t] = y[t];
     __syncthreads();
@@ -362,7 +304,7 @@ template <int Q> __global__ __launch_bounds__(256) void k_pmg_comb_cols(int64_t 
     }
 #pragma unroll
     for (int q = 0; q < Q; ++q)
-        if ((mask >> q) & 1u) x[i * Q + q] += s[q];
+        if ((mask >> q) & 1u) x[i * Q + q] += dinv ? s[q] * dinv[i] : s[q];
 }
 // a coefficient field of the fine level -- nq2 samples per cell at the order-2 rule's nodes, `width` values each -- for the coarse level: every cell's
 // weighted mean at each of the nq1 nodes of the P1 rule (a preconditioner needs the coarse OPERATOR only approximately)
@@ -385,108 +327,6 @@ void fixed_dots(hipStream_t st, int64_t n, int np, const double* a0, const doubl
     hipLaunchKernelGGL(k_pmg_reduce, dim3(1), dim3(256), 0, st, part, np, out);
 }
 
-// ---- the outer method, FLEXIBLE GMRES (right-preconditioned: A Z_k = V_{k+1} H_k with Z_j = M^-1 v_j kept, so M^-1 may be a different operator every time it
-// is applied).  One preconditioner application per iteration -- precond(v_j, z_j, w, stop) leaves z_j and w = A z_j (stop: no further iteration makes sense) --,
-// the residual norm from the Givens recurrence; the residual of the iterate computed at every restart by residual(rr) (r = rhs - A x, rr = r.r: the recurrence's
-// word is not taken for convergence).  Gram-Schmidt twice per vector (the Krylov basis of a solve to 1e-10 is ill-conditioned by then); restart after s.mk vectors.
-// On entry r holds the residual of x and rr its square; x += Z y [* comb_dinv] per cycle.  Shared by the two-level solver and FDAPDE_SOLVER_AMG (eng_amg.hip).
-int fgmres_outer(fdapde_ctx* c, const FgmresSpace& s, double* x, double* r, const double* comb_dinv, double rtol, int maxit, double bb,
-                 const std::function<int(const double*, double*, double*, bool&)>& precond, const std::function<int(double&)>& residual, double& rr, int& it,
-                 bool& converged, bool& broke) {
-    hipStream_t st = c->stream;
-    const int64_t n2 = s.n;
-    const int mk = s.mk;
-    const dim3 gv(g1n(n2)), bv(256);
-    double* V = s.V;
-    double* Z = s.Z;
-    std::vector<double> H((size_t)(mk + 1) * mk, 0.0), cs((size_t)mk), sn((size_t)mk), gg((size_t)mk + 1), hj((size_t)mk + 4), yy((size_t)mk);
-    auto Hat = [&](int i, int j) -> double& { return H[(size_t)j * (mk + 1) + i]; };
-    const unsigned gnp = (unsigned)s.np;
-    while (!converged && !broke && it < maxit) {
-        // (r holds the residual of x, rr its square)
-        const double beta = std::sqrt(rr);
-        if (!(beta > 0.0) || !std::isfinite(beta)) {
-            broke = !std::isfinite(beta);
-            converged = !broke;
-            break;
-        }
-        hipLaunchKernelGGL(k_pmg_scale, gv, bv, 0, st, n2, r, 1.0 / beta, V);
-        std::fill(gg.begin(), gg.end(), 0.0);
-        gg[0] = beta;
-        int k = 0;   // columns of this cycle
-        bool cycle_done = false;
-        while (!cycle_done && k < mk && it < maxit) {
-            const int j = k;
-            double* zj = Z + (size_t)j * (size_t)n2;
-            double* w = V + (size_t)(j + 1) * (size_t)n2;
-            const double* vj = V + (size_t)j * (size_t)n2;
-            bool stop = false;
-            if (int rc = precond(vj, zj, w, stop)) return rc;
-            if (stop) {
-                broke = true;
-                break;
-            }
-            // Gram-Schmidt, twice: h = V^T w, w -= V h, then the same on what is left (its coefficients add to h)
-            double wnorm2 = 0;
-            for (int pass = 0; pass < 2; ++pass) {
-                hipLaunchKernelGGL(k_pmg_mdot, dim3(gnp), bv, 0, st, n2, V, n2, j + 1, w, s.part);
-                hipLaunchKernelGGL(k_pmg_mreduce, dim3((unsigned)(j + 2)), bv, 0, st, s.part, s.np, s.dots);
-                hipLaunchKernelGGL(k_pmg_msub, dim3(gnp), bv, 0, st, n2, V, n2, j + 1, s.dots, w, s.part);
-                hipLaunchKernelGGL(k_pmg_mreduce, dim3(1), bv, 0, st, s.part, s.np, s.dots + (j + 2));
-                HIPCHK(c, hipMemcpyAsync(hj.data(), s.dots, sizeof(double) * (size_t)(j + 3), hipMemcpyDeviceToHost, st));
-                HIPCHK(c, hipStreamSynchronize(st));
-                for (int i = 0; i <= j; ++i) Hat(i, j) = pass == 0 ? hj[(size_t)i] : Hat(i, j) + hj[(size_t)i];
-                wnorm2 = hj[(size_t)j + 2];
-            }
-            const double hn = std::sqrt(wnorm2);
-            if (!std::isfinite(hn)) {
-                broke = true;
-                break;
-            }
-            Hat(j + 1, j) = hn;
-            for (int i = 0; i < j; ++i) {
-                const double a0 = Hat(i, j), a1 = Hat(i + 1, j);
-                Hat(i, j) = cs[(size_t)i] * a0 + sn[(size_t)i] * a1, Hat(i + 1, j) = -sn[(size_t)i] * a0 + cs[(size_t)i] * a1;
-            }
-            const double d = std::hypot(Hat(j, j), Hat(j + 1, j));
-            if (!(d > 0.0)) {   // (a zero column: M^-1 v_j = 0 -- nothing this basis can do)
-                broke = true;
-                break;
-            }
-            cs[(size_t)j] = Hat(j, j) / d, sn[(size_t)j] = Hat(j + 1, j) / d;
-            Hat(j, j) = d, Hat(j + 1, j) = 0.0;
-            gg[(size_t)j + 1] = -sn[(size_t)j] * gg[(size_t)j], gg[(size_t)j] = cs[(size_t)j] * gg[(size_t)j];
-            ++k, ++it;
-            rr = gg[(size_t)k] * gg[(size_t)k];
-            if (rr <= rtol * rtol * bb || !(hn > 1e-300)) cycle_done = true;   // (hn = 0: the exact solution lies in this basis)
-            else hipLaunchKernelGGL(k_pmg_scale, gv, bv, 0, st, n2, w, 1.0 / hn, w);
-        }
-        if (k > 0) {   // x += Z y, H y = g (upper triangular after the rotations)
-            for (int i = k - 1; i >= 0; --i) {
-                double sacc = gg[(size_t)i];
-                for (int q = i + 1; q < k; ++q) sacc -= Hat(i, q) * yy[(size_t)q];
-                yy[(size_t)i] = sacc / Hat(i, i);
-            }
-            HIPCHK(c, hipMemcpyAsync(s.dots, yy.data(), sizeof(double) * (size_t)k, hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(k_pmg_comb, gv, bv, 0, st, n2, Z, n2, k, s.dots, comb_dinv, x);
-            HIPCHK(c, hipStreamSynchronize(st));   // (yy is the host's)
-        }
-        if (broke) break;
-        // the residual of the new iterate, computed (it starts the next cycle, and the recurrence's word is not taken for convergence)
-        if (int rc = residual(rr)) return rc;
-        if (!std::isfinite(rr)) {
-            broke = true;
-            break;
-        }
-        converged = rr <= rtol * rtol * bb;
-        if (!converged && k == 0) {
-            broke = true;
-            break;
-        }
-    }
-    return FDAPDE_OK;
-}
-
 // a_q . b_q of Q interleaved columns into out[0 .. Q-1] (device): per column the sums of fixed_dots' first product
 void fixed_dots_cols(hipStream_t st, int64_t n, int np, int Q, const double* a, const double* b, double* part, double* out) {
     by_cols(Q, [&](auto qq) {
@@ -496,17 +336,22 @@ void fixed_dots_cols(hipStream_t st, int64_t n, int np, int Q, const double* a, 
     hipLaunchKernelGGL(k_pmg_mreduce, dim3((unsigned)Q), dim3(256), 0, st, part, np, out);
 }
 
-// ---- fgmres_outer for Q columns side by side (the multilevel handles' batches: eng_amg.hip, eng_block_amg.hip).  Q INDEPENDENT Krylov spaces -- not a block
-// method --, vectors interleaved (kernels_cols.h), s.n words per column, basis vectors s.n Q apart; the host keeps a Hessenberg matrix and the rotations per
-// column.  The columns run in lockstep and share the cycle position: one preconditioner launch sequence, one read-back per Gram-Schmidt pass for all of them.
-// What happens to a column is what fgmres_outer does to it -- the same kernels' sums in the same order, the same host arithmetic -- so its iterate is the
-// single-column run's, bit for bit.  A column whose recurrence says "converged" (or whose new vector vanished) gets its x update and its true residual at
-// once; if that agrees the column is FROZEN (nothing writes to it any more), if not it is handed back (S.handed): fgmres_outer would restart that column alone,
-// and so does the caller, on the single-column path from the column's iterate.  A restart at s.mk vectors and maxit end all columns still running at once.
+// ---- the outer method, FLEXIBLE GMRES (right-preconditioned: A Z_k = V_{k+1} H_k with Z_j = M^-1 v_j kept, so M^-1 may be a different operator every time it
+// is applied), for Q columns side by side: the two-level solver and the multilevel solvers' single columns at Q = 1, the multilevel handles' batches (eng_amg.hip,
+// eng_block_amg.hip) at Q = 2, 4, 8.  Q INDEPENDENT Krylov spaces -- not a block method --, vectors interleaved (kernels_cols.h), s.n words per column, basis
+// vectors s.n Q apart; the host keeps a Hessenberg matrix and the rotations per column.  The columns run in lockstep and share the cycle position: one
+// preconditioner application per iteration, one read-back per Gram-Schmidt pass for all of them (Gram-Schmidt twice per vector: the Krylov basis of a solve to
+// 1e-10 is ill-conditioned by then).  What happens to a column does not depend on Q -- the same kernels' sums in the same order, the same host arithmetic -- so
+// its iterate is the one-column run's, bit for bit.  The residual norm comes from the Givens recurrence, but the recurrence's word is not taken for convergence:
+// a column whose recurrence says "converged" (or whose new vector vanished) gets its x update and its true residual at once.  If that agrees the column is
+// FROZEN (nothing writes to it any more).  If not, the column wants a cycle of its own, out of step with the others: at Q = 1 there are no others, it stays
+// live and the next cycle starts in the loop (S.handed is never set); at Q > 1 it is handed back (S.handed) and the caller runs that restart at Q = 1 from the
+// column's iterate.  A restart at s.mk vectors and maxit end all columns still running at once.
 // On entry r holds the residuals, S.rr their squares, S.bb the squared norms the stop rule is relative to, S.converged / S.broke the columns that do not
-// start; precond(v, z, w) leaves z = M^-1 v and w = A z for all Q columns, residual(rr) r = rhs - A x and its squared norms.
-int fgmres_outer_cols(fdapde_ctx* c, const FgmresSpace& s, int Q, double* x, double* r, double rtol, int maxit,
-                      const std::function<int(const double*, double*, double*)>& precond, const std::function<int(double*)>& residual, FgmresCols& S) {
+// start; precond(v, z, w, stop) leaves z = M^-1 v and w = A z for all Q columns (stop: no further iteration makes sense -- every column still in the cycle
+// breaks and leaves with the vectors it had), residual(rr) r = rhs - A x and its squared norms; x += Z y [* comb_dinv, one value per row] per column and cycle.
+int fgmres_outer(fdapde_ctx* c, const FgmresSpace& s, int Q, double* x, double* r, const double* comb_dinv, double rtol, int maxit,
+                 const std::function<int(const double*, double*, double*, bool&)>& precond, const std::function<int(double*)>& residual, FgmresCols& S) {
     hipStream_t st = c->stream;
     const int64_t n = s.n, nq = s.n * Q;
     const int mk = s.mk;
@@ -531,7 +376,7 @@ int fgmres_outer_cols(fdapde_ctx* c, const FgmresSpace& s, int Q, double* x, dou
     auto scale = [&](const double* a, const ColScal& f, double* out) {
         by_cols(Q, [&](auto qq) {
             constexpr int QC = decltype(qq)::value;
-            hipLaunchKernelGGL(k_pmg_scale_cols<QC>, gv, bv, 0, st, n, a, f, out);
+            hipLaunchKernelGGL(k_pmg_scale<QC>, gv, bv, 0, st, n, a, f, out);
         });
     };
     // x += Z y for the columns of mask, every one from its own triangular system of k columns
@@ -551,7 +396,7 @@ int fgmres_outer_cols(fdapde_ctx* c, const FgmresSpace& s, int Q, double* x, dou
         HIPCHK(c, hipMemcpyAsync(s.dots, ybuf.data(), sizeof(double) * (size_t)k * Q, hipMemcpyHostToDevice, st));
         by_cols(Q, [&](auto qq) {
             constexpr int QC = decltype(qq)::value;
-            hipLaunchKernelGGL(k_pmg_comb_cols<QC>, gv, bv, 0, st, n, Z, nq, k, s.dots, mask, x);
+            hipLaunchKernelGGL(k_pmg_comb<QC>, gv, bv, 0, st, n, Z, nq, k, s.dots, comb_dinv, mask, x);
         });
         HIPCHK(c, hipStreamSynchronize(st));   // (ybuf is the host's)
         return FDAPDE_OK;
@@ -581,13 +426,21 @@ int fgmres_outer_cols(fdapde_ctx* c, const FgmresSpace& s, int Q, double* x, dou
             double* zj = Z + (size_t)j * (size_t)nq;
             double* w = V + (size_t)(j + 1) * (size_t)nq;
             const double* vj = V + (size_t)j * (size_t)nq;
-            if (int rc = precond(vj, zj, w)) return rc;
+            bool stop = false;
+            if (int rc = precond(vj, zj, w, stop)) return rc;
+            if (stop) {
+                if (int rc = comb(cyc, k)) return rc;
+                for (int q = 0; q < Q; ++q)
+                    if ((cyc >> q) & 1u) S.broke[q] = true, S.it[q] = it;
+                live &= ~cyc, cyc = 0;
+                break;
+            }
             for (int pass = 0; pass < 2; ++pass) {   // Gram-Schmidt, twice; ONE read-back per pass for all columns
                 by_cols(Q, [&](auto qq) {
                     constexpr int QC = decltype(qq)::value;
-                    hipLaunchKernelGGL(k_pmg_mdot_cols<QC>, dim3(gnp), bv, 0, st, n, V, nq, j + 1, w, s.part);
+                    hipLaunchKernelGGL(k_pmg_mdot<QC>, dim3(gnp), bv, 0, st, n, V, nq, j + 1, w, s.part);
                     hipLaunchKernelGGL(k_pmg_mreduce, dim3((unsigned)((j + 2) * Q)), bv, 0, st, s.part, s.np, s.dots);
-                    hipLaunchKernelGGL(k_pmg_msub_cols<QC>, dim3(gnp), bv, 0, st, n, V, nq, j + 1, s.dots, w, s.part);
+                    hipLaunchKernelGGL(k_pmg_msub<QC>, dim3(gnp), bv, 0, st, n, V, nq, j + 1, s.dots, w, s.part);
                     hipLaunchKernelGGL(k_pmg_mreduce, dim3((unsigned)Q), bv, 0, st, s.part, s.np, s.dots + (size_t)(j + 2) * Q);
                 });
                 HIPCHK(c, hipMemcpyAsync(hj.data(), s.dots, sizeof(double) * (size_t)(j + 3) * Q, hipMemcpyDeviceToHost, st));
@@ -633,7 +486,7 @@ int fgmres_outer_cols(fdapde_ctx* c, const FgmresSpace& s, int Q, double* x, dou
                 live &= ~brk, cyc &= ~brk;
             }
             ++k, ++it;
-            scale(w, fw, w);   // (the next basis vector; zeros in the columns that have just left the cycle)
+            if (fw.mask) scale(w, fw, w);   // (the next basis vector of the columns that go on, zeros in those that have just left; nobody goes on: the slot is not read)
             if (done) {   // the recurrence's word is not taken for convergence: the column's x update and its true residual, as at the end of a cycle
                 if (int rc = comb(done, k)) return rc;
                 if (int rc = residual(rrv.data())) return rc;
@@ -642,9 +495,13 @@ int fgmres_outer_cols(fdapde_ctx* c, const FgmresSpace& s, int Q, double* x, dou
                     S.rr[q] = rrv[(size_t)q], S.it[q] = it;
                     if (!std::isfinite(S.rr[q])) S.broke[q] = true;
                     else if (S.rr[q] <= tol2 * S.bb[q]) S.converged[q] = true;
-                    else if (it < maxit) S.handed[q] = true;   // (fgmres_outer would restart this column alone: the single-column path does)
+                    else if (it < maxit) {   // the column restarts alone: in place at Q = 1, by the caller above
+                        if (Q == 1) continue;
+                        S.handed[q] = true;
+                    }
+                    live &= ~(1u << q);
                 }
-                live &= ~done, cyc &= ~done;
+                cyc &= ~done;
             }
         }
         if (cyc) {   // a restart after mk vectors, or maxit: all the columns still in the cycle at once
@@ -1124,7 +981,7 @@ int pmg_run(fdapde_ctx* c, const double* A, const double* f_dev, const double* g
                     lam = std::sqrt(h[1] / h[0]);
                     if (std::getenv("FDAPDE_DEBUG_PMG_POWER")) std::fprintf(stderr, "pmg: power iteration %d: %.4f\n", pi, lam);
                     if (!(h[1] > 0.0)) break;
-                    hipLaunchKernelGGL(k_pmg_scale, gv, bv, 0, st, n2, rb, 1.0 / std::sqrt(h[1]), tb);
+                    hipLaunchKernelGGL(k_pmg_scale<1>, gv, bv, 0, st, n2, rb, ColScal{{1.0 / std::sqrt(h[1])}, 1u}, tb);
                 }
                 m.omega = lam > 0.0 && std::isfinite(lam) ? 1.5 / lam : 0.0;
                 m.omega_A = A, m.omega_key = coarse_key, m.omega_bnd = fv, m.omega_extra = extra_reaction;
@@ -1159,14 +1016,17 @@ int pmg_run(fdapde_ctx* c, const double* A, const double* f_dev, const double* g
             }
             return FDAPDE_OK;
         };
-        auto residual = [&](double& rr_out) -> int {
+        auto residual = [&](double* rr_out) -> int {
             apply_K(x, v);
             hipLaunchKernelGGL(k_pmg_residual, gv, bv, 0, st, n2, c->bnd.p, use_bnd, f_dev, g_dev, v, r);
             if (int rc = dots(r, r, nullptr, nullptr, nullptr, nullptr)) return rc;
-            rr_out = h[0];
+            rr_out[0] = h[0];
             return FDAPDE_OK;
         };
-        if (int rc = fgmres_outer(c, fs, x, r, comb_dinv, rtol, maxit, bb, precond, residual, rr, it, converged, broke)) return rc;
+        FgmresCols S{};
+        S.rr[0] = rr, S.bb[0] = bb, S.converged[0] = converged;
+        if (int rc = fgmres_outer(c, fs, 1, x, r, comb_dinv, rtol, maxit, precond, residual, S)) return rc;
+        rr = S.rr[0], it = S.it[0], converged = S.converged[0], broke = S.broke[0];
     } else
     while (!converged && it < maxit) {
         if (int rc = dots(r0, r, nullptr, nullptr, nullptr, nullptr)) return rc;
@@ -1236,7 +1096,7 @@ int pmg_run(fdapde_ctx* c, const double* A, const double* f_dev, const double* g
                      fine_apps, coarse_calls, coarse_iters, coarse_multi, true_rel, c->info.t_solve_ms);
     c->pmg.last_coarse_iters = coarse_iters, c->pmg.last_coarse_calls = coarse_calls;
     if (!converged) {
-        c->err = coarse_fail >= 4 ? "FDAPDE_SOLVER_PMG: the coarse level's solves do not converge" : broke ? "FDAPDE_SOLVER_PMG: BiCGStab broke down" : "maxit reached";
+        c->err = coarse_fail >= 4 ? "FDAPDE_SOLVER_PMG: the coarse level's solves do not converge" : broke ? (fgmres && mk > 0 ? "FDAPDE_SOLVER_PMG: the flexible GMRES broke down" : "FDAPDE_SOLVER_PMG: BiCGStab broke down") : "maxit reached";
         return FDAPDE_ENOCONV;
     }
     return FDAPDE_OK;

@@ -165,28 +165,26 @@ void pmg_release(fdapde_ctx* c);
 int e_solve_pmg(fdapde_ctx* c, const fdapde_options* opt, fdapde_info* info);
 int pmg_run(fdapde_ctx* c, const double* A, const double* f_dev, const double* g_dev, int use_bnd, const double* x0_dev, double extra_reaction, int64_t coarse_key,
             double rtol, int maxit);
-// the flexible GMRES outer loop (eng_pmg.hip) and its basis: V_0 .. V_mk, Z_0 .. Z_{mk-1} (n apart), part >= (mk + 2) * np, dots >= mk + 4 doubles
+// the flexible GMRES outer loop (eng_pmg.hip) for Q in {1, 2, 4, 8} columns in lockstep and its basis: interleaved vectors (kernels_cols.h), n words per
+// column, V_0 .. V_mk, Z_0 .. Z_{mk-1} (n Q apart), part >= (mk + 2) Q np, dots >= (mk + 4) Q doubles
 struct FgmresSpace {
     int64_t n;
     int mk;
     double *V, *Z, *part, *dots;
     int np;
 };
-int fgmres_outer(fdapde_ctx* c, const FgmresSpace& s, double* x, double* r, const double* comb_dinv, double rtol, int maxit, double bb,
-                 const std::function<int(const double*, double*, double*, bool&)>& precond, const std::function<int(double&)>& residual, double& rr, int& it,
-                 bool& converged, bool& broke);
-void fixed_dots(hipStream_t st, int64_t n, int np, const double* a0, const double* b0, const double* a1, const double* b1, const double* a2, const double* b2,
-                double* part, double* out);
-// the same loop for Q <= 8 columns in lockstep (interleaved vectors: kernels_cols.h; s.n words per column, basis vectors s.n Q apart, part >= (mk + 2) Q np,
-// dots >= (mk + 4) Q).  Per column: in rr / bb / converged / broke, out also it and handed (the recurrence said "converged", the true residual did not: the
-// caller finishes that column on the single-column path from its iterate)
+// per column: in rr / bb / converged / broke, out also it and handed (Q > 1 only -- the recurrence said "converged", the true residual did not: the caller
+// finishes that column at Q = 1 from its iterate; a single column restarts inside the loop)
 struct FgmresCols {
     double rr[8], bb[8];
     int it[8];
     bool converged[8], broke[8], handed[8];
 };
-int fgmres_outer_cols(fdapde_ctx* c, const FgmresSpace& s, int Q, double* x, double* r, double rtol, int maxit,
-                      const std::function<int(const double*, double*, double*)>& precond, const std::function<int(double*)>& residual, FgmresCols& S);
+int fgmres_outer(fdapde_ctx* c, const FgmresSpace& s, int Q, double* x, double* r, const double* comb_dinv, double rtol, int maxit,
+                 const std::function<int(const double*, double*, double*, bool&)>& precond, const std::function<int(double*)>& residual, FgmresCols& S);
+// three dot products of single vectors (the BiCGStab outer method, the power iterations), and one per column of Q interleaved columns: the bits of the first
+void fixed_dots(hipStream_t st, int64_t n, int np, const double* a0, const double* b0, const double* a1, const double* b1, const double* a2, const double* b2,
+                double* part, double* out);
 void fixed_dots_cols(hipStream_t st, int64_t n, int np, int Q, const double* a, const double* b, double* part, double* out);
 // eng_amg.hip: FDAPDE_SOLVER_AMG
 bool amg_eligible(const fdapde_ctx* c);

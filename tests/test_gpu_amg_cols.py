@@ -1,5 +1,5 @@
 """The columns of fdapde_lin_solve under FDAPDE_SOLVER_AMG side by side (knob `amg_cols`; csrc/eng_amg.hip: the cycle kernels at Q = 2, 4, 8 columns, amg_cycle; csrc/eng_pmg.hip:
-fgmres_outer_cols), against the column-by-column path (`amg_cols` = 1: the same kernels at Q = 1) on the same hierarchy.
+fgmres_outer at that width), against the column-by-column path (`amg_cols` = 1: the same kernels at Q = 1) on the same hierarchy.
 
 With the hierarchy fixed the k-th iterate of a column is ONE vector, and every cycle kernel orders a column's sums in the same way at every width: a batch
 must hand out the column-by-column run's BITS -- np.array_equal per column at `rtol = 1e-30, maxit = k` (k = 1, 2, 5) and at convergence.  Right-hand sides of

@@ -1,5 +1,5 @@
 """The columns of fdapde_block_solve under FDAPDE_SOLVER_BLOCK_AMG side by side (knob `amg_cols`; the k_bamg_* kernels at Q = 2, 4, 8 columns and k_block_spmv_cols of
-csrc/kernels_block.h, block_amg_batch of csrc/eng_block_amg.hip, fgmres_outer_cols of csrc/eng_pmg.hip), against the column-by-column path (`amg_cols` = 1) on
+csrc/kernels_block.h, block_amg_batch of csrc/eng_block_amg.hip, fgmres_outer of csrc/eng_pmg.hip at that width), against the column-by-column path (`amg_cols` = 1) on
 the same hierarchy: np.array_equal per column at the k-th iterate (`rtol = 1e-30, maxit = k`, k = 1, 2, 5) and at convergence.
 
 Cases a, d, e, g, h of block_iter_ref.AMG_CASES, blocks built as tests/test_gpu_block_iterates.py builds them: both lane widths, absorption (e), a correction that

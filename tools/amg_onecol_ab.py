@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Bit identity of the multilevel solvers between two builds of the library: the single-column path as the one-column instantiation of the column kernels
-(csrc/eng_amg.hip, csrc/kernels_block.h) against the parent commit's hand-written single-column kernels.  -> section 1 of profiles/amg_onecol_ab.txt
+"""Bit identity of the multilevel and two-level solvers between two builds of the library: the single-column path as the one-column instantiation of the column
+kernels (csrc/eng_amg.hip, csrc/kernels_block.h) and of the flexible GMRES (fgmres_outer, csrc/eng_pmg.hip) against a parent commit's hand-written single-column
+forms.  -> section 1 of profiles/amg_onecol_ab.txt and of profiles/fgmres_onecol_ab.txt
 
     FDAPDE_HIP_LIB=tools/bin/variants/libfdapde_hip_parent.so python tools/amg_onecol_ab.py run parent.npz      (one process per library)
     python tools/amg_onecol_ab.py run new.npz
@@ -16,7 +17,14 @@ first with np.array_equal and ends with "<k> arrays differ".
   handle_dense  ... on unit_square(12): 169 DOFs, the hierarchy is the dense level alone
   block         fdapde_block_solve, FDAPDE_SOLVER_BLOCK_AMG: the smoothing system of unit_square(32), lambda 1e-4, 11 columns at amg_cols 1 and 8
   parabolic     fdapde_solve_parabolic stepping with FDAPDE_SOLVER_AMG: unit_square(48) P1, 12 steps with Dirichlet data
-amg_setup_check 1 and amg_coarse_rows 256 throughout, as the tests: every hierarchy but handle_dense's has three levels."""
+  pmg.*         fdapde_solve, FDAPDE_SOLVER_PMG: unit_cube(9) P2, C5's operator with Dirichlet data -- at the default knobs, pmg_restart 5 (restarts),
+                pmg_smooth 0 (the additive form), pmg_blocked 0 and 1, and pmg_smooth 0 with pmg_blocked 0 (the x update without dinv)
+  pmg_indefinite, pmg_budget12   ... by name where the coarse level does not help (tests/test_gpu_pmg.py): -Lap - 300 on unit_cube(8), FDAPDE_ENOCONV at maxit; -Lap +
+                b.grad + 1 on unit_square(60) with pmg_inner_maxit 12
+  pmg_stop, pmg_stop2d   ... -Lap - 300 on unit_cube(8) with pmg_inner_maxit 3 and on unit_square(60): four coarse solves in a row get nowhere, the preconditioner raises
+                `stop`, the iterate keeps the vectors of the cycle so far -- FDAPDE_ENOCONV, "the coarse level's solves do not converge"
+  pmg_parabolic fdapde_solve_parabolic stepping with FDAPDE_SOLVER_PMG: unit_square(20) P2, 6 steps with Dirichlet data (warm starts)
+amg_setup_check 1 and amg_coarse_rows 256 throughout the multilevel cases, as the tests: every hierarchy but handle_dense's has three levels."""
 import os
 import sys
 
@@ -114,11 +122,74 @@ def parabolic_case(capi, meshgen, out):
     c.close()
 
 
+def record_pmg(out, name, info, x):
+    out[name + ".counts"] = np.array([info.iters, info.converged, info.method_used], dtype=np.int64)
+    out[name + ".relres"] = np.array([info.relres])
+    out[name + ".x"] = np.asarray(x)
+    print(f"{name:<22} iterations {info.iters} converged {info.converged} method {info.method_used} relres {info.relres:.3e}", flush=True)
+
+
+def pmg_context(capi, meshgen, dim, nx, op, zero=False, **knobs):
+    nodes, cells, bnd = meshgen.unit_square(nx) if dim == 2 else meshgen.unit_cube(nx)
+    c = capi.Context(0)
+    c.mesh_upload(nodes, cells, bnd)
+    nd = c.dofs_build(2)
+    c.tune("pmg_setup_check", 1)
+    coords = c.dofs_get()[2]
+    c.set_operator(op)
+    qn = c.quadrature_nodes()
+    c.set_forcing(1.0 + np.sin(3.0 * qn[:, 0]) * qn[:, 1])
+    c.set_dirichlet(np.zeros(coords.shape[0]) if zero else 0.3 * np.cos(2.0 * coords[:, 0]) + coords[:, -1])
+    c.init()
+    for k, v in knobs.items():
+        c.tune(k, v)
+    return c
+
+
+def pmg_cases(capi, meshgen, workloads, out):
+    arms = (("default", {}), ("restart5", {"pmg_restart": 5}), ("smooth0", {"pmg_smooth": 0}), ("blocked0", {"pmg_blocked": 0}), ("blocked1", {"pmg_blocked": 1}),
+            ("smooth0_blocked0", {"pmg_smooth": 0, "pmg_blocked": 0}))
+    for arm, knobs in arms:   # (a context per arm: no knob of one arm reaches the next)
+        c = pmg_context(capi, meshgen, 3, 9, workloads.c5_operator(capi), **knobs)
+        info = c.solve(method=capi.SOLVER_PMG, rtol=1e-11, raise_on_noconv=False)
+        record_pmg(out, f"pmg.{arm}", info, c.solution())
+        c.close()
+    # where the coarse level does not help (tests/test_gpu_pmg.py: the indefinite operator by name, a coarse budget of 12): pmg_indefinite ends at maxit, pmg_budget12
+    # converges; pmg_stop and pmg_stop2d end with "the coarse level's solves do not converge" after 11 and 24 iterations -- the preconditioner raised `stop`
+    adr, indef = -capi.laplacian() + capi.advection([2.0, 1.0]) + capi.reaction(1.0), -capi.laplacian() + capi.reaction(-300.0)
+    for name, args, kw, maxit in (("pmg_indefinite", (3, 8, indef), {}, 400), ("pmg_budget12", (2, 60, adr), {"zero": True, "pmg_inner_maxit": 12}, 300),
+                                  ("pmg_stop", (3, 8, indef), {"pmg_inner_maxit": 3}, 100), ("pmg_stop2d", (2, 60, indef), {}, 100)):
+        c = pmg_context(capi, meshgen, *args, **kw)
+        info = c.solve(method=capi.SOLVER_PMG, rtol=1e-10 if "zero" in kw else 1e-11, maxit=maxit, raise_on_noconv=False)
+        record_pmg(out, name, info, c.solution())
+        print(f"{'':<22} status text: {c.lib.fdapde_last_error(c._ctx).decode()}", flush=True)
+        c.close()
+
+
+def pmg_parabolic_case(capi, meshgen, out):
+    nodes, cells, bnd = meshgen.unit_square(20)
+    c = capi.Context(0)
+    c.mesh_upload(nodes, cells, bnd)
+    c.dofs_build(2)
+    coords = c.dofs_get()[2]
+    qn = c.quadrature_nodes()
+    c.set_operator(capi.dt() - capi.laplacian() + capi.advection([1.0, -0.5]))
+    c.tune("dense_rows", 0)
+    times = np.linspace(0.0, 0.2, 7)
+    c.set_forcing(np.stack([np.sin(2.0 * qn[:, 0]) * (1.0 + t) for t in times], axis=1))
+    c.init()
+    u0 = np.cos(coords[:, 0]) * coords[:, 1]
+    G = np.stack([0.1 * np.sin(coords[:, 0] + 3.0 * t) for t in times], axis=1)
+    U, info = c.solve_parabolic(times, u0, G, method=capi.SOLVER_PMG, rtol=1e-11)
+    record_pmg(out, "pmg_parabolic", info, U)
+    c.close()
+
+
 def run(path):
     from fdapde_loader import load_package
 
     capi = load_package().capi
-    from fdapde_core_amd import meshgen
+    from fdapde_core_amd import meshgen, workloads
 
     if capi.load().fdapde_device_count() < 1:
         raise SystemExit("amg_onecol_ab.py needs a HIP device")
@@ -131,6 +202,8 @@ def run(path):
     handle_case(capi, meshgen, out, "handle_dense", 12, -capi.laplacian() + capi.reaction(2.0), True)
     block_case(capi, meshgen, out)
     parabolic_case(capi, meshgen, out)
+    pmg_cases(capi, meshgen, workloads, out)
+    pmg_parabolic_case(capi, meshgen, out)
     np.savez(path, **out)
 
 
