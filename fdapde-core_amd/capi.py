@@ -51,7 +51,7 @@ SYMBOLS = [
     "fdapde_ctx_create_multi", "fdapde_ctx_devices", "fdapde_partition_build", "fdapde_partition_sizes", "fdapde_partition_get", "fdapde_partition_whole",
     "fdapde_partition_peers",
     "fdapde_block_compute", "fdapde_block_solve", "fdapde_block_spmv", "fdapde_block_bench_spmv", "fdapde_gram_pointwise",
-    "fdapde_amg_hierarchy", "fdapde_amg_aggregates", "fdapde_amg_cols_trace",
+    "fdapde_amg_hierarchy", "fdapde_amg_aggregates", "fdapde_amg_order", "fdapde_amg_damping", "fdapde_amg_cols_trace",
 ]
 AMG_OF_SOLVE, AMG_OF_HANDLE, AMG_OF_BLOCK = 0, 1, 2   # `which` of fdapde_amg_hierarchy
 PARTITION_ROWDIST, PARTITION_ELEMENTS = 0, 1
@@ -639,8 +639,9 @@ class Context:
         return dict(batches=b.value, batched_cols=q.value, single_cols=s.value)
 
     def amg_aggregates(self, which, level):
-        """fdapde_amg_aggregates: for the block handle (which = 2) and a level that has a next one, the row of level + 1 every block row of `level` belongs
-        to (level 0 in the reference DOF numbering) -> int32 array.  FdapdeError(ENOTINIT) where no hierarchy is live, (EUNSUPPORTED) for which 0 / 1"""
+        """fdapde_amg_aggregates: for a live hierarchy (`which` as amg_hierarchy) and a level that has a next one, the row of level + 1 every row of `level`
+        belongs to (the block handle's: block rows; level 0 in the reference DOF numbering; -1: a row of no aggregate, a Dirichlet row of fdapde_solve's level 0)
+        -> int32 array.  FdapdeError(ENOTINIT) where no such hierarchy is live"""
         n = C.c_int64(0)
         rc = self.lib.fdapde_amg_aggregates(self._ctx, int(which), int(level), C.c_int64(0), None, C.byref(n))
         if rc != EINVAL or n.value <= 0:   # (a valid level answers EINVAL to the empty buffer and leaves its row count)
@@ -648,6 +649,25 @@ class Context:
         agg = np.full(n.value, -1, dtype=np.int32)
         self._check(self.lib.fdapde_amg_aggregates(self._ctx, int(which), int(level), C.c_int64(agg.size), _ip(agg), C.byref(n)))
         return agg
+
+    def amg_order(self, which):
+        """fdapde_amg_order: the reference DOF of every row of a live hierarchy's level 0, in the level's own order -> int32 array"""
+        n = C.c_int64(0)
+        rc = self.lib.fdapde_amg_order(self._ctx, int(which), C.c_int64(0), None, C.byref(n))
+        if rc != EINVAL or n.value <= 0:   # (a live hierarchy answers EINVAL to the empty buffer and leaves its row count)
+            self._check(rc)
+        order = np.full(n.value, -1, dtype=np.int32)
+        self._check(self.lib.fdapde_amg_order(self._ctx, int(which), C.c_int64(order.size), _ip(order), C.byref(n)))
+        return order
+
+    def amg_damping(self, which):
+        """fdapde_amg_damping: the smoothers' damping of a live hierarchy, per level, exactly as the cycle takes it (0 on the last level, which is inverted;
+        the block handle's: 0.7) -> float64 array.  FdapdeError(ENOTINIT) where no such hierarchy is live"""
+        nl = C.c_int32()
+        self._check(self.lib.fdapde_amg_damping(self._ctx, int(which), 0, C.byref(nl), None))
+        om = np.zeros(nl.value, dtype=np.float64)
+        self._check(self.lib.fdapde_amg_damping(self._ctx, int(which), nl.value, C.byref(nl), _dp(om)))
+        return om
 
     # ---- multi-GPU
     @staticmethod

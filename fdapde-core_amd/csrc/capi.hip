@@ -457,10 +457,31 @@ int fdapde_amg_cols_trace(fdapde_ctx* c, int32_t which, int32_t* batches, int32_
 int fdapde_amg_aggregates(fdapde_ctx* c, int32_t which, int32_t level, int64_t cap, int32_t* agg, int64_t* n_rows) {
     if (!c || which < 0 || which > 2) return FDAPDE_EINVAL;
     if (c->group) return fail(c, FDAPDE_EUNSUPPORTED, "fdapde_amg_aggregates: one-device contexts only");
-    if (which != 2) return fail(c, FDAPDE_EUNSUPPORTED, "fdapde_amg_aggregates: only the block handle's hierarchy (which = 2) hands its aggregates out");
-    const int rc = fdapde_engine::block_amg_aggregates_ctx(c, level, cap, agg, n_rows);
-    if (rc == FDAPDE_ENOTINIT) return fail(c, rc, "fdapde_amg_aggregates: no block hierarchy is live (it is built by the first solve that names FDAPDE_SOLVER_BLOCK_AMG)");
-    if (rc == FDAPDE_EINVAL) return fail(c, rc, "fdapde_amg_aggregates: `level` must have a next level, and `agg` room for the level's block rows (`cap`)");
+    const int rc = which == 0   ? fdapde_engine::amg_aggregates(c, c->amg, level, cap, agg, n_rows)
+                   : which == 1 ? fdapde_engine::amg_aggregates(c, fdapde_engine::amg_lin_live(c), level, cap, agg, n_rows)
+                                : fdapde_engine::block_amg_aggregates_ctx(c, level, cap, agg, n_rows);
+    if (rc == FDAPDE_ENOTINIT) return fail(c, rc, "fdapde_amg_aggregates: no hierarchy of that kind is live (it is built by the first solve that names the multilevel method)");
+    if (rc == FDAPDE_EINVAL) return fail(c, rc, "fdapde_amg_aggregates: `level` must have a next level, and `agg` room for the level's rows (`cap`)");
+    return rc;
+}
+
+int fdapde_amg_order(fdapde_ctx* c, int32_t which, int64_t cap, int32_t* order, int64_t* n_rows) {
+    if (!c || which < 0 || which > 2) return FDAPDE_EINVAL;
+    if (c->group) return fail(c, FDAPDE_EUNSUPPORTED, "fdapde_amg_order: one-device contexts only");
+    const int rc = which == 0   ? fdapde_engine::amg_order(c, c->amg, cap, order, n_rows)
+                   : which == 1 ? fdapde_engine::amg_order(c, fdapde_engine::amg_lin_live(c), cap, order, n_rows)
+                                : fdapde_engine::block_amg_order_ctx(c, cap, order, n_rows);
+    if (rc == FDAPDE_ENOTINIT) return fail(c, rc, "fdapde_amg_order: no hierarchy of that kind is live (it is built by the first solve that names the multilevel method)");
+    if (rc == FDAPDE_EINVAL) return fail(c, rc, "fdapde_amg_order: `order` must have room for level 0's rows (`cap`)");
+    return rc;
+}
+
+int fdapde_amg_damping(fdapde_ctx* c, int32_t which, int32_t cap, int32_t* n_levels, double* omega) {
+    if (!c || which < 0 || which > 2 || cap < 0 || (cap > 0 && !omega)) return FDAPDE_EINVAL;
+    const int rc = which == 0   ? fdapde_engine::amg_damping(c->amg, cap, n_levels, omega)
+                   : which == 1 ? fdapde_engine::amg_damping(fdapde_engine::amg_lin_live(c), cap, n_levels, omega)
+                                : fdapde_engine::block_amg_damping_ctx(c, cap, n_levels, omega);
+    if (rc == FDAPDE_ENOTINIT) return fail(c, rc, "fdapde_amg_damping: no hierarchy of that kind is live (it is built by the first solve that names the multilevel method)");
     return rc;
 }
 

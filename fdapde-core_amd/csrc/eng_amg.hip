@@ -176,6 +176,8 @@ __global__ void k_amg_scale(int64_t n, const double* a, double f, double* out) {
 // copies of every width, Q = 1 included, alike (s += a x, r - om s, z + om d (r - s), w -= h v): that is a property of this compiler, not of the language -- the
 // block forms in kernels_block.h needed theirs spelled out.  tests/test_gpu_amg_cols.py holds every column of Q = 2, 4, 8 to the Q = 1 run's bits on 2-D and
 // 3-D, P1 and P2 hierarchies; if a toolchain changes a width's fusion that test fails, and the remedy is kernels_block.h's.
+// tests/test_gpu_amg_iterates.py holds the result of every width to an extended-precision restatement of the cycle on the device's own aggregates and damping
+// (fdapde_amg_aggregates, fdapde_amg_damping): the k-th iterate within a few hundred u of its scale, measured 2 - 80.
 
 // pre-smoothing from zero and the restricted residual in one pass, a team per aggregate: zt_i = om d_i r_i for its members, and
 // rc_a = sum over members i of (r_i - sum_j a_ij om d_j r_j); word w of column q of rc at rc[w * rs + q * cs] (interleaved, or column-major for the dense
@@ -741,8 +743,9 @@ int amg_cols_trace(const AmgHierarchy* H, int32_t* batches, int32_t* batched_col
 }
 
 // (a hierarchy fdapde_lin_compute has outlived is not live: the next solve builds the new matrix's, and its trace starts at zero)
+const AmgHierarchy* amg_lin_live(const fdapde_ctx* c) { return c->amg_lin && c->amg_lin->key == c->amg_lin_epoch ? c->amg_lin : nullptr; }
 int amg_lin_cols_trace(const fdapde_ctx* c, int32_t* batches, int32_t* batched_cols, int32_t* single_cols) {
-    return amg_cols_trace(c->amg_lin && c->amg_lin->key == c->amg_lin_epoch ? c->amg_lin : nullptr, batches, batched_cols, single_cols);
+    return amg_cols_trace(amg_lin_live(c), batches, batched_cols, single_cols);
 }
 
 // fdapde_amg_hierarchy: rows and entries per level, counted in scalar unknowns (H->per of them to a node)
@@ -755,6 +758,49 @@ int amg_describe(const AmgHierarchy* H, int32_t cap, int32_t* n_levels, int64_t*
     }
     if (absorbed) *absorbed = H->absorbed;
     if (setup_ms) *setup_ms = H->setup_ms;
+    return FDAPDE_OK;
+}
+
+// fdapde_amg_aggregates: agg[i] = the row of level + 1 that row i of `level` belongs to, -1 for a row of no aggregate (level 0's Dirichlet rows under use_bnd);
+// level 0: i in the reference DOF numbering, through dof_i2e; deeper levels in the level's own numbering.  The block form's rows are block rows.  The resident
+// maps copied out, no kernel
+int amg_aggregates(fdapde_ctx* c, const AmgHierarchy* H, int32_t level, int64_t cap, int32_t* agg, int64_t* n_rows) {
+    if (!H) return FDAPDE_ENOTINIT;
+    if (level < 0 || (size_t)level + 1 >= H->lv.size()) return FDAPDE_EINVAL;
+    const AmgLevel& L = *H->lv[(size_t)level];
+    if (n_rows) *n_rows = L.n;
+    if (!agg || cap < L.n) return FDAPDE_EINVAL;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::vector<int32_t> own, i2e;
+    if (int rc = fetch(c, L.agg.p, (size_t)L.n, own)) return rc;
+    if (level > 0) {
+        std::copy(own.begin(), own.end(), agg);
+        return FDAPDE_OK;
+    }
+    if (int rc = fetch(c, c->dof_i2e.p, (size_t)L.n, i2e)) return rc;
+    for (int64_t i = 0; i < L.n; ++i) agg[i2e[(size_t)i]] = own[(size_t)i];
+    return FDAPDE_OK;
+}
+
+// fdapde_amg_order: order[i] = the reference DOF that row i of level 0 is (dof_i2e): the order level 0's own arithmetic runs in -- k_amg_hashvec's vector is a
+// function of the row index
+int amg_order(fdapde_ctx* c, const AmgHierarchy* H, int64_t cap, int32_t* order, int64_t* n_rows) {
+    if (!H) return FDAPDE_ENOTINIT;
+    const int64_t n = H->lv[0]->n;
+    if (n_rows) *n_rows = n;
+    if (!order || cap < n) return FDAPDE_EINVAL;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(order, c->dof_i2e.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
+    return FDAPDE_OK;
+}
+
+// fdapde_amg_damping: the smoother's damping per level as the cycle kernels take it, 0 on the last level (inverted, not smoothed)
+int amg_damping(const AmgHierarchy* H, int32_t cap, int32_t* n_levels, double* omega) {
+    if (!H) return FDAPDE_ENOTINIT;
+    if (n_levels) *n_levels = (int32_t)H->lv.size();
+    for (size_t l = 0; omega && l < H->lv.size() && (int64_t)l < (int64_t)cap; ++l) omega[l] = l + 1 < H->lv.size() ? H->lv[l]->om : 0.0;
     return FDAPDE_OK;
 }
 

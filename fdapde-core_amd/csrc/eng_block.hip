@@ -67,6 +67,12 @@ int block_amg_cols_trace_ctx(const fdapde_ctx* c, int32_t* batches, int32_t* bat
 int block_amg_aggregates_ctx(fdapde_ctx* c, int32_t level, int64_t cap, int32_t* agg, int64_t* n_rows) {
     return block_amg_aggregates(c, c->block ? c->block->amg : nullptr, level, cap, agg, n_rows);
 }
+int block_amg_order_ctx(fdapde_ctx* c, int64_t cap, int32_t* order, int64_t* n_rows) {
+    return block_amg_order(c, c->block ? c->block->amg : nullptr, cap, order, n_rows);
+}
+int block_amg_damping_ctx(const fdapde_ctx* c, int32_t cap, int32_t* n_levels, double* omega) {
+    return block_amg_damping(c->block ? c->block->amg : nullptr, cap, n_levels, omega);
+}
 
 namespace {
 

@@ -150,6 +150,7 @@ int block_amg_build_pass(fdapde_ctx* c, BlockAmg** slot, const double* raw, int 
         break;
     }
     for (auto& L : H->lv) level_team(*L);
+    for (size_t l = 0; l + 1 < H->lv.size(); ++l) H->lv[l]->om = kBamgOmega;   // (what fdapde_amg_damping answers; the kernels take the constant)
     if (int rc = amg_cols_prepare(c, *H, 1)) return rc;   // (the work vectors: one column until a batch asks for more)
     BamgLevel& C = blk(*H->lv.back());
     if (2 * C.n > kDenseMaxRows) return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_BLOCK_AMG: the coarsest level is too large for the dense inverse");
@@ -184,26 +185,12 @@ int block_amg_describe(const BlockAmg* H, int32_t cap, int32_t* n_levels, int64_
     return amg_describe(H, cap, n_levels, rows, nnz, absorbed, setup_ms);   // (rows 2 n_l, entries 4 nnz_l: per = 2)
 }
 
-// fdapde_amg_aggregates for the block handle: agg[i] = the row of level + 1 that block row i of `level` belongs to (level 0: i in the reference DOF
-// numbering, through dof_i2e; deeper levels in the level's own numbering).  The resident maps copied out, no kernel
+// fdapde_amg_aggregates / fdapde_amg_damping / fdapde_amg_order for the block handle: the levels are AmgLevel, the answers amg_aggregates' / amg_damping's (eng_amg.hip)
 int block_amg_aggregates(fdapde_ctx* c, const BlockAmg* H, int32_t level, int64_t cap, int32_t* agg, int64_t* n_rows) {
-    if (!H) return FDAPDE_ENOTINIT;
-    if (level < 0 || (size_t)level + 1 >= H->lv.size()) return FDAPDE_EINVAL;
-    const AmgLevel& L = *H->lv[(size_t)level];
-    if (n_rows) *n_rows = L.n;
-    if (!agg || cap < L.n) return FDAPDE_EINVAL;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    std::vector<int32_t> own, i2e;
-    if (int rc = fetch(c, L.agg.p, (size_t)L.n, own)) return rc;
-    if (level > 0) {
-        std::copy(own.begin(), own.end(), agg);
-        return FDAPDE_OK;
-    }
-    if (int rc = fetch(c, c->dof_i2e.p, (size_t)L.n, i2e)) return rc;
-    for (int64_t i = 0; i < L.n; ++i) agg[i2e[(size_t)i]] = own[(size_t)i];
-    return FDAPDE_OK;
+    return amg_aggregates(c, H, level, cap, agg, n_rows);
 }
+int block_amg_damping(const BlockAmg* H, int32_t cap, int32_t* n_levels, double* omega) { return amg_damping(H, cap, n_levels, omega); }
+int block_amg_order(fdapde_ctx* c, const BlockAmg* H, int64_t cap, int32_t* order, int64_t* n_rows) { return amg_order(c, H, cap, order, n_rows); }
 
 int block_amg_cols_trace(const BlockAmg* H, int32_t* batches, int32_t* batched_cols, int32_t* single_cols) { return amg_cols_trace(H, batches, batched_cols, single_cols); }
 void block_amg_count_single(BlockAmg* H) { ++H->single_cols; }

@@ -202,6 +202,14 @@ int amg_describe(const AmgHierarchy* h, int32_t cap, int32_t* n_levels, int64_t*
 // fdapde_amg_cols_trace: the hierarchy's Q-column runs, the columns they took, the columns solved one by one; FDAPDE_ENOTINIT for NULL
 int amg_cols_trace(const AmgHierarchy* h, int32_t* batches, int32_t* batched_cols, int32_t* single_cols);
 int amg_lin_cols_trace(const fdapde_ctx* c, int32_t* batches, int32_t* batched_cols, int32_t* single_cols);   // the handle's (none once fdapde_lin_compute has outlived it)
+const AmgHierarchy* amg_lin_live(const fdapde_ctx* c);   // the handle's hierarchy, NULL once fdapde_lin_compute has outlived it
+// fdapde_amg_aggregates: the map row -> row of the next level of `level` (level 0 in the reference DOF numbering, -1: a row of no aggregate), for the scalar
+// hierarchies and the block form's alike; FDAPDE_ENOTINIT for NULL, FDAPDE_EINVAL for a level without a next one, a NULL agg or cap < the level's rows
+int amg_aggregates(fdapde_ctx* c, const AmgHierarchy* h, int32_t level, int64_t cap, int32_t* agg, int64_t* n_rows);
+// fdapde_amg_order: the reference DOF of every row of level 0, in the level's own order; FDAPDE_ENOTINIT for NULL, FDAPDE_EINVAL for a NULL order or cap < its rows
+int amg_order(fdapde_ctx* c, const AmgHierarchy* h, int64_t cap, int32_t* order, int64_t* n_rows);
+// fdapde_amg_damping: the smoother's damping of the first `cap` levels, 0 on the last one; FDAPDE_ENOTINIT for NULL
+int amg_damping(const AmgHierarchy* h, int32_t cap, int32_t* n_levels, double* omega);
 int block_amg_cols_trace_ctx(const fdapde_ctx* c, int32_t* batches, int32_t* batched_cols, int32_t* single_cols);
 int dense_step_loop(fdapde_ctx* c, fdapde_ctx::Dense& D, int32_t n_times, double inv_dt, const double* g_ext_dev, double* u0, double* sol_ext);
 void preload_dense();
@@ -210,6 +218,8 @@ void block_release(fdapde_ctx* c);
 void block_amg_forget(fdapde_ctx* c);   // the block handle's hierarchy is built again by its next solve (a set-up knob changed)
 int block_amg_describe_ctx(const fdapde_ctx* c, int32_t cap, int32_t* n_levels, int64_t* rows, int64_t* nnz, int32_t* absorbed, double* setup_ms);
 int block_amg_aggregates_ctx(fdapde_ctx* c, int32_t level, int64_t cap, int32_t* agg, int64_t* n_rows);
+int block_amg_damping_ctx(const fdapde_ctx* c, int32_t cap, int32_t* n_levels, double* omega);
+int block_amg_order_ctx(fdapde_ctx* c, int64_t cap, int32_t* order, int64_t* n_rows);
 int e_block_compute(fdapde_ctx* c, const double* a11, const double* a12, const double* a21, const double* a22, int32_t symmetric);
 int e_block_solve(fdapde_ctx* c, const fdapde_options* opt, const double* b, int32_t n_rhs, double* x, fdapde_info* info);
 int e_block_spmv(fdapde_ctx* c, const double* x, double* y);
@@ -223,6 +233,8 @@ void block_amg_free(BlockAmg* h);
 int block_amg_build(fdapde_ctx* c, BlockAmg** slot, const double* raw, int strength_block);
 int block_amg_describe(const BlockAmg* h, int32_t cap, int32_t* n_levels, int64_t* rows, int64_t* nnz, int32_t* absorbed, double* setup_ms);   // rows: 2 n_l
 int block_amg_aggregates(fdapde_ctx* c, const BlockAmg* h, int32_t level, int64_t cap, int32_t* agg, int64_t* n_rows);   // fdapde_amg_aggregates, which 2
+int block_amg_order(fdapde_ctx* c, const BlockAmg* h, int64_t cap, int32_t* order, int64_t* n_rows);   // fdapde_amg_order, which 2 (block rows)
+int block_amg_damping(const BlockAmg* h, int32_t cap, int32_t* n_levels, double* omega);   // fdapde_amg_damping, which 2: 0.7 on every level that has a next one
 int block_amg_run(fdapde_ctx* c, BlockAmg* h, const double* raw, const double* b_dev, double* x_dev, double rtol, int maxit, int* iters, double* relres,
                   bool* converged, bool* broke, bool warm = false);   // warm: x_dev holds the iterate to start from (a column a batch handed back)
 // Q in {2, 4, 8} columns side by side (knob amg_cols; block_amg_width: the widest batch for `left` columns): ext (device) holds the stacked columns in the

@@ -538,12 +538,24 @@ int fdapde_tune(fdapde_ctx *ctx, const char *key, int32_t value);
  * first build of "amg_absorb" 2 included.  Any output pointer may be NULL.  FDAPDE_ENOTINIT where no such hierarchy is live. */
 int fdapde_amg_hierarchy(fdapde_ctx *ctx, int32_t which, int32_t cap, int32_t *n_levels, int64_t *rows, int64_t *nnz, int32_t *absorbed, double *setup_ms);
 /* The aggregates of a live hierarchy as data (diagnostic, like fdapde_amg_hierarchy: what a test needs to restate everything numerical that is built on
- * them).  which = 2, the block handle's, and level < *n_levels - 1 of fdapde_amg_hierarchy: agg[i] = the row of level + 1 that block row i of `level`
- * belongs to, *n_rows = the level's block rows (rows[level] / 2).  Level 0 is given in the reference DOF numbering, deeper levels in the level's own row
- * numbering.  cap: the room of agg in entries.  FDAPDE_ENOTINIT where no hierarchy is live; FDAPDE_EINVAL for a level outside that range, a NULL agg or
- * cap < *n_rows (*n_rows is set where the level is valid); FDAPDE_EUNSUPPORTED for which = 0 and 1 (the scalar hierarchies do not hand theirs out) and
- * for multi-device contexts. */
+ * them).  which as in fdapde_amg_hierarchy, and level < *n_levels - 1: agg[i] = the row of level + 1 that row i of `level` belongs to (the block handle's:
+ * block row i), -1 for a row that belongs to no aggregate (a Dirichlet row of fdapde_solve's level 0); *n_rows = the level's rows (the block handle's:
+ * block rows, rows[level] / 2).  Level 0 is given in the reference DOF numbering, deeper levels in the level's own row numbering.  cap: the room of agg
+ * in entries.  FDAPDE_ENOTINIT where no such hierarchy is live -- the factor-once handle's is not once fdapde_lin_compute has outlived it --;
+ * FDAPDE_EINVAL for a level outside that range, a NULL agg or cap < *n_rows (*n_rows is set where the level is valid); FDAPDE_EUNSUPPORTED for
+ * multi-device contexts. */
 int fdapde_amg_aggregates(fdapde_ctx *ctx, int32_t which, int32_t level, int64_t cap, int32_t *agg, int64_t *n_rows);
+/* The order level 0 of a live hierarchy keeps its rows in (diagnostic, with fdapde_amg_aggregates).  which as in fdapde_amg_hierarchy.  order[i] = the
+ * reference DOF that row i of level 0 is (the block handle's: block row i), *n_rows = level 0's rows.  fdapde_amg_aggregates hands level 0 out in the
+ * reference numbering; what level 0 computes from its row INDEX -- the fixed start vector of the damping's power iteration -- needs this order to be
+ * restated.  Deeper levels are handed out in their own order.  cap: the room of order in entries.  FDAPDE_ENOTINIT where no such hierarchy is live;
+ * FDAPDE_EINVAL for a NULL order or cap < *n_rows (*n_rows is set); FDAPDE_EUNSUPPORTED for multi-device contexts. */
+int fdapde_amg_order(fdapde_ctx *ctx, int32_t which, int64_t cap, int32_t *order, int64_t *n_rows);
+/* The damping of a live hierarchy's smoothers as data (diagnostic, with fdapde_amg_aggregates).  which as in fdapde_amg_hierarchy.  *n_levels: its levels;
+ * omega[l] for the first min(cap, *n_levels) of them: the factor of D^-1 in level l's smoother exactly as the cycle takes it -- 0 and 1:
+ * 1.5 / lambda_max(D^-1 A) from 15 power iterations off a fixed start vector (a function of the row index in the level's own order: fdapde_amg_order), 2: 0.7 -- and 0 on the last level, which is inverted.  omega may be NULL
+ * with cap = 0.  FDAPDE_ENOTINIT where no such hierarchy is live (as fdapde_amg_aggregates). */
+int fdapde_amg_damping(fdapde_ctx *ctx, int32_t which, int32_t cap, int32_t *n_levels, double *omega);
 /* How the columns of a multilevel handle's solves were run since its hierarchy was built.  which as in fdapde_amg_hierarchy: 1 = the factor-once handle's
  * (FDAPDE_SOLVER_AMG), 2 = the block handle's (FDAPDE_SOLVER_BLOCK_AMG); 0, fdapde_solve's own, is FDAPDE_EUNSUPPORTED (one column).  *batches: runs of
  * 2, 4 or 8 columns side by side ("amg_cols"); *batched_cols: the columns they took; *single_cols: the columns solved one by one -- a column a batch

@@ -147,10 +147,12 @@ def test_the_query_is_exported_and_a_host_only_context_has_no_hierarchy():
     with pytest.raises(capi.FdapdeError) as e:
         c.amg_hierarchy(3)
     assert e.value.status == capi.EINVAL
-    # ... and fdapde_amg_aggregates likewise: no block hierarchy, the scalar ones do not hand theirs out, no fourth kind
-    assert "fdapde_amg_aggregates" in capi.SYMBOLS and hasattr(capi.load(), "fdapde_amg_aggregates")
-    for which, status in ((2, capi.ENOTINIT), (0, capi.EUNSUPPORTED), (1, capi.EUNSUPPORTED), (3, capi.EINVAL)):
-        with pytest.raises(capi.FdapdeError) as e:
-            c.amg_aggregates(which, 0)
-        assert e.value.status == status, which
+    # ... and fdapde_amg_aggregates / fdapde_amg_damping / fdapde_amg_order likewise: no hierarchy of any kind is live, no fourth kind
+    for symbol in ("fdapde_amg_aggregates", "fdapde_amg_damping", "fdapde_amg_order"):
+        assert symbol in capi.SYMBOLS and hasattr(capi.load(), symbol)
+    for which, status in ((2, capi.ENOTINIT), (0, capi.ENOTINIT), (1, capi.ENOTINIT), (3, capi.EINVAL)):
+        for call in (lambda: c.amg_aggregates(which, 0), lambda: c.amg_damping(which), lambda: c.amg_order(which)):
+            with pytest.raises(capi.FdapdeError) as e:
+                call()
+            assert e.value.status == status, which
     c.close()

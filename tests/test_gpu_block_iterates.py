@@ -228,10 +228,14 @@ def test_the_getter_refuses_what_it_cannot_answer(env):
         assert e.value.status == capi.ENOTINIT, "no hierarchy before the first multilevel solve"
     s = _multilevel(env, "g")
     c, levels, n0 = s["c"], len(s["h"]["rows"]), s["n"]
-    for which in (capi.AMG_OF_SOLVE, capi.AMG_OF_HANDLE):
-        with pytest.raises(capi.FdapdeError) as e:
-            c.amg_aggregates(which, 0)
-        assert e.value.status == capi.EUNSUPPORTED
+    for which in (capi.AMG_OF_SOLVE, capi.AMG_OF_HANDLE):   # (a context with a block hierarchy only: the scalar ones are not live)
+        for call in (lambda: c.amg_aggregates(which, 0), lambda: c.amg_damping(which)):
+            with pytest.raises(capi.FdapdeError) as e:
+                call()
+            assert e.value.status == capi.ENOTINIT
+    om = c.amg_damping(capi.AMG_OF_BLOCK)
+    assert om.shape == (levels,) and (om[:-1] == ir.OMEGA).all() and om[-1] == 0.0, "0.7 on every level that has a next one"
+    assert np.array_equal(np.sort(c.amg_order(capi.AMG_OF_BLOCK)), np.arange(n0)), "level 0's block rows are the DOFs, each once"
     for level in (-1, levels - 1, levels):   # (the last level has no next one)
         with pytest.raises(capi.FdapdeError) as e:
             c.amg_aggregates(capi.AMG_OF_BLOCK, level)
@@ -243,6 +247,20 @@ def test_the_getter_refuses_what_it_cannot_answer(env):
     assert c.lib.fdapde_amg_aggregates(c._ctx, 3, 0, C.c_int64(n0), buf.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(rows)) == capi.EINVAL
     assert c.lib.fdapde_amg_aggregates(c._ctx, 2, 0, C.c_int64(n0), buf.ctypes.data_as(C.POINTER(C.c_int32)), None) == capi.OK
     assert np.array_equal(buf, s["aggs"][0])
+    # the same calls succeed once a scalar solve has run on that context: the factor-once handle's hierarchy (which = 1) of stiffness + mass
+    c.lin_compute(values=c.matrix_values(capi.MAT_STIFF) + c.matrix_values(capi.MAT_MASS), symmetric=True)
+    _, info = c.lin_solve(np.ones(n0), method=capi.SOLVER_AMG, rtol=1e-10)
+    assert info.converged == 1 and info.method_used == capi.SOLVER_AMG
+    hs = c.amg_hierarchy(capi.AMG_OF_HANDLE)
+    assert len(hs["rows"]) >= 2 and hs["rows"][0] == n0
+    agg, om = c.amg_aggregates(capi.AMG_OF_HANDLE, 0), c.amg_damping(capi.AMG_OF_HANDLE)
+    assert agg.shape == (n0,) and agg.min() == 0 and agg.max() == hs["rows"][1] - 1 and len(np.unique(agg)) == hs["rows"][1]
+    assert om.shape == (len(hs["rows"]),) and (om[:-1] > 0.0).all() and om[-1] == 0.0
+    with pytest.raises(capi.FdapdeError) as e:
+        c.amg_aggregates(capi.AMG_OF_SOLVE, 0)
+    assert e.value.status == capi.ENOTINIT, "fdapde_solve's is still not live"
+    assert np.array_equal(c.amg_aggregates(capi.AMG_OF_BLOCK, 0), s["aggs"][0]) and c.amg_hierarchy(capi.AMG_OF_BLOCK) == s["h"], "the block hierarchy stays"
     m = capi.Context(devices=[0, 0])
     assert m.lib.fdapde_amg_aggregates(m._ctx, 2, 0, C.c_int64(n0), buf.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(rows)) == capi.EUNSUPPORTED
+    assert m.lib.fdapde_amg_aggregates(m._ctx, 0, 0, C.c_int64(n0), buf.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(rows)) == capi.EUNSUPPORTED
     m.close()
