@@ -51,6 +51,7 @@ SYMBOLS = [
     "fdapde_ctx_create_multi", "fdapde_ctx_devices", "fdapde_partition_build", "fdapde_partition_sizes", "fdapde_partition_get", "fdapde_partition_whole",
     "fdapde_partition_peers",
     "fdapde_block_compute", "fdapde_block_solve", "fdapde_block_spmv", "fdapde_block_bench_spmv", "fdapde_gram_pointwise",
+    "fdapde_kron_compute", "fdapde_kron_solve", "fdapde_kron_spmv", "fdapde_kron_bench_spmv",
     "fdapde_amg_hierarchy", "fdapde_amg_aggregates", "fdapde_amg_order", "fdapde_amg_damping", "fdapde_amg_cols_trace",
 ]
 AMG_OF_SOLVE, AMG_OF_HANDLE, AMG_OF_BLOCK = 0, 1, 2   # `which` of fdapde_amg_hierarchy
@@ -451,6 +452,87 @@ class Context:
         """(average ms of k_block_spmv on the scaled blocks, algorithmic bytes per launch)"""
         ms, by = C.c_double(), C.c_double()
         self._check(self.lib.fdapde_block_bench_spmv(self._ctx, reps, C.byref(ms), C.byref(by)))
+        return ms.value, by.value
+
+    # ---- Kronecker-sum operators sum_k T_k (x) S_k on the FEM pattern (the reference's Kronecker(A, B) under fdapde::SparseLU): the space-time systems' handle
+    def kron_compute(self, terms, symmetric=False):
+        """fdapde_kron_compute: terms = [(T, S_values), ...], T dense q x q, S_values nnz values aligned with pattern_get().  Terms that hand over the
+        SAME S_values object share one spatial factor.  q and the number of terms are checked by the library (EINVAL); a None factor goes through as NULL"""
+        nnz = self.sizes()["nnz"]
+        terms = list(terms)
+        q = 0
+        for T, _ in terms:
+            if T is not None:
+                q = int(np.asarray(T).shape[0]) if np.asarray(T).ndim == 2 else 0
+                break
+        keep_t, keep_s, by_id = [], [], {}
+        for T, S in terms:
+            if T is None:
+                keep_t.append(None)
+            else:
+                t = np.asfortranarray(np.asarray(T, dtype=float))
+                if t.ndim != 2 or t.shape != (q, q):
+                    raise ValueError("kron_compute(): every T must be q x q")
+                keep_t.append(t)
+            if S is None:
+                keep_s.append(None)
+            else:
+                if id(S) not in by_id:
+                    v = np.ascontiguousarray(S, dtype=float).reshape(-1)
+                    if v.size != nnz:
+                        raise ValueError(f"kron_compute(): a spatial factor holds {v.size} values, the pattern has {nnz} entries")
+                    by_id[id(S)] = v
+                keep_s.append(by_id[id(S)])
+        PP = C.POINTER(C.c_double) * max(1, len(terms))
+        tp = PP(*[_dp(t) if t is not None else C.POINTER(C.c_double)() for t in keep_t])
+        sp_ = PP(*[_dp(s) if s is not None else C.POINTER(C.c_double)() for s in keep_s])
+        self._check(self.lib.fdapde_kron_compute(self._ctx, q, len(terms), tp, sp_, 1 if symmetric else 0))
+        self._kron_q = q
+
+    def _kron_rows(self):
+        return getattr(self, "_kron_q", 0) * self.sizes()["n_dofs"]
+
+    def kron_solve(self, b, method=SOLVER_AUTO, rtol=1e-10, maxit=0, raise_on_noconv=True):
+        """fdapde_kron_solve: b (q n_dofs,) or (q n_dofs, n_rhs) in the Kronecker order (index r n_dofs + i) -> (x, Info).
+        raise_on_noconv=False: FDAPDE_ENOCONV is reported through info.converged only, x holds the last iterate of every column"""
+        b = np.asarray(b, dtype=float)
+        one = b.ndim == 1
+        B = b.reshape(b.shape[0], -1)
+        if getattr(self, "_kron_q", 0) and B.shape[0] != self._kron_rows():
+            raise ValueError("kron_solve(): b must hold q n_dofs rows")
+        flat = np.ascontiguousarray(B.T).reshape(-1)
+        out = np.zeros_like(flat)
+        opt = Options(method=method, maxit=maxit, rtol=rtol, assembly=0, check_every=0, time_spmv=0)
+        info = Info()
+        rc = self.lib.fdapde_kron_solve(self._ctx, C.byref(opt), _dp(flat), B.shape[1], _dp(out), C.byref(info))
+        if rc != OK and (raise_on_noconv or rc != ENOCONV):
+            self._check(rc)
+        X = np.ascontiguousarray(out.reshape(B.shape[1], B.shape[0]).T)
+        return (X[:, 0] if one else X), info
+
+    def kron_solve_inplace(self, bx, method=SOLVER_AUTO, rtol=1e-10, maxit=0):
+        """fdapde_kron_solve with x = b: bx (q n_dofs, n_rhs) Fortran-ordered float64 is overwritten by the solutions -> Info"""
+        assert bx.dtype == np.float64 and bx.ndim == 2 and bx.flags.f_contiguous
+        if getattr(self, "_kron_q", 0) and bx.shape[0] != self._kron_rows():
+            raise ValueError("kron_solve_inplace(): bx must hold q n_dofs rows")
+        opt = Options(method=method, maxit=maxit, rtol=rtol, assembly=0, check_every=0, time_spmv=0)
+        info = Info()
+        self._check(self.lib.fdapde_kron_solve(self._ctx, C.byref(opt), _dp(bx), bx.shape[1], _dp(bx), C.byref(info)))
+        return info
+
+    def kron_spmv(self, x):
+        """y = A x, vectors of q n_dofs in the Kronecker order"""
+        x = np.ascontiguousarray(x, dtype=float).reshape(-1)
+        if getattr(self, "_kron_q", 0) and x.size != self._kron_rows():
+            raise ValueError("kron_spmv(): x must hold q n_dofs values")
+        y = np.zeros_like(x)
+        self._check(self.lib.fdapde_kron_spmv(self._ctx, _dp(x), _dp(y)))
+        return y
+
+    def kron_bench_spmv(self, reps=50):
+        """(average ms of the Krylov stage's operator D^-1 A, algorithmic bytes per application)"""
+        ms, by = C.c_double(), C.c_double()
+        self._check(self.lib.fdapde_kron_bench_spmv(self._ctx, reps, C.byref(ms), C.byref(by)))
         return ms.value, by.value
 
     def gram_pointwise(self, cell_ids, values, weights=None):

@@ -77,6 +77,7 @@ void fdapde_ctx_destroy(fdapde_ctx* c) {
     fdapde_engine::pmg_release(c);               // (... and the coarse level's context)
     fdapde_engine::amg_release(c);               // (... and the aggregation hierarchies)
     fdapde_engine::block_release(c);             // (... and the 2 x 2 block handle)
+    fdapde_engine::kron_release(c);              // (... and the Kronecker-sum handle)
     if (c->has_device) {
         (void)hipSetDevice(c->device);
         fdapde_engine::partition_free(c);
@@ -330,6 +331,28 @@ int fdapde_block_bench_spmv(fdapde_ctx* c, int32_t reps, double* avg_ms, double*
     if (c->group) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, kBlockNoGroup);
     return fdapde_engine::e_block_bench_spmv(c, reps, avg_ms, algorithmic_bytes);
 }
+// the Kronecker-sum handle (eng_kron.hip): single-device contexts only
+static const char* const kKronNoGroup = "the Kronecker-sum handle takes one-GPU contexts, not a multi-device context";
+int fdapde_kron_compute(fdapde_ctx* c, int32_t q, int32_t n_terms, const double* const* T, const double* const* S, int32_t symmetric) {
+    if (!c) return FDAPDE_EINVAL;
+    if (c->group) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, kKronNoGroup);
+    return fdapde_engine::e_kron_compute(c, q, n_terms, T, S, symmetric);
+}
+int fdapde_kron_solve(fdapde_ctx* c, const fdapde_options* opt, const double* b, int32_t n_rhs, double* x, fdapde_info* info) {
+    if (!c) return FDAPDE_EINVAL;
+    if (c->group) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, kKronNoGroup);
+    return fdapde_engine::e_kron_solve(c, opt, b, n_rhs, x, info);
+}
+int fdapde_kron_spmv(fdapde_ctx* c, const double* x, double* y) {
+    if (!c) return FDAPDE_EINVAL;
+    if (c->group) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, kKronNoGroup);
+    return fdapde_engine::e_kron_spmv(c, x, y);
+}
+int fdapde_kron_bench_spmv(fdapde_ctx* c, int32_t reps, double* avg_ms, double* algorithmic_bytes) {
+    if (!c) return FDAPDE_EINVAL;
+    if (c->group) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, kKronNoGroup);
+    return fdapde_engine::e_kron_bench_spmv(c, reps, avg_ms, algorithmic_bytes);
+}
 int fdapde_gram_pointwise(fdapde_ctx* c, int64_t n_locs, const int32_t* cell_ids, const double* values, const double* weights, double* out_values) {
     if (!c) return FDAPDE_EINVAL;
     if (c->group) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, kBlockNoGroup);
@@ -538,6 +561,8 @@ int fdapde_tune(fdapde_ctx* c, const char* key, int32_t value) {
     else if (k == "amg_coarse_rows" && value >= 1 && value <= 8192) c->amg_coarse_rows = value;
     else if (k == "amg_setup_check" && (value == 0 || value == 1)) c->amg_setup_check = value;
     else if (k == "amg_cols" && (value == 1 || value == 2 || value == 4 || value == 8)) c->amg_cols = value;
+    else if (k == "kron_dinv_mb" && value >= 0) c->kron_dinv_mb = value;   // (read by the next fdapde_kron_compute)
+    else if (k == "kron_fuse" && (value == 0 || value == 1)) c->kron_fuse = value;
     else if (k == "amg_absorb" && value >= 0 && value <= 2) {   // the hierarchies are built again by the next solve that needs one
         if (value != c->amg_absorb) fdapde_engine::amg_release(c), fdapde_engine::block_amg_forget(c);
         c->amg_absorb = value;

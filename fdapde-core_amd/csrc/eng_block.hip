@@ -14,6 +14,7 @@
 
 #include "context.h"
 #include "engine.h"
+#include "eng_gmres.h"
 #include "kernels_block.h"
 #include "kernels_dense.h"
 #include "kernels_gmres.h"
@@ -90,61 +91,10 @@ void launch_block_spmv(fdapde_ctx* c, const double* vals, const double* x, doubl
     hipLaunchKernelGGL(k_block_spmv<T>, dim3(g1(n, 256 / T)), dim3(256), 0, c->stream, n, c->rowptr.p, c->colidx.p, vals, x, y, stop);
 }
 
-int vec_grid2(int64_t n2) { return (int)std::max<int64_t>(1, std::min<int64_t>(1024, (n2 + 255) / 256)); }
-
-// restarted GMRES(m) on D^-1 A z = D^-1 b for the column staged in B.bt: the loop of run_gmres (eng_solve.hip) on the handle's buffers -- the same
-// stop rule (the estimate inside a cycle, the TRUE residual at its end, which the next cycle starts from and relres reports)
+// restarted GMRES(m) on D^-1 A z = D^-1 b for the column staged in B.bt: handle_gmres (eng_gmres.h) on the handle's buffers
 int block_gmres(fdapde_ctx* c, BlockHandle& B, double tol2, int maxit, int32_t h_ctl[4], double h_sc[4]) {
-    const int64_t n2 = 2 * B.n;
-    const int m = c->gmres_m;
-    hipStream_t st = c->stream;
-    const int vg = vec_grid2(n2);
-    HIPCHK(c, B.gm_V.alloc((size_t)(m + 1) * (size_t)n2));
-    HIPCHK(c, B.gm_s.alloc((size_t)gm_state_doubles(m) + (size_t)m + 2));
-    const size_t gm_norm_at = (size_t)(m + 1) * kGmStripes;
-    HIPCHK(c, B.gm_part.alloc(gm_norm_at + (size_t)std::max(vg, kGmStripes)));
-    double* gm_norm = B.gm_part.p + gm_norm_at;
-    double* gs = B.gm_s.p;
-    double* h_pass = gs + gm_state_doubles(m);
-    double* hcol = gs + 3 * m + 1;
-    double* w = B.w.p;
-    hipLaunchKernelGGL(k_block_krylov_init, dim3(vg), dim3(256), 0, st, n2, B.bt.p, B.x.p, B.r.p, B.gm_part.p);
-    hipLaunchKernelGGL(k_block_krylov_init_fin, dim3(1), dim3(64), 0, st, B.gm_part.p, vg, B.sc.p, B.ctl.p);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(h_ctl, B.ctl.p, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(h_sc, B.sc.p, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    bool stop = h_ctl[0] != 0;
-    while (!stop) {
-        hipLaunchKernelGGL(k_gm_cycle_init, dim3(vg), dim3(256), 0, st, n2, m, B.r.p, B.sc.p, gs, B.gm_V.p, B.ctl.p);
-        for (int j = 0; j < m; ++j) {
-            const double* vj = B.gm_V.p + (size_t)j * n2;
-            launch_block_spmv(c, B.scaled.p, vj, w, B.ctl.p);
-            for (int pass = 0; pass < 2; ++pass) {
-                hipLaunchKernelGGL(k_gm_dots, dim3(kGmStripes, j + 1), dim3(256), 0, st, n2, B.gm_V.p, w, B.gm_part.p, B.ctl.p);
-                hipLaunchKernelGGL(k_gm_reduce, dim3(j + 1), dim3(256), 0, st, B.gm_part.p, h_pass, hcol, pass, B.ctl.p);
-                hipLaunchKernelGGL(k_gm_axpy, dim3(vg), dim3(256), 0, st, n2, j + 1, B.gm_V.p, h_pass, w, gm_norm, pass, B.ctl.p);
-            }
-            hipLaunchKernelGGL(k_gm_hess, dim3(1), dim3(256), 0, st, j, m, gm_norm, vg, gs, B.sc.p, B.ctl.p, tol2, maxit);
-            hipLaunchKernelGGL(k_gm_next, dim3(vg), dim3(256), 0, st, n2, w, gs, m, B.gm_V.p + (size_t)(j + 1) * n2, B.ctl.p);
-            if (j % 10 == 9 && j + 1 < m) {
-                HIPCHK(c, hipMemcpyAsync(h_ctl, B.ctl.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-                HIPCHK(c, hipStreamSynchronize(st));
-                if (h_ctl[0] != 0) break;
-            }
-        }
-        hipLaunchKernelGGL(k_gm_solve_y, dim3(1), dim3(1), 0, st, m, gs);
-        hipLaunchKernelGGL(k_gm_update_x, dim3(vg), dim3(256), 0, st, n2, m, B.gm_V.p, gs, B.x.p);
-        launch_block_spmv(c, B.scaled.p, B.x.p, B.t.p, nullptr);
-        hipLaunchKernelGGL(k_gm_residual, dim3(vg), dim3(256), 0, st, n2, B.bt.p, B.t.p, B.r.p, B.gm_part.p);
-        hipLaunchKernelGGL(k_gm_cycle_fin, dim3(1), dim3(256), 0, st, B.gm_part.p, vg, B.sc.p, B.ctl.p, tol2, maxit);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(h_ctl, B.ctl.p, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemcpyAsync(h_sc, B.sc.p, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        stop = h_ctl[0] != 0;
-    }
-    return FDAPDE_OK;
+    return handle_gmres(c, HandleGmresWork{B.bt, B.x, B.r, B.w, B.t, B.sc, B.gm_V, B.gm_s, B.gm_part, B.ctl}, 2 * B.n,
+                        [&](const double* x, double* y, const int32_t* stop) { launch_block_spmv(c, B.scaled.p, x, y, stop); }, tol2, maxit, h_ctl, h_sc);
 }
 
 bool block_dense_eligible(const fdapde_ctx* c, const BlockHandle& B) {

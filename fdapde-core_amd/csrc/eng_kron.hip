@@ -1,0 +1,368 @@
+// eng_kron.hip -- the Kronecker-sum handle: A = sum_k T_k (x) S_k with dense q x q time factors and spatial factors on the FEM pattern (the reference's
+// Kronecker(A, B), fdaPDE/linear_algebra/kronecker_product.h:56-80, evaluated into an explicit sparse matrix and handed to SparseLU there): the space-time
+// separable smoothing system and the monolithic parabolic system, kept as factors (kernels_kron.h).
+//   fdapde_kron_compute      terms -> n_S distinct spatial factors interleaved per pattern entry in the internal order, the summed time factors, D_i^-1
+//   fdapde_kron_solve        restarted GMRES(m) on D^-1 A (kernels_gmres.h, buffers of the handle's own), or the dense inverse of the q n-row matrix
+//   fdapde_kron_spmv         y = A x
+//   fdapde_kron_bench_spmv   HIP-event timing of the Krylov stage's operator
+// Independent of the n x n handle of fdapde_lin_compute and of the 2 x 2 block handle: nothing here writes a buffer one of the other solves reads back.
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <vector>
+
+#include "context.h"
+#include "engine.h"
+#include "eng_gmres.h"
+#include "host_kron.h"
+#include "kernels_dense.h"
+#include "kernels_gmres.h"
+#include "kernels_kron.h"
+#include "kernels_krylov.h"
+
+namespace fdapde_engine {
+
+struct KronHandle {
+    bool ready = false, symmetric = false;
+    bool have_dinv = false;            // D^-1 fits the budget (knob kron_dinv_mb) and was built
+    bool jacobi_ok = false;            // ... and every diagonal block was invertible: the Krylov stage is available
+    bool t_in_lds = false;             // the time factors are small enough to be copied into LDS by every workgroup of the product (kKronLdsFactorDoubles)
+    int q = 0, ns = 0, Q = 2;          // unknowns per DOF, distinct spatial factors, team width
+    int64_t n = 0, nnz = 0;            // the space the handle was computed on
+    DBuf<double> vals, tm, dinv;       // [n_S nnz] spatial values, [n_S q q] time factors, [q q n] inverted diagonal blocks
+    DBuf<int32_t> band;                // [2 q] first / last non-zero column of every T-row
+    DBuf<double> ext;                  // staging: factors / columns in the reference numbering
+    DBuf<double> bt, x, r, w, t, sc, gm_V, gm_s, gm_part;
+    DBuf<int32_t> ctl, flag;
+    DBuf<int32_t> rowptr2, colidx2;    // the q n-row CSR form (dense stage), built on first use
+    DBuf<double> val2, dn_b, dn_x;
+    bool expanded = false;
+    fdapde_ctx::Dense dense;
+    int64_t cols = 0;                  // columns solved against the current matrix
+    double krylov_ms = 0;              // ... and the host time the Krylov columns among them took
+};
+
+void kron_release(fdapde_ctx* c) {
+    if (!c->kron) return;
+    if (c->has_device) {
+        (void)hipSetDevice(c->device);
+        (void)hipStreamSynchronize(c->stream);
+    }
+    delete c->kron;
+    c->kron = nullptr;
+}
+
+namespace {
+
+const char* const kKronFirst = "call fdapde_kron_compute first";
+
+int kron_guard(fdapde_ctx* c) {
+    if (int rc = need_device(c)) return rc;
+    if (c->comm != nullptr || c->ar_fn != nullptr || c->halo_ready || c->rd.ready)
+        return fail(c, FDAPDE_EUNSUPPORTED, "the Kronecker-sum handle takes one-GPU contexts, not a rank of a multi-GPU job");
+    if (!c->dev_ready) return fail(c, FDAPDE_ENOTINIT, "call fdapde_dofs_build first");
+    return FDAPDE_OK;
+}
+bool kron_live(const fdapde_ctx* c) { return c->kron && c->kron->ready && c->kron->n == c->hs.n_dofs && c->kron->nnz == c->hs.nnz; }
+
+int team_width(int q) {
+    int Q = 2;
+    while (Q < q) Q *= 2;
+    return Q;
+}
+
+// y = A x, or y = D^-1 A x with the inverse fused into the epilogue
+void launch_kron_spmv(fdapde_ctx* c, const KronHandle& K, bool fuse, const double* x, double* y, const int32_t* stop) {
+    const size_t lds = sizeof(double) * kron_spmv_lds_doubles(K.q, K.ns, fuse, K.t_in_lds);
+    const dim3 grid(g1(K.n, 256 / K.Q)), block(256);
+#define FDAPDE_KRON_SPMV(QQ)                                                                                                                                   \
+    case QQ:                                                                                                                                                   \
+        if (fuse)                                                                                                                                              \
+            hipLaunchKernelGGL((k_kron_spmv<QQ, true>), grid, block, lds, c->stream, K.n, K.q, K.ns, c->rowptr.p, c->colidx.p, K.vals.p, K.tm.p, K.band.p,     \
+                               K.dinv.p, x, y, stop, K.t_in_lds ? 1 : 0);                                                                                      \
+        else                                                                                                                                                   \
+            hipLaunchKernelGGL((k_kron_spmv<QQ, false>), grid, block, lds, c->stream, K.n, K.q, K.ns, c->rowptr.p, c->colidx.p, K.vals.p, K.tm.p, K.band.p,    \
+                               (const double*)nullptr, x, y, stop, K.t_in_lds ? 1 : 0);                                                                        \
+        break;
+    switch (K.Q) {
+        FDAPDE_KRON_SPMV(2)
+        FDAPDE_KRON_SPMV(4)
+        FDAPDE_KRON_SPMV(8)
+        FDAPDE_KRON_SPMV(16)
+        FDAPDE_KRON_SPMV(32)
+        FDAPDE_KRON_SPMV(64)
+    }
+#undef FDAPDE_KRON_SPMV
+}
+
+// y_i = D_i^-1 x_i (y may be x)
+void launch_kron_dinv(fdapde_ctx* c, const KronHandle& K, const double* x, double* y, const int32_t* stop) {
+    const dim3 grid(g1(K.n, 256 / K.Q)), block(256);
+    switch (K.Q) {
+    case 2: hipLaunchKernelGGL(k_kron_dinv_apply<2>, grid, block, 0, c->stream, K.n, K.q, K.dinv.p, x, y, stop); break;
+    case 4: hipLaunchKernelGGL(k_kron_dinv_apply<4>, grid, block, 0, c->stream, K.n, K.q, K.dinv.p, x, y, stop); break;
+    case 8: hipLaunchKernelGGL(k_kron_dinv_apply<8>, grid, block, 0, c->stream, K.n, K.q, K.dinv.p, x, y, stop); break;
+    case 16: hipLaunchKernelGGL(k_kron_dinv_apply<16>, grid, block, 0, c->stream, K.n, K.q, K.dinv.p, x, y, stop); break;
+    case 32: hipLaunchKernelGGL(k_kron_dinv_apply<32>, grid, block, 0, c->stream, K.n, K.q, K.dinv.p, x, y, stop); break;
+    case 64: hipLaunchKernelGGL(k_kron_dinv_apply<64>, grid, block, 0, c->stream, K.n, K.q, K.dinv.p, x, y, stop); break;
+    }
+}
+
+void launch_kron_diag_inv(fdapde_ctx* c, KronHandle& K) {
+    const dim3 grid(g1(K.n, 64 / K.Q)), block(64);
+#define FDAPDE_KRON_DIAG(QQ)                                                                                                                                   \
+    case QQ:                                                                                                                                                   \
+        hipLaunchKernelGGL(k_kron_diag_inv<QQ>, grid, block, 0, c->stream, K.n, K.q, K.ns, c->rowptr.p, c->colidx.p, K.vals.p, K.tm.p, K.dinv.p, K.flag.p);    \
+        break;
+    switch (K.Q) {
+        FDAPDE_KRON_DIAG(2)
+        FDAPDE_KRON_DIAG(4)
+        FDAPDE_KRON_DIAG(8)
+        FDAPDE_KRON_DIAG(16)
+        FDAPDE_KRON_DIAG(32)
+        FDAPDE_KRON_DIAG(64)
+    }
+#undef FDAPDE_KRON_DIAG
+}
+
+// the Krylov stage's operator y = D^-1 A x: one launch with the inverse fused into the epilogue (knob kron_fuse = 1), or the product and the batched
+// q x q matvec as two
+void launch_kron_op(fdapde_ctx* c, const KronHandle& K, const double* x, double* y, const int32_t* stop) {
+    if (c->kron_fuse) {
+        launch_kron_spmv(c, K, true, x, y, stop);
+    } else {
+        launch_kron_spmv(c, K, false, x, y, stop);
+        launch_kron_dinv(c, K, y, y, stop);
+    }
+}
+
+// restarted GMRES(m) on D^-1 A z = D^-1 b for the column staged in K.bt: handle_gmres (eng_gmres.h) over q n words
+int kron_gmres(fdapde_ctx* c, KronHandle& K, double tol2, int maxit, int32_t h_ctl[4], double h_sc[4]) {
+    return handle_gmres(c, HandleGmresWork{K.bt, K.x, K.r, K.w, K.t, K.sc, K.gm_V, K.gm_s, K.gm_part, K.ctl}, (int64_t)K.q * K.n,
+                        [&](const double* x, double* y, const int32_t* stop) { launch_kron_op(c, K, x, y, stop); }, tol2, maxit, h_ctl, h_sc);
+}
+
+bool kron_dense_eligible(const fdapde_ctx* c, const KronHandle& K) {
+    const int64_t nq = (int64_t)K.q * K.n;
+    return c->dense_rows > 0 && nq <= c->dense_rows && nq <= kDenseMaxRows;
+}
+
+int kron_dense_build(fdapde_ctx* c, KronHandle& K) {
+    const int64_t nq = (int64_t)K.q * K.n, nnz2 = (int64_t)K.q * K.q * K.nnz;
+    if (!K.expanded) {
+        HIPCHK(c, K.rowptr2.alloc((size_t)(nq + 1)));
+        HIPCHK(c, K.colidx2.alloc((size_t)nnz2));
+        HIPCHK(c, K.val2.alloc((size_t)nnz2));
+        hipLaunchKernelGGL(k_kron_expand, dim3(g1(nq + 1)), dim3(256), 0, c->stream, K.n, K.q, K.ns, c->rowptr.p, c->colidx.p, K.vals.p, K.tm.p, K.rowptr2.p, K.colidx2.p,
+                           K.val2.p);
+        HIPCHK(c, hipGetLastError());
+        K.expanded = true;
+    }
+    return dense_build_csr(c, nq, K.rowptr2.p, K.colidx2.p, K.val2.p, nullptr, 0, K.dense);
+}
+
+}   // namespace
+
+int e_kron_compute(fdapde_ctx* c, int32_t q, int32_t n_terms, const double* const* T, const double* const* S, int32_t symmetric) {
+    if (!c) return FDAPDE_EINVAL;
+    if (int rc = kron_guard(c)) return rc;
+    if (q < 1 || q > kKronMaxQ) return fail(c, FDAPDE_EINVAL, "fdapde_kron_compute: q must lie in 1 .. 64");
+    if (n_terms < 1 || n_terms > kKronMaxTerms) return fail(c, FDAPDE_EINVAL, "fdapde_kron_compute: n_terms must lie in 1 .. 8");
+    if (!T || !S) return fail(c, FDAPDE_EINVAL, "fdapde_kron_compute: a NULL factor");
+    for (int k = 0; k < n_terms; ++k)
+        if (!T[k] || !S[k]) return fail(c, FDAPDE_EINVAL, "fdapde_kron_compute: a NULL factor");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const int64_t n = c->hs.n_dofs, nnz = c->hs.nnz, nq = (int64_t)q * n;
+    const double* s_of[kKronMaxTerms];
+    std::vector<double> tm((size_t)n_terms * q * q);
+    std::vector<int32_t> band(2 * (size_t)q);
+    const int ns = fdapde_hip::kron_merge_terms(q, n_terms, T, S, s_of, tm.data(), band.data());
+    if (!c->kron) c->kron = new KronHandle();
+    KronHandle& K = *c->kron;
+    if (K.q != q || K.ns != ns || K.n != n || K.nnz != nnz) {   // another shape: what was sized for the previous one goes (DBuf::alloc only grows -- 4 GB of D^-1 at q = 32 would stay)
+        HIPCHK(c, hipStreamSynchronize(st));
+        for (DBuf<double>* v : {&K.vals, &K.dinv, &K.ext, &K.bt, &K.x, &K.r, &K.w, &K.t, &K.gm_V, &K.val2, &K.dn_b, &K.dn_x, &K.dense.X}) v->release();
+        K.rowptr2.release(), K.colidx2.release();
+    }
+    K.ready = false, K.expanded = false, K.n = n, K.nnz = nnz, K.q = q, K.ns = ns, K.Q = team_width(q), K.symmetric = symmetric != 0;
+    K.dense.ready = K.dense.failed = false, K.cols = 0, K.krylov_ms = 0, K.jacobi_ok = false;
+    K.t_in_lds = ns * q * q <= kKronLdsFactorDoubles;
+    K.have_dinv = 8.0 * (double)q * (double)q * (double)n <= (double)c->kron_dinv_mb * 1048576.0;
+    HIPCHK(c, K.ext.alloc((size_t)std::max<int64_t>((int64_t)ns * nnz, nq)));
+    HIPCHK(c, K.vals.alloc((size_t)((int64_t)ns * nnz)));
+    HIPCHK(c, K.tm.upload(tm.data(), (size_t)ns * q * q, st));
+    HIPCHK(c, K.band.upload(band.data(), band.size(), st));
+    if (K.have_dinv) HIPCHK(c, K.dinv.alloc((size_t)q * q * (size_t)n));
+    else K.dinv.release();
+    HIPCHK(c, K.flag.alloc(1));
+    HIPCHK(c, K.ctl.alloc(8));
+    HIPCHK(c, K.sc.alloc(32));
+    for (DBuf<double>* v : {&K.bt, &K.x, &K.r, &K.w, &K.t}) HIPCHK(c, v->alloc((size_t)nq));
+    for (int sg = 0; sg < ns; ++sg) HIPCHK(c, hipMemcpyAsync(K.ext.p + (size_t)sg * nnz, s_of[sg], sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemsetAsync(K.flag.p, 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(k_kron_pack, dim3(g1(nnz * ns)), dim3(256), 0, st, nnz, ns, c->slot_i2e.p, K.ext.p, K.vals.p);
+    if (K.have_dinv) launch_kron_diag_inv(c, K);
+    HIPCHK(c, hipGetLastError());
+    int32_t h_flag = 0;
+    HIPCHK(c, hipMemcpyAsync(&h_flag, K.flag.p, sizeof h_flag, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));   // (the caller's factors and the host copies of the time factors have been read)
+    K.jacobi_ok = K.have_dinv && h_flag == 0;
+    K.ready = true;
+    return FDAPDE_OK;
+}
+
+int e_kron_spmv(fdapde_ctx* c, const double* x, double* y) {
+    if (!c || !x || !y) return FDAPDE_EINVAL;
+    if (int rc = kron_guard(c)) return rc;
+    if (!kron_live(c)) return fail(c, FDAPDE_ENOTINIT, kKronFirst);
+    HIPCHK(c, hipSetDevice(c->device));
+    KronHandle& K = *c->kron;
+    hipStream_t st = c->stream;
+    const int64_t n = K.n, nq = (int64_t)K.q * n;
+    HIPCHK(c, hipMemcpyAsync(K.ext.p, x, sizeof(double) * (size_t)nq, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_kron_stage, dim3(g1(nq), 1), dim3(256), 0, st, n, K.q, c->dof_i2e.p, K.ext.p, K.w.p, (int64_t)K.q, (int64_t)1);
+    launch_kron_spmv(c, K, false, K.w.p, K.t.p, nullptr);
+    hipLaunchKernelGGL(k_kron_unstage, dim3(g1(nq), 1), dim3(256), 0, st, n, K.q, c->dof_i2e.p, K.t.p, K.ext.p, (int64_t)K.q, (int64_t)1);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(y, K.ext.p, sizeof(double) * (size_t)nq, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    return FDAPDE_OK;
+}
+
+// times `reps` launches of the Krylov stage's operator (D^-1 A, fused or as two launches: knob kron_fuse; the plain product where D^-1 is not there) with
+// HIP events on the context's stream
+int e_kron_bench_spmv(fdapde_ctx* c, int32_t reps, double* avg_ms, double* algorithmic_bytes) {
+    if (!c || reps < 1) return FDAPDE_EINVAL;
+    if (int rc = kron_guard(c)) return rc;
+    if (!kron_live(c)) return fail(c, FDAPDE_ENOTINIT, kKronFirst);
+    HIPCHK(c, hipSetDevice(c->device));
+    KronHandle& K = *c->kron;
+    const int64_t n = K.n, nq = (int64_t)K.q * n;
+    auto op = [&]() {
+        if (K.have_dinv) launch_kron_op(c, K, K.w.p, K.t.p, nullptr);
+        else launch_kron_spmv(c, K, false, K.w.p, K.t.p, nullptr);
+    };
+    hipLaunchKernelGGL(k_fill_f64, dim3(g1(nq)), dim3(256), 0, c->stream, nq, 1.0, K.w.p);
+    for (int i = 0; i < 3; ++i) op();
+    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    for (int i = 0; i < reps; ++i) op();
+    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+    HIPCHK(c, hipEventSynchronize(c->ev1));
+    HIPCHK(c, hipGetLastError());
+    float ms = 0;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    if (avg_ms) *avg_ms = (double)ms / reps;
+    if (algorithmic_bytes)
+        *algorithmic_bytes = 8.0 * K.ns * (double)K.nnz + 4.0 * (double)K.nnz + 4.0 * (double)(n + 1) + 16.0 * (double)nq + (K.have_dinv ? 8.0 * K.q * (double)nq : 0.0);
+    return FDAPDE_OK;
+}
+
+int e_kron_solve(fdapde_ctx* c, const fdapde_options* opt, const double* b, int32_t n_rhs, double* x, fdapde_info* info) {
+    if (!c || !b || !x || n_rhs < 1) return FDAPDE_EINVAL;
+    if (int rc = kron_guard(c)) return rc;
+    if (!kron_live(c)) return fail(c, FDAPDE_ENOTINIT, kKronFirst);
+    HIPCHK(c, hipSetDevice(c->device));
+    KronHandle& K = *c->kron;
+    const int64_t n = K.n, nq = (int64_t)K.q * n;
+    {   // an in-place solve: finished columns are written to x while later ones still read b
+        const double *b0 = b, *b1 = b + (size_t)nq * n_rhs, *x0 = x, *x1 = x + (size_t)nq * n_rhs;
+        if (b0 < x1 && x0 < b1) {
+            std::vector<double> b_copy(b0, b1);
+            return e_kron_solve(c, opt, b_copy.data(), n_rhs, x, info);
+        }
+    }
+    hipStream_t st = c->stream;
+    const int method = opt ? opt->method : FDAPDE_SOLVER_AUTO;
+    const bool open = method == FDAPDE_SOLVER_AUTO, dense_named = method == FDAPDE_SOLVER_DENSE;
+    if (!open && !dense_named && method != FDAPDE_SOLVER_GMRES)
+        return fail(c, FDAPDE_EUNSUPPORTED, "fdapde_kron_solve runs FDAPDE_SOLVER_GMRES, FDAPDE_SOLVER_DENSE or the open method");
+    const double rtol = (opt && opt->rtol > 0) ? opt->rtol : 1e-10;
+    const int maxit = (opt && opt->maxit > 0) ? opt->maxit : 2000;
+    fdapde_info out{};
+    const auto t_call = std::chrono::steady_clock::now();
+    const bool eligible = kron_dense_eligible(c, K);
+    if (dense_named && !eligible) return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_DENSE takes Kronecker systems of up to `dense_rows` (at most 8192) rows");
+    if (method == FDAPDE_SOLVER_GMRES && !K.have_dinv)
+        return fail(c, FDAPDE_EUNSUPPORTED, "the inverted diagonal blocks (8 q^2 n bytes) exceed the budget `kron_dinv_mb`: no Krylov stage for this Kronecker handle");
+    if (method == FDAPDE_SOLVER_GMRES && !K.jacobi_ok) {
+        out.method_used = FDAPDE_SOLVER_GMRES;
+        c->info = out;
+        if (info) *info = out;
+        return fail(c, FDAPDE_ENOCONV, "a DOF's diagonal block is singular (a pivot <= 1e-14 max|entry|): no block-Jacobi form for the Krylov stage");
+    }
+    if (open && !eligible && !K.jacobi_ok)
+        return fail(c, FDAPDE_EUNSUPPORTED, K.have_dinv ? "a DOF's diagonal block is singular: no block-Jacobi form for the Krylov stage, and the system is too large for the dense inverse"
+                                                        : "the inverted diagonal blocks exceed the budget `kron_dinv_mb`, and the system is too large for the dense inverse");
+    HIPCHK(c, K.ext.alloc((size_t)std::max<int64_t>((int64_t)K.ns * K.nnz, nq)));
+    if ((open || dense_named) && eligible) {   // the rent-or-buy rule of fdapde_lin_solve, with q n as the row count
+        fdapde_ctx::Dense& D = K.dense;
+        if (!D.ready && (!D.failed || dense_named) &&
+            (dense_named || !K.jacobi_ok || c->dense_after == 0 || (K.cols + n_rhs > c->dense_after && K.krylov_ms >= 0.5 * dense_build_estimate_ms(nq))))
+            if (int rc = kron_dense_build(c, K)) return rc;
+        if ((dense_named || !K.jacobi_ok) && !D.ready) {
+            out.method_used = FDAPDE_SOLVER_DENSE, out.relres = D.check;
+            c->info = out;
+            if (info) *info = out;
+            c->err = "FDAPDE_SOLVER_DENSE: the Kronecker matrix is singular to working precision (no usable pivot, or max |I - A X| beyond 1e-6)";
+            return FDAPDE_ENOCONV;
+        }
+        if (D.ready) {
+            const size_t cnt = (size_t)nq * (size_t)n_rhs;
+            HIPCHK(c, K.dn_b.alloc(cnt));
+            HIPCHK(c, K.dn_x.alloc(cnt));
+            // the columns cross in slices of the staging buffer's size, every slice one product
+            const int per = (int)std::max<int64_t>(1, (int64_t)(K.ext.n / (size_t)nq));
+            for (int j0 = 0; j0 < n_rhs; j0 += per) {
+                const int nc = std::min(per, n_rhs - j0);
+                HIPCHK(c, hipMemcpyAsync(K.ext.p, b + (size_t)j0 * nq, sizeof(double) * (size_t)nq * nc, hipMemcpyHostToDevice, st));
+                hipLaunchKernelGGL(k_kron_stage, dim3(g1(nq), nc), dim3(256), 0, st, n, K.q, c->dof_i2e.p, K.ext.p, K.dn_b.p + (size_t)j0 * nq, (int64_t)1, n);
+            }
+            if (int rc = dense_apply(c, D, n_rhs, K.dn_b.p, K.dn_x.p)) return rc;
+            for (int j0 = 0; j0 < n_rhs; j0 += per) {
+                const int nc = std::min(per, n_rhs - j0);
+                hipLaunchKernelGGL(k_kron_unstage, dim3(g1(nq), nc), dim3(256), 0, st, n, K.q, c->dof_i2e.p, K.dn_x.p + (size_t)j0 * nq, K.ext.p, (int64_t)1, n);
+                HIPCHK(c, hipGetLastError());
+                HIPCHK(c, hipMemcpyAsync(x + (size_t)j0 * nq, K.ext.p, sizeof(double) * (size_t)nq * nc, hipMemcpyDeviceToHost, st));
+                HIPCHK(c, hipStreamSynchronize(st));
+            }
+            K.cols += n_rhs;
+            out.iters = D.refine ? 1 : 0, out.converged = 1, out.relres = D.check, out.method_used = FDAPDE_SOLVER_DENSE;
+            out.t_solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+            c->info = out;
+            if (info) *info = out;
+            return FDAPDE_OK;
+        }
+    }
+    // Krylov stage, the columns one after another
+    K.cols += n_rhs;
+    const double tol2 = rtol * rtol;
+    int total = 0, rc_all = FDAPDE_OK;
+    double worst = 0;
+    bool broke = false;
+    for (int32_t j = 0; j < n_rhs; ++j) {
+        HIPCHK(c, hipMemcpyAsync(K.ext.p, b + (size_t)j * nq, sizeof(double) * (size_t)nq, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_kron_stage, dim3(g1(nq), 1), dim3(256), 0, st, n, K.q, c->dof_i2e.p, K.ext.p, K.bt.p, (int64_t)K.q, (int64_t)1);
+        launch_kron_dinv(c, K, K.bt.p, K.bt.p, nullptr);
+        int32_t h_ctl[4] = {0, 0, 0, 0};
+        double h_sc[4] = {0, 0, 0, 0};
+        if (int rc = kron_gmres(c, K, tol2, maxit, h_ctl, h_sc)) return rc;
+        const double bb = h_sc[0], rr = h_sc[3];
+        const double rel = bb > 0 ? std::sqrt(rr / bb) : 0.0;
+        if (!(rr <= tol2 * bb && h_ctl[2] == 0)) rc_all = FDAPDE_ENOCONV, broke = broke || h_ctl[2] != 0;
+        total += h_ctl[1], worst = rel > worst ? rel : worst;
+        hipLaunchKernelGGL(k_kron_unstage, dim3(g1(nq), 1), dim3(256), 0, st, n, K.q, c->dof_i2e.p, K.x.p, K.ext.p, (int64_t)K.q, (int64_t)1);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(x + (size_t)j * nq, K.ext.p, sizeof(double) * (size_t)nq, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+    }
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+    K.krylov_ms += ms;
+    out.iters = total, out.relres = worst, out.converged = rc_all == FDAPDE_OK ? 1 : 0, out.method_used = FDAPDE_SOLVER_GMRES, out.t_solve_ms = ms;
+    c->info = out;
+    if (info) *info = out;
+    if (rc_all == FDAPDE_ENOCONV) c->err = broke ? "GMRES stagnated or broke down in at least one column" : "maxit reached in at least one column";
+    return rc_all;
+}
+
+}   // namespace fdapde_engine

@@ -309,6 +309,7 @@ int e_dofs_build(fdapde_ctx* c, int order, int64_t* n_dofs) {
     amg_release(c);
     c->matrix_dirty = true;
     block_release(c);   // (the 2 x 2 block handle belongs to the space it was computed on)
+    kron_release(c);    // (... and so does the Kronecker-sum handle)
     c->halo_ready = false, c->lin_ready = false, c->sp_built[0] = c->sp_built[1] = false, c->sp_cur = -1;
     release_rowdist(c);   // (keys / owners / layouts of the row-distributed form belong to the space that is being replaced)
     c->eval_grid.release();   // (the point-location grid of the mesh before)

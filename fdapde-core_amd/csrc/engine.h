@@ -225,6 +225,13 @@ int e_block_solve(fdapde_ctx* c, const fdapde_options* opt, const double* b, int
 int e_block_spmv(fdapde_ctx* c, const double* x, double* y);
 int e_block_bench_spmv(fdapde_ctx* c, int32_t reps, double* avg_ms, double* algorithmic_bytes);
 int e_gram_pointwise(fdapde_ctx* c, int64_t n_locs, const int32_t* cell_ids, const double* values, const double* weights, double* out_values);
+// eng_kron.hip: Kronecker-sum operators sum_k T_k (x) S_k, T_k dense q x q, S_k on the FEM pattern (the space-time systems' handle)
+void kron_release(fdapde_ctx* c);
+int e_kron_compute(fdapde_ctx* c, int32_t q, int32_t n_terms, const double* const* T, const double* const* S, int32_t symmetric);
+int e_kron_solve(fdapde_ctx* c, const fdapde_options* opt, const double* b, int32_t n_rhs, double* x, fdapde_info* info);
+int e_kron_spmv(fdapde_ctx* c, const double* x, double* y);
+int e_kron_bench_spmv(fdapde_ctx* c, int32_t reps, double* avg_ms, double* algorithmic_bytes);
+
 // eng_block_amg.hip: FDAPDE_SOLVER_BLOCK_AMG, the point-block multilevel preconditioner of the block handle -- the hierarchy of the unscaled block CSR
 // `raw` on the context's pattern (strength_block: which of a11 a12 a21 a22 the aggregation reads), and one column A x = b against it (b, x: interleaved,
 // internal order, device)

@@ -5,6 +5,8 @@
 //   SMW<SparseSolver>    Sherman-Morrison-Woodbury solve    fdaPDE/linear_algebra/smw.h:38-59
 //   SparseBlockMatrix<double,2,2>   four sparse blocks as one matrix   fdaPDE/linear_algebra/sparse_block_matrix.h:29-128
 //                        (what PDE::BlockSolver factors: SMW<PDE<...>::BlockSolver> solves the smoothing system under a low-rank update)
+//   Kronecker(T, S), KroneckerSum   lazy dense (x) sparse products and their sums   fdaPDE/linear_algebra/kronecker_product.h:56-80
+//                        (what PDE::KroneckerSolver factors without forming the product: the space-time systems; eval() gives the explicit matrix)
 // The heavy step of SMW, A^{-1} [b | U] (1 + q right-hand sides against one prepared sparse system), runs on the device as ONE
 // batched multi-column solve through the factor-once handle (PDE::SparseSolver -> fdapde_lin_compute / fdapde_lin_solve);
 // everything dense is q x q or n x q host work.
@@ -119,6 +121,98 @@ template <typename T> SpMatrix<T> zero_block(int64_t rows, int64_t cols) {
     z.n_rows = rows, z.n_cols = cols, z.rowptr.assign((size_t)rows + 1, 0);
     return z;
 }
+
+// ---- Kronecker(A, B) (kronecker_product.h:56-80) --------------------------------------------------------------------------------------------------
+// Kronecker(T, S), T dense q x q and S sparse n x n, is a LAZY expression: nothing is multiplied out.  Products add, subtract and scale to a KroneckerSum
+// sum_k T_k (x) S_k, which PDE::KroneckerSolver::compute() hands to the device factor by factor (fdapde_kron_compute); eval() gives the explicit sparse
+// matrix the reference's expression evaluates to (q n rows, entry (r n + i, s n + j) = sum_k T_k(r, s) S_k(i, j), sorted columns, entries of a term
+// whose T_k(r, s) is an exact zero not stored).  Every factor is copied into the expression.
+class KroneckerSum;
+class KroneckerProduct {
+   public:
+    KroneckerProduct(const DMatrix<double>& t, const SpMatrix<double>& s) : T(t), S(s) {
+        if (t.rows() != t.cols() || t.rows() < 1) throw std::runtime_error("Kronecker: the dense factor must be square");
+        if (s.rows() != s.cols()) throw std::runtime_error("Kronecker: the sparse factor must be square");
+    }
+    int64_t rows() const { return T.rows() * S.rows(); }
+    int64_t cols() const { return rows(); }
+    inline SpMatrix<double> eval() const;
+    DMatrix<double> T;
+    SpMatrix<double> S;
+};
+inline KroneckerProduct Kronecker(const DMatrix<double>& t, const SpMatrix<double>& s) { return KroneckerProduct(t, s); }
+// dense (x) dense, evaluated at once (host)
+inline DMatrix<double> Kronecker(const DMatrix<double>& a, const DMatrix<double>& b) {
+    DMatrix<double> c(a.rows() * b.rows(), a.cols() * b.cols());
+    for (int64_t ja = 0; ja < a.cols(); ++ja)
+        for (int64_t jb = 0; jb < b.cols(); ++jb)
+            for (int64_t ia = 0; ia < a.rows(); ++ia)
+                for (int64_t ib = 0; ib < b.rows(); ++ib) c(ia * b.rows() + ib, ja * b.cols() + jb) = a(ia, ja) * b(ib, jb);
+    return c;
+}
+
+class KroneckerSum {
+   public:
+    KroneckerSum() = default;
+    KroneckerSum(const KroneckerProduct& p) : terms_ {p} { }   // (a single product is a sum of one term)
+    const std::vector<KroneckerProduct>& terms() const { return terms_; }
+    int64_t time_size() const { return terms_.empty() ? 0 : terms_[0].T.rows(); }
+    int64_t space_size() const { return terms_.empty() ? 0 : terms_[0].S.rows(); }
+    int64_t rows() const { return time_size() * space_size(); }
+    int64_t cols() const { return rows(); }
+    KroneckerSum& operator+=(const KroneckerSum& o) {
+        if (&o == this) return *this += KroneckerSum(o);   // (a += a: the loop below would walk the vector it grows)
+        for (const KroneckerProduct& p : o.terms_) {
+            if (!terms_.empty() && (p.T.rows() != time_size() || p.S.rows() != space_size())) throw std::runtime_error("KroneckerSum: the terms' factors differ in size");
+            terms_.push_back(p);
+        }
+        return *this;
+    }
+    KroneckerSum& operator*=(double s) {
+        for (KroneckerProduct& p : terms_)
+            for (int64_t i = 0; i < p.T.size(); ++i) p.T.data()[i] *= s;
+        return *this;
+    }
+    // the explicit matrix
+    SpMatrix<double> eval() const {
+        const int64_t q = time_size(), n = space_size();
+        SpMatrix<double> a;
+        a.n_rows = a.n_cols = q * n;
+        a.rowptr.assign((size_t)(q * n) + 1, 0);
+        std::vector<std::pair<int32_t, double>> row;
+        for (int64_t r = 0; r < q; ++r)
+            for (int64_t i = 0; i < n; ++i) {
+                row.clear();
+                for (const KroneckerProduct& p : terms_)
+                    for (int64_t s = 0; s < q; ++s) {
+                        const double t = p.T(r, s);
+                        if (t == 0.0) continue;
+                        for (int32_t k = p.S.rowptr[(size_t)i]; k < p.S.rowptr[(size_t)i + 1]; ++k)
+                            row.emplace_back((int32_t)(s * n + p.S.colidx[(size_t)k]), t * p.S.values[(size_t)k]);
+                    }
+                std::stable_sort(row.begin(), row.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
+                for (size_t k = 0; k < row.size(); ++k) {
+                    if (k > 0 && row[k].first == row[k - 1].first) a.values.back() += row[k].second;   // (the terms in the order they were added)
+                    else a.colidx.push_back(row[k].first), a.values.push_back(row[k].second);
+                }
+                a.rowptr[(size_t)(r * n + i) + 1] = (int32_t)a.colidx.size();
+            }
+        return a;
+    }
+   private:
+    std::vector<KroneckerProduct> terms_;
+};
+inline SpMatrix<double> KroneckerProduct::eval() const { return KroneckerSum(*this).eval(); }
+inline KroneckerSum operator+(KroneckerSum a, const KroneckerSum& b) { return a += b; }
+inline KroneckerSum operator-(KroneckerSum a, KroneckerSum b) { return a += (b *= -1.0); }
+inline KroneckerSum operator*(double s, KroneckerSum a) { return a *= s; }
+inline KroneckerSum operator*(KroneckerSum a, double s) { return a *= s; }
+inline KroneckerSum operator-(KroneckerSum a) { return a *= -1.0; }
+inline KroneckerSum operator+(const KroneckerProduct& a, const KroneckerProduct& b) { return KroneckerSum(a) += KroneckerSum(b); }
+inline KroneckerSum operator-(const KroneckerProduct& a, const KroneckerProduct& b) { return KroneckerSum(a) += (KroneckerSum(b) *= -1.0); }
+inline KroneckerSum operator*(double s, const KroneckerProduct& a) { return KroneckerSum(a) *= s; }
+inline KroneckerSum operator*(const KroneckerProduct& a, double s) { return KroneckerSum(a) *= s; }
+inline KroneckerSum operator-(const KroneckerProduct& a) { return KroneckerSum(a) *= -1.0; }
 
 // ---- small dense LU with partial pivoting (the DenseSolver of SMW; q x q) ----------------------------------------------
 class PartialPivLU {

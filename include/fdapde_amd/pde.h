@@ -622,6 +622,76 @@ template <typename D, typename F, int R> class PDE<D, DifferentialExpr, F, FEM_H
     }
     bool owns_context_of(const BlockSolver& s) const { return s.ctx_.shared_with(ctx_); }
 
+    // "factor once, solve many" on a sum of Kronecker products sum_k T_k (x) S_k whose spatial factors lie on this PDE's pattern: fdapde::SparseLU on what
+    // the reference's Kronecker(A, B) evaluates to (linear_algebra/kronecker_product.h:56-80; KroneckerSum in include/fdapde_amd/linear_algebra.h) -- the
+    // space-time separable smoothing system and the monolithic parabolic system, kept as factors on the device (fdapde_kron_compute).  Right-hand sides and
+    // solutions in the reference's Kronecker order: index r n_dofs + i for T-row r and DOF i.  Terms with equal spatial values share one factor.  Context
+    // lifetime as SparseSolver.  solver_options().method names the stage: FDAPDE_SOLVER_GMRES, FDAPDE_SOLVER_DENSE (or left open).
+    class KroneckerSolver {
+       public:
+        // a: KroneckerSum -- a.terms()[k].T dense q x q, .S an SpMatrix<double> of n_dofs x n_dofs with entries on the pattern (a sub-pattern is filled up with zeros)
+        template <typename KronSum> void compute(const KronSum& a, bool symmetric = false) {
+            const auto& terms = a.terms();
+            if (terms.empty()) throw std::runtime_error("KroneckerSolver: a sum without terms");
+            q_ = a.time_size();
+            if (a.space_size() != n_) throw std::runtime_error("KroneckerSolver: every spatial factor must be n_dofs x n_dofs");
+            std::vector<std::vector<double>> hold(terms.size());
+            std::vector<const double*> tp(terms.size()), sp(terms.size());
+            for (size_t k = 0; k < terms.size(); ++k) {
+                tp[k] = terms[k].T.data();
+                sp[k] = on_pattern(terms[k].S, hold[k]);
+                for (size_t j = 0; j < k; ++j)   // equal values: one spatial factor (the engine merges terms whose pointers are equal)
+                    if (sp[j] != sp[k] && std::equal(sp[k], sp[k] + colidx_.size(), sp[j])) {
+                        sp[k] = sp[j];
+                        break;
+                    }
+            }
+            computed_ = fdapde_kron_compute(ctx_.get(), (int32_t)q_, (int32_t)terms.size(), tp.data(), sp.data(), symmetric ? 1 : 0) == FDAPDE_OK;
+        }
+        DMatrix<double> solve(const DMatrix<double>& b) const {
+            if (!computed_) throw std::runtime_error("KroneckerSolver: compute() first");
+            if (b.rows() != q_ * n_) throw std::runtime_error("KroneckerSolver: right-hand sides need q n_dofs rows");
+            DMatrix<double> x(b.rows(), b.cols());
+            const int rc = fdapde_kron_solve(ctx_.get(), &opt_, b.data(), (int32_t)b.cols(), x.data(), &info_);
+            if (rc != FDAPDE_OK) throw std::runtime_error(fdapde_last_error(ctx_.get()));
+            return x;
+        }
+        explicit operator bool() const { return computed_; }
+        fdapde_options& solver_options() { return opt_; }
+        const fdapde_info& info() const { return info_; }   // of the last solve(): iterations summed over the columns, the worst column's relres, the stage
+       private:
+        friend class PDE;
+        KroneckerSolver(fdapde::hip::context_handle ctx, int64_t n, std::vector<int32_t> rowptr, std::vector<int32_t> colidx) :
+            ctx_(std::move(ctx)), n_(n), rowptr_(std::move(rowptr)), colidx_(std::move(colidx)) { }
+        // values of `a` aligned with the PDE's pattern
+        const double* on_pattern(const SpMatrix<double>& a, std::vector<double>& hold) const {
+            if (a.rows() != n_ || a.cols() != n_) throw std::runtime_error("KroneckerSolver: every spatial factor must be n_dofs x n_dofs");
+            if (a.rowptr == rowptr_ && a.colidx == colidx_) return a.values.data();
+            hold.assign(colidx_.size(), 0.0);
+            for (int64_t i = 0; i < n_; ++i) {
+                int32_t k = rowptr_[(size_t)i];
+                for (int32_t t = a.rowptr[(size_t)i]; t < a.rowptr[(size_t)i + 1]; ++t) {
+                    while (k < rowptr_[(size_t)i + 1] && colidx_[(size_t)k] < a.colidx[(size_t)t]) ++k;
+                    if (k == rowptr_[(size_t)i + 1] || colidx_[(size_t)k] != a.colidx[(size_t)t])
+                        throw std::runtime_error("KroneckerSolver: a spatial factor has an entry off the FEM pattern");
+                    hold[(size_t)k] += a.values[(size_t)t];
+                }
+            }
+            return hold.data();
+        }
+        fdapde::hip::context_handle ctx_;
+        int64_t n_ = 0, q_ = 0;
+        std::vector<int32_t> rowptr_, colidx_;
+        bool computed_ = false;
+        fdapde_options opt_ {FDAPDE_SOLVER_AUTO, 0, 0.0, FDAPDE_ASSEMBLY_ROWS, 0, 0};
+        mutable fdapde_info info_ {};
+    };
+    KroneckerSolver make_kronecker_solver() {
+        ctx_.unique();   // (as make_solver)
+        return KroneckerSolver(ctx_.observer(), n_dofs_, stiff_.rowptr, stiff_.colidx);
+    }
+    bool owns_context_of(const KroneckerSolver& s) const { return s.ctx_.shared_with(ctx_); }
+
    private:
     // rows of (column, value) pairs -> CSR with sorted columns, duplicates summed like setFromTriplets
     void fill_csr(std::vector<std::vector<std::pair<int32_t, double>>>& rows, SpMatrix<double>& P) const {

@@ -331,6 +331,39 @@ int fdapde_block_spmv(fdapde_ctx *ctx, const double *x, double *y);
 int fdapde_block_bench_spmv(fdapde_ctx *ctx, int32_t reps, double *avg_ms, double *algorithmic_bytes);
 int fdapde_gram_pointwise(fdapde_ctx *ctx, int64_t n_locs, const int32_t *cell_ids, const double *values, const double *weights, double *out_values);
 
+/* ---- Kronecker-sum operators on the FEM pattern: A = sum_{k < n_terms} T_k (x) S_k -- the reference's Kronecker(A, B) (fdaPDE/linear_algebra/
+ *      kronecker_product.h:56-80), which it evaluates into an explicit sparse matrix and hands to SparseLU: every block of a space-time separable smoothing
+ *      system [ -(I_m (x) Psi^T Psi) - lambda_T (P_t (x) R0), lambda (M_t (x) R1^T) ; lambda (M_t (x) R1), lambda (M_t (x) R0) ] and of the monolithic parabolic
+ *      system.  Here the factors stay factors.  T_k: dense q x q, column-major, 1 <= q <= 64; S_k: n_dofs x n_dofs on the pattern, nnz values aligned with
+ *      fdapde_pattern_get; 1 <= n_terms <= 8.  Unknowns in the reference's Kronecker order: index r n_dofs + i for T-row r and DOF i (DOF ids).  The 2 x 2
+ *      structure of a space-time system (q = 2 m) is carried by the T_k: a21 = lambda M_t (x) R1 is [[0, 0], [lambda M_t, 0]] (x) R1; a transposed spatial
+ *      factor is handed over as a value array of its own (the pattern is structurally symmetric), as fdapde_block_compute takes a12 and a21.
+ * fdapde_kron_compute: T and S are arrays of n_terms pointers.  Terms whose S pointers are equal share one spatial factor (their T are summed on the host):
+ * the kernels see n_S <= 8 distinct factors, stored interleaved per pattern entry in the solver's internal DOF order, and vectors interleaved per DOF (unknown
+ * r of DOF i at i q + r).  D_i = sum T_sigma S_sigma[i, i], the q x q diagonal block of every DOF, is inverted once (Gauss-Jordan with partial pivoting): left
+ * point-block Jacobi for the Krylov stage.  A pivot not above 1e-14 times the block's largest entry (or not finite) makes the Krylov stage unavailable for that
+ * matrix.  D^-1 takes 8 q^2 n_dofs bytes; above the budget "kron_dinv_mb" (fdapde_tune, default 2048 MiB, read by fdapde_kron_compute) it is not built and the
+ * Krylov stage is unavailable as well.  `symmetric` is recorded only.  The call replaces a previous Kronecker handle of the context; the handle is independent
+ * of fdapde_lin_compute's and fdapde_block_compute's (all three may be live).  Needs fdapde_dofs_build (FDAPDE_ENOTINIT); q or n_terms out of range, a NULL
+ * pointer: FDAPDE_EINVAL; a rank of a multi-GPU job and a multi-device context: FDAPDE_EUNSUPPORTED.  fdapde_ctx_clone does NOT carry the handle (it carries the two knobs)
+ * (fdapde_kron_solve on a clone: FDAPDE_ENOTINIT), as it does not carry the block handle; fdapde_dofs_build drops it.
+ * fdapde_kron_solve: b and x column-major q n_dofs x n_rhs in the order above; x may overlap b; columns one after another.  FDAPDE_SOLVER_GMRES: restarted
+ * GMRES(gmres_m = 50) on D^-1 A, stop rule |D^-1 (b - A x)| <= rtol |D^-1 b| on the true residual at the end of a cycle (rtol <= 0: 1e-10; maxit <= 0: 2000);
+ * FDAPDE_EUNSUPPORTED where D^-1 exceeds the budget, FDAPDE_ENOCONV (nothing written to x) where a diagonal block is singular.  FDAPDE_SOLVER_DENSE:
+ * q n_dofs <= dense_rows (8192): the factors are expanded to an explicit CSR matrix and inverted, built in the call, all columns in one product; above the limit
+ * FDAPDE_EUNSUPPORTED, a singular matrix FDAPDE_ENOCONV.  FDAPDE_SOLVER_AUTO: GMRES, and the rent-or-buy rule of fdapde_lin_solve with q n_dofs as the row
+ * count (at once where the Krylov stage is unavailable; FDAPDE_EUNSUPPORTED where neither stage can run).  Every other method: FDAPDE_EUNSUPPORTED.  info as
+ * fdapde_block_solve: iters summed over the columns, relres the worst column's, method_used the stage; FDAPDE_ENOCONV from an exhausted budget leaves the last
+ * iterate of every column in x.
+ * fdapde_kron_spmv: y = A x, host vectors of q n_dofs in the order above.  The same bits every run (no atomics, fixed summation order).
+ * fdapde_kron_bench_spmv: times `reps` applications of the Krylov stage's operator D^-1 A with HIP events (k_kron_spmv with D^-1 fused into its epilogue, or
+ * followed by k_kron_dinv_apply: fdapde_tune "kron_fuse"; the plain product where D^-1 was not built); algorithmic bytes per application
+ * 8 n_S nnz + 4 nnz + 4 (n + 1) + 16 q n, plus the 8 q^2 n of D^-1. */
+int fdapde_kron_compute(fdapde_ctx *ctx, int32_t q, int32_t n_terms, const double *const *T, const double *const *S, int32_t symmetric);
+int fdapde_kron_solve(fdapde_ctx *ctx, const fdapde_options *opt, const double *b, int32_t n_rhs, double *x, fdapde_info *info);
+int fdapde_kron_spmv(fdapde_ctx *ctx, const double *x, double *y);
+int fdapde_kron_bench_spmv(fdapde_ctx *ctx, int32_t reps, double *avg_ms, double *algorithmic_bytes);
+
 /* ---- basis evaluation (PDE__::eval_basis, pde/pde.h:149-158; policies basis/lagrangian_basis.h:203-283) -------------------
  * fdapde_eval_pointwise: for each location (column-major n_locs x N) the containing cell (reference cell id, -1 if outside;
  * TreeSearch::locate, geometry/tree_search.h:73-90) and the n_basis values psi_h(invJ (p - x0)), row-major n_locs x n_basis.
@@ -529,7 +562,9 @@ int fdapde_partition_peers(fdapde_ctx *ctx, int32_t rank, int32_t *n_peers, int3
  *                 another value drops the live hierarchies), "amg_cols" (the widest batch of columns fdapde_lin_solve under FDAPDE_SOLVER_AMG and
  *                 fdapde_block_solve under FDAPDE_SOLVER_BLOCK_AMG solve side by side -- n_rhs columns go in batches of 8, then 4, then 2, a last one
  *                 alone; every column's iterates are those of a column-by-column run, bit for bit --: 1, 2, 4 or 8; 8.  1 = column by column.  The
- *                 hierarchy stays) */
+ *                 hierarchy stays)
+ *   Kronecker     "kron_dinv_mb" (the MiB the inverted diagonal blocks of the Kronecker handle may take, >= 0; 2048; read by the next fdapde_kron_compute),
+ *                 "kron_fuse" (1, the default: D^-1 applied in the epilogue of the operator kernel; 0: by a batched q x q matvec kernel of its own) */
 int fdapde_tune(fdapde_ctx *ctx, const char *key, int32_t value);
 /* The live hierarchy of a multilevel solver as data.  which: 0 = fdapde_solve's (FDAPDE_SOLVER_AMG; fdapde_solve_parabolic builds its own per call and
  * drops it when it returns), 1 = the factor-once handle's, 2 = the 2 x 2 block handle's (FDAPDE_SOLVER_BLOCK_AMG).  *n_levels: its levels, the last one the
