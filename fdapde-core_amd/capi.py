@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("FDAPDE_HIP_LIB") or os.path.join(_HERE, "lib", "libfd
 OK, EINVAL, ENOMEM, ENODEVICE, EHIP, ENOTINIT, ENOCONV, EUNSUPPORTED, ERCCL = range(9)
 LAPLACIAN, DIFFUSION, ADVECTION, REACTION, DT = range(5)
 SOLVER_AUTO, SOLVER_CG, SOLVER_BICGSTAB, SOLVER_CG_SR, SOLVER_CG_FUSED, SOLVER_GMRES, SOLVER_DENSE, SOLVER_PMG, SOLVER_AMG, SOLVER_BLOCK_AMG = range(10)
+SOLVER_KRON_AMG = 10
 ASSEMBLY_ROWS, ASSEMBLY_ATOMIC, ASSEMBLY_COLOURED, ASSEMBLY_PARTITIONED, ASSEMBLY_WAVE = range(5)
 MAT_STIFF, MAT_MASS = 0, 1
 
@@ -52,6 +53,7 @@ SYMBOLS = [
     "fdapde_partition_peers",
     "fdapde_block_compute", "fdapde_block_solve", "fdapde_block_spmv", "fdapde_block_bench_spmv", "fdapde_gram_pointwise",
     "fdapde_kron_compute", "fdapde_kron_solve", "fdapde_kron_spmv", "fdapde_kron_bench_spmv",
+    "fdapde_kron_amg_hierarchy", "fdapde_kron_amg_aggregates",
     "fdapde_amg_hierarchy", "fdapde_amg_aggregates", "fdapde_amg_order", "fdapde_amg_damping", "fdapde_amg_cols_trace",
 ]
 AMG_OF_SOLVE, AMG_OF_HANDLE, AMG_OF_BLOCK = 0, 1, 2   # `which` of fdapde_amg_hierarchy
@@ -534,6 +536,27 @@ class Context:
         ms, by = C.c_double(), C.c_double()
         self._check(self.lib.fdapde_kron_bench_spmv(self._ctx, reps, C.byref(ms), C.byref(by)))
         return ms.value, by.value
+
+    def kron_amg_hierarchy(self):
+        """fdapde_kron_amg_hierarchy: the live hierarchy of FDAPDE_SOLVER_KRON_AMG (rows counted as q n_l, entries as q^2 nnz_l) ->
+        dict(rows, nnz: per level, the last level the inverted one; absorbed; setup_ms).  FdapdeError(ENOTINIT) where none is live"""
+        nl, ab, ms = C.c_int32(), C.c_int32(), C.c_double()
+        self._check(self.lib.fdapde_kron_amg_hierarchy(self._ctx, 0, C.byref(nl), None, None, None, None))
+        rows, nnz = np.zeros(nl.value, dtype=np.int64), np.zeros(nl.value, dtype=np.int64)
+        self._check(self.lib.fdapde_kron_amg_hierarchy(self._ctx, nl.value, C.byref(nl), rows.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                       nnz.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(ab), C.byref(ms)))
+        return dict(rows=[int(r) for r in rows], nnz=[int(z) for z in nnz], absorbed=ab.value, setup_ms=ms.value)
+
+    def kron_amg_aggregates(self, level):
+        """fdapde_kron_amg_aggregates: for a level of the live hierarchy that has a next one, the DOF of level + 1 every DOF of `level` belongs to (level 0
+        in the reference DOF numbering) -> int32 array.  FdapdeError(ENOTINIT) where no hierarchy is live"""
+        n = C.c_int64(0)
+        rc = self.lib.fdapde_kron_amg_aggregates(self._ctx, int(level), C.c_int64(0), None, C.byref(n))
+        if rc != EINVAL or n.value <= 0:   # (a valid level answers EINVAL to the empty buffer and leaves its row count)
+            self._check(rc)
+        agg = np.full(n.value, -1, dtype=np.int32)
+        self._check(self.lib.fdapde_kron_amg_aggregates(self._ctx, int(level), C.c_int64(agg.size), _ip(agg), C.byref(n)))
+        return agg
 
     def gram_pointwise(self, cell_ids, values, weights=None):
         """Psi^T W Psi on the FEM pattern (nnz values aligned with pattern_get()) from cell ids and row-major n_locs x n_basis values"""

@@ -283,9 +283,11 @@ int fdapde_solver_trace(fdapde_ctx* c, int32_t* small_front, int32_t* graph_repl
     return FDAPDE_OK;
 }
 static const char* const kBlockAmgOnly = "FDAPDE_SOLVER_BLOCK_AMG is a method of fdapde_block_solve (the 2 x 2 block handle) only";
+static const char* const kKronAmgOnly = "FDAPDE_SOLVER_KRON_AMG is a method of fdapde_kron_solve (the Kronecker-sum handle) only";
 int fdapde_solve(fdapde_ctx* c, const fdapde_options* opt, fdapde_info* info) {
     if (!c) return FDAPDE_EINVAL;
     if (opt && opt->method == FDAPDE_SOLVER_BLOCK_AMG) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, kBlockAmgOnly);
+    if (opt && opt->method == FDAPDE_SOLVER_KRON_AMG) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, kKronAmgOnly);
     if (c->group && opt && opt->method == FDAPDE_SOLVER_AMG) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_AMG takes one-GPU contexts, not a multi-device context");
     if (c->group) return fdapde_engine::g_solve(c, opt, info);
     return fdapde_engine::e_solve(c, opt, info);
@@ -293,6 +295,7 @@ int fdapde_solve(fdapde_ctx* c, const fdapde_options* opt, fdapde_info* info) {
 int fdapde_solve_parabolic(fdapde_ctx* c, const fdapde_options* opt, int32_t n_times, double delta_t, const double* initial_condition, const double* dirichlet, double* solution, fdapde_info* info) {
     if (!c) return FDAPDE_EINVAL;
     if (opt && opt->method == FDAPDE_SOLVER_BLOCK_AMG) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, kBlockAmgOnly);
+    if (opt && opt->method == FDAPDE_SOLVER_KRON_AMG) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, kKronAmgOnly);
     if (c->group && opt && opt->method == FDAPDE_SOLVER_AMG) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_AMG takes one-GPU contexts, not a multi-device context");
     if (c->group) return fdapde_engine::g_solve_parabolic(c, opt, n_times, delta_t, initial_condition, dirichlet, solution, info);
     return fdapde_engine::e_solve_parabolic(c, opt, n_times, delta_t, initial_condition, dirichlet, solution, info);
@@ -305,6 +308,7 @@ int fdapde_lin_compute(fdapde_ctx* c, int32_t which, const double* values, int32
 int fdapde_lin_solve(fdapde_ctx* c, const fdapde_options* opt, const double* b, int32_t n_rhs, double* x, fdapde_info* info) {
     if (!c) return FDAPDE_EINVAL;
     if (opt && opt->method == FDAPDE_SOLVER_BLOCK_AMG) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, kBlockAmgOnly);
+    if (opt && opt->method == FDAPDE_SOLVER_KRON_AMG) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, kKronAmgOnly);
     if (c->group && opt && opt->method == FDAPDE_SOLVER_AMG) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_AMG takes one-GPU contexts, not a multi-device context");
     if (c->group) return fdapde_engine::g_lin_solve(c, opt, b, n_rhs, x, info);
     return fdapde_engine::e_lin_solve(c, opt, b, n_rhs, x, info);
@@ -318,6 +322,7 @@ int fdapde_block_compute(fdapde_ctx* c, const double* a11, const double* a12, co
 }
 int fdapde_block_solve(fdapde_ctx* c, const fdapde_options* opt, const double* b, int32_t n_rhs, double* x, fdapde_info* info) {
     if (!c) return FDAPDE_EINVAL;
+    if (opt && opt->method == FDAPDE_SOLVER_KRON_AMG) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, kKronAmgOnly);
     if (c->group) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, kBlockNoGroup);
     return fdapde_engine::e_block_solve(c, opt, b, n_rhs, x, info);
 }
@@ -352,6 +357,21 @@ int fdapde_kron_bench_spmv(fdapde_ctx* c, int32_t reps, double* avg_ms, double* 
     if (!c) return FDAPDE_EINVAL;
     if (c->group) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, kKronNoGroup);
     return fdapde_engine::e_kron_bench_spmv(c, reps, avg_ms, algorithmic_bytes);
+}
+// the Kronecker handle's live hierarchy as data: amg_describe / amg_aggregates on it
+int fdapde_kron_amg_hierarchy(fdapde_ctx* c, int32_t cap, int32_t* n_levels, int64_t* rows, int64_t* nnz, int32_t* absorbed, double* setup_ms) {
+    if (!c || cap < 0 || (cap > 0 && !rows && !nnz)) return FDAPDE_EINVAL;
+    const int rc = fdapde_engine::kron_amg_describe_ctx(c, cap, n_levels, rows, nnz, absorbed, setup_ms);
+    if (rc == FDAPDE_ENOTINIT) return fdapde_engine::fail(c, rc, "fdapde_kron_amg_hierarchy: no hierarchy is live (it is built by the first fdapde_kron_solve that names FDAPDE_SOLVER_KRON_AMG)");
+    return rc;
+}
+int fdapde_kron_amg_aggregates(fdapde_ctx* c, int32_t level, int64_t cap, int32_t* agg, int64_t* n_rows) {
+    if (!c) return FDAPDE_EINVAL;
+    if (c->group) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, kKronNoGroup);
+    const int rc = fdapde_engine::kron_amg_aggregates_ctx(c, level, cap, agg, n_rows);
+    if (rc == FDAPDE_ENOTINIT) return fdapde_engine::fail(c, rc, "fdapde_kron_amg_aggregates: no hierarchy is live (it is built by the first fdapde_kron_solve that names FDAPDE_SOLVER_KRON_AMG)");
+    if (rc == FDAPDE_EINVAL) return fdapde_engine::fail(c, rc, "fdapde_kron_amg_aggregates: `level` must have a next level, and `agg` room for the level's rows (`cap`)");
+    return rc;
 }
 int fdapde_gram_pointwise(fdapde_ctx* c, int64_t n_locs, const int32_t* cell_ids, const double* values, const double* weights, double* out_values) {
     if (!c) return FDAPDE_EINVAL;
@@ -563,8 +583,12 @@ int fdapde_tune(fdapde_ctx* c, const char* key, int32_t value) {
     else if (k == "amg_cols" && (value == 1 || value == 2 || value == 4 || value == 8)) c->amg_cols = value;
     else if (k == "kron_dinv_mb" && value >= 0) c->kron_dinv_mb = value;   // (read by the next fdapde_kron_compute)
     else if (k == "kron_fuse" && (value == 0 || value == 1)) c->kron_fuse = value;
+    else if (k == "kron_amg_term" && value >= -1 && value < 8) {   // read by the build of the hierarchy: a live one goes
+        if (value != c->kron_amg_term) fdapde_engine::kron_amg_forget(c);
+        c->kron_amg_term = value;
+    }
     else if (k == "amg_absorb" && value >= 0 && value <= 2) {   // the hierarchies are built again by the next solve that needs one
-        if (value != c->amg_absorb) fdapde_engine::amg_release(c), fdapde_engine::block_amg_forget(c);
+        if (value != c->amg_absorb) fdapde_engine::amg_release(c), fdapde_engine::block_amg_forget(c), fdapde_engine::kron_amg_forget(c);
         c->amg_absorb = value;
     }
     else if (k == "pmg_restart" && value >= 2 && value <= 50) c->pmg_restart = (int)value;

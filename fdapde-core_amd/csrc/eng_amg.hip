@@ -122,6 +122,17 @@ __global__ void k_bamg_gsum(int64_t m, const uint64_t* keys, const int32_t* idx,
     double* o = bv_c + 4 * (int64_t)pos[e];
     o[0] = s0, o[1] = s1, o[2] = s2, o[3] = s3;
 }
+// ... and a payload of any other width (the Kronecker form's n_S spatial values per entry): one thread per coarse entry and component, the same order
+__global__ void k_amg_gsum_pay(int64_t m, int width, const uint64_t* keys, const int32_t* idx, const int32_t* head, const int32_t* pos, const double* pay, double* pay_c) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t e = t / width;
+    if (e >= m || !head[e]) return;
+    const int s = (int)(t - e * width);
+    const uint64_t key = keys[e];
+    double sum = 0.0;
+    for (int64_t q = e; q < m && keys[q] == key; ++q) sum += pay[(int64_t)width * idx[q] + s];
+    pay_c[(int64_t)width * pos[e] + s] = sum;
+}
 // members of every aggregate, ascending: keys agg(i) (nc for none), sorted stably with the row index
 __global__ void k_amg_mkeys(int64_t n, const int32_t* agg, uint32_t nc, uint32_t* keys, int32_t* idx) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -457,10 +468,10 @@ inline int key_bits(uint64_t v) {
 }
 
 // the Galerkin product P^T A P of piecewise-constant P (agg) on the device: a stable key sort, a segmented sum in ascending fine-slot order.  pay (or
-// NULL): the block form's four doubles per entry, summed per coarse entry over the same sorted slots into pay_c
+// NULL): `width` doubles per entry (the block form's four, the Kronecker form's n_S), summed per coarse entry over the same sorted slots into pay_c
 int dev_galerkin(fdapde_ctx* c, int64_t n, int64_t nnz, const int32_t* rp, const int32_t* ci, const double* a, const int32_t* agg, int32_t nc, AmgLevel& out,
                  const double* pay, int width, DBuf<double>* pay_c) {
-    if (pay && width != 4) return fail(c, FDAPDE_EINVAL, "dev_galerkin: the device sums payloads of four doubles per entry only");
+    if (pay && width < 1) return fail(c, FDAPDE_EINVAL, "dev_galerkin: a payload of no width");
     hipStream_t st = c->stream;
     const dim3 bv(256);
     const uint64_t ncu = (uint64_t)nc, sentinel = ncu * ncu;
@@ -490,10 +501,11 @@ int dev_galerkin(fdapde_ctx* c, int64_t n, int64_t nnz, const int32_t* rp, const
     HIPCHK(c, out.rp_own.alloc((size_t)nc + 1));
     HIPCHK(c, out.ci_own.alloc((size_t)std::max(nnz_c, 1)));
     HIPCHK(c, out.a_own.alloc((size_t)std::max(nnz_c, 1) + 2));
-    if (pay) HIPCHK(c, pay_c->alloc(4 * (size_t)std::max(nnz_c, 1)));
+    if (pay) HIPCHK(c, pay_c->alloc((size_t)width * (size_t)std::max(nnz_c, 1)));
     HIPCHK(c, hipMemcpyAsync(out.rp_own.p + nc, &nnz_c, sizeof(int32_t), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_amg_gsum, dim3(gn(nnz)), bv, 0, st, nnz, keys_s.p, idx_s.p, a, head.p, pos.p, ncu, out.rp_own.p, out.ci_own.p, out.a_own.p);
-    if (pay) hipLaunchKernelGGL(k_bamg_gsum, dim3(gn(nnz)), bv, 0, st, nnz, keys_s.p, idx_s.p, head.p, pos.p, pay, pay_c->p);
+    if (pay && width == 4) hipLaunchKernelGGL(k_bamg_gsum, dim3(gn(nnz)), bv, 0, st, nnz, keys_s.p, idx_s.p, head.p, pos.p, pay, pay_c->p);
+    else if (pay) hipLaunchKernelGGL(k_amg_gsum_pay, dim3(gn(nnz * width)), bv, 0, st, nnz, width, keys_s.p, idx_s.p, head.p, pos.p, pay, pay_c->p);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(st));   // (nnz_c is this frame's; the scratch goes out of scope)
     out.rp = out.rp_own.p, out.ci = out.ci_own.p, out.a = out.a_own.p;

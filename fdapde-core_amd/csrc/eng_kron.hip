@@ -2,7 +2,8 @@
 // Kronecker(A, B), fdaPDE/linear_algebra/kronecker_product.h:56-80, evaluated into an explicit sparse matrix and handed to SparseLU there): the space-time
 // separable smoothing system and the monolithic parabolic system, kept as factors (kernels_kron.h).
 //   fdapde_kron_compute      terms -> n_S distinct spatial factors interleaved per pattern entry in the internal order, the summed time factors, D_i^-1
-//   fdapde_kron_solve        restarted GMRES(m) on D^-1 A (kernels_gmres.h, buffers of the handle's own), or the dense inverse of the q n-row matrix
+//   fdapde_kron_solve        restarted GMRES(m) on D^-1 A (kernels_gmres.h, buffers of the handle's own), or the dense inverse of the q n-row matrix, or
+//                            (by name) flexible GMRES around the point-block multilevel cycle of eng_kron_amg.hip
 //   fdapde_kron_spmv         y = A x
 //   fdapde_kron_bench_spmv   HIP-event timing of the Krylov stage's operator
 // Independent of the n x n handle of fdapde_lin_compute and of the 2 x 2 block handle: nothing here writes a buffer one of the other solves reads back.
@@ -40,6 +41,10 @@ struct KronHandle {
     fdapde_ctx::Dense dense;
     int64_t cols = 0;                  // columns solved against the current matrix
     double krylov_ms = 0;              // ... and the host time the Krylov columns among them took
+    int n_terms = 0, term_sg[kKronMaxTerms] = {};   // the spatial factor every term of the caller's went into
+    double tnorm[kKronMaxTerms] = {};  // |T_sigma|_F of the summed time factors (entries in storage order)
+    KronAmg* amg = nullptr;            // FDAPDE_SOLVER_KRON_AMG's hierarchy of the current matrix (eng_kron_amg.hip), built by its first solve
+    ~KronHandle() { kron_amg_free(amg); }
 };
 
 void kron_release(fdapde_ctx* c) {
@@ -50,6 +55,21 @@ void kron_release(fdapde_ctx* c) {
     }
     delete c->kron;
     c->kron = nullptr;
+}
+
+void kron_amg_forget(fdapde_ctx* c) {
+    if (!c->kron || !c->kron->amg) return;
+    if (c->has_device) {
+        (void)hipSetDevice(c->device);
+        (void)hipStreamSynchronize(c->stream);
+    }
+    kron_amg_free(c->kron->amg), c->kron->amg = nullptr;
+}
+int kron_amg_describe_ctx(const fdapde_ctx* c, int32_t cap, int32_t* n_levels, int64_t* rows, int64_t* nnz, int32_t* absorbed, double* setup_ms) {
+    return kron_amg_describe(c->kron ? c->kron->amg : nullptr, cap, n_levels, rows, nnz, absorbed, setup_ms);
+}
+int kron_amg_aggregates_ctx(fdapde_ctx* c, int32_t level, int64_t cap, int32_t* agg, int64_t* n_rows) {
+    return kron_amg_aggregates(c, c->kron ? c->kron->amg : nullptr, level, cap, agg, n_rows);
 }
 
 namespace {
@@ -161,6 +181,56 @@ int kron_dense_build(fdapde_ctx* c, KronHandle& K) {
     return dense_build_csr(c, nq, K.rowptr2.p, K.colidx2.p, K.val2.p, nullptr, 0, K.dense);
 }
 
+// FDAPDE_SOLVER_KRON_AMG by name: the hierarchy built by the first such solve after fdapde_kron_compute, the columns one after another on the UNSCALED
+// system (stop rule: the true residual |b - A x| <= rtol |b| -- not the D^-1-scaled one of the GMRES stage)
+int kron_amg_solve(fdapde_ctx* c, KronHandle& K, const fdapde_options* opt, const double* b, int32_t n_rhs, double* x, fdapde_info* info) {
+    const int64_t n = K.n, nq = (int64_t)K.q * n;
+    hipStream_t st = c->stream;
+    const double rtol = (opt && opt->rtol > 0) ? opt->rtol : 1e-10;
+    const int maxit = (opt && opt->maxit > 0) ? opt->maxit : 200;
+    fdapde_info out{};
+    out.method_used = FDAPDE_SOLVER_KRON_AMG;
+    const auto t_call = std::chrono::steady_clock::now();
+    if (!K.have_dinv)
+        return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_KRON_AMG: the inverted diagonal blocks (8 q^2 n bytes) exceed the budget `kron_dinv_mb`: no block-Jacobi smoother");
+    if (!K.jacobi_ok)
+        return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_KRON_AMG: a DOF's diagonal block is singular (a pivot <= 1e-14 max|entry|): no block-Jacobi smoother");
+    if (!K.amg) {
+        if (c->kron_amg_term >= K.n_terms) return fail(c, FDAPDE_EINVAL, "FDAPDE_SOLVER_KRON_AMG: the knob `kron_amg_term` names a term the handle was not given");
+        KronAmgSource src{K.q, K.ns, K.Q, K.t_in_lds, K.vals.p, K.tm.p, K.dinv.p, K.band.p, {}, c->kron_amg_term < 0 ? -1 : K.term_sg[c->kron_amg_term]};
+        std::copy(K.tnorm, K.tnorm + kKronMaxTerms, src.tnorm);
+        if (int rc = kron_amg_build(c, &K.amg, src)) {
+            c->info = out;
+            if (info) *info = out;
+            return rc;
+        }
+    }
+    HIPCHK(c, K.ext.alloc((size_t)std::max<int64_t>((int64_t)K.ns * K.nnz, nq)));
+    int total = 0, rc_all = FDAPDE_OK;   // (K.cols and K.krylov_ms stay: the open method's rent-or-buy rule counts its own columns only)
+    double worst = 0;
+    bool broke_any = false;
+    for (int32_t j = 0; j < n_rhs; ++j) {
+        HIPCHK(c, hipMemcpyAsync(K.ext.p, b + (size_t)j * nq, sizeof(double) * (size_t)nq, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_kron_stage, dim3(g1(nq), 1), dim3(256), 0, st, n, K.q, c->dof_i2e.p, K.ext.p, K.bt.p, (int64_t)K.q, (int64_t)1);
+        int it = 0;
+        double rel = 0;
+        bool conv = false, broke = false;
+        if (int rc = kron_amg_run(c, K.amg, K.bt.p, K.x.p, rtol, maxit, &it, &rel, &conv, &broke)) return rc;
+        if (!conv) rc_all = FDAPDE_ENOCONV, broke_any = broke_any || broke;
+        total += it, worst = rel > worst || std::isnan(rel) ? rel : worst;
+        hipLaunchKernelGGL(k_kron_unstage, dim3(g1(nq), 1), dim3(256), 0, st, n, K.q, c->dof_i2e.p, K.x.p, K.ext.p, (int64_t)K.q, (int64_t)1);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(x + (size_t)j * nq, K.ext.p, sizeof(double) * (size_t)nq, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+    }
+    out.iters = total, out.relres = worst, out.converged = rc_all == FDAPDE_OK ? 1 : 0, out.persistent = 0;
+    out.t_solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+    c->info = out;
+    if (info) *info = out;
+    if (rc_all == FDAPDE_ENOCONV) c->err = broke_any ? "FDAPDE_SOLVER_KRON_AMG: the flexible GMRES broke down in at least one column" : "FDAPDE_SOLVER_KRON_AMG: maxit reached in at least one column";
+    return rc_all;
+}
+
 }   // namespace
 
 int e_kron_compute(fdapde_ctx* c, int32_t q, int32_t n_terms, const double* const* T, const double* const* S, int32_t symmetric) {
@@ -180,6 +250,22 @@ int e_kron_compute(fdapde_ctx* c, int32_t q, int32_t n_terms, const double* cons
     const int ns = fdapde_hip::kron_merge_terms(q, n_terms, T, S, s_of, tm.data(), band.data());
     if (!c->kron) c->kron = new KronHandle();
     KronHandle& K = *c->kron;
+    if (K.amg) {   // (the hierarchy belonged to the previous matrix)
+        HIPCHK(c, hipStreamSynchronize(st));
+        kron_amg_free(K.amg), K.amg = nullptr;
+    }
+    K.n_terms = n_terms;
+    for (int k = 0; k < n_terms; ++k) {
+        int sg = 0;
+        while (s_of[sg] != S[k]) ++sg;
+        K.term_sg[k] = sg;
+    }
+    for (int sg = 0; sg < kKronMaxTerms; ++sg) {
+        double s2 = 0.0;
+        if (sg < ns)
+            for (int e = 0; e < q * q; ++e) s2 += tm[(size_t)sg * q * q + e] * tm[(size_t)sg * q * q + e];
+        K.tnorm[sg] = std::sqrt(s2);
+    }
     if (K.q != q || K.ns != ns || K.n != n || K.nnz != nnz) {   // another shape: what was sized for the previous one goes (DBuf::alloc only grows -- 4 GB of D^-1 at q = 32 would stay)
         HIPCHK(c, hipStreamSynchronize(st));
         for (DBuf<double>* v : {&K.vals, &K.dinv, &K.ext, &K.bt, &K.x, &K.r, &K.w, &K.t, &K.gm_V, &K.val2, &K.dn_b, &K.dn_x, &K.dense.X}) v->release();
@@ -275,8 +361,9 @@ int e_kron_solve(fdapde_ctx* c, const fdapde_options* opt, const double* b, int3
     hipStream_t st = c->stream;
     const int method = opt ? opt->method : FDAPDE_SOLVER_AUTO;
     const bool open = method == FDAPDE_SOLVER_AUTO, dense_named = method == FDAPDE_SOLVER_DENSE;
+    if (method == FDAPDE_SOLVER_KRON_AMG) return kron_amg_solve(c, K, opt, b, n_rhs, x, info);
     if (!open && !dense_named && method != FDAPDE_SOLVER_GMRES)
-        return fail(c, FDAPDE_EUNSUPPORTED, "fdapde_kron_solve runs FDAPDE_SOLVER_GMRES, FDAPDE_SOLVER_DENSE or the open method");
+        return fail(c, FDAPDE_EUNSUPPORTED, "fdapde_kron_solve runs FDAPDE_SOLVER_GMRES, FDAPDE_SOLVER_DENSE, FDAPDE_SOLVER_KRON_AMG or the open method");
     const double rtol = (opt && opt->rtol > 0) ? opt->rtol : 1e-10;
     const int maxit = (opt && opt->maxit > 0) ? opt->maxit : 2000;
     fdapde_info out{};

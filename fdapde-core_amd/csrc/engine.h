@@ -231,6 +231,27 @@ int e_kron_compute(fdapde_ctx* c, int32_t q, int32_t n_terms, const double* cons
 int e_kron_solve(fdapde_ctx* c, const fdapde_options* opt, const double* b, int32_t n_rhs, double* x, fdapde_info* info);
 int e_kron_spmv(fdapde_ctx* c, const double* x, double* y);
 int e_kron_bench_spmv(fdapde_ctx* c, int32_t reps, double* avg_ms, double* algorithmic_bytes);
+void kron_amg_forget(fdapde_ctx* c);   // the Kronecker handle's hierarchy is built again by its next solve (a set-up knob changed)
+int kron_amg_describe_ctx(const fdapde_ctx* c, int32_t cap, int32_t* n_levels, int64_t* rows, int64_t* nnz, int32_t* absorbed, double* setup_ms);
+int kron_amg_aggregates_ctx(fdapde_ctx* c, int32_t level, int64_t cap, int32_t* agg, int64_t* n_rows);
+
+// eng_kron_amg.hip: FDAPDE_SOLVER_KRON_AMG, the point-block multilevel preconditioner of the Kronecker-sum handle -- the hierarchy of the handle's factors
+// on the context's pattern (src: the handle's device arrays, tnorm the Frobenius norms of its time factors, pick the spatial factor the aggregation reads or
+// -1 for the weighted sum of magnitudes), and one column A x = b against it (b, x: interleaved, internal order, device)
+struct KronAmg;
+struct KronAmgSource {
+    int q, ns, Q;
+    bool t_in_lds;
+    const double *vals, *tm, *dinv;
+    const int32_t* band;
+    double tnorm[8];
+    int pick;
+};
+void kron_amg_free(KronAmg* h);
+int kron_amg_build(fdapde_ctx* c, KronAmg** slot, const KronAmgSource& src);
+int kron_amg_describe(const KronAmg* h, int32_t cap, int32_t* n_levels, int64_t* rows, int64_t* nnz, int32_t* absorbed, double* setup_ms);   // rows: q n_l
+int kron_amg_aggregates(fdapde_ctx* c, const KronAmg* h, int32_t level, int64_t cap, int32_t* agg, int64_t* n_rows);
+int kron_amg_run(fdapde_ctx* c, KronAmg* h, const double* b_dev, double* x_dev, double rtol, int maxit, int* iters, double* relres, bool* converged, bool* broke);
 
 // eng_block_amg.hip: FDAPDE_SOLVER_BLOCK_AMG, the point-block multilevel preconditioner of the block handle -- the hierarchy of the unscaled block CSR
 // `raw` on the context's pattern (strength_block: which of a11 a12 a21 a22 the aggregation reads), and one column A x = b against it (b, x: interleaved,

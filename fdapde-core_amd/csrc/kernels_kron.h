@@ -262,5 +262,221 @@ static __global__ void k_kron_expand(int64_t n, int q, int ns, const int32_t* ro
         }
 }
 
+// ... and in the interleaved order the vectors use (row i q + r, column j q + s): what the multilevel cycle's coarsest level is inverted from.  The same
+// entry sums; a row's columns ascend (entry outer, s inner).
+static __global__ void k_kron_expand_il(int64_t n, int q, int ns, const int32_t* rowptr, const int32_t* colidx, const double* vals, const double* tm, int32_t* rowptr2,
+                                        int32_t* colidx2, double* val2) {
+#pragma clang fp contract(off)
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t > n * q) return;
+    if (t == n * q) {
+        rowptr2[t] = (int32_t)((int64_t)rowptr[n] * q * q);
+        return;
+    }
+    const int64_t i = t / q, r = t - i * q;
+    const int32_t k0 = rowptr[i], len = rowptr[i + 1] - k0;
+    int64_t o = (int64_t)k0 * q * q + r * (int64_t)len * q;
+    rowptr2[t] = (int32_t)o;
+    for (int32_t k = k0; k < k0 + len; ++k)
+        for (int s = 0; s < q; ++s, ++o) {
+            double v = 0.0;
+            for (int sg = 0; sg < ns; ++sg) v = __builtin_fma(tm[((size_t)sg * q + s) * q + r], vals[(int64_t)k * ns + sg], v);
+            colidx2[o] = (int32_t)((int64_t)colidx[k] * q + s), val2[o] = v;
+        }
+}
+
+// ---- the multilevel cycle of FDAPDE_SOLVER_KRON_AMG (eng_kron_amg.hip): the cycle kernels of kernels_block.h carried to q unknowns per DOF ------------
+// A level is a Kronecker sum on its own pattern (rp / ci / n_S values per entry, the SAME time factors on every level), the inverted q x q diagonal blocks
+// (k_kron_diag_inv on the level's arrays) and vectors interleaved per DOF; the smoother is om D^-1.  The access pattern is k_kron_spmv's: a team of Q lanes
+// per row, lane l owns T-row l, the epilogue through LDS with the band skip, lanes l >= q and teams past the last row issue no global load or store.  One
+// column (the cycle op of the same name at Q = 1 columns).  Contraction off, every sum in a fixed order.
+
+// the scalar strength matrix on the pattern: s_k = -sum_sigma w_sigma |S_sigma[k]| (w_sigma = |T_sigma|_F, sigma ascending; every coupling counts as an
+// M-matrix coupling by its magnitude), or -- pick >= 0 -- the spatial factor `pick` as given
+static __global__ void k_kamg_strength(int64_t nnz, int ns, const double* vals, const double* w, int pick, double* out) {
+#pragma clang fp contract(off)
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nnz) return;
+    if (pick >= 0) {
+        out[k] = vals[k * ns + pick];
+        return;
+    }
+    double s = 0.0;
+    for (int sg = 0; sg < ns; ++sg) s = __builtin_fma(w[sg], fabs(vals[k * ns + sg]), s);
+    out[k] = -s;
+}
+
+// LDS doubles of the cycle kernels: 256 n_S for the z_sigma of every team, 256 for a row's residual, n_S q^2 for the time factors where they are copied
+__host__ __device__ inline size_t kamg_lds_doubles(int q, int ns, bool t_in_lds) { return (size_t)256 * (size_t)ns + 256 + (t_in_lds ? (size_t)ns * q * q : 0); }
+
+// the spatial half of a row's product: zt[sigma Q + l] = sum_j S_sigma[row, j] v_j[l], entries ascending, v_j[l] = ld(j) (every lane writes: idle ones zeros)
+template <int Q, typename LD>
+__device__ __forceinline__ void kamg_row(bool act, int64_t row, int l, int ns, const int32_t* rp, const int32_t* ci, const double* vals, LD&& ld, double* zt) {
+#pragma clang fp contract(off)
+    double z[kKronMaxTerms];
+#pragma unroll
+    for (int s = 0; s < kKronMaxTerms; ++s) z[s] = 0.0;
+    if (act) {
+        const int rs = rp[row], re = rp[row + 1];
+        int k = rs;
+        for (; k + 4 <= re; k += 4) {   // (k_kron_spmv's: four gathers in flight, the additions in entry order)
+            int32_t cj[4];
+            double xv[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) cj[u] = ci[k + u];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) xv[u] = ld((int64_t)cj[u]);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const double* v = vals + (int64_t)(k + u) * ns;
+#pragma unroll
+                for (int s = 0; s < kKronMaxTerms; ++s)
+                    if (s < ns) z[s] = __builtin_fma(v[s], xv[u], z[s]);
+            }
+        }
+        for (; k < re; ++k) {
+            const double xv = ld((int64_t)ci[k]);
+            const double* v = vals + (int64_t)k * ns;
+#pragma unroll
+            for (int s = 0; s < kKronMaxTerms; ++s)
+                if (s < ns) z[s] = __builtin_fma(v[s], xv, z[s]);
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < kKronMaxTerms; ++s)
+        if (s < ns) zt[s * Q + l] = z[s];
+}
+// ... and the time half (after a barrier): sum_sigma sum_s T_sigma[l, s] z_sigma[s], sigma outer, s ascending within the band, one fma each
+template <int Q> __device__ __forceinline__ double kamg_time(int l, int q, int ns, const double* tt, const int32_t* band, const double* zt) {
+#pragma clang fp contract(off)
+    const int lo = band[2 * l], hi = band[2 * l + 1];
+    double acc = 0.0;
+    for (int sg = 0; sg < ns; ++sg) {
+#pragma unroll 4
+        for (int s = lo; s <= hi; ++s) acc = __builtin_fma(tt[((size_t)sg * q + s) * q + l], zt[sg * Q + s], acc);
+    }
+    return acc;
+}
+
+// pre-smoothing from zero: zt_i = om D_i^-1 r_i (k_kron_dinv_apply's sum, scaled)
+template <int Q>
+static __global__ __launch_bounds__(256) void k_kamg_smooth(int64_t n, int q, const double* dinv, double om, const double* r, double* zt) {
+#pragma clang fp contract(off)
+    __shared__ double xs[256];
+    const int l = threadIdx.x % Q, team = threadIdx.x / Q;
+    const int64_t row = (int64_t)blockIdx.x * (256 / Q) + team;
+    const bool act = l < q && row < n;
+    xs[threadIdx.x] = act ? r[row * q + l] : 0.0;
+    __syncthreads();
+    if (!act) return;
+    const double* d = dinv + (size_t)row * q * q;
+    double o = 0.0;
+#pragma unroll 8
+    for (int s = 0; s < q; ++s) o = __builtin_fma(d[(size_t)s * q + l], xs[team * Q + s], o);
+    zt[row * q + l] = om * o;
+}
+
+// the restricted residual of the smoothed zt, a team per aggregate: rc_a = sum over its members i, ascending, of (r_i - (A zt)_i); unknown l of aggregate a at
+// rc[(a q + l) rs] (one column: interleaved and column-major coincide).  The member loop runs to the workgroup's longest aggregate (a barrier per member row).
+template <int Q>
+static __global__ __launch_bounds__(256) void k_kamg_pre_restrict(int64_t nc, int q, int ns, const int32_t* mptr, const int32_t* midx, const int32_t* rp, const int32_t* ci,
+                                                                  const double* vals, const double* tm, const int32_t* band, const double* r, const double* zt,
+                                                                  double* rc, int64_t rs, int t_in_lds) {
+#pragma clang fp contract(off)
+    extern __shared__ double kron_lds[];
+    constexpr int TEAMS = 256 / Q;
+    const int l = threadIdx.x % Q, team = threadIdx.x / Q;
+    const int64_t ag = (int64_t)blockIdx.x * TEAMS + team;
+    const bool lane_ok = l < q, ag_ok = lane_ok && ag < nc;
+    double* zl = kron_lds + (size_t)team * ns * Q;
+    double* tl = kron_lds + 256 * ns + 256;
+    if (t_in_lds)
+        for (int t = threadIdx.x; t < ns * q * q; t += 256) tl[t] = tm[t];
+    const double* tt = t_in_lds ? tl : tm;
+    const int32_t m1 = ag_ok ? mptr[ag + 1] : 0;
+    int32_t m = ag_ok ? mptr[ag] : 0;
+    double c = 0.0;
+    for (; __syncthreads_or(m < m1); ++m) {
+        const bool act = m < m1;   // (ag_ok: else m1 = 0)
+        const int64_t i = act ? midx[m] : 0;
+        kamg_row<Q>(act, i, l, ns, rp, ci, vals, [&](int64_t j) { return zt[j * q + l]; }, zl);
+        __syncthreads();
+        if (act) c += r[i * q + l] - kamg_time<Q>(l, q, ns, tt, band, zl);
+    }
+    if (ag_ok) rc[(ag * q + l) * rs] = c;
+}
+
+// out_i = z_i + om D_i^-1 (r_i - (A z)_i) with z = zt + P e: prolongation (every row has an aggregate), residual and post-smoothing in one pass
+template <int Q>
+static __global__ __launch_bounds__(256) void k_kamg_post(int64_t n, int q, int ns, const int32_t* rp, const int32_t* ci, const double* vals, const double* tm,
+                                                          const int32_t* band, const double* dinv, double om, const int32_t* agg, const double* e, const double* r,
+                                                          const double* zt, double* out, int t_in_lds) {
+#pragma clang fp contract(off)
+    extern __shared__ double kron_lds[];
+    constexpr int TEAMS = 256 / Q;
+    const int l = threadIdx.x % Q, team = threadIdx.x / Q;
+    const int64_t row = (int64_t)blockIdx.x * TEAMS + team;
+    const bool act = l < q && row < n;
+    double* zl = kron_lds + (size_t)team * ns * Q;
+    double* ys = kron_lds + 256 * ns;
+    double* tl = ys + 256;
+    if (t_in_lds)
+        for (int t = threadIdx.x; t < ns * q * q; t += 256) tl[t] = tm[t];
+    kamg_row<Q>(act, row, l, ns, rp, ci, vals, [&](int64_t j) { return zt[j * q + l] + e[(int64_t)agg[j] * q + l]; }, zl);
+    __syncthreads();
+    double zi = 0.0, d = 0.0;
+    if (act) {
+        zi = zt[row * q + l] + e[(int64_t)agg[row] * q + l];
+        d = r[row * q + l] - kamg_time<Q>(l, q, ns, t_in_lds ? tl : tm, band, zl);
+    }
+    ys[team * Q + l] = d;
+    __syncthreads();
+    if (!act) return;
+    const double* di = dinv + (size_t)row * q * q;
+    double o = 0.0;
+#pragma unroll 8
+    for (int s = 0; s < q; ++s) o = __builtin_fma(di[(size_t)s * q + l], ys[team * Q + s], o);
+    out[row * q + l] = __builtin_fma(om, o, zi);
+}
+
+// y = A x and the three dot products p_d . q_d of a GCR step (any of the vectors may be y itself; p2 may be NULL: a zero) as per-workgroup partials
+// part[d gridDim.x + block]: a fixed grid, the workgroup strides over the rows, a lane sums its own unknown's products, then the wavefronts' sums in order
+template <int Q>
+static __global__ __launch_bounds__(256) void k_kamg_spmv_dots(int64_t n, int q, int ns, const int32_t* rp, const int32_t* ci, const double* vals, const double* tm,
+                                                               const int32_t* band, const double* x, double* y, const double* p0, const double* q0, const double* p1,
+                                                               const double* q1, const double* p2, const double* q2, double* part, int t_in_lds) {
+#pragma clang fp contract(off)
+    extern __shared__ double kron_lds[];
+    __shared__ double red[3][4];
+    constexpr int TEAMS = 256 / Q;
+    const int l = threadIdx.x % Q, team = threadIdx.x / Q;
+    double* zl = kron_lds + (size_t)team * ns * Q;
+    double* tl = kron_lds + 256 * ns + 256;
+    if (t_in_lds)
+        for (int t = threadIdx.x; t < ns * q * q; t += 256) tl[t] = tm[t];
+    const double* tt = t_in_lds ? tl : tm;
+    double d0 = 0.0, d1 = 0.0, d2 = 0.0;
+    for (int64_t base = (int64_t)blockIdx.x * TEAMS; base < n; base += (int64_t)gridDim.x * TEAMS) {   // (the same trips for every lane of the workgroup)
+        const int64_t row = base + team;
+        const bool act = l < q && row < n;
+        kamg_row<Q>(act, row, l, ns, rp, ci, vals, [&](int64_t j) { return x[j * q + l]; }, zl);
+        __syncthreads();
+        if (act) {
+            const int64_t w = row * q + l;
+            const double yi = kamg_time<Q>(l, q, ns, tt, band, zl);
+            y[w] = yi;
+            d0 += (p0 == y ? yi : p0[w]) * (q0 == y ? yi : q0[w]);
+            d1 += (p1 == y ? yi : p1[w]) * (q1 == y ? yi : q1[w]);
+            if (p2) d2 += (p2 == y ? yi : p2[w]) * (q2 == y ? yi : q2[w]);
+        }
+        __syncthreads();
+    }
+    const int wv = threadIdx.x >> 6;
+    const double t0 = wave_sum(d0), t1 = wave_sum(d1), t2 = wave_sum(d2);
+    if ((threadIdx.x & 63) == 0) red[0][wv] = t0, red[1][wv] = t1, red[2][wv] = t2;
+    __syncthreads();
+    if (threadIdx.x < 3) part[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
+}
+
 }  // namespace fdapde_hip
 #endif

@@ -626,7 +626,8 @@ template <typename D, typename F, int R> class PDE<D, DifferentialExpr, F, FEM_H
     // the reference's Kronecker(A, B) evaluates to (linear_algebra/kronecker_product.h:56-80; KroneckerSum in include/fdapde_amd/linear_algebra.h) -- the
     // space-time separable smoothing system and the monolithic parabolic system, kept as factors on the device (fdapde_kron_compute).  Right-hand sides and
     // solutions in the reference's Kronecker order: index r n_dofs + i for T-row r and DOF i.  Terms with equal spatial values share one factor.  Context
-    // lifetime as SparseSolver.  solver_options().method names the stage: FDAPDE_SOLVER_GMRES, FDAPDE_SOLVER_DENSE (or left open).
+    // lifetime as SparseSolver.  solver_options().method names the stage: FDAPDE_SOLVER_GMRES, FDAPDE_SOLVER_DENSE, FDAPDE_SOLVER_KRON_AMG
+    // (the point-block multilevel preconditioner; by name only), or is left open.
     class KroneckerSolver {
        public:
         // a: KroneckerSum -- a.terms()[k].T dense q x q, .S an SpMatrix<double> of n_dofs x n_dofs with entries on the pattern (a sub-pattern is filled up with zeros)

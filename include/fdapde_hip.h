@@ -121,7 +121,24 @@ enum { FDAPDE_SOLVER_AUTO = 0, FDAPDE_SOLVER_CG = 1, FDAPDE_SOLVER_BICGSTAB = 2,
                                 relative residual, info.persistent = 0; FDAPDE_ENOCONV leaves the last iterate of every column, and is also the answer to
                                 a singular coarsest level; a singular diagonal block of a DOF (the 1e-14 rule of fdapde_block_compute) and coarsening
                                 that stalls above the dense limit with absorption too (or with `amg_absorb` 0) are FDAPDE_EUNSUPPORTED.  Taken by name only: the open method never chooses it.
-                                Order-2 spaces in 3-D are allowed, but pairwise matching serves them poorly (no iteration count is claimed). */ };
+                                Order-2 spaces in 3-D are allowed, but pairwise matching serves them poorly (no iteration count is claimed). */,
+       FDAPDE_SOLVER_KRON_AMG = 10 /* fdapde_kron_solve only (fdapde_solve, fdapde_solve_parabolic, fdapde_lin_solve and fdapde_block_solve answer
+                                FDAPDE_EUNSUPPORTED): flexible GMRES(gmres_m, at most 64) on the UNSCALED Kronecker-sum system, right-preconditioned by the
+                                multilevel cycle of FDAPDE_SOLVER_BLOCK_AMG on POINT-BLOCK unknowns -- the q unknowns of a DOF stay together on every level.
+                                With P = P_scalar (x) I_q every level is again a Kronecker sum with the SAME time factors and n_S spatial values per coarse
+                                entry.  Aggregates from double pairwise matching (knob `amg_absorb` as for FDAPDE_SOLVER_AMG) on a scalar strength matrix on
+                                the pattern: -sum_sigma |T_sigma|_F |S_sigma[i,j]| by default, or -- knob `kron_amg_term` = k -- the spatial factor of the
+                                caller's term k as given.  Galerkin sums in a fixed order (the same bits every run), smoother 0.7 D^-1 with D the q x q
+                                diagonal blocks of every level, two GCR steps per coarse level always, the last level -- at most `amg_coarse_rows` rows counted
+                                as q n_l, or where coarsening stalls at no more than `dense_rows` -- inverted once.  The hierarchy is built by the first such
+                                solve after fdapde_kron_compute and kept until the next one, fdapde_dofs_build, or a change of `amg_absorb` or `kron_amg_term`.
+                                Stop rule: |b - A x| <= rtol |b| on the true residual -- NOT the D^-1-scaled rule of the handle's FDAPDE_SOLVER_GMRES stage.
+                                rtol 1e-10 and maxit 200 by default; columns one after another, info.iters summed over them, info.relres the worst column's
+                                true relative residual, info.persistent = 0; FDAPDE_ENOCONV leaves the last iterate of every column, and is also the answer
+                                to a singular coarsest level.  FDAPDE_EUNSUPPORTED: D^-1 of the handle was not built or the D^-1 of all levels together exceed
+                                `kron_dinv_mb`, a singular diagonal block of a DOF (the 1e-14 rule of fdapde_kron_compute), coarsening that stalls above the
+                                dense limit with absorption too (or with `amg_absorb` 0).  `kron_amg_term` at or beyond the handle's n_terms: FDAPDE_EINVAL.
+                                Taken by name only: the open method never chooses it. */ };
 /* ROWS: row-owner sweep (default; no atomics, bitwise reproducible).  The others are element-wise scatter forms kept as measured
  * alternatives and cross-checks: ATOMIC / COLOURED = lane per (cell, row) with a slot search, fp64 atomics / one launch per colour;
  * PARTITIONED = one workgroup per cell partition, colours walked inside the workgroup, atomics only on rows shared between
@@ -345,24 +362,30 @@ int fdapde_gram_pointwise(fdapde_ctx *ctx, int64_t n_locs, const int32_t *cell_i
  * matrix.  D^-1 takes 8 q^2 n_dofs bytes; above the budget "kron_dinv_mb" (fdapde_tune, default 2048 MiB, read by fdapde_kron_compute) it is not built and the
  * Krylov stage is unavailable as well.  `symmetric` is recorded only.  The call replaces a previous Kronecker handle of the context; the handle is independent
  * of fdapde_lin_compute's and fdapde_block_compute's (all three may be live).  Needs fdapde_dofs_build (FDAPDE_ENOTINIT); q or n_terms out of range, a NULL
- * pointer: FDAPDE_EINVAL; a rank of a multi-GPU job and a multi-device context: FDAPDE_EUNSUPPORTED.  fdapde_ctx_clone does NOT carry the handle (it carries the two knobs)
+ * pointer: FDAPDE_EINVAL; a rank of a multi-GPU job and a multi-device context: FDAPDE_EUNSUPPORTED.  fdapde_ctx_clone does NOT carry the handle (it carries the knobs)
  * (fdapde_kron_solve on a clone: FDAPDE_ENOTINIT), as it does not carry the block handle; fdapde_dofs_build drops it.
  * fdapde_kron_solve: b and x column-major q n_dofs x n_rhs in the order above; x may overlap b; columns one after another.  FDAPDE_SOLVER_GMRES: restarted
  * GMRES(gmres_m = 50) on D^-1 A, stop rule |D^-1 (b - A x)| <= rtol |D^-1 b| on the true residual at the end of a cycle (rtol <= 0: 1e-10; maxit <= 0: 2000);
  * FDAPDE_EUNSUPPORTED where D^-1 exceeds the budget, FDAPDE_ENOCONV (nothing written to x) where a diagonal block is singular.  FDAPDE_SOLVER_DENSE:
  * q n_dofs <= dense_rows (8192): the factors are expanded to an explicit CSR matrix and inverted, built in the call, all columns in one product; above the limit
  * FDAPDE_EUNSUPPORTED, a singular matrix FDAPDE_ENOCONV.  FDAPDE_SOLVER_AUTO: GMRES, and the rent-or-buy rule of fdapde_lin_solve with q n_dofs as the row
- * count (at once where the Krylov stage is unavailable; FDAPDE_EUNSUPPORTED where neither stage can run).  Every other method: FDAPDE_EUNSUPPORTED.  info as
+ * count (at once where the Krylov stage is unavailable; FDAPDE_EUNSUPPORTED where neither stage can run).  FDAPDE_SOLVER_KRON_AMG (by name only): flexible
+ * GMRES on the unscaled system around a point-block multilevel cycle, see the enum.  Every other method: FDAPDE_EUNSUPPORTED.  info as
  * fdapde_block_solve: iters summed over the columns, relres the worst column's, method_used the stage; FDAPDE_ENOCONV from an exhausted budget leaves the last
  * iterate of every column in x.
  * fdapde_kron_spmv: y = A x, host vectors of q n_dofs in the order above.  The same bits every run (no atomics, fixed summation order).
  * fdapde_kron_bench_spmv: times `reps` applications of the Krylov stage's operator D^-1 A with HIP events (k_kron_spmv with D^-1 fused into its epilogue, or
  * followed by k_kron_dinv_apply: fdapde_tune "kron_fuse"; the plain product where D^-1 was not built); algorithmic bytes per application
- * 8 n_S nnz + 4 nnz + 4 (n + 1) + 16 q n, plus the 8 q^2 n of D^-1. */
+ * 8 n_S nnz + 4 nnz + 4 (n + 1) + 16 q n, plus the 8 q^2 n of D^-1.
+ * fdapde_kron_amg_hierarchy / fdapde_kron_amg_aggregates: the live hierarchy of FDAPDE_SOLVER_KRON_AMG as data, as fdapde_amg_hierarchy /
+ * fdapde_amg_aggregates hand out the other solvers': rows[l] = q n_l and nnz[l] = q^2 nnz_l (counted as scalars); agg[i] = the DOF of level + 1 that DOF i of
+ * `level` belongs to, *n_rows = the level's DOFs (rows[level] / q), level 0 in the reference DOF numbering.  FDAPDE_ENOTINIT where no hierarchy is live. */
 int fdapde_kron_compute(fdapde_ctx *ctx, int32_t q, int32_t n_terms, const double *const *T, const double *const *S, int32_t symmetric);
 int fdapde_kron_solve(fdapde_ctx *ctx, const fdapde_options *opt, const double *b, int32_t n_rhs, double *x, fdapde_info *info);
 int fdapde_kron_spmv(fdapde_ctx *ctx, const double *x, double *y);
 int fdapde_kron_bench_spmv(fdapde_ctx *ctx, int32_t reps, double *avg_ms, double *algorithmic_bytes);
+int fdapde_kron_amg_hierarchy(fdapde_ctx *ctx, int32_t cap, int32_t *n_levels, int64_t *rows, int64_t *nnz, int32_t *absorbed, double *setup_ms);
+int fdapde_kron_amg_aggregates(fdapde_ctx *ctx, int32_t level, int64_t cap, int32_t *agg, int64_t *n_rows);
 
 /* ---- basis evaluation (PDE__::eval_basis, pde/pde.h:149-158; policies basis/lagrangian_basis.h:203-283) -------------------
  * fdapde_eval_pointwise: for each location (column-major n_locs x N) the containing cell (reference cell id, -1 if outside;
@@ -564,7 +587,9 @@ int fdapde_partition_peers(fdapde_ctx *ctx, int32_t rank, int32_t *n_peers, int3
  *                 alone; every column's iterates are those of a column-by-column run, bit for bit --: 1, 2, 4 or 8; 8.  1 = column by column.  The
  *                 hierarchy stays)
  *   Kronecker     "kron_dinv_mb" (the MiB the inverted diagonal blocks of the Kronecker handle may take, >= 0; 2048; read by the next fdapde_kron_compute),
- *                 "kron_fuse" (1, the default: D^-1 applied in the epilogue of the operator kernel; 0: by a batched q x q matvec kernel of its own) */
+ *                 "kron_fuse" (1, the default: D^-1 applied in the epilogue of the operator kernel; 0: by a batched q x q matvec kernel of its own),
+ *                 "kron_amg_term" (FDAPDE_SOLVER_KRON_AMG aggregates on the spatial factor of that term of fdapde_kron_compute as given, 0 .. 7; -1, the
+ *                 default: on the weighted sum of the factors' magnitudes; read by the build of the hierarchy, setting another value drops a live one) */
 int fdapde_tune(fdapde_ctx *ctx, const char *key, int32_t value);
 /* The live hierarchy of a multilevel solver as data.  which: 0 = fdapde_solve's (FDAPDE_SOLVER_AMG; fdapde_solve_parabolic builds its own per call and
  * drops it when it returns), 1 = the factor-once handle's, 2 = the 2 x 2 block handle's (FDAPDE_SOLVER_BLOCK_AMG).  *n_levels: its levels, the last one the

@@ -13,7 +13,16 @@ distinct spatial factors) on a 2-D P1 mesh of about 0.5 M DOFs (unit_square(708)
 
 D^-1 takes 8 q^2 n bytes: 4.1 GB at q = 32 on the 2-D mesh, above the default budget (kron_dinv_mb = 2048), which this tool raises to 8192 and says so.
 
-usage: kron_time.py [OUT]      (OUT defaults to profiles/kron_time.txt)"""
+usage: kron_time.py [OUT]      (OUT defaults to profiles/kron_time.txt)
+
+FDAPDE_SOLVER_KRON_AMG against the GMRES stage as it was (the multilevel stage) on the same eight rows:
+
+  kron_time.py --amg PARENT_LIB [OUT] [MESH ...]     (OUT defaults to profiles/kron_amg_time.txt; MESH: 2d, 3d; both by default)
+
+PARENT_LIB is libfdapde_hip.so built from the parent commit.  Every measurement is one fresh process (`--amg-child`) that sets one mesh up, and for every
+q computes the handle, solves once to warm up (the first FDAPDE_SOLVER_KRON_AMG solve also builds the hierarchy, whose set-up time and rows per level
+it reports) and then times ONE solve by the host clock (the call ends in a stream synchronise).  Five rounds; in every round this tree's library solving
+by FDAPDE_SOLVER_KRON_AMG and the parent's solving by FDAPDE_SOLVER_GMRES alternate -> median, smallest and largest of five."""
 import os
 import socket
 import sys
@@ -138,7 +147,121 @@ def one_mesh(capi, torch, kr, br, label, mesh, out, table):
     c.close()
 
 
+MESHES = {"2d": ("2-D P1, unit_square(708)", "unit_square", 708), "3d": ("3-D P1, unit_cube(58)", "unit_cube", 58)}
+
+
+def amg_child(mesh_key, method_name):
+    """one fresh process: a mesh, every q, one warm-up and one timed solve each -> a JSON line per q"""
+    import json
+
+    from fdapde_loader import load_package
+
+    capi = load_package().capi
+    from fdapde_core_amd import meshgen
+    import block_ref as br
+    import kron_ref as kr
+
+    _, gen, nx = MESHES[mesh_key]
+    nodes, cells, bnd = getattr(meshgen, gen)(nx)
+    c = capi.Context(0)
+    c.mesh_upload(nodes, cells, bnd)
+    nd = c.dofs_build(1)
+    c.set_operator(-capi.laplacian())
+    c.set_forcing(np.zeros(c.quadrature_nodes().shape[0]))
+    c.init()
+    rp, ci = c.pattern_get()
+    r1, r0 = c.matrix_values(capi.MAT_STIFF), c.matrix_values(capi.MAT_MASS)
+    obs = br.observed_nodes(nodes.shape[0])
+    gram = br.gram_selection_values(rp, ci, obs, nd)
+    r1t = br.transpose_values(rp, ci, r1, nd)
+    amg = method_name == "KRON_AMG"
+    method = capi.SOLVER_KRON_AMG if amg else capi.SOLVER_GMRES
+    for q in QS:
+        m = q // 2
+        Mt, Pt = kr.time_mass(m), kr.time_penalty(m)
+        terms = [(kr._in_block(-np.eye(m), m, 0, 0), gram), (kr._in_block(-LAMBDA * Pt, m, 0, 0), r0), (kr._in_block(LAMBDA * Mt, m, 0, 1), r1t),
+                 (kr._in_block(LAMBDA * Mt, m, 1, 0), r1), (kr._in_block(LAMBDA * Mt, m, 1, 1), r0)]   # (kron_ref.spacetime_terms, the gram matrix built once)
+        b = kr.spacetime_rhs(obs, LAMBDA, nd, m)
+        c.tune("kron_dinv_mb", 16384)   # (q = 32 in 2-D: 4.1 GB at level 0, and the multilevel stage counts every level's)
+        c.kron_compute(terms, symmetric=True)
+        maxit = 200 if amg else 1000
+        row = dict(mesh=mesh_key, q=q, rows=q * nd, method=method_name)
+        try:
+            c.kron_solve(b, method=method, rtol=1e-10, maxit=maxit, raise_on_noconv=False)   # warm-up (and the set-up)
+            t0 = time.perf_counter()
+            x, info = c.kron_solve(b, method=method, rtol=1e-10, maxit=maxit, raise_on_noconv=False)
+            row.update(wall_ms=1e3 * (time.perf_counter() - t0), iters=info.iters, converged=info.converged, relres=info.relres)
+            if amg:
+                h = c.kron_amg_hierarchy()
+                row.update(setup_ms=h["setup_ms"], levels=h["rows"], absorbed=h["absorbed"])
+        except capi.FdapdeError as e:   # (a refusal is recorded as such)
+            row.update(refused=str(e)[:200])
+        print("ROW " + json.dumps(row), flush=True)
+    c.close()
+
+
+def amg_main(parent_lib, out_path, meshes):
+    import json
+    import subprocess
+
+    def child(mesh_key, method_name, lib):
+        env = dict(os.environ)
+        if lib:
+            env["FDAPDE_HIP_LIB"] = lib
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--amg-child", mesh_key, method_name], capture_output=True, text=True, env=env, timeout=900)
+        if r.returncode != 0:
+            raise SystemExit(f"a measuring process failed ({mesh_key}, {method_name}): rc {r.returncode}\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}")
+        return [json.loads(line[4:]) for line in r.stdout.splitlines() if line.startswith("ROW ")]
+
+    out = [f"tools/kron_time.py --amg on {socket.gethostname()} (MI355X), {time.strftime('%Y-%m-%d %H:%M:%S')}",
+           "space-time smoothing system, lambda = lambda_T = 1e-4, rtol 1e-10; five rounds, every figure from a fresh process (one warm-up solve, one timed solve);",
+           "KRON_AMG: this tree's library, FDAPDE_SOLVER_KRON_AMG (maxit 200); GMRES: the PARENT commit's library, FDAPDE_SOLVER_GMRES (maxit 1000), alternating", ""]
+    table = []
+    for mk in meshes:
+        got = {"KRON_AMG": {}, "GMRES": {}}
+        for rnd in range(5):
+            for name, lib in (("KRON_AMG", None), ("GMRES", parent_lib)):
+                for row in child(mk, name, lib):
+                    got[name].setdefault(row["q"], []).append(row)
+            print(f"{mk}: round {rnd + 1} of 5 done", flush=True)
+        out.append(f"{MESHES[mk][0]}")
+        for q in QS:
+            a, g = got["KRON_AMG"][q], got["GMRES"][q]
+            out.append(f"  q = {q:2d}, q n = {a[0]['rows']}")
+            if "refused" in a[0]:
+                out.append(f"    KRON_AMG refused: {a[0]['refused']}")
+                continue
+            ta, tg = [r["wall_ms"] for r in a], [r["wall_ms"] for r in g]
+            ts = [r["setup_ms"] for r in a]
+            out.append(f"    KRON_AMG  {a[0]['iters']} iterations, converged {a[0]['converged']}, relres {a[0]['relres']:.2e} (unscaled), solve {spread(ta)}; "
+                       f"set-up {spread(ts)}, absorbed {a[0]['absorbed']}, {len(a[0]['levels'])} levels, rows {' / '.join(str(r) for r in a[0]['levels'])}")
+            out.append(f"    GMRES     {g[0]['iters']} iterations, converged {g[0]['converged']}, relres {g[0]['relres']:.2e} (D^-1-scaled), solve {spread(tg)}")
+            ratio = float(np.median(ta) / np.median(tg))
+            out.append(f"    KRON_AMG / GMRES  {ratio:.2f} x the time, {a[0]['iters'] / max(g[0]['iters'], 1):.2f} x the iterations -> {'wins' if ratio < 1 else 'loses'}")
+            table.append((MESHES[mk][0].split(",")[0], q, a[0]["rows"], " / ".join(str(r) for r in a[0]["levels"]), float(np.median(ts)), a[0]["iters"], float(np.median(ta)),
+                          min(ta), max(ta), g[0]["iters"], float(np.median(tg)), min(tg), max(tg), ratio))
+        out.append("")
+    out += ["| mesh | q | q n | rows per level | set-up, ms | KRON_AMG iterations | KRON_AMG solve, ms (smallest, largest) | GMRES iterations | GMRES solve, ms (smallest, largest) | time ratio |",
+            "|---|---|---|---|---|---|---|---|---|---|"]
+    for r in table:
+        out.append("| {} | {} | {} | {} | {:.1f} | {} | {:.1f} ({:.1f}, {:.1f}) | {} | {:.1f} ({:.1f}, {:.1f}) | {:.2f} |".format(*r))
+    text = "\n".join(out) + "\n"
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as fh:
+        fh.write(text)
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--amg-child":
+        return amg_child(sys.argv[2], sys.argv[3])
+    if len(sys.argv) > 1 and sys.argv[1] == "--amg":
+        if len(sys.argv) < 3:
+            raise SystemExit("usage: kron_time.py --amg PARENT_LIB [OUT] [MESH ...]")
+        rest = sys.argv[3:]
+        out_path = rest[0] if rest and rest[0] not in MESHES else os.path.join(ROOT, "profiles", "kron_amg_time.txt")
+        meshes = [a for a in rest if a in MESHES] or list(MESHES)
+        return amg_main(os.path.abspath(sys.argv[2]), out_path, meshes)
     import torch   # (before the library: torch brings its own HIP runtime and finds no device once another copy has been initialised)
 
     if torch.cuda.is_available():
