@@ -48,7 +48,7 @@ SYMBOLS = [
     "fdapde_info_get", "fdapde_spmv", "fdapde_bench_spmv", "fdapde_tune", "fdapde_stream", "fdapde_synchronize",
     "fdapde_comm_unique_id", "fdapde_comm_init", "fdapde_halo_setup", "fdapde_solve_parabolic",
     "fdapde_lin_compute", "fdapde_lin_solve", "fdapde_eval_pointwise", "fdapde_project", "fdapde_cell_integrals", "fdapde_comm_init_callback", "fdapde_comm_set_exchange_callback", "fdapde_halo_setup_peers",
-    "fdapde_solver_layout", "fdapde_topology_build", "fdapde_topology_get", "fdapde_comm_allreduce", "fdapde_comm_library", "fdapde_solver_layout_kind", "fdapde_solver_layout_partition", "fdapde_solver_trace", "fdapde_rowdist_setup", "fdapde_ctx_clone", "fdapde_comm_count",
+    "fdapde_solver_layout", "fdapde_topology_build", "fdapde_topology_get", "fdapde_comm_allreduce", "fdapde_comm_library", "fdapde_solver_layout_kind", "fdapde_solver_layout_partition", "fdapde_solver_trace", "fdapde_solve_reuse_count", "fdapde_rowdist_setup", "fdapde_ctx_clone", "fdapde_comm_count",
     "fdapde_ctx_create_multi", "fdapde_ctx_devices", "fdapde_partition_build", "fdapde_partition_sizes", "fdapde_partition_get", "fdapde_partition_whole",
     "fdapde_partition_peers",
     "fdapde_block_compute", "fdapde_block_solve", "fdapde_block_spmv", "fdapde_block_bench_spmv", "fdapde_gram_pointwise",
@@ -725,6 +725,12 @@ class Context:
         f, g = C.c_int32(), C.c_int32()
         self._check(self.lib.fdapde_solver_trace(self._ctx, C.byref(f), C.byref(g)))
         return dict(small_front=f.value, graph_replays=g.value)
+
+    def solve_reuse_count(self):
+        """fdapde_solve calls of this context that took the prepared (Jacobi-scaled, filled) system of the solve before them"""
+        n = C.c_int64()
+        self._check(self.lib.fdapde_solve_reuse_count(self._ctx, C.byref(n)))
+        return n.value
 
     def amg_hierarchy(self, which=AMG_OF_SOLVE):
         """fdapde_amg_hierarchy: the live hierarchy of fdapde_solve (0), the factor-once handle (1) or the block handle (2, rows counted as 2 n_l) ->

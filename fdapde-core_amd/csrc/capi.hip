@@ -159,6 +159,7 @@ int fdapde_mesh_upload(fdapde_ctx* c, int M, int N, int64_t n_nodes, const doubl
     c->op.clear(), c->coef_of_op = false, c->fq_i.clear(), c->fq_cols = 0, c->g_i.clear(), c->have_g = false;
     if (c->topo_ready) dev_topology_release(&c->topo), c->topo_ready = false;
     c->mesh_on_dev = false;
+    c->drop_prepared("another mesh was uploaded");
     if (int rc = host_set_mesh(c->hs, M, N, n_nodes, nodes, n_cells, cells, bnd, c->err)) return rc;
     if (c->has_device) {   // the mesh is resident on the device from here on: the function space (any order) and the topology tables are built from it
         const HostSpace& hs = c->hs;
@@ -280,6 +281,11 @@ int fdapde_solver_trace(fdapde_ctx* c, int32_t* small_front, int32_t* graph_repl
     if (!c) return FDAPDE_EINVAL;
     if (small_front) *small_front = c->front_used ? 1 : 0;
     if (graph_replays) *graph_replays = c->graph_replays;
+    return FDAPDE_OK;
+}
+int fdapde_solve_reuse_count(fdapde_ctx* c, int64_t* count) {
+    if (!c || !count) return FDAPDE_EINVAL;
+    *count = c->prep_hits;
     return FDAPDE_OK;
 }
 static const char* const kBlockAmgOnly = "FDAPDE_SOLVER_BLOCK_AMG is a method of fdapde_block_solve (the 2 x 2 block handle) only";
@@ -543,6 +549,7 @@ int fdapde_tune(fdapde_ctx* c, const char* key, int32_t value) {
     if (c->group) return fdapde_engine::g_tune(c, key, value);
     const std::string k(key);
     drop_graph(c);
+    c->drop_prepared("fdapde_tune was called");   // (layouts, paths and thresholds hang on the knobs: the next fdapde_solve prepares in full)
     if (k == "spmv_team" && (value == 2 || value == 4 || value == 8 || value == 16 || value == 32)) {
         if (value != c->spmv_team) c->sp_built[0] = c->sp_built[1] = false, c->sp_cur = -1, c->solved = false, c->scaled_owner = fdapde_ctx::kScaledNone;   // segmented patterns depend on it
         c->spmv_team = value;
@@ -599,6 +606,7 @@ int fdapde_tune(fdapde_ctx* c, const char* key, int32_t value) {
     else if (k == "dense_hostb" && (value == 0 || value == 1)) c->dense_hostb = value;
     else if (k == "small_rows" && value >= 0) c->small_rows = value;
     else if (k == "small_front_rows" && value >= 0) c->small_front_rows = value;
+    else if (k == "solve_reuse" && (value == 0 || value == 1)) c->solve_reuse = value;
     else if (k == "auto_gmres" && (value == 0 || value == 1)) c->auto_gmres = value;
     else if (k == "asm_split_varying" && (value == 0 || value == 1)) c->asm_split_varying = value;
     else if (k == "asm_row_stat" && (value == 0 || value == 1)) c->asm_row_stat = value, c->stiff_stat_valid = false;

@@ -291,6 +291,27 @@ struct fdapde_ctx {
     // handle prepares again whenever anybody else has been there in between)
     enum { kScaledNone = 0, kScaledSolve, kScaledParabolic, kScaledLin, kScaledPmg };
     int scaled_owner = kScaledNone;
+    // The prepared system of fdapde_solve, kept across solves of an UNCHANGED matrix: scale, sval (or sval_stale / sval_A), sp_cur / sval_layout,
+    // ps[v].filled, bk[v].filled / bk_cur and persist_plain are what a full solve_prepare of (A, init_count, use_bnd, symmetric) left, its interior
+    // diagonal was positive and the host has SEEN that flag.  While `valid`, solve_prepare of the same system only resets ctl (no scale kernel, no flag
+    // read-back, no wait, no scaled copy, no fill).  One-GPU contexts only (no comm / ar_fn / group: the collectives of the distributed forms are taken
+    // by all ranks together), scaled_owner == kScaledSolve, never the one-workgroup front kernel's systems (k_small_front scales and fills by itself).
+    // Everything that can make it stale calls drop_prepared: there is no wide key to compare.
+    struct Prepared {
+        bool valid = false;
+        bool pending = false;      // written by a prepare that ASSUMED the positive diagonal (diag_deferred): valid once fdapde_solve has read ctl[4] == 0
+        const double* A = nullptr;
+        int64_t init_count = -1;
+        int use_bnd = 0;
+        bool symmetric = true;
+        const char* why = "no solve yet";   // why there is none (FDAPDE_DEBUG_SETUP prints it with the miss)
+    } prep;
+    int solve_reuse = 1;          // knob: 0 = every fdapde_solve prepares in full
+    int64_t prep_hits = 0;        // prepares served from the record (fdapde_solve_reuse_count)
+    void drop_prepared(const char* why) {
+        if (prep.valid || prep.pending) prep.why = why;
+        prep.valid = prep.pending = false;
+    }
     // multi-GPU (element partition): RCCL communicator + interface maps
     ncclComm_t comm = nullptr;
     fdapde_allreduce_fn ar_fn = nullptr;     // host-staged transport (tests / non-RCCL fabrics) instead of the RCCL communicator

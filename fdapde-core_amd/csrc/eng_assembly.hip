@@ -557,6 +557,7 @@ int e_assemble_operator(fdapde_ctx* c, int32_t which, int32_t n_terms, const fda
     AsmArgs a = asm_args(c);
     a.vals = c->vals[which].p;
     if (which == FDAPDE_MAT_STIFF) c->stiff_stat_valid = false;   // (the row statistics belong to what fdapde_init assembled)
+    if (which == FDAPDE_MAT_STIFF) c->drop_prepared("fdapde_assemble_operator rewrote the stiffness matrix");
     rc = launch_assembly(c, a, op, assembly);
     if (rc) return rc;
     if (op.mirror)

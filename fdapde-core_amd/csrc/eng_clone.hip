@@ -65,6 +65,7 @@ int clone_state(const fdapde_ctx* s, fdapde_ctx* d) {
         HIPCHK(d, hipStreamSynchronize(s->stream));   // whatever the source still has in flight
     }
     d->info = s->info;
+    d->drop_prepared("a clone prepares its first solve in full");   // (scale, scaled copy and filled layouts do not travel)
     // ---- problem data: operator (space-varying coefficient rows already in the internal cell order), forcing samples, Dirichlet data
     d->op.clear();
     for (const HostTerm& t : s->op) {

@@ -862,6 +862,7 @@ int pmg_run(fdapde_ctx* c, const double* A, const double* f_dev, const double* g
                 hipLaunchKernelGGL(k_pmg_fill_cols, dim3(g1n(bk.meta.n_entries)), bv, 0, st, bk.meta.n_entries, bk.ell_src.p, c->colidx.p, A, m.dinv.p, bk.ell_val.p);
             HIPCHK(c, hipGetLastError());
             c->bk[0].filled = c->bk[1].filled = false, c->bk_cur = -1;   // (not the scaled matrix of the Krylov stages: they fill it again)
+            c->drop_prepared("the two-level solver filled the blocked-ELL layout");
             c->scaled_owner = fdapde_ctx::kScaledPmg, m.fine_A = A, m.fine_key = coarse_key, m.fine_bnd = fv;
         }
     }

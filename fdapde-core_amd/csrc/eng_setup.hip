@@ -315,6 +315,7 @@ int e_dofs_build(fdapde_ctx* c, int order, int64_t* n_dofs) {
     c->eval_grid.release();   // (the point-location grid of the mesh before)
     c->asm_max_visits = -1;
     c->scaled_owner = fdapde_ctx::kScaledNone;
+    c->drop_prepared("the function space was built again");
     c->ps[0].tried = c->ps[0].ok = c->ps[1].tried = c->ps[1].ok = false;
     c->bk[0].tried = c->bk[0].ok = c->bk[1].tried = c->bk[1].ok = false, c->bk_cur = -1;
     drop_graph(c);
@@ -469,6 +470,7 @@ int e_dofs_set_boundary(fdapde_ctx* c, const uint8_t* bnd) {
     c->rd.lay[1].tried = c->rd.lay[1].ok = false;   // (row-distributed form: rebuilt -- collectively -- by the next solve)
     drop_graph(c);
     c->solved = false, c->scaled_owner = fdapde_ctx::kScaledNone;
+    c->drop_prepared("the boundary mask changed");
     if (c->dev_ready) {
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, c->bnd.upload(hs.dof_bnd_i.data(), hs.dof_bnd_i.size(), c->stream));

@@ -200,18 +200,20 @@ int build_blocked(fdapde_ctx* c, int v) {
                      100.0 * (double)(pl.n_entries - pl.nnz) / (double)(pl.n_entries > 0 ? pl.n_entries : 1), bk.lds_bytes, pl.max_imp, (long long)pl.n_imp);
     bk.meta = std::move(pl);
     bk.filled = false, bk.ok = true;
+    c->drop_prepared("the blocked-ELL layout was built again");
     return FDAPDE_OK;
 }
 
 // Dirichlet reduction + Jacobi scaling of the system matrix A (internal slots): scale, sval = diag(s) A diag(s).
-// Done once per matrix (per solve for the elliptic problem, once for all time steps of the parabolic one).
-int solve_prepare(fdapde_ctx* c, const double* A, int use_bnd, SolveState* ss, bool symmetric, bool allow_defer = false) {
+// Done once per matrix (once for all time steps of the parabolic problem; for the elliptic one once per assembled matrix: `reuse`, fdapde_solve's
+// first prepare of a call, is served from the context's prepared-system record while nothing has made it stale -- fdapde_ctx::Prepared).
+int solve_prepare(fdapde_ctx* c, const double* A, int use_bnd, SolveState* ss, bool symmetric, bool allow_defer = false, bool reuse = false) {
     const int64_t n = c->hs.n_dofs;
     hipStream_t st = c->stream;
+    if (!reuse) c->drop_prepared("another solver, or a later stage of the same solve, prepared a system in the shared buffers");
     ss->dist = (c->comm != nullptr || c->ar_fn != nullptr) && c->halo_ready;   // multi-GPU: sub-assembled operator of this rank's cells
     ss->owned = ss->dist ? c->owned.p : nullptr;
     ss->use_bnd = use_bnd, ss->symmetric = symmetric;
-    c->sval_stale = false;
     ss->rowdist = (c->comm != nullptr || c->ar_fn != nullptr) && c->rd.ready && !ss->dist;
     if (ss->rowdist) ss->owned = c->rd.owned.p;
     // small systems on one GPU (the sizes the reference is used at: a 289-DOF solve is a 130 us launch inside 250 us of wall time): no wait for
@@ -223,6 +225,32 @@ int solve_prepare(fdapde_ctx* c, const double* A, int use_bnd, SolveState* ss, b
     // ... and the smallest of them (one workgroup): flag reset, scale and fill are left to k_small_front (solve_run), if the layout turns out to be one it takes
     bool front_candidate = ss->diag_deferred && (symmetric || c->persist_bicg) && c->small_front_rows > 0 && n <= c->small_front_rows && A == c->vals[FDAPDE_MAT_STIFF].p &&
                            c->stiff_stat_valid && c->persist && !c->persist_broken;
+    // the system the record describes, again: scale, the scaled copy and the filled layout are in place bit for bit, and its diagonal was seen positive
+    const bool may_record = reuse && c->solve_reuse && !ss->dist && !ss->rowdist && c->comm == nullptr && c->ar_fn == nullptr && c->group == nullptr;
+    if (reuse) {
+        const fdapde_ctx::Prepared& pr = c->prep;
+        const char* miss = nullptr;
+        if (!c->solve_reuse) miss = "knob solve_reuse is 0";
+        else if (!may_record) miss = "a rank of a multi-GPU job prepares with the others";
+        else if (front_candidate) miss = "a one-workgroup system: its front kernel scales and fills";
+        else if (c->persist_broken) miss = "the single launch is on hold after a timeout";   // (its retry countdown belongs to the full prepare)
+        else if (!pr.valid) miss = pr.why;
+        else if (pr.A != A || pr.init_count != c->init_count) miss = "the matrix was assembled again";
+        else if (pr.use_bnd != use_bnd) miss = "Dirichlet data were set or removed";
+        else if (pr.symmetric != symmetric) miss = "the Krylov stage changed (CG <-> BiCGStab)";
+        if (std::getenv("FDAPDE_DEBUG_SETUP"))
+            std::fprintf(stderr, "solve_prepare: prepared system %s%s%s\n", miss ? "MISS (" : "HIT", miss ? miss : "", miss ? ")" : "");
+        if (!miss) {   // what a solve needs afresh: its control words
+            HIPCHK(c, hipMemsetAsync(c->ctl.p, 0, 8 * sizeof(int32_t), st));
+            c->h_ctl[3] = 0;
+            ss->diag_deferred = false, ss->diag_positive = true;
+            c->persist_plain = symmetric ? 0 : 1;   // (fdapde_solver_prepare may have set it from the operator in between)
+            ++c->prep_hits;
+            return FDAPDE_OK;
+        }
+        c->drop_prepared(miss);
+    }
+    c->sval_stale = false;
     if (!front_candidate) HIPCHK(c, hipMemsetAsync(c->ctl.p, 0, 8 * sizeof(int32_t), st));
     if (front_candidate) {
     } else if (ss->dist) {   // the diagonal is a sum over the ranks sharing a DOF
@@ -339,6 +367,11 @@ int solve_prepare(fdapde_ctx* c, const double* A, int use_bnd, SolveState* ss, b
     else if (persist)
         if (int rc = c->sval_stale ? fill_persist_scaled(c, use_bnd ? 1 : 0, A) : fill_persist(c, use_bnd ? 1 : 0)) return rc;
     HIPCHK(c, hipGetLastError());
+    if (may_record && !ss->front_pending && ss->diag_positive && !c->persist_broken) {   // (a non-positive diagonal is never kept)
+        fdapde_ctx::Prepared& pr = c->prep;
+        pr.A = A, pr.init_count = c->init_count, pr.use_bnd = use_bnd, pr.symmetric = symmetric;
+        pr.pending = ss->diag_deferred, pr.valid = !ss->diag_deferred;   // (deferred: fdapde_solve confirms it once it has read the flag)
+    }
     return FDAPDE_OK;
 }
 
@@ -564,6 +597,7 @@ int solve_run(fdapde_ctx* c, const SolveState& ss, const double* A, const double
         if (rc_p) return rc_p;
         clk.mark("solve_run: run_persist");
         if (persisted) stop = true, launched = c->h_ctl[1], unscaled = true;
+        else c->drop_prepared("the single launch gave up (persist_broken) or its layout does not launch");   // (a retry goes through a full prepare)
     }
     if (bicg && !dist && !ss.rowdist && c->persist && c->persist_bicg && !c->persist_broken) {   // the whole BiCGStab as one launch
         const fdapde_ctx::Persist& ps = c->ps[ss.use_bnd ? 1 : 0];
@@ -577,6 +611,7 @@ int solve_run(fdapde_ctx* c, const SolveState& ss, const double* A, const double
             c->persist_tail = nullptr;
             if (rc_p) return rc_p;
             if (persisted) stop = true, launched = c->h_ctl[1], unscaled = true;
+            else c->drop_prepared("the single launch gave up (persist_broken) or its layout does not launch");
         }
     }
     // one iteration of the fused-update CG: SpMV (p.y, y.y) + k_cgf_update; arguments depend on the iteration's parity only
@@ -889,6 +924,14 @@ int e_solver_prepare(fdapde_ctx* c, int32_t with_dirichlet) {
     if (!c->dev_ready) return fail(c, FDAPDE_ENOTINIT, "call fdapde_dofs_build first");
     HIPCHK(c, hipSetDevice(c->device));
     const int v = with_dirichlet ? 1 : 0;
+    struct FilledGuard {   // a layout built again here no longer holds the prepared system's values
+        fdapde_ctx* c;
+        int v;
+        bool ps_filled, bk_filled;
+        ~FilledGuard() {
+            if (c->ps[v].filled != ps_filled || c->bk[v].filled != bk_filled) c->drop_prepared("fdapde_solver_prepare built the solver's layout again");
+        }
+    } filled_guard{c, v, c->ps[v].filled, c->bk[v].filled};
     if (c->persist && !c->persist_broken && c->comm == nullptr && c->ar_fn == nullptr && (c->op_symmetric || c->persist_bicg)) {
         // single GPU: the single-launch solver's layout (CG for a symmetric operator, BiCGStab on the plain storage otherwise); when the
         // system qualifies for it, the compact pattern and the column codes of the multi-launch SpMV are not needed (a matrix that turns
@@ -977,6 +1020,9 @@ int e_solve(fdapde_ctx* c, const fdapde_options* opt, fdapde_info* info) {
     const int check_every = (opt && opt->check_every > 0) ? opt->check_every : 32;
     const double* A = c->vals[FDAPDE_MAT_STIFF].p;
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    // (a solve by another solver's name in between: the next Jacobi-Krylov solve prepares in full)
+    if (opt && (opt->method == FDAPDE_SOLVER_PMG || opt->method == FDAPDE_SOLVER_AMG || opt->method == FDAPDE_SOLVER_DENSE))
+        c->drop_prepared("a solve by the name of another solver came in between");
     if (opt && opt->method == FDAPDE_SOLVER_PMG) return e_solve_pmg(c, opt, info);   // the two-level solver of order-2 spaces (eng_pmg.hip), by name
     if (opt && opt->method == FDAPDE_SOLVER_AMG) return e_solve_amg(c, opt, info);   // the aggregation multilevel solver (eng_amg.hip), by name only
     if (opt && opt->method == FDAPDE_SOLVER_DENSE) {
@@ -1021,12 +1067,13 @@ int e_solve(fdapde_ctx* c, const fdapde_options* opt, fdapde_info* info) {
         HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     }
     SolveState ss;
+    if (c->scaled_owner != fdapde_ctx::kScaledSolve) c->drop_prepared("the shared buffers held another solver's system");
     c->scaled_owner = fdapde_ctx::kScaledSolve;
     DebugClock clk;
     const bool open_method = !opt || opt->method == FDAPDE_SOLVER_AUTO;
     const bool skip_cg = open_method && c->cg_broke_down;   // (this very matrix broke CG before: see below)
     const int gm_budget = !open_method ? -1 : ((opt && opt->maxit > 0) ? 0 : default_maxit(c, n));   // (the GMRES stage of the open method)
-    if (int rc = solve_prepare(c, A, c->have_g ? 1 : 0, &ss, c->op_symmetric && !skip_cg, /*allow_defer=*/true)) return rc;
+    if (int rc = solve_prepare(c, A, c->have_g ? 1 : 0, &ss, c->op_symmetric && !skip_cg, /*allow_defer=*/true, /*reuse=*/true)) return rc;
     clk.mark("fdapde_solve: solve_prepare");
     HIPCHK(c, hipEventRecord(c->ev1, c->stream));   // (a solve that ends before its epilogue -- an early refusal -- still leaves a recorded event)
     c->ev1_at_end = true;
@@ -1042,7 +1089,9 @@ int e_solve(fdapde_ctx* c, const fdapde_options* opt, fdapde_info* info) {
             HIPCHK(c, hipMemcpyAsync(c->h_ctl + 4, c->ctl.p + 4, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
         }
+        if (c->h_ctl[4] == 0 && c->prep.pending) c->prep.valid = true, c->prep.pending = false;   // (the host has seen the flag: the prepared system may be kept)
         if (c->h_ctl[4] != 0) {   // a non-positive interior diagonal after all: everything again with the decision taken up front
+            c->drop_prepared("an interior diagonal entry is not positive");
             if (int rc2 = solve_prepare(c, A, c->have_g ? 1 : 0, &ss, c->op_symmetric && !skip_cg, false)) return rc2;
             rc = solve_run_restarting(c, ss, A, c->force.p, c->g.p, nullptr, skip_cg ? FDAPDE_SOLVER_BICGSTAB : (opt ? opt->method : FDAPDE_SOLVER_AUTO), rtol,
                                       maxit, check_every, opt ? opt->time_spmv : 0, gm_budget);
@@ -1062,6 +1111,7 @@ int e_solve(fdapde_ctx* c, const fdapde_options* opt, fdapde_info* info) {
         // reference's 5-point rule has a negative weight, its mass matrix is indefinite (integrator_tables.h:275-292).  The reference's LU solves
         // such a system all the same (fem_linear_elliptic_solver.h:38-47); so does BiCGStab.  Only where the caller left the method open.
         c->cg_broke_down = true;   // (until the matrix is assembled again)
+        c->drop_prepared("CG broke down: the system is prepared again for BiCGStab");
         if (int rc2 = solve_prepare(c, A, c->have_g ? 1 : 0, &ss, false)) return rc2;
         rc = solve_run_restarting(c, ss, A, c->force.p, c->g.p, nullptr, FDAPDE_SOLVER_BICGSTAB, rtol, maxit, check_every, opt ? opt->time_spmv : 0, gm_budget);
         clk.mark("fdapde_solve: solve_run (BiCGStab after a CG breakdown)");

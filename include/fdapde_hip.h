@@ -442,6 +442,10 @@ int fdapde_solver_layout_partition(fdapde_ctx *ctx, int32_t with_dirichlet, int3
  * one-workgroup single launch ran as one kernel (fdapde_tune "small_front_rows"; plain storage only), graph_replays = the chunks of the
  * fused-update CG that were replayed from a captured graph (fdapde_tune "use_graph": a capture that fails falls back to plain launches). */
 int fdapde_solver_trace(fdapde_ctx *ctx, int32_t *small_front, int32_t *graph_replays);
+/* How many fdapde_solve calls on this context took the Jacobi-scaled system of the solve before them instead of preparing it again: the scale, the
+ * scaled copy and the filled solver layout are kept while the stiffness matrix is the one they were made from (a repeated fdapde_init of an unchanged
+ * operator reproduces it bit for bit) with the same Dirichlet mask, on a one-GPU context (fdapde_tune "solve_reuse").  Read-only; never reset. */
+int fdapde_solve_reuse_count(fdapde_ctx *ctx, int64_t *count);
 /* ---- multi-GPU: element-partitioned meshes, one context (= one rank) per GPU --------------------------------------------
  * No reference counterpart (the reference is single-threaded, single address space).  Each rank uploads the sub-mesh of
  * its own cells (local node numbering), assembles its sub-assembled operator with the calls above, and the solve sums the
@@ -560,7 +564,9 @@ int fdapde_partition_peers(fdapde_ctx *ctx, int32_t rank, int32_t *n_peers, int3
  *                 "auto_gmres" (0: the open method ends with BiCGStab), "gmres_m" (restart length, default 50),
  *                 "small_rows" (systems of up to that many DOFs: no wait for the positive-diagonal flag, outcome through a pinned record; 0: off),
  *                 "small_front_rows" (one-workgroup systems of up to that many DOFs: ONE kernel in front of the single launch -- k_small_front --
- *                 and the epilogue inside the launch; 0: the separate launches), "asm_items_fuse" (0: the P2 mass matrix in a sweep of its own)
+ *                 and the epilogue inside the launch; 0: the separate launches), "asm_items_fuse" (0: the P2 mass matrix in a sweep of its own),
+ *                 "solve_reuse" (1, the default: fdapde_solve keeps the Jacobi-scaled system and the filled layout across solves of an unchanged matrix;
+ *                 0: every fdapde_solve prepares in full.  Any fdapde_tune call makes the next fdapde_solve prepare in full once)
  *   measurement   knobs kept for the A/B figures of DESIGN.md: "asm_row_stat" (0: the solve's Jacobi scaling reads the whole matrix instead of the (diagonal, row maximum)
  *                 pairs fdapde_init leaves), "bicg_shadow" (shadow residual of the multi-launch BiCGStab: 0 = r0, 1 = pseudo-random, 2 = r0 with randomly scaled entries),
  *                 "persist_bicg" (0: non-symmetric systems always take the multi-launch BiCGStab), "persist_fill_fused" (1: the single launch's blocks filled straight from
