@@ -52,6 +52,7 @@ SYMBOLS = [
     "fdapde_ctx_create_multi", "fdapde_ctx_devices", "fdapde_partition_build", "fdapde_partition_sizes", "fdapde_partition_get", "fdapde_partition_whole",
     "fdapde_partition_peers",
     "fdapde_block_compute", "fdapde_block_solve", "fdapde_block_spmv", "fdapde_block_bench_spmv", "fdapde_gram_pointwise",
+    "fdapde_block_set_obs", "fdapde_block_obs_info",
     "fdapde_kron_compute", "fdapde_kron_solve", "fdapde_kron_spmv", "fdapde_kron_bench_spmv",
     "fdapde_kron_amg_hierarchy", "fdapde_kron_amg_aggregates",
     "fdapde_amg_hierarchy", "fdapde_amg_aggregates", "fdapde_amg_order", "fdapde_amg_damping", "fdapde_amg_cols_trace",
@@ -451,10 +452,47 @@ class Context:
         return y
 
     def block_bench_spmv(self, reps=50):
-        """(average ms of k_block_spmv on the scaled blocks, algorithmic bytes per launch)"""
+        """(average ms of the Krylov stage's operator -- k_block_spmv on the scaled blocks and, with a data term live, its two products --, algorithmic bytes
+        per application)"""
         ms, by = C.c_double(), C.c_double()
         self._check(self.lib.fdapde_block_bench_spmv(self._ctx, reps, C.byref(ms), C.byref(by)))
         return ms.value, by.value
+
+    def block_set_obs(self, psi, weights=None, scale=-1.0):
+        """fdapde_block_set_obs: the handle's matrix becomes A + scale [Psi^T W Psi, 0; 0, 0], the term kept factored.  psi: a scipy.sparse matrix
+        (n_obs x n_dofs; duplicates summed, columns sorted), a triple (rowptr, colidx, values) handed to the library as it is, or None (clears the term).
+        weights: one per row, or None (W = I)"""
+        if psi is None:
+            self._check(self.lib.fdapde_block_set_obs(self._ctx, C.c_int64(0), None, None, None, None, C.c_double(scale)))
+            return
+        if isinstance(psi, (tuple, list)):
+            rp, ci, v = psi
+        else:
+            m = psi.tocsr().copy()
+            m.sum_duplicates()
+            m.sort_indices()
+            if m.shape[1] != self.sizes()["n_dofs"]:
+                raise ValueError("block_set_obs(): Psi needs n_dofs columns")
+            rp, ci, v = m.indptr, m.indices, m.data
+        rp = np.ascontiguousarray(rp, dtype=np.int64).reshape(-1)
+        ci = np.ascontiguousarray(ci, dtype=np.int32).reshape(-1)
+        v = np.ascontiguousarray(v, dtype=float).reshape(-1)
+        if rp.size < 1 or ci.size != v.size or (rp.size > 1 and rp.max() > ci.size):
+            raise ValueError("block_set_obs(): rowptr / colidx / values do not fit together")
+        n_obs = rp.size - 1
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=float).reshape(-1)
+            if w.size != n_obs:
+                raise ValueError("block_set_obs(): one weight per row of Psi")
+        self._check(self.lib.fdapde_block_set_obs(self._ctx, C.c_int64(n_obs), rp.ctypes.data_as(C.POINTER(C.c_int64)), _ip(ci), _dp(v),
+                                                  None if w is None else _dp(w), C.c_double(scale)))
+
+    def block_obs_info(self):
+        """fdapde_block_obs_info -> dict(n_obs, nnz, team_rows, team_cols): the live data term's sizes and the lanes per row of Psi / of Psi^T"""
+        n_obs, nnz, tr, tc = C.c_int64(), C.c_int64(), C.c_int32(), C.c_int32()
+        self._check(self.lib.fdapde_block_obs_info(self._ctx, C.byref(n_obs), C.byref(nnz), C.byref(tr), C.byref(tc)))
+        return {"n_obs": n_obs.value, "nnz": nnz.value, "team_rows": tr.value, "team_cols": tc.value}
 
     # ---- Kronecker-sum operators sum_k T_k (x) S_k on the FEM pattern (the reference's Kronecker(A, B) under fdapde::SparseLU): the space-time systems' handle
     def kron_compute(self, terms, symmetric=False):

@@ -342,6 +342,16 @@ int fdapde_block_bench_spmv(fdapde_ctx* c, int32_t reps, double* avg_ms, double*
     if (c->group) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, kBlockNoGroup);
     return fdapde_engine::e_block_bench_spmv(c, reps, avg_ms, algorithmic_bytes);
 }
+int fdapde_block_set_obs(fdapde_ctx* c, int64_t n_obs, const int64_t* rowptr, const int32_t* colidx, const double* values, const double* weights, double scale) {
+    if (!c) return FDAPDE_EINVAL;
+    if (c->group) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, kBlockNoGroup);
+    return fdapde_engine::e_block_set_obs(c, n_obs, rowptr, colidx, values, weights, scale);
+}
+int fdapde_block_obs_info(fdapde_ctx* c, int64_t* n_obs, int64_t* nnz, int32_t* team_rows, int32_t* team_cols) {
+    if (!c) return FDAPDE_EINVAL;
+    if (c->group) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, kBlockNoGroup);
+    return fdapde_engine::e_block_obs_info(c, n_obs, nnz, team_rows, team_cols);
+}
 // the Kronecker-sum handle (eng_kron.hip): single-device contexts only
 static const char* const kKronNoGroup = "the Kronecker-sum handle takes one-GPU contexts, not a multi-device context";
 int fdapde_kron_compute(fdapde_ctx* c, int32_t q, int32_t n_terms, const double* const* T, const double* const* S, int32_t symmetric) {
@@ -588,6 +598,7 @@ int fdapde_tune(fdapde_ctx* c, const char* key, int32_t value) {
     else if (k == "amg_coarse_rows" && value >= 1 && value <= 8192) c->amg_coarse_rows = value;
     else if (k == "amg_setup_check" && (value == 0 || value == 1)) c->amg_setup_check = value;
     else if (k == "amg_cols" && (value == 1 || value == 2 || value == 4 || value == 8)) c->amg_cols = value;
+    else if (k == "block_obs_team" && (value == 0 || value == 8 || value == 64)) c->block_obs_team = value;   // (read by the next fdapde_block_set_obs)
     else if (k == "kron_dinv_mb" && value >= 0) c->kron_dinv_mb = value;   // (read by the next fdapde_kron_compute)
     else if (k == "kron_fuse" && (value == 0 || value == 1)) c->kron_fuse = value;
     else if (k == "kron_amg_term" && value >= -1 && value < 8) {   // read by the build of the hierarchy: a live one goes

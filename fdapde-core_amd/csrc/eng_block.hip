@@ -6,6 +6,8 @@
 //                          (by name) flexible GMRES around the point-block multilevel cycle of eng_block_amg.hip
 //   fdapde_block_spmv      y = A x with the unscaled blocks
 //   fdapde_gram_pointwise  Psi^T W Psi from what fdapde_eval_pointwise / fdapde_project hand out
+//   fdapde_block_set_obs   the data term kept factored: the handle's matrix becomes A + scale [Psi^T W Psi, 0; 0, 0] with Psi a CSR matrix of any row length
+//                          (areal designs: Psi^T Psi is far off the pattern); set-up in host_obs.cpp, the two products per application in kernels_obs.h
 // Independent of the n x n handle of fdapde_lin_compute: nothing here writes a buffer one of the other solves reads back.
 #include <algorithm>
 #include <chrono>
@@ -15,12 +17,24 @@
 #include "context.h"
 #include "engine.h"
 #include "eng_gmres.h"
+#include "host_obs.h"
 #include "kernels_block.h"
 #include "kernels_dense.h"
 #include "kernels_gmres.h"
 #include "kernels_krylov.h"
+#include "kernels_obs.h"
 
 namespace fdapde_engine {
+
+// the factored data term of the current matrix (fdapde_block_set_obs): Psi and Psi^T in the internal order on the device, the host copy for the dense stage
+struct BlockObs {
+    bool live = false;
+    double scale = 0;
+    int team_rows = 8, team_cols = 8;   // lanes per row of Psi (k_obs_gather) / of Psi^T (k_obs_scatter, k_obs_diag)
+    fdapde_hip::ObsHost host;
+    DBuf<int32_t> rp, ci, trp, tci;
+    DBuf<double> v, tv, w, t, g;        // t [n_obs]: W Psi x_1 between the two products; g [n]: the term's share of every diagonal block
+};
 
 struct BlockHandle {
     bool ready = false, symmetric = false;
@@ -38,6 +52,7 @@ struct BlockHandle {
     double krylov_ms = 0;              // ... and the host time the Krylov columns among them took
     bool given[4] = {false, false, false, false};   // which of a11 a12 a21 a22 were handed over (not NULL)
     BlockAmg* amg = nullptr;           // FDAPDE_SOLVER_BLOCK_AMG's hierarchy of the current matrix (eng_block_amg.hip), built by its first solve
+    BlockObs obs;
     ~BlockHandle() { block_amg_free(amg); }
 };
 
@@ -91,10 +106,42 @@ void launch_block_spmv(fdapde_ctx* c, const double* vals, const double* x, doubl
     hipLaunchKernelGGL(k_block_spmv<T>, dim3(g1(n, 256 / T)), dim3(256), 0, c->stream, n, c->rowptr.p, c->colidx.p, vals, x, y, stop);
 }
 
+// y += D^-1 [scale Psi^T W Psi x_1; 0] (dinv = NULL: without D^-1) behind a launch_block_spmv that wrote y: two launches, team widths as chosen per matrix
+void launch_obs_term(fdapde_ctx* c, BlockHandle& B, const double* dinv, const double* x, double* y, const int32_t* stop) {
+    BlockObs& O = B.obs;
+    const int64_t m = O.host.n_obs, n = B.n;
+    hipStream_t st = c->stream;
+    if (O.team_rows == 64) hipLaunchKernelGGL(k_obs_gather<64>, dim3(g1(m, 4)), dim3(256), 0, st, m, O.rp.p, O.ci.p, O.v.p, O.w.p, x, O.t.p, stop);
+    else hipLaunchKernelGGL(k_obs_gather<8>, dim3(g1(m, 32)), dim3(256), 0, st, m, O.rp.p, O.ci.p, O.v.p, O.w.p, x, O.t.p, stop);
+    if (O.team_cols == 64) hipLaunchKernelGGL(k_obs_scatter<64>, dim3(g1(n, 4)), dim3(256), 0, st, n, O.trp.p, O.tci.p, O.tv.p, O.t.p, O.scale, dinv, y, stop);
+    else hipLaunchKernelGGL(k_obs_scatter<8>, dim3(g1(n, 32)), dim3(256), 0, st, n, O.trp.p, O.tci.p, O.tv.p, O.t.p, O.scale, dinv, y, stop);
+}
+
+// the Krylov stage's operator D^-1 (A + the term): one launch without a term, three with one
+void launch_block_op(fdapde_ctx* c, BlockHandle& B, const double* x, double* y, const int32_t* stop) {
+    launch_block_spmv(c, B.scaled.p, x, y, stop);
+    if (B.obs.live) launch_obs_term(c, B, B.dinv.p, x, y, stop);
+}
+
 // restarted GMRES(m) on D^-1 A z = D^-1 b for the column staged in B.bt: handle_gmres (eng_gmres.h) on the handle's buffers
 int block_gmres(fdapde_ctx* c, BlockHandle& B, double tol2, int maxit, int32_t h_ctl[4], double h_sc[4]) {
     return handle_gmres(c, HandleGmresWork{B.bt, B.x, B.r, B.w, B.t, B.sc, B.gm_V, B.gm_s, B.gm_part, B.ctl}, 2 * B.n,
-                        [&](const double* x, double* y, const int32_t* stop) { launch_block_spmv(c, B.scaled.p, x, y, stop); }, tol2, maxit, h_ctl, h_sc);
+                        [&](const double* x, double* y, const int32_t* stop) { launch_block_op(c, B, x, y, stop); }, tol2, maxit, h_ctl, h_sc);
+}
+
+// D^-1 of every DOF (g: the data term's share of the (1,1) entries, or NULL), the singular-block flag and the scaled copy, from `raw`
+int block_rescale(fdapde_ctx* c, BlockHandle& B, const double* g) {
+    hipStream_t st = c->stream;
+    const int64_t n = B.n;
+    HIPCHK(c, hipMemsetAsync(B.flag.p, 0, sizeof(int32_t), st));
+    hipLaunchKernelGGL(k_block_diag_inv, dim3(g1(n)), dim3(256), 0, st, n, c->rowptr.p, c->colidx.p, B.raw.p, g, B.dinv.p, B.flag.p);
+    hipLaunchKernelGGL(k_block_scale, dim3(g1(n, 256 / kBlockTeam)), dim3(256), 0, st, n, c->rowptr.p, B.raw.p, B.dinv.p, B.scaled.p);
+    HIPCHK(c, hipGetLastError());
+    int32_t h_flag = 0;
+    HIPCHK(c, hipMemcpyAsync(&h_flag, B.flag.p, sizeof h_flag, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    B.jacobi_ok = h_flag == 0;
+    return FDAPDE_OK;
 }
 
 bool block_dense_eligible(const fdapde_ctx* c, const BlockHandle& B) {
@@ -103,6 +150,22 @@ bool block_dense_eligible(const fdapde_ctx* c, const BlockHandle& B) {
 
 int block_dense_build(fdapde_ctx* c, BlockHandle& B) {
     const int64_t n = B.n;
+    if (B.obs.live) {   // the term merged into the expanded matrix by the host (set-up): build and refinement see the true matrix
+        hipStream_t st = c->stream;
+        if (int rc = ensure_host(c, kHostPattern)) return rc;
+        std::vector<double> raw((size_t)(4 * B.nnz));
+        HIPCHK(c, hipMemcpyAsync(raw.data(), B.raw.p, sizeof(double) * raw.size(), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        std::vector<int32_t> rp2, ci2;
+        std::vector<double> v2;
+        fdapde_hip::obs_merge_dense(c->hs.rowptr_i.data(), c->hs.colidx_i.data(), raw.data(), B.obs.host, B.obs.scale, &rp2, &ci2, &v2);
+        B.expanded = false;   // (the buffers hold the merged matrix, not k_block_expand's)
+        HIPCHK(c, B.rowptr2.upload(rp2.data(), rp2.size(), st));
+        HIPCHK(c, B.colidx2.upload(ci2.data(), ci2.size(), st));
+        HIPCHK(c, B.val2.upload(v2.data(), v2.size(), st));
+        HIPCHK(c, hipStreamSynchronize(st));   // (the host vectors have been read)
+        return dense_build_csr(c, 2 * n, B.rowptr2.p, B.colidx2.p, B.val2.p, nullptr, 0, B.dense);
+    }
     if (!B.expanded) {
         HIPCHK(c, B.rowptr2.alloc((size_t)(2 * n + 1)));
         HIPCHK(c, B.colidx2.alloc((size_t)(4 * B.nnz)));
@@ -124,6 +187,8 @@ int block_amg_solve(fdapde_ctx* c, BlockHandle& B, const fdapde_options* opt, co
     fdapde_info out{};
     out.method_used = FDAPDE_SOLVER_BLOCK_AMG;
     const auto t_call = std::chrono::steady_clock::now();
+    if (B.obs.live)
+        return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_BLOCK_AMG: a factored data term (fdapde_block_set_obs) is live; the hierarchy is built from pattern entries only");
     if (!B.jacobi_ok)
         return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_BLOCK_AMG: a DOF's diagonal block is singular (|det| <= 1e-14 max|entry|^2): no block-Jacobi smoother");
     if (!B.amg) {
@@ -189,6 +254,7 @@ int e_block_compute(fdapde_ctx* c, const double* a11, const double* a12, const d
     B.ready = false, B.expanded = false, B.n = n, B.nnz = nnz, B.symmetric = symmetric != 0;
     B.dense.ready = B.dense.failed = false, B.cols = 0, B.krylov_ms = 0;
     block_amg_free(B.amg), B.amg = nullptr;   // (the hierarchy belonged to the previous matrix)
+    B.obs.live = false;                       // (... and so did the data term)
     B.given[0] = a11 != nullptr, B.given[1] = a12 != nullptr, B.given[2] = a21 != nullptr, B.given[3] = a22 != nullptr;
     HIPCHK(c, B.ext.alloc((size_t)std::max<int64_t>(4 * nnz, 2 * n)));
     HIPCHK(c, B.raw.alloc((size_t)(4 * nnz)));
@@ -203,16 +269,81 @@ int e_block_compute(fdapde_ctx* c, const double* a11, const double* a12, const d
         if (blocks[q]) HIPCHK(c, hipMemcpyAsync(B.ext.p + (size_t)q * nnz, blocks[q], sizeof(double) * (size_t)nnz, hipMemcpyHostToDevice, st));
         else HIPCHK(c, hipMemsetAsync(B.ext.p + (size_t)q * nnz, 0, sizeof(double) * (size_t)nnz, st));
     }
-    HIPCHK(c, hipMemsetAsync(B.flag.p, 0, sizeof(int32_t), st));
     hipLaunchKernelGGL(k_block_pack, dim3(g1(nnz)), dim3(256), 0, st, nnz, c->slot_i2e.p, B.ext.p, B.raw.p);
-    hipLaunchKernelGGL(k_block_diag_inv, dim3(g1(n)), dim3(256), 0, st, n, c->rowptr.p, c->colidx.p, B.raw.p, B.dinv.p, B.flag.p);
-    hipLaunchKernelGGL(k_block_scale, dim3(g1(n, 256 / kBlockTeam)), dim3(256), 0, st, n, c->rowptr.p, B.raw.p, B.dinv.p, B.scaled.p);
-    HIPCHK(c, hipGetLastError());
-    int32_t h_flag = 0;
-    HIPCHK(c, hipMemcpyAsync(&h_flag, B.flag.p, sizeof h_flag, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));   // (the caller's blocks have been read)
-    B.jacobi_ok = h_flag == 0;
+    if (int rc = block_rescale(c, B, nullptr)) return rc;   // (synchronises: the caller's blocks have been read)
     B.ready = true;
+    return FDAPDE_OK;
+}
+
+namespace {
+int block_live(fdapde_ctx* c) {
+    if (!c->block || !c->block->ready || c->block->n != c->hs.n_dofs || c->block->nnz != c->hs.nnz) return fail(c, FDAPDE_ENOTINIT, "call fdapde_block_compute first");
+    return FDAPDE_OK;
+}
+// what a change of the term invalidates: the dense inverse, the multilevel hierarchy, the rent-or-buy count
+void block_matrix_changed(BlockHandle& B) {
+    B.dense.ready = B.dense.failed = false, B.expanded = false, B.cols = 0, B.krylov_ms = 0;
+    block_amg_free(B.amg), B.amg = nullptr;
+}
+}   // namespace
+
+int e_block_set_obs(fdapde_ctx* c, int64_t n_obs, const int64_t* rowptr, const int32_t* colidx, const double* values, const double* weights, double scale) {
+    if (!c) return FDAPDE_EINVAL;
+    if (int rc = block_guard(c)) return rc;
+    if (int rc = block_live(c)) return rc;
+    if (n_obs < 0) return fail(c, FDAPDE_EINVAL, "fdapde_block_set_obs: n_obs is negative");
+    HIPCHK(c, hipSetDevice(c->device));
+    BlockHandle& B = *c->block;
+    BlockObs& O = B.obs;
+    hipStream_t st = c->stream;
+    const int64_t n = B.n;
+    if (n_obs == 0 || !rowptr) {   // clears the term
+        if (!O.live) return FDAPDE_OK;
+        HIPCHK(c, hipStreamSynchronize(st));
+        O.live = false;
+        block_matrix_changed(B);
+        return block_rescale(c, B, nullptr);
+    }
+    std::string why;
+    if (!fdapde_hip::obs_validate(n, n_obs, rowptr, colidx, values, weights, scale, &why)) {   // (nothing launched, the previous term stays)
+        c->err = why;
+        return FDAPDE_EINVAL;
+    }
+    if (int rc = ensure_host(c, kHostPerm)) return rc;
+    HIPCHK(c, hipStreamSynchronize(st));
+    fdapde_hip::ObsHost& P = O.host;
+    O.live = false;
+    block_matrix_changed(B);
+    fdapde_hip::obs_build(n, n_obs, rowptr, colidx, values, weights, c->hs.dof_e2i.data(), &P);
+    O.scale = scale;
+    O.team_rows = fdapde_hip::obs_team_width(P.n_obs, P.nnz, c->block_obs_team);
+    O.team_cols = fdapde_hip::obs_team_width(P.n, P.nnz, c->block_obs_team);
+    HIPCHK(c, O.rp.upload(P.rp.data(), P.rp.size(), st));
+    HIPCHK(c, O.ci.upload(P.ci.data(), P.ci.size(), st));
+    HIPCHK(c, O.v.upload(P.v.data(), P.v.size(), st));
+    HIPCHK(c, O.trp.upload(P.trp.data(), P.trp.size(), st));
+    HIPCHK(c, O.tci.upload(P.tci.data(), P.tci.size(), st));
+    HIPCHK(c, O.tv.upload(P.tv.data(), P.tv.size(), st));
+    HIPCHK(c, O.w.upload(P.w.data(), P.w.size(), st));
+    HIPCHK(c, O.t.alloc((size_t)n_obs));
+    HIPCHK(c, O.g.alloc((size_t)n));
+    if (O.team_cols == 64) hipLaunchKernelGGL(k_obs_diag<64>, dim3(g1(n, 4)), dim3(256), 0, st, n, O.trp.p, O.tci.p, O.tv.p, O.w.p, scale, O.g.p, (const int32_t*)nullptr);
+    else hipLaunchKernelGGL(k_obs_diag<8>, dim3(g1(n, 32)), dim3(256), 0, st, n, O.trp.p, O.tci.p, O.tv.p, O.w.p, scale, O.g.p, (const int32_t*)nullptr);
+    if (int rc = block_rescale(c, B, O.g.p)) return rc;   // (synchronises: the uploads are done)
+    O.live = true;
+    return FDAPDE_OK;
+}
+
+int e_block_obs_info(fdapde_ctx* c, int64_t* n_obs, int64_t* nnz, int32_t* team_rows, int32_t* team_cols) {
+    if (!c) return FDAPDE_EINVAL;
+    if (int rc = block_guard(c)) return rc;
+    if (int rc = block_live(c)) return rc;
+    const BlockObs& O = c->block->obs;
+    if (!O.live) return fail(c, FDAPDE_ENOTINIT, "fdapde_block_obs_info: no data term is live (fdapde_block_set_obs)");
+    if (n_obs) *n_obs = O.host.n_obs;
+    if (nnz) *nnz = O.host.nnz;
+    if (team_rows) *team_rows = O.team_rows;
+    if (team_cols) *team_cols = O.team_cols;
     return FDAPDE_OK;
 }
 
@@ -227,6 +358,7 @@ int e_block_spmv(fdapde_ctx* c, const double* x, double* y) {
     HIPCHK(c, hipMemcpyAsync(B.ext.p, x, sizeof(double) * (size_t)(2 * n), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_block_stage, dim3(g1(n), 1), dim3(256), 0, st, n, c->dof_i2e.p, B.ext.p, nullptr, B.w.p);
     launch_block_spmv(c, B.raw.p, B.w.p, B.t.p, nullptr);
+    if (B.obs.live) launch_obs_term(c, B, nullptr, B.w.p, B.t.p, nullptr);
     hipLaunchKernelGGL(k_block_unstage, dim3(g1(n), 1), dim3(256), 0, st, n, c->dof_i2e.p, B.t.p, B.ext.p);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(y, B.ext.p, sizeof(double) * (size_t)(2 * n), hipMemcpyDeviceToHost, st));
@@ -234,7 +366,9 @@ int e_block_spmv(fdapde_ctx* c, const double* x, double* y) {
     return FDAPDE_OK;
 }
 
-// times `reps` launches of k_block_spmv on the scaled values (the launch inside the Krylov stage) with HIP events on the context's stream
+// times `reps` applications of the Krylov stage's operator with HIP events on the context's stream: k_block_spmv on the scaled values and, with a data term
+// live, k_obs_gather and k_obs_scatter behind it.  Algorithmic bytes per application, every array once per pass: 36 nnz + 4 (n + 1) + 32 n for the block
+// product; the term adds (kernels_obs.h), nz = nnz(Psi), m = n_obs: gather 12 nz + 4 (m + 1) + 8 m + 8 n + 8 m, scatter 12 nz + 4 (n + 1) + 8 m + 16 n + 32 n
 int e_block_bench_spmv(fdapde_ctx* c, int32_t reps, double* avg_ms, double* algorithmic_bytes) {
     if (!c || reps < 1) return FDAPDE_EINVAL;
     if (int rc = block_guard(c)) return rc;
@@ -243,15 +377,21 @@ int e_block_bench_spmv(fdapde_ctx* c, int32_t reps, double* avg_ms, double* algo
     BlockHandle& B = *c->block;
     const int64_t n = B.n;
     hipLaunchKernelGGL(k_fill_f64, dim3(g1(2 * n)), dim3(256), 0, c->stream, 2 * n, 1.0, B.w.p);
-    for (int i = 0; i < 3; ++i) launch_block_spmv(c, B.scaled.p, B.w.p, B.t.p, nullptr);
+    for (int i = 0; i < 3; ++i) launch_block_op(c, B, B.w.p, B.t.p, nullptr);
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-    for (int i = 0; i < reps; ++i) launch_block_spmv(c, B.scaled.p, B.w.p, B.t.p, nullptr);
+    for (int i = 0; i < reps; ++i) launch_block_op(c, B, B.w.p, B.t.p, nullptr);
     HIPCHK(c, hipEventRecord(c->ev1, c->stream));
     HIPCHK(c, hipEventSynchronize(c->ev1));
     float ms = 0;
     HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
     if (avg_ms) *avg_ms = (double)ms / reps;
-    if (algorithmic_bytes) *algorithmic_bytes = 36.0 * (double)B.nnz + 4.0 * (double)(n + 1) + 32.0 * (double)n;
+    if (algorithmic_bytes) {
+        *algorithmic_bytes = 36.0 * (double)B.nnz + 4.0 * (double)(n + 1) + 32.0 * (double)n;
+        if (B.obs.live) {
+            const double nz = (double)B.obs.host.nnz, m = (double)B.obs.host.n_obs;
+            *algorithmic_bytes += 24.0 * nz + 4.0 * (m + 1) + 4.0 * (double)(n + 1) + 24.0 * m + 56.0 * (double)n;
+        }
+    }
     return FDAPDE_OK;
 }
 

@@ -63,7 +63,7 @@ int level_dinv(fdapde_ctx* c, BamgLevel& L, bool* bad) {
     HIPCHK(c, flag.alloc(1));
     HIPCHK(c, hipMemsetAsync(flag.p, 0, sizeof(int32_t), st));
     HIPCHK(c, L.dinv4.alloc(4 * (size_t)L.n));
-    hipLaunchKernelGGL(k_block_diag_inv, dim3(gn(L.n)), dim3(256), 0, st, L.n, L.rp, L.ci, L.bv, L.dinv4.p, flag.p);
+    hipLaunchKernelGGL(k_block_diag_inv, dim3(gn(L.n)), dim3(256), 0, st, L.n, L.rp, L.ci, L.bv, (const double*)nullptr, L.dinv4.p, flag.p);
     HIPCHK(c, hipGetLastError());
     int32_t h = 0;
     HIPCHK(c, hipMemcpyAsync(&h, flag.p, sizeof h, hipMemcpyDeviceToHost, st));

@@ -224,6 +224,8 @@ int e_block_compute(fdapde_ctx* c, const double* a11, const double* a12, const d
 int e_block_solve(fdapde_ctx* c, const fdapde_options* opt, const double* b, int32_t n_rhs, double* x, fdapde_info* info);
 int e_block_spmv(fdapde_ctx* c, const double* x, double* y);
 int e_block_bench_spmv(fdapde_ctx* c, int32_t reps, double* avg_ms, double* algorithmic_bytes);
+int e_block_set_obs(fdapde_ctx* c, int64_t n_obs, const int64_t* rowptr, const int32_t* colidx, const double* values, const double* weights, double scale);
+int e_block_obs_info(fdapde_ctx* c, int64_t* n_obs, int64_t* nnz, int32_t* team_rows, int32_t* team_cols);
 int e_gram_pointwise(fdapde_ctx* c, int64_t n_locs, const int32_t* cell_ids, const double* values, const double* weights, double* out_values);
 // eng_kron.hip: Kronecker-sum operators sum_k T_k (x) S_k, T_k dense q x q, S_k on the FEM pattern (the space-time systems' handle)
 void kron_release(fdapde_ctx* c);

@@ -18,6 +18,7 @@
 //   kernels_krylov.h    Jacobi scaling, CG / BiCGStab vector kernels, multi-GPU interface exchange, numbering changes
 //   kernels_multirhs.h  Q right-hand sides at once against one prepared system (SpMM + batched fused-update CG)
 //   kernels_persist.h   the whole CG solve of a small system as one launch (matrix resident in LDS, granule hand-offs)
+//   kernels_obs.h       the factored data term Psi^T W Psi of the 2 x 2 block handle (two rectangular sparse products)
 #ifndef FDAPDE_KERNELS_H
 #define FDAPDE_KERNELS_H
 
@@ -29,5 +30,6 @@
 #include "kernels_multirhs.h"
 #include "kernels_persist.h"
 #include "kernels_small.h"
+#include "kernels_obs.h"
 
 #endif

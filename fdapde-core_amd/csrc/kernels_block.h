@@ -67,14 +67,16 @@ static __global__ void k_block_pack(int64_t nnz, const int32_t* slot_i2e, const 
     o[1] = blk_v2f64_t{ext[2 * nnz + e], ext[3 * nnz + e]};
 }
 
-// D_i^-1 of every DOF's diagonal block; flag raised where |det| <= 1e-14 max|entry|^2 (or the block is missing / not finite): no block-Jacobi form
-static __global__ void k_block_diag_inv(int64_t n, const int32_t* rowptr, const int32_t* colidx, const double* raw, double* dinv, int32_t* flag) {
+// D_i^-1 of every DOF's diagonal block; flag raised where |det| <= 1e-14 max|entry|^2 (or the block is missing / not finite): no block-Jacobi form.
+// add11: a per-DOF addend to the (1,1) entry of D_i (the factored data term's share, kernels_obs.h k_obs_diag), or NULL
+static __global__ void k_block_diag_inv(int64_t n, const int32_t* rowptr, const int32_t* colidx, const double* raw, const double* add11, double* dinv, int32_t* flag) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int32_t k0 = rowptr[i], k1 = rowptr[i + 1];
     const int32_t d = blk_lower_bound(colidx, k0, k1, (int32_t)i);
     double a = 0, b = 0, cc = 0, e = 0;
     if (d < k1 && colidx[d] == (int32_t)i) a = raw[4 * (int64_t)d], b = raw[4 * (int64_t)d + 1], cc = raw[4 * (int64_t)d + 2], e = raw[4 * (int64_t)d + 3];
+    if (add11) a += add11[i];
     const double det = a * e - b * cc;
     const double mx = fmax(fmax(fabs(a), fabs(b)), fmax(fabs(cc), fabs(e)));
     double* o = dinv + 4 * i;

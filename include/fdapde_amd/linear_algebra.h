@@ -4,7 +4,9 @@
 //   PartialPivLU         small dense LU (q x q)             stands in for Eigen::PartialPivLU<DMatrix<double>>
 //   SMW<SparseSolver>    Sherman-Morrison-Woodbury solve    fdaPDE/linear_algebra/smw.h:38-59
 //   SparseBlockMatrix<double,2,2>   four sparse blocks as one matrix   fdaPDE/linear_algebra/sparse_block_matrix.h:29-128
-//                        (what PDE::BlockSolver factors: SMW<PDE<...>::BlockSolver> solves the smoothing system under a low-rank update)
+//                        (what PDE::BlockSolver factors: SMW<PDE<...>::BlockSolver> solves the smoothing system under a low-rank update; the data term
+//                        Psi^T W Psi may stay factored -- BlockSolver::compute(A, Psi, weights, scale), set_observations -- which is the only door for an
+//                        areal Psi, whose Psi^T Psi does not lie on the pattern a block must lie on)
 //   Kronecker(T, S), KroneckerSum   lazy dense (x) sparse products and their sums   fdaPDE/linear_algebra/kronecker_product.h:56-80
 //                        (what PDE::KroneckerSolver factors without forming the product: the space-time systems; eval() gives the explicit matrix)
 // The heavy step of SMW, A^{-1} [b | U] (1 + q right-hand sides against one prepared sparse system), runs on the device as ONE

@@ -578,6 +578,25 @@ template <typename D, typename F, int R> class PDE<D, DifferentialExpr, F, FEM_H
             for (int q = 0; q < 4; ++q) p[q] = on_pattern(m.block(q / 2, q % 2), v[q]);
             computed_ = fdapde_block_compute(ctx_.get(), p[0], p[1], p[2], p[3], symmetric ? 1 : 0) == FDAPDE_OK;
         }
+        // ... with the data term kept factored: the matrix is m + scale [ Psi^T W Psi, 0 ; 0, 0 ] (fdapde_block_set_obs).  Psi: what eval_basis(0 | 1, .) and
+        // eval_basis_nearest return -- an areal Psi, whose Psi^T Psi is far off the pattern, goes through this door only; the smoothing system leaves
+        // m.block(0, 0) without entries and passes scale = -1.  weights: one per row of Psi, or empty (W = I).
+        template <typename BlockMatrix>
+        void compute(const BlockMatrix& m, const SpMatrix<double>& Psi, const DVector<double>& weights = DVector<double> {}, double scale = -1.0,
+                     bool symmetric = false) {
+            compute(m, symmetric);
+            if (computed_) set_observations(Psi, weights, scale);
+        }
+        // replaces the data term of the computed matrix (an iteratively reweighted model changes W this way); a Psi without rows clears it
+        void set_observations(const SpMatrix<double>& Psi, const DVector<double>& weights = DVector<double> {}, double scale = -1.0) {
+            if (!computed_) throw std::runtime_error("BlockSolver: compute() first");
+            if (Psi.rows() > 0 && Psi.cols() != n_) throw std::runtime_error("BlockSolver: Psi needs n_dofs columns");
+            if (!is_empty(weights) && weights.size() != Psi.rows()) throw std::runtime_error("BlockSolver: one weight per row of Psi");
+            const std::vector<int64_t> rowptr(Psi.rowptr.begin(), Psi.rowptr.end());
+            const int rc = fdapde_block_set_obs(ctx_.get(), Psi.rows(), Psi.rows() > 0 ? rowptr.data() : nullptr, Psi.colidx.data(), Psi.values.data(),
+                                                is_empty(weights) ? nullptr : weights.data(), scale);
+            if (rc != FDAPDE_OK) throw std::runtime_error(fdapde_last_error(ctx_.get()));
+        }
         DMatrix<double> solve(const DMatrix<double>& b) const {
             if (!computed_) throw std::runtime_error("BlockSolver: compute() first");
             if (b.rows() != 2 * n_) throw std::runtime_error("BlockSolver: right-hand sides need 2 n_dofs rows");

@@ -337,8 +337,26 @@ int fdapde_lin_solve(fdapde_ctx *ctx, const fdapde_options *opt, const double *b
  * fdapde_block_compute and dropped with the matrix; see the enumerator.  Every other method: FDAPDE_EUNSUPPORTED.  info as fdapde_lin_solve: iters summed over the columns, relres
  * the worst column's, method_used the stage; FDAPDE_ENOCONV leaves the last iterate of every column in x.
  * fdapde_block_spmv: y = A x with the unscaled blocks, stacked host vectors of 2 n_dofs (parity tests, the byte figure).
- * fdapde_block_bench_spmv: times `reps` launches of the Krylov stage's operator kernel (k_block_spmv on D^-1 A) with HIP events; algorithmic bytes per
- * launch 36 nnz + 4 (n + 1) + 32 n.
+ * fdapde_block_bench_spmv: times `reps` applications of the Krylov stage's operator (k_block_spmv on D^-1 A and, with a data term live, its two products
+ * behind it) with HIP events; algorithmic bytes per application 36 nnz + 4 (n + 1) + 32 n, and with a term of nz entries in n_obs rows, every array once
+ * per pass, 24 nz + 4 (n_obs + 1) + 4 (n + 1) + 24 n_obs + 56 n more (Psi and Psi^T: values and columns; both row-start arrays; w, and t written and read;
+ * the first unknowns of x; the first column of D^-1; y read and written).
+ * fdapde_block_set_obs: the data term kept FACTORED -- after it the handle's matrix is A + scale [ Psi^T W Psi, 0 ; 0, 0 ], A the four blocks of the last
+ * fdapde_block_compute, Psi an n_obs x n_dofs CSR matrix (rowptr of n_obs + 1, columns = DOF ids in the reference numbering, strictly ascending within a
+ * row; empty rows allowed -- a point outside the mesh), W = diag(weights), NULL = ones.  The smoothing system passes scale = -1 and leaves a11 NULL.  Rows may
+ * be of any length: an areal design (eval_basis with areal_evaluation, basis/lagrangian_basis.h:203-283) has rows over every DOF of a region, and Psi^T Psi
+ * is far off the pattern, which fdapde_block_compute cannot take.  Every product applies Psi^T (W (Psi x_1)) as two sparse rectangular products (work
+ * linear in nnz(Psi), no atomics, a fixed summation order: the same bits every run; for pointwise designs the reproducible alternative to
+ * fdapde_gram_pointwise).  A team of 8 or 64 lanes per row, chosen per matrix for Psi and Psi^T separately: a mean row length above 16 takes 64 (knob
+ * "block_obs_team").  The term's diagonal joins D: it may make a diagonal block invertible, or singular.  Needs a live block handle (FDAPDE_ENOTINIT);
+ * FDAPDE_EINVAL, checked on the host before anything is launched and with the previous term left live, for a column outside [0, n_dofs), a row not
+ * strictly ascending, a non-monotone rowptr, a non-finite value, weight or scale; n_obs = 0 or a NULL rowptr clears the term; a second call replaces it (an
+ * iteratively reweighted model changes W that way); fdapde_block_compute and fdapde_dofs_build drop it.  The call drops a live dense inverse and a live
+ * FDAPDE_SOLVER_BLOCK_AMG hierarchy.  With a term live FDAPDE_SOLVER_GMRES, FDAPDE_SOLVER_DENSE (the host merges scale Psi^T W Psi into the 2 n-row
+ * matrix: set-up) and the open method work as before; FDAPDE_SOLVER_BLOCK_AMG answers FDAPDE_EUNSUPPORTED (its hierarchy is built from pattern entries).
+ * Ranks of a multi-GPU job and multi-device contexts: FDAPDE_EUNSUPPORTED.
+ * fdapde_block_obs_info: the live term's rows and entries and the lanes per row of Psi (team_rows) and of Psi^T (team_cols); any pointer may be NULL;
+ * without a term FDAPDE_ENOTINIT.
  * fdapde_gram_pointwise: Psi^T W Psi on the FEM pattern (nnz values aligned with fdapde_pattern_get) from what fdapde_eval_pointwise / fdapde_project hand
  * out: reference cell ids and row-major n_locs x n_basis values; rows with cell id -1 are skipped, weights may be NULL (all ones); a cell id the mesh does
  * not have: FDAPDE_EINVAL.  Accumulated on the device with fp64 atomics: the order of the additions, hence the last bits, may differ run to run. */
@@ -347,6 +365,9 @@ int fdapde_block_solve(fdapde_ctx *ctx, const fdapde_options *opt, const double 
 int fdapde_block_spmv(fdapde_ctx *ctx, const double *x, double *y);
 int fdapde_block_bench_spmv(fdapde_ctx *ctx, int32_t reps, double *avg_ms, double *algorithmic_bytes);
 int fdapde_gram_pointwise(fdapde_ctx *ctx, int64_t n_locs, const int32_t *cell_ids, const double *values, const double *weights, double *out_values);
+int fdapde_block_set_obs(fdapde_ctx *ctx, int64_t n_obs, const int64_t *rowptr, const int32_t *colidx, const double *values,
+                         const double *weights, double scale);
+int fdapde_block_obs_info(fdapde_ctx *ctx, int64_t *n_obs, int64_t *nnz, int32_t *team_rows, int32_t *team_cols);
 
 /* ---- Kronecker-sum operators on the FEM pattern: A = sum_{k < n_terms} T_k (x) S_k -- the reference's Kronecker(A, B) (fdaPDE/linear_algebra/
  *      kronecker_product.h:56-80), which it evaluates into an explicit sparse matrix and hands to SparseLU: every block of a space-time separable smoothing
@@ -592,6 +613,8 @@ int fdapde_partition_peers(fdapde_ctx *ctx, int32_t rank, int32_t *n_peers, int3
  *                 fdapde_block_solve under FDAPDE_SOLVER_BLOCK_AMG solve side by side -- n_rhs columns go in batches of 8, then 4, then 2, a last one
  *                 alone; every column's iterates are those of a column-by-column run, bit for bit --: 1, 2, 4 or 8; 8.  1 = column by column.  The
  *                 hierarchy stays)
+ *   block handle  "block_obs_team" (lanes per row of the data term's two products: 0, the default = 64 where the mean row length of Psi -- of Psi^T for the
+ *                 second product -- is above 16, else 8; 8 or 64 force that width for both; read by the next fdapde_block_set_obs)
  *   Kronecker     "kron_dinv_mb" (the MiB the inverted diagonal blocks of the Kronecker handle may take, >= 0; 2048; read by the next fdapde_kron_compute),
  *                 "kron_fuse" (1, the default: D^-1 applied in the epilogue of the operator kernel; 0: by a batched q x q matvec kernel of its own),
  *                 "kron_amg_term" (FDAPDE_SOLVER_KRON_AMG aggregates on the spatial factor of that term of fdapde_kron_compute as given, 0 .. 7; -1, the
