@@ -54,6 +54,7 @@ SYMBOLS = [
     "fdapde_block_compute", "fdapde_block_solve", "fdapde_block_spmv", "fdapde_block_bench_spmv", "fdapde_gram_pointwise",
     "fdapde_block_set_obs", "fdapde_block_obs_info",
     "fdapde_kron_compute", "fdapde_kron_solve", "fdapde_kron_spmv", "fdapde_kron_bench_spmv",
+    "fdapde_kron_set_obs", "fdapde_kron_obs_info",
     "fdapde_kron_amg_hierarchy", "fdapde_kron_amg_aggregates",
     "fdapde_amg_hierarchy", "fdapde_amg_aggregates", "fdapde_amg_order", "fdapde_amg_damping", "fdapde_amg_cols_trace",
 ]
@@ -574,6 +575,54 @@ class Context:
         ms, by = C.c_double(), C.c_double()
         self._check(self.lib.fdapde_kron_bench_spmv(self._ctx, reps, C.byref(ms), C.byref(by)))
         return ms.value, by.value
+
+    def kron_set_obs(self, Psi, Phi=None, weights=None, scale=-1.0):
+        """fdapde_kron_set_obs: the handle's matrix becomes A + scale (Phi (x) Psi)^T W (Phi (x) Psi), the term kept factored.  Psi: a scipy.sparse matrix
+        (n_obs x n_dofs; duplicates summed, columns sorted), a triple (rowptr, colidx, values) handed to the library as it is, or None (clears the term).
+        Phi: dense p x q, or None ([I_p 0] with p taken from the weights' first axis, else q).  weights: (p, n_obs) or flat (instant-major), or None (W = I)"""
+        if Psi is None:
+            self._check(self.lib.fdapde_kron_set_obs(self._ctx, 1, None, C.c_int64(0), None, None, None, None, C.c_double(scale)))
+            return
+        if isinstance(Psi, (tuple, list)):
+            rp, ci, v = Psi
+        else:
+            m = Psi.tocsr().copy()
+            m.sum_duplicates()
+            m.sort_indices()
+            if m.shape[1] != self.sizes()["n_dofs"]:
+                raise ValueError("kron_set_obs(): Psi needs n_dofs columns")
+            rp, ci, v = m.indptr, m.indices, m.data
+        rp = np.ascontiguousarray(rp, dtype=np.int64).reshape(-1)
+        ci = np.ascontiguousarray(ci, dtype=np.int32).reshape(-1)
+        v = np.ascontiguousarray(v, dtype=float).reshape(-1)
+        if rp.size < 1 or ci.size != v.size or (rp.size > 1 and rp.max() > ci.size):
+            raise ValueError("kron_set_obs(): rowptr / colidx / values do not fit together")
+        n_obs = rp.size - 1
+        phi = None
+        if Phi is not None:
+            phi = np.asfortranarray(np.asarray(Phi, dtype=float))
+            if phi.ndim != 2 or (getattr(self, "_kron_q", 0) and phi.shape[1] != self._kron_q):
+                raise ValueError("kron_set_obs(): Phi must be p x q")
+            p = phi.shape[0]
+        elif weights is not None and np.ndim(weights) == 2:
+            p = np.shape(weights)[0]
+        elif weights is not None and n_obs > 0:
+            p = np.size(weights) // n_obs
+        else:
+            p = getattr(self, "_kron_q", 0)
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=float).reshape(-1)
+            if w.size != p * n_obs:
+                raise ValueError("kron_set_obs(): p n_obs weights")
+        self._check(self.lib.fdapde_kron_set_obs(self._ctx, int(p), None if phi is None else _dp(phi), C.c_int64(n_obs), rp.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                 _ip(ci), _dp(v), None if w is None else _dp(w), C.c_double(scale)))
+
+    def kron_obs_info(self):
+        """fdapde_kron_obs_info -> dict(p, n_obs, nnz, form_rows, form_cols): the live data term's sizes and the form (1 narrow, 2 wide) for Psi / for Psi^T"""
+        p, n_obs, nnz, fr, fc = C.c_int32(), C.c_int64(), C.c_int64(), C.c_int32(), C.c_int32()
+        self._check(self.lib.fdapde_kron_obs_info(self._ctx, C.byref(p), C.byref(n_obs), C.byref(nnz), C.byref(fr), C.byref(fc)))
+        return {"p": p.value, "n_obs": n_obs.value, "nnz": nnz.value, "form_rows": fr.value, "form_cols": fc.value}
 
     def kron_amg_hierarchy(self):
         """fdapde_kron_amg_hierarchy: the live hierarchy of FDAPDE_SOLVER_KRON_AMG (rows counted as q n_l, entries as q^2 nnz_l) ->

@@ -374,6 +374,17 @@ int fdapde_kron_bench_spmv(fdapde_ctx* c, int32_t reps, double* avg_ms, double* 
     if (c->group) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, kKronNoGroup);
     return fdapde_engine::e_kron_bench_spmv(c, reps, avg_ms, algorithmic_bytes);
 }
+int fdapde_kron_set_obs(fdapde_ctx* c, int32_t p, const double* Phi, int64_t n_obs, const int64_t* rowptr, const int32_t* colidx, const double* values,
+                        const double* weights, double scale) {
+    if (!c) return FDAPDE_EINVAL;
+    if (c->group) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, kKronNoGroup);
+    return fdapde_engine::e_kron_set_obs(c, p, Phi, n_obs, rowptr, colidx, values, weights, scale);
+}
+int fdapde_kron_obs_info(fdapde_ctx* c, int32_t* p, int64_t* n_obs, int64_t* nnz, int32_t* form_rows, int32_t* form_cols) {
+    if (!c) return FDAPDE_EINVAL;
+    if (c->group) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, kKronNoGroup);
+    return fdapde_engine::e_kron_obs_info(c, p, n_obs, nnz, form_rows, form_cols);
+}
 // the Kronecker handle's live hierarchy as data: amg_describe / amg_aggregates on it
 int fdapde_kron_amg_hierarchy(fdapde_ctx* c, int32_t cap, int32_t* n_levels, int64_t* rows, int64_t* nnz, int32_t* absorbed, double* setup_ms) {
     if (!c || cap < 0 || (cap > 0 && !rows && !nnz)) return FDAPDE_EINVAL;
@@ -601,6 +612,7 @@ int fdapde_tune(fdapde_ctx* c, const char* key, int32_t value) {
     else if (k == "block_obs_team" && (value == 0 || value == 8 || value == 64)) c->block_obs_team = value;   // (read by the next fdapde_block_set_obs)
     else if (k == "kron_dinv_mb" && value >= 0) c->kron_dinv_mb = value;   // (read by the next fdapde_kron_compute)
     else if (k == "kron_fuse" && (value == 0 || value == 1)) c->kron_fuse = value;
+    else if (k == "kron_obs_form" && value >= 0 && value <= 2) c->kron_obs_form = value;   // (read by the next fdapde_kron_set_obs)
     else if (k == "kron_amg_term" && value >= -1 && value < 8) {   // read by the build of the hierarchy: a live one goes
         if (value != c->kron_amg_term) fdapde_engine::kron_amg_forget(c);
         c->kron_amg_term = value;

@@ -513,7 +513,8 @@ struct fdapde_ctx {
     int block_obs_team = 0;       // knob: lanes per row of the block handle's data term (kernels_obs.h): 0 = by mean row length (above 16: 64, else 8), 8, 64; read by fdapde_block_set_obs
     int kron_dinv_mb = 2048;      // knob: the inverted diagonal blocks of the Kronecker handle (8 q^2 n bytes) may take that many MiB; above it fdapde_kron_compute builds none (no Krylov stage)
     int kron_fuse = 1;            // knob: 1 = D^-1 applied in the epilogue of k_kron_spmv, 0 = by k_kron_dinv_apply in a launch of its own (measured: DESIGN.md section 15)
-    int kron_amg_term = -1;       // knob: FDAPDE_SOLVER_KRON_AMG aggregates on the spatial factor of that term of fdapde_kron_compute as given (-1: on -sum |T_sigma|_F |S_sigma|)
+    int kron_obs_form = 0;        // knob: the form of the Kronecker handle's data-term kernels (kernels_kron_obs.h): 0 = by mean row length (above 16: wide), 1 narrow, 2 wide; read by fdapde_kron_set_obs
+    int kron_amg_term = -1;      // knob: FDAPDE_SOLVER_KRON_AMG aggregates on the spatial factor of that term of fdapde_kron_compute as given (-1: on -sum |T_sigma|_F |S_sigma|)
     int64_t amg_lin_epoch = 0;    // fdapde_lin_compute calls: the handle's hierarchy belongs to the matrix of one of them
     int64_t amg_coarse_rows = 1024;   // knob: coarsening stops at a level of at most that many rows, which is inverted once (dense_build_estimate_ms(1024) ~ 2.5 ms)
     int amg_absorb = 2;           // knob: 0 = the multilevel set-ups pair only, 1 = every pass also absorbs the rows it left single, 2 = pair only and, where that ends in

@@ -92,7 +92,7 @@ int clone_state(const fdapde_ctx* s, fdapde_ctx* d) {
         HIPCHK(d, d->force.alloc(n * cols));
     }
     d->amg_cols = s->amg_cols;
-    d->kron_dinv_mb = s->kron_dinv_mb, d->kron_fuse = s->kron_fuse, d->kron_amg_term = s->kron_amg_term;   // (the knobs, not the handle)
+    d->kron_dinv_mb = s->kron_dinv_mb, d->kron_fuse = s->kron_fuse, d->kron_amg_term = s->kron_amg_term, d->kron_obs_form = s->kron_obs_form;   // (the knobs, not the handle)
     d->asm_fq_bc = s->asm_fq_bc, d->asm_fq_block = s->asm_fq_block, d->asm_fuse_mass = s->asm_fuse_mass, d->asm_row_stat = s->asm_row_stat;
     if (s->have_g)
         if (int rc = copy_buf(d, d->g, s->g, n)) return rc;

@@ -6,22 +6,41 @@
 //                            (by name) flexible GMRES around the point-block multilevel cycle of eng_kron_amg.hip
 //   fdapde_kron_spmv         y = A x
 //   fdapde_kron_bench_spmv   HIP-event timing of the Krylov stage's operator
+//   fdapde_kron_set_obs      the data term kept factored: the handle's matrix becomes A + scale (Phi (x) Psi)^T W (Phi (x) Psi) with Phi small and dense, Psi a
+//                            CSR matrix of any row length, W diagonal (areal designs, missing observations, observation instants off the time nodes); set-up in
+//                            host_kron_obs.cpp / host_obs.cpp, the two products per application in kernels_kron_obs.h
 // Independent of the n x n handle of fdapde_lin_compute and of the 2 x 2 block handle: nothing here writes a buffer one of the other solves reads back.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <string>
+#include <type_traits>
 #include <vector>
 
 #include "context.h"
 #include "engine.h"
 #include "eng_gmres.h"
 #include "host_kron.h"
+#include "host_kron_obs.h"
 #include "kernels_dense.h"
 #include "kernels_gmres.h"
 #include "kernels_kron.h"
+#include "kernels_kron_obs.h"
 #include "kernels_krylov.h"
 
 namespace fdapde_engine {
+
+// the factored data term of the current matrix (fdapde_kron_set_obs): Psi and Psi^T in the internal order on the device, host copies for the dense stage
+struct KronObs {
+    bool live = false;
+    double scale = 0;
+    int p = 0, QP = 2;                  // rows of Phi, team width of the term's kernels (the power of two >= max(p, q))
+    int form_rows = 1, form_cols = 1;   // 1 narrow / 2 wide for Psi (k_kron_obs_gather) / for Psi^T (k_kron_obs_scatter, k_kron_obs_diag)
+    fdapde_hip::ObsHost host;
+    std::vector<double> h_phi, h_w;     // [p q] column-major, [n_obs p] interleaved per observation
+    DBuf<int32_t> rp, ci, trp, tci;
+    DBuf<double> v, tv, w, phi, t, g;   // t [n_obs p]: W (Phi (x) Psi) x between the two products; g [n p]: the term's share of every diagonal block
+};
 
 struct KronHandle {
     bool ready = false, symmetric = false;
@@ -44,6 +63,7 @@ struct KronHandle {
     int n_terms = 0, term_sg[kKronMaxTerms] = {};   // the spatial factor every term of the caller's went into
     double tnorm[kKronMaxTerms] = {};  // |T_sigma|_F of the summed time factors (entries in storage order)
     KronAmg* amg = nullptr;            // FDAPDE_SOLVER_KRON_AMG's hierarchy of the current matrix (eng_kron_amg.hip), built by its first solve
+    KronObs obs;
     ~KronHandle() { kron_amg_free(amg); }
 };
 
@@ -128,11 +148,15 @@ void launch_kron_dinv(fdapde_ctx* c, const KronHandle& K, const double* x, doubl
     }
 }
 
+// (with a data term live: its share Phi^T diag(g_i) Phi joins D_i)
 void launch_kron_diag_inv(fdapde_ctx* c, KronHandle& K) {
     const dim3 grid(g1(K.n, 64 / K.Q)), block(64);
+    const double *g = K.obs.live ? K.obs.g.p : nullptr, *phi = K.obs.live ? K.obs.phi.p : nullptr;
+    const int p = K.obs.live ? K.obs.p : 0;
 #define FDAPDE_KRON_DIAG(QQ)                                                                                                                                   \
     case QQ:                                                                                                                                                   \
-        hipLaunchKernelGGL(k_kron_diag_inv<QQ>, grid, block, 0, c->stream, K.n, K.q, K.ns, c->rowptr.p, c->colidx.p, K.vals.p, K.tm.p, K.dinv.p, K.flag.p);    \
+        hipLaunchKernelGGL(k_kron_diag_inv<QQ>, grid, block, 0, c->stream, K.n, K.q, K.ns, c->rowptr.p, c->colidx.p, K.vals.p, K.tm.p, g, phi, p, K.dinv.p,    \
+                           K.flag.p);                                                                                                                          \
         break;
     switch (K.Q) {
         FDAPDE_KRON_DIAG(2)
@@ -145,8 +169,38 @@ void launch_kron_diag_inv(fdapde_ctx* c, KronHandle& K) {
 #undef FDAPDE_KRON_DIAG
 }
 
+template <typename F> void by_obs_team(int QP, F&& f) {
+    switch (QP) {
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 8: f(std::integral_constant<int, 8>{}); break;
+    case 16: f(std::integral_constant<int, 16>{}); break;
+    case 32: f(std::integral_constant<int, 32>{}); break;
+    case 64: f(std::integral_constant<int, 64>{}); break;
+    }
+}
+
+// y += [D^-1] scale (Phi (x) Psi)^T W (Phi (x) Psi) x (dinv = NULL: without D^-1) behind a product that wrote y: two launches, the forms as chosen per matrix
+void launch_kron_obs(fdapde_ctx* c, const KronHandle& K, const double* dinv, const double* x, double* y, const int32_t* stop) {
+    const KronObs& O = K.obs;
+    const int64_t m = O.host.n_obs, n = K.n;
+    hipStream_t st = c->stream;
+    by_obs_team(O.QP, [&](auto t) {
+        constexpr int QP = decltype(t)::value;
+        if (O.form_rows == 2)
+            hipLaunchKernelGGL((k_kron_obs_gather<QP, true>), dim3((unsigned)m), dim3(256), 0, st, m, K.q, O.p, O.rp.p, O.ci.p, O.v.p, O.phi.p, O.w.p, x, O.t.p, stop);
+        else
+            hipLaunchKernelGGL((k_kron_obs_gather<QP, false>), dim3(g1(m, 256 / QP)), dim3(256), 0, st, m, K.q, O.p, O.rp.p, O.ci.p, O.v.p, O.phi.p, O.w.p, x, O.t.p, stop);
+        if (O.form_cols == 2)
+            hipLaunchKernelGGL((k_kron_obs_scatter<QP, true>), dim3((unsigned)n), dim3(256), 0, st, n, K.q, O.p, O.trp.p, O.tci.p, O.tv.p, O.phi.p, O.t.p, O.scale, dinv, y, stop);
+        else
+            hipLaunchKernelGGL((k_kron_obs_scatter<QP, false>), dim3(g1(n, 256 / QP)), dim3(256), 0, st, n, K.q, O.p, O.trp.p, O.tci.p, O.tv.p, O.phi.p, O.t.p, O.scale, dinv, y,
+                               stop);
+    });
+}
+
 // the Krylov stage's operator y = D^-1 A x: one launch with the inverse fused into the epilogue (knob kron_fuse = 1), or the product and the batched
-// q x q matvec as two
+// q x q matvec as two; with a data term live its two products behind either (D^-1 (A x) + D^-1 z: the same sums under both settings)
 void launch_kron_op(fdapde_ctx* c, const KronHandle& K, const double* x, double* y, const int32_t* stop) {
     if (c->kron_fuse) {
         launch_kron_spmv(c, K, true, x, y, stop);
@@ -154,6 +208,25 @@ void launch_kron_op(fdapde_ctx* c, const KronHandle& K, const double* x, double*
         launch_kron_spmv(c, K, false, x, y, stop);
         launch_kron_dinv(c, K, y, y, stop);
     }
+    if (K.obs.live) launch_kron_obs(c, K, K.dinv.p, x, y, stop);
+}
+
+// D^-1 of every DOF (with the live term's share) and the singular-block flag; synchronises
+int kron_rediag(fdapde_ctx* c, KronHandle& K) {
+    hipStream_t st = c->stream;
+    K.jacobi_ok = false;
+    if (!K.have_dinv) {
+        HIPCHK(c, hipStreamSynchronize(st));
+        return FDAPDE_OK;
+    }
+    HIPCHK(c, hipMemsetAsync(K.flag.p, 0, sizeof(int32_t), st));
+    launch_kron_diag_inv(c, K);
+    HIPCHK(c, hipGetLastError());
+    int32_t h_flag = 0;
+    HIPCHK(c, hipMemcpyAsync(&h_flag, K.flag.p, sizeof h_flag, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    K.jacobi_ok = h_flag == 0;
+    return FDAPDE_OK;
 }
 
 // restarted GMRES(m) on D^-1 A z = D^-1 b for the column staged in K.bt: handle_gmres (eng_gmres.h) over q n words
@@ -169,6 +242,27 @@ bool kron_dense_eligible(const fdapde_ctx* c, const KronHandle& K) {
 
 int kron_dense_build(fdapde_ctx* c, KronHandle& K) {
     const int64_t nq = (int64_t)K.q * K.n, nnz2 = (int64_t)K.q * K.q * K.nnz;
+    if (K.obs.live) {   // the term merged into the expanded matrix by the host (set-up): build and refinement see the true matrix
+        hipStream_t st = c->stream;
+        HIPCHK(c, K.rowptr2.alloc((size_t)(nq + 1)));
+        HIPCHK(c, K.colidx2.alloc((size_t)nnz2));
+        HIPCHK(c, K.val2.alloc((size_t)nnz2));
+        hipLaunchKernelGGL(k_kron_expand, dim3(g1(nq + 1)), dim3(256), 0, st, K.n, K.q, K.ns, c->rowptr.p, c->colidx.p, K.vals.p, K.tm.p, K.rowptr2.p, K.colidx2.p, K.val2.p);
+        HIPCHK(c, hipGetLastError());
+        std::vector<int32_t> rp((size_t)(nq + 1)), ci((size_t)nnz2), rp2, ci2;
+        std::vector<double> v((size_t)nnz2), v2;
+        HIPCHK(c, hipMemcpyAsync(rp.data(), K.rowptr2.p, sizeof(int32_t) * rp.size(), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(ci.data(), K.colidx2.p, sizeof(int32_t) * ci.size(), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(v.data(), K.val2.p, sizeof(double) * v.size(), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        fdapde_hip::kron_obs_merge_dense(K.q, rp.data(), ci.data(), v.data(), K.obs.host, K.obs.p, K.obs.h_phi.data(), K.obs.h_w.data(), K.obs.scale, &rp2, &ci2, &v2);
+        K.expanded = false;   // (the buffers hold the merged matrix, not k_kron_expand's)
+        HIPCHK(c, K.rowptr2.upload(rp2.data(), rp2.size(), st));
+        HIPCHK(c, K.colidx2.upload(ci2.data(), ci2.size(), st));
+        HIPCHK(c, K.val2.upload(v2.data(), v2.size(), st));
+        HIPCHK(c, hipStreamSynchronize(st));   // (the host vectors have been read)
+        return dense_build_csr(c, nq, K.rowptr2.p, K.colidx2.p, K.val2.p, nullptr, 0, K.dense);
+    }
     if (!K.expanded) {
         HIPCHK(c, K.rowptr2.alloc((size_t)(nq + 1)));
         HIPCHK(c, K.colidx2.alloc((size_t)nnz2));
@@ -191,6 +285,8 @@ int kron_amg_solve(fdapde_ctx* c, KronHandle& K, const fdapde_options* opt, cons
     fdapde_info out{};
     out.method_used = FDAPDE_SOLVER_KRON_AMG;
     const auto t_call = std::chrono::steady_clock::now();
+    if (K.obs.live)
+        return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_KRON_AMG: a factored data term (fdapde_kron_set_obs) is live; the hierarchy is built from pattern entries only");
     if (!K.have_dinv)
         return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_KRON_AMG: the inverted diagonal blocks (8 q^2 n bytes) exceed the budget `kron_dinv_mb`: no block-Jacobi smoother");
     if (!K.jacobi_ok)
@@ -271,6 +367,7 @@ int e_kron_compute(fdapde_ctx* c, int32_t q, int32_t n_terms, const double* cons
         for (DBuf<double>* v : {&K.vals, &K.dinv, &K.ext, &K.bt, &K.x, &K.r, &K.w, &K.t, &K.gm_V, &K.val2, &K.dn_b, &K.dn_x, &K.dense.X}) v->release();
         K.rowptr2.release(), K.colidx2.release();
     }
+    K.obs.live = false;   // (the data term belonged to the previous matrix)
     K.ready = false, K.expanded = false, K.n = n, K.nnz = nnz, K.q = q, K.ns = ns, K.Q = team_width(q), K.symmetric = symmetric != 0;
     K.dense.ready = K.dense.failed = false, K.cols = 0, K.krylov_ms = 0, K.jacobi_ok = false;
     K.t_in_lds = ns * q * q <= kKronLdsFactorDoubles;
@@ -298,6 +395,88 @@ int e_kron_compute(fdapde_ctx* c, int32_t q, int32_t n_terms, const double* cons
     return FDAPDE_OK;
 }
 
+namespace {
+// what a change of the term invalidates: the dense inverse, the expanded matrix, the multilevel hierarchy, the rent-or-buy count
+void kron_matrix_changed(KronHandle& K) {
+    K.dense.ready = K.dense.failed = false, K.expanded = false, K.cols = 0, K.krylov_ms = 0;
+    kron_amg_free(K.amg), K.amg = nullptr;
+}
+}   // namespace
+
+int e_kron_set_obs(fdapde_ctx* c, int32_t p, const double* Phi, int64_t n_obs, const int64_t* rowptr, const int32_t* colidx, const double* values,
+                   const double* weights, double scale) {
+    if (!c) return FDAPDE_EINVAL;
+    if (int rc = kron_guard(c)) return rc;
+    if (!kron_live(c)) return fail(c, FDAPDE_ENOTINIT, kKronFirst);
+    if (n_obs < 0) return fail(c, FDAPDE_EINVAL, "fdapde_kron_set_obs: n_obs is negative");
+    HIPCHK(c, hipSetDevice(c->device));
+    KronHandle& K = *c->kron;
+    KronObs& O = K.obs;
+    hipStream_t st = c->stream;
+    const int64_t n = K.n;
+    if (n_obs == 0 || !rowptr) {   // clears the term
+        if (!O.live) return FDAPDE_OK;
+        HIPCHK(c, hipStreamSynchronize(st));
+        O.live = false;
+        kron_matrix_changed(K);
+        return kron_rediag(c, K);
+    }
+    std::string why;
+    if (!fdapde_hip::kron_obs_validate(n, K.q, p, Phi, n_obs, rowptr, colidx, values, weights, scale, &why)) {   // (nothing launched, the previous term stays)
+        c->err = why;
+        return FDAPDE_EINVAL;
+    }
+    if (int rc = ensure_host(c, kHostPerm)) return rc;
+    HIPCHK(c, hipStreamSynchronize(st));
+    fdapde_hip::ObsHost& P = O.host;
+    O.live = false;
+    kron_matrix_changed(K);
+    fdapde_hip::obs_build(n, n_obs, rowptr, colidx, values, nullptr, c->hs.dof_e2i.data(), &P);
+    fdapde_hip::kron_obs_phi(K.q, p, Phi, &O.h_phi);
+    fdapde_hip::kron_obs_weights(p, n_obs, weights, &O.h_w);
+    O.scale = scale, O.p = p, O.QP = fdapde_hip::kron_obs_team_width(K.q, p);
+    O.form_rows = fdapde_hip::kron_obs_form(P.n_obs, P.nnz, c->kron_obs_form);
+    O.form_cols = fdapde_hip::kron_obs_form(P.n, P.nnz, c->kron_obs_form);
+    HIPCHK(c, O.rp.upload(P.rp.data(), P.rp.size(), st));
+    HIPCHK(c, O.ci.upload(P.ci.data(), P.ci.size(), st));
+    HIPCHK(c, O.v.upload(P.v.data(), P.v.size(), st));
+    HIPCHK(c, O.trp.upload(P.trp.data(), P.trp.size(), st));
+    HIPCHK(c, O.tci.upload(P.tci.data(), P.tci.size(), st));
+    HIPCHK(c, O.tv.upload(P.tv.data(), P.tv.size(), st));
+    HIPCHK(c, O.w.upload(O.h_w.data(), O.h_w.size(), st));
+    HIPCHK(c, O.phi.upload(O.h_phi.data(), O.h_phi.size(), st));
+    HIPCHK(c, O.t.alloc((size_t)n_obs * p));
+    HIPCHK(c, O.g.alloc((size_t)n * p));
+    by_obs_team(O.QP, [&](auto t) {
+        constexpr int QP = decltype(t)::value;
+        if (O.form_cols == 2)
+            hipLaunchKernelGGL((k_kron_obs_diag<QP, true>), dim3((unsigned)n), dim3(256), 0, st, n, p, O.trp.p, O.tci.p, O.tv.p, O.w.p, scale, O.g.p, (const int32_t*)nullptr);
+        else
+            hipLaunchKernelGGL((k_kron_obs_diag<QP, false>), dim3(g1(n, 256 / QP)), dim3(256), 0, st, n, p, O.trp.p, O.tci.p, O.tv.p, O.w.p, scale, O.g.p,
+                               (const int32_t*)nullptr);
+    });
+    O.live = true;
+    if (int rc = kron_rediag(c, K)) {   // (synchronises: the uploads are done)
+        O.live = false;
+        return rc;
+    }
+    return FDAPDE_OK;
+}
+
+int e_kron_obs_info(fdapde_ctx* c, int32_t* p, int64_t* n_obs, int64_t* nnz, int32_t* form_rows, int32_t* form_cols) {
+    if (!c) return FDAPDE_EINVAL;
+    if (int rc = kron_guard(c)) return rc;
+    if (!kron_live(c)) return fail(c, FDAPDE_ENOTINIT, kKronFirst);
+    const KronObs& O = c->kron->obs;
+    if (!O.live) return fail(c, FDAPDE_ENOTINIT, "fdapde_kron_obs_info: no data term is live (fdapde_kron_set_obs)");
+    if (p) *p = O.p;
+    if (n_obs) *n_obs = O.host.n_obs;
+    if (nnz) *nnz = O.host.nnz;
+    if (form_rows) *form_rows = O.form_rows;
+    if (form_cols) *form_cols = O.form_cols;
+    return FDAPDE_OK;
+}
+
 int e_kron_spmv(fdapde_ctx* c, const double* x, double* y) {
     if (!c || !x || !y) return FDAPDE_EINVAL;
     if (int rc = kron_guard(c)) return rc;
@@ -309,6 +488,7 @@ int e_kron_spmv(fdapde_ctx* c, const double* x, double* y) {
     HIPCHK(c, hipMemcpyAsync(K.ext.p, x, sizeof(double) * (size_t)nq, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_kron_stage, dim3(g1(nq), 1), dim3(256), 0, st, n, K.q, c->dof_i2e.p, K.ext.p, K.w.p, (int64_t)K.q, (int64_t)1);
     launch_kron_spmv(c, K, false, K.w.p, K.t.p, nullptr);
+    if (K.obs.live) launch_kron_obs(c, K, nullptr, K.w.p, K.t.p, nullptr);
     hipLaunchKernelGGL(k_kron_unstage, dim3(g1(nq), 1), dim3(256), 0, st, n, K.q, c->dof_i2e.p, K.t.p, K.ext.p, (int64_t)K.q, (int64_t)1);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(y, K.ext.p, sizeof(double) * (size_t)nq, hipMemcpyDeviceToHost, st));
@@ -327,7 +507,10 @@ int e_kron_bench_spmv(fdapde_ctx* c, int32_t reps, double* avg_ms, double* algor
     const int64_t n = K.n, nq = (int64_t)K.q * n;
     auto op = [&]() {
         if (K.have_dinv) launch_kron_op(c, K, K.w.p, K.t.p, nullptr);
-        else launch_kron_spmv(c, K, false, K.w.p, K.t.p, nullptr);
+        else {
+            launch_kron_spmv(c, K, false, K.w.p, K.t.p, nullptr);
+            if (K.obs.live) launch_kron_obs(c, K, nullptr, K.w.p, K.t.p, nullptr);
+        }
     };
     hipLaunchKernelGGL(k_fill_f64, dim3(g1(nq)), dim3(256), 0, c->stream, nq, 1.0, K.w.p);
     for (int i = 0; i < 3; ++i) op();
@@ -339,8 +522,13 @@ int e_kron_bench_spmv(fdapde_ctx* c, int32_t reps, double* avg_ms, double* algor
     float ms = 0;
     HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
     if (avg_ms) *avg_ms = (double)ms / reps;
-    if (algorithmic_bytes)
+    if (algorithmic_bytes) {
         *algorithmic_bytes = 8.0 * K.ns * (double)K.nnz + 4.0 * (double)K.nnz + 4.0 * (double)(n + 1) + 16.0 * (double)nq + (K.have_dinv ? 8.0 * K.q * (double)nq : 0.0);
+        if (K.obs.live) {   // gather 12 nz + 4 (m + 1) + 8 q n + 16 p m, scatter 12 nz + 4 (n + 1) + 8 p m + 16 q n (+ 8 q^2 n in the Krylov stage)
+            const double nz = (double)K.obs.host.nnz, m = (double)K.obs.host.n_obs, pm = K.obs.p * m;
+            *algorithmic_bytes += 24.0 * nz + 4.0 * (m + 1) + 4.0 * (double)(n + 1) + 24.0 * pm + 24.0 * (double)nq + (K.have_dinv ? 8.0 * K.q * (double)nq : 0.0);
+        }
+    }
     return FDAPDE_OK;
 }
 

@@ -108,7 +108,8 @@ int level_dinv(fdapde_ctx* c, KronAmg& H, KamgLevel& L, bool* bad) {
     HIPCHK(c, L.dq_own.alloc((size_t)L.q * L.q * (size_t)std::max<int64_t>(L.n, 1)));
     by_kron_team(L.Q, [&](auto t) {
         constexpr int QQ = decltype(t)::value;
-        hipLaunchKernelGGL(k_kron_diag_inv<QQ>, dim3(g1(L.n, 64 / QQ)), dim3(64), 0, st, L.n, L.q, L.ns, L.rp, L.ci, L.sv, L.tm, L.dq_own.p, H.flag.p);
+        hipLaunchKernelGGL(k_kron_diag_inv<QQ>, dim3(g1(L.n, 64 / QQ)), dim3(64), 0, st, L.n, L.q, L.ns, L.rp, L.ci, L.sv, L.tm, (const double*)nullptr,
+                           (const double*)nullptr, 0,L.dq_own.p, H.flag.p);
     });
     HIPCHK(c, hipGetLastError());
     int32_t h = 0;

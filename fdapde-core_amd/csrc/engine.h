@@ -233,6 +233,9 @@ int e_kron_compute(fdapde_ctx* c, int32_t q, int32_t n_terms, const double* cons
 int e_kron_solve(fdapde_ctx* c, const fdapde_options* opt, const double* b, int32_t n_rhs, double* x, fdapde_info* info);
 int e_kron_spmv(fdapde_ctx* c, const double* x, double* y);
 int e_kron_bench_spmv(fdapde_ctx* c, int32_t reps, double* avg_ms, double* algorithmic_bytes);
+int e_kron_set_obs(fdapde_ctx* c, int32_t p, const double* Phi, int64_t n_obs, const int64_t* rowptr, const int32_t* colidx, const double* values,
+                   const double* weights, double scale);
+int e_kron_obs_info(fdapde_ctx* c, int32_t* p, int64_t* n_obs, int64_t* nnz, int32_t* form_rows, int32_t* form_cols);
 void kron_amg_forget(fdapde_ctx* c);   // the Kronecker handle's hierarchy is built again by its next solve (a set-up knob changed)
 int kron_amg_describe_ctx(const fdapde_ctx* c, int32_t cap, int32_t* n_levels, int64_t* rows, int64_t* nnz, int32_t* absorbed, double* setup_ms);
 int kron_amg_aggregates_ctx(fdapde_ctx* c, int32_t level, int64_t cap, int32_t* agg, int64_t* n_rows);

@@ -135,9 +135,11 @@ static __global__ __launch_bounds__(256) void k_kron_dinv_apply(int64_t n, int q
 // Gauss-Jordan with partial pivoting in LDS (lane l owns row l, resp. column l where a row is scaled or two rows are swapped; the row exchanges are undone
 // as column exchanges in reverse order at the end).  flag raised where a pivot is not above 1e-14 times the block's largest entry, or is not finite, or the
 // DOF has no diagonal entry: no point-block Jacobi form (the block's inverse is then left as the identity).  LDS: 64 Q doubles (32 KiB at Q = 64).
+// g ([p n], p contiguous per DOF), phi (p x q, column-major): the factored data term's share Phi^T diag(g_i) Phi of D_i (kernels_kron_obs.h k_kron_obs_diag),
+// added after the pattern's sum with tau ascending, or NULL.
 template <int Q>
 static __global__ __launch_bounds__(64) void k_kron_diag_inv(int64_t n, int q, int ns, const int32_t* rowptr, const int32_t* colidx, const double* vals, const double* tm,
-                                                             double* dinv, int32_t* flag) {
+                                                             const double* g, const double* phi, int p, double* dinv, int32_t* flag) {
 #pragma clang fp contract(off)
     __shared__ double a_all[64 * Q];
     __shared__ int32_t piv_all[64];
@@ -156,6 +158,8 @@ static __global__ __launch_bounds__(64) void k_kron_diag_inv(int64_t n, int q, i
             double v = 0.0;
             if (has)
                 for (int sg = 0; sg < ns; ++sg) v = __builtin_fma(tm[((size_t)sg * q + c) * q + l], vals[(int64_t)d * ns + sg], v);
+            if (g)
+                for (int tau = 0; tau < p; ++tau) v = __builtin_fma(phi[tau + (size_t)l * p] * g[i * p + tau], phi[tau + (size_t)c * p], v);
             a[l + c * q] = v;
         }
     } else if (lane_ok) {

@@ -9,6 +9,8 @@
 //                        areal Psi, whose Psi^T Psi does not lie on the pattern a block must lie on)
 //   Kronecker(T, S), KroneckerSum   lazy dense (x) sparse products and their sums   fdaPDE/linear_algebra/kronecker_product.h:56-80
 //                        (what PDE::KroneckerSolver factors without forming the product: the space-time systems; eval() gives the explicit matrix)
+//                        (the data term (Phi (x) Psi)^T W (Phi (x) Psi) may stay factored -- KroneckerSolver::compute(A, Phi, Psi, weights, scale),
+//                        set_observations --: areal designs, missing observations and observation instants off the time nodes)
 // The heavy step of SMW, A^{-1} [b | U] (1 + q right-hand sides against one prepared sparse system), runs on the device as ONE
 // batched multi-column solve through the factor-once handle (PDE::SparseSolver -> fdapde_lin_compute / fdapde_lin_solve);
 // everything dense is q x q or n x q host work.

@@ -668,6 +668,33 @@ template <typename D, typename F, int R> class PDE<D, DifferentialExpr, F, FEM_H
             }
             computed_ = fdapde_kron_compute(ctx_.get(), (int32_t)q_, (int32_t)terms.size(), tp.data(), sp.data(), symmetric ? 1 : 0) == FDAPDE_OK;
         }
+        // ... with the data term kept factored: the matrix is a + scale (Phi (x) Psi)^T W (Phi (x) Psi) (fdapde_kron_set_obs).  Phi: p x q, a time basis at the p
+        // observation instants (a space-time smoothing system passes [Phi_t, 0]); without rows it stands for [I_p 0], p = weights.size() / Psi.rows(), or q
+        // without weights.  Psi: what eval_basis(0 | 1, .) and eval_basis_nearest return -- areal designs, missing observations (exact zeros in the weights) and
+        // observation instants off the time nodes go through this door only.  weights: p Psi.rows() of them, instant tau at location k at tau Psi.rows() + k, or
+        // empty (W = I).
+        template <typename KronSum>
+        void compute(const KronSum& a, const DMatrix<double>& Phi, const SpMatrix<double>& Psi, const DVector<double>& weights = DVector<double> {}, double scale = -1.0,
+                     bool symmetric = false) {
+            compute(a, symmetric);
+            if (computed_) set_observations(Phi, Psi, weights, scale);
+        }
+        // replaces the data term of the computed matrix (an iteratively reweighted model changes W this way); a Psi without rows clears it
+        void set_observations(const DMatrix<double>& Phi, const SpMatrix<double>& Psi, const DVector<double>& weights = DVector<double> {}, double scale = -1.0) {
+            if (!computed_) throw std::runtime_error("KroneckerSolver: compute() first");
+            if (Psi.rows() > 0 && Psi.cols() != n_) throw std::runtime_error("KroneckerSolver: Psi needs n_dofs columns");
+            const bool have_phi = Phi.rows() > 0;
+            if (have_phi && Phi.cols() != q_) throw std::runtime_error("KroneckerSolver: Phi needs q columns");
+            int64_t p = have_phi ? Phi.rows() : q_;
+            if (!is_empty(weights) && Psi.rows() > 0) {
+                if (!have_phi) p = weights.size() / Psi.rows();
+                if (weights.size() != p * Psi.rows()) throw std::runtime_error("KroneckerSolver: p weights per row of Psi");
+            }
+            const std::vector<int64_t> rowptr(Psi.rowptr.begin(), Psi.rowptr.end());
+            const int rc = fdapde_kron_set_obs(ctx_.get(), (int32_t)p, have_phi ? Phi.data() : nullptr, Psi.rows(), Psi.rows() > 0 ? rowptr.data() : nullptr,
+                                               Psi.colidx.data(), Psi.values.data(), is_empty(weights) ? nullptr : weights.data(), scale);
+            if (rc != FDAPDE_OK) throw std::runtime_error(fdapde_last_error(ctx_.get()));
+        }
         DMatrix<double> solve(const DMatrix<double>& b) const {
             if (!computed_) throw std::runtime_error("KroneckerSolver: compute() first");
             if (b.rows() != q_ * n_) throw std::runtime_error("KroneckerSolver: right-hand sides need q n_dofs rows");

@@ -397,7 +397,30 @@ int fdapde_block_obs_info(fdapde_ctx *ctx, int64_t *n_obs, int64_t *nnz, int32_t
  * fdapde_kron_spmv: y = A x, host vectors of q n_dofs in the order above.  The same bits every run (no atomics, fixed summation order).
  * fdapde_kron_bench_spmv: times `reps` applications of the Krylov stage's operator D^-1 A with HIP events (k_kron_spmv with D^-1 fused into its epilogue, or
  * followed by k_kron_dinv_apply: fdapde_tune "kron_fuse"; the plain product where D^-1 was not built); algorithmic bytes per application
- * 8 n_S nnz + 4 nnz + 4 (n + 1) + 16 q n, plus the 8 q^2 n of D^-1.
+ * 8 n_S nnz + 4 nnz + 4 (n + 1) + 16 q n, plus the 8 q^2 n of D^-1.  With a data term live (fdapde_kron_set_obs) its two products run behind it and
+ * add, every array once per pass, nz = nnz(Psi), m = n_obs: the gather 12 nz + 4 (m + 1) + 8 q n + 16 p m, the scatter 12 nz + 4 (n + 1) + 8 p m + 16 q n,
+ * plus 8 q^2 n for D^-1 in the Krylov stage.
+ * fdapde_kron_set_obs: the data term kept FACTORED -- after it the handle's matrix is A + scale (Phi (x) Psi)^T diag(w) (Phi (x) Psi), A the Kronecker sum of
+ * the last fdapde_kron_compute.  Phi: p x q, dense, column-major, 1 <= p <= 64 (a time basis evaluated at p observation instants; the 2 x 2 structure is
+ * carried by Phi as the T_k carry it: a space-time system passes [Phi_t, 0] with q = 2 m); NULL stands for [I_p 0] and needs p <= q.  Psi: an n_obs x n_dofs
+ * CSR matrix exactly as fdapde_block_set_obs takes it (int64 rowptr of n_obs + 1, columns = DOF ids in the reference numbering, strictly ascending within a
+ * row; empty rows allowed; rows of any length: an areal design's Psi^T Psi is far off the pattern).  weights: p n_obs of them, the weight of instant tau at
+ * location k at tau n_obs + k (the reference's Kronecker order, as for the unknowns); NULL = ones; exact zeros are expected (a missing observation: the
+ * term is then no Kronecker product of a time matrix with ONE spatial matrix).  The smoothing system passes scale = -1.  Every product applies the term as
+ * two sparse rectangular products with q-vectors per DOF and two small dense products per row (no atomics, a fixed summation order: the same bits every
+ * run).  Teams of QP lanes, the power of two >= max(p, q); two forms chosen per matrix, for Psi and Psi^T separately: narrow (a team per row) and wide (a
+ * workgroup per row, its sub-teams' partial sums added in a fixed order); a mean row length above 16 takes the wide form (the threshold of
+ * fdapde_block_set_obs, inherited, not measured for these kernels; knob "kron_obs_form").  The term's share Phi^T diag(g_i) Phi, g_i[tau] = scale sum_k
+ * w[tau, k] Psi[k, i]^2, joins the diagonal block D_i, which is inverted again at every call: a term may make a block invertible, or singular.  Needs a live
+ * Kronecker handle (FDAPDE_ENOTINIT); FDAPDE_EINVAL, checked on the host before anything is launched and with the previous term left live, for p out of
+ * range, Phi == NULL with p > q, a non-finite entry of Phi, a non-finite weight or scale, and what fdapde_block_set_obs refuses of Psi; n_obs = 0 or a NULL
+ * rowptr clears the term; a second call replaces it; fdapde_kron_compute and fdapde_dofs_build drop it.  Every change of the term drops a live dense
+ * inverse, the expanded matrix, a live FDAPDE_SOLVER_KRON_AMG hierarchy and the column counters of the rent-or-buy rule.  With a term live
+ * FDAPDE_SOLVER_GMRES, FDAPDE_SOLVER_DENSE (the host merges the term into the expanded q n-row matrix: set-up) and the open method work as before;
+ * FDAPDE_SOLVER_KRON_AMG answers FDAPDE_EUNSUPPORTED (its hierarchy is built from pattern entries; whether it preconditions the off-pattern term was not
+ * measured) until the term is cleared.  Ranks of a multi-GPU job and multi-device contexts: FDAPDE_EUNSUPPORTED; fdapde_ctx_clone carries the knob, not the term.
+ * fdapde_kron_obs_info: the live term's p, rows and entries of Psi and the form (1 narrow, 2 wide) for Psi (form_rows) and for Psi^T (form_cols); any
+ * pointer may be NULL; without a term FDAPDE_ENOTINIT.
  * fdapde_kron_amg_hierarchy / fdapde_kron_amg_aggregates: the live hierarchy of FDAPDE_SOLVER_KRON_AMG as data, as fdapde_amg_hierarchy /
  * fdapde_amg_aggregates hand out the other solvers': rows[l] = q n_l and nnz[l] = q^2 nnz_l (counted as scalars); agg[i] = the DOF of level + 1 that DOF i of
  * `level` belongs to, *n_rows = the level's DOFs (rows[level] / q), level 0 in the reference DOF numbering.  FDAPDE_ENOTINIT where no hierarchy is live. */
@@ -405,6 +428,9 @@ int fdapde_kron_compute(fdapde_ctx *ctx, int32_t q, int32_t n_terms, const doubl
 int fdapde_kron_solve(fdapde_ctx *ctx, const fdapde_options *opt, const double *b, int32_t n_rhs, double *x, fdapde_info *info);
 int fdapde_kron_spmv(fdapde_ctx *ctx, const double *x, double *y);
 int fdapde_kron_bench_spmv(fdapde_ctx *ctx, int32_t reps, double *avg_ms, double *algorithmic_bytes);
+int fdapde_kron_set_obs(fdapde_ctx *ctx, int32_t p, const double *Phi, int64_t n_obs, const int64_t *rowptr, const int32_t *colidx, const double *values,
+                        const double *weights, double scale);
+int fdapde_kron_obs_info(fdapde_ctx *ctx, int32_t *p, int64_t *n_obs, int64_t *nnz, int32_t *form_rows, int32_t *form_cols);
 int fdapde_kron_amg_hierarchy(fdapde_ctx *ctx, int32_t cap, int32_t *n_levels, int64_t *rows, int64_t *nnz, int32_t *absorbed, double *setup_ms);
 int fdapde_kron_amg_aggregates(fdapde_ctx *ctx, int32_t level, int64_t cap, int32_t *agg, int64_t *n_rows);
 
@@ -617,6 +643,9 @@ int fdapde_partition_peers(fdapde_ctx *ctx, int32_t rank, int32_t *n_peers, int3
  *                 second product -- is above 16, else 8; 8 or 64 force that width for both; read by the next fdapde_block_set_obs)
  *   Kronecker     "kron_dinv_mb" (the MiB the inverted diagonal blocks of the Kronecker handle may take, >= 0; 2048; read by the next fdapde_kron_compute),
  *                 "kron_fuse" (1, the default: D^-1 applied in the epilogue of the operator kernel; 0: by a batched q x q matvec kernel of its own),
+ *                 "kron_obs_form" (the form of the data term's kernels: 0, the default = wide, a workgroup per row, where the mean row length of Psi -- of
+ *                 Psi^T for the second product -- is above 16, else narrow, a team per row; 1 or 2 force narrow / wide for both; read by the next
+ *                 fdapde_kron_set_obs),
  *                 "kron_amg_term" (FDAPDE_SOLVER_KRON_AMG aggregates on the spatial factor of that term of fdapde_kron_compute as given, 0 .. 7; -1, the
  *                 default: on the weighted sum of the factors' magnitudes; read by the build of the hierarchy, setting another value drops a live one) */
 int fdapde_tune(fdapde_ctx *ctx, const char *key, int32_t value);

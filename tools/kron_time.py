@@ -22,7 +22,23 @@ FDAPDE_SOLVER_KRON_AMG against the GMRES stage as it was (the multile
 PARENT_LIB is libfdapde_hip.so built from the parent commit.  Every measurement is one fresh process (`--amg-child`) that sets one mesh up, and for every
 q computes the handle, solves once to warm up (the first FDAPDE_SOLVER_KRON_AMG solve also builds the hierarchy, whose set-up time and rows per level
 it reports) and then times ONE solve by the host clock (the call ends in a stream synchronise).  Five rounds; in every round this tree's library solving
-by FDAPDE_SOLVER_KRON_AMG and the parent's solving by FDAPDE_SOLVER_GMRES alternate -> median, smallest and largest of five."""
+by FDAPDE_SOLVER_KRON_AMG and the parent's solving by FDAPDE_SOLVER_GMRES alternate -> median, smallest and largest of five.
+
+The factored data term of fdapde_kron_set_obs:
+
+  kron_time.py --obs [OUT] [--parent-lib PATH] [a | a2d | a3d] [b] [c]     (OUT defaults to profiles/kron_obs_time.txt; the parts to run, all by default;
+  a2d / a3d: part (a) on one of its two meshes)
+
+Every measurement is a process of its own (`--obs-child`), HIP events around 100 operator applications behind 3 warm-ups (fdapde_kron_bench_spmv), the
+median of five windows with the smallest and the largest.  The handle is the four pattern terms of the space-time smoothing system (q = 2 m), the term
+Phi = [H, 0] with the hat functions of the m time nodes at p = m random instants, about 30 % of the observations missing.
+  (a) the Krylov stage's operator with the term live under kron_obs_form 0 (the rule), 1 (narrow) and 2 (wide), and without a term: areal Psi over 32 x 32
+      tiles and pointwise Psi of 10^6 random locations on the 2-D mesh (unit_square(708)), areal Psi over 8^3 tiles on the 3-D mesh (unit_cube(118)),
+      q = 2, 10, 16: time, bytes by the model of fdapde_kron_bench_spmv, rate;
+  (b) the price of factoring: the pointwise design with all observations present (Phi = NULL, p = m) against the five-term handle with I_m (x) G,
+      G = fdapde_gram_pointwise's values on the pattern: per operator application and per GMRES(50) solve (2-D mesh, q = 10);
+  (c) the guard: the operator of the five-term handle with NO term live, this library and the parent commit's (PATH: its libfdapde_hip.so) alternating --
+      the new median against the spread of the parent's five windows."""
 import os
 import socket
 import sys
@@ -252,7 +268,179 @@ def amg_main(parent_lib, out_path, meshes):
         fh.write(text)
 
 
+# ---- --obs: the factored data term (fdapde_kron_set_obs) ---------------------------------------------------------------------------------------------
+OBS_MESHES = {"sq": ("2-D P1, unit_square(708)", "unit_square", 708), "cube": ("3-D P1, unit_cube(118)", "unit_cube", 118)}
+OBS_QS = (2, 10, 16)
+
+
+def obs_child(argv):
+    """--obs-child KIND MESH Q FORM: KIND areal | pointwise (the operator with a term), none (the four-term handle alone), op_term | op_five (all observations
+    present: factored / on the pattern), solve_term | solve_five (one GMRES solve of those), guard (the five-term handle of kron_ref.spacetime_terms)"""
+    import json
+
+    from fdapde_loader import load_package
+
+    capi = load_package().capi
+    from fdapde_core_amd import meshgen
+    import block_ref as br
+    import block_time as bt
+    import kron_obs_ref as ko
+    import kron_ref as kr
+
+    kind, which, q, form = argv[0], argv[1], int(argv[2]), int(argv[3])
+    m = q // 2
+    _, gen, nx = OBS_MESHES[which]
+    mesh = getattr(meshgen, gen)(nx)
+    c, n_nodes = bt.space(capi, mesh)
+    rp, ci = c.pattern_get()
+    nd = len(rp) - 1
+    r1, r0 = c.matrix_values(capi.MAT_STIFF), c.matrix_values(capi.MAT_MASS)
+    r1t = br.transpose_values(rp, ci, r1, nd)
+    Mt, Pt = kr.time_mass(m), kr.time_penalty(m)
+    four = [(kr._in_block(-LAMBDA * Pt, m, 0, 0), r0), (kr._in_block(LAMBDA * Mt, m, 0, 1), r1t), (kr._in_block(LAMBDA * Mt, m, 1, 0), r1),
+            (kr._in_block(LAMBDA * Mt, m, 1, 1), r0)]
+    res = {"kind": kind, "mesh": which, "q": q, "n_dofs": nd, "pattern_nnz": len(ci)}
+    need_mb = 8.0 * q * q * nd / 1048576.0
+    if need_mb > 2048:
+        c.tune("kron_dinv_mb", 8192)
+        res["dinv_mb"] = need_mb
+    rng = np.random.default_rng(5)
+    psi = None
+    if kind == "areal":
+        psi = bt._tiles_psi(c, mesh, 32 if which == "sq" else 8)
+    elif kind in ("pointwise", "op_term", "op_five", "solve_term", "solve_five"):
+        psi, cells, vals = bt._pointwise_psi(c, mesh, 1000000)
+    if psi is not None:
+        res.update(n_obs=psi.shape[0], nnz=int(psi.nnz), longest_row=int(np.diff(psi.indptr).max()), longest_col=int(np.bincount(psi.indices, minlength=nd).max()))
+    t0 = time.perf_counter()
+    if kind == "guard":
+        obs = br.observed_nodes(n_nodes)
+        c.kron_compute([(kr._in_block(-np.eye(m), m, 0, 0), br.gram_selection_values(rp, ci, obs, nd))] + four, symmetric=True)
+    elif kind in ("op_five", "solve_five"):
+        c.kron_compute([(kr._in_block(-np.eye(m), m, 0, 0), c.gram_pointwise(cells, vals))] + four, symmetric=True)
+    else:
+        c.kron_compute(four, symmetric=True)
+        if kind in ("areal", "pointwise"):
+            times = np.sort(rng.uniform(0, 1, m))
+            W = (rng.uniform(size=(m, psi.shape[0])) >= 0.3).astype(float)
+            c.tune("kron_obs_form", form)
+            c.kron_set_obs(psi, Phi=np.hstack([ko.hats(m, times), np.zeros((m, m))]), weights=W, scale=-1.0)
+        elif kind in ("op_term", "solve_term"):
+            c.kron_set_obs(psi, Phi=None, weights=np.ones((m, psi.shape[0])), scale=-1.0)
+        if kind != "none":
+            info = c.kron_obs_info()
+            res.update(p=info["p"], form_rows=info["form_rows"], form_cols=info["form_cols"])
+    res["setup_ms"] = 1e3 * (time.perf_counter() - t0)
+    if kind in ("solve_term", "solve_five"):
+        z = rng.standard_normal(m * psi.shape[0])
+        b = np.concatenate([-np.concatenate([psi.T @ z[r * psi.shape[0]:(r + 1) * psi.shape[0]] for r in range(m)]), LAMBDA * 0.1 * rng.standard_normal(m * nd)])
+        c.kron_solve(b, method=capi.SOLVER_GMRES, rtol=1e-10, maxit=1000, raise_on_noconv=False)   # (warm-up: the work buffers)
+        t0 = time.perf_counter()
+        x, info = c.kron_solve(b, method=capi.SOLVER_GMRES, rtol=1e-10, maxit=1000, raise_on_noconv=False)
+        res.update(solve_ms=1e3 * (time.perf_counter() - t0), iters=info.iters, converged=info.converged, relres=info.relres)
+    else:
+        win, by = [], 0.0
+        for _ in range(5):
+            ms, by = c.kron_bench_spmv(REPS)
+            win.append(ms)
+        res.update(windows_ms=win, bytes=by)
+    c.close()
+    print("OBS_RESULT " + json.dumps(res))
+
+
+def obs_main(out_path, parent_lib, parts):
+    import json
+    import subprocess
+
+    def child(kind, which, q, form=0, lib=None):
+        env = dict(os.environ)
+        if lib:
+            env["FDAPDE_HIP_LIB"] = lib
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--obs-child", kind, which, str(q), str(form)], capture_output=True, text=True, env=env, timeout=600)
+        for line in r.stdout.splitlines():
+            if line.startswith("OBS_RESULT "):
+                print(line, file=sys.stderr, flush=True)   # (progress)
+                return json.loads(line[len("OBS_RESULT "):])
+        raise SystemExit(f"child {kind} {which} {q} {form} failed (rc {r.returncode}):\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}")
+
+    def op_line(r):
+        med = float(np.median(r["windows_ms"]))
+        return f"{spread(r['windows_ms'])}; {r['bytes'] / 1e6:.1f} MB by the model -> {r['bytes'] / (med * 1e-3) / 1e12:.2f} TB/s"
+
+    out = [f"tools/kron_time.py --obs on {socket.gethostname()} (MI355X), {time.strftime('%Y-%m-%d %H:%M:%S')}",
+           f"HIP events around {REPS} operator applications behind 3 warm-ups, five windows (median, smallest, largest), every line a process of its own", ""]
+
+    def flush():
+        text = "\n".join(out) + "\n"
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as fh:
+            fh.write(text)
+        return text
+
+    if "a" in parts or "a2d" in parts or "a3d" in parts:
+        out.append("(a) the Krylov stage's operator with a data term live: k_kron_spmv (D^-1 fused in) + k_kron_obs_gather + k_kron_obs_scatter; p = m = q / 2")
+        for which, kinds in (("sq", ("areal", "pointwise")), ("cube", ("areal",))):
+            if "a" not in parts and ("a2d" if which == "sq" else "a3d") not in parts:
+                continue
+            for q in OBS_QS:
+                base = child("none", which, q)
+                out.append(f"{OBS_MESHES[which][0]}: {base['n_dofs']} DOFs, {base['pattern_nnz']} pattern entries, q = {q}; without a term {op_line(base)}")
+                for kind in kinds:
+                    got = {}
+                    for form in (0, 1, 2):
+                        r = got[form] = child(kind, which, q, form)
+                        out.append(f"  {kind:9s} Psi {r['n_obs']} x {r['n_dofs']}, {r['nnz']} entries, longest row {r['longest_row']} / column {r['longest_col']}; kron_obs_form {form} -> "
+                                   f"{r['form_rows']} / {r['form_cols']}: {op_line(r)}")
+                        flush()
+                    med = {f: float(np.median(got[f]["windows_ms"])) for f in got}
+                    best = min(med, key=med.get)
+                    same = (got[best]["form_rows"], got[best]["form_cols"]) == (got[0]["form_rows"], got[0]["form_cols"])
+                    out.append(f"  -> fastest: kron_obs_form {best} ({med[best]:.4f} ms); the rule's choice {got[0]['form_rows']} / {got[0]['form_cols']} ({med[0]:.4f} ms) "
+                               f"{'is that setting' if best == 0 or same else 'is NOT the fastest'}")
+        out.append("")
+    if "b" in parts:
+        out.append("(b) the price of factoring (2-D mesh, 10^6 random locations, every observation present, q = 10): the term factored (Phi = NULL, p = m) against the "
+                   "five-term handle with I_m (x) G, G = fdapde_gram_pointwise's values")
+        for kind, label in (("op_term", "operator, factored"), ("op_five", "operator, on the pattern")):
+            r = child(kind, "sq", 10)
+            out.append(f"  {label:28s} {op_line(r)}; set-up {r['setup_ms']:.1f} ms")
+            flush()
+        for kind, label in (("solve_term", "GMRES(50) solve, factored"), ("solve_five", "GMRES(50) solve, on the pattern")):
+            r = child(kind, "sq", 10)
+            out.append(f"  {label:32s} iterations {r['iters']}, converged {r['converged']}, relres {r['relres']:.2e}, {r['solve_ms']:.1f} ms "
+                       f"({r['solve_ms'] / max(r['iters'], 1):.3f} ms per iteration); set-up {r['setup_ms']:.1f} ms")
+            flush()
+        out.append("")
+    if "c" in parts:
+        out.append("(c) the guard: fdapde_kron_bench_spmv of the five-term handle with NO term live, this library and the parent commit's alternating")
+        if parent_lib:
+            for which, q in (("sq", 2), ("sq", 10), ("sq", 16), ("cube", 10)):
+                new, old = child("guard", which, q), child("guard", which, q, lib=parent_lib)
+                med = float(np.median(new["windows_ms"]))
+                inside = min(old["windows_ms"]) <= med <= max(old["windows_ms"])
+                out.append(f"  {which:4s} q = {q:2d}: this library {spread(new['windows_ms'])} | the parent's {spread(old['windows_ms'])} -> the new median "
+                           f"{'lies within' if inside else 'is OUTSIDE'} the parent's spread")
+                flush()
+        else:
+            out.append("  (no --parent-lib given: not measured)")
+    print(flush())
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "--obs-child":
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        return obs_child(sys.argv[2:])
+    if len(sys.argv) > 1 and sys.argv[1] == "--obs":
+        rest = sys.argv[2:]
+        parent = None
+        if "--parent-lib" in rest:
+            i = rest.index("--parent-lib")
+            parent = os.path.abspath(rest[i + 1])
+            del rest[i:i + 2]
+        known = ("a", "a2d", "a3d", "b", "c")
+        parts = [a for a in rest if a in known] or ["a", "b", "c"]
+        paths = [a for a in rest if a not in known]
+        return obs_main(paths[0] if paths else os.path.join(ROOT, "profiles", "kron_obs_time.txt"), parent, parts)
     if len(sys.argv) > 1 and sys.argv[1] == "--amg-child":
         return amg_child(sys.argv[2], sys.argv[3])
     if len(sys.argv) > 1 and sys.argv[1] == "--amg":
