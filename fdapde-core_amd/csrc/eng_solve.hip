@@ -1,6 +1,14 @@
 // eng_solve.hip -- the multi-launch solve driver: SpMV dispatch, solver layouts (compact CSR pattern, blocked ELL), Jacobi scaling and
-// Dirichlet reduction (solve_prepare), the Krylov loops (solve_run: fused-update / single-reduction / textbook CG, BiCGStab; hand-over to
-// the single-launch solver of persist_engine.hip), elliptic / parabolic / factor-once entry points, result getters, SpMV benchmarks.
+// Dirichlet reduction (solve_prepare), the Krylov driver (solve_run), elliptic / parabolic / factor-once entry points, result getters, SpMV
+// benchmarks.  The three long paths are sequences of file-local stages (anonymous namespaces, in front of the function that calls them):
+//   solve_run          resolve_method, then the stages of one SolveRun record (its member functions): start_up -> run_gmres | run_rowdist |
+//                      single_launch (the hand-over to persist_engine.hip) -> run_chunks (one enqueue_* per method: fused-update / single-reduction /
+//                      two-kernel CG, BiCGStab on one GPU and element-partitioned; chunk_graph for the captured chunk; read_outcome) -> finish
+//   e_solve_parabolic  the dense loops, then step_loop around amg_run / pmg_run / the Krylov step; every path ends in stepper_end
+//   e_lin_solve        the stages of one LinCall record: dense_stage, batches, direct_column, columns_side_by_side, columns_one_by_one advance
+//                      its ColumnTally
+// What fdapde_solve, the stepper and the handle say and decide alike (outcome_from, open_gmres_budget, cg_breakdown_agreed, the texts of
+// FDAPDE_SOLVER_DENSE) stands once, in front of run_gmres.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -8,6 +16,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <string>
+#include <type_traits>
 
 #include <dlfcn.h>
 #include <hip/hip_ext.h>
@@ -388,6 +398,59 @@ int ensure_sval(fdapde_ctx* c) {
 // "CG broke down" (p.Ap <= 0) can only be said of a CG: the breakdown word of a BiCGStab or GMRES stage that followed means something else
 static inline bool is_cg_method(int m) { return m == FDAPDE_SOLVER_CG || m == FDAPDE_SOLVER_CG_SR || m == FDAPDE_SOLVER_CG_FUSED; }
 
+namespace {
+
+// ---- what fdapde_solve, the parabolic stepper and the handle's solve say and decide alike -------------------------------------------------
+
+// the outcome of a Krylov run as its kernels leave it: sc[0] = |b|^2, sc[3] = |r|^2, ctl[2] = the breakdown word
+struct Outcome { double relres; int converged; };
+inline Outcome outcome_of(double bb, double rr, bool broke, double tol2) { return {bb > 0 ? sqrt(rr / bb) : 0.0, (rr <= tol2 * bb && !broke) ? 1 : 0}; }
+inline Outcome outcome_from(const double* h_sc, const int32_t* h_ctl, double tol2) { return outcome_of(h_sc[0], h_sc[3], h_ctl[2] != 0, tol2); }
+
+// the scalars of the run into h_sc -- with the stop flag, the iteration count and the breakdown word into h_ctl unless h_ctl holds them already -- and the wait
+int read_outcome(fdapde_ctx* c, bool ctl_too = true) {
+    if (ctl_too) HIPCHK(c, hipMemcpyAsync(c->h_ctl, c->ctl.p, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_sc, c->sc.p, 4 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return FDAPDE_OK;
+}
+
+// the GMRES stage of the open method (solve_run_restarting's gmres_budget): none for a method the caller named, what BiCGStab leaves of a budget the
+// caller set, else the default budget of its own
+inline int open_gmres_budget(const fdapde_ctx* c, const fdapde_options* opt, int64_t n) {
+    const bool open_method = !opt || opt->method == FDAPDE_SOLVER_AUTO;
+    return !open_method ? -1 : ((opt && opt->maxit > 0) ? 0 : default_maxit(c, n));
+}
+
+// "CG broke down where the method was left open" -- a turn the ranks of a multi-GPU job take TOGETHER: the breakdown word comes out of sums every rank
+// holds bit for bit, and the ranks say so to each other before any of them re-prepares (a rank that disagreed would leave the others in the
+// collectives of the second solve).  rc: what the CG stage returned; disagree: the caller's text for ranks that do not agree
+int cg_breakdown_agreed(fdapde_ctx* c, const SolveState& ss, int rc, bool open_method, const char* disagree, bool* broke) {
+    *broke = rc == FDAPDE_ENOCONV && c->h_ctl[2] != 0 && open_method && is_cg_method(c->info.method_used);
+    if ((ss.dist || ss.rowdist) && open_method && (rc == FDAPDE_OK || rc == FDAPDE_ENOCONV)) {
+        int yes = 0;
+        if (int rc2 = ranks_saying_yes(c, *broke, &yes)) return rc2;
+        if (yes != 0 && yes != c->world) return fail(c, FDAPDE_ERCCL, disagree);
+        *broke = yes == c->world;
+    }
+    return FDAPDE_OK;
+}
+
+// FDAPDE_SOLVER_DENSE by name: the refusal of a system it does not take, and the report of a matrix (`what`) it could not invert
+constexpr const char* kDenseRefusal = "FDAPDE_SOLVER_DENSE takes one-GPU systems of up to `dense_rows` (at most 8192) DOFs";
+inline std::string dense_singular(const char* what) {
+    return std::string("FDAPDE_SOLVER_DENSE: ") + what + " is singular to working precision (no usable pivot, or max |I - A X| beyond 1e-6)";
+}
+// a call that ends before any solve: the record names the method (and the inverse's check), nothing of an earlier solve stays in it
+int bare_answer(fdapde_ctx* c, int method, double check, fdapde_info* info, int rc) {
+    c->info = fdapde_info{};
+    c->info.method_used = method, c->info.relres = check;
+    if (info) *info = c->info;
+    return rc;
+}
+
+}   // namespace
+
 // Restarted GMRES(m) on the scaled system (kernels_gmres.h); x, r, sc, ctl as k_krylov_init / _fin left them, bt = the scaled right-hand side.
 // Leaves x (scaled iterate), sc[0] / sc[3] (|b|^2, |b - A x|^2 TRUE) and ctl like the other methods; h_ctl / h_sc hold the last read-back.
 int run_gmres(fdapde_ctx* c, double tol2, int maxit) {
@@ -438,411 +501,445 @@ int run_gmres(fdapde_ctx* c, double tol2, int maxit) {
         hipLaunchKernelGGL(k_gm_residual, dim3(vg), dim3(256), 0, st, n, c->gm_b.p, c->t.p, c->r.p, c->gm_part.p);
         hipLaunchKernelGGL(k_gm_cycle_fin, dim3(1), dim3(256), 0, st, c->gm_part.p, vg, c->sc.p, c->ctl.p, tol2, maxit);
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(c->h_ctl, c->ctl.p, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemcpyAsync(c->h_sc, c->sc.p, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
+        if (int rc = read_outcome(c)) return rc;
         stop = c->h_ctl[0] != 0;
     }
     return FDAPDE_OK;
 }
+
+// ---- the stages of solve_run: file-local, in the order solve_run calls them -------------------------------------------------------------------
+namespace {
+
+// Which method runs: what the caller asked for, resolved against what solve_prepare found and the platform -- or a refusal with its text
+struct MethodChoice { int method, refusal; const char* why; };
+MethodChoice resolve_method(int asked, const SolveState& ss, bool op_symmetric, int world) {
+    int m = asked;
+    if (ss.rowdist) {
+        // (warm starts: the caller's initial guess must hold the owners' values at the ghost columns -- the parabolic stepper imports them
+        //  after every step, rowdist_import_ghosts)
+        if (m == FDAPDE_SOLVER_CG_SR) return {m, FDAPDE_EUNSUPPORTED, "the row-distributed solve runs the fused-update CG or BiCGStab"};
+        m = (m == FDAPDE_SOLVER_BICGSTAB || !ss.symmetric) ? FDAPDE_SOLVER_BICGSTAB : FDAPDE_SOLVER_CG_FUSED;
+    }
+    if (m == FDAPDE_SOLVER_AUTO)   // symmetric + positive diagonal: CG (fused-update form on one GPU, single-reduction form on several)
+        m = (op_symmetric && ss.diag_positive) ? (ss.dist ? FDAPDE_SOLVER_CG : FDAPDE_SOLVER_CG_FUSED) : FDAPDE_SOLVER_BICGSTAB;
+    if (m == FDAPDE_SOLVER_CG && ss.dist && world > 1) m = FDAPDE_SOLVER_CG_SR;   // one all-reduce per iteration
+    if (m == FDAPDE_SOLVER_CG_FUSED && ss.dist) m = FDAPDE_SOLVER_CG_SR;         // y.y of the assembled y would need its own all-reduce
+    if (is_cg_method(m) && !ss.diag_positive) return {m, FDAPDE_ENOCONV, "CG needs a positive diagonal (operator not SPD?); use BiCGStab"};
+    if (m == FDAPDE_SOLVER_GMRES && (ss.dist || ss.rowdist)) return {m, FDAPDE_EUNSUPPORTED, "GMRES runs on one-GPU contexts"};
+    return {m, FDAPDE_OK, nullptr};
+}
+
+// Grid of the fused update kernels (k_cgf_update, V elements per lane; k_cgsr_update, kCgV): one workgroup per 256 V double2 elements -- with the
+// XCD-aware mapping (knob cgf_band) of the elements of each of the SpMV's eight row bands, workgroup b serving band b % 8
+struct UpdateGrid {
+    int64_t band2;   // double2 elements of a row band; 0: no bands
+    int grid;
+};
+inline UpdateGrid update_grid(int64_t n, int V, int cgf_band) {
+    const int64_t band2 = cgf_band ? (((((n + 7) / 8) + 31) & ~int64_t(31)) >> 1) : 0, span = band2 > 0 ? band2 : (n >> 1);
+    const int per = std::max(1, (int)((span + 256 * V - 1) / (256 * V)));
+    return {band2, band2 > 0 ? 8 * per : per};
+}
+
+struct EventPair { hipEvent_t e0, e1; };
+template <typename F> void by_cgf_v(int V, F&& f) {
+    switch (V) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 8: f(std::integral_constant<int, 8>{}); break;
+    default: f(std::integral_constant<int, 4>{}); break;
+    }
+}
+// Phase statistics of the single launch into c->info: stamps of every workgroup (s_memrealtime ticks of 10 ns).  The operator application of an
+// iteration is complete when the SLOWEST workgroup has its rows: spmv_avg_ms = max over workgroups of their average operator phase (SpMV + import
+// wait); the mean over workgroups is reported next to it; all-gather (which contains the wait for the slowest) and update: means
+void persist_phase_stats(fdapde_ctx* c, int v) {
+    if (c->persist_host_stats.empty() || !(c->persist_host_stats[0] > 0)) return;
+    const size_t G = c->persist_host_stats.size() / 4;
+    double mx = 0, mean = 0, gat = 0, upd = 0;
+    for (size_t g = 0; g < G; ++g) {
+        const double* st = &c->persist_host_stats[4 * g];
+        const double n_it = st[0] > 0 ? st[0] : 1;
+        mx = std::max(mx, st[1] / n_it), mean += st[1] / n_it, gat += st[2] / n_it, upd += st[3] / n_it;
+    }
+    if (std::getenv("FDAPDE_DEBUG_PERSIST")) {   // per-workgroup operator phases (us), with the workgroup's ELL entries
+        std::vector<int64_t> eo(G + 1);
+        std::vector<int32_t> io(G + 1), xo(G + 1);
+        (void)hipMemcpy(eo.data(), c->ps[v].ell_off.p, sizeof(int64_t) * (G + 1), hipMemcpyDeviceToHost);
+        (void)hipMemcpy(io.data(), c->ps[v].imp_off.p, sizeof(int32_t) * (G + 1), hipMemcpyDeviceToHost);
+        (void)hipMemcpy(xo.data(), c->ps[v].exp_off.p, sizeof(int32_t) * (G + 1), hipMemcpyDeviceToHost);
+        for (size_t g = 0; g < G; ++g)
+            std::fprintf(stderr, "persist wg %zu: operator %.2f us gather %.2f us entries %lld imports %d exports %d\n", g,
+                         c->persist_host_stats[4 * g + 1] / std::max(1.0, c->persist_host_stats[4 * g]) * 1e-2,
+                         c->persist_host_stats[4 * g + 2] / std::max(1.0, c->persist_host_stats[4 * g]) * 1e-2, (long long)(eo[g + 1] - eo[g]),
+                         io[g + 1] - io[g], xo[g + 1] - xo[g]);
+    }
+    c->info.spmv_avg_ms = mx * 1e-5, c->info.spmv_timed = (int32_t)c->persist_host_stats[0];
+    c->info.spmv_mean_ms = mean / (double)G * 1e-5, c->info.gather_avg_ms = gat / (double)G * 1e-5, c->info.update_avg_ms = upd / (double)G * 1e-5;
+}
+
+// What the stages of one solve_run share
+struct SolveRun {
+    fdapde_ctx* c; int64_t n; hipStream_t st; double tol2;   // the context, its rows and stream, rtol^2
+    int np_spmv;            // partial pairs the SpMV leaves for the vector kernels: one per workgroup of the kernel that applies the scaled operator
+    const uint8_t* owned;
+    bool dist, rowdist;
+    UpdateGrid upd;         // of the method's fused update (fused-update CG: knob cgf_v elements per lane; single-reduction CG: kCgV)
+    int bi_grid;            // of BiCGStab's vector kernels
+    hipEvent_t* ev;         // event pairs of the timed iterations: n_timed of them, `timed` handed out so far
+    int n_timed, timed;
+    int launched;           // iterations enqueued so far (or run by a single launch, by GMRES)
+    bool stop;              // the stop flag as last read back
+
+    // the event pair of iteration `it` if it is a timed one (every kTimeStride-th, while pairs are left), else two nulls
+    EventPair timed_pair(int it) {
+        if (!(timed < n_timed && it % kTimeStride == kTimePhase)) return {nullptr, nullptr};
+        const int k = timed++;
+        return {ev[2 * k], ev[2 * k + 1]};
+    }
+
+    // Start-up: the Dirichlet lift g~ and A g~, the warm start, x / r / p and the scalars of iteration 0 -- as ONE one-workgroup kernel (or two around
+    // A g~) for the smallest systems (`front`: solve_prepare's front_pending), with the ranks' sums in between on several GPUs, or as plain launches
+    int start_up(const SolveState& ss, bool front, int method, const double* A, const double* f_dev, const double* g_dev, const double* u0_dev) {
+        const bool bicg = method == FDAPDE_SOLVER_BICGSTAB, cgf = method == FDAPDE_SOLVER_CG_FUSED;
+        const double* fvec = f_dev;
+        if (dist) {   // the forcing vector is a sum over the ranks sharing a DOF
+            HIPCHK(c, hipMemcpyAsync(c->tmp_e.p, f_dev, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
+            if (int rc = halo_sum(c, c->tmp_e.p, nullptr, 0)) return rc;
+            fvec = c->tmp_e.p;
+        }
+        // the lift is zero (no Dirichlet data, or homogeneous data on one GPU -- across ranks the data may differ, and every rank
+        // must take the same path through the collectives): A g~ = 0, written by the lift kernel itself (no memset launch)
+        const bool zero_lift = !ss.use_bnd || (!dist && !rowdist && g_dev == c->g.p && c->g_zero);
+        SmallFrontArgs fa{};
+        if (front) {
+            const fdapde_ctx::Persist& ps = c->ps[ss.use_bnd ? 1 : 0];
+            fa.n = n, fa.use_bnd = ss.use_bnd, fa.zero_y = zero_lift ? 1 : 0, fa.vec_grid = c->vec_grid;
+            fa.stat = c->stiff_stat.p, fa.bnd = c->bnd.p, fa.scale = c->scale.p, fa.ctl = c->ctl.p;
+            fa.nsl = ps.meta.nsl, fa.ell_off = ps.ell_off.p, fa.sl_off = ps.sl_off.p, fa.slot_dof = ps.slot_dof.p, fa.src = ps.ell_src.p, fa.col = ps.ell_col.p;
+            fa.A = ss.front_A, fa.ell_val = ps.ell_val.p;
+            fa.g = g_dev, fa.gt = c->gt.p, fa.y = c->y.p, fa.u = c->u.p;
+            if (!zero_lift) {
+                fa.phases = 1;
+                hipLaunchKernelGGL(k_small_front, dim3(1), dim3(256), 0, st, fa);
+            }
+        } else
+            hipLaunchKernelGGL(k_lift, dim3(g1(n)), dim3(256), 0, st, n, c->bnd.p, g_dev, ss.use_bnd, c->gt.p, zero_lift ? c->y.p : (double*)nullptr);
+        if (!zero_lift) {
+            launch_spmv(c, A, c->gt.p, c->y.p, nullptr, nullptr, nullptr);   // y = A g~
+            if (dist)
+                if (int rc = halo_sum(c, c->y.p, nullptr, 0)) return rc;
+        }
+        const double* ax = nullptr;
+        if (u0_dev) {   // warm start: x = (u0 - g~) / s, r = b~ - At x
+            if (int rc = ensure_sval(c)) return rc;
+            hipLaunchKernelGGL(k_krylov_init, dim3(c->vec_grid), dim3(256), 0, st, n, fvec, c->y.p, c->scale.p, c->x.p, c->r.p, c->p.p,
+                               (double*)nullptr, c->part_b.p, owned, u0_dev, c->gt.p, (const double*)nullptr, 1);
+            launch_spmv(c, c->sval.p, c->x.p, c->t.p, nullptr, nullptr, nullptr);
+            if (dist)
+                if (int rc = halo_sum(c, c->t.p, nullptr, 0)) return rc;
+            ax = c->t.p;
+        }
+        // fused-update CG: its launch 0 reads the explicit r.r from the second half of part_b (seeded by whichever kernel ends the start-up)
+        double* seed = cgf ? c->part_b.p + upd.grid : (double*)nullptr;
+        const int n_seed = cgf ? upd.grid : 0;
+        if (front) {   // (one GPU, cold start: what the two launches of the other branches do)
+            fa.phases = zero_lift ? 3 : 2;
+            fa.f = fvec, fa.x = c->x.p, fa.r = c->r.p, fa.p = c->p.p, fa.r0 = bicg ? c->r0.p : (double*)nullptr, fa.partial = c->part_b.p, fa.sc = c->sc.p;
+            fa.seed = seed, fa.n_seed = n_seed, fa.tol2 = tol2;
+            hipLaunchKernelGGL(k_small_front, dim3(1), dim3(256), 0, st, fa);
+        } else {
+            hipLaunchKernelGGL(k_krylov_init, dim3(c->vec_grid), dim3(256), 0, st, n, fvec, c->y.p, c->scale.p, c->x.p, c->r.p, c->p.p,
+                               bicg ? c->r0.p : (double*)nullptr, c->part_b.p, owned, u0_dev, c->gt.p, ax, 0);
+            if (dist || rowdist) {
+                hipLaunchKernelGGL(k_reduce_partials2, dim3(1), dim3(256), 0, st, c->part_b.p, c->vec_grid, c->sbuf.p);
+                if (int rc = allreduce_sum(c, c->sbuf.p, 2)) return rc;
+                hipLaunchKernelGGL(k_krylov_init_fin, dim3(1), dim3(256), 0, st, c->sbuf.p, 1, c->sc.p, c->ctl.p, tol2, (double*)nullptr, 0);
+            } else
+                hipLaunchKernelGGL(k_krylov_init_fin, dim3(1), dim3(256), 0, st, c->part_b.p, c->vec_grid, c->sc.p, c->ctl.p, tol2, seed, n_seed);
+        }
+        if (method == FDAPDE_SOLVER_GMRES) {   // the scaled right-hand side, for the true residual at the end of every restart cycle (c->y still holds A g~)
+            HIPCHK(c, c->gm_b.alloc((size_t)n));
+            hipLaunchKernelGGL(k_gm_rhs, dim3(g1(n)), dim3(256), 0, st, n, fvec, c->y.p, c->scale.p, c->gm_b.p);
+        }
+        if (method == FDAPDE_SOLVER_CG_SR) {   // p = s = 0 before the first update (beta = 0 there)
+            HIPCHK(c, hipMemsetAsync(c->p.p, 0, sizeof(double) * (size_t)n, st));
+            HIPCHK(c, hipMemsetAsync(c->s.p, 0, sizeof(double) * (size_t)n, st));
+        }
+        HIPCHK(c, hipGetLastError());
+        return FDAPDE_OK;
+    }
+
+    // The whole iteration as ONE launch where the prepared layout takes it (kernels_persist.h: the fused-update CG; kernels_persist_bicg.h: BiCGStab on
+    // plain storage of at most 8 rows per thread); it leaves sc / ctl as the chunk loop would.  *ran = false: not a system for it, or the launch gave up
+    int single_launch(const SolveState& ss, bool bicg, int maxit, bool* ran) {
+        const int v = ss.use_bnd ? 1 : 0;
+        const fdapde_ctx::Persist& ps = c->ps[v];
+        *ran = false;
+        if (dist || rowdist || !c->persist || c->persist_broken || !ps.ok || !ps.filled) return FDAPDE_OK;
+        if (bicg && (!c->persist_bicg || ps.meta.sym || ps.meta.R > 8)) return FDAPDE_OK;
+        DebugClock clk;
+        // the epilogue kernel (and, for fdapde_solve, the end-of-solve event) is enqueued BEHIND the launch before the host waits for it: one wait
+        // for launch, outcome and solution together; if the launch gave up, the chunk loop's epilogue redoes it from its own iterate
+        c->persist_tail = [this]() -> int {
+            if (!c->tail_in_launch) hipLaunchKernelGGL(k_unscale, dim3(g1(n)), dim3(256), 0, st, n, c->scale.p, c->persist_x.p, c->gt.p, c->u.p);
+            if (c->ev1_at_end) HIPCHK(c, hipEventRecord(c->ev1, st));
+            return FDAPDE_OK;
+        };
+        const int rc = run_persist(c, v, tol2, maxit, ran, bicg);
+        c->persist_tail = nullptr;
+        if (rc) return rc;
+        clk.mark("solve_run: run_persist");
+        if (!*ran) c->drop_prepared("the single launch gave up (persist_broken) or its layout does not launch");   // (a retry goes through a full prepare)
+        return FDAPDE_OK;
+    }
+
+    // ---- one iteration of each multi-launch method, enqueued; `it` counts from the start of this solve_run ---------------------------------------
+
+    // fused-update CG: SpMV (p.y, y.y) + k_cgf_update; the arguments depend on the iteration's parity only (which a captured chunk relies on)
+    void enqueue_cgf(int it, EventPair ev) {
+        const int cg = upd.grid;
+        launch_spmv(c, c->sval.p, c->p.p, c->y.p, c->p.p, c->part_a.p, c->ctl.p, ev.e0, ev.e1);   // p.y and y.y
+        by_cgf_v(c->cgf_v, [&](auto v) {
+            hipLaunchKernelGGL((k_cgf_update<decltype(v)::value>), dim3(cg), dim3(256), 0, st, n, c->y.p, c->p.p, c->x.p, c->r.p, c->part_a.p, np_spmv,
+                               c->part_b.p + (size_t)((it + 1) & 1) * cg, cg, c->part_b.p + (size_t)(it & 1) * cg, c->sc.p, tol2, c->ctl.p, upd.band2, c->cgf_nt, c->cgf_lazy, it & 1);
+        });
+    }
+    // ... and behind the last update of a chunk: its explicit r.r -> sc[3] / stop flag
+    void enqueue_cgf_fin(int done) {
+        hipLaunchKernelGGL(k_cgf_fin, dim3(1), dim3(256), 0, st, c->part_b.p + (size_t)((done - 1) & 1) * upd.grid, upd.grid, c->sc.p, tol2, c->ctl.p);
+    }
+
+    // single-reduction CG: w = At r with delta = r.(At r) and gamma = r.r (owned rows) fused; multi-GPU: ONE all-reduce carries the interface entries
+    // of w and both partials
+    int enqueue_cgsr(int it) {
+        const EventPair ev = timed_pair(it);
+        launch_spmv(c, c->sval.p, c->r.p, c->y.p, c->r.p, c->part_a.p, c->ctl.p, ev.e0, ev.e1, 1, owned);
+        const double* part = c->part_a.p;
+        int np = np_spmv;
+        if (dist) {
+            // pack -> all-reduce; the update kernel reads the summed interface rows straight from hbuf (no unpack launch)
+            if (int rc = halo_sum(c, c->y.p, c->part_a.p, c->spmv_grid, /*unpack=*/false)) return rc;
+            part = c->hbuf.p + c->n_if, np = 1;
+        }
+        hipLaunchKernelGGL(k_cgsr_update, dim3(upd.grid), dim3(256), 0, st, n, c->r.p, c->y.p, c->p.p, c->s.p, c->x.p, part, np, c->sc.p, it & 1,
+                           it == 0 ? 1 : 0, tol2, c->ctl.p, dist ? c->if_slot.p : (const int32_t*)nullptr, dist ? c->hbuf.p : (const double*)nullptr, upd.band2);
+        return FDAPDE_OK;
+    }
+
+    // CG in the two-kernel form.  Element-partitioned: one all-reduce carries the interface entries of A_p p and the rank's p.Ap partial; a second
+    // one (a single double) carries r.r.  Every rank takes the same stop decision from the same numbers.
+    int enqueue_cg(int it) {
+        const int parity = it & 1, cg = c->cg_grid;
+        const EventPair ev = timed_pair(it);
+        launch_spmv(c, c->sval.p, c->p.p, c->y.p, c->p.p, c->part_a.p, c->ctl.p, ev.e0, ev.e1);
+        if (dist)
+            if (int rc = halo_sum(c, c->y.p, c->part_a.p, c->spmv_grid)) return rc;
+        hipLaunchKernelGGL(k_cg_update_xr, dim3(cg), dim3(256), 0, st, n, c->y.p, c->r.p, dist ? c->hbuf.p + c->n_if : c->part_a.p, dist ? 1 : np_spmv, c->part_b.p, c->sc.p, parity, c->ctl.p, owned);
+        if (dist) {
+            hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(256), 0, st, c->part_b.p, cg, c->sbuf.p);
+            if (int rc = allreduce_sum(c, c->sbuf.p, 1)) return rc;
+        }
+        hipLaunchKernelGGL(k_cg_update_p, dim3(cg), dim3(256), 0, st, n, c->r.p, c->p.p, c->x.p, dist ? c->sbuf.p : c->part_b.p, dist ? 1 : cg, c->sc.p, parity, tol2, c->ctl.p);
+        return FDAPDE_OK;
+    }
+
+    // BiCGStab on one GPU: the dots ride on the two SpMVs
+    int enqueue_bicg(int it) {
+        const int bg = bi_grid, np = np_spmv;
+        hipLaunchKernelGGL(k_bicg_p, dim3(bg), dim3(256), 0, st, n, c->r.p, c->y.p, c->p.p, c->part_b.p, bg, c->sc.p, it == 0 ? 1 : 0, c->ctl.p);
+        const EventPair ev = timed_pair(it);
+        launch_spmv(c, c->sval.p, c->p.p, c->y.p, c->r0.p, c->part_a.p, c->ctl.p, ev.e0, ev.e1);   // v = At p, r0.v
+        hipLaunchKernelGGL(k_bicg_s, dim3(bg), dim3(256), 0, st, n, c->r.p, c->y.p, c->s.p, c->part_a.p, np, c->sc.p, c->ctl.p);
+        launch_spmv(c, c->sval.p, c->s.p, c->t.p, c->s.p, c->part_a.p, c->ctl.p);                 // t = At s, t.s, t.t
+        hipLaunchKernelGGL(k_bicg_xr, dim3(bg), dim3(256), 0, st, n, c->p.p, c->s.p, c->t.p, c->r0.p, c->x.p, c->r.p, c->part_a.p, np, c->part_b.p, c->sc.p, c->ctl.p, (const uint8_t*)nullptr);
+        hipLaunchKernelGGL(k_bicg_fin, dim3(1), dim3(256), 0, st, c->part_a.p, np, c->part_b.p, bg, c->sc.p, tol2, c->ctl.p);
+        return FDAPDE_OK;
+    }
+
+    // BiCGStab element-partitioned: every operator application is followed by the interface sum, which also carries the dot fused into the SpMV
+    // (w.(A x) needs no weighting); dots of assembled vectors (t.t, r0.r, r.r) count owned rows and cross in two small all-reduces.
+    // sbuf: [0..1] = (r0.r, r.r), [4..5] = (t.s, t.t).
+    int enqueue_bicg_dist(int it) {
+        const int bg = bi_grid;
+        hipLaunchKernelGGL(k_bicg_p, dim3(bg), dim3(256), 0, st, n, c->r.p, c->y.p, c->p.p, c->sbuf.p, 1, c->sc.p, it == 0 ? 1 : 0, c->ctl.p);
+        const EventPair ev = timed_pair(it);
+        launch_spmv(c, c->sval.p, c->p.p, c->y.p, c->r0.p, c->part_a.p, c->ctl.p, ev.e0, ev.e1);
+        if (int rc = halo_sum(c, c->y.p, c->part_a.p, c->spmv_grid)) return rc;
+        hipLaunchKernelGGL(k_bicg_s, dim3(bg), dim3(256), 0, st, n, c->r.p, c->y.p, c->s.p, c->hbuf.p + c->n_if, 1, c->sc.p, c->ctl.p);
+        launch_spmv(c, c->sval.p, c->s.p, c->t.p, c->s.p, c->part_a.p, c->ctl.p);
+        if (int rc = halo_sum(c, c->t.p, c->part_a.p, c->spmv_grid)) return rc;
+        hipLaunchKernelGGL(k_sq_owned, dim3(c->vec_grid), dim3(256), 0, st, n, c->t.p, owned, c->part_b.p, c->ctl.p);
+        hipLaunchKernelGGL(k_bicg_tt_fin, dim3(1), dim3(256), 0, st, c->part_b.p, c->vec_grid, c->hbuf.p + c->n_if, c->sbuf.p + 4);
+        if (int rc = allreduce_sum(c, c->sbuf.p + 5, 1)) return rc;
+        hipLaunchKernelGGL(k_bicg_xr, dim3(bg), dim3(256), 0, st, n, c->p.p, c->s.p, c->t.p, c->r0.p, c->x.p, c->r.p, c->sbuf.p + 4, 1, c->part_b.p, c->sc.p, c->ctl.p, owned);
+        hipLaunchKernelGGL(k_reduce_partials2, dim3(1), dim3(256), 0, st, c->part_b.p, bg, c->sbuf.p);
+        if (int rc = allreduce_sum(c, c->sbuf.p, 2)) return rc;
+        hipLaunchKernelGGL(k_bicg_fin, dim3(1), dim3(256), 0, st, c->sbuf.p + 4, 1, c->sbuf.p, 1, c->sc.p, tol2, c->ctl.p);
+        return FDAPDE_OK;
+    }
+
+    // The captured chunk of the fused-update CG (2 * chunk + 1 kernel nodes), made again when anything its launches bake in has changed: the arguments repeat
+    // with period 2, so the graph captured for iterations 0 .. chunk-1 serves every even-aligned chunk.  True where c->cg_graph_exec can be replayed
+    bool chunk_graph(int chunk) {
+        GraphKey key;
+        std::memset(&key, 0, sizeof key);   // padding bytes take part in the memcmp below
+        key.sval = c->sval.p, key.rowptr = c->sp_cur >= 0 ? (const void*)c->sp_rowptr[c->sp_cur].p : (const void*)c->rowptr.p;
+        key.n = n, key.tol2 = tol2, key.chunk = chunk, key.v = c->cgf_v, key.grid = c->spmv_grid, key.team = c->spmv_team;
+        key.c16 = c->spmv_c16, key.sp_cur = c->sp_cur;
+        // the blocked-ELL layout the captured SpMV nodes read from (its arrays and grid are baked into the graph)
+        key.bk_cur = c->bk_cur, key.bk_G = c->bk_cur >= 0 ? c->bk[c->bk_cur].meta.G : 0;
+        key.bk_val = c->bk_cur >= 0 ? (const void*)c->bk[c->bk_cur].ell_val.p : nullptr;
+        if (c->cg_graph_exec && std::memcmp(&key, &c->cg_graph_key, sizeof key) == 0) return true;
+        if (c->cg_graph_exec) (void)hipGraphExecDestroy(c->cg_graph_exec), c->cg_graph_exec = nullptr;
+        hipGraph_t g = nullptr;
+        if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+            for (int it = 0; it < chunk; ++it) enqueue_cgf(it, {nullptr, nullptr});
+            enqueue_cgf_fin(chunk);
+            if (hipStreamEndCapture(st, &g) == hipSuccess && g && hipGraphInstantiate(&c->cg_graph_exec, g, nullptr, nullptr, 0) == hipSuccess)
+                c->cg_graph_key = key;
+            else
+                c->cg_graph_exec = nullptr;
+            if (g) (void)hipGraphDestroy(g);
+        }
+        (void)hipGetLastError();
+        return c->cg_graph_exec != nullptr;
+    }
+
+    // The chunk loop of the multi-launch methods: up to check_every iterations enqueued (a full, untimed, even-aligned chunk of the fused-update CG as
+    // one graph replay), then the outcome read back and waited for -- until the stop flag is up or maxit iterations are out
+    int run_chunks(int method, int maxit, int check_every) {
+        const bool cgf = method == FDAPDE_SOLVER_CG_FUSED;
+        if (!stop && launched < maxit)   // the multi-launch kernels read the scaled full-pattern copy
+            if (int rc = ensure_sval(c)) return rc;
+        while (!stop && launched < maxit) {
+            const int chunk = (maxit - launched) < check_every ? (maxit - launched) : check_every;
+            bool graphed = false;
+            if (cgf && c->use_graph && chunk == check_every && (chunk & 1) == 0 && (launched & 1) == 0 && timed >= n_timed)
+                if (chunk_graph(chunk) && hipGraphLaunch(c->cg_graph_exec, st) == hipSuccess) launched += chunk, graphed = true, ++c->graph_replays;
+            for (int it = 0; !graphed && it < chunk; ++it, ++launched) {
+                int rc = FDAPDE_OK;
+                switch (method) {
+                case FDAPDE_SOLVER_CG_SR: rc = enqueue_cgsr(launched); break;
+                case FDAPDE_SOLVER_CG_FUSED: enqueue_cgf(launched, timed_pair(launched)); break;
+                case FDAPDE_SOLVER_BICGSTAB: rc = dist ? enqueue_bicg_dist(launched) : enqueue_bicg(launched); break;
+                default: rc = enqueue_cg(launched); break;
+                }
+                if (rc) return rc;
+            }
+            if (cgf && launched > 0 && !graphed) enqueue_cgf_fin(launched);
+            HIPCHK(c, hipGetLastError());
+            if (int rc = read_outcome(c)) return rc;
+            stop = c->h_ctl[0] != 0;
+        }
+        return FDAPDE_OK;
+    }
+
+    // The end: whatever the method still owes the iterate, u = g~ + s x behind it, the outcome and the timing figures into c->info
+    int finish(const SolveState& ss, int method, bool persisted, bool unscaled) {
+        if (method == FDAPDE_SOLVER_CG_SR && !stop && launched > 0 && !dist) {
+            // single-reduction CG out of iterations: sc[3] is the gamma = r.r its last SpMV measured, the residual BEFORE the last update.  info.relres is
+            // the residual of the x that is handed out: r.r of the last update, summed here (r vanishes on the Dirichlet rows).  A run whose LAST
+            // permitted update meets rtol therefore reports converged = 1 (the stale gamma said 0: the next SpMV would have seen it).  One GPU only:
+            // the element-partitioned form (dist) would need an all-reduce of its own for this and still reports the gamma of before its last update.
+            hipLaunchKernelGGL(k_sq_norm, dim3(c->vec_grid), dim3(256), 0, st, n, c->r.p, c->part_b.p);
+            hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(256), 0, st, c->part_b.p, c->vec_grid, c->sc.p + 3);
+            HIPCHK(c, hipGetLastError());
+            if (int rc = read_outcome(c, /*ctl_too=*/false)) return rc;
+        }
+        if (launched == 0 && !persisted)   // already converged at the initial guess
+            if (int rc = read_outcome(c)) return rc;
+        if (method == FDAPDE_SOLVER_CG_FUSED && c->cgf_lazy && !persisted)   // an update of x may still be pending (convergence seen at a poll, or maxit)
+            hipLaunchKernelGGL(k_cgf_flush, dim3(c->vec_grid), dim3(256), 0, st, n, c->p.p, c->r.p, c->x.p, c->sc.p, c->ctl.p);
+        if (!unscaled) {   // (else c->u already holds the solution: the single launch's epilogue ran behind it)
+            hipLaunchKernelGGL(k_unscale, dim3(g1(n)), dim3(256), 0, st, n, c->scale.p, persisted ? c->persist_x.p : c->x.p, c->gt.p, c->u.p);
+            HIPCHK(c, hipGetLastError());
+            if (c->ev1_at_end) HIPCHK(c, hipEventRecord(c->ev1, st));
+            if (!c->defer_end_sync) HIPCHK(c, hipStreamSynchronize(st));   // (h_ctl / h_sc were read back behind a wait of their own)
+        }
+        const Outcome out = outcome_from(c->h_sc, c->h_ctl, tol2);
+        c->info.iters = c->h_ctl[1];
+        c->info.relres = out.relres, c->info.converged = out.converged;
+        c->info.method_used = method;
+        c->info.spmv_avg_ms = 0, c->info.spmv_timed = 0;
+        {   // launches after the stop flag return at once; only iterations that really ran are averaged
+            int real = 0;   // sample k was iteration k * kTimeStride
+            while (real < timed && real * kTimeStride + kTimePhase < c->info.iters) ++real;
+            double sum = 0;
+            for (int i = 0; i < real; ++i) {
+                float t = 0;
+                HIPCHK(c, hipEventElapsedTime(&t, ev[2 * i], ev[2 * i + 1]));
+                sum += t;
+            }
+            if (real > 0) c->info.spmv_avg_ms = sum / real, c->info.spmv_timed = real;
+        }
+        c->info.persistent = persisted ? 1 : 0;
+        c->info.launch_ms = persisted ? c->persist_launch_ms : 0.0;
+        c->info.gather_avg_ms = c->info.update_avg_ms = c->info.spmv_mean_ms = 0;
+        if (persisted) persist_phase_stats(c, ss.use_bnd ? 1 : 0);
+        if (!c->info.converged) {
+            c->err = c->h_ctl[2] ? "Krylov breakdown (operator not SPD for CG, or BiCGStab rho/omega = 0)" : "maxit reached";
+            return FDAPDE_ENOCONV;   // reference: success = false (fem_linear_elliptic_solver.h:42-45)
+        }
+        return FDAPDE_OK;
+    }
+};
+
+}   // namespace
 
 // Krylov solve of A u = f with u = g on the Dirichlet DOFs (if ss.use_bnd), on the system prepared by solve_prepare.
 //   f_dev : right-hand side, internal order, sub-assembled (summed over ranks here when dist)
 //   g_dev : Dirichlet values, internal order (read on boundary DOFs only)
 //   u0_dev: initial guess in u-space or nullptr (cold start)
 // Result in c->u.  Fills c->info (iters, relres, converged, method_used, spmv timing).
+// A refusal (resolve_method: a method the platform or the diagonal does not admit) comes before anything is enqueued: c->gt, c->y and the
+// Krylov vectors are left untouched, no collective is entered (every rank refuses alike), and front_pending is never set on a system that is refused.
 int solve_run(fdapde_ctx* c, const SolveState& ss, const double* A, const double* f_dev, const double* g_dev, const double* u0_dev,
               int method, double rtol, int maxit, int check_every, int n_timed) {
-    const int64_t n = c->hs.n_dofs;
-    hipStream_t st = c->stream;
-    const bool dist = ss.dist;
-    const uint8_t* owned = ss.owned;
     // nothing of an earlier solve may be read as this one's outcome by a caller that sees an early return (solve_run_restarting)
     c->h_ctl[0] = c->h_ctl[1] = c->h_ctl[2] = c->h_ctl[3] = 0, c->h_ctl_seen = 4;
     c->info.iters = 0, c->info.method_used = method, c->info.relres = 0, c->info.converged = 0;
-    c->graph_replays = 0;
-    // partial pairs the SpMV leaves for the vector kernels: one per workgroup of the kernel that applies the scaled operator
-    const int np_spmv = (c->bk_cur >= 0 && !dist) ? c->bk[c->bk_cur].meta.G : c->spmv_grid;
-    const double* fvec = f_dev;
-    if (ss.rowdist) {
-        // (warm starts: the caller's initial guess must hold the owners' values at the ghost columns -- the parabolic stepper imports them
-        //  after every step, rowdist_import_ghosts)
-        const bool want_bicg = method == FDAPDE_SOLVER_BICGSTAB || !ss.symmetric;
-        if (method == FDAPDE_SOLVER_CG_SR) return fail(c, FDAPDE_EUNSUPPORTED, "the row-distributed solve runs the fused-update CG or BiCGStab");
-        method = want_bicg ? FDAPDE_SOLVER_BICGSTAB : FDAPDE_SOLVER_CG_FUSED;
-    }
-    if (dist) {   // the forcing vector is a sum over the ranks sharing a DOF
-        HIPCHK(c, hipMemcpyAsync(c->tmp_e.p, f_dev, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
-        if (int rc = halo_sum(c, c->tmp_e.p, nullptr, 0)) return rc;
-        fvec = c->tmp_e.p;
-    }
-    // the lift is zero (no Dirichlet data, or homogeneous data on one GPU -- across ranks the data may differ, and every rank
-    // must take the same path through the collectives): A g~ = 0, written by the lift kernel itself (no memset launch)
-    const bool zero_lift = !ss.use_bnd || (!dist && !ss.rowdist && g_dev == c->g.p && c->g_zero);
+    c->graph_replays = 0, c->front_used = false;
+    const MethodChoice choice = resolve_method(method, ss, c->op_symmetric, c->world);
+    if (choice.refusal) return fail(c, choice.refusal, choice.why);
+    method = choice.method;
+    const bool bicg = method == FDAPDE_SOLVER_BICGSTAB, cgf = method == FDAPDE_SOLVER_CG_FUSED;
     // the smallest systems (solve_prepare: front_pending): everything in front of the single launch as ONE one-workgroup kernel, or two around A g~
     const bool front = ss.front_pending;
     ss.front_pending = false;
     c->front_used = front;
-    SmallFrontArgs fa{};
-    if (front) {
-        const fdapde_ctx::Persist& ps = c->ps[ss.use_bnd ? 1 : 0];
-        fa.n = n, fa.use_bnd = ss.use_bnd, fa.zero_y = zero_lift ? 1 : 0, fa.vec_grid = c->vec_grid;
-        fa.stat = c->stiff_stat.p, fa.bnd = c->bnd.p, fa.scale = c->scale.p, fa.ctl = c->ctl.p;
-        fa.nsl = ps.meta.nsl, fa.ell_off = ps.ell_off.p, fa.sl_off = ps.sl_off.p, fa.slot_dof = ps.slot_dof.p, fa.src = ps.ell_src.p, fa.col = ps.ell_col.p;
-        fa.A = ss.front_A, fa.ell_val = ps.ell_val.p;
-        fa.g = g_dev, fa.gt = c->gt.p, fa.y = c->y.p, fa.u = c->u.p;
-        if (!zero_lift) {
-            fa.phases = 1;
-            hipLaunchKernelGGL(k_small_front, dim3(1), dim3(256), 0, st, fa);
-        }
-    } else
-        hipLaunchKernelGGL(k_lift, dim3(g1(n)), dim3(256), 0, st, n, c->bnd.p, g_dev, ss.use_bnd, c->gt.p, zero_lift ? c->y.p : (double*)nullptr);
-    if (!zero_lift) {
-        launch_spmv(c, A, c->gt.p, c->y.p, nullptr, nullptr, nullptr);   // y = A g~
-        if (dist)
-            if (int rc = halo_sum(c, c->y.p, nullptr, 0)) return rc;
-    }
-    if (method == FDAPDE_SOLVER_AUTO)   // symmetric + positive diagonal: CG (fused-update form on one GPU, single-reduction form on several)
-        method = (c->op_symmetric && ss.diag_positive) ? (dist ? FDAPDE_SOLVER_CG : FDAPDE_SOLVER_CG_FUSED) : FDAPDE_SOLVER_BICGSTAB;
-    if (method == FDAPDE_SOLVER_CG && dist && c->world > 1) method = FDAPDE_SOLVER_CG_SR;   // one all-reduce per iteration
-    if (method == FDAPDE_SOLVER_CG_FUSED && dist) method = FDAPDE_SOLVER_CG_SR;   // y.y of the assembled y would need its own all-reduce
-    if ((method == FDAPDE_SOLVER_CG || method == FDAPDE_SOLVER_CG_SR || method == FDAPDE_SOLVER_CG_FUSED) && !ss.diag_positive)
-        return fail(c, FDAPDE_ENOCONV, "CG needs a positive diagonal (operator not SPD?); use BiCGStab");
-    const bool bicg = method == FDAPDE_SOLVER_BICGSTAB, cgsr = method == FDAPDE_SOLVER_CG_SR, cgf = method == FDAPDE_SOLVER_CG_FUSED;
-    const bool gmres = method == FDAPDE_SOLVER_GMRES;
-    if (gmres && (dist || ss.rowdist)) return fail(c, FDAPDE_EUNSUPPORTED, "GMRES runs on one-GPU contexts");
-    const double tol2 = rtol * rtol;
-    const double* ax = nullptr;
-    if (u0_dev) {   // warm start: x = (u0 - g~) / s, r = b~ - At x
-        if (int rc = ensure_sval(c)) return rc;
-        hipLaunchKernelGGL(k_krylov_init, dim3(c->vec_grid), dim3(256), 0, st, n, fvec, c->y.p, c->scale.p, c->x.p, c->r.p, c->p.p,
-                           (double*)nullptr, c->part_b.p, owned, u0_dev, c->gt.p, (const double*)nullptr, 1);
-        launch_spmv(c, c->sval.p, c->x.p, c->t.p, nullptr, nullptr, nullptr);
-        if (dist)
-            if (int rc = halo_sum(c, c->t.p, nullptr, 0)) return rc;
-        ax = c->t.p;
-    }
-    if (!front)
-        hipLaunchKernelGGL(k_krylov_init, dim3(c->vec_grid), dim3(256), 0, st, n, fvec, c->y.p, c->scale.p, c->x.p, c->r.p, c->p.p,
-                           bicg ? c->r0.p : (double*)nullptr, c->part_b.p, owned, u0_dev, c->gt.p, ax, 0);
-    if (front) {   // (one GPU, cold start: what the two launches of the other branch do)
-        const int V = c->cgf_v;
-        const int64_t b2 = c->cgf_band ? (((((n + 7) / 8) + 31) & ~int64_t(31)) >> 1) : 0, span = b2 > 0 ? b2 : (n >> 1);
-        const int per = (int)((span + 256 * V - 1) / (256 * V)) > 0 ? (int)((span + 256 * V - 1) / (256 * V)) : 1;
-        const int cg = b2 > 0 ? 8 * per : per;
-        fa.phases = zero_lift ? 3 : 2;
-        fa.f = fvec, fa.x = c->x.p, fa.r = c->r.p, fa.p = c->p.p, fa.r0 = bicg ? c->r0.p : (double*)nullptr, fa.partial = c->part_b.p, fa.sc = c->sc.p;
-        fa.seed = cgf ? c->part_b.p + cg : (double*)nullptr, fa.n_seed = cgf ? cg : 0, fa.tol2 = tol2;
-        hipLaunchKernelGGL(k_small_front, dim3(1), dim3(256), 0, st, fa);
-    } else if (dist || ss.rowdist) {
-        hipLaunchKernelGGL(k_reduce_partials2, dim3(1), dim3(256), 0, st, c->part_b.p, c->vec_grid, c->sbuf.p);
-        if (int rc = allreduce_sum(c, c->sbuf.p, 2)) return rc;
-        hipLaunchKernelGGL(k_krylov_init_fin, dim3(1), dim3(256), 0, st, c->sbuf.p, 1, c->sc.p, c->ctl.p, tol2, (double*)nullptr, 0);
-    } else {
-        // fused-update CG: its launch 0 reads the explicit r.r from the second half of part_b (seeded here)
-        const int V = c->cgf_v;
-        const int64_t b2 = c->cgf_band ? (((((n + 7) / 8) + 31) & ~int64_t(31)) >> 1) : 0, span = b2 > 0 ? b2 : (n >> 1);
-        const int per = (int)((span + 256 * V - 1) / (256 * V)) > 0 ? (int)((span + 256 * V - 1) / (256 * V)) : 1;
-        const int cg = b2 > 0 ? 8 * per : per;
-        hipLaunchKernelGGL(k_krylov_init_fin, dim3(1), dim3(256), 0, st, c->part_b.p, c->vec_grid, c->sc.p, c->ctl.p, tol2,
-                           cgf ? c->part_b.p + cg : (double*)nullptr, cgf ? cg : 0);
-    }
-    if (bicg && c->bicg_shadow && !dist && !ss.rowdist) {   // a shadow residual other than r0 (knob; measurements): r0~ and rho_0 = (r0~, r0)
-        hipLaunchKernelGGL(k_bicg_shadow, dim3(c->vec_grid), dim3(256), 0, st, n, c->bicg_shadow, c->r.p, c->r0.p, c->part_b.p);
-        hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(256), 0, st, c->part_b.p, c->vec_grid, c->sc.p + 9);
-    }
-    if (gmres) {   // the scaled right-hand side, for the true residual at the end of every restart cycle (c->y still holds A g~)
-        HIPCHK(c, c->gm_b.alloc((size_t)n));
-        hipLaunchKernelGGL(k_gm_rhs, dim3(g1(n)), dim3(256), 0, st, n, fvec, c->y.p, c->scale.p, c->gm_b.p);
-    }
-    if (cgsr) {   // p = s = 0 before the first update (beta = 0 there)
-        HIPCHK(c, hipMemsetAsync(c->p.p, 0, sizeof(double) * (size_t)n, st));
-        HIPCHK(c, hipMemsetAsync(c->s.p, 0, sizeof(double) * (size_t)n, st));
-    }
-    HIPCHK(c, hipGetLastError());
-    n_timed = n_timed < 0 ? 0 : (n_timed > 256 ? 256 : n_timed);
-    while ((int)c->ev_spmv.size() < 2 * n_timed) {
+    const int64_t n = c->hs.n_dofs;
+    SolveRun R{};
+    R.c = c, R.n = n, R.st = c->stream, R.tol2 = rtol * rtol;
+    R.np_spmv = (c->bk_cur >= 0 && !ss.dist) ? c->bk[c->bk_cur].meta.G : c->spmv_grid;
+    R.owned = ss.owned, R.dist = ss.dist, R.rowdist = ss.rowdist;
+    R.upd = update_grid(n, method == FDAPDE_SOLVER_CG_SR ? kCgV : c->cgf_v, c->cgf_band);
+    R.bi_grid = std::max(1, (int)(((n >> 1) + 256 * kBiV - 1) / (256 * kBiV)));
+    if (int rc = R.start_up(ss, front, method, A, f_dev, g_dev, u0_dev)) return rc;
+    R.n_timed = n_timed < 0 ? 0 : (n_timed > 256 ? 256 : n_timed);
+    while ((int)c->ev_spmv.size() < 2 * R.n_timed) {
         hipEvent_t e;
         HIPCHK(c, hipEventCreate(&e));
         c->ev_spmv.push_back(e);
     }
-    int timed = 0, launched = 0;
-    bool stop = false;
-    bool persisted = false;
-    bool unscaled = false;   // c->u already holds the solution (the single launch's epilogue ran behind it)
-    if (gmres) {
+    R.ev = c->ev_spmv.data();
+    bool persisted = false;   // the iteration ran as one launch (per rank): the iterate is c->persist_x
+    bool unscaled = false;    // ... and c->u already holds the solution (the launch's epilogue ran behind it)
+    if (method == FDAPDE_SOLVER_GMRES) {
         if (int rc = ensure_sval(c)) return rc;
-        if (int rc = run_gmres(c, tol2, maxit)) return rc;
-        stop = true, launched = c->h_ctl[1];
-        HIPCHK(c, hipMemcpyAsync(c->h_sc, c->sc.p, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-    }
-    if (ss.rowdist) {   // one launch per rank, the launches of all ranks acting as one grid (kernels_persist.h DIST)
-        if (int rc = run_rowdist(c, ss.use_bnd ? 1 : 0, tol2, maxit, &persisted, bicg)) return rc;
+        if (int rc = run_gmres(c, R.tol2, maxit)) return rc;
+        R.stop = true, R.launched = c->h_ctl[1];
+        if (int rc = read_outcome(c, /*ctl_too=*/false)) return rc;
+    } else if (ss.rowdist) {   // one launch per rank, the launches of all ranks acting as one grid (kernels_persist.h DIST)
+        if (int rc = run_rowdist(c, ss.use_bnd ? 1 : 0, R.tol2, maxit, &persisted, bicg)) return rc;
         if (!persisted) return fail(c, FDAPDE_EUNSUPPORTED, "row-distributed solve: an in-kernel hand-off between the ranks' launches timed out (boards not visible across the devices, or a rank's launch could not be resident); use the element-partitioned exchange (fdapde_halo_setup_peers) instead");
-        stop = true, launched = c->h_ctl[1];
+        R.stop = true, R.launched = c->h_ctl[1];
+    } else if (cgf || bicg) {
+        if (int rc = R.single_launch(ss, bicg, maxit, &persisted)) return rc;
+        if (persisted) R.stop = true, R.launched = c->h_ctl[1], unscaled = true;
     }
-    if (cgf && !dist && !ss.rowdist && c->persist && !c->persist_broken && c->ps[ss.use_bnd ? 1 : 0].ok && c->ps[ss.use_bnd ? 1 : 0].filled) {
-        // the whole iteration as ONE launch (kernels_persist.h); it leaves sc / ctl as the loop below would
-        DebugClock clk;
-        // the epilogue kernel (and, for fdapde_solve, the end-of-solve event) is enqueued BEHIND the launch before the host waits for it: one wait
-        // for launch, outcome and solution together; if the launch gave up, the fall-back below redoes the epilogue from its own iterate
-        c->persist_tail = [&]() -> int {
-            if (!c->tail_in_launch) hipLaunchKernelGGL(k_unscale, dim3(g1(n)), dim3(256), 0, st, n, c->scale.p, c->persist_x.p, c->gt.p, c->u.p);
-            if (c->ev1_at_end) HIPCHK(c, hipEventRecord(c->ev1, st));
-            return FDAPDE_OK;
-        };
-        const int rc_p = run_persist(c, ss.use_bnd ? 1 : 0, tol2, maxit, &persisted);
-        c->persist_tail = nullptr;
-        if (rc_p) return rc_p;
-        clk.mark("solve_run: run_persist");
-        if (persisted) stop = true, launched = c->h_ctl[1], unscaled = true;
-        else c->drop_prepared("the single launch gave up (persist_broken) or its layout does not launch");   // (a retry goes through a full prepare)
-    }
-    if (bicg && !dist && !ss.rowdist && c->persist && c->persist_bicg && !c->persist_broken) {   // the whole BiCGStab as one launch
-        const fdapde_ctx::Persist& ps = c->ps[ss.use_bnd ? 1 : 0];
-        if (ps.ok && ps.filled && !ps.meta.sym && ps.meta.R <= 8) {
-            c->persist_tail = [&]() -> int {   // (as for the CG launch above)
-                if (!c->tail_in_launch) hipLaunchKernelGGL(k_unscale, dim3(g1(n)), dim3(256), 0, st, n, c->scale.p, c->persist_x.p, c->gt.p, c->u.p);
-                if (c->ev1_at_end) HIPCHK(c, hipEventRecord(c->ev1, st));
-                return FDAPDE_OK;
-            };
-            const int rc_p = run_persist(c, ss.use_bnd ? 1 : 0, tol2, maxit, &persisted, /*bicg=*/true);
-            c->persist_tail = nullptr;
-            if (rc_p) return rc_p;
-            if (persisted) stop = true, launched = c->h_ctl[1], unscaled = true;
-            else c->drop_prepared("the single launch gave up (persist_broken) or its layout does not launch");
-        }
-    }
-    // one iteration of the fused-update CG: SpMV (p.y, y.y) + k_cgf_update; arguments depend on the iteration's parity only
-    const int cgf_V = c->cgf_v;
-    // XCD-aware mapping of the update kernel (knob cgf_band): workgroup b serves the elements of SpMV row band b % 8
-    const int64_t cgf_band2 = c->cgf_band ? (((((n + 7) / 8) + 31) & ~int64_t(31)) >> 1) : 0;
-    const int64_t cgf_span = cgf_band2 > 0 ? cgf_band2 : (n >> 1);
-    const int cgf_per = (int)((cgf_span + 256 * cgf_V - 1) / (256 * cgf_V)) > 0 ? (int)((cgf_span + 256 * cgf_V - 1) / (256 * cgf_V)) : 1;
-    const int cgf_grid = cgf_band2 > 0 ? 8 * cgf_per : cgf_per;
-    auto enqueue_cgf = [&](int it, hipEvent_t e0, hipEvent_t e1) {
-        const int cg = cgf_grid;
-        launch_spmv(c, c->sval.p, c->p.p, c->y.p, c->p.p, c->part_a.p, c->ctl.p, e0, e1);   // p.y and y.y
-#define CGF_GO(...)                                                                                                        \
-    hipLaunchKernelGGL((k_cgf_update<__VA_ARGS__>), dim3(cg), dim3(256), 0, st, n, c->y.p, c->p.p, c->x.p, c->r.p, c->part_a.p, np_spmv, \
-                       c->part_b.p + (size_t)((it + 1) & 1) * cg, cg, c->part_b.p + (size_t)(it & 1) * cg, c->sc.p, tol2, c->ctl.p, \
-                       cgf_band2, c->cgf_nt, c->cgf_lazy, it & 1)
-        if (cgf_V == 1) CGF_GO(1);
-        else if (cgf_V == 2) CGF_GO(2);
-        else if (cgf_V == 8) CGF_GO(8);
-        else CGF_GO(4);
-#undef CGF_GO
-    };
-    auto enqueue_cgf_fin = [&](int done) {   // explicit r.r of the last update -> sc[3] / stop flag
-        hipLaunchKernelGGL(k_cgf_fin, dim3(1), dim3(256), 0, st, c->part_b.p + (size_t)((done - 1) & 1) * cgf_grid, cgf_grid, c->sc.p, tol2,
-                           c->ctl.p);
-    };
-    const int bi_grid = (int)(((n >> 1) + 256 * kBiV - 1) / (256 * kBiV)) > 0 ? (int)(((n >> 1) + 256 * kBiV - 1) / (256 * kBiV)) : 1;
-    if (!stop && launched < maxit && !ss.rowdist)   // the multi-launch kernels read the scaled full-pattern copy
-        if (int rc = ensure_sval(c)) return rc;
-    while (!stop && launched < maxit && !ss.rowdist) {
-        const int chunk = (maxit - launched) < check_every ? (maxit - launched) : check_every;
-        // a full chunk of the fused-update CG with no timed launch replays ONE hipGraph (2 * chunk + 1 kernel nodes): the
-        // arguments repeat with period 2, so the graph captured for iterations 0 .. chunk-1 serves every even-aligned chunk
-        bool graphed = false;
-        if (cgf && c->use_graph && chunk == check_every && (chunk & 1) == 0 && (launched & 1) == 0 && timed >= n_timed) {
-            GraphKey key;
-            std::memset(&key, 0, sizeof key);   // padding bytes take part in the memcmp below
-            key.sval = c->sval.p, key.rowptr = c->sp_cur >= 0 ? (const void*)c->sp_rowptr[c->sp_cur].p : (const void*)c->rowptr.p;
-            key.n = n, key.tol2 = tol2, key.chunk = chunk, key.v = cgf_V, key.grid = c->spmv_grid, key.team = c->spmv_team;
-            key.c16 = c->spmv_c16, key.sp_cur = c->sp_cur;
-            // the blocked-ELL layout the captured SpMV nodes read from (its arrays and grid are baked into the graph)
-            key.bk_cur = c->bk_cur, key.bk_G = c->bk_cur >= 0 ? c->bk[c->bk_cur].meta.G : 0;
-            key.bk_val = c->bk_cur >= 0 ? (const void*)c->bk[c->bk_cur].ell_val.p : nullptr;
-            if (!c->cg_graph_exec || std::memcmp(&key, &c->cg_graph_key, sizeof key) != 0) {
-                if (c->cg_graph_exec) (void)hipGraphExecDestroy(c->cg_graph_exec), c->cg_graph_exec = nullptr;
-                hipGraph_t g = nullptr;
-                if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                    for (int it = 0; it < chunk; ++it) enqueue_cgf(it, nullptr, nullptr);
-                    enqueue_cgf_fin(chunk);
-                    if (hipStreamEndCapture(st, &g) == hipSuccess && g &&
-                        hipGraphInstantiate(&c->cg_graph_exec, g, nullptr, nullptr, 0) == hipSuccess)
-                        c->cg_graph_key = key;
-                    else
-                        c->cg_graph_exec = nullptr;
-                    if (g) (void)hipGraphDestroy(g);
-                }
-                (void)hipGetLastError();
-            }
-            if (c->cg_graph_exec && hipGraphLaunch(c->cg_graph_exec, st) == hipSuccess) launched += chunk, graphed = true, ++c->graph_replays;
-        }
-        for (int it = 0; !graphed && it < chunk; ++it, ++launched) {
-            if (cgsr) {
-                const int parity = launched & 1;
-                const bool tm = timed < n_timed && launched % kTimeStride == kTimePhase;   // every kTimeStride-th iteration is timed
-                // w = At r with delta = r.(At r) and gamma = r.r (owned rows) fused; multi-GPU: ONE all-reduce carries the
-                // interface entries of w and both partials
-                launch_spmv(c, c->sval.p, c->r.p, c->y.p, c->r.p, c->part_a.p, c->ctl.p, tm ? c->ev_spmv[2 * timed] : nullptr,
-                            tm ? c->ev_spmv[2 * timed + 1] : nullptr, 1, owned);
-                if (tm) ++timed;
-                const double* part = c->part_a.p;
-                int np = np_spmv;
-                if (dist) {
-                    // pack -> all-reduce; the update kernel reads the summed interface rows straight from hbuf (no unpack launch)
-                    if (int rc = halo_sum(c, c->y.p, c->part_a.p, c->spmv_grid, /*unpack=*/false)) return rc;
-                    part = c->hbuf.p + c->n_if, np = 1;
-                }
-                // XCD-aware mapping like k_cgf_update (kCgV elements per lane, bands of the SpMV's rows)
-                const int64_t sr_band2 = c->cgf_band ? (((((n + 7) / 8) + 31) & ~int64_t(31)) >> 1) : 0, sr_span = sr_band2 > 0 ? sr_band2 : (n >> 1);
-                const int sr_per = (int)((sr_span + 256 * kCgV - 1) / (256 * kCgV)) > 0 ? (int)((sr_span + 256 * kCgV - 1) / (256 * kCgV)) : 1;
-                hipLaunchKernelGGL(k_cgsr_update, dim3(sr_band2 > 0 ? 8 * sr_per : sr_per), dim3(256), 0, st, n, c->r.p, c->y.p, c->p.p,
-                                   c->s.p, c->x.p, part, np, c->sc.p, parity, launched == 0 ? 1 : 0, tol2, c->ctl.p,
-                                   dist ? c->if_slot.p : (const int32_t*)nullptr, dist ? c->hbuf.p : (const double*)nullptr, sr_band2);
-            } else if (cgf) {
-                const bool tm = timed < n_timed && launched % kTimeStride == kTimePhase;   // every kTimeStride-th iteration is timed
-                enqueue_cgf(launched, tm ? c->ev_spmv[2 * timed] : nullptr, tm ? c->ev_spmv[2 * timed + 1] : nullptr);
-                if (tm) ++timed;
-            } else if (!bicg) {
-                const int parity = launched & 1;
-                const bool tm = timed < n_timed && launched % kTimeStride == kTimePhase;   // every kTimeStride-th iteration is timed
-                launch_spmv(c, c->sval.p, c->p.p, c->y.p, c->p.p, c->part_a.p, c->ctl.p,
-                            tm ? c->ev_spmv[2 * timed] : nullptr, tm ? c->ev_spmv[2 * timed + 1] : nullptr);
-                if (tm) ++timed;
-                if (!dist) {
-                    hipLaunchKernelGGL(k_cg_update_xr, dim3(c->cg_grid), dim3(256), 0, st, n, c->y.p, c->r.p, c->part_a.p,
-                                       np_spmv, c->part_b.p, c->sc.p, parity, c->ctl.p, owned);
-                    hipLaunchKernelGGL(k_cg_update_p, dim3(c->cg_grid), dim3(256), 0, st, n, c->r.p, c->p.p, c->x.p, c->part_b.p,
-                                       c->cg_grid, c->sc.p, parity, tol2, c->ctl.p);
-                } else {
-                    // one all-reduce carries the interface entries of A_p p and the rank's p.Ap partial; a second one
-                    // (a single double) carries r.r.  Every rank takes the same stop decision from the same numbers.
-                    if (int rc = halo_sum(c, c->y.p, c->part_a.p, c->spmv_grid)) return rc;
-                    hipLaunchKernelGGL(k_cg_update_xr, dim3(c->cg_grid), dim3(256), 0, st, n, c->y.p, c->r.p, c->hbuf.p + c->n_if, 1,
-                                       c->part_b.p, c->sc.p, parity, c->ctl.p, owned);
-                    hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(256), 0, st, c->part_b.p, c->cg_grid, c->sbuf.p);
-                    if (int rc = allreduce_sum(c, c->sbuf.p, 1)) return rc;
-                    hipLaunchKernelGGL(k_cg_update_p, dim3(c->cg_grid), dim3(256), 0, st, n, c->r.p, c->p.p, c->x.p, c->sbuf.p, 1,
-                                       c->sc.p, parity, tol2, c->ctl.p);
-                }
-            } else if (!dist) {
-                hipLaunchKernelGGL(k_bicg_p, dim3(bi_grid), dim3(256), 0, st, n, c->r.p, c->y.p, c->p.p, c->part_b.p,
-                                   bi_grid, c->sc.p, launched == 0 ? 1 : 0, c->ctl.p);
-                const bool tm = timed < n_timed && launched % kTimeStride == kTimePhase;   // every kTimeStride-th iteration is timed
-                launch_spmv(c, c->sval.p, c->p.p, c->y.p, c->r0.p, c->part_a.p, c->ctl.p,   // v = At p, r0.v
-                            tm ? c->ev_spmv[2 * timed] : nullptr, tm ? c->ev_spmv[2 * timed + 1] : nullptr);
-                if (tm) ++timed;
-                hipLaunchKernelGGL(k_bicg_s, dim3(bi_grid), dim3(256), 0, st, n, c->r.p, c->y.p, c->s.p, c->part_a.p,
-                                   np_spmv, c->sc.p, c->ctl.p);
-                launch_spmv(c, c->sval.p, c->s.p, c->t.p, c->s.p, c->part_a.p, c->ctl.p);    // t = At s, t.s, t.t
-                hipLaunchKernelGGL(k_bicg_xr, dim3(bi_grid), dim3(256), 0, st, n, c->p.p, c->s.p, c->t.p, c->r0.p, c->x.p,
-                                   c->r.p, c->part_a.p, np_spmv, c->part_b.p, c->sc.p, c->ctl.p, (const uint8_t*)nullptr);
-                hipLaunchKernelGGL(k_bicg_fin, dim3(1), dim3(256), 0, st, c->part_a.p, np_spmv, c->part_b.p, bi_grid,
-                                   c->sc.p, tol2, c->ctl.p);
-            } else {
-                // element-partitioned BiCGStab: every operator application is followed by the interface sum, which also carries
-                // the dot fused into the SpMV (w.(A x) needs no weighting); dots of assembled vectors (t.t, r0.r, r.r) count
-                // owned rows and cross in two small all-reduces.  sbuf: [0..1] = (r0.r, r.r), [4..5] = (t.s, t.t).
-                hipLaunchKernelGGL(k_bicg_p, dim3(bi_grid), dim3(256), 0, st, n, c->r.p, c->y.p, c->p.p, c->sbuf.p, 1, c->sc.p,
-                                   launched == 0 ? 1 : 0, c->ctl.p);
-                const bool tm = timed < n_timed && launched % kTimeStride == kTimePhase;   // every kTimeStride-th iteration is timed
-                launch_spmv(c, c->sval.p, c->p.p, c->y.p, c->r0.p, c->part_a.p, c->ctl.p,
-                            tm ? c->ev_spmv[2 * timed] : nullptr, tm ? c->ev_spmv[2 * timed + 1] : nullptr);
-                if (tm) ++timed;
-                if (int rc = halo_sum(c, c->y.p, c->part_a.p, c->spmv_grid)) return rc;
-                hipLaunchKernelGGL(k_bicg_s, dim3(bi_grid), dim3(256), 0, st, n, c->r.p, c->y.p, c->s.p, c->hbuf.p + c->n_if, 1,
-                                   c->sc.p, c->ctl.p);
-                launch_spmv(c, c->sval.p, c->s.p, c->t.p, c->s.p, c->part_a.p, c->ctl.p);
-                if (int rc = halo_sum(c, c->t.p, c->part_a.p, c->spmv_grid)) return rc;
-                hipLaunchKernelGGL(k_sq_owned, dim3(c->vec_grid), dim3(256), 0, st, n, c->t.p, owned, c->part_b.p, c->ctl.p);
-                hipLaunchKernelGGL(k_bicg_tt_fin, dim3(1), dim3(256), 0, st, c->part_b.p, c->vec_grid, c->hbuf.p + c->n_if,
-                                   c->sbuf.p + 4);
-                if (int rc = allreduce_sum(c, c->sbuf.p + 5, 1)) return rc;
-                hipLaunchKernelGGL(k_bicg_xr, dim3(bi_grid), dim3(256), 0, st, n, c->p.p, c->s.p, c->t.p, c->r0.p, c->x.p,
-                                   c->r.p, c->sbuf.p + 4, 1, c->part_b.p, c->sc.p, c->ctl.p, owned);
-                hipLaunchKernelGGL(k_reduce_partials2, dim3(1), dim3(256), 0, st, c->part_b.p, bi_grid, c->sbuf.p);
-                if (int rc = allreduce_sum(c, c->sbuf.p, 2)) return rc;
-                hipLaunchKernelGGL(k_bicg_fin, dim3(1), dim3(256), 0, st, c->sbuf.p + 4, 1, c->sbuf.p, 1, c->sc.p, tol2, c->ctl.p);
-            }
-        }
-        if (cgf && launched > 0 && !graphed) enqueue_cgf_fin(launched);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(c->h_ctl, c->ctl.p, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemcpyAsync(c->h_sc, c->sc.p, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        stop = c->h_ctl[0] != 0;
-    }
-    if (cgsr && !stop && launched > 0 && !dist) {
-        // single-reduction CG out of iterations: sc[3] is the gamma = r.r its last SpMV measured, the residual BEFORE the last update.  info.relres is
-        // the residual of the x that is handed out: r.r of the last update, summed here (r vanishes on the Dirichlet rows).  A run whose LAST
-        // permitted update meets rtol therefore reports converged = 1 (the stale gamma said 0: the next SpMV would have seen it).  One GPU only:
-        // the element-partitioned form (dist) would need an all-reduce of its own for this and still reports the gamma of before its last update.
-        hipLaunchKernelGGL(k_sq_norm, dim3(c->vec_grid), dim3(256), 0, st, n, c->r.p, c->part_b.p);
-        hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(256), 0, st, c->part_b.p, c->vec_grid, c->sc.p + 3);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(c->h_sc, c->sc.p, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-    }
-    if (launched == 0 && !persisted) {   // already converged at the initial guess
-        HIPCHK(c, hipMemcpyAsync(c->h_ctl, c->ctl.p, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipMemcpyAsync(c->h_sc, c->sc.p, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-    }
-    if (cgf && c->cgf_lazy && !persisted)   // an update of x may still be pending (convergence seen at a poll, or maxit)
-        hipLaunchKernelGGL(k_cgf_flush, dim3(c->vec_grid), dim3(256), 0, st, n, c->p.p, c->r.p, c->x.p, c->sc.p, c->ctl.p);
-    if (!unscaled) {
-        hipLaunchKernelGGL(k_unscale, dim3(g1(n)), dim3(256), 0, st, n, c->scale.p, persisted ? c->persist_x.p : c->x.p, c->gt.p, c->u.p);
-        HIPCHK(c, hipGetLastError());
-        if (c->ev1_at_end) HIPCHK(c, hipEventRecord(c->ev1, st));
-        if (!c->defer_end_sync) HIPCHK(c, hipStreamSynchronize(st));   // (h_ctl / h_sc were read back behind a wait of their own)
-    }
-    const double bb = c->h_sc[0], rr = c->h_sc[3];
-    c->info.iters = c->h_ctl[1];
-    c->info.relres = bb > 0 ? sqrt(rr / bb) : 0.0;
-    c->info.converged = (rr <= tol2 * bb && c->h_ctl[2] == 0) ? 1 : 0;
-    c->info.method_used = method;
-    c->info.spmv_avg_ms = 0, c->info.spmv_timed = 0;
-    {   // launches after the stop flag return at once; only iterations that really ran are averaged
-        int real = 0;   // sample k was iteration k * kTimeStride
-        while (real < timed && real * kTimeStride + kTimePhase < c->info.iters) ++real;
-        double sum = 0;
-        for (int i = 0; i < real; ++i) {
-            float t = 0;
-            HIPCHK(c, hipEventElapsedTime(&t, c->ev_spmv[2 * i], c->ev_spmv[2 * i + 1]));
-            sum += t;
-        }
-        if (real > 0) c->info.spmv_avg_ms = sum / real, c->info.spmv_timed = real;
-    }
-    c->info.persistent = persisted ? 1 : 0;
-    c->info.launch_ms = persisted ? c->persist_launch_ms : 0.0;
-    c->info.gather_avg_ms = c->info.update_avg_ms = c->info.spmv_mean_ms = 0;
-    if (persisted && !c->persist_host_stats.empty() && c->persist_host_stats[0] > 0) {
-        // phase stamps of every workgroup (s_memrealtime ticks of 10 ns).  The operator application of an iteration is complete when
-        // the SLOWEST workgroup has its rows: spmv_avg_ms = max over workgroups of their average operator phase (SpMV + import wait);
-        // the mean over workgroups is reported next to it; all-gather (which contains the wait for the slowest) and update: means
-        const size_t G = c->persist_host_stats.size() / 4;
-        double mx = 0, mean = 0, gat = 0, upd = 0;
-        for (size_t g = 0; g < G; ++g) {
-            const double* st = &c->persist_host_stats[4 * g];
-            const double n_it = st[0] > 0 ? st[0] : 1;
-            mx = std::max(mx, st[1] / n_it), mean += st[1] / n_it, gat += st[2] / n_it, upd += st[3] / n_it;
-        }
-        if (std::getenv("FDAPDE_DEBUG_PERSIST")) {   // per-workgroup operator phases (us), with the workgroup's ELL entries
-            std::vector<int64_t> eo(G + 1);
-            std::vector<int32_t> io(G + 1), xo(G + 1);
-            const int v = ss.use_bnd ? 1 : 0;
-            (void)hipMemcpy(eo.data(), c->ps[v].ell_off.p, sizeof(int64_t) * (G + 1), hipMemcpyDeviceToHost);
-            (void)hipMemcpy(io.data(), c->ps[v].imp_off.p, sizeof(int32_t) * (G + 1), hipMemcpyDeviceToHost);
-            (void)hipMemcpy(xo.data(), c->ps[v].exp_off.p, sizeof(int32_t) * (G + 1), hipMemcpyDeviceToHost);
-            for (size_t g = 0; g < G; ++g)
-                std::fprintf(stderr, "persist wg %zu: operator %.2f us gather %.2f us entries %lld imports %d exports %d\n", g,
-                             c->persist_host_stats[4 * g + 1] / std::max(1.0, c->persist_host_stats[4 * g]) * 1e-2,
-                             c->persist_host_stats[4 * g + 2] / std::max(1.0, c->persist_host_stats[4 * g]) * 1e-2, (long long)(eo[g + 1] - eo[g]),
-                             io[g + 1] - io[g], xo[g + 1] - xo[g]);
-        }
-        c->info.spmv_avg_ms = mx * 1e-5, c->info.spmv_timed = (int32_t)c->persist_host_stats[0];
-        c->info.spmv_mean_ms = mean / (double)G * 1e-5, c->info.gather_avg_ms = gat / (double)G * 1e-5, c->info.update_avg_ms = upd / (double)G * 1e-5;
-    }
-    if (!c->info.converged) {
-        c->err = c->h_ctl[2] ? "Krylov breakdown (operator not SPD for CG, or BiCGStab rho/omega = 0)" : "maxit reached";
-        return FDAPDE_ENOCONV;   // reference: success = false (fem_linear_elliptic_solver.h:42-45)
-    }
-    return FDAPDE_OK;
+    if (int rc = R.run_chunks(method, maxit, check_every)) return rc;
+    return R.finish(ss, method, persisted, unscaled);
 }
 
 // solve_run, with a BiCGStab that BROKE DOWN (rho, r0.v or omega exactly 0 -- on advection-dominated operators the recurrences get there --
@@ -860,7 +957,6 @@ int solve_run_restarting(fdapde_ctx* c, const SolveState& ss, const double* A, c
     // (1 089 DOFs, Pe 150: 43 ms of BiCGStab in front of a 10 ms inversion).  CG stages and budgets the caller set are untouched.
     const bool will_bicg = method == FDAPDE_SOLVER_BICGSTAB || (method == FDAPDE_SOLVER_AUTO && !(c->op_symmetric && ss.diag_positive));
     const bool later_stage = gmres_budget > 0 && !ss.dist && !ss.rowdist && (c->auto_gmres || dense_eligible(c));
-    const int full_maxit = maxit;
     if (will_bicg && later_stage) {
         int64_t cap = 2 * n + 200;
         // ... and where that later stage is the dense direct solve, rent or buy: BiCGStab may spend what the inversion will cost (its estimate over ~3 us +
@@ -869,7 +965,6 @@ int solve_run_restarting(fdapde_ctx* c, const SolveState& ss, const double* A, c
         if (dense_eligible(c)) cap = std::min<int64_t>(cap, std::max<int64_t>(200, (int64_t)(1e3 * dense_build_estimate_ms(n) / (3.0 + (double)n / 700.0))));
         maxit = (int)std::min<int64_t>(maxit, cap);
     }
-    (void)full_maxit;
     int rc = solve_run(c, ss, A, f_dev, g_dev, u0_dev, method, rtol, maxit, check_every, n_timed);
     int total = c->info.iters;
     const bool may_restart = method == FDAPDE_SOLVER_BICGSTAB || method == FDAPDE_SOLVER_AUTO;   // a method named explicitly is never replaced
@@ -1028,8 +1123,7 @@ int e_solve(fdapde_ctx* c, const fdapde_options* opt, fdapde_info* info) {
     if (opt && opt->method == FDAPDE_SOLVER_DENSE) {
         // the direct solve asked for by name (what the reference's SparseLU does, fem_linear_elliptic_solver.h:38-47): the reference's own row-zeroed matrix
         // inverted on the device, one product; no Krylov stage in front, no fall-back behind -- a singular matrix is reported (success = false)
-        if (!dense_eligible(c))
-            return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_DENSE takes one-GPU systems of up to `dense_rows` (at most 8192) DOFs");
+        if (!dense_eligible(c)) return fail(c, FDAPDE_EUNSUPPORTED, kDenseRefusal);
         bool solved = false;
         c->scaled_owner = fdapde_ctx::kScaledNone;
         if (int rc = dense_direct(c, A, c->have_g ? 1 : 0, c->force.p, c->g.p, &solved)) return rc;
@@ -1044,7 +1138,7 @@ int e_solve(fdapde_ctx* c, const fdapde_options* opt, fdapde_info* info) {
         c->solved = solved, c->dirichlet_applied = c->have_g;
         if (info) *info = c->info;
         if (!solved) {
-            c->err = "FDAPDE_SOLVER_DENSE: the matrix is singular to working precision (no usable pivot, or max |I - A X| beyond 1e-6)";
+            c->err = dense_singular("the matrix");
             return FDAPDE_ENOCONV;
         }
         return FDAPDE_OK;
@@ -1072,7 +1166,7 @@ int e_solve(fdapde_ctx* c, const fdapde_options* opt, fdapde_info* info) {
     DebugClock clk;
     const bool open_method = !opt || opt->method == FDAPDE_SOLVER_AUTO;
     const bool skip_cg = open_method && c->cg_broke_down;   // (this very matrix broke CG before: see below)
-    const int gm_budget = !open_method ? -1 : ((opt && opt->maxit > 0) ? 0 : default_maxit(c, n));   // (the GMRES stage of the open method)
+    const int gm_budget = open_gmres_budget(c, opt, n);
     if (int rc = solve_prepare(c, A, c->have_g ? 1 : 0, &ss, c->op_symmetric && !skip_cg, /*allow_defer=*/true, /*reuse=*/true)) return rc;
     clk.mark("fdapde_solve: solve_prepare");
     HIPCHK(c, hipEventRecord(c->ev1, c->stream));   // (a solve that ends before its epilogue -- an early refusal -- still leaves a recorded event)
@@ -1097,15 +1191,8 @@ int e_solve(fdapde_ctx* c, const fdapde_options* opt, fdapde_info* info) {
                                       maxit, check_every, opt ? opt->time_spmv : 0, gm_budget);
         }
     }
-    // (the ranks of a multi-GPU job take this turn TOGETHER: the breakdown word comes out of sums every rank holds bit for bit, and the ranks say so to
-    //  each other before any of them re-prepares -- a rank that disagreed would leave the others in the collectives of the second solve)
-    bool cg_broke = rc == FDAPDE_ENOCONV && c->h_ctl[2] != 0 && (!opt || opt->method == FDAPDE_SOLVER_AUTO) && is_cg_method(c->info.method_used);
-    if ((ss.dist || ss.rowdist) && (!opt || opt->method == FDAPDE_SOLVER_AUTO) && (rc == FDAPDE_OK || rc == FDAPDE_ENOCONV)) {
-        int yes = 0;
-        if (int rc2 = ranks_saying_yes(c, cg_broke, &yes)) return rc2;
-        if (yes != 0 && yes != c->world) return fail(c, FDAPDE_ERCCL, "fdapde_solve: the ranks disagree on the outcome of the CG stage");
-        cg_broke = yes == c->world;
-    }
+    bool cg_broke = false;
+    if (int rc2 = cg_breakdown_agreed(c, ss, rc, open_method, "fdapde_solve: the ranks disagree on the outcome of the CG stage", &cg_broke)) return rc2;
     if (cg_broke) {
         // CG broke down (p.Ap <= 0): the operator is symmetric but not positive definite -- e.g. 3-D P2 with a large reaction term: the
         // reference's 5-point rule has a negative weight, its mass matrix is indefinite (integrator_tables.h:275-292).  The reference's LU solves
@@ -1173,10 +1260,70 @@ int coarse_solve(fdapde_ctx* c, SolveState* ss, double rtol, int maxit, fdapde_i
     return rc;
 }
 
+namespace {
+
+// what the steps of an iterative stepper add up to: iterations, the worst relres, FDAPDE_ENOCONV if a step did not converge
+struct StepTally {
+    int iters = 0, rc = FDAPDE_OK;
+    double worst = 0;
+    bool gave_up = false;   // (give_up_on_first: the first step did not converge, nothing of the call is done)
+};
+
+// The time-stepping loop of the iterative solvers: rhs = (M / dt) u_i + f_{i+1}, the Dirichlet column i + 1 up and into the internal order (gcol),
+// one solve -- step(i, rhs, gcol, uprev) leaves c->u and c->info and returns FDAPDE_OK, FDAPDE_ENOCONV or a hard error --, u_i <- u, the column
+// down.  Everything is on the one stream; wait_each_step: the host waits for the column before the next step starts
+template <typename Step>
+int step_loop(fdapde_ctx* c, int32_t n_times, double inv_dt, const double* dirichlet, double* solution, double* rhs, double* gcol, double* uprev, bool wait_each_step,
+              bool give_up_on_first, Step&& step, StepTally& tally) {
+    const int64_t n = c->hs.n_dofs;
+    hipStream_t st = c->stream;
+    for (int32_t i = 0; i + 1 < n_times; ++i) {
+        launch_spmv(c, c->vals[FDAPDE_MAT_MASS].p, uprev, c->s.p, nullptr, nullptr, nullptr);   // M u_i
+        hipLaunchKernelGGL(k_parabolic_rhs, dim3(g1(n)), dim3(256), 0, st, n, c->s.p, inv_dt, c->force.p + (size_t)(i + 1) * n, rhs);
+        if (dirichlet) {   // column i + 1 as handed over, brought into the internal order on the device (no wait here)
+            HIPCHK(c, hipMemcpyAsync(c->tmp_i.p, dirichlet + (size_t)(i + 1) * n, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(k_gather_f64, dim3(g1(n)), dim3(256), 0, st, n, c->dof_i2e.p, c->tmp_i.p, gcol);
+        }
+        const int rc = step(i, rhs, gcol, uprev);
+        if (rc != FDAPDE_OK && rc != FDAPDE_ENOCONV) return rc;
+        if (rc == FDAPDE_ENOCONV && i == 0 && give_up_on_first) {
+            tally.gave_up = true;
+            c->err.clear();
+            return FDAPDE_OK;
+        }
+        if (rc == FDAPDE_ENOCONV) tally.rc = rc;
+        tally.iters += c->info.iters, tally.worst = std::max(tally.worst, c->info.relres);
+        HIPCHK(c, hipMemcpyAsync(uprev, c->u.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(k_scatter_f64, dim3(g1(n)), dim3(256), 0, st, n, c->dof_i2e.p, c->u.p, c->tmp_e.p);
+        HIPCHK(c, hipMemcpyAsync(solution + (size_t)(i + 1) * n, c->tmp_e.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
+        if (wait_each_step) HIPCHK(c, hipStreamSynchronize(st));   // (tmp_e is reused by the next step)
+    }
+    return FDAPDE_OK;
+}
+
+// The end of every path of the stepper: the event behind the last download and the wait for it, the call's figures into the record.  method_used
+// < 0: the record keeps what the last step ran (and its `persistent`); owner < 0: the shared buffers keep their owner
+int stepper_end(fdapde_ctx* c, const StepTally& t, int method_used, int owner, int64_t open_steps, fdapde_info* info) {
+    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+    HIPCHK(c, hipEventSynchronize(c->ev1));
+    float ms = 0;
+    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    c->info.t_solve_ms = ms, c->info.iters = t.iters, c->info.relres = t.worst, c->info.converged = t.rc == FDAPDE_OK ? 1 : 0;
+    if (method_used >= 0) c->info.method_used = method_used, c->info.persistent = 0;
+    if (owner >= 0) c->scaled_owner = owner;
+    c->open_solves += open_steps;
+    if (info) *info = c->info;
+    return t.rc;
+}
+
+}   // namespace
+
 // FEMLinearParabolicSolver::solve (fdaPDE/finite_elements/solvers/fem_linear_parabolic_solver.h:37-72): implicit Euler,
 //   K = M / dt + A ; Dirichlet rows of K ; for i = 0 .. m-2:  rhs = (M / dt) u_i + f_{i+1} ; rhs[boundary] = g(., i+1) ;
 //   u_{i+1} = K^{-1} rhs.   The reference factorises K once with SparseLU; here K is scaled once and every step is a
 //   Jacobi-PCG (or BiCGStab) solve warm-started from u_i.  Forcing columns come from fdapde_set_forcing (n_times columns).
+// Four solvers: a small K is inverted once (the dense loops, below); FDAPDE_SOLVER_AMG, the two-level solver and the Jacobi-Krylov stages go
+// through step_loop, each with its own step.
 int e_solve_parabolic(fdapde_ctx* c, const fdapde_options* opt, int32_t n_times, double delta_t, const double* initial_condition,
                            const double* dirichlet, double* solution, fdapde_info* info) {
     if (!c || n_times < 1 || !(delta_t > 0) || !initial_condition || !solution) return FDAPDE_EINVAL;
@@ -1192,217 +1339,124 @@ int e_solve_parabolic(fdapde_ctx* c, const fdapde_options* opt, int32_t n_times,
     const int maxit = (opt && opt->maxit > 0) ? opt->maxit : default_maxit(c, n);
     const int check_every = (opt && opt->check_every > 0) ? opt->check_every : 8;
     const double inv_dt = 1.0 / delta_t;
-    DBuf<double> kmat, uprev, rhs, gcol;
+    const bool open_method = !opt || opt->method == FDAPDE_SOLVER_AUTO;
+    const int use_bnd = dirichlet ? 1 : 0;
+    DBuf<double> kmat, uprev, rhs, gcol;   // (released when the call returns)
     HIPCHK(c, kmat.alloc((size_t)hs.nnz + 2));
     HIPCHK(c, uprev.alloc((size_t)n));
     HIPCHK(c, rhs.alloc((size_t)n));
     HIPCHK(c, gcol.alloc((size_t)n));
     std::vector<double> tmp((size_t)n);
     if (int rc = ensure_host(c, kHostPerm)) return rc;
-    auto to_internal = [&](const double* ext) {
-        for (int64_t i = 0; i < n; ++i) tmp[(size_t)i] = ext[hs.dof_i2e[(size_t)i]];
+    // u_0 into the internal order and up (tmp is pageable: the wait), solution_.col(0) = initial condition (line 46)
+    auto initial_up = [&]() -> int {
+        for (int64_t i = 0; i < n; ++i) tmp[(size_t)i] = initial_condition[hs.dof_i2e[(size_t)i]];
+        HIPCHK(c, hipMemcpyAsync(uprev.p, tmp.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        std::memcpy(solution, initial_condition, sizeof(double) * (size_t)n);
+        return FDAPDE_OK;
     };
     HIPCHK(c, hipEventRecord(c->ev0, st));
     hipLaunchKernelGGL(k_matrix_combine, dim3(g1(hs.nnz)), dim3(256), 0, st, hs.nnz, c->vals[FDAPDE_MAT_MASS].p,
                        c->vals[FDAPDE_MAT_STIFF].p, inv_dt, kmat.p);
     // K is fixed over the steps: the reference factorises it ONCE and back-substitutes per step (fem_linear_parabolic_solver.h:41,56-68).  A small K is
-    // inverted once here (kernels_dense.h) and a step is two products -- M u_i and K^-1 rhs -- with nothing returning to the host inside the loop.
+    // inverted once here (kernels_dense.h) and a step is two products -- M u_i and K^-1 rhs -- with nothing returning to the host inside the loop: every
+    // Dirichlet column goes up in front, the solution stays on the device and comes down once.
     // (a warm-started Krylov step of such a system costs ~0.2 ms: worth it when the steps add up to half an inversion)
     const bool dense_named = opt && opt->method == FDAPDE_SOLVER_DENSE;
-    if (dense_named && !dense_eligible(c))
-        return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_DENSE takes one-GPU systems of up to `dense_rows` (at most 8192) DOFs");
-    if ((!opt || opt->method == FDAPDE_SOLVER_AUTO || dense_named) && dense_eligible(c) &&
+    if (dense_named && !dense_eligible(c)) return fail(c, FDAPDE_EUNSUPPORTED, kDenseRefusal);
+    if ((open_method || dense_named) && dense_eligible(c) &&
         (dense_named || c->dense_after == 0 || (n_times - 1 > c->dense_after && 0.2 * (n_times - 1) >= 0.5 * dense_build_estimate_ms(n)))) {
         fdapde_ctx::Dense& D = c->step_dense;
         D.ready = D.failed = false;
-        if (int rc = dense_build(c, kmat.p, dirichlet ? 1 : 0, D)) return rc;
+        if (int rc = dense_build(c, kmat.p, use_bnd, D)) return rc;
         if (D.ready) {
             DBuf<double> d_dir, d_sol;
             const size_t cols = (size_t)n_times;
             HIPCHK(c, d_sol.alloc((size_t)n * cols));
             if (dirichlet) HIPCHK(c, d_dir.upload(dirichlet, (size_t)n * cols, st));
-            to_internal(initial_condition);
-            HIPCHK(c, hipMemcpyAsync(uprev.p, tmp.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
-            HIPCHK(c, hipStreamSynchronize(st));   // (tmp is pageable)
+            if (int rc = initial_up()) return rc;
             if (!D.refine && c->dense_fold) {   // ONE product per step: u_{i+1} = (K^-1 M / dt) u_i + K^-1 (f_{i+1}, g_{i+1})
                 if (int rc = dense_step_loop(c, D, n_times, inv_dt, dirichlet ? d_dir.p : nullptr, uprev.p, d_sol.p)) return rc;
             } else
-            for (int32_t i = 0; i + 1 < n_times; ++i) {
-                launch_spmv(c, c->vals[FDAPDE_MAT_MASS].p, uprev.p, c->s.p, nullptr, nullptr, nullptr);   // M u_i
-                dense_step_rhs(c, c->s.p, inv_dt, c->force.p + (size_t)(i + 1) * n, dirichlet ? d_dir.p + (size_t)(i + 1) * n : nullptr, rhs.p);   // (+ rhs[boundary] = g(., i + 1), line 66)
-                if (int rc = dense_apply(c, D, 1, rhs.p, c->u.p)) return rc;
-                dense_step_out(c, c->u.p, uprev.p, d_sol.p + (size_t)(i + 1) * n);
-            }
+                for (int32_t i = 0; i + 1 < n_times; ++i) {
+                    launch_spmv(c, c->vals[FDAPDE_MAT_MASS].p, uprev.p, c->s.p, nullptr, nullptr, nullptr);   // M u_i
+                    dense_step_rhs(c, c->s.p, inv_dt, c->force.p + (size_t)(i + 1) * n, dirichlet ? d_dir.p + (size_t)(i + 1) * n : nullptr, rhs.p);   // (+ rhs[boundary] = g(., i + 1), line 66)
+                    if (int rc = dense_apply(c, D, 1, rhs.p, c->u.p)) return rc;
+                    dense_step_out(c, c->u.p, uprev.p, d_sol.p + (size_t)(i + 1) * n);
+                }
             HIPCHK(c, hipGetLastError());
             HIPCHK(c, hipMemcpyAsync(solution + (size_t)n, d_sol.p + (size_t)n, sizeof(double) * (size_t)n * (cols - 1), hipMemcpyDeviceToHost, st));
-            HIPCHK(c, hipEventRecord(c->ev1, st));
-            HIPCHK(c, hipEventSynchronize(c->ev1));
-            std::memcpy(solution, initial_condition, sizeof(double) * (size_t)n);   // solution_.col(0) = initial condition (line 46)
-            float ms_d = 0;
-            HIPCHK(c, hipEventElapsedTime(&ms_d, c->ev0, c->ev1));
-            c->info.t_solve_ms = ms_d, c->info.iters = D.refine ? n_times - 1 : 0, c->info.relres = D.check, c->info.converged = 1;
-            c->info.method_used = FDAPDE_SOLVER_DENSE, c->info.persistent = 0, c->info.launch_ms = 0;
-            c->scaled_owner = fdapde_ctx::kScaledNone;
+            StepTally t;
+            t.iters = D.refine ? n_times - 1 : 0, t.worst = D.check;
+            c->info.launch_ms = 0;
+            const int rc = stepper_end(c, t, FDAPDE_SOLVER_DENSE, fdapde_ctx::kScaledNone, 0, info);
             D.X.release(), D.ready = false;   // (K belongs to this call)
-            if (info) *info = c->info;
-            kmat.release(), uprev.release(), rhs.release(), gcol.release();
-            return FDAPDE_OK;
+            return rc;
         }
-        if (dense_named) {
-            c->info = fdapde_info{};
-            c->info.method_used = FDAPDE_SOLVER_DENSE, c->info.relres = D.check;
-            if (info) *info = c->info;
-            c->err = "FDAPDE_SOLVER_DENSE: M / dt + A is singular to working precision (no usable pivot, or max |I - A X| beyond 1e-6)";
-            return FDAPDE_ENOCONV;
-        }
+        if (dense_named) return c->err = dense_singular("M / dt + A"), bare_answer(c, FDAPDE_SOLVER_DENSE, D.check, info, FDAPDE_ENOCONV);
     }
     // FDAPDE_SOLVER_AMG by name: the hierarchy of K built once for the call, every step warm-started from the previous column (eng_amg.hip)
     if (opt && opt->method == FDAPDE_SOLVER_AMG) {
         if (!amg_eligible(c)) return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_AMG takes one-GPU contexts");
         const int am_maxit = (opt->maxit > 0) ? opt->maxit : 200;
-        if (int rc = amg_build(c, &c->amg, kmat.p, dirichlet ? 1 : 0, c->op_symmetric)) {
-            c->info = fdapde_info{};
-            c->info.method_used = FDAPDE_SOLVER_AMG;
-            if (info) *info = c->info;
-            return rc;
-        }
-        to_internal(initial_condition);
-        HIPCHK(c, hipMemcpyAsync(uprev.p, tmp.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        int total = 0, rc_am = FDAPDE_OK;
-        double worst_am = 0;
-        for (int32_t i = 0; i + 1 < n_times; ++i) {
-            launch_spmv(c, c->vals[FDAPDE_MAT_MASS].p, uprev.p, c->s.p, nullptr, nullptr, nullptr);   // M u_i
-            hipLaunchKernelGGL(k_parabolic_rhs, dim3(g1(n)), dim3(256), 0, st, n, c->s.p, inv_dt, c->force.p + (size_t)(i + 1) * n, rhs.p);
-            if (dirichlet) {
-                HIPCHK(c, hipMemcpyAsync(c->tmp_i.p, dirichlet + (size_t)(i + 1) * n, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
-                hipLaunchKernelGGL(k_gather_f64, dim3(g1(n)), dim3(256), 0, st, n, c->dof_i2e.p, c->tmp_i.p, gcol.p);
-            }
-            const int rc = amg_run(c, c->amg, kmat.p, rhs.p, gcol.p, dirichlet ? 1 : 0, uprev.p, rtol, am_maxit);
-            if (rc != FDAPDE_OK && rc != FDAPDE_ENOCONV) return rc;
-            if (rc == FDAPDE_ENOCONV) rc_am = rc;
-            total += c->info.iters, worst_am = std::max(worst_am, c->info.relres);
-            HIPCHK(c, hipMemcpyAsync(uprev.p, c->u.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
-            hipLaunchKernelGGL(k_scatter_f64, dim3(g1(n)), dim3(256), 0, st, n, c->dof_i2e.p, c->u.p, c->tmp_e.p);
-            HIPCHK(c, hipMemcpyAsync(solution + (size_t)(i + 1) * n, c->tmp_e.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
-            HIPCHK(c, hipStreamSynchronize(st));   // (tmp_e is reused by the next step)
-        }
-        std::memcpy(solution, initial_condition, sizeof(double) * (size_t)n);   // solution_.col(0) = initial condition (line 46)
-        HIPCHK(c, hipEventRecord(c->ev1, st));
-        HIPCHK(c, hipEventSynchronize(c->ev1));
-        float ms_a = 0;
-        HIPCHK(c, hipEventElapsedTime(&ms_a, c->ev0, c->ev1));
-        c->info.t_solve_ms = ms_a, c->info.iters = total, c->info.relres = worst_am, c->info.converged = rc_am == FDAPDE_OK ? 1 : 0;
-        c->info.method_used = FDAPDE_SOLVER_AMG, c->info.persistent = 0;
-        amg_forget(c);   // (K belongs to this call)
-        if (info) *info = c->info;
-        if (rc_am != FDAPDE_OK) c->err = "FDAPDE_SOLVER_AMG: a step did not converge";
-        kmat.release(), uprev.release(), rhs.release(), gcol.release();
-        return rc_am;
+        if (int rc = amg_build(c, &c->amg, kmat.p, use_bnd, c->op_symmetric)) return bare_answer(c, FDAPDE_SOLVER_AMG, 0.0, info, rc);
+        if (int rc = initial_up()) return rc;
+        StepTally t;
+        auto step = [&](int32_t, const double* rhs_i, const double* g_i, const double* u_i) {
+            return amg_run(c, c->amg, kmat.p, rhs_i, g_i, use_bnd, u_i, rtol, am_maxit);
+        };
+        if (int rc = step_loop(c, n_times, inv_dt, dirichlet, solution, rhs.p, gcol.p, uprev.p, /*wait_each_step=*/true, /*give_up_on_first=*/false, step, t)) return rc;
+        if (t.rc != FDAPDE_OK) c->err = "FDAPDE_SOLVER_AMG: a step did not converge";
+        const int rc = stepper_end(c, t, FDAPDE_SOLVER_AMG, -1, 0, info);
+        amg_forget(c);   // (K belongs to this call; behind the event and its wait, so that t_solve_ms does not hold the teardown)
+        return rc;
     }
     // Large order-2 systems (or FDAPDE_SOLVER_PMG by name): every step through the two-level solver (eng_pmg.hip) -- the coarse operator is the P1 assembly of
     // the same terms + M1 / dt, built once for the call; a step starts from the previous column.  A first step it does not solve sends the open method to
-    // the Jacobi-preconditioned loop below.
+    // the Jacobi-preconditioned steps below, from the start.
     const bool pmg_named = opt && opt->method == FDAPDE_SOLVER_PMG;
     if (pmg_named && !pmg_eligible(c))
         return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_PMG takes one-GPU contexts and order-2 spaces");
-    if (pmg_named || ((!opt || opt->method == FDAPDE_SOLVER_AUTO) && c->pmg_auto && n >= c->pmg_auto_rows &&
+    if (pmg_named || (open_method && c->pmg_auto && n >= c->pmg_auto_rows &&
                       (n >= c->pmg_auto_first_rows || c->pmg.ready || c->open_solves >= 1 || n_times > 5) && pmg_eligible(c))) {
         const int pm_maxit = pmg_named ? ((opt && opt->maxit > 0) ? opt->maxit : 400) : ((opt && opt->maxit > 0) ? std::min(opt->maxit, 60) : 60);
-        to_internal(initial_condition);
-        HIPCHK(c, hipMemcpyAsync(uprev.p, tmp.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        int total = 0, rc_pm = FDAPDE_OK;
-        double worst_pm = 0;
-        bool gave_up = false;
-        for (int32_t i = 0; i + 1 < n_times; ++i) {
-            launch_spmv(c, c->vals[FDAPDE_MAT_MASS].p, uprev.p, c->s.p, nullptr, nullptr, nullptr);   // M u_i
-            hipLaunchKernelGGL(k_parabolic_rhs, dim3(g1(n)), dim3(256), 0, st, n, c->s.p, inv_dt, c->force.p + (size_t)(i + 1) * n, rhs.p);
-            if (dirichlet) {
-                HIPCHK(c, hipMemcpyAsync(c->tmp_i.p, dirichlet + (size_t)(i + 1) * n, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
-                hipLaunchKernelGGL(k_gather_f64, dim3(g1(n)), dim3(256), 0, st, n, c->dof_i2e.p, c->tmp_i.p, gcol.p);
-            }
-            const int rc = pmg_run(c, kmat.p, rhs.p, gcol.p, dirichlet ? 1 : 0, uprev.p, inv_dt, 2 * c->init_count + 1, rtol, pm_maxit);
-            if (rc != FDAPDE_OK && rc != FDAPDE_ENOCONV) return rc;
-            if (rc == FDAPDE_ENOCONV && i == 0 && !pmg_named) {   // not a system for it: the loop below, from the start
-                gave_up = true;
-                c->err.clear();
-                break;
-            }
-            if (rc == FDAPDE_ENOCONV) rc_pm = rc;
-            total += c->info.iters, worst_pm = std::max(worst_pm, c->info.relres);
-            HIPCHK(c, hipMemcpyAsync(uprev.p, c->u.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
-            hipLaunchKernelGGL(k_scatter_f64, dim3(g1(n)), dim3(256), 0, st, n, c->dof_i2e.p, c->u.p, c->tmp_e.p);
-            HIPCHK(c, hipMemcpyAsync(solution + (size_t)(i + 1) * n, c->tmp_e.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
-            HIPCHK(c, hipStreamSynchronize(st));   // (tmp_e is reused by the next step)
-        }
-        if (!gave_up) {
-            std::memcpy(solution, initial_condition, sizeof(double) * (size_t)n);   // solution_.col(0) = initial condition (line 46)
-            HIPCHK(c, hipEventRecord(c->ev1, st));
-            HIPCHK(c, hipEventSynchronize(c->ev1));
-            float ms_p = 0;
-            HIPCHK(c, hipEventElapsedTime(&ms_p, c->ev0, c->ev1));
-            c->info.t_solve_ms = ms_p, c->info.iters = total, c->info.relres = worst_pm, c->info.converged = rc_pm == FDAPDE_OK ? 1 : 0;
-            c->info.method_used = FDAPDE_SOLVER_PMG, c->info.persistent = 0;
-            c->scaled_owner = fdapde_ctx::kScaledNone;
-            if (!pmg_named) c->open_solves += n_times - 1;
-            if (info) *info = c->info;
-            kmat.release(), uprev.release(), rhs.release(), gcol.release();
-            return rc_pm;
-        }
+        if (int rc = initial_up()) return rc;
+        StepTally t;
+        auto step = [&](int32_t, const double* rhs_i, const double* g_i, const double* u_i) {
+            return pmg_run(c, kmat.p, rhs_i, g_i, use_bnd, u_i, inv_dt, 2 * c->init_count + 1, rtol, pm_maxit);
+        };
+        if (int rc = step_loop(c, n_times, inv_dt, dirichlet, solution, rhs.p, gcol.p, uprev.p, /*wait_each_step=*/true, /*give_up_on_first=*/!pmg_named, step, t)) return rc;
+        if (!t.gave_up) return stepper_end(c, t, FDAPDE_SOLVER_PMG, fdapde_ctx::kScaledNone, pmg_named ? 0 : n_times - 1, info);
     }
+    // The Jacobi-Krylov stages (solve_run_restarting), K prepared once: a step's outcome is read inside solve_run and what follows it is ordered by the
+    // stream, so the host does not wait between the steps
     SolveState ss;
     c->scaled_owner = fdapde_ctx::kScaledParabolic;
-    if (int rc = solve_prepare(c, kmat.p, dirichlet ? 1 : 0, &ss, c->op_symmetric)) return rc;
-    to_internal(initial_condition);
-    HIPCHK(c, hipMemcpyAsync(uprev.p, tmp.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    std::memcpy(solution, initial_condition, sizeof(double) * (size_t)n);   // solution_.col(0) = initial condition (line 46)
-    int total_iters = 0, rc_all = FDAPDE_OK;
-    double worst = 0;
+    if (int rc = solve_prepare(c, kmat.p, use_bnd, &ss, c->op_symmetric)) return rc;
+    if (int rc = initial_up()) return rc;
     int step_method = opt ? opt->method : FDAPDE_SOLVER_AUTO;
-    for (int32_t i = 0; i + 1 < n_times; ++i) {
-        launch_spmv(c, c->vals[FDAPDE_MAT_MASS].p, uprev.p, c->s.p, nullptr, nullptr, nullptr);   // M u_i
-        hipLaunchKernelGGL(k_parabolic_rhs, dim3(g1(n)), dim3(256), 0, st, n, c->s.p, inv_dt, c->force.p + (size_t)(i + 1) * n, rhs.p);
-        if (dirichlet) {   // column i + 1 as handed over, brought into the internal order on the device (everything on the one stream: no wait here)
-            HIPCHK(c, hipMemcpyAsync(c->tmp_i.p, dirichlet + (size_t)(i + 1) * n, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(k_gather_f64, dim3(g1(n)), dim3(256), 0, st, n, c->dof_i2e.p, c->tmp_i.p, gcol.p);
-        }
-        c->defer_end_sync = true;   // (the step's outcome is read inside solve_run; what follows it is ordered by the stream)
-        const int open_step = !(!opt || opt->method == FDAPDE_SOLVER_AUTO) ? -1 : ((opt && opt->maxit > 0) ? 0 : default_maxit(c, n));
-        int rc = solve_run_restarting(c, ss, kmat.p, rhs.p, gcol.p, uprev.p, step_method, rtol, maxit, check_every, 0, open_step);
-        bool cg_broke = rc == FDAPDE_ENOCONV && c->h_ctl[2] != 0 && step_method == FDAPDE_SOLVER_AUTO && is_cg_method(c->info.method_used);
-        if ((ss.dist || ss.rowdist) && step_method == FDAPDE_SOLVER_AUTO && (rc == FDAPDE_OK || rc == FDAPDE_ENOCONV)) {   // (the ranks decide together: see fdapde_solve)
-            int yes = 0;
-            if (int rc2 = ranks_saying_yes(c, cg_broke, &yes)) return rc2;
-            if (yes != 0 && yes != c->world) return fail(c, FDAPDE_ERCCL, "fdapde_solve_parabolic: the ranks disagree on the outcome of the CG stage");
-            cg_broke = yes == c->world;
-        }
+    const int open_step = open_gmres_budget(c, opt, n);
+    auto krylov_step = [&](int32_t, const double* rhs_i, const double* g_i, const double* u_i) -> int {
+        c->defer_end_sync = true;
+        int rc = solve_run_restarting(c, ss, kmat.p, rhs_i, g_i, u_i, step_method, rtol, maxit, check_every, 0, open_step);
+        bool cg_broke = false;
+        if (int rc2 = cg_breakdown_agreed(c, ss, rc, step_method == FDAPDE_SOLVER_AUTO,
+                                          "fdapde_solve_parabolic: the ranks disagree on the outcome of the CG stage", &cg_broke))
+            return rc2;
         if (cg_broke) {   // M / dt + A symmetric but not positive definite (see fdapde_solve): this step again and every later one with BiCGStab
-            if (int rc2 = solve_prepare(c, kmat.p, dirichlet ? 1 : 0, &ss, false)) return rc2;
+            if (int rc2 = solve_prepare(c, kmat.p, use_bnd, &ss, false)) return rc2;
             step_method = FDAPDE_SOLVER_BICGSTAB;
-            rc = solve_run_restarting(c, ss, kmat.p, rhs.p, gcol.p, uprev.p, step_method, rtol, maxit, check_every, 0, open_step);
+            rc = solve_run_restarting(c, ss, kmat.p, rhs_i, g_i, u_i, step_method, rtol, maxit, check_every, 0, open_step);
         }
         c->defer_end_sync = false;
-        if (rc != FDAPDE_OK && rc != FDAPDE_ENOCONV) return rc;
-        if (rc == FDAPDE_ENOCONV) rc_all = rc;
-        total_iters += c->info.iters;
-        worst = c->info.relres > worst ? c->info.relres : worst;
-        if (ss.rowdist)   // u_{i+1} of the columns other ranks own: read by the next step's M u_i and warm start
+        if ((rc == FDAPDE_OK || rc == FDAPDE_ENOCONV) && ss.rowdist)   // u_{i+1} of the columns other ranks own: read by the next step's M u_i and warm start
             if (int rc2 = rowdist_import_ghosts(c, ss.use_bnd ? 1 : 0, c->u.p)) return rc2;
-        HIPCHK(c, hipMemcpyAsync(uprev.p, c->u.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL(k_scatter_f64, dim3(g1(n)), dim3(256), 0, st, n, c->dof_i2e.p, c->u.p, c->tmp_e.p);
-        HIPCHK(c, hipMemcpyAsync(solution + (size_t)(i + 1) * n, c->tmp_e.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
-    }
-    HIPCHK(c, hipEventRecord(c->ev1, st));
-    HIPCHK(c, hipEventSynchronize(c->ev1));
-    float ms = 0;
-    HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    c->info.t_solve_ms = ms, c->info.iters = total_iters, c->info.relres = worst, c->info.converged = rc_all == FDAPDE_OK ? 1 : 0;
-    if (!opt || opt->method == FDAPDE_SOLVER_AUTO) c->open_solves += n_times - 1;
-    if (info) *info = c->info;
-    kmat.release(), uprev.release(), rhs.release(), gcol.release();
-    return rc_all;
+        return rc;
+    };
+    StepTally t;
+    if (int rc = step_loop(c, n_times, inv_dt, dirichlet, solution, rhs.p, gcol.p, uprev.p, /*wait_each_step=*/false, /*give_up_on_first=*/false, krylov_step, t)) return rc;
+    return stepper_end(c, t, -1, -1, open_method ? n_times - 1 : 0, info);
 }
 
 // Q columns of fdapde_lin_solve at once (kernels_multirhs.h): b_ext / x_ext are Q host columns of n, reference numbering
@@ -1455,12 +1509,10 @@ int lin_solve_batch(fdapde_ctx* c, const double* b_ext, double* x_ext, double rt
     // (the scalar pass behind an exhausted budget counts itself where no column has converged: iterations are what was applied to x)
     *iters = std::min<int>(c->h_ctl[1], launched), *converged = c->h_ctl[2] == 0, *relres = 0;
     for (int q = 0; q < Q; ++q) {
-        const double bb = h_sc[(size_t)q], rr = h_sc[(size_t)Q + q];
-        const double rel = bb > 0 ? sqrt(rr / bb) : 0.0;
-        *relres = rel > *relres ? rel : *relres;
-        if (!(rr <= tol2 * bb)) *converged = false;
+        const Outcome out = outcome_of(h_sc[(size_t)q], h_sc[(size_t)Q + q], c->h_ctl[2] != 0, tol2);
+        *relres = out.relres > *relres ? out.relres : *relres;
+        if (!out.converged) *converged = false;
     }
-    for (DBuf<double>* b : {&B, &X, &R, &P, &Y, &part_spmm, &part_rr, &sc}) b->release();
     return FDAPDE_OK;
 }
 
@@ -1493,14 +1545,166 @@ int e_lin_compute(fdapde_ctx* c, int32_t which, const double* values, int32_t sy
     return FDAPDE_OK;
 }
 
+// ---- the stages of fdapde_lin_solve: each takes the columns from t.j0 on that are its own and advances the tally ------------------------------
+namespace {
+
+struct ColumnTally {
+    int total = 0, rc_all = FDAPDE_OK;   // iterations of all columns; FDAPDE_ENOCONV if a column did not converge
+    double worst = 0;                    // the worst relres
+    bool breakdown = false;              // a CG column stopped on p.Ap <= 0
+    int32_t j0 = 0;                      // columns done
+};
+struct LinCall {   // one fdapde_lin_solve, as its stages see it
+    fdapde_ctx* c; const double* b; double* x; int32_t n_rhs; int64_t n;   // the context, b and x as handed over, their columns and rows
+    double rtol;
+    int maxit, check_every, method, gm_budget;
+    ColumnTally t;
+
+    // "Factor once" that pays per solve (kernels_dense.h): a small system that has been asked for more than `dense_after` columns gets its dense
+    // inverse -- built once, ~ms -- and every column from then on is ONE matrix-vector product, b and x through pinned memory.  Where the method was
+    // left open; by name (dense_named) the inverse is built now, whatever the columns so far have cost.  *done: the call is answered (rc its answer)
+    int dense_stage(bool dense_named, fdapde_info* info, bool* done) {
+        fdapde_ctx::Dense& D = c->lin_dense;
+        *done = false;
+        if (!D.ready && (!D.failed || dense_named) && (dense_named || c->dense_after == 0 || (c->lin_cols + n_rhs > c->dense_after && c->lin_krylov_ms >= 0.5 * dense_build_estimate_ms(n))))
+            if (int rc = dense_build(c, c->lin_mat.p, 0, D)) return rc;
+        if (!D.ready && !dense_named) return FDAPDE_OK;
+        *done = true;
+        if (!D.ready) return c->err = dense_singular("the matrix"), bare_answer(c, FDAPDE_SOLVER_DENSE, D.check, info, FDAPDE_ENOCONV);
+        const auto t0 = std::chrono::steady_clock::now();
+        if (int rc = dense_solve_host(c, D, b, n_rhs, x)) return rc;
+        c->lin_cols += n_rhs;
+        c->info.iters = D.refine ? 1 : 0, c->info.converged = 1, c->info.relres = D.check, c->info.method_used = FDAPDE_SOLVER_DENSE, c->info.persistent = 0;
+        c->info.launch_ms = 0, c->info.spmv_avg_ms = 0, c->info.spmv_timed = 0;
+        c->info.t_solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if (info) *info = c->info;
+        return FDAPDE_OK;
+    }
+
+    // several columns against a symmetric positive system on one GPU: batches of 8 / 4 columns share every pass over the matrix (kernels_multirhs.h);
+    // what is left goes column by column (pairs are faster that way: C3-size system, 77 ms against 92 ms batched)
+    int batches() {
+        if (!c->lin_sq_ready) {   // full-pattern scaled copy (explicit unit diagonal), once per prepared matrix
+            HIPCHK(c, c->lin_sq.alloc((size_t)c->hs.nnz + 2));
+            hipLaunchKernelGGL(k_scale_matrix, dim3(g1(n * 16)), dim3(256), 0, c->stream, n, c->rowptr.p, c->colidx.p, c->lin_mat.p, c->scale.p, c->lin_sq.p);
+            c->lin_sq_ready = true;
+        }
+        while (n_rhs - t.j0 >= 4) {
+            const int q = n_rhs - t.j0 >= 8 ? 8 : 4;
+            int its = 0;
+            double rel = 0;
+            bool ok = true;
+            const double* bq = b + (size_t)t.j0 * n;
+            double* xq = x + (size_t)t.j0 * n;
+            const int rc = q == 8 ? lin_solve_batch<8>(c, bq, xq, rtol, maxit, check_every, &its, &rel, &ok) : lin_solve_batch<4>(c, bq, xq, rtol, maxit, check_every, &its, &rel, &ok);
+            if (rc != FDAPDE_OK) return rc;
+            if (!ok) t.rc_all = FDAPDE_ENOCONV, t.breakdown = t.breakdown || c->h_ctl[2] != 0;   // (lin_solve_batch leaves h_ctl of its last read-back)
+            t.total += its, t.worst = rel > t.worst ? rel : t.worst;
+            c->info.method_used = method;
+            t.j0 += q;
+        }
+        return FDAPDE_OK;
+    }
+
+    // ONE column against a system of one workgroup (a caller that cannot batch: 0.15 ms of wall time around a 50 us launch on the general path --
+    // upload, two small kernels, the launch, two read-backs, three waits): the launch does it all (run_persist_direct).  *done: it ran, the record is
+    // filled and the tally holds the column
+    int direct_column(fdapde_info* info, bool* done) {
+        const double tol2 = rtol * rtol;
+        *done = false;
+        if (int rc = run_persist_direct(c, 0, tol2, maxit, b, x, done)) return rc;
+        if (!*done) return FDAPDE_OK;
+        const Outcome out = outcome_from(c->h_sc, c->h_ctl, tol2);
+        c->info.iters = c->h_ctl[1], c->info.relres = out.relres, c->info.converged = out.converged;
+        c->info.method_used = method, c->info.persistent = 1, c->info.launch_ms = 0.0, c->info.t_solve_ms = 0.0;
+        c->info.spmv_avg_ms = 0, c->info.spmv_timed = 0;
+        if (info) *info = c->info;
+        t.total = c->info.iters, t.worst = out.relres, t.breakdown = c->h_ctl[2] != 0, t.rc_all = out.converged ? FDAPDE_OK : FDAPDE_ENOCONV, t.j0 = 1;
+        return FDAPDE_OK;
+    }
+
+    // several columns against a system the single-launch solver holds in few workgroups (the small systems the reference's users solve by the
+    // thousand: one or two of 256 CUs busy per solve): Q columns side by side in ONE launch of G x Q workgroups, each column with boards of
+    // its own; the same arithmetic per column as one by one, hence the same bits.  (A single column too: three small launches around the solve
+    // instead of seven.)  Columns it leaves -- more workgroups than fit after all, a launch that gave up, a BiCGStab column that broke down (this
+    // batch and what follows: solve_run_restarting restarts them) -- go one by one
+    int columns_side_by_side(bool cols_bicg) {
+        hipStream_t st = c->stream;
+        fdapde_ctx::Persist& ps = c->ps[0];
+        const int G = ps.meta.G;
+        const int cap = (ps.per_cu > 0 ? ps.per_cu : 1) * c->n_cu / (G > 0 ? G : 1);   // columns whose workgroups are resident together
+        const double tol2 = rtol * rtol;
+        const int np = c->vec_grid;
+        while (n_rhs - t.j0 >= 1 && cap >= 1) {
+            const int Q = std::min(std::min<int>(n_rhs - t.j0, cap), 64);
+            const size_t qn = (size_t)Q * (size_t)n;
+            HIPCHK(c, c->cols_b.alloc(qn));
+            HIPCHK(c, c->cols_r.alloc(qn));
+            HIPCHK(c, c->cols_x.alloc(qn));
+            HIPCHK(c, c->cols_sc.alloc(4 * (size_t)Q));
+            HIPCHK(c, c->cols_ctl.alloc(4 * (size_t)Q));
+            HIPCHK(c, c->cols_part.alloc(2 * (size_t)np * Q));
+            HIPCHK(c, hipMemcpyAsync(c->cols_b.p, b + (size_t)t.j0 * n, sizeof(double) * qn, hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(k_cols_init, dim3(np, Q), dim3(256), 0, st, n, c->cols_b.p, c->dof_i2e.p, c->scale.p, c->cols_r.p, c->cols_part.p);
+            hipLaunchKernelGGL(k_cols_init_fin, dim3(Q), dim3(256), 0, st, c->cols_part.p, np, c->cols_sc.p, c->cols_ctl.p);
+            HIPCHK(c, hipGetLastError());
+            std::vector<int32_t> h_ctl(4 * (size_t)Q);
+            std::vector<double> h_sc(4 * (size_t)Q);
+            bool ran = false;
+            if (int rc = run_persist_cols(c, 0, tol2, maxit, Q, c->cols_r.p, c->cols_x.p, c->cols_sc.p, c->cols_ctl.p, h_ctl.data(), h_sc.data(), &ran, cols_bicg))
+                return rc;
+            if (!ran) break;
+            if (cols_bicg && c->bicg_restart) {
+                bool broke = false;
+                for (int k = 0; k < Q; ++k) broke = broke || h_ctl[4 * (size_t)k + 2] != 0;
+                if (broke) break;
+            }
+            hipLaunchKernelGGL(k_cols_finish, dim3(g1(n), Q), dim3(256), 0, st, n, c->cols_x.p, c->scale.p, c->dof_i2e.p, c->cols_b.p);
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipMemcpyAsync(x + (size_t)t.j0 * n, c->cols_b.p, sizeof(double) * qn, hipMemcpyDeviceToHost, st));
+            for (int k = 0; k < Q; ++k) {
+                const Outcome out = outcome_from(&h_sc[4 * (size_t)k], &h_ctl[4 * (size_t)k], tol2);
+                if (!out.converged) t.rc_all = FDAPDE_ENOCONV;
+                t.breakdown = t.breakdown || h_ctl[4 * (size_t)k + 2] != 0;
+                t.total += h_ctl[4 * (size_t)k + 1], t.worst = out.relres > t.worst ? out.relres : t.worst;
+            }
+            c->info.method_used = method, c->info.persistent = 1, c->info.launch_ms = c->persist_launch_ms;
+            t.j0 += Q;
+        }
+        return FDAPDE_OK;
+    }
+
+    // column by column through the Krylov stages (solve_run_restarting): upload + gather, the solve, scatter + download, all on the one stream
+    int columns_one_by_one(DebugClock& clk) {
+        hipStream_t st = c->stream;
+        for (int32_t j = t.j0; j < n_rhs; ++j) {
+            HIPCHK(c, hipMemcpyAsync(c->tmp_e.p, b + (size_t)j * n, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(k_gather_f64, dim3(g1(n)), dim3(256), 0, st, n, c->dof_i2e.p, c->tmp_e.p, c->lin_rhs.p);
+            clk.mark("lin_solve: upload + gather issued");
+            c->defer_end_sync = true;
+            const int rc = solve_run_restarting(c, c->lin_state->ss, c->lin_mat.p, c->lin_rhs.p, c->g.p, nullptr, method, rtol, maxit, check_every, 0, gm_budget);
+            c->defer_end_sync = false;
+            clk.mark("lin_solve: solve_run");
+            if (rc != FDAPDE_OK && rc != FDAPDE_ENOCONV) return rc;
+            if (rc == FDAPDE_ENOCONV) t.rc_all = rc, t.breakdown = t.breakdown || (c->h_ctl[2] != 0 && is_cg_method(c->info.method_used));
+            t.total += c->info.iters, t.worst = c->info.relres > t.worst ? c->info.relres : t.worst;
+            hipLaunchKernelGGL(k_scatter_f64, dim3(g1(n)), dim3(256), 0, st, n, c->dof_i2e.p, c->u.p, c->tmp_e.p);
+            HIPCHK(c, hipMemcpyAsync(x + (size_t)j * n, c->tmp_e.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
+            clk.mark("lin_solve: solution download issued");
+        }
+        return FDAPDE_OK;
+    }
+};
+
+}   // namespace
+
 // fdapde::SparseLU::solve(b) (fdaPDE/utils/symbols.h:148-155), dense right-hand sides: b, x column-major n_dofs x n_rhs
 int e_lin_solve(fdapde_ctx* c, const fdapde_options* opt, const double* b, int32_t n_rhs, double* x, fdapde_info* info) {
     if (!c || !b || !x || n_rhs < 1) return FDAPDE_EINVAL;
     if (int rc = need_device(c)) return rc;
     if (!c->lin_ready) return fail(c, FDAPDE_ENOTINIT, "call fdapde_lin_compute first");
     HIPCHK(c, hipSetDevice(c->device));
-    const HostSpace& hs = c->hs;
-    const int64_t n = hs.n_dofs;
+    const int64_t n = c->hs.n_dofs;
     {   // in-place solves (x overlapping b: Eigen's x = lu.solve(x) idiom): finished columns are written to x while later columns and a
         // BiCGStab retry still read b -- work from a private copy of the right-hand sides
         const double *b0 = b, *b1 = b + (size_t)n * n_rhs, *x0 = x, *x1 = x + (size_t)n * n_rhs;
@@ -1510,41 +1714,21 @@ int e_lin_solve(fdapde_ctx* c, const fdapde_options* opt, const double* b, int32
         }
     }
     if (opt && opt->method == FDAPDE_SOLVER_AMG) return amg_lin_solve(c, opt, b, n_rhs, x, info);   // (eng_amg.hip; after the in-place copy above)
-    hipStream_t st = c->stream;
-    const double rtol = (opt && opt->rtol > 0) ? opt->rtol : 1e-10;
-    const int maxit = (opt && opt->maxit > 0) ? opt->maxit : default_maxit(c, n);
-    const int check_every = (opt && opt->check_every > 0) ? opt->check_every : 32;
-    int method = opt ? opt->method : FDAPDE_SOLVER_AUTO;
-    if (method == FDAPDE_SOLVER_AUTO)
-        method = (c->lin_symmetric && c->lin_state->ss.diag_positive) ? FDAPDE_SOLVER_CG_FUSED : FDAPDE_SOLVER_BICGSTAB;
-    // "Factor once" that pays per solve (kernels_dense.h): a small system that has been asked for more than `dense_after` columns gets its dense
-    // inverse -- built once, ~ms -- and every column from then on is ONE matrix-vector product, b and x through pinned memory.  Where the method was
-    // left open; a method named explicitly runs as named.
-    const bool dense_named = opt && opt->method == FDAPDE_SOLVER_DENSE;   // asked for by name: the inverse is built now, whatever the columns so far have cost
-    if (dense_named && !dense_eligible(c))
-        return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_DENSE takes one-GPU systems of up to `dense_rows` (at most 8192) DOFs");
-    if ((!opt || opt->method == FDAPDE_SOLVER_AUTO || dense_named) && dense_eligible(c)) {
-        fdapde_ctx::Dense& D = c->lin_dense;
-        if (!D.ready && (!D.failed || dense_named) &&
-            (dense_named || c->dense_after == 0 || (c->lin_cols + n_rhs > c->dense_after && c->lin_krylov_ms >= 0.5 * dense_build_estimate_ms(n))))
-            if (int rc = dense_build(c, c->lin_mat.p, 0, D)) return rc;
-        if (dense_named && !D.ready) {
-            c->info = fdapde_info{};
-            c->info.method_used = FDAPDE_SOLVER_DENSE, c->info.relres = D.check;
-            if (info) *info = c->info;
-            c->err = "FDAPDE_SOLVER_DENSE: the matrix is singular to working precision (no usable pivot, or max |I - A X| beyond 1e-6)";
-            return FDAPDE_ENOCONV;
-        }
-        if (D.ready) {
-            const auto t0 = std::chrono::steady_clock::now();
-            if (int rc = dense_solve_host(c, D, b, n_rhs, x)) return rc;
-            c->lin_cols += n_rhs;
-            c->info.iters = D.refine ? 1 : 0, c->info.converged = 1, c->info.relres = D.check, c->info.method_used = FDAPDE_SOLVER_DENSE, c->info.persistent = 0;
-            c->info.launch_ms = 0, c->info.spmv_avg_ms = 0, c->info.spmv_timed = 0;
-            c->info.t_solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            if (info) *info = c->info;
-            return FDAPDE_OK;
-        }
+    const SolveState& ss = c->lin_state->ss;
+    const bool open_method = !opt || opt->method == FDAPDE_SOLVER_AUTO;
+    LinCall L{c, b, x, n_rhs, n};   // (the rest below; the tally starts at zero)
+    L.rtol = (opt && opt->rtol > 0) ? opt->rtol : 1e-10;
+    L.maxit = (opt && opt->maxit > 0) ? opt->maxit : default_maxit(c, n);
+    L.check_every = (opt && opt->check_every > 0) ? opt->check_every : 32;
+    L.gm_budget = open_gmres_budget(c, opt, n);
+    L.method = opt ? opt->method : FDAPDE_SOLVER_AUTO;
+    if (L.method == FDAPDE_SOLVER_AUTO) L.method = (c->lin_symmetric && ss.diag_positive) ? FDAPDE_SOLVER_CG_FUSED : FDAPDE_SOLVER_BICGSTAB;
+    const bool dense_named = opt && opt->method == FDAPDE_SOLVER_DENSE;
+    if (dense_named && !dense_eligible(c)) return fail(c, FDAPDE_EUNSUPPORTED, kDenseRefusal);
+    if ((open_method || dense_named) && dense_eligible(c)) {
+        bool done = false;
+        const int rc = L.dense_stage(dense_named, info, &done);
+        if (rc || done) return rc;
     }
     c->lin_cols += n_rhs;
     struct KrylovClock {   // host time of this call's Krylov columns, towards the handle's rent-or-buy decision
@@ -1558,156 +1742,56 @@ int e_lin_solve(fdapde_ctx* c, const fdapde_options* opt, const double* b, int32
         c->scaled_owner = fdapde_ctx::kScaledLin;
     }
     c->solved = false;   // c->u is about to hold the handle's solutions, not PDE::solution()
-    DBuf<double>& rhs = c->lin_rhs;
-    HIPCHK(c, rhs.alloc((size_t)n));
+    HIPCHK(c, c->lin_rhs.alloc((size_t)n));
     DebugClock clk;
-    HIPCHK(c, hipEventRecord(c->ev0, st));
-    int total = 0, rc_all = FDAPDE_OK;
-    double worst = 0;
-    int32_t j0 = 0;
-    bool breakdown = false;   // a CG column stopped on p.Ap <= 0
+    HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+    ColumnTally& t = L.t;
     // the handle was told "symmetric" and CG broke down: the matrix is not positive definite (3-D P2 mass matrices are not: negative quadrature
     // weight).  The reference's SparseLU does not care (utils/symbols.h:133-160): prepare the plain storage and solve every column with BiCGStab.
     auto retry_as_bicgstab = [&]() -> int {
         c->lin_symmetric = false, c->scaled_owner = fdapde_ctx::kScaledNone;
         if (int rc = solve_prepare(c, c->lin_mat.p, 0, &c->lin_state->ss, false)) return rc;
         c->scaled_owner = fdapde_ctx::kScaledLin, c->lin_sq_ready = false;
-        const int spent = total;   // the CG iterations before the breakdown count
-        c->lin_cols -= n_rhs;      // (the same columns again: counted once)
+        const int spent = t.total;   // the CG iterations before the breakdown count
+        c->lin_cols -= n_rhs;        // (the same columns again: counted once)
         const int rc = e_lin_solve(c, opt, b, n_rhs, x, info);
         c->info.iters += spent;
         if (info) info->iters = c->info.iters;
         return rc;
     };
-    const bool may_retry = c->lin_symmetric && (!opt || opt->method == FDAPDE_SOLVER_AUTO) && method == FDAPDE_SOLVER_CG_FUSED &&
-                           !c->lin_state->ss.dist && !c->lin_state->ss.rowdist;
-    // several columns against a symmetric positive system on one GPU: batches of 8 / 4 columns share every pass over the
-    // matrix (kernels_multirhs.h); what is left goes column by column
+    const bool one_gpu = !ss.dist && !ss.rowdist;
+    const bool cgf = L.method == FDAPDE_SOLVER_CG_FUSED;
+    const bool may_retry = c->lin_symmetric && open_method && cgf && one_gpu;
     // (a system the persistent CG takes is faster column by column -- one launch each, no vector traffic -- than batched through
     // the multi-launch SpMM: C3-size, 22.5 ms per column against 32 ms per column in a batch of 8)
     const bool persist_cols = c->persist && !c->persist_broken && c->ps[0].ok && c->ps[0].filled && c->ps[0].meta.R <= kPersistRmax;   // (the wide form: one column)
-    const bool batched = c->multi_rhs && n_rhs >= 4 && method == FDAPDE_SOLVER_CG_FUSED && !c->lin_state->ss.dist && !c->lin_state->ss.rowdist && !persist_cols;
-    if (batched) {
-        if (!c->lin_sq_ready) {   // full-pattern scaled copy (explicit unit diagonal), once per prepared matrix
-            HIPCHK(c, c->lin_sq.alloc((size_t)hs.nnz + 2));
-            hipLaunchKernelGGL(k_scale_matrix, dim3(g1(n * 16)), dim3(256), 0, st, n, c->rowptr.p, c->colidx.p, c->lin_mat.p, c->scale.p,
-                               c->lin_sq.p);
-            c->lin_sq_ready = true;
-        }
-        while (n_rhs - j0 >= 4) {   // pairs are faster column by column (C3-size system: 77 ms against 92 ms batched)
-            const int q = n_rhs - j0 >= 8 ? 8 : 4;
-            int its = 0, rc = FDAPDE_OK;
-            double rel = 0;
-            bool ok = true;
-            if (q == 8) rc = lin_solve_batch<8>(c, b + (size_t)j0 * n, x + (size_t)j0 * n, rtol, maxit, check_every, &its, &rel, &ok);
-            else rc = lin_solve_batch<4>(c, b + (size_t)j0 * n, x + (size_t)j0 * n, rtol, maxit, check_every, &its, &rel, &ok);
-            if (rc != FDAPDE_OK) return rc;
-            if (!ok) rc_all = FDAPDE_ENOCONV, breakdown = breakdown || c->h_ctl[2] != 0;   // (lin_solve_batch leaves h_ctl of its last read-back)
-            total += its, worst = rel > worst ? rel : worst;
-            c->info.method_used = method;
-            j0 += q;
+    if (c->multi_rhs && n_rhs >= 4 && cgf && one_gpu && !persist_cols)
+        if (int rc = L.batches()) return rc;
+    const bool side_by_side = persist_cols && c->persist_cols && one_gpu && !ss.use_bnd;
+    if (n_rhs == 1 && side_by_side && c->persist_direct && cgf && c->ps[0].meta.G == 1) {
+        bool done = false;
+        if (int rc = L.direct_column(info, &done)) return rc;
+        if (done) {
+            if (t.rc_all == FDAPDE_OK) return FDAPDE_OK;
+            if (t.breakdown && may_retry) return retry_as_bicgstab();
+            c->err = t.breakdown ? "Krylov breakdown (operator not SPD for CG)" : "maxit reached";
+            return FDAPDE_ENOCONV;
         }
     }
-    // several columns against a system the single-launch CG holds in few workgroups (the small systems the reference's users solve by the
-    // thousand: one or two of 256 CUs busy per solve): Q columns side by side in ONE launch of G x Q workgroups, each column with boards of
-    // its own; the same arithmetic per column as one by one, hence the same bits
-    // ONE column against a system of one workgroup (a caller that cannot batch: 0.15 ms of wall time around a 50 us launch on the general
-    // path -- upload, two small kernels, the launch, two read-backs, three waits): the launch does it all (run_persist_direct)
-    if (n_rhs == 1 && persist_cols && c->persist_cols && c->persist_direct && method == FDAPDE_SOLVER_CG_FUSED && !c->lin_state->ss.dist &&
-        !c->lin_state->ss.rowdist && !c->lin_state->ss.use_bnd && c->ps[0].meta.G == 1) {
-        bool ran = false;
-        const double tol2 = rtol * rtol;
-        if (int rc = run_persist_direct(c, 0, tol2, maxit, b, x, &ran)) return rc;
-        if (ran) {
-            const double bb = c->h_sc[0], rr = c->h_sc[3];
-            c->info.iters = c->h_ctl[1], c->info.relres = bb > 0 ? sqrt(rr / bb) : 0.0;
-            c->info.converged = (rr <= tol2 * bb && c->h_ctl[2] == 0) ? 1 : 0;
-            c->info.method_used = method, c->info.persistent = 1, c->info.launch_ms = 0.0, c->info.t_solve_ms = 0.0;
-            c->info.spmv_avg_ms = 0, c->info.spmv_timed = 0;
-            if (info) *info = c->info;
-            if (!c->info.converged) {
-                if (c->h_ctl[2] && may_retry) {
-                    total = c->info.iters;
-                    return retry_as_bicgstab();
-                }
-                c->err = c->h_ctl[2] ? "Krylov breakdown (operator not SPD for CG)" : "maxit reached";
-                return FDAPDE_ENOCONV;
-            }
-            return FDAPDE_OK;
-        }
-    }
-    const bool cols_bicg = method == FDAPDE_SOLVER_BICGSTAB && c->persist_bicg && !c->ps[0].meta.sym && c->ps[0].meta.R <= 8;   // (the single-launch BiCGStab's own limits)
-    if (persist_cols && c->persist_cols && (method == FDAPDE_SOLVER_CG_FUSED || cols_bicg) && !c->lin_state->ss.dist && !c->lin_state->ss.rowdist &&
-        !c->lin_state->ss.use_bnd) {
-        fdapde_ctx::Persist& ps = c->ps[0];
-        const int G = ps.meta.G;
-        const int cap = (ps.per_cu > 0 ? ps.per_cu : 1) * c->n_cu / (G > 0 ? G : 1);   // columns whose workgroups are resident together
-        const double tol2 = rtol * rtol;
-        const int np = c->vec_grid;
-        while (n_rhs - j0 >= 1 && cap >= 1) {   // (a single column too: three small launches around the solve instead of seven)
-            const int Q = std::min(std::min<int>(n_rhs - j0, cap), 64);
-            const size_t qn = (size_t)Q * (size_t)n;
-            HIPCHK(c, c->cols_b.alloc(qn));
-            HIPCHK(c, c->cols_r.alloc(qn));
-            HIPCHK(c, c->cols_x.alloc(qn));
-            HIPCHK(c, c->cols_sc.alloc(4 * (size_t)Q));
-            HIPCHK(c, c->cols_ctl.alloc(4 * (size_t)Q));
-            HIPCHK(c, c->cols_part.alloc(2 * (size_t)np * Q));
-            HIPCHK(c, hipMemcpyAsync(c->cols_b.p, b + (size_t)j0 * n, sizeof(double) * qn, hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(k_cols_init, dim3(np, Q), dim3(256), 0, st, n, c->cols_b.p, c->dof_i2e.p, c->scale.p, c->cols_r.p, c->cols_part.p);
-            hipLaunchKernelGGL(k_cols_init_fin, dim3(Q), dim3(256), 0, st, c->cols_part.p, np, c->cols_sc.p, c->cols_ctl.p);
-            HIPCHK(c, hipGetLastError());
-            std::vector<int32_t> h_ctl(4 * (size_t)Q);
-            std::vector<double> h_sc(4 * (size_t)Q);
-            bool ran = false;
-            if (int rc = run_persist_cols(c, 0, tol2, maxit, Q, c->cols_r.p, c->cols_x.p, c->cols_sc.p, c->cols_ctl.p, h_ctl.data(), h_sc.data(), &ran, cols_bicg))
-                return rc;
-            if (!ran) break;   // (more workgroups than fit after all, or a launch that gave up: these columns go one by one below)
-            if (cols_bicg && c->bicg_restart) {   // a BiCGStab column that broke down: this batch and what follows one by one (solve_run_restarting)
-                bool broke = false;
-                for (int k = 0; k < Q; ++k) broke = broke || h_ctl[4 * (size_t)k + 2] != 0;
-                if (broke) break;
-            }
-            hipLaunchKernelGGL(k_cols_finish, dim3(g1(n), Q), dim3(256), 0, st, n, c->cols_x.p, c->scale.p, c->dof_i2e.p, c->cols_b.p);
-            HIPCHK(c, hipGetLastError());
-            HIPCHK(c, hipMemcpyAsync(x + (size_t)j0 * n, c->cols_b.p, sizeof(double) * qn, hipMemcpyDeviceToHost, st));
-            for (int k = 0; k < Q; ++k) {
-                const double bb = h_sc[4 * (size_t)k], rr = h_sc[4 * (size_t)k + 3];
-                const double rel = bb > 0 ? sqrt(rr / bb) : 0.0;
-                if (!(rr <= tol2 * bb && h_ctl[4 * (size_t)k + 2] == 0)) rc_all = FDAPDE_ENOCONV;
-                breakdown = breakdown || h_ctl[4 * (size_t)k + 2] != 0;
-                total += h_ctl[4 * (size_t)k + 1], worst = rel > worst ? rel : worst;
-            }
-            c->info.method_used = method, c->info.persistent = 1, c->info.launch_ms = c->persist_launch_ms;
-            j0 += Q;
-        }
-    }
-    for (int32_t j = j0; j < n_rhs; ++j) {
-        HIPCHK(c, hipMemcpyAsync(c->tmp_e.p, b + (size_t)j * n, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_gather_f64, dim3(g1(n)), dim3(256), 0, st, n, c->dof_i2e.p, c->tmp_e.p, rhs.p);
-        clk.mark("lin_solve: upload + gather issued");
-        c->defer_end_sync = true;
-        const int rc = solve_run_restarting(c, c->lin_state->ss, c->lin_mat.p, rhs.p, c->g.p, nullptr, method, rtol, maxit, check_every, 0,
-                                            !(!opt || opt->method == FDAPDE_SOLVER_AUTO) ? -1 : ((opt && opt->maxit > 0) ? 0 : default_maxit(c, n)));
-        c->defer_end_sync = false;
-        clk.mark("lin_solve: solve_run");
-        if (rc != FDAPDE_OK && rc != FDAPDE_ENOCONV) return rc;
-        if (rc == FDAPDE_ENOCONV) rc_all = rc, breakdown = breakdown || (c->h_ctl[2] != 0 && is_cg_method(c->info.method_used));
-        total += c->info.iters, worst = c->info.relres > worst ? c->info.relres : worst;
-        hipLaunchKernelGGL(k_scatter_f64, dim3(g1(n)), dim3(256), 0, st, n, c->dof_i2e.p, c->u.p, c->tmp_e.p);
-        HIPCHK(c, hipMemcpyAsync(x + (size_t)j * n, c->tmp_e.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
-        clk.mark("lin_solve: solution download issued");
-    }
-    HIPCHK(c, hipEventRecord(c->ev1, st));
+    const bool cols_bicg = L.method == FDAPDE_SOLVER_BICGSTAB && c->persist_bicg && !c->ps[0].meta.sym && c->ps[0].meta.R <= 8;   // (the single-launch BiCGStab's own limits)
+    if (side_by_side && (cgf || cols_bicg))
+        if (int rc = L.columns_side_by_side(cols_bicg)) return rc;
+    if (int rc = L.columns_one_by_one(clk)) return rc;
+    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
     HIPCHK(c, hipEventSynchronize(c->ev1));
-    if (rc_all == FDAPDE_ENOCONV && breakdown && may_retry) return retry_as_bicgstab();
+    if (t.rc_all == FDAPDE_ENOCONV && t.breakdown && may_retry) return retry_as_bicgstab();
     float ms = 0;
     HIPCHK(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    c->info.t_solve_ms = ms, c->info.iters = total, c->info.relres = worst, c->info.converged = rc_all == FDAPDE_OK ? 1 : 0;
-    if (rc_all == FDAPDE_ENOCONV)
-        c->err = breakdown ? "Krylov breakdown in at least one column (matrix not positive definite for CG, or BiCGStab rho / omega = 0)" : "maxit reached in at least one column";
+    c->info.t_solve_ms = ms, c->info.iters = t.total, c->info.relres = t.worst, c->info.converged = t.rc_all == FDAPDE_OK ? 1 : 0;
+    if (t.rc_all == FDAPDE_ENOCONV)
+        c->err = t.breakdown ? "Krylov breakdown in at least one column (matrix not positive definite for CG, or BiCGStab rho / omega = 0)" : "maxit reached in at least one column";
     if (info) *info = c->info;
-    return rc_all;
+    return t.rc_all;
 }
 
 int e_matrix_values(fdapde_ctx* c, int32_t which, double* values) {

@@ -615,7 +615,7 @@ int fdapde_partition_peers(fdapde_ctx *ctx, int32_t rank, int32_t *n_peers, int3
  *                 "solve_reuse" (1, the default: fdapde_solve keeps the Jacobi-scaled system and the filled layout across solves of an unchanged matrix;
  *                 0: every fdapde_solve prepares in full.  Any fdapde_tune call makes the next fdapde_solve prepare in full once)
  *   measurement   knobs kept for the A/B figures of DESIGN.md: "asm_row_stat" (0: the solve's Jacobi scaling reads the whole matrix instead of the (diagonal, row maximum)
- *                 pairs fdapde_init leaves), "bicg_shadow" (shadow residual of the multi-launch BiCGStab: 0 = r0, 1 = pseudo-random, 2 = r0 with randomly scaled entries),
+ *                 pairs fdapde_init leaves),
  *                 "persist_bicg" (0: non-symmetric systems always take the multi-launch BiCGStab), "persist_fill_fused" (1: the single launch's blocks filled straight from
  *                 the unscaled matrix), "persist_late" (CG layouts with late-import workgroups instead of doubled rows per thread), "persist_gather_waves" /
  *                 "persist_poll_sleep" (the dot all-gather of the single launch), "persist_wide_gj" (passes of a phase of the wide form that load together: 4 / 6 / 12),
