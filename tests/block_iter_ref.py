@@ -8,7 +8,8 @@ correction / 0.7 D^-1, the two GCR steps below the finest level in k_amg_coef's 
 UNSCALED system, restarted from the true residual.  With the aggregates fixed, iterate k of that scheme is ONE vector in exact arithmetic: the order of
 the sums, the team width of a kernel, the form of the last level's solve and the orthogonalisation variant do not change it.
 
-The handle's GMRES stage (block_gmres in csrc/eng_block.hip): GMRES(m) on D^-1 A z = D^-1 b with D^-1 formed here, in np.longdouble.
+The handle's GMRES stage (block_gmres in csrc/eng_block.hip): GMRES(m) on D^-1 A z = D^-1 b with D^-1 formed here, in np.longdouble; with a factored data
+term live (fdapde_block_set_obs) A and D are the full matrix's, the term applied as its two rectangular products (ObsTerm, GMRES_OBS_CASES).
 
 Vectors are handed in and out STACKED in the caller's numbering (f = the first block row's n entries, then g), as fdapde_block_solve takes them.
 
@@ -160,7 +161,19 @@ class Hierarchy:
     def __init__(self, rp, ci, blocks, n, aggregates, dt=LD, like_device=False):
         self.dt, self.like_device = dt, like_device
         bv = np.stack([np.zeros(len(ci)) if b is None else np.asarray(b, dtype=float) for b in blocks], axis=1)
-        self.A = [BlockCsr(rp, ci, bv, dt)]
+        self._levels(BlockCsr(rp, ci, bv, dt), n, aggregates)
+
+    per = 2   # unknowns per row (tests/kron_iter_ref.py: q)
+
+    def _diag_inverse(self, A):
+        return block_diag_inverse(A.diagonal_blocks(), self.dt, self.like_device)
+
+    def _galerkin(self, A, agg, nc):
+        return galerkin(A, agg, nc)
+
+    def _levels(self, A0, n, aggregates):
+        """every level from level 0's matrix and the maps row -> row of the next level"""
+        self.A = [A0]
         self.agg, self.members, self.dinv = [], [], []
         assert n == self.A[0].n
         for agg in aggregates:
@@ -171,13 +184,16 @@ class Hierarchy:
             order = np.argsort(agg, kind="stable")
             self.agg.append(agg)
             self.members.append((order, np.flatnonzero(np.concatenate([[True], np.diff(agg[order]) != 0]))))
-            self.dinv.append(block_diag_inverse(A.diagonal_blocks(), dt, like_device))
-            self.A.append(galerkin(A, agg, nc))
+            self.dinv.append(self._diag_inverse(A))
+            self.A.append(self._galerkin(A, agg, nc))
         self.rows = [A.n for A in self.A]
         self.entries = [len(A.ci) for A in self.A]
-        last = self.A[-1].dense()
+        self._set_last(self.A[-1].dense())
+
+    def _set_last(self, last):
+        """the last level's solve from its dense matrix (interleaved order)"""
         assert last.shape[0] <= LAST_LEVEL_ROWS, last.shape
-        if like_device:   # the explicit inverse of the row-equilibrated matrix (csrc/eng_dense.hip), one refinement step where max |I - A X| asks for it
+        if self.like_device:   # the explicit inverse of the row-equilibrated matrix (csrc/eng_dense.hip), one refinement step where max |I - A X| asks for it
             rs = 1.0 / np.abs(last).max(axis=1)
             self.last, self.X = last, np.linalg.inv(rs[:, None] * last) * rs[None, :]
             self.refine = not np.abs(np.eye(len(rs)) - last @ self.X).max() < 1e-13
@@ -192,18 +208,22 @@ class Hierarchy:
 
     def restrict(self, l, r):
         order, starts = self.members[l]
-        return _segment_sums(r.reshape(-1, 2), order, starts).reshape(-1)
+        return _segment_sums(r.reshape(-1, self.per), order, starts).reshape(-1)
 
     def prolong(self, l, e):
-        return e.reshape(-1, 2)[self.agg[l]].reshape(-1)
+        return e.reshape(-1, self.per)[self.agg[l]].reshape(-1)
+
+    def smooth(self, l, r):
+        """D^-1 r of level l"""
+        return _dinv_apply(self.dinv[l], r)
 
     def cycle(self, l, r):
         """block_amg_ref.Hierarchy.cycle's formulas"""
-        A, dinv = self.A[l], self.dinv[l]
+        A = self.A[l]
         om = self.dt(OMEGA)
-        zt = om * _dinv_apply(dinv, r)
+        zt = om * self.smooth(l, r)
         z = zt + self.prolong(l, self.correction(l + 1, self.restrict(l, r - A.mv(zt))))
-        return z + om * _dinv_apply(dinv, r - A.mv(z))
+        return z + om * self.smooth(l, r - A.mv(z))
 
     def correction(self, m, b):
         """the last level exactly; elsewhere two GCR steps around the cycle with k_amg_coef's rules: a step that cannot be taken contributes nothing"""
@@ -293,23 +313,78 @@ def fgmres_float64(rp, ci, blocks, n, aggregates, b, K, restart=50):
     return fgmres_iterates(Hierarchy(rp, ci, blocks, n, aggregates, dt=np.float64, like_device=True), b, K, restart)
 
 
-def _gmres(rp, ci, blocks, n, b, K, restart, dt, like_device):
+def csr_product(indptr, indices, data, X):
+    """M X for a CSR matrix of ANY row length (an empty row gives 0) and X of one or two axes, the row sums by reduceat in the precision of data and X"""
+    indptr = np.asarray(indptr, dtype=np.int64)
+    terms = data * X[indices] if X.ndim == 1 else data[:, None] * X[indices]
+    out = np.zeros((len(indptr) - 1,) + X.shape[1:], dtype=terms.dtype)
+    filled = np.flatnonzero(np.diff(indptr) > 0)
+    if len(filled):
+        out[filled] = np.add.reduceat(terms, indptr[filled], axis=0)
+    return out
+
+
+class ObsTerm:
+    """the factored data term scale Psi^T W Psi of the first field (fdapde_block_set_obs), applied as its two rectangular products in dtype dt"""
+
+    def __init__(self, Psi, weights, scale, dt):
+        P = Psi.tocsr().copy()
+        P.sum_duplicates()
+        P.sort_indices()
+        T = P.T.tocsr()
+        T.sort_indices()
+        self.P = (P.indptr, P.indices, P.data.astype(dt))
+        self.T = (T.indptr, T.indices, T.data.astype(dt))
+        self.w = (np.ones(P.shape[0]) if weights is None else np.asarray(weights, dtype=float)).astype(dt)
+        self.scale, self.dt = dt(scale), dt
+
+    def apply(self, x1, absolute=False):
+        """scale Psi^T W Psi x1, or |scale| |Psi|^T |W| |Psi| |x1|"""
+        f = np.abs if absolute else (lambda v: v)
+        P, T = ((m[0], m[1], f(m[2])) for m in (self.P, self.T))
+        return f(self.scale) * csr_product(*T, f(self.w) * csr_product(*P, f(x1)))
+
+    def diagonal(self):
+        """the term's share of every DOF's diagonal entry: scale sum_k w_k Psi[k, i]^2"""
+        ip, idx, v = self.T
+        return self.scale * csr_product(ip, idx, v * v, self.w)
+
+
+def _gmres(rp, ci, blocks, n, b, K, restart, dt, like_device, obs=None):
     bv = np.stack([np.zeros(len(ci)) if v is None else np.asarray(v, dtype=float) for v in blocks], axis=1)
     A = BlockCsr(rp, ci, bv, dt)
     assert A.n == n
-    dinv = block_diag_inverse(A.diagonal_blocks(), dt, like_device)
+    diag = A.diagonal_blocks()
+    if obs is not None:   # the diagonal blocks of the full matrix: the term's share goes to a11
+        term = ObsTerm(*obs, dt)
+        diag = diag.copy()
+        diag[:, 0] += term.diagonal()
+    dinv = block_diag_inverse(diag, dt, like_device)
     At = A.left_scaled(dinv, like_device)
     bt = _dinv_apply(dinv, interleave(np.asarray(b, dtype=float)).astype(dt))
-    return _pack(_iterates(dt, At.mv, At.amv, None, bt, K, restart))
+    if obs is None:
+        return _pack(_iterates(dt, At.mv, At.amv, None, bt, K, restart))
+
+    def first_field(z):
+        return np.stack([z, np.zeros_like(z)], axis=1).reshape(-1)
+
+    def mv(x):   # (as launch_obs_term: the scaled pattern product, then D^-1 [z; 0] added)
+        return At.mv(x) + _dinv_apply(dinv, first_field(term.apply(x.reshape(-1, 2)[:, 0])))
+
+    def amv(x):
+        return At.amv(x) + _dinv_apply(np.abs(dinv), first_field(term.apply(x.reshape(-1, 2)[:, 0], absolute=True)))
+
+    return _pack(_iterates(dt, mv, amv, None, bt, K, restart))
 
 
-def gmres_iterates(rp, ci, blocks, n, b, K, restart=50):
-    """GMRES(restart) on D^-1 A z = D^-1 b, D^-1 formed in np.longdouble -> [Iterate]: x_k, s = sum_j |y_j| |v_j|, rho_k and res_scale of the SCALED system"""
-    return _gmres(rp, ci, blocks, n, b, K, restart, LD, False)
+def gmres_iterates(rp, ci, blocks, n, b, K, restart=50, obs=None):
+    """GMRES(restart) on D^-1 A z = D^-1 b, D^-1 formed in np.longdouble -> [Iterate]: x_k, s = sum_j |y_j| |v_j|, rho_k and res_scale of the SCALED system.
+    obs = (Psi, weights, scale): A and D are the full matrix's, A + scale [Psi^T W Psi, 0; 0, 0], the term applied as its two rectangular products"""
+    return _gmres(rp, ci, blocks, n, b, K, restart, LD, False, obs)
 
 
-def gmres_float64(rp, ci, blocks, n, b, K, restart=50):
-    return _gmres(rp, ci, blocks, n, b, K, restart, np.float64, True)
+def gmres_float64(rp, ci, blocks, n, b, K, restart=50, obs=None):
+    return _gmres(rp, ci, blocks, n, b, K, restart, np.float64, True, obs)
 
 
 # ---- the units of the bounds -----------------------------------------------------------------------------------------------------------------------
@@ -361,10 +436,52 @@ GMRES_CASES = {
 C_AMG = {1: 64.0, 2: 16.0, 3: 16.0, 5: 32.0, 8: 16.0}
 C_GMRES = {1: 2048.0, 2: 4096.0, 3: 256.0, 5: 128.0, 7: 32.0, 8: 64.0}
 C_MAX = 2.0 ** 12
+# the GMRES stage with a factored data term live (block_obs_ref's system: the (1,1) block is the term's alone), on the mesh, order and lambda of a system
+# of AMG_CASES: (system, design as kron_obs_ref.design_psi takes it, k).  Each runs under block_obs_team = 8 and = 64 against the same reference; a set of
+# constants of its own by the same rule
+GMRES_OBS_CASES = {
+    "a-areal": ("a", ("tiles", 2), (1, 2, 3, 5, 8)),      # 4 tiles: rows of 81 entries
+    "a-points": ("a", ("points", 400), (1, 2, 3, 5, 8)),  # rows of 3
+}
+OBS_TEAMS = (8, 64)
+C_GMRES_OBS = {1: 256.0, 2: 32.0, 3: 64.0, 5: 64.0, 8: 64.0}
 
 
 def constant_for(r_cpu):
     return float(2.0 ** np.ceil(np.log2(max(4.0 * r_cpu, 1.0))))
+
+
+# ---- the profile the CPU tests write (tests/test_block_iter_cpu.py, tests/test_kron_iter_cpu.py) -------------------------------------------------------
+def write_profile(path, header, stages, tag, lines):
+    """replace the block of lines that starts with `tag`: the header, the CPU tables in a fixed order, then whatever else the file holds (the GPU's lines)"""
+    import os
+
+    old = open(path).read().splitlines() if os.path.exists(path) else []
+    groups = {t: [ln for ln in old if ln.startswith(t)] for t in stages}
+    groups[tag] = lines
+    rest = [ln for ln in old if ln and not ln.startswith("#") and not ln.startswith(tuple(stages))]
+    new = list(header) + [ln for t in stages for ln in groups[t]] + rest
+    if new != old:   # (a run that measures what is committed leaves the file alone)
+        with open(path, "w") as fh:
+            fh.write("\n".join(new) + "\n")
+
+
+def constants_table(path, header, stages, stage, cases, measure, constants):
+    """measure(name, K) -> {k: worst ratio} for every (name, ks) of cases; writes the stage's lines and holds the committed constants to the rule"""
+    worst, lines = {}, []
+    for name, ks in cases:
+        ratios = measure(name, max(ks))
+        for k in ks:
+            worst[k] = max(worst.get(k, 0.0), ratios[k])
+        lines.append(f"cpu {stage} {name}: " + " ".join(f"{k}={ratios[k]:.3g}" for k in ks))
+    lines.append(f"cpu {stage} c(k) = 4 r_cpu(k) rounded up to a power of two: " + " ".join(f"{k}={constant_for(worst[k]):g}" for k in sorted(worst)))
+    print("\n".join(lines))
+    write_profile(path, header, stages, f"cpu {stage} ", lines)
+    assert sorted(worst) == sorted(constants)
+    for k in sorted(worst):
+        assert 4.0 * worst[k] <= constants[k], (stage, k, worst[k], constants[k])   # (r_cpu still fits c / 4)
+        assert constants[k] <= C_MAX, "a case whose checker needs more is replaced by a better-conditioned one: the constant is not raised"
+    return worst
 
 
 def interior_dof(rp, n):

@@ -65,35 +65,11 @@ HEADER = ["# k-th iterates of the 2 x 2 block handle's two Krylov stages against
           "# Units: block_amg max |x - x_ref| / (u max s) per field, gmres max_i |x - x_ref|_i / (u s_i); [relres]: |relres - rho_k| / (u || |A| s || / ||b||); u = 2^-53.",
           "# cpu lines: the float64 numpy checkers (also against relres' unit), rewritten by tests/test_block_iter_cpu.py; gpu lines: an MI355X, appended by",
           "# tests/test_gpu_block_iterates.py under FDAPDE_BLOCK_ITER_PROFILE."]
-STAGES = ("cpu block_amg ", "cpu gmres ")
-
-
-def _write_profile(tag, lines):
-    """replace the block of lines that starts with `tag`: the header, the CPU tables in a fixed order, then whatever else the file holds (the GPU's lines)"""
-    old = open(PROFILE).read().splitlines() if os.path.exists(PROFILE) else []
-    groups = {t: [ln for ln in old if ln.startswith(t)] for t in STAGES}
-    groups[tag] = lines
-    rest = [ln for ln in old if ln and not ln.startswith("#") and not ln.startswith(STAGES)]
-    new = HEADER + [ln for t in STAGES for ln in groups[t]] + rest
-    if new != old:   # (a run that measures what is committed leaves the file alone)
-        with open(PROFILE, "w") as fh:
-            fh.write("\n".join(new) + "\n")
+STAGES = ("cpu block_amg ", "cpu gmres ", "cpu gmres_obs ")
 
 
 def _table(stage, cases, measure, constants):
-    worst, lines = {}, []
-    for name, ks in cases:
-        ratios = measure(name, max(ks))
-        for k in ks:
-            worst[k] = max(worst.get(k, 0.0), ratios[k])
-        lines.append(f"cpu {stage} {name}: " + " ".join(f"{k}={ratios[k]:.3g}" for k in ks))
-    lines.append(f"cpu {stage} c(k) = 4 r_cpu(k) rounded up to a power of two: " + " ".join(f"{k}={ir.constant_for(worst[k]):g}" for k in sorted(worst)))
-    print("\n".join(lines))
-    _write_profile(f"cpu {stage} ", lines)
-    assert sorted(worst) == sorted(constants)
-    for k in sorted(worst):
-        assert 4.0 * worst[k] <= constants[k], (stage, k, worst[k], constants[k])   # (r_cpu still fits c / 4)
-        assert constants[k] <= ir.C_MAX, "a case whose checker needs more is replaced by a better-conditioned one: the constant is not raised"
+    ir.constants_table(PROFILE, HEADER, STAGES, stage, cases, measure, constants)
 
 
 def test_multilevel_constants_fit(oracle):
@@ -126,6 +102,51 @@ def test_gmres_constants_fit(oracle):
         return {it.k: max(ir.entry_ratio(c.x.astype(np.float64), it), ir.relres_ratio(c.rho, it)) for it, c in zip(ref, chk)}
 
     _table("gmres", [(name, case[3]) for name, case in ir.GMRES_CASES.items()], measure, ir.C_GMRES)
+
+
+def _obs_system(oracle, name):
+    """-> (rowptr, colidx, blocks, n, right-hand side, Psi) of a case of GMRES_OBS_CASES: block_obs_ref's system on the oracle's matrices and Psi"""
+    import block_obs_ref as bo
+    import kron_obs_ref as ko
+    from fdapde_loader import load_package
+
+    load_package()
+    from fdapde_core_amd import meshgen
+
+    system, design, _ = ir.GMRES_OBS_CASES[name]
+    mesh, order, lam, advection = ir.AMG_CASES[system][:4]
+    assert not advection
+    nodes, cells, bnd = getattr(meshgen, mesh[0])(mesh[1])
+    m = oracle.Mesh(np.ascontiguousarray(nodes, dtype=float), np.ascontiguousarray(cells, dtype=np.int32), np.ascontiguousarray(bnd, dtype=np.uint8))
+    dofs, _, nd, _ = oracle.enumerate_dofs(m, order)
+    R1 = oracle.assemble_operator(m, order, dofs, nd, -oracle.laplacian())
+    R0 = oracle.assemble_operator(m, order, dofs, nd, oracle.reaction(1.0))
+    Psi = ko.design_psi(oracle, m, None, order, dofs, nd, design)
+    rp, ci = np.asarray(R1.rowptr, dtype=np.int64), np.asarray(R1.colidx, dtype=np.int64)
+    return rp, ci, bo.smoothing_blocks(rp, ci, R1.values, R0.values, lam, nd), nd, bo.smoothing_rhs(Psi, lam, nd), Psi
+
+
+def test_gmres_constants_with_a_term_fit(oracle):
+    import block_obs_ref as bo
+    import scipy.sparse.linalg as spl
+
+    def measure(name, K):
+        rp, ci, blocks, n, b, Psi = _obs_system(oracle, name)
+        rows = np.diff(Psi.indptr)
+        assert (rows.max() > 64) if name == "a-areal" else (rows.max() <= 3), "an areal row is longer than a team of 64; a pointwise row holds one cell's DOFs"
+        obs = (Psi, None, -1.0)
+        ref = ir.gmres_iterates(rp, ci, blocks, n, b, K, obs=obs)
+        chk = ir.gmres_float64(rp, ci, blocks, n, b, K, obs=obs)
+        return {it.k: max(ir.entry_ratio(c.x.astype(np.float64), it), ir.relres_ratio(c.rho, it)) for it, c in zip(ref, chk)}
+
+    _table("gmres_obs", [(name, case[2]) for name, case in ir.GMRES_OBS_CASES.items()], measure, ir.C_GMRES_OBS)
+    # the reference with a term checks itself: at k large enough it agrees with SuperLU on the explicit system
+    rp, ci, blocks, n, b, Psi = _obs_system(oracle, "a-points")
+    x_lu = spl.splu(bo.system(rp, ci, blocks, n, Psi).tocsc()).solve(b)
+    its = ir.gmres_iterates(rp, ci, blocks, n, b, 300, restart=300, obs=(Psi, None, -1.0))
+    err = float(np.abs(its[-1].x - x_lu).max() / np.abs(x_lu).max())
+    print(f"GMRES reference with a pointwise term at k = 300: rho {its[-1].rho:.2e}, error against SuperLU {err:.2e}")
+    assert err <= 1e-9
 
 
 @pytest.mark.parametrize("name", ["a", "f", "g"])

@@ -13,7 +13,8 @@ spreads its rounding over the whole domain)
     |info.relres - rho_k| <= c_amg(k) u || |A| s || / ||b||, and info.relres within 1e-12 relative of the residual of the vector handed out.
 
 The handle's GMRES stage (block_gmres, the k_gm_* kernels on D^-1 A): entrywise |x_gpu - x_ref|_i <= c_gm(k) u s_i, s = sum_j |y_j| |v_j|, exactly 0 where
-s_i = 0 (the Krylov front has not arrived), and relres against rho_k of the scaled system in the same form.
+s_i = 0 (the Krylov front has not arrived), and relres against rho_k of the scaled system in the same form.  The same with fdapde_block_set_obs's term
+live (an areal and a pointwise Psi, each under block_obs_team = 8 and = 64 against one reference; constants of their own by the same rule).
 
 c(k) = 4 r_cpu(k) rounded up to a power of two, r_cpu the worst ratio of the float64 numpy checkers of the same schemes against the reference on the same
 cases (tests/test_block_iter_cpu.py measures it on the oracle's matrices and fails if it no longer fits or exceeds 2^12; profiles/block_iterates.txt).
@@ -216,6 +217,49 @@ def test_gmres_stage_iterates(env, name):
         if not rr <= ir.C_GMRES[k]:
             bad.append((k, "relres", rr / ir.C_GMRES[k]))
     assert not bad, (name, "(k, what, times the bound)", bad)   # (every k is run and printed before the verdict)
+
+
+@pytest.mark.parametrize("team", ir.OBS_TEAMS)
+@pytest.mark.parametrize("name", list(ir.GMRES_OBS_CASES))
+def test_gmres_stage_iterates_with_a_factored_term(env, oracle, name, team):
+    """the stage with fdapde_block_set_obs's term live (k_obs_gather / k_obs_scatter behind k_block_spmv, the term's share in D^-1): the same bounds, with
+    constants of their own by the same rule, under both team widths against ONE reference"""
+    import block_obs_ref as bo
+    import kron_obs_ref as ko
+
+    capi, meshgen = env
+    system, design, ks = ir.GMRES_OBS_CASES[name]
+    mesh, order, lam, advection = ir.AMG_CASES[system][:4]
+    s = _context(env, system, dict(block_obs_team=team))
+    c, nd = s["c"], s["n"]
+    nodes, cells, bnd = getattr(meshgen, mesh[0])(mesh[1])
+    om = oracle.Mesh(np.ascontiguousarray(nodes, dtype=float), np.ascontiguousarray(cells, dtype=np.int32), np.ascontiguousarray(bnd, dtype=np.uint8))
+    dofs, _, ond, _ = oracle.enumerate_dofs(om, order)
+    assert ond == nd and np.array_equal(c.dofs_get()[0], dofs), "the oracle and the library number the DOFs alike"
+    Psi = ko.design_psi(oracle, om, None, order, dofs, nd, design)
+    rows = np.diff(Psi.indptr)
+    assert (rows.max() > 64) if name == "a-areal" else (rows.max() <= 3), "an areal row is longer than a team of 64; a pointwise row holds one cell's DOFs"
+    blocks = bo.smoothing_blocks(s["rp"], s["ci"], c.matrix_values(capi.MAT_STIFF), c.matrix_values(capi.MAT_MASS), lam, nd)
+    b = bo.smoothing_rhs(Psi, lam, nd)
+    c.block_compute(*blocks, symmetric=True)   # (the context is this test's own: block_obs_team is part of its key)
+    c.block_set_obs(Psi, weights=None, scale=-1.0)
+    info = c.block_obs_info()
+    assert info["team_rows"] == team and info["team_cols"] == team and info["nnz"] == Psi.nnz, "the team width under test"
+    its = ir.gmres_iterates(s["rp"], s["ci"], blocks, nd, b, max(ks), obs=(Psi, None, -1.0))
+    bad = []
+    for k in ks:
+        x, inf = _solve(env, s, b, capi.SOLVER_GMRES, k)
+        ref = its[k - 1]
+        assert not x[ref.s == 0].any()
+        ratio, rr = ir.entry_ratio(x, ref), ir.relres_ratio(inf.relres, ref)
+        _note(f"gmres_obs {name} team {team}", k, ratio)
+        _note(f"gmres_obs {name} team {team} [relres]", k, rr)
+        print(f"gmres_obs {name} team {team} k={k}: worst |err| / (u s) = {ratio:.3g}, relres {rr:.3g} (c = {ir.C_GMRES_OBS[k]:g})")
+        if (np.abs(x.astype(ir.LD) - ref.x) > ir.C_GMRES_OBS[k] * U * ref.s).any():
+            bad.append((k, "iterate", ratio / ir.C_GMRES_OBS[k]))
+        if not rr <= ir.C_GMRES_OBS[k]:
+            bad.append((k, "relres", rr / ir.C_GMRES_OBS[k]))
+    assert not bad, (name, team, "(k, what, times the bound)", bad)   # (every k is run and printed before the verdict)
 
 
 def test_the_getter_refuses_what_it_cannot_answer(env):
