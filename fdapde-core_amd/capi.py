@@ -52,7 +52,7 @@ SYMBOLS = [
     "fdapde_ctx_create_multi", "fdapde_ctx_devices", "fdapde_partition_build", "fdapde_partition_sizes", "fdapde_partition_get", "fdapde_partition_whole",
     "fdapde_partition_peers",
     "fdapde_block_compute", "fdapde_block_solve", "fdapde_block_spmv", "fdapde_block_bench_spmv", "fdapde_gram_pointwise",
-    "fdapde_block_set_obs", "fdapde_block_obs_info",
+    "fdapde_block_set_obs", "fdapde_block_obs_info", "fdapde_block_obs_amg_levels",
     "fdapde_kron_compute", "fdapde_kron_solve", "fdapde_kron_spmv", "fdapde_kron_bench_spmv",
     "fdapde_kron_set_obs", "fdapde_kron_obs_info",
     "fdapde_kron_amg_hierarchy", "fdapde_kron_amg_aggregates",
@@ -494,6 +494,16 @@ class Context:
         n_obs, nnz, tr, tc = C.c_int64(), C.c_int64(), C.c_int32(), C.c_int32()
         self._check(self.lib.fdapde_block_obs_info(self._ctx, C.byref(n_obs), C.byref(nnz), C.byref(tr), C.byref(tc)))
         return {"n_obs": n_obs.value, "nnz": nnz.value, "team_rows": tr.value, "team_cols": tc.value}
+
+    def block_amg_obs_levels(self):
+        """fdapde_block_obs_amg_levels -> dict(nnz, longest_row, team_rows, team_cols: per level of the live block hierarchy that carries the data term -- knob
+        block_amg_obs = 1).  FdapdeError(ENOTINIT) where no live hierarchy carries a term"""
+        nl = C.c_int32()
+        self._check(self.lib.fdapde_block_obs_amg_levels(self._ctx, 0, C.byref(nl), None, None, None, None))
+        nnz = np.zeros(nl.value, dtype=np.int64)
+        lr, tr, tc = (np.zeros(nl.value, dtype=np.int32) for _ in range(3))
+        self._check(self.lib.fdapde_block_obs_amg_levels(self._ctx, nl.value, C.byref(nl), nnz.ctypes.data_as(C.POINTER(C.c_int64)), _ip(lr), _ip(tr), _ip(tc)))
+        return dict(nnz=[int(z) for z in nnz], longest_row=[int(z) for z in lr], team_rows=[int(z) for z in tr], team_cols=[int(z) for z in tc])
 
     # ---- Kronecker-sum operators sum_k T_k (x) S_k on the FEM pattern (the reference's Kronecker(A, B) under fdapde::SparseLU): the space-time systems' handle
     def kron_compute(self, terms, symmetric=False):

@@ -352,6 +352,11 @@ int fdapde_block_obs_info(fdapde_ctx* c, int64_t* n_obs, int64_t* nnz, int32_t* 
     if (c->group) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, kBlockNoGroup);
     return fdapde_engine::e_block_obs_info(c, n_obs, nnz, team_rows, team_cols);
 }
+int fdapde_block_obs_amg_levels(fdapde_ctx* c, int32_t cap, int32_t* n_levels, int64_t* nnz, int32_t* longest_row, int32_t* team_rows, int32_t* team_cols) {
+    if (!c) return FDAPDE_EINVAL;
+    if (c->group) return fdapde_engine::fail(c, FDAPDE_EUNSUPPORTED, kBlockNoGroup);
+    return fdapde_engine::e_block_amg_obs_levels(c, cap, n_levels, nnz, longest_row, team_rows, team_cols);
+}
 // the Kronecker-sum handle (eng_kron.hip): single-device contexts only
 static const char* const kKronNoGroup = "the Kronecker-sum handle takes one-GPU contexts, not a multi-device context";
 int fdapde_kron_compute(fdapde_ctx* c, int32_t q, int32_t n_terms, const double* const* T, const double* const* S, int32_t symmetric) {
@@ -609,6 +614,10 @@ int fdapde_tune(fdapde_ctx* c, const char* key, int32_t value) {
     else if (k == "amg_setup_check" && (value == 0 || value == 1)) c->amg_setup_check = value;
     else if (k == "amg_cols" && (value == 1 || value == 2 || value == 4 || value == 8)) c->amg_cols = value;
     else if (k == "block_obs_team" && (value == 0 || value == 8 || value == 64)) c->block_obs_team = value;   // (read by the next fdapde_block_set_obs)
+    else if (k == "block_amg_obs" && (value == 0 || value == 1)) {   // read by the build of the block handle's hierarchy: a live one goes
+        if (value != c->block_amg_obs) fdapde_engine::block_amg_forget(c);
+        c->block_amg_obs = value;
+    }
     else if (k == "kron_dinv_mb" && value >= 0) c->kron_dinv_mb = value;   // (read by the next fdapde_kron_compute)
     else if (k == "kron_fuse" && (value == 0 || value == 1)) c->kron_fuse = value;
     else if (k == "kron_obs_form" && value >= 0 && value <= 2) c->kron_obs_form = value;   // (read by the next fdapde_kron_set_obs)

@@ -510,6 +510,7 @@ struct fdapde_ctx {
     fdapde_engine::BlockHandle* block = nullptr;   // the 2 x 2 block system's handle (eng_block.hip); not carried by fdapde_ctx_clone
     fdapde_engine::KronHandle* kron = nullptr;     // the Kronecker-sum operator's handle (eng_kron.hip); not carried by fdapde_ctx_clone either
     int block_obs_team = 0;       // knob: lanes per row of the block handle's data term (kernels_obs.h): 0 = by mean row length (above 16: 64, else 8), 8, 64; read by fdapde_block_set_obs
+    int block_amg_obs = 0;        // knob: 1 = FDAPDE_SOLVER_BLOCK_AMG carries a live factored data term through its levels (eng_block_amg.hip), one column at a time; 0 = it refuses one
     int kron_dinv_mb = 2048;      // knob: the inverted diagonal blocks of the Kronecker handle (8 q^2 n bytes) may take that many MiB; above it fdapde_kron_compute builds none (no Krylov stage)
     int kron_fuse = 1;            // knob: 1 = D^-1 applied in the epilogue of k_kron_spmv, 0 = by k_kron_dinv_apply in a launch of its own (measured: DESIGN.md section 15)
     int kron_obs_form = 0;        // knob: the form of the Kronecker handle's data-term kernels (kernels_kron_obs.h): 0 = by mean row length (above 16: wide), 1 narrow, 2 wide; read by fdapde_kron_set_obs

@@ -31,6 +31,7 @@ struct BlockObs {
     bool live = false;
     double scale = 0;
     int team_rows = 8, team_cols = 8;   // lanes per row of Psi (k_obs_gather) / of Psi^T (k_obs_scatter, k_obs_diag)
+    int team_knob = 0;                  // the knob block_obs_team they were chosen under
     fdapde_hip::ObsHost host;
     DBuf<int32_t> rp, ci, trp, tci;
     DBuf<double> v, tv, w, t, g;        // t [n_obs]: W Psi x_1 between the two products; g [n]: the term's share of every diagonal block
@@ -187,13 +188,15 @@ int block_amg_solve(fdapde_ctx* c, BlockHandle& B, const fdapde_options* opt, co
     fdapde_info out{};
     out.method_used = FDAPDE_SOLVER_BLOCK_AMG;
     const auto t_call = std::chrono::steady_clock::now();
-    if (B.obs.live)
-        return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_BLOCK_AMG: a factored data term (fdapde_block_set_obs) is live; the hierarchy is built from pattern entries only");
+    if (B.obs.live && !c->block_amg_obs)
+        return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_BLOCK_AMG: a factored data term (fdapde_block_set_obs) is live; the hierarchy is built from pattern entries only unless the knob block_amg_obs is 1");
     if (!B.jacobi_ok)
         return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_BLOCK_AMG: a DOF's diagonal block is singular (|det| <= 1e-14 max|entry|^2): no block-Jacobi smoother");
     if (!B.amg) {
         const int strength = B.given[2] ? 2 : B.given[1] ? 1 : B.given[3] ? 3 : 0;   // the (2,1) block, else (1,2), (2,2), (1,1)
-        if (int rc = block_amg_build(c, &B.amg, B.raw.p, strength)) {
+        const BlockObs& O = B.obs;   // (live only under block_amg_obs = 1: the levels carry the term)
+        const BlockAmgTerm term{&O.host, O.scale, O.team_rows, O.team_cols, O.team_knob, O.rp.p, O.ci.p, O.trp.p, O.tci.p, O.v.p, O.tv.p, O.w.p, O.g.p};
+        if (int rc = block_amg_build(c, &B.amg, B.raw.p, strength, O.live ? &term : nullptr)) {
             c->info = out;
             if (info) *info = out;
             return rc;
@@ -316,6 +319,7 @@ int e_block_set_obs(fdapde_ctx* c, int64_t n_obs, const int64_t* rowptr, const i
     block_matrix_changed(B);
     fdapde_hip::obs_build(n, n_obs, rowptr, colidx, values, weights, c->hs.dof_e2i.data(), &P);
     O.scale = scale;
+    O.team_knob = c->block_obs_team;
     O.team_rows = fdapde_hip::obs_team_width(P.n_obs, P.nnz, c->block_obs_team);
     O.team_cols = fdapde_hip::obs_team_width(P.n, P.nnz, c->block_obs_team);
     HIPCHK(c, O.rp.upload(P.rp.data(), P.rp.size(), st));
@@ -345,6 +349,15 @@ int e_block_obs_info(fdapde_ctx* c, int64_t* n_obs, int64_t* nnz, int32_t* team_
     if (team_rows) *team_rows = O.team_rows;
     if (team_cols) *team_cols = O.team_cols;
     return FDAPDE_OK;
+}
+
+int e_block_amg_obs_levels(fdapde_ctx* c, int32_t cap, int32_t* n_levels, int64_t* nnz, int32_t* longest_row, int32_t* team_rows, int32_t* team_cols) {
+    if (!c) return FDAPDE_EINVAL;
+    if (int rc = block_guard(c)) return rc;
+    if (int rc = block_live(c)) return rc;
+    if (!block_amg_has_term(c->block->amg))
+        return fail(c, FDAPDE_ENOTINIT, "fdapde_block_obs_amg_levels: no live hierarchy carries a data term (knob block_amg_obs, fdapde_block_set_obs, a FDAPDE_SOLVER_BLOCK_AMG solve)");
+    return block_amg_obs_levels(c->block->amg, cap, n_levels, nnz, longest_row, team_rows, team_cols, nullptr);
 }
 
 int e_block_spmv(fdapde_ctx* c, const double* x, double* y) {

@@ -16,6 +16,11 @@
 //             correction is always two GCR steps preconditioned by the next level's cycle -- GCR because the system is indefinite (flexible CG may divide
 //             by zero), no early exit (it would need a host read-back inside the cycle).
 //   outer     fgmres_outer (eng_pmg.hip) on the UNSCALED system, right-preconditioned by the cycle; the stop rule is the true residual |b - A x| <= rtol |b|.
+//   the term  (knob block_amg_obs = 1) a live factored data term scale [Psi^T W Psi, 0; 0, 0] rides beside the pattern levels: P = P_s (x) I_2 with entries 1, so
+//             its Galerkin product is the term of Psi_{l+1} = Psi_l P_s (host_obs.h obs_coarsen: the same rows, columns through agg).  The aggregates do not see
+//             it.  Its diagonal share g_l joins D_l; the coarsest level is inverted with the term merged in (obs_merge_dense); the cycle's launches add the
+//             term's products behind the pattern kernels, through Psi_l P_s = Psi_{l+1} never through P (block_pre_restrict, block_post, block_spmv_dots);
+//             one column at a time.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -27,8 +32,10 @@
 #include "amg_setup.h"
 #include "context.h"
 #include "engine.h"
+#include "host_obs.h"
 #include "kernels_block.h"
 #include "kernels_dense.h"
+#include "kernels_obs.h"
 
 namespace fdapde_engine {
 
@@ -41,29 +48,64 @@ constexpr int kBamgMaxRestart = 64;  // fgmres_outer's Gram-Schmidt kernels hold
 inline int block_restart_len(const fdapde_ctx* c, int maxit) { return std::max(1, std::min(std::min(c->gmres_m, kBamgMaxRestart), std::max(maxit, 1))); }
 
 // a level: the scalar level (n block rows; a = the strength matrix on the pattern; agg, mptr, midx; team, np; the work vectors at 2 n words) and its blocks
+// a level's share of a carried data term: Psi_l and its transpose on the device (level 0: the handle's arrays; below: obs_coarsen's, kept on the host too)
+struct BamgTerm {
+    int64_t m = 0, nnz = 0;                       // n_obs, nnz(Psi_l)
+    int32_t longest_row = 0;
+    double scale = 0;
+    int team_rows = 8, team_cols = 8;             // lanes per row of Psi_l / of Psi_l^T (obs_team_width per level, knob block_obs_team)
+    const int32_t *rp = nullptr, *ci = nullptr, *trp = nullptr, *tci = nullptr;
+    const double *v = nullptr, *tv = nullptr, *w = nullptr, *g = nullptr;   // (w: the handle's on every level; g: the term's share of D_l)
+    fdapde_hip::ObsHost host;
+    DBuf<int32_t> rp_own, ci_own, trp_own, tci_own;
+    DBuf<double> v_own, tv_own, g_own;
+    DBuf<double> t, t2, s;                        // t [n_obs]: W Psi_l zt between pre- and post-smoothing; t2 [n_obs], s [n_l]: the products of y = A x
+};
 struct BamgLevel : AmgLevel {
     const double* bv = nullptr;                   // four doubles per entry (level 0: the handle's)
     DBuf<double> bv_own, dinv4;                   // (dinv4: the inverted 2 x 2 diagonal blocks, four doubles per row)
+    std::unique_ptr<BamgTerm> term;               // the carried data term, or none
 };
 inline BamgLevel& blk(AmgLevel& L) { return static_cast<BamgLevel&>(L); }
+
+// the term's launches, one column: t = W Psi x_1 (acc: t += ...), y_i += D_i^-1 [scale Psi^T t; 0] (dinv NULL: without D^-1), s = scale Psi^T t
+void term_gather(hipStream_t st, const BamgTerm& O, const double* x, double* t, bool acc) {
+    if (acc) {
+        if (O.team_rows == 64) hipLaunchKernelGGL(k_obs_gather_acc<64>, dim3(g1(O.m, 4)), dim3(256), 0, st, O.m, O.rp, O.ci, O.v, O.w, x, t);
+        else hipLaunchKernelGGL(k_obs_gather_acc<8>, dim3(g1(O.m, 32)), dim3(256), 0, st, O.m, O.rp, O.ci, O.v, O.w, x, t);
+    } else {
+        if (O.team_rows == 64) hipLaunchKernelGGL(k_obs_gather<64>, dim3(g1(O.m, 4)), dim3(256), 0, st, O.m, O.rp, O.ci, O.v, O.w, x, t, (const int32_t*)nullptr);
+        else hipLaunchKernelGGL(k_obs_gather<8>, dim3(g1(O.m, 32)), dim3(256), 0, st, O.m, O.rp, O.ci, O.v, O.w, x, t, (const int32_t*)nullptr);
+    }
+}
+void term_scatter(hipStream_t st, const BamgTerm& O, int64_t n, const double* t, double scale, const double* dinv, double* y) {
+    if (O.team_cols == 64) hipLaunchKernelGGL(k_obs_scatter<64>, dim3(g1(n, 4)), dim3(256), 0, st, n, O.trp, O.tci, O.tv, t, scale, dinv, y, (const int32_t*)nullptr);
+    else hipLaunchKernelGGL(k_obs_scatter<8>, dim3(g1(n, 32)), dim3(256), 0, st, n, O.trp, O.tci, O.tv, t, scale, dinv, y, (const int32_t*)nullptr);
+}
+void term_scatter_store(hipStream_t st, const BamgTerm& O, int64_t n, const double* t, double scale, double* s) {
+    if (O.team_cols == 64) hipLaunchKernelGGL(k_obs_scatter_store<64>, dim3(g1(n, 4)), dim3(256), 0, st, n, O.trp, O.tci, O.tv, t, scale, s);
+    else hipLaunchKernelGGL(k_obs_scatter_store<8>, dim3(g1(n, 32)), dim3(256), 0, st, n, O.trp, O.tci, O.tv, t, scale, s);
+}
 }   // namespace
 
 struct BlockAmg : AmgHierarchy {   // (D: 2 n_L rows; the coarse corrections are GCR steps)
     DBuf<int32_t> rp2, ci2;
     DBuf<double> val2;
+    bool term = false;             // the levels carry the handle's factored data term (knob block_amg_obs): one column at a time
+    double term_ms = 0.0;          // ... and what attaching it cost (part of setup_ms): the host's coarsening, the uploads, g_l
 };
 
 void block_amg_free(BlockAmg* h) { delete h; }
 
 namespace {
 // D^-1 of a level's diagonal blocks (today's 1e-14 rule: k_block_diag_inv); *bad: a block was singular
-int level_dinv(fdapde_ctx* c, BamgLevel& L, bool* bad) {
+int level_dinv(fdapde_ctx* c, BamgLevel& L, bool* bad) {   // (with a carried term D is judged with its share g_l)
     hipStream_t st = c->stream;
     DBuf<int32_t> flag;
     HIPCHK(c, flag.alloc(1));
     HIPCHK(c, hipMemsetAsync(flag.p, 0, sizeof(int32_t), st));
     HIPCHK(c, L.dinv4.alloc(4 * (size_t)L.n));
-    hipLaunchKernelGGL(k_block_diag_inv, dim3(gn(L.n)), dim3(256), 0, st, L.n, L.rp, L.ci, L.bv, (const double*)nullptr, L.dinv4.p, flag.p);
+    hipLaunchKernelGGL(k_block_diag_inv, dim3(gn(L.n)), dim3(256), 0, st, L.n, L.rp, L.ci, L.bv, L.term ? L.term->g : (const double*)nullptr, L.dinv4.p, flag.p);
     HIPCHK(c, hipGetLastError());
     int32_t h = 0;
     HIPCHK(c, hipMemcpyAsync(&h, flag.p, sizeof h, hipMemcpyDeviceToHost, st));
@@ -86,6 +128,10 @@ void block_pre_restrict(hipStream_t st, int Q, AmgLevel& L, AmgLevel& N, const d
         hipLaunchKernelGGL((k_bamg_pre_restrict<T, QC>), dim3(g1(N.n, 256 / T)), dim3(256), 0, st, N.n, L.mptr.p, L.midx.p, L.rp, L.ci, blk(L).bv, blk(L).dinv4.p, kBamgOmega,
                            r, L.zt.p, rc, rs, cs);
     });
+    if (BamgTerm* O = blk(L).term.get()) {   // (Q = 1, so rc[2 I] is the first unknown of aggregate I under either layout) rc -= P^T [scale Psi_l^T t; 0], t = W Psi_l zt
+        term_gather(st, *O, L.zt.p, O->t.p, false);
+        term_scatter(st, *blk(N).term, N.n, O->t.p, -O->scale, nullptr, rc);
+    }
 }
 void block_post(hipStream_t st, int Q, AmgLevel& L, AmgLevel& N, const double* r, double* out) {
     by_team_cols<8>(L.team, Q, [&](auto t, auto q) {
@@ -93,9 +139,20 @@ void block_post(hipStream_t st, int Q, AmgLevel& L, AmgLevel& N, const double* r
         hipLaunchKernelGGL((k_bamg_post<T, QC>), dim3(g1(L.n, 256 / T)), dim3(256), 0, st, L.n, L.rp, L.ci, blk(L).bv, blk(L).dinv4.p, kBamgOmega, L.agg.p, N.e.p, r,
                            L.zt.p, out);
     });
+    if (BamgTerm* O = blk(L).term.get()) {   // t += W Psi_{l+1} e: t = W Psi_l (zt + P e); out -= om D^-1 [scale Psi_l^T t; 0]
+        term_gather(st, *blk(N).term, N.e.p, O->t.p, true);
+        term_scatter(st, *O, L.n, O->t.p, -kBamgOmega * O->scale, blk(L).dinv4.p, out);
+    }
 }
 void block_spmv_dots(hipStream_t st, int Q, AmgLevel& L, const double* x, double* y, const double* p0, const double* q0, const double* p1, const double* q1,
                      const double* p2, const double* q2) {
+    if (BamgTerm* O = blk(L).term.get()) {   // (Q = 1) the term is inside y before the dots: s = scale Psi_l^T W Psi_l x_1 joins the rows of k_bamg_spmv_dots
+        term_gather(st, *O, x, O->t2.p, false);
+        term_scatter_store(st, *O, L.n, O->t2.p, O->scale, O->s.p);
+        if (L.team <= 8) hipLaunchKernelGGL((k_bamg_spmv_dots<8, 1, true>), dim3((unsigned)L.np), dim3(256), 0, st, L.n, L.rp, L.ci, blk(L).bv, x, y, p0, q0, p1, q1, p2, q2, L.part.p, (const double*)O->s.p);
+        else hipLaunchKernelGGL((k_bamg_spmv_dots<16, 1, true>), dim3((unsigned)L.np), dim3(256), 0, st, L.n, L.rp, L.ci, blk(L).bv, x, y, p0, q0, p1, q1, p2, q2, L.part.p, (const double*)O->s.p);
+        return;
+    }
     by_team_cols<8>(L.team, Q, [&](auto t, auto q) {
         constexpr int T = decltype(t)::value, QC = decltype(q)::value;
         hipLaunchKernelGGL((k_bamg_spmv_dots<T, QC>), dim3((unsigned)L.np), dim3(256), 0, st, L.n, L.rp, L.ci, blk(L).bv, x, y, p0, q0, p1, q1, p2, q2, L.part.p);
@@ -103,8 +160,69 @@ void block_spmv_dots(hipStream_t st, int Q, AmgLevel& L, const double* x, double
 }
 constexpr AmgCycleOps kBlockOps{block_pre_restrict, block_post, block_spmv_dots};
 
+// The handle's data term beside the pattern levels: Psi_{l+1} = Psi_l P_s through every level's agg on the host, uploaded; g_l by k_obs_diag; the work vectors
+int block_amg_attach_term(fdapde_ctx* c, BlockAmg& H, const BlockAmgTerm& src) {
+    hipStream_t st = c->stream;
+    const fdapde_hip::ObsHost* fine = src.host;
+    for (size_t l = 0; l < H.lv.size(); ++l) {
+        BamgLevel& L = blk(*H.lv[l]);
+        L.term.reset(new BamgTerm());
+        BamgTerm& O = *L.term;
+        O.m = src.host->n_obs, O.scale = src.scale, O.w = src.w;
+        if (l == 0) {
+            O.nnz = src.host->nnz, O.longest_row = src.host->longest_row, O.team_rows = src.team_rows, O.team_cols = src.team_cols;
+            O.rp = src.rp, O.ci = src.ci, O.trp = src.trp, O.tci = src.tci, O.v = src.v, O.tv = src.tv, O.g = src.g;
+        } else {
+            std::vector<int32_t> agg;
+            HIPCHK(c, hipStreamSynchronize(st));
+            if (int rc = fetch(c, H.lv[l - 1]->agg.p, (size_t)H.lv[l - 1]->n, agg)) return rc;
+            fdapde_hip::obs_coarsen(*fine, agg.data(), L.n, &O.host);
+            const fdapde_hip::ObsHost& P = O.host;
+            O.nnz = P.nnz, O.longest_row = P.longest_row;
+            O.team_rows = fdapde_hip::obs_team_width(P.n_obs, P.nnz, src.team_knob);
+            O.team_cols = fdapde_hip::obs_team_width(P.n, P.nnz, src.team_knob);
+            HIPCHK(c, O.rp_own.upload(P.rp.data(), P.rp.size(), st));
+            HIPCHK(c, O.ci_own.upload(P.ci.data(), P.ci.size(), st));
+            HIPCHK(c, O.v_own.upload(P.v.data(), P.v.size(), st));
+            HIPCHK(c, O.trp_own.upload(P.trp.data(), P.trp.size(), st));
+            HIPCHK(c, O.tci_own.upload(P.tci.data(), P.tci.size(), st));
+            HIPCHK(c, O.tv_own.upload(P.tv.data(), P.tv.size(), st));
+            HIPCHK(c, O.g_own.alloc((size_t)L.n));
+            O.rp = O.rp_own.p, O.ci = O.ci_own.p, O.trp = O.trp_own.p, O.tci = O.tci_own.p, O.v = O.v_own.p, O.tv = O.tv_own.p, O.g = O.g_own.p;
+            if (O.team_cols == 64) hipLaunchKernelGGL(k_obs_diag<64>, dim3(g1(L.n, 4)), dim3(256), 0, st, L.n, O.trp, O.tci, O.tv, O.w, O.scale, O.g_own.p, (const int32_t*)nullptr);
+            else hipLaunchKernelGGL(k_obs_diag<8>, dim3(g1(L.n, 32)), dim3(256), 0, st, L.n, O.trp, O.tci, O.tv, O.w, O.scale, O.g_own.p, (const int32_t*)nullptr);
+            HIPCHK(c, hipGetLastError());
+            fine = &O.host;
+        }
+        HIPCHK(c, O.t.alloc((size_t)O.m));
+        HIPCHK(c, O.t2.alloc((size_t)O.m));
+        HIPCHK(c, O.s.alloc((size_t)L.n));
+    }
+    HIPCHK(c, hipStreamSynchronize(st));   // (the uploads have read the host arrays)
+    H.term = true;
+    return FDAPDE_OK;
+}
+
+// the coarsest level's 2 n-row matrix with the term merged in by the host (as block_dense_build does for level 0): pattern, blocks and Psi_L -> H.rp2 / ci2 / val2
+int block_amg_merge_coarsest(fdapde_ctx* c, BlockAmg& H, const BlockAmgTerm& src) {
+    hipStream_t st = c->stream;
+    BamgLevel& C = blk(*H.lv.back());
+    std::vector<int32_t> rp, ci, rp2, ci2;
+    std::vector<double> bv, v2;
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (int rc = fetch(c, C.rp, (size_t)C.n + 1, rp)) return rc;
+    if (int rc = fetch(c, C.ci, (size_t)C.nnz, ci)) return rc;
+    if (int rc = fetch(c, C.bv, 4 * (size_t)C.nnz, bv)) return rc;
+    fdapde_hip::obs_merge_dense(rp.data(), ci.data(), bv.data(), H.lv.size() == 1 ? *src.host : C.term->host, src.scale, &rp2, &ci2, &v2);
+    HIPCHK(c, H.rp2.upload(rp2.data(), rp2.size(), st));
+    HIPCHK(c, H.ci2.upload(ci2.data(), ci2.size(), st));
+    HIPCHK(c, H.val2.upload(v2.data(), v2.size(), st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    return FDAPDE_OK;
+}
+
 // the hierarchy with (absorb) or without absorption on every level; *stalled: the answer is the "coarsening stalled above the dense limit" refusal
-int block_amg_build_pass(fdapde_ctx* c, BlockAmg** slot, const double* raw, int strength_block, int absorb, bool* stalled) {
+int block_amg_build_pass(fdapde_ctx* c, BlockAmg** slot, const double* raw, int strength_block, const BlockAmgTerm* term, int absorb, bool* stalled) {
     *stalled = false;
     hipStream_t st = c->stream;
     const auto t0 = std::chrono::steady_clock::now();
@@ -136,6 +254,11 @@ int block_amg_build_pass(fdapde_ctx* c, BlockAmg** slot, const double* raw, int 
         N->bv = N->bv_own.p;
         H->lv.push_back(std::move(N));
     }
+    if (term) {   // (the aggregates are the pattern's: the term follows them)
+        const auto t1 = std::chrono::steady_clock::now();
+        if (int rc = block_amg_attach_term(c, *H, *term)) return rc;
+        H->term_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+    }
     // the smoother of every level that has a next one; a singular diagonal block below level 0 ends the hierarchy one level above
     for (size_t l = 0; l + 1 < H->lv.size(); ++l) {
         bool bad = false;
@@ -154,18 +277,22 @@ int block_amg_build_pass(fdapde_ctx* c, BlockAmg** slot, const double* raw, int 
     if (int rc = amg_cols_prepare(c, *H, 1)) return rc;   // (the work vectors: one column until a batch asks for more)
     BamgLevel& C = blk(*H->lv.back());
     if (2 * C.n > kDenseMaxRows) return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_BLOCK_AMG: the coarsest level is too large for the dense inverse");
-    HIPCHK(c, H->rp2.alloc((size_t)(2 * C.n + 1)));
-    HIPCHK(c, H->ci2.alloc((size_t)std::max<int64_t>(4 * C.nnz, 1)));
-    HIPCHK(c, H->val2.alloc((size_t)std::max<int64_t>(4 * C.nnz, 1)));
-    hipLaunchKernelGGL(k_block_expand, dim3(gn(C.n + 1)), dim3(256), 0, st, C.n, C.rp, C.ci, C.bv, H->rp2.p, H->ci2.p, H->val2.p);
-    HIPCHK(c, hipGetLastError());
+    if (term) {
+        if (int rc = block_amg_merge_coarsest(c, *H, *term)) return rc;
+    } else {
+        HIPCHK(c, H->rp2.alloc((size_t)(2 * C.n + 1)));
+        HIPCHK(c, H->ci2.alloc((size_t)std::max<int64_t>(4 * C.nnz, 1)));
+        HIPCHK(c, H->val2.alloc((size_t)std::max<int64_t>(4 * C.nnz, 1)));
+        hipLaunchKernelGGL(k_block_expand, dim3(gn(C.n + 1)), dim3(256), 0, st, C.n, C.rp, C.ci, C.bv, H->rp2.p, H->ci2.p, H->val2.p);
+        HIPCHK(c, hipGetLastError());
+    }
     if (int rc = dense_build_csr(c, 2 * C.n, H->rp2.p, H->ci2.p, H->val2.p, nullptr, 0, H->D)) return rc;
     if (!H->D.ready) return fail(c, FDAPDE_ENOCONV, "FDAPDE_SOLVER_BLOCK_AMG: the coarsest level is singular to working precision");
     H->setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     if (std::getenv("FDAPDE_DEBUG_SETUP")) {
         std::string rows;
         for (size_t l = 0; l < H->lv.size(); ++l) rows += (l ? " / " : "") + std::to_string(2 * H->lv[l]->n);
-        std::fprintf(stderr, "block amg: %zu levels, rows %s, set-up %.2f ms, absorbed %d\n", H->lv.size(), rows.c_str(), H->setup_ms, H->absorbed);
+        std::fprintf(stderr, "block amg: %zu levels, rows %s, set-up %.2f ms (the data term %.2f), absorbed %d\n", H->lv.size(), rows.c_str(), H->setup_ms, H->term_ms, H->absorbed);
     }
     *slot = H.release();
     return FDAPDE_OK;
@@ -173,12 +300,12 @@ int block_amg_build_pass(fdapde_ctx* c, BlockAmg** slot, const double* raw, int 
 }   // namespace
 
 // the hierarchy of the handle's matrix: raw = the unscaled block CSR on the context's pattern, strength_block = which of its four blocks the aggregation reads.
-// Knob amg_absorb: amg_build_retry (amg_setup.h)
-int block_amg_build(fdapde_ctx* c, BlockAmg** slot, const double* raw, int strength_block) {
+// Knob amg_absorb: amg_build_retry (amg_setup.h).  term: the handle's live data term for the levels to carry (knob block_amg_obs), or NULL
+int block_amg_build(fdapde_ctx* c, BlockAmg** slot, const double* raw, int strength_block, const BlockAmgTerm* term) {
     delete *slot;
     *slot = nullptr;
     HIPCHK(c, hipSetDevice(c->device));
-    return amg_build_retry(c, slot, [&](int absorb, bool* stalled) { return block_amg_build_pass(c, slot, raw, strength_block, absorb, stalled); });
+    return amg_build_retry(c, slot, [&](int absorb, bool* stalled) { return block_amg_build_pass(c, slot, raw, strength_block, term, absorb, stalled); });
 }
 
 int block_amg_describe(const BlockAmg* H, int32_t cap, int32_t* n_levels, int64_t* rows, int64_t* nnz, int32_t* absorbed, double* setup_ms) {
@@ -191,6 +318,22 @@ int block_amg_aggregates(fdapde_ctx* c, const BlockAmg* H, int32_t level, int64_
 }
 int block_amg_damping(const BlockAmg* H, int32_t cap, int32_t* n_levels, double* omega) { return amg_damping(H, cap, n_levels, omega); }
 int block_amg_order(fdapde_ctx* c, const BlockAmg* H, int64_t cap, int32_t* order, int64_t* n_rows) { return amg_order(c, H, cap, order, n_rows); }
+
+// fdapde_block_obs_amg_levels: the carried term level by level
+int block_amg_obs_levels(const BlockAmg* H, int32_t cap, int32_t* n_levels, int64_t* nnz, int32_t* longest_row, int32_t* team_rows, int32_t* team_cols, double* term_ms) {
+    if (!H || !H->term) return FDAPDE_ENOTINIT;
+    if (n_levels) *n_levels = (int32_t)H->lv.size();
+    for (size_t l = 0; l < H->lv.size() && (int64_t)l < (int64_t)cap; ++l) {
+        const BamgTerm& O = *static_cast<const BamgLevel&>(*H->lv[l]).term;
+        if (nnz) nnz[l] = O.nnz;
+        if (longest_row) longest_row[l] = O.longest_row;
+        if (team_rows) team_rows[l] = O.team_rows;
+        if (team_cols) team_cols[l] = O.team_cols;
+    }
+    if (term_ms) *term_ms = H->term_ms;
+    return FDAPDE_OK;
+}
+bool block_amg_has_term(const BlockAmg* H) { return H && H->term; }
 
 int block_amg_cols_trace(const BlockAmg* H, int32_t* batches, int32_t* batched_cols, int32_t* single_cols) { return amg_cols_trace(H, batches, batched_cols, single_cols); }
 void block_amg_count_single(BlockAmg* H) { ++H->single_cols; }
@@ -216,6 +359,10 @@ int block_amg_cols(fdapde_ctx* c, BlockAmg& H, const double* raw, int Q, const d
     auto spmv = [&](const double* in, double* out) {   // (one column: the block handle's own kernel)
         if (Q == 1) {
             hipLaunchKernelGGL(k_block_spmv<kBlockTeam>, dim3(g1(n, 256 / kBlockTeam)), dim3(256), 0, st, n, L0.rp, L0.ci, raw, in, out, (const int32_t*)nullptr);
+            if (BamgTerm* O = blk(L0).term.get()) {   // ... and the term's two products behind it
+                term_gather(st, *O, in, O->t2.p, false);
+                term_scatter(st, *O, n, O->t2.p, O->scale, nullptr, out);
+            }
             return;
         }
         by_cols(Q, [&](auto q) {
@@ -287,6 +434,7 @@ int block_amg_run(fdapde_ctx* c, BlockAmg* hp, const double* raw, const double* 
 // the widest batch for `left` columns under the knob amg_cols and the basis budget (amg_cols_width); block_amg_run's restart length is kept
 int block_amg_width(const fdapde_ctx* c, const BlockAmg* H, int32_t left, int maxit) {
     const int mk = block_restart_len(c, maxit);
+    if (H->term) return 1;   // (the term's launches are one column's)
     return amg_cols_width(std::min<int32_t>(left, c->amg_cols), 2 * H->lv[0]->n, mk);
 }
 

@@ -11,6 +11,9 @@
 
 #include "context.h"
 
+namespace fdapde_hip {
+struct ObsHost;   // host_obs.h
+}
 namespace fdapde_engine {
 
 // FDAPDE_DEBUG_TIMING=1: wall-clock marks of the host side of a solve on stderr (where a first solve spends its time)
@@ -226,6 +229,7 @@ int e_block_spmv(fdapde_ctx* c, const double* x, double* y);
 int e_block_bench_spmv(fdapde_ctx* c, int32_t reps, double* avg_ms, double* algorithmic_bytes);
 int e_block_set_obs(fdapde_ctx* c, int64_t n_obs, const int64_t* rowptr, const int32_t* colidx, const double* values, const double* weights, double scale);
 int e_block_obs_info(fdapde_ctx* c, int64_t* n_obs, int64_t* nnz, int32_t* team_rows, int32_t* team_cols);
+int e_block_amg_obs_levels(fdapde_ctx* c, int32_t cap, int32_t* n_levels, int64_t* nnz, int32_t* longest_row, int32_t* team_rows, int32_t* team_cols);
 int e_gram_pointwise(fdapde_ctx* c, int64_t n_locs, const int32_t* cell_ids, const double* values, const double* weights, double* out_values);
 // eng_kron.hip: Kronecker-sum operators sum_k T_k (x) S_k, T_k dense q x q, S_k on the FEM pattern (the space-time systems' handle)
 void kron_release(fdapde_ctx* c);
@@ -262,8 +266,22 @@ int kron_amg_run(fdapde_ctx* c, KronAmg* h, const double* b_dev, double* x_dev, 
 // `raw` on the context's pattern (strength_block: which of a11 a12 a21 a22 the aggregation reads), and one column A x = b against it (b, x: interleaved,
 // internal order, device)
 struct BlockAmg;
+// the handle's live factored data term as the hierarchy takes it (knob block_amg_obs): Psi and Psi^T in the internal order on the device, the host copy the
+// coarsening starts from, the weights, the term's share g of level 0's diagonal blocks; the arrays outlive the hierarchy (a change of the term drops it)
+struct BlockAmgTerm {
+    const fdapde_hip::ObsHost* host;
+    double scale;
+    int team_rows, team_cols;   // level 0's lanes per row of Psi / of Psi^T
+    int team_knob;              // block_obs_team as fdapde_block_set_obs read it: the coarse levels' widths follow it too
+    const int32_t *rp, *ci, *trp, *tci;
+    const double *v, *tv, *w, *g;
+};
 void block_amg_free(BlockAmg* h);
-int block_amg_build(fdapde_ctx* c, BlockAmg** slot, const double* raw, int strength_block);
+int block_amg_build(fdapde_ctx* c, BlockAmg** slot, const double* raw, int strength_block, const BlockAmgTerm* term = nullptr);
+// fdapde_block_obs_amg_levels: per level nnz(Psi_l), its longest row, the lanes per row of Psi_l / Psi_l^T; term_ms: the term's share of the set-up;
+// FDAPDE_ENOTINIT where h is NULL or carries no term
+int block_amg_obs_levels(const BlockAmg* h, int32_t cap, int32_t* n_levels, int64_t* nnz, int32_t* longest_row, int32_t* team_rows, int32_t* team_cols, double* term_ms);
+bool block_amg_has_term(const BlockAmg* h);
 int block_amg_describe(const BlockAmg* h, int32_t cap, int32_t* n_levels, int64_t* rows, int64_t* nnz, int32_t* absorbed, double* setup_ms);   // rows: 2 n_l
 int block_amg_aggregates(fdapde_ctx* c, const BlockAmg* h, int32_t level, int64_t cap, int32_t* agg, int64_t* n_rows);   // fdapde_amg_aggregates, which 2
 int block_amg_order(fdapde_ctx* c, const BlockAmg* h, int64_t cap, int32_t* order, int64_t* n_rows);   // fdapde_amg_order, which 2 (block rows)

@@ -67,6 +67,41 @@ void obs_build(int64_t n_dofs, int64_t n_obs, const int64_t* rowptr, const int32
         }
 }
 
+void obs_coarsen(const ObsHost& fine, const int32_t* agg, int64_t n_coarse, ObsHost* out) {
+    ObsHost& P = *out;
+    P.n_obs = fine.n_obs, P.n = n_coarse, P.longest_row = 0, P.longest_col = 0;
+    P.w = fine.w;
+    P.rp.assign((size_t)fine.n_obs + 1, 0), P.ci.clear(), P.v.clear();
+    std::vector<double> acc((size_t)n_coarse, 0.0);
+    std::vector<uint8_t> seen((size_t)n_coarse, 0);
+    std::vector<int32_t> touched;
+    for (int64_t k = 0; k < fine.n_obs; ++k) {
+        touched.clear();
+        for (int32_t e = fine.rp[k]; e < fine.rp[k + 1]; ++e) {   // (ascending fine columns: the order of every sum)
+            const int32_t j = agg[fine.ci[e]];
+            if (!seen[j]) seen[j] = 1, touched.push_back(j);
+            acc[j] += fine.v[e];
+        }
+        std::sort(touched.begin(), touched.end());
+        for (int32_t j : touched) P.ci.push_back(j), P.v.push_back(acc[j]), acc[j] = 0.0, seen[j] = 0;
+        P.rp[k + 1] = (int32_t)P.ci.size();
+        P.longest_row = std::max<int32_t>(P.longest_row, (int32_t)touched.size());
+    }
+    P.nnz = (int64_t)P.ci.size();
+    P.trp.assign((size_t)n_coarse + 1, 0), P.tci.resize((size_t)P.nnz), P.tv.resize((size_t)P.nnz);
+    for (int64_t e = 0; e < P.nnz; ++e) ++P.trp[P.ci[e] + 1];
+    for (int64_t i = 0; i < n_coarse; ++i) {
+        P.longest_col = std::max(P.longest_col, P.trp[i + 1]);
+        P.trp[i + 1] += P.trp[i];
+    }
+    std::vector<int32_t> at(P.trp.begin(), P.trp.end() - 1);
+    for (int64_t k = 0; k < P.n_obs; ++k)
+        for (int32_t e = P.rp[k]; e < P.rp[k + 1]; ++e) {
+            const int32_t s = at[P.ci[e]]++;
+            P.tci[s] = (int32_t)k, P.tv[s] = P.v[e];
+        }
+}
+
 int obs_team_width(int64_t rows, int64_t nnz, int knob) {
     if (knob == 8 || knob == 64) return knob;
     return nnz > 16 * rows ? 64 : 8;

@@ -33,6 +33,12 @@ void obs_build(int64_t n_dofs, int64_t n_obs, const int64_t* rowptr, const int32
 // lanes per row for a CSR matrix of `rows` rows and `nnz` entries: a mean row length above 16 takes 64, otherwise 8 (knob block_obs_team: 0 this rule, 8, 64)
 int obs_team_width(int64_t rows, int64_t nnz, int knob);
 
+// Psi of the next level of an aggregation hierarchy, Psi_c = Psi P with P piecewise constant (agg[i] in [0, n_coarse): the coarse column of fine column i):
+// the same n_obs rows and weights, the columns through agg, equal columns within a row summed in ascending fine-column order, columns ascending; the
+// transpose by counting as obs_build does; longest_row / longest_col set.  A row may collapse to one entry, an empty row stays empty, rows are not compacted:
+// Psi_l P = Psi_{l+1} holds row for row.  (Psi_c P_c)^T W (Psi_c P_c) is then the Galerkin product of the term.  out must not be &fine.
+void obs_coarsen(const ObsHost& fine, const int32_t* agg, int64_t n_coarse, ObsHost* out);
+
 // The dense stage's matrix: the block CSR (rowptr / colidx of n rows in the internal order, raw = [a11 a12 a21 a22] per entry) expanded to 2 n rows in the
 // interleaved order (row 2 i + p, column 2 j + q) with scale Psi^T W Psi added to the (2 i, 2 j) entries; entries off the pattern are inserted, columns
 // ascending within a row.  (Psi^T W Psi)[i, j] is summed over the observations in ascending order.

@@ -329,11 +329,13 @@ static __global__ __launch_bounds__(256) void k_bamg_post(int64_t n, const int32
     }
 }
 // y = A x and the three dot products p_d . q_d of a GCR step per column (any of the vectors may be y itself) as per-workgroup partials
-// part[(d Q + q) gridDim.x + block]: a fixed grid, every team strides over the rows, the same bits every run
-template <int T, int Q>
+// part[(d Q + q) gridDim.x + block]: a fixed grid, every team strides over the rows, the same bits every run.
+// ADD: add[i Q + q] (the factored data term's share of the row, kernels_obs.h k_obs_scatter_store) joins the first component of row i before the products;
+// algorithmic bytes per launch 36 nnz + 4 (n + 1) + 16 n (x) + 16 n (y) + 16 n per vector of the dots that is not y, and 8 n more for add
+template <int T, int Q, bool ADD = false>
 static __global__ __launch_bounds__(256) void k_bamg_spmv_dots(int64_t n, const int32_t* rp, const int32_t* ci, const double* bv, const double* x, double* y,
                                                                const double* p0, const double* q0, const double* p1, const double* q1, const double* p2,
-                                                               const double* q2, double* part) {
+                                                               const double* q2, double* part, const double* add = nullptr) {
 #pragma clang fp contract(off)
     __shared__ double red[3 * Q][4];
     const int lane = threadIdx.x % T;
@@ -361,6 +363,10 @@ static __global__ __launch_bounds__(256) void k_bamg_spmv_dots(int64_t n, const 
             blk_v2f64_t yi[Q];
 #pragma unroll
             for (int q = 0; q < Q; ++q) yi[q] = blk_v2f64_t{s0[q], s1[q]};
+            if constexpr (ADD) {
+#pragma unroll
+                for (int q = 0; q < Q; ++q) yi[q].x += add[i * Q + q];
+            }
             blk_st_cols<Q>(y + 2 * i * Q, yi);
             auto dots = [&](const double* a, const double* b, double (&d)[Q]) {
                 blk_v2f64_t u[Q], w[Q];

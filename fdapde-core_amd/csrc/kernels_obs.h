@@ -11,6 +11,10 @@
 // Algorithmic bytes of the term per operator application (every array once per pass), nz = nnz(Psi):
 //   gather   12 nz + 4 (n_obs + 1) + 8 n_obs (w) + 8 n (x_1) + 8 n_obs (t written)
 //   scatter  12 nz + 4 (n + 1) + 8 n_obs (t) + 16 n (the first column of D^-1) + 32 n (y read and written)
+// The multilevel cycle of FDAPDE_SOLVER_BLOCK_AMG with the term carried (knob block_amg_obs, eng_block_amg.hip) keeps one Psi_l per level, Psi_{l+1} = Psi_l P_s
+// (host_obs.h obs_coarsen), and two more forms of the products, one column each:
+//   k_obs_gather_acc     t += W Psi x_1      12 nz + 4 (n_obs + 1) + 8 n_obs (w) + 8 n (x_1) + 16 n_obs (t read and written)
+//   k_obs_scatter_store  s = scale Psi^T t   12 nz + 4 (n + 1) + 8 n_obs (t) + 8 n (s written; an empty row stores 0)
 #ifndef FDAPDE_KERNELS_OBS_H
 #define FDAPDE_KERNELS_OBS_H
 
@@ -62,6 +66,38 @@ static __global__ __launch_bounds__(256) void k_obs_scatter(int64_t n, const int
             y[2 * row] += s;
         }
     }
+}
+
+// t_k += w_k (Psi x_1)_k: the second half of W Psi (zt + P e) = W Psi_l zt + W Psi_{l+1} e in the cycle's post-smoothing, over the next level's shorter rows
+template <int T>
+static __global__ __launch_bounds__(256) void k_obs_gather_acc(int64_t n_obs, const int32_t* rp, const int32_t* ci, const double* v, const double* w, const double* x,
+                                                               double* t) {
+    constexpr int TEAMS = 256 / T;
+    const int l = threadIdx.x % T;
+    const int64_t row = (int64_t)blockIdx.x * TEAMS + threadIdx.x / T;
+    const bool row_ok = row < n_obs;
+    const int64_t rc = row_ok ? row : n_obs - 1;
+    const int rs = rp[rc], re = rp[rc + 1];
+    double a = 0.0;
+    for (int k = rs + l; k < re; k += T) a += v[k] * x[2 * (int64_t)ci[k]];
+    a = team_sum<T>(a);
+    if (l == 0 && row_ok) t[row] += w[row] * a;
+}
+
+// s_i = scale (Psi^T t)_i stored (not added): the term's share of a coarse level's y = A x, which k_bamg_spmv_dots adds before its dot products
+template <int T>
+static __global__ __launch_bounds__(256) void k_obs_scatter_store(int64_t n, const int32_t* trp, const int32_t* tci, const double* tv, const double* t, double scale,
+                                                                  double* s) {
+    constexpr int TEAMS = 256 / T;
+    const int l = threadIdx.x % T;
+    const int64_t row = (int64_t)blockIdx.x * TEAMS + threadIdx.x / T;
+    const bool row_ok = row < n;
+    const int64_t rc = row_ok ? row : n - 1;
+    const int rs = trp[rc], re = trp[rc + 1];
+    double a = 0.0;
+    for (int k = rs + l; k < re; k += T) a += tv[k] * t[tci[k]];
+    a = team_sum<T>(a);
+    if (l == 0 && row_ok) s[row] = re > rs ? scale * a : 0.0;
 }
 
 template <int T>

@@ -597,6 +597,11 @@ template <typename D, typename F, int R> class PDE<D, DifferentialExpr, F, FEM_H
                                                 is_empty(weights) ? nullptr : weights.data(), scale);
             if (rc != FDAPDE_OK) throw std::runtime_error(fdapde_last_error(ctx_.get()));
         }
+        // FDAPDE_SOLVER_BLOCK_AMG with a data term live: the hierarchy carries the term level by level (the knob "block_amg_obs"; off, the default, that
+        // solve refuses a live term).  May be called before or after compute(); a change drops the live hierarchy
+        void carry_observations(bool on = true) {
+            if (fdapde_tune(ctx_.get(), "block_amg_obs", on ? 1 : 0) != FDAPDE_OK) throw std::runtime_error(fdapde_last_error(ctx_.get()));
+        }
         DMatrix<double> solve(const DMatrix<double>& b) const {
             if (!computed_) throw std::runtime_error("BlockSolver: compute() first");
             if (b.rows() != 2 * n_) throw std::runtime_error("BlockSolver: right-hand sides need 2 n_dofs rows");

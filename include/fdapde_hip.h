@@ -121,7 +121,13 @@ enum { FDAPDE_SOLVER_AUTO = 0, FDAPDE_SOLVER_CG = 1, FDAPDE_SOLVER_BICGSTAB = 2,
                                 relative residual, info.persistent = 0; FDAPDE_ENOCONV leaves the last iterate of every column, and is also the answer to
                                 a singular coarsest level; a singular diagonal block of a DOF (the 1e-14 rule of fdapde_block_compute) and coarsening
                                 that stalls above the dense limit with absorption too (or with `amg_absorb` 0) are FDAPDE_EUNSUPPORTED.  Taken by name only: the open method never chooses it.
-                                Order-2 spaces in 3-D are allowed, but pairwise matching serves them poorly (no iteration count is claimed). */,
+                                Order-2 spaces in 3-D are allowed, but pairwise matching serves them poorly (no iteration count is claimed).
+                                A live factored data term (fdapde_block_set_obs): FDAPDE_EUNSUPPORTED by default; under the knob `block_amg_obs` = 1 the
+                                hierarchy carries it -- P is piecewise constant, so level l + 1 holds the term of Psi_{l+1} = Psi_l P_s (the same rows, the
+                                columns through the aggregates, built by the host), its diagonal joins D_l, the last level is inverted with the term
+                                merged in, and the cycle adds the term's two products per level behind the pattern kernels (no atomics, the same bits
+                                every run).  The aggregates are the pattern's.  With a term carried the columns go one by one whatever `amg_cols` says.
+                                fdapde_block_obs_amg_levels reports the levels. */,
        FDAPDE_SOLVER_KRON_AMG = 10 /* fdapde_kron_solve only (fdapde_solve, fdapde_solve_parabolic, fdapde_lin_solve and fdapde_block_solve answer
                                 FDAPDE_EUNSUPPORTED): flexible GMRES(gmres_m, at most 64) on the UNSCALED Kronecker-sum system, right-preconditioned by the
                                 multilevel cycle of FDAPDE_SOLVER_BLOCK_AMG on POINT-BLOCK unknowns -- the q unknowns of a DOF stay together on every level.
@@ -353,10 +359,14 @@ int fdapde_lin_solve(fdapde_ctx *ctx, const fdapde_options *opt, const double *b
  * strictly ascending, a non-monotone rowptr, a non-finite value, weight or scale; n_obs = 0 or a NULL rowptr clears the term; a second call replaces it (an
  * iteratively reweighted model changes W that way); fdapde_block_compute and fdapde_dofs_build drop it.  The call drops a live dense inverse and a live
  * FDAPDE_SOLVER_BLOCK_AMG hierarchy.  With a term live FDAPDE_SOLVER_GMRES, FDAPDE_SOLVER_DENSE (the host merges scale Psi^T W Psi into the 2 n-row
- * matrix: set-up) and the open method work as before; FDAPDE_SOLVER_BLOCK_AMG answers FDAPDE_EUNSUPPORTED (its hierarchy is built from pattern entries).
+ * matrix: set-up) and the open method work as before; FDAPDE_SOLVER_BLOCK_AMG answers FDAPDE_EUNSUPPORTED (its hierarchy is built from pattern entries)
+ * unless the knob "block_amg_obs" is 1: then its hierarchy carries the term level by level (see FDAPDE_SOLVER_BLOCK_AMG), the columns one by one.
  * Ranks of a multi-GPU job and multi-device contexts: FDAPDE_EUNSUPPORTED.
  * fdapde_block_obs_info: the live term's rows and entries and the lanes per row of Psi (team_rows) and of Psi^T (team_cols); any pointer may be NULL;
  * without a term FDAPDE_ENOTINIT.
+ * fdapde_block_obs_amg_levels: the data term as the live FDAPDE_SOLVER_BLOCK_AMG hierarchy carries it ("block_amg_obs" = 1): *n_levels = the hierarchy's
+ * levels, and for the first `cap` of them nnz(Psi_l), the longest row of Psi_l and the lanes per row of Psi_l (team_rows) and of Psi_l^T (team_cols); any
+ * output pointer may be NULL.  FDAPDE_ENOTINIT where no live hierarchy carries a term.
  * fdapde_gram_pointwise: Psi^T W Psi on the FEM pattern (nnz values aligned with fdapde_pattern_get) from what fdapde_eval_pointwise / fdapde_project hand
  * out: reference cell ids and row-major n_locs x n_basis values; rows with cell id -1 are skipped, weights may be NULL (all ones); a cell id the mesh does
  * not have: FDAPDE_EINVAL.  Accumulated on the device with fp64 atomics: the order of the additions, hence the last bits, may differ run to run. */
@@ -368,6 +378,8 @@ int fdapde_gram_pointwise(fdapde_ctx *ctx, int64_t n_locs, const int32_t *cell_i
 int fdapde_block_set_obs(fdapde_ctx *ctx, int64_t n_obs, const int64_t *rowptr, const int32_t *colidx, const double *values,
                          const double *weights, double scale);
 int fdapde_block_obs_info(fdapde_ctx *ctx, int64_t *n_obs, int64_t *nnz, int32_t *team_rows, int32_t *team_cols);
+int fdapde_block_obs_amg_levels(fdapde_ctx *ctx, int32_t cap, int32_t *n_levels, int64_t *nnz, int32_t *longest_row, int32_t *team_rows,
+                                int32_t *team_cols);
 
 /* ---- Kronecker-sum operators on the FEM pattern: A = sum_{k < n_terms} T_k (x) S_k -- the reference's Kronecker(A, B) (fdaPDE/linear_algebra/
  *      kronecker_product.h:56-80), which it evaluates into an explicit sparse matrix and hands to SparseLU: every block of a space-time separable smoothing
@@ -640,7 +652,9 @@ int fdapde_partition_peers(fdapde_ctx *ctx, int32_t rank, int32_t *n_peers, int3
  *                 alone; every column's iterates are those of a column-by-column run, bit for bit --: 1, 2, 4 or 8; 8.  1 = column by column.  The
  *                 hierarchy stays)
  *   block handle  "block_obs_team" (lanes per row of the data term's two products: 0, the default = 64 where the mean row length of Psi -- of Psi^T for the
- *                 second product -- is above 16, else 8; 8 or 64 force that width for both; read by the next fdapde_block_set_obs)
+ *                 second product -- is above 16, else 8; 8 or 64 force that width for both; read by the next fdapde_block_set_obs),
+ *                 "block_amg_obs" (0, the default: FDAPDE_SOLVER_BLOCK_AMG refuses a live factored data term; 1: its hierarchy carries the term, one
+ *                 column at a time; without a live term the knob changes nothing; another value drops the live block hierarchy)
  *   Kronecker     "kron_dinv_mb" (the MiB the inverted diagonal blocks of the Kronecker handle may take, >= 0; 2048; read by the next fdapde_kron_compute),
  *                 "kron_fuse" (1, the default: D^-1 applied in the epilogue of the operator kernel; 0: by a batched q x q matvec kernel of its own),
  *                 "kron_obs_form" (the form of the data term's kernels: 0, the default = wide, a workgroup per row, where the mean row length of Psi -- of
