@@ -1,7 +1,7 @@
 // amg_setup.h -- what FDAPDE_SOLVER_AMG (eng_amg.hip) and the block form of eng_block_amg.hip share: a level, a hierarchy, the level step of the set-up
 // (pairwise handshake matching twice -- absorb: the rows it leaves single join the pair of their most strongly coupled paired neighbour --, the Galerkin
 // products of piecewise-constant P, the members of every aggregate; compared with the host loops of host_amg.cpp under the knob amg_setup_check), the
-// stall rule, the retry with absorption, and the K-cycle's recursion.
+// stall rule, the retry with absorption, the K-cycle's recursion, and the column run of the operator handles' point-block hierarchies (amg_point_cols).
 #ifndef FDAPDE_AMG_SETUP_H
 #define FDAPDE_AMG_SETUP_H
 
@@ -13,6 +13,8 @@
 
 #include "amg_rows.h"
 #include "context.h"
+#include "engine.h"
+#include "kernels_block.h"
 
 namespace fdapde_engine {
 
@@ -121,6 +123,84 @@ inline int amg_restart_len(int64_t n, int maxit) {
 }
 // the widest batch the basis budget allows: Q (2 mk + 1) n words within 16 GB, else 4, 2, 1 (the restart length is never shortened)
 int amg_cols_width(int want, int64_t n_words, int mk);
+
+// ---- the point-block hierarchies of the operator handles (eng_block_amg.hip, eng_kron_amg.hip): H.per unknowns of a DOF kept together
+struct BlockAmg : AmgHierarchy {   // (D: 2 n_L rows; the coarse corrections are GCR steps)
+    DBuf<int32_t> rp2, ci2;
+    DBuf<double> val2;
+    bool term = false;             // the levels carry the handle's factored data term (knob block_amg_obs): one column at a time
+    double term_ms = 0.0;          // ... and what attaching it cost (part of setup_ms): the host's coarsening, the uploads, g_l
+};
+struct KronAmg : AmgHierarchy {    // (D: q n_L rows; the coarse corrections are GCR steps)
+    DBuf<int32_t> rp2, ci2, flag;
+    DBuf<double> val2;
+};
+// the restart length of their outer iteration: the knob gmres_m, never more than maxit nor than the 64 coefficients fgmres_outer's Gram-Schmidt kernels hold --
+// one rule for a single-column run and for a batch
+inline int amg_point_restart_len(const fdapde_ctx* c, int maxit) { return std::max(1, std::min(std::min(c->gmres_m, 64), std::max(maxit, 1))); }
+// One run against such a hierarchy for Q columns side by side: A x = b per column (b, x: H.per n Q words, the columns interleaved as in kernels_cols.h, internal
+// order, on the device; x is written -- warm: x holds the iterates to start from; r, t: scratch of the same size), spmv(in, out) = the level-0 product the
+// hierarchy was built from.  The outer iteration is fgmres_outer at width Q on the UNSCALED system; what is handed out is judged by its own residual:
+// S.converged, and rel = |b - A x| / |b| per column.  A template as handle_gmres is: the product is the caller's lambda
+template <class Product> int amg_point_cols(fdapde_ctx* c, AmgHierarchy& H, int Q, Product&& spmv, const double* b, double* x, double* r, double* t, bool warm, double rtol, int maxit,
+                   FgmresCols& S, double* rel) {
+    hipStream_t st = c->stream;
+    const int64_t n2 = H.per * H.lv[0]->n;
+    const size_t nq = (size_t)n2 * (size_t)Q;
+    const int np = (int)std::min<int64_t>(1024, std::max<int64_t>(1, (n2 + 4095) / 4096));
+    const int mk = amg_point_restart_len(c, maxit);
+    if (int rc = amg_cols_prepare(c, H, Q)) return rc;
+    HIPCHK(c, H.basis.alloc((size_t)(2 * mk + 1) * nq));
+    HIPCHK(c, H.part.alloc((size_t)Q * ((size_t)(mk + 2) * (size_t)np + 3 * (size_t)np)));
+    HIPCHK(c, H.dots.alloc((size_t)Q * (size_t)(mk + 4)));
+    double h[kAmgColsMax];
+    auto dots = [&](const double* a0) -> int {
+        fixed_dots_cols(st, n2, np, Q, a0, a0, H.part.p, H.dots.p);
+        HIPCHK(c, hipMemcpyAsync(h, H.dots.p, sizeof(double) * (size_t)Q, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        return FDAPDE_OK;
+    };
+    auto residual = [&](double* rr_out) -> int {   // the TRUE residuals of the iterates
+        spmv(x, t);
+        hipLaunchKernelGGL(k_bamg_residual, dim3(gn((int64_t)nq)), dim3(256), 0, st, (int64_t)nq, b, (const double*)t, r);
+        if (int rc = dots(r)) return rc;
+        std::copy(h, h + Q, rr_out);
+        return FDAPDE_OK;
+    };
+    if (!warm) HIPCHK(c, hipMemsetAsync(x, 0, sizeof(double) * nq, st));
+    HIPCHK(c, hipMemcpyAsync(r, b, sizeof(double) * nq, hipMemcpyDeviceToDevice, st));
+    if (int rc = dots(r)) return rc;
+    bool live = false;   // a column that starts (0 < |b|^2 < inf), and is judged by its own residual at the end
+    for (int q = 0; q < Q; ++q) {
+        S.bb[q] = S.rr[q] = h[q], S.converged[q] = !(h[q] > 0.0) && std::isfinite(h[q]), S.broke[q] = !std::isfinite(h[q]);
+        live = live || (h[q] > 0.0 && std::isfinite(h[q]));
+    }
+    if (warm && live) {   // (a column a batch handed back: the residual of its iterate starts the first cycle)
+        if (int rc = residual(S.rr)) return rc;
+        for (int q = 0; q < Q; ++q)
+            if (!std::isfinite(S.rr[q])) S.broke[q] = true;
+    }
+    const bool one_level = H.lv.size() == 1;
+    auto precond = [&](const double* v, double* z, double* w, bool&) -> int {
+        if (one_level) {
+            if (int rc = amg_dense_cols(c, H, Q, v, z)) return rc;
+        } else if (int rc = amg_cycle(c, H, 0, Q, v, z))
+            return rc;
+        spmv(z, w);
+        return FDAPDE_OK;
+    };
+    FgmresSpace fs{n2, mk, H.basis.p, H.basis.p + (size_t)(mk + 1) * nq, H.part.p, H.dots.p, np};
+    if (int rc = fgmres_outer(c, fs, Q, x, r, nullptr, rtol, maxit, precond, residual, S)) return rc;
+    double rr[kAmgColsMax];
+    if (live)   // what is handed out is judged by its own residual, whichever way the loop ended
+        if (int rc = residual(rr)) return rc;
+    for (int q = 0; q < Q; ++q) {
+        if (S.bb[q] > 0.0 && std::isfinite(S.bb[q])) S.rr[q] = rr[q], S.converged[q] = std::isfinite(rr[q]) && rr[q] <= rtol * rtol * S.bb[q];
+        rel[q] = S.bb[q] > 0.0 ? std::sqrt(S.rr[q] / S.bb[q]) : 0.0;
+    }
+    HIPCHK(c, hipGetLastError());
+    return FDAPDE_OK;
+}
 
 }   // namespace fdapde_engine
 #endif

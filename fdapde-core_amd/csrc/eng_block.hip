@@ -3,7 +3,8 @@
 // utils/symbols.h:133-160, linear_algebra/smw.h:38-59), and Psi^T W Psi on that pattern (kernels_block.h).
 //   fdapde_block_compute   blocks -> block CSR in the internal order, D^-1 A folded into a second copy (left block-Jacobi)
 //   fdapde_block_solve     restarted GMRES(m) on D^-1 A (kernels_gmres.h, buffers of the handle's own), or the dense inverse of the 2 n-row matrix, or
-//                          (by name) flexible GMRES around the point-block multilevel cycle of eng_block_amg.hip
+//                          (by name) flexible GMRES around the point-block multilevel cycle of eng_block_amg.hip.  The stages, the column loops and the
+//                          ending are handle_solve's (eng_handle.h, shared with eng_kron.hip); here: the refusals and block_ops -- staging, operator, builds
 //   fdapde_block_spmv      y = A x with the unscaled blocks
 //   fdapde_gram_pointwise  Psi^T W Psi from what fdapde_eval_pointwise / fdapde_project hand out
 //   fdapde_block_set_obs   the data term kept factored: the handle's matrix becomes A + scale [Psi^T W Psi, 0; 0, 0] with Psi a CSR matrix of any row length
@@ -14,9 +15,10 @@
 #include <cmath>
 #include <vector>
 
+#include "amg_setup.h"
 #include "context.h"
 #include "engine.h"
-#include "eng_gmres.h"
+#include "eng_handle.h"
 #include "host_obs.h"
 #include "kernels_block.h"
 #include "kernels_dense.h"
@@ -37,20 +39,8 @@ struct BlockObs {
     DBuf<double> v, tv, w, t, g;        // t [n_obs]: W Psi x_1 between the two products; g [n]: the term's share of every diagonal block
 };
 
-struct BlockHandle {
-    bool ready = false, symmetric = false;
-    bool jacobi_ok = false;            // every diagonal block was invertible: the Krylov stage is available
-    int64_t n = 0, nnz = 0;            // the space the handle was computed on
+struct BlockHandle : HandleCore {      // (the vectors at 2 n words, ext at least max(4 nnz, 2 n), the dense stage on 2 n rows)
     DBuf<double> raw, scaled, dinv;    // [4 nnz] unscaled / D^-1-scaled values, [4 n] the inverted diagonal blocks
-    DBuf<double> ext;                  // staging: blocks / stacked columns in the reference numbering
-    DBuf<double> bt, x, r, w, t, sc, gm_V, gm_s, gm_part;
-    DBuf<int32_t> ctl, flag;
-    DBuf<int32_t> rowptr2, colidx2;    // the 2 n-row CSR form (dense stage), built on first use
-    DBuf<double> val2, dn_b, dn_x;
-    bool expanded = false;
-    fdapde_ctx::Dense dense;
-    int64_t cols = 0;                  // columns solved against the current matrix
-    double krylov_ms = 0;              // ... and the host time the Krylov columns among them took
     bool given[4] = {false, false, false, false};   // which of a11 a12 a21 a22 were handed over (not NULL)
     BlockAmg* amg = nullptr;           // FDAPDE_SOLVER_BLOCK_AMG's hierarchy of the current matrix (eng_block_amg.hip), built by its first solve
     BlockObs obs;
@@ -75,31 +65,28 @@ void block_amg_forget(fdapde_ctx* c) {
     }
     block_amg_free(c->block->amg), c->block->amg = nullptr;
 }
+// fdapde_amg_hierarchy / _cols_trace / _aggregates / _order / _damping, which 2: the answers of eng_amg.hip on the hierarchy's base (rows 2 n_l, entries 4 nnz_l: per = 2)
+static const AmgHierarchy* block_hierarchy(const fdapde_ctx* c) { return c->block ? c->block->amg : nullptr; }
 int block_amg_describe_ctx(const fdapde_ctx* c, int32_t cap, int32_t* n_levels, int64_t* rows, int64_t* nnz, int32_t* absorbed, double* setup_ms) {
-    return block_amg_describe(c->block ? c->block->amg : nullptr, cap, n_levels, rows, nnz, absorbed, setup_ms);
+    return amg_describe(block_hierarchy(c), cap, n_levels, rows, nnz, absorbed, setup_ms);
 }
 int block_amg_cols_trace_ctx(const fdapde_ctx* c, int32_t* batches, int32_t* batched_cols, int32_t* single_cols) {
-    return block_amg_cols_trace(c->block ? c->block->amg : nullptr, batches, batched_cols, single_cols);
+    return amg_cols_trace(block_hierarchy(c), batches, batched_cols, single_cols);
 }
-int block_amg_aggregates_ctx(fdapde_ctx* c, int32_t level, int64_t cap, int32_t* agg, int64_t* n_rows) {
-    return block_amg_aggregates(c, c->block ? c->block->amg : nullptr, level, cap, agg, n_rows);
-}
-int block_amg_order_ctx(fdapde_ctx* c, int64_t cap, int32_t* order, int64_t* n_rows) {
-    return block_amg_order(c, c->block ? c->block->amg : nullptr, cap, order, n_rows);
-}
-int block_amg_damping_ctx(const fdapde_ctx* c, int32_t cap, int32_t* n_levels, double* omega) {
-    return block_amg_damping(c->block ? c->block->amg : nullptr, cap, n_levels, omega);
-}
+int block_amg_aggregates_ctx(fdapde_ctx* c, int32_t level, int64_t cap, int32_t* agg, int64_t* n_rows) { return amg_aggregates(c, block_hierarchy(c), level, cap, agg, n_rows); }
+int block_amg_order_ctx(fdapde_ctx* c, int64_t cap, int32_t* order, int64_t* n_rows) { return amg_order(c, block_hierarchy(c), cap, order, n_rows); }
+int block_amg_damping_ctx(const fdapde_ctx* c, int32_t cap, int32_t* n_levels, double* omega) { return amg_damping(block_hierarchy(c), cap, n_levels, omega); }
 
 namespace {
 
-int block_guard(fdapde_ctx* c) {
-    if (int rc = need_device(c)) return rc;
-    if (c->comm != nullptr || c->ar_fn != nullptr || c->halo_ready || c->rd.ready)
-        return fail(c, FDAPDE_EUNSUPPORTED, "the 2 x 2 block handle takes one-GPU contexts, not a rank of a multi-GPU job");
-    if (!c->dev_ready) return fail(c, FDAPDE_ENOTINIT, "call fdapde_dofs_build first");
-    return FDAPDE_OK;
-}
+constexpr HandleWords kBlockWords{
+    "the 2 x 2 block handle takes one-GPU contexts, not a rank of a multi-GPU job",
+    "call fdapde_block_compute first",
+    "fdapde_block_solve runs FDAPDE_SOLVER_GMRES, FDAPDE_SOLVER_DENSE, FDAPDE_SOLVER_BLOCK_AMG or the open method",
+    "FDAPDE_SOLVER_DENSE takes block systems of up to `dense_rows` (at most 8192) rows",
+    "the block matrix",   // (dense_singular's `what`)
+    "FDAPDE_SOLVER_BLOCK_AMG: the flexible GMRES broke down in at least one column",
+    "FDAPDE_SOLVER_BLOCK_AMG: maxit reached in at least one column"};
 
 void launch_block_spmv(fdapde_ctx* c, const double* vals, const double* x, double* y, const int32_t* stop) {
     const int64_t n = c->hs.n_dofs;
@@ -124,12 +111,6 @@ void launch_block_op(fdapde_ctx* c, BlockHandle& B, const double* x, double* y, 
     if (B.obs.live) launch_obs_term(c, B, B.dinv.p, x, y, stop);
 }
 
-// restarted GMRES(m) on D^-1 A z = D^-1 b for the column staged in B.bt: handle_gmres (eng_gmres.h) on the handle's buffers
-int block_gmres(fdapde_ctx* c, BlockHandle& B, double tol2, int maxit, int32_t h_ctl[4], double h_sc[4]) {
-    return handle_gmres(c, HandleGmresWork{B.bt, B.x, B.r, B.w, B.t, B.sc, B.gm_V, B.gm_s, B.gm_part, B.ctl}, 2 * B.n,
-                        [&](const double* x, double* y, const int32_t* stop) { launch_block_op(c, B, x, y, stop); }, tol2, maxit, h_ctl, h_sc);
-}
-
 // D^-1 of every DOF (g: the data term's share of the (1,1) entries, or NULL), the singular-block flag and the scaled copy, from `raw`
 int block_rescale(fdapde_ctx* c, BlockHandle& B, const double* g) {
     hipStream_t st = c->stream;
@@ -143,10 +124,6 @@ int block_rescale(fdapde_ctx* c, BlockHandle& B, const double* g) {
     HIPCHK(c, hipStreamSynchronize(st));
     B.jacobi_ok = h_flag == 0;
     return FDAPDE_OK;
-}
-
-bool block_dense_eligible(const fdapde_ctx* c, const BlockHandle& B) {
-    return c->dense_rows > 0 && 2 * B.n <= c->dense_rows && 2 * B.n <= kDenseMaxRows;
 }
 
 int block_dense_build(fdapde_ctx* c, BlockHandle& B) {
@@ -178,75 +155,59 @@ int block_dense_build(fdapde_ctx* c, BlockHandle& B) {
     return dense_build_csr(c, 2 * n, B.rowptr2.p, B.colidx2.p, B.val2.p, nullptr, 0, B.dense);
 }
 
-// FDAPDE_SOLVER_BLOCK_AMG by name: the hierarchy built by the first such solve after fdapde_block_compute, the columns in batches side by side (knob amg_cols) on the UNSCALED
-// system (stop rule: the true residual |b - A x| <= rtol |b| -- not the D^-1-scaled one of the GMRES stage)
-int block_amg_solve(fdapde_ctx* c, BlockHandle& B, const fdapde_options* opt, const double* b, int32_t n_rhs, double* x, fdapde_info* info) {
+// what a change of the term invalidates: handle_matrix_changed's and the multilevel hierarchy
+void block_matrix_changed(BlockHandle& B) {
+    handle_matrix_changed(B);
+    block_amg_free(B.amg), B.amg = nullptr;
+}
+
+// What handle_solve (eng_handle.h) and fdapde_block_spmv take from this handle.  Staging: one kernel under every layout -- D^-1 folded in for the Krylov stage,
+// the dense stage's order is the internal one.  FDAPDE_SOLVER_BLOCK_AMG: the hierarchy built by the first such solve after fdapde_block_compute, the columns in
+// batches side by side (knob amg_cols) on the UNSCALED system (stop rule: the true residual |b - A x| <= rtol |b| -- not the D^-1-scaled one of the GMRES stage)
+auto block_ops(fdapde_ctx* c, BlockHandle& B) {
     const int64_t n = B.n, n2 = 2 * n;
     hipStream_t st = c->stream;
-    const double rtol = (opt && opt->rtol > 0) ? opt->rtol : 1e-10;
-    const int maxit = (opt && opt->maxit > 0) ? opt->maxit : 200;
-    fdapde_info out{};
-    out.method_used = FDAPDE_SOLVER_BLOCK_AMG;
-    const auto t_call = std::chrono::steady_clock::now();
-    if (B.obs.live && !c->block_amg_obs)
-        return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_BLOCK_AMG: a factored data term (fdapde_block_set_obs) is live; the hierarchy is built from pattern entries only unless the knob block_amg_obs is 1");
-    if (!B.jacobi_ok)
-        return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_BLOCK_AMG: a DOF's diagonal block is singular (|det| <= 1e-14 max|entry|^2): no block-Jacobi smoother");
-    if (!B.amg) {
-        const int strength = B.given[2] ? 2 : B.given[1] ? 1 : B.given[3] ? 3 : 0;   // the (2,1) block, else (1,2), (2,2), (1,1)
-        const BlockObs& O = B.obs;   // (live only under block_amg_obs = 1: the levels carry the term)
-        const BlockAmgTerm term{&O.host, O.scale, O.team_rows, O.team_cols, O.team_knob, O.rp.p, O.ci.p, O.trp.p, O.tci.p, O.v.p, O.tv.p, O.w.p, O.g.p};
-        if (int rc = block_amg_build(c, &B.amg, B.raw.p, strength, O.live ? &term : nullptr)) {
-            c->info = out;
-            if (info) *info = out;
-            return rc;
-        }
-    }
-    HIPCHK(c, B.ext.alloc((size_t)std::max<int64_t>(4 * B.nnz, n2 * kAmgColsMax)));
-    int total = 0, rc_all = FDAPDE_OK;   // (B.cols and B.krylov_ms stay: the open method's rent-or-buy rule counts its own columns only)
-    double worst = 0;
-    bool broke_any = false;
-    for (int32_t j = 0; j < n_rhs; ++j) {
+    return HandleOps{
+        kBlockWords, FDAPDE_SOLVER_BLOCK_AMG, n2, std::max<int64_t>(4 * B.nnz, n2),
+        [c, &B, n, st](HandleLayout layout, const double* ext, double* dst, int ncols) {
+            hipLaunchKernelGGL(k_block_stage, dim3(g1(n), ncols), dim3(256), 0, st, n, c->dof_i2e.p, ext, layout == kLayoutKrylov ? B.dinv.p : nullptr, dst);
+        },
+        [c, n, st](HandleLayout, const double* src, double* ext, int ncols) {
+            hipLaunchKernelGGL(k_block_unstage, dim3(g1(n), ncols), dim3(256), 0, st, n, c->dof_i2e.p, src, ext);
+        },
+        [c, &B](const double* x, double* y, const int32_t* stop) { launch_block_op(c, B, x, y, stop); },
+        [c, &B] { return block_dense_build(c, B); },
+        [c, &B] {
+            if (B.amg) return (int)FDAPDE_OK;
+            const int strength = B.given[2] ? 2 : B.given[1] ? 1 : B.given[3] ? 3 : 0;   // the (2,1) block, else (1,2), (2,2), (1,1)
+            const BlockObs& O = B.obs;   // (live only under block_amg_obs = 1: the levels carry the term)
+            const BlockAmgTerm term{&O.host, O.scale, O.team_rows, O.team_cols, O.team_knob, O.rp.p, O.ci.p, O.trp.p, O.tci.p, O.v.p, O.tv.p, O.w.p, O.g.p};
+            return block_amg_build(c, &B.amg, B.raw.p, strength, O.live ? &term : nullptr);
+        },
+        [c, &B](const double* b, double* x, double rtol, int maxit, int* it, double* rel, bool* conv, bool* broke) {
+            return block_amg_run(c, B.amg, B.raw.p, b, x, rtol, maxit, it, rel, conv, broke);
+        },
         // batches of 8, then 4, then 2 columns side by side (knob amg_cols; one host <-> device copy per batch), a last single column as before
-        const int Q = block_amg_width(c, B.amg, n_rhs - j, maxit);
-        if (Q > 1) {
+        [c, &B, n2, st](const double* b, double* x, int32_t left, double rtol, int maxit, HandleTally& t, int* took) -> int {
+            const int Q = block_amg_width(c, B.amg, left, maxit);
+            *took = Q > 1 ? Q : 0;
+            if (Q == 1) return ++B.amg->single_cols, (int)FDAPDE_OK;
             const size_t cnt = (size_t)n2 * (size_t)Q;
-            HIPCHK(c, hipMemcpyAsync(B.ext.p, b + (size_t)j * n2, sizeof(double) * cnt, hipMemcpyHostToDevice, st));
+            HIPCHK(c, hipMemcpyAsync(B.ext.p, b, sizeof(double) * cnt, hipMemcpyHostToDevice, st));
             bool not_conv = false;
-            if (int rc = block_amg_batch(c, B.amg, B.raw.p, Q, B.ext.p, B.bt.p, B.x.p, rtol, maxit, &total, &worst, &not_conv, &broke_any)) return rc;
-            if (not_conv) rc_all = FDAPDE_ENOCONV;
-            HIPCHK(c, hipMemcpyAsync(x + (size_t)j * n2, B.ext.p, sizeof(double) * cnt, hipMemcpyDeviceToHost, st));
+            if (int rc = block_amg_batch(c, B.amg, B.raw.p, Q, B.ext.p, B.bt.p, B.x.p, rtol, maxit, &t.total, &t.worst, &not_conv, &t.broke)) return rc;
+            if (not_conv) t.rc_all = FDAPDE_ENOCONV;
+            HIPCHK(c, hipMemcpyAsync(x, B.ext.p, sizeof(double) * cnt, hipMemcpyDeviceToHost, st));
             HIPCHK(c, hipStreamSynchronize(st));
-            j += Q - 1;
-            continue;
-        }
-        block_amg_count_single(B.amg);
-        HIPCHK(c, hipMemcpyAsync(B.ext.p, b + (size_t)j * n2, sizeof(double) * (size_t)n2, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_block_stage, dim3(g1(n), 1), dim3(256), 0, st, n, c->dof_i2e.p, B.ext.p, nullptr, B.bt.p);
-        int it = 0;
-        double rel = 0;
-        bool conv = false, broke = false;
-        if (int rc = block_amg_run(c, B.amg, B.raw.p, B.bt.p, B.x.p, rtol, maxit, &it, &rel, &conv, &broke)) return rc;
-        if (!conv) rc_all = FDAPDE_ENOCONV, broke_any = broke_any || broke;
-        total += it, worst = rel > worst || std::isnan(rel) ? rel : worst;
-        hipLaunchKernelGGL(k_block_unstage, dim3(g1(n), 1), dim3(256), 0, st, n, c->dof_i2e.p, B.x.p, B.ext.p);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(x + (size_t)j * n2, B.ext.p, sizeof(double) * (size_t)n2, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-    }
-    out.iters = total, out.relres = worst, out.converged = rc_all == FDAPDE_OK ? 1 : 0, out.persistent = 0;
-    out.t_solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
-    c->info = out;
-    if (info) *info = out;
-    if (rc_all == FDAPDE_ENOCONV) c->err = broke_any ? "FDAPDE_SOLVER_BLOCK_AMG: the flexible GMRES broke down in at least one column" : "FDAPDE_SOLVER_BLOCK_AMG: maxit reached in at least one column";
-    return rc_all;
+            return FDAPDE_OK;
+        }};
 }
 
 }   // namespace
 
 int e_block_compute(fdapde_ctx* c, const double* a11, const double* a12, const double* a21, const double* a22, int32_t symmetric) {
     if (!c) return FDAPDE_EINVAL;
-    if (int rc = block_guard(c)) return rc;
+    if (int rc = handle_guard(c, kBlockWords)) return rc;
     if ((!a11 && !a12) || (!a21 && !a22)) return fail(c, FDAPDE_EINVAL, "fdapde_block_compute: a block row without a block (the matrix would be singular)");
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
@@ -254,9 +215,8 @@ int e_block_compute(fdapde_ctx* c, const double* a11, const double* a12, const d
     const int64_t n = hs.n_dofs, nnz = hs.nnz;
     if (!c->block) c->block = new BlockHandle();
     BlockHandle& B = *c->block;
-    B.ready = false, B.expanded = false, B.n = n, B.nnz = nnz, B.symmetric = symmetric != 0;
-    B.dense.ready = B.dense.failed = false, B.cols = 0, B.krylov_ms = 0;
-    block_amg_free(B.amg), B.amg = nullptr;   // (the hierarchy belonged to the previous matrix)
+    B.ready = false, B.n = n, B.nnz = nnz, B.symmetric = symmetric != 0;
+    block_matrix_changed(B);                  // (the inverse and the hierarchy belonged to the previous matrix)
     B.obs.live = false;                       // (... and so did the data term)
     B.given[0] = a11 != nullptr, B.given[1] = a12 != nullptr, B.given[2] = a21 != nullptr, B.given[3] = a22 != nullptr;
     HIPCHK(c, B.ext.alloc((size_t)std::max<int64_t>(4 * nnz, 2 * n)));
@@ -278,22 +238,10 @@ int e_block_compute(fdapde_ctx* c, const double* a11, const double* a12, const d
     return FDAPDE_OK;
 }
 
-namespace {
-int block_live(fdapde_ctx* c) {
-    if (!c->block || !c->block->ready || c->block->n != c->hs.n_dofs || c->block->nnz != c->hs.nnz) return fail(c, FDAPDE_ENOTINIT, "call fdapde_block_compute first");
-    return FDAPDE_OK;
-}
-// what a change of the term invalidates: the dense inverse, the multilevel hierarchy, the rent-or-buy count
-void block_matrix_changed(BlockHandle& B) {
-    B.dense.ready = B.dense.failed = false, B.expanded = false, B.cols = 0, B.krylov_ms = 0;
-    block_amg_free(B.amg), B.amg = nullptr;
-}
-}   // namespace
-
 int e_block_set_obs(fdapde_ctx* c, int64_t n_obs, const int64_t* rowptr, const int32_t* colidx, const double* values, const double* weights, double scale) {
     if (!c) return FDAPDE_EINVAL;
-    if (int rc = block_guard(c)) return rc;
-    if (int rc = block_live(c)) return rc;
+    if (int rc = handle_guard(c, kBlockWords)) return rc;
+    if (int rc = handle_live(c, c->block, kBlockWords)) return rc;
     if (n_obs < 0) return fail(c, FDAPDE_EINVAL, "fdapde_block_set_obs: n_obs is negative");
     HIPCHK(c, hipSetDevice(c->device));
     BlockHandle& B = *c->block;
@@ -340,8 +288,8 @@ int e_block_set_obs(fdapde_ctx* c, int64_t n_obs, const int64_t* rowptr, const i
 
 int e_block_obs_info(fdapde_ctx* c, int64_t* n_obs, int64_t* nnz, int32_t* team_rows, int32_t* team_cols) {
     if (!c) return FDAPDE_EINVAL;
-    if (int rc = block_guard(c)) return rc;
-    if (int rc = block_live(c)) return rc;
+    if (int rc = handle_guard(c, kBlockWords)) return rc;
+    if (int rc = handle_live(c, c->block, kBlockWords)) return rc;
     const BlockObs& O = c->block->obs;
     if (!O.live) return fail(c, FDAPDE_ENOTINIT, "fdapde_block_obs_info: no data term is live (fdapde_block_set_obs)");
     if (n_obs) *n_obs = O.host.n_obs;
@@ -353,8 +301,8 @@ int e_block_obs_info(fdapde_ctx* c, int64_t* n_obs, int64_t* nnz, int32_t* team_
 
 int e_block_amg_obs_levels(fdapde_ctx* c, int32_t cap, int32_t* n_levels, int64_t* nnz, int32_t* longest_row, int32_t* team_rows, int32_t* team_cols) {
     if (!c) return FDAPDE_EINVAL;
-    if (int rc = block_guard(c)) return rc;
-    if (int rc = block_live(c)) return rc;
+    if (int rc = handle_guard(c, kBlockWords)) return rc;
+    if (int rc = handle_live(c, c->block, kBlockWords)) return rc;
     if (!block_amg_has_term(c->block->amg))
         return fail(c, FDAPDE_ENOTINIT, "fdapde_block_obs_amg_levels: no live hierarchy carries a data term (knob block_amg_obs, fdapde_block_set_obs, a FDAPDE_SOLVER_BLOCK_AMG solve)");
     return block_amg_obs_levels(c->block->amg, cap, n_levels, nnz, longest_row, team_rows, team_cols, nullptr);
@@ -362,19 +310,19 @@ int e_block_amg_obs_levels(fdapde_ctx* c, int32_t cap, int32_t* n_levels, int64_
 
 int e_block_spmv(fdapde_ctx* c, const double* x, double* y) {
     if (!c || !x || !y) return FDAPDE_EINVAL;
-    if (int rc = block_guard(c)) return rc;
-    if (!c->block || !c->block->ready || c->block->n != c->hs.n_dofs || c->block->nnz != c->hs.nnz) return fail(c, FDAPDE_ENOTINIT, "call fdapde_block_compute first");
+    if (int rc = handle_guard(c, kBlockWords)) return rc;
+    if (int rc = handle_live(c, c->block, kBlockWords)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     BlockHandle& B = *c->block;
     hipStream_t st = c->stream;
-    const int64_t n = B.n;
-    HIPCHK(c, hipMemcpyAsync(B.ext.p, x, sizeof(double) * (size_t)(2 * n), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_block_stage, dim3(g1(n), 1), dim3(256), 0, st, n, c->dof_i2e.p, B.ext.p, nullptr, B.w.p);
+    const auto ops = block_ops(c, B);
+    HIPCHK(c, hipMemcpyAsync(B.ext.p, x, sizeof(double) * (size_t)ops.rows, hipMemcpyHostToDevice, st));
+    ops.stage(kLayoutPlain, B.ext.p, B.w.p, 1);
     launch_block_spmv(c, B.raw.p, B.w.p, B.t.p, nullptr);
     if (B.obs.live) launch_obs_term(c, B, nullptr, B.w.p, B.t.p, nullptr);
-    hipLaunchKernelGGL(k_block_unstage, dim3(g1(n), 1), dim3(256), 0, st, n, c->dof_i2e.p, B.t.p, B.ext.p);
+    ops.unstage(kLayoutPlain, B.t.p, B.ext.p, 1);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(y, B.ext.p, sizeof(double) * (size_t)(2 * n), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(y, B.ext.p, sizeof(double) * (size_t)ops.rows, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     return FDAPDE_OK;
 }
@@ -384,8 +332,8 @@ int e_block_spmv(fdapde_ctx* c, const double* x, double* y) {
 // product; the term adds (kernels_obs.h), nz = nnz(Psi), m = n_obs: gather 12 nz + 4 (m + 1) + 8 m + 8 n + 8 m, scatter 12 nz + 4 (n + 1) + 8 m + 16 n + 32 n
 int e_block_bench_spmv(fdapde_ctx* c, int32_t reps, double* avg_ms, double* algorithmic_bytes) {
     if (!c || reps < 1) return FDAPDE_EINVAL;
-    if (int rc = block_guard(c)) return rc;
-    if (!c->block || !c->block->ready || c->block->n != c->hs.n_dofs || c->block->nnz != c->hs.nnz) return fail(c, FDAPDE_ENOTINIT, "call fdapde_block_compute first");
+    if (int rc = handle_guard(c, kBlockWords)) return rc;
+    if (int rc = handle_live(c, c->block, kBlockWords)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     BlockHandle& B = *c->block;
     const int64_t n = B.n;
@@ -410,108 +358,32 @@ int e_block_bench_spmv(fdapde_ctx* c, int32_t reps, double* avg_ms, double* algo
 
 int e_block_solve(fdapde_ctx* c, const fdapde_options* opt, const double* b, int32_t n_rhs, double* x, fdapde_info* info) {
     if (!c || !b || !x || n_rhs < 1) return FDAPDE_EINVAL;
-    if (int rc = block_guard(c)) return rc;
-    if (!c->block || !c->block->ready || c->block->n != c->hs.n_dofs || c->block->nnz != c->hs.nnz) return fail(c, FDAPDE_ENOTINIT, "call fdapde_block_compute first");
+    if (int rc = handle_guard(c, kBlockWords)) return rc;
+    if (int rc = handle_live(c, c->block, kBlockWords)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     BlockHandle& B = *c->block;
-    const int64_t n = B.n, n2 = 2 * n;
-    {   // an in-place solve: finished columns are written to x while later ones still read b
-        const double *b0 = b, *b1 = b + (size_t)n2 * n_rhs, *x0 = x, *x1 = x + (size_t)n2 * n_rhs;
-        if (b0 < x1 && x0 < b1) {
-            std::vector<double> b_copy(b0, b1);
-            return e_block_solve(c, opt, b_copy.data(), n_rhs, x, info);
-        }
+    HandleCall k;
+    if (int rc = handle_call(c, kBlockWords, FDAPDE_SOLVER_BLOCK_AMG, 2 * B.n, opt, &k)) return rc;
+    if (k.amg) {
+        if (B.obs.live && !c->block_amg_obs)
+            return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_BLOCK_AMG: a factored data term (fdapde_block_set_obs) is live; the hierarchy is built from pattern entries only unless the knob block_amg_obs is 1");
+        if (!B.jacobi_ok)
+            return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_BLOCK_AMG: a DOF's diagonal block is singular (|det| <= 1e-14 max|entry|^2): no block-Jacobi smoother");
+    } else {
+        if (!k.dense_named && !k.eligible && !B.jacobi_ok)
+            return fail(c, FDAPDE_EUNSUPPORTED, "a DOF's diagonal block is singular: no block-Jacobi form for the Krylov stage, and the system is too large for the dense inverse");
+        if (k.method == FDAPDE_SOLVER_GMRES && !B.jacobi_ok)
+            return fail(c, FDAPDE_EUNSUPPORTED, "a DOF's diagonal block is singular (|det| <= 1e-14 max|entry|^2): no block-Jacobi form for the Krylov stage");
     }
-    hipStream_t st = c->stream;
-    const int method = opt ? opt->method : FDAPDE_SOLVER_AUTO;
-    const bool open = method == FDAPDE_SOLVER_AUTO, dense_named = method == FDAPDE_SOLVER_DENSE;
-    if (method == FDAPDE_SOLVER_BLOCK_AMG) return block_amg_solve(c, B, opt, b, n_rhs, x, info);
-    if (!open && !dense_named && method != FDAPDE_SOLVER_GMRES)
-        return fail(c, FDAPDE_EUNSUPPORTED, "fdapde_block_solve runs FDAPDE_SOLVER_GMRES, FDAPDE_SOLVER_DENSE, FDAPDE_SOLVER_BLOCK_AMG or the open method");
-    const double rtol = (opt && opt->rtol > 0) ? opt->rtol : 1e-10;
-    const int maxit = (opt && opt->maxit > 0) ? opt->maxit : 2000;
-    fdapde_info out{};
-    const auto t_call = std::chrono::steady_clock::now();
-    const bool eligible = block_dense_eligible(c, B);
-    if (dense_named && !eligible) return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_DENSE takes block systems of up to `dense_rows` (at most 8192) rows");
-    if (!dense_named && !eligible && !B.jacobi_ok)
-        return fail(c, FDAPDE_EUNSUPPORTED, "a DOF's diagonal block is singular: no block-Jacobi form for the Krylov stage, and the system is too large for the dense inverse");
-    if (method == FDAPDE_SOLVER_GMRES && !B.jacobi_ok)
-        return fail(c, FDAPDE_EUNSUPPORTED, "a DOF's diagonal block is singular (|det| <= 1e-14 max|entry|^2): no block-Jacobi form for the Krylov stage");
-    HIPCHK(c, B.ext.alloc((size_t)std::max<int64_t>(4 * B.nnz, 2 * n)));
-    if ((open || dense_named) && eligible) {   // the rent-or-buy rule of fdapde_lin_solve, with 2 n as the row count
-        fdapde_ctx::Dense& D = B.dense;
-        if (!D.ready && (!D.failed || dense_named) &&
-            (dense_named || !B.jacobi_ok || c->dense_after == 0 || (B.cols + n_rhs > c->dense_after && B.krylov_ms >= 0.5 * dense_build_estimate_ms(n2))))
-            if (int rc = block_dense_build(c, B)) return rc;
-        if ((dense_named || !B.jacobi_ok) && !D.ready) {
-            out.method_used = FDAPDE_SOLVER_DENSE, out.relres = D.check;
-            c->info = out;
-            if (info) *info = out;
-            c->err = "FDAPDE_SOLVER_DENSE: the block matrix is singular to working precision (no usable pivot, or max |I - A X| beyond 1e-6)";
-            return FDAPDE_ENOCONV;
-        }
-        if (D.ready) {
-            const size_t cnt = (size_t)n2 * (size_t)n_rhs;
-            HIPCHK(c, B.dn_b.alloc(cnt));
-            HIPCHK(c, B.dn_x.alloc(cnt));
-            // the columns cross in slices of the staging buffer's size, every slice one product
-            const int per = (int)std::max<int64_t>(1, (int64_t)(B.ext.n / (size_t)n2));
-            for (int j0 = 0; j0 < n_rhs; j0 += per) {
-                const int q = std::min(per, n_rhs - j0);
-                HIPCHK(c, hipMemcpyAsync(B.ext.p, b + (size_t)j0 * n2, sizeof(double) * (size_t)n2 * q, hipMemcpyHostToDevice, st));
-                hipLaunchKernelGGL(k_block_stage, dim3(g1(n), q), dim3(256), 0, st, n, c->dof_i2e.p, B.ext.p, nullptr, B.dn_b.p + (size_t)j0 * n2);
-            }
-            if (int rc = dense_apply(c, D, n_rhs, B.dn_b.p, B.dn_x.p)) return rc;
-            for (int j0 = 0; j0 < n_rhs; j0 += per) {
-                const int q = std::min(per, n_rhs - j0);
-                hipLaunchKernelGGL(k_block_unstage, dim3(g1(n), q), dim3(256), 0, st, n, c->dof_i2e.p, B.dn_x.p + (size_t)j0 * n2, B.ext.p);
-                HIPCHK(c, hipGetLastError());
-                HIPCHK(c, hipMemcpyAsync(x + (size_t)j0 * n2, B.ext.p, sizeof(double) * (size_t)n2 * q, hipMemcpyDeviceToHost, st));
-                HIPCHK(c, hipStreamSynchronize(st));
-            }
-            B.cols += n_rhs;
-            out.iters = D.refine ? 1 : 0, out.converged = 1, out.relres = D.check, out.method_used = FDAPDE_SOLVER_DENSE;
-            out.t_solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
-            c->info = out;
-            if (info) *info = out;
-            return FDAPDE_OK;
-        }
-    }
-    // Krylov stage, the columns one after another
-    B.cols += n_rhs;
-    const double tol2 = rtol * rtol;
-    int total = 0, rc_all = FDAPDE_OK;
-    double worst = 0;
-    bool broke = false;
-    for (int32_t j = 0; j < n_rhs; ++j) {
-        HIPCHK(c, hipMemcpyAsync(B.ext.p, b + (size_t)j * n2, sizeof(double) * (size_t)n2, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_block_stage, dim3(g1(n), 1), dim3(256), 0, st, n, c->dof_i2e.p, B.ext.p, B.dinv.p, B.bt.p);
-        int32_t h_ctl[4] = {0, 0, 0, 0};
-        double h_sc[4] = {0, 0, 0, 0};
-        if (int rc = block_gmres(c, B, tol2, maxit, h_ctl, h_sc)) return rc;
-        const double bb = h_sc[0], rr = h_sc[3];
-        const double rel = bb > 0 ? std::sqrt(rr / bb) : 0.0;
-        if (!(rr <= tol2 * bb && h_ctl[2] == 0)) rc_all = FDAPDE_ENOCONV, broke = broke || h_ctl[2] != 0;
-        total += h_ctl[1], worst = rel > worst ? rel : worst;
-        hipLaunchKernelGGL(k_block_unstage, dim3(g1(n), 1), dim3(256), 0, st, n, c->dof_i2e.p, B.x.p, B.ext.p);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(x + (size_t)j * n2, B.ext.p, sizeof(double) * (size_t)n2, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-    }
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
-    B.krylov_ms += ms;
-    out.iters = total, out.relres = worst, out.converged = rc_all == FDAPDE_OK ? 1 : 0, out.method_used = FDAPDE_SOLVER_GMRES, out.t_solve_ms = ms;
-    c->info = out;
-    if (info) *info = out;
-    if (rc_all == FDAPDE_ENOCONV) c->err = broke ? "GMRES stagnated or broke down in at least one column" : "maxit reached in at least one column";
-    return rc_all;
+    auto ops = block_ops(c, B);
+    if (k.amg) ops.ext_words = std::max<int64_t>(4 * B.nnz, ops.rows * kAmgColsMax);   // (a batch of columns crosses at once)
+    return handle_solve(c, B, ops, k, opt, b, n_rhs, x, info);
 }
 
 // Psi^T W Psi on the FEM pattern from the rows fdapde_eval_pointwise / fdapde_project hand out: Psi(i, dofs(cell_i, h)) = values[i nb + h]
 int e_gram_pointwise(fdapde_ctx* c, int64_t n_locs, const int32_t* cell_ids, const double* values, const double* weights, double* out_values) {
     if (!c || n_locs < 1 || !cell_ids || !values || !out_values) return FDAPDE_EINVAL;
-    if (int rc = block_guard(c)) return rc;
+    if (int rc = handle_guard(c, kBlockWords)) return rc;
     const HostSpace& hs = c->hs;
     for (int64_t k = 0; k < n_locs; ++k)
         if (cell_ids[k] < -1 || cell_ids[k] >= hs.n_cells) {

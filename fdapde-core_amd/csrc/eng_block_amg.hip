@@ -16,6 +16,8 @@
 //             correction is always two GCR steps preconditioned by the next level's cycle -- GCR because the system is indefinite (flexible CG may divide
 //             by zero), no early exit (it would need a host read-back inside the cycle).
 //   outer     fgmres_outer (eng_pmg.hip) on the UNSCALED system, right-preconditioned by the cycle; the stop rule is the true residual |b - A x| <= rtol |b|.
+//             The run of Q columns is amg_point_cols (amg_setup.h, shared with eng_kron_amg.hip) with this handle's product; the loop over a call's columns is
+//             handle_solve's (eng_handle.h), which takes block_amg_run and -- for batches -- block_amg_batch from eng_block.hip's callables.
 //   the term  (knob block_amg_obs = 1) a live factored data term scale [Psi^T W Psi, 0; 0, 0] rides beside the pattern levels: P = P_s (x) I_2 with entries 1, so
 //             its Galerkin product is the term of Psi_{l+1} = Psi_l P_s (host_obs.h obs_coarsen: the same rows, columns through agg).  The aggregates do not see
 //             it.  Its diagonal share g_l joins D_l; the coarsest level is inverted with the term merged in (obs_merge_dense); the cycle's launches add the
@@ -43,9 +45,6 @@ namespace {
 using namespace fdapde_hip;
 
 constexpr double kBamgOmega = 0.7;   // the smoother's damping: fixed (the spectrum of D^-1 A is not one-sided: no power iteration)
-constexpr int kBamgMaxRestart = 64;  // fgmres_outer's Gram-Schmidt kernels hold that many coefficients
-// the restart length of the outer iteration: the knob gmres_m, never more than maxit -- one rule for the single-column run and for a batch
-inline int block_restart_len(const fdapde_ctx* c, int maxit) { return std::max(1, std::min(std::min(c->gmres_m, kBamgMaxRestart), std::max(maxit, 1))); }
 
 // a level: the scalar level (n block rows; a = the strength matrix on the pattern; agg, mptr, midx; team, np; the work vectors at 2 n words) and its blocks
 // a level's share of a carried data term: Psi_l and its transpose on the device (level 0: the handle's arrays; below: obs_coarsen's, kept on the host too)
@@ -87,13 +86,6 @@ void term_scatter_store(hipStream_t st, const BamgTerm& O, int64_t n, const doub
     else hipLaunchKernelGGL(k_obs_scatter_store<8>, dim3(g1(n, 32)), dim3(256), 0, st, n, O.trp, O.tci, O.tv, t, scale, s);
 }
 }   // namespace
-
-struct BlockAmg : AmgHierarchy {   // (D: 2 n_L rows; the coarse corrections are GCR steps)
-    DBuf<int32_t> rp2, ci2;
-    DBuf<double> val2;
-    bool term = false;             // the levels carry the handle's factored data term (knob block_amg_obs): one column at a time
-    double term_ms = 0.0;          // ... and what attaching it cost (part of setup_ms): the host's coarsening, the uploads, g_l
-};
 
 void block_amg_free(BlockAmg* h) { delete h; }
 
@@ -308,17 +300,6 @@ int block_amg_build(fdapde_ctx* c, BlockAmg** slot, const double* raw, int stren
     return amg_build_retry(c, slot, [&](int absorb, bool* stalled) { return block_amg_build_pass(c, slot, raw, strength_block, term, absorb, stalled); });
 }
 
-int block_amg_describe(const BlockAmg* H, int32_t cap, int32_t* n_levels, int64_t* rows, int64_t* nnz, int32_t* absorbed, double* setup_ms) {
-    return amg_describe(H, cap, n_levels, rows, nnz, absorbed, setup_ms);   // (rows 2 n_l, entries 4 nnz_l: per = 2)
-}
-
-// fdapde_amg_aggregates / fdapde_amg_damping / fdapde_amg_order for the block handle: the levels are AmgLevel, the answers amg_aggregates' / amg_damping's (eng_amg.hip)
-int block_amg_aggregates(fdapde_ctx* c, const BlockAmg* H, int32_t level, int64_t cap, int32_t* agg, int64_t* n_rows) {
-    return amg_aggregates(c, H, level, cap, agg, n_rows);
-}
-int block_amg_damping(const BlockAmg* H, int32_t cap, int32_t* n_levels, double* omega) { return amg_damping(H, cap, n_levels, omega); }
-int block_amg_order(fdapde_ctx* c, const BlockAmg* H, int64_t cap, int32_t* order, int64_t* n_rows) { return amg_order(c, H, cap, order, n_rows); }
-
 // fdapde_block_obs_amg_levels: the carried term level by level
 int block_amg_obs_levels(const BlockAmg* H, int32_t cap, int32_t* n_levels, int64_t* nnz, int32_t* longest_row, int32_t* team_rows, int32_t* team_cols, double* term_ms) {
     if (!H || !H->term) return FDAPDE_ENOTINIT;
@@ -335,28 +316,16 @@ int block_amg_obs_levels(const BlockAmg* H, int32_t cap, int32_t* n_levels, int6
 }
 bool block_amg_has_term(const BlockAmg* H) { return H && H->term; }
 
-int block_amg_cols_trace(const BlockAmg* H, int32_t* batches, int32_t* batched_cols, int32_t* single_cols) { return amg_cols_trace(H, batches, batched_cols, single_cols); }
-void block_amg_count_single(BlockAmg* H) { ++H->single_cols; }
 
 namespace {
-// One run against the hierarchy for Q columns side by side: A x = b per column (b, x: 2 n Q words, the columns interleaved as in kernels_cols.h, internal order,
-// on the device; x is written -- warm: x holds the iterates to start from; r, t: scratch of the same size), raw = the matrix the hierarchy was built from.  The
-// outer iteration is fgmres_outer at width Q; what is handed out is judged by its own residual: S.converged, and rel = |b - A x| / |b| per column.
-// block_amg_run is the call at Q = 1, block_amg_batch drives those at Q = 2, 4, 8
+// Q columns side by side against the hierarchy: amg_point_cols (amg_setup.h) with the product of the matrix the hierarchy was built from (raw, and the carried
+// term).  block_amg_run is the call at Q = 1, block_amg_batch drives those at Q = 2, 4, 8
 int block_amg_cols(fdapde_ctx* c, BlockAmg& H, const double* raw, int Q, const double* b, double* x, double* r, double* t, bool warm, double rtol, int maxit,
                    FgmresCols& S, double* rel) {
     hipStream_t st = c->stream;
     AmgLevel& L0 = *H.lv[0];
-    const int64_t n = L0.n, n2 = 2 * n;
-    const size_t nq = (size_t)n2 * (size_t)Q;
-    const int np = (int)std::min<int64_t>(1024, std::max<int64_t>(1, (n2 + 4095) / 4096));
-    const int mk = block_restart_len(c, maxit);
-    if (int rc = amg_cols_prepare(c, H, Q)) return rc;
-    HIPCHK(c, H.basis.alloc((size_t)(2 * mk + 1) * nq));
-    HIPCHK(c, H.part.alloc((size_t)Q * ((size_t)(mk + 2) * (size_t)np + 3 * (size_t)np)));
-    HIPCHK(c, H.dots.alloc((size_t)Q * (size_t)(mk + 4)));
-    double h[kAmgColsMax];
-    auto spmv = [&](const double* in, double* out) {   // (one column: the block handle's own kernel)
+    const int64_t n = L0.n;
+    return amg_point_cols(c, H, Q, [&](const double* in, double* out) {   // (one column: the block handle's own kernel)
         if (Q == 1) {
             hipLaunchKernelGGL(k_block_spmv<kBlockTeam>, dim3(g1(n, 256 / kBlockTeam)), dim3(256), 0, st, n, L0.rp, L0.ci, raw, in, out, (const int32_t*)nullptr);
             if (BamgTerm* O = blk(L0).term.get()) {   // ... and the term's two products behind it
@@ -370,53 +339,7 @@ int block_amg_cols(fdapde_ctx* c, BlockAmg& H, const double* raw, int Q, const d
             if constexpr (QC > 1)
                 hipLaunchKernelGGL((k_block_spmv_cols<kBlockTeam, QC>), dim3(g1(n, 256 / kBlockTeam)), dim3(256), 0, st, n, L0.rp, L0.ci, raw, in, out);
         });
-    };
-    auto dots = [&](const double* a0) -> int {
-        fixed_dots_cols(st, n2, np, Q, a0, a0, H.part.p, H.dots.p);
-        HIPCHK(c, hipMemcpyAsync(h, H.dots.p, sizeof(double) * (size_t)Q, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        return FDAPDE_OK;
-    };
-    auto residual = [&](double* rr_out) -> int {   // the TRUE residuals of the iterates
-        spmv(x, t);
-        hipLaunchKernelGGL(k_bamg_residual, dim3(gn((int64_t)nq)), dim3(256), 0, st, (int64_t)nq, b, (const double*)t, r);
-        if (int rc = dots(r)) return rc;
-        std::copy(h, h + Q, rr_out);
-        return FDAPDE_OK;
-    };
-    if (!warm) HIPCHK(c, hipMemsetAsync(x, 0, sizeof(double) * nq, st));
-    HIPCHK(c, hipMemcpyAsync(r, b, sizeof(double) * nq, hipMemcpyDeviceToDevice, st));
-    if (int rc = dots(r)) return rc;
-    bool live = false;   // a column that starts (0 < |b|^2 < inf), and is judged by its own residual at the end
-    for (int q = 0; q < Q; ++q) {
-        S.bb[q] = S.rr[q] = h[q], S.converged[q] = !(h[q] > 0.0) && std::isfinite(h[q]), S.broke[q] = !std::isfinite(h[q]);
-        live = live || (h[q] > 0.0 && std::isfinite(h[q]));
-    }
-    if (warm && live) {   // (a column a batch handed back: the residual of its iterate starts the first cycle)
-        if (int rc = residual(S.rr)) return rc;
-        for (int q = 0; q < Q; ++q)
-            if (!std::isfinite(S.rr[q])) S.broke[q] = true;
-    }
-    const bool one_level = H.lv.size() == 1;
-    auto precond = [&](const double* v, double* z, double* w, bool&) -> int {
-        if (one_level) {
-            if (int rc = amg_dense_cols(c, H, Q, v, z)) return rc;
-        } else if (int rc = amg_cycle(c, H, 0, Q, v, z))
-            return rc;
-        spmv(z, w);
-        return FDAPDE_OK;
-    };
-    FgmresSpace fs{n2, mk, H.basis.p, H.basis.p + (size_t)(mk + 1) * nq, H.part.p, H.dots.p, np};
-    if (int rc = fgmres_outer(c, fs, Q, x, r, nullptr, rtol, maxit, precond, residual, S)) return rc;
-    double rr[kAmgColsMax];
-    if (live)   // what is handed out is judged by its own residual, whichever way the loop ended
-        if (int rc = residual(rr)) return rc;
-    for (int q = 0; q < Q; ++q) {
-        if (S.bb[q] > 0.0 && std::isfinite(S.bb[q])) S.rr[q] = rr[q], S.converged[q] = std::isfinite(rr[q]) && rr[q] <= rtol * rtol * S.bb[q];
-        rel[q] = S.bb[q] > 0.0 ? std::sqrt(S.rr[q] / S.bb[q]) : 0.0;
-    }
-    HIPCHK(c, hipGetLastError());
-    return FDAPDE_OK;
+    }, b, x, r, t, warm, rtol, maxit, S, rel);
 }
 }   // namespace
 
@@ -433,7 +356,7 @@ int block_amg_run(fdapde_ctx* c, BlockAmg* hp, const double* raw, const double* 
 
 // the widest batch for `left` columns under the knob amg_cols and the basis budget (amg_cols_width); block_amg_run's restart length is kept
 int block_amg_width(const fdapde_ctx* c, const BlockAmg* H, int32_t left, int maxit) {
-    const int mk = block_restart_len(c, maxit);
+    const int mk = amg_point_restart_len(c, maxit);
     if (H->term) return 1;   // (the term's launches are one column's)
     return amg_cols_width(std::min<int32_t>(left, c->amg_cols), 2 * H->lv[0]->n, mk);
 }

@@ -96,6 +96,7 @@ int dense_build_csr(fdapde_ctx* c, int64_t n, const int32_t* rowptr, const int32
     HIPCHK(c, worst.alloc(2));
     HIPCHK(c, hipMemsetAsync(cand.p, 0, 2 * (size_t)G * sizeof(unsigned long long), st));
     HIPCHK(c, hipMemsetAsync(status.p, 0, 4 * sizeof(int32_t), st));
+    HIPCHK(c, hipMemsetAsync(perm.p, 0, (size_t)n * sizeof(int32_t), st));   // (an inversion that ends without a usable pivot leaves the rest of the pivot sequence unwritten: k_dense_unpermute indexes with all of it)
     HIPCHK(c, hipMemsetAsync(worst.p, 0, 2 * sizeof(unsigned long long), st));
     hipLaunchKernelGGL(k_dense_fill, dim3((unsigned)n), dim3(256), 0, st, n, ld, rowptr, colidx, A, bnd, use_bnd, S.p, rs.p);
     const double* result = S.p;

@@ -3,7 +3,8 @@
 // separable smoothing system and the monolithic parabolic system, kept as factors (kernels_kron.h).
 //   fdapde_kron_compute      terms -> n_S distinct spatial factors interleaved per pattern entry in the internal order, the summed time factors, D_i^-1
 //   fdapde_kron_solve        restarted GMRES(m) on D^-1 A (kernels_gmres.h, buffers of the handle's own), or the dense inverse of the q n-row matrix, or
-//                            (by name) flexible GMRES around the point-block multilevel cycle of eng_kron_amg.hip
+//                            (by name) flexible GMRES around the point-block multilevel cycle of eng_kron_amg.hip.  The stages, the column loop and the
+//                            ending are handle_solve's (eng_handle.h, shared with eng_block.hip); here: the refusals and kron_ops -- staging, operator, builds
 //   fdapde_kron_spmv         y = A x
 //   fdapde_kron_bench_spmv   HIP-event timing of the Krylov stage's operator
 //   fdapde_kron_set_obs      the data term kept factored: the handle's matrix becomes A + scale (Phi (x) Psi)^T W (Phi (x) Psi) with Phi small and dense, Psi a
@@ -17,9 +18,10 @@
 #include <type_traits>
 #include <vector>
 
+#include "amg_setup.h"
 #include "context.h"
 #include "engine.h"
-#include "eng_gmres.h"
+#include "eng_handle.h"
 #include "host_kron.h"
 #include "host_kron_obs.h"
 #include "kernels_dense.h"
@@ -42,24 +44,12 @@ struct KronObs {
     DBuf<double> v, tv, w, phi, t, g;   // t [n_obs p]: W (Phi (x) Psi) x between the two products; g [n p]: the term's share of every diagonal block
 };
 
-struct KronHandle {
-    bool ready = false, symmetric = false;
+struct KronHandle : HandleCore {       // (the vectors at q n words, ext at least max(n_S nnz, q n), the dense stage on q n rows; jacobi_ok implies have_dinv)
     bool have_dinv = false;            // D^-1 fits the budget (knob kron_dinv_mb) and was built
-    bool jacobi_ok = false;            // ... and every diagonal block was invertible: the Krylov stage is available
     bool t_in_lds = false;             // the time factors are small enough to be copied into LDS by every workgroup of the product (kKronLdsFactorDoubles)
     int q = 0, ns = 0, Q = 2;          // unknowns per DOF, distinct spatial factors, team width
-    int64_t n = 0, nnz = 0;            // the space the handle was computed on
     DBuf<double> vals, tm, dinv;       // [n_S nnz] spatial values, [n_S q q] time factors, [q q n] inverted diagonal blocks
     DBuf<int32_t> band;                // [2 q] first / last non-zero column of every T-row
-    DBuf<double> ext;                  // staging: factors / columns in the reference numbering
-    DBuf<double> bt, x, r, w, t, sc, gm_V, gm_s, gm_part;
-    DBuf<int32_t> ctl, flag;
-    DBuf<int32_t> rowptr2, colidx2;    // the q n-row CSR form (dense stage), built on first use
-    DBuf<double> val2, dn_b, dn_x;
-    bool expanded = false;
-    fdapde_ctx::Dense dense;
-    int64_t cols = 0;                  // columns solved against the current matrix
-    double krylov_ms = 0;              // ... and the host time the Krylov columns among them took
     int n_terms = 0, term_sg[kKronMaxTerms] = {};   // the spatial factor every term of the caller's went into
     double tnorm[kKronMaxTerms] = {};  // |T_sigma|_F of the summed time factors (entries in storage order)
     KronAmg* amg = nullptr;            // FDAPDE_SOLVER_KRON_AMG's hierarchy of the current matrix (eng_kron_amg.hip), built by its first solve
@@ -85,25 +75,24 @@ void kron_amg_forget(fdapde_ctx* c) {
     }
     kron_amg_free(c->kron->amg), c->kron->amg = nullptr;
 }
+// fdapde_kron_amg_hierarchy / _aggregates: the answers of eng_amg.hip on the hierarchy's base (rows q n_l, entries q^2 nnz_l: per = q)
 int kron_amg_describe_ctx(const fdapde_ctx* c, int32_t cap, int32_t* n_levels, int64_t* rows, int64_t* nnz, int32_t* absorbed, double* setup_ms) {
-    return kron_amg_describe(c->kron ? c->kron->amg : nullptr, cap, n_levels, rows, nnz, absorbed, setup_ms);
+    return amg_describe(c->kron ? c->kron->amg : nullptr, cap, n_levels, rows, nnz, absorbed, setup_ms);
 }
 int kron_amg_aggregates_ctx(fdapde_ctx* c, int32_t level, int64_t cap, int32_t* agg, int64_t* n_rows) {
-    return kron_amg_aggregates(c, c->kron ? c->kron->amg : nullptr, level, cap, agg, n_rows);
+    return amg_aggregates(c, c->kron ? c->kron->amg : nullptr, level, cap, agg, n_rows);
 }
 
 namespace {
 
-const char* const kKronFirst = "call fdapde_kron_compute first";
-
-int kron_guard(fdapde_ctx* c) {
-    if (int rc = need_device(c)) return rc;
-    if (c->comm != nullptr || c->ar_fn != nullptr || c->halo_ready || c->rd.ready)
-        return fail(c, FDAPDE_EUNSUPPORTED, "the Kronecker-sum handle takes one-GPU contexts, not a rank of a multi-GPU job");
-    if (!c->dev_ready) return fail(c, FDAPDE_ENOTINIT, "call fdapde_dofs_build first");
-    return FDAPDE_OK;
-}
-bool kron_live(const fdapde_ctx* c) { return c->kron && c->kron->ready && c->kron->n == c->hs.n_dofs && c->kron->nnz == c->hs.nnz; }
+constexpr HandleWords kKronWords{
+    "the Kronecker-sum handle takes one-GPU contexts, not a rank of a multi-GPU job",
+    "call fdapde_kron_compute first",
+    "fdapde_kron_solve runs FDAPDE_SOLVER_GMRES, FDAPDE_SOLVER_DENSE, FDAPDE_SOLVER_KRON_AMG or the open method",
+    "FDAPDE_SOLVER_DENSE takes Kronecker systems of up to `dense_rows` (at most 8192) rows",
+    "the Kronecker matrix",   // (dense_singular's `what`)
+    "FDAPDE_SOLVER_KRON_AMG: the flexible GMRES broke down in at least one column",
+    "FDAPDE_SOLVER_KRON_AMG: maxit reached in at least one column"};
 
 int team_width(int q) {
     int Q = 2;
@@ -115,37 +104,21 @@ int team_width(int q) {
 void launch_kron_spmv(fdapde_ctx* c, const KronHandle& K, bool fuse, const double* x, double* y, const int32_t* stop) {
     const size_t lds = sizeof(double) * kron_spmv_lds_doubles(K.q, K.ns, fuse, K.t_in_lds);
     const dim3 grid(g1(K.n, 256 / K.Q)), block(256);
-#define FDAPDE_KRON_SPMV(QQ)                                                                                                                                   \
-    case QQ:                                                                                                                                                   \
-        if (fuse)                                                                                                                                              \
-            hipLaunchKernelGGL((k_kron_spmv<QQ, true>), grid, block, lds, c->stream, K.n, K.q, K.ns, c->rowptr.p, c->colidx.p, K.vals.p, K.tm.p, K.band.p,     \
-                               K.dinv.p, x, y, stop, K.t_in_lds ? 1 : 0);                                                                                      \
-        else                                                                                                                                                   \
-            hipLaunchKernelGGL((k_kron_spmv<QQ, false>), grid, block, lds, c->stream, K.n, K.q, K.ns, c->rowptr.p, c->colidx.p, K.vals.p, K.tm.p, K.band.p,    \
-                               (const double*)nullptr, x, y, stop, K.t_in_lds ? 1 : 0);                                                                        \
-        break;
-    switch (K.Q) {
-        FDAPDE_KRON_SPMV(2)
-        FDAPDE_KRON_SPMV(4)
-        FDAPDE_KRON_SPMV(8)
-        FDAPDE_KRON_SPMV(16)
-        FDAPDE_KRON_SPMV(32)
-        FDAPDE_KRON_SPMV(64)
-    }
-#undef FDAPDE_KRON_SPMV
+    by_team(K.Q, [&](auto t) {
+        constexpr int QQ = decltype(t)::value;
+        if (fuse)
+            hipLaunchKernelGGL((k_kron_spmv<QQ, true>), grid, block, lds, c->stream, K.n, K.q, K.ns, c->rowptr.p, c->colidx.p, K.vals.p, K.tm.p, K.band.p, K.dinv.p, x, y, stop,
+                               K.t_in_lds ? 1 : 0);
+        else
+            hipLaunchKernelGGL((k_kron_spmv<QQ, false>), grid, block, lds, c->stream, K.n, K.q, K.ns, c->rowptr.p, c->colidx.p, K.vals.p, K.tm.p, K.band.p,
+                               (const double*)nullptr, x, y, stop, K.t_in_lds ? 1 : 0);
+    });
 }
 
 // y_i = D_i^-1 x_i (y may be x)
 void launch_kron_dinv(fdapde_ctx* c, const KronHandle& K, const double* x, double* y, const int32_t* stop) {
     const dim3 grid(g1(K.n, 256 / K.Q)), block(256);
-    switch (K.Q) {
-    case 2: hipLaunchKernelGGL(k_kron_dinv_apply<2>, grid, block, 0, c->stream, K.n, K.q, K.dinv.p, x, y, stop); break;
-    case 4: hipLaunchKernelGGL(k_kron_dinv_apply<4>, grid, block, 0, c->stream, K.n, K.q, K.dinv.p, x, y, stop); break;
-    case 8: hipLaunchKernelGGL(k_kron_dinv_apply<8>, grid, block, 0, c->stream, K.n, K.q, K.dinv.p, x, y, stop); break;
-    case 16: hipLaunchKernelGGL(k_kron_dinv_apply<16>, grid, block, 0, c->stream, K.n, K.q, K.dinv.p, x, y, stop); break;
-    case 32: hipLaunchKernelGGL(k_kron_dinv_apply<32>, grid, block, 0, c->stream, K.n, K.q, K.dinv.p, x, y, stop); break;
-    case 64: hipLaunchKernelGGL(k_kron_dinv_apply<64>, grid, block, 0, c->stream, K.n, K.q, K.dinv.p, x, y, stop); break;
-    }
+    by_team(K.Q, [&](auto t) { hipLaunchKernelGGL(k_kron_dinv_apply<decltype(t)::value>, grid, block, 0, c->stream, K.n, K.q, K.dinv.p, x, y, stop); });
 }
 
 // (with a data term live: its share Phi^T diag(g_i) Phi joins D_i)
@@ -153,31 +126,9 @@ void launch_kron_diag_inv(fdapde_ctx* c, KronHandle& K) {
     const dim3 grid(g1(K.n, 64 / K.Q)), block(64);
     const double *g = K.obs.live ? K.obs.g.p : nullptr, *phi = K.obs.live ? K.obs.phi.p : nullptr;
     const int p = K.obs.live ? K.obs.p : 0;
-#define FDAPDE_KRON_DIAG(QQ)                                                                                                                                   \
-    case QQ:                                                                                                                                                   \
-        hipLaunchKernelGGL(k_kron_diag_inv<QQ>, grid, block, 0, c->stream, K.n, K.q, K.ns, c->rowptr.p, c->colidx.p, K.vals.p, K.tm.p, g, phi, p, K.dinv.p,    \
-                           K.flag.p);                                                                                                                          \
-        break;
-    switch (K.Q) {
-        FDAPDE_KRON_DIAG(2)
-        FDAPDE_KRON_DIAG(4)
-        FDAPDE_KRON_DIAG(8)
-        FDAPDE_KRON_DIAG(16)
-        FDAPDE_KRON_DIAG(32)
-        FDAPDE_KRON_DIAG(64)
-    }
-#undef FDAPDE_KRON_DIAG
-}
-
-template <typename F> void by_obs_team(int QP, F&& f) {
-    switch (QP) {
-    case 2: f(std::integral_constant<int, 2>{}); break;
-    case 4: f(std::integral_constant<int, 4>{}); break;
-    case 8: f(std::integral_constant<int, 8>{}); break;
-    case 16: f(std::integral_constant<int, 16>{}); break;
-    case 32: f(std::integral_constant<int, 32>{}); break;
-    case 64: f(std::integral_constant<int, 64>{}); break;
-    }
+    by_team(K.Q, [&](auto t) {
+        hipLaunchKernelGGL(k_kron_diag_inv<decltype(t)::value>, grid, block, 0, c->stream, K.n, K.q, K.ns, c->rowptr.p, c->colidx.p, K.vals.p, K.tm.p, g, phi, p, K.dinv.p, K.flag.p);
+    });
 }
 
 // y += [D^-1] scale (Phi (x) Psi)^T W (Phi (x) Psi) x (dinv = NULL: without D^-1) behind a product that wrote y: two launches, the forms as chosen per matrix
@@ -185,7 +136,7 @@ void launch_kron_obs(fdapde_ctx* c, const KronHandle& K, const double* dinv, con
     const KronObs& O = K.obs;
     const int64_t m = O.host.n_obs, n = K.n;
     hipStream_t st = c->stream;
-    by_obs_team(O.QP, [&](auto t) {
+    by_team(O.QP, [&](auto t) {
         constexpr int QP = decltype(t)::value;
         if (O.form_rows == 2)
             hipLaunchKernelGGL((k_kron_obs_gather<QP, true>), dim3((unsigned)m), dim3(256), 0, st, m, K.q, O.p, O.rp.p, O.ci.p, O.v.p, O.phi.p, O.w.p, x, O.t.p, stop);
@@ -229,17 +180,6 @@ int kron_rediag(fdapde_ctx* c, KronHandle& K) {
     return FDAPDE_OK;
 }
 
-// restarted GMRES(m) on D^-1 A z = D^-1 b for the column staged in K.bt: handle_gmres (eng_gmres.h) over q n words
-int kron_gmres(fdapde_ctx* c, KronHandle& K, double tol2, int maxit, int32_t h_ctl[4], double h_sc[4]) {
-    return handle_gmres(c, HandleGmresWork{K.bt, K.x, K.r, K.w, K.t, K.sc, K.gm_V, K.gm_s, K.gm_part, K.ctl}, (int64_t)K.q * K.n,
-                        [&](const double* x, double* y, const int32_t* stop) { launch_kron_op(c, K, x, y, stop); }, tol2, maxit, h_ctl, h_sc);
-}
-
-bool kron_dense_eligible(const fdapde_ctx* c, const KronHandle& K) {
-    const int64_t nq = (int64_t)K.q * K.n;
-    return c->dense_rows > 0 && nq <= c->dense_rows && nq <= kDenseMaxRows;
-}
-
 int kron_dense_build(fdapde_ctx* c, KronHandle& K) {
     const int64_t nq = (int64_t)K.q * K.n, nnz2 = (int64_t)K.q * K.q * K.nnz;
     if (K.obs.live) {   // the term merged into the expanded matrix by the host (set-up): build and refinement see the true matrix
@@ -275,63 +215,48 @@ int kron_dense_build(fdapde_ctx* c, KronHandle& K) {
     return dense_build_csr(c, nq, K.rowptr2.p, K.colidx2.p, K.val2.p, nullptr, 0, K.dense);
 }
 
-// FDAPDE_SOLVER_KRON_AMG by name: the hierarchy built by the first such solve after fdapde_kron_compute, the columns one after another on the UNSCALED
-// system (stop rule: the true residual |b - A x| <= rtol |b| -- not the D^-1-scaled one of the GMRES stage)
-int kron_amg_solve(fdapde_ctx* c, KronHandle& K, const fdapde_options* opt, const double* b, int32_t n_rhs, double* x, fdapde_info* info) {
+// what a change of the term invalidates: handle_matrix_changed's and the multilevel hierarchy
+void kron_matrix_changed(KronHandle& K) {
+    handle_matrix_changed(K);
+    kron_amg_free(K.amg), K.amg = nullptr;
+}
+
+// What handle_solve (eng_handle.h) and fdapde_kron_spmv take from this handle.  Staging: a DOF's q unknowns together (strides q, 1) in the internal order, D^-1
+// behind it in place for the Krylov stage; the dense stage's order is the expanded matrix's (strides 1, n).  FDAPDE_SOLVER_KRON_AMG: the hierarchy built by
+// the first such solve after fdapde_kron_compute, the columns one after another on the UNSCALED system (stop rule: the true residual |b - A x| <= rtol |b|)
+auto kron_ops(fdapde_ctx* c, KronHandle& K) {
     const int64_t n = K.n, nq = (int64_t)K.q * n;
     hipStream_t st = c->stream;
-    const double rtol = (opt && opt->rtol > 0) ? opt->rtol : 1e-10;
-    const int maxit = (opt && opt->maxit > 0) ? opt->maxit : 200;
-    fdapde_info out{};
-    out.method_used = FDAPDE_SOLVER_KRON_AMG;
-    const auto t_call = std::chrono::steady_clock::now();
-    if (K.obs.live)
-        return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_KRON_AMG: a factored data term (fdapde_kron_set_obs) is live; the hierarchy is built from pattern entries only");
-    if (!K.have_dinv)
-        return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_KRON_AMG: the inverted diagonal blocks (8 q^2 n bytes) exceed the budget `kron_dinv_mb`: no block-Jacobi smoother");
-    if (!K.jacobi_ok)
-        return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_KRON_AMG: a DOF's diagonal block is singular (a pivot <= 1e-14 max|entry|): no block-Jacobi smoother");
-    if (!K.amg) {
-        if (c->kron_amg_term >= K.n_terms) return fail(c, FDAPDE_EINVAL, "FDAPDE_SOLVER_KRON_AMG: the knob `kron_amg_term` names a term the handle was not given");
-        KronAmgSource src{K.q, K.ns, K.Q, K.t_in_lds, K.vals.p, K.tm.p, K.dinv.p, K.band.p, {}, c->kron_amg_term < 0 ? -1 : K.term_sg[c->kron_amg_term]};
-        std::copy(K.tnorm, K.tnorm + kKronMaxTerms, src.tnorm);
-        if (int rc = kron_amg_build(c, &K.amg, src)) {
-            c->info = out;
-            if (info) *info = out;
-            return rc;
-        }
-    }
-    HIPCHK(c, K.ext.alloc((size_t)std::max<int64_t>((int64_t)K.ns * K.nnz, nq)));
-    int total = 0, rc_all = FDAPDE_OK;   // (K.cols and K.krylov_ms stay: the open method's rent-or-buy rule counts its own columns only)
-    double worst = 0;
-    bool broke_any = false;
-    for (int32_t j = 0; j < n_rhs; ++j) {
-        HIPCHK(c, hipMemcpyAsync(K.ext.p, b + (size_t)j * nq, sizeof(double) * (size_t)nq, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_kron_stage, dim3(g1(nq), 1), dim3(256), 0, st, n, K.q, c->dof_i2e.p, K.ext.p, K.bt.p, (int64_t)K.q, (int64_t)1);
-        int it = 0;
-        double rel = 0;
-        bool conv = false, broke = false;
-        if (int rc = kron_amg_run(c, K.amg, K.bt.p, K.x.p, rtol, maxit, &it, &rel, &conv, &broke)) return rc;
-        if (!conv) rc_all = FDAPDE_ENOCONV, broke_any = broke_any || broke;
-        total += it, worst = rel > worst || std::isnan(rel) ? rel : worst;
-        hipLaunchKernelGGL(k_kron_unstage, dim3(g1(nq), 1), dim3(256), 0, st, n, K.q, c->dof_i2e.p, K.x.p, K.ext.p, (int64_t)K.q, (int64_t)1);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(x + (size_t)j * nq, K.ext.p, sizeof(double) * (size_t)nq, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-    }
-    out.iters = total, out.relres = worst, out.converged = rc_all == FDAPDE_OK ? 1 : 0, out.persistent = 0;
-    out.t_solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
-    c->info = out;
-    if (info) *info = out;
-    if (rc_all == FDAPDE_ENOCONV) c->err = broke_any ? "FDAPDE_SOLVER_KRON_AMG: the flexible GMRES broke down in at least one column" : "FDAPDE_SOLVER_KRON_AMG: maxit reached in at least one column";
-    return rc_all;
+    return HandleOps{
+        kKronWords, FDAPDE_SOLVER_KRON_AMG, nq, std::max<int64_t>((int64_t)K.ns * K.nnz, nq),
+        [c, &K, n, nq, st](HandleLayout layout, const double* ext, double* dst, int ncols) {
+            const bool dense = layout == kLayoutDense;
+            hipLaunchKernelGGL(k_kron_stage, dim3(g1(nq), ncols), dim3(256), 0, st, n, K.q, c->dof_i2e.p, ext, dst, dense ? (int64_t)1 : (int64_t)K.q, dense ? n : (int64_t)1);
+            if (layout == kLayoutKrylov) launch_kron_dinv(c, K, dst, dst, nullptr);
+        },
+        [c, &K, n, nq, st](HandleLayout layout, const double* src, double* ext, int ncols) {
+            const bool dense = layout == kLayoutDense;
+            hipLaunchKernelGGL(k_kron_unstage, dim3(g1(nq), ncols), dim3(256), 0, st, n, K.q, c->dof_i2e.p, src, ext, dense ? (int64_t)1 : (int64_t)K.q, dense ? n : (int64_t)1);
+        },
+        [c, &K](const double* x, double* y, const int32_t* stop) { launch_kron_op(c, K, x, y, stop); },
+        [c, &K] { return kron_dense_build(c, K); },
+        [c, &K] {
+            if (K.amg) return (int)FDAPDE_OK;
+            KronAmgSource src{K.q, K.ns, K.Q, K.t_in_lds, K.vals.p, K.tm.p, K.dinv.p, K.band.p, {}, c->kron_amg_term < 0 ? -1 : K.term_sg[c->kron_amg_term]};
+            std::copy(K.tnorm, K.tnorm + kKronMaxTerms, src.tnorm);
+            return kron_amg_build(c, &K.amg, src);
+        },
+        [c, &K](const double* b, double* x, double rtol, int maxit, int* it, double* rel, bool* conv, bool* broke) {
+            return kron_amg_run(c, K.amg, b, x, rtol, maxit, it, rel, conv, broke);
+        },
+        nullptr};
 }
 
 }   // namespace
 
 int e_kron_compute(fdapde_ctx* c, int32_t q, int32_t n_terms, const double* const* T, const double* const* S, int32_t symmetric) {
     if (!c) return FDAPDE_EINVAL;
-    if (int rc = kron_guard(c)) return rc;
+    if (int rc = handle_guard(c, kKronWords)) return rc;
     if (q < 1 || q > kKronMaxQ) return fail(c, FDAPDE_EINVAL, "fdapde_kron_compute: q must lie in 1 .. 64");
     if (n_terms < 1 || n_terms > kKronMaxTerms) return fail(c, FDAPDE_EINVAL, "fdapde_kron_compute: n_terms must lie in 1 .. 8");
     if (!T || !S) return fail(c, FDAPDE_EINVAL, "fdapde_kron_compute: a NULL factor");
@@ -368,8 +293,8 @@ int e_kron_compute(fdapde_ctx* c, int32_t q, int32_t n_terms, const double* cons
         K.rowptr2.release(), K.colidx2.release();
     }
     K.obs.live = false;   // (the data term belonged to the previous matrix)
-    K.ready = false, K.expanded = false, K.n = n, K.nnz = nnz, K.q = q, K.ns = ns, K.Q = team_width(q), K.symmetric = symmetric != 0;
-    K.dense.ready = K.dense.failed = false, K.cols = 0, K.krylov_ms = 0, K.jacobi_ok = false;
+    K.ready = false, K.n = n, K.nnz = nnz, K.q = q, K.ns = ns, K.Q = team_width(q), K.symmetric = symmetric != 0, K.jacobi_ok = false;
+    handle_matrix_changed(K);
     K.t_in_lds = ns * q * q <= kKronLdsFactorDoubles;
     K.have_dinv = 8.0 * (double)q * (double)q * (double)n <= (double)c->kron_dinv_mb * 1048576.0;
     HIPCHK(c, K.ext.alloc((size_t)std::max<int64_t>((int64_t)ns * nnz, nq)));
@@ -395,19 +320,11 @@ int e_kron_compute(fdapde_ctx* c, int32_t q, int32_t n_terms, const double* cons
     return FDAPDE_OK;
 }
 
-namespace {
-// what a change of the term invalidates: the dense inverse, the expanded matrix, the multilevel hierarchy, the rent-or-buy count
-void kron_matrix_changed(KronHandle& K) {
-    K.dense.ready = K.dense.failed = false, K.expanded = false, K.cols = 0, K.krylov_ms = 0;
-    kron_amg_free(K.amg), K.amg = nullptr;
-}
-}   // namespace
-
 int e_kron_set_obs(fdapde_ctx* c, int32_t p, const double* Phi, int64_t n_obs, const int64_t* rowptr, const int32_t* colidx, const double* values,
                    const double* weights, double scale) {
     if (!c) return FDAPDE_EINVAL;
-    if (int rc = kron_guard(c)) return rc;
-    if (!kron_live(c)) return fail(c, FDAPDE_ENOTINIT, kKronFirst);
+    if (int rc = handle_guard(c, kKronWords)) return rc;
+    if (int rc = handle_live(c, c->kron, kKronWords)) return rc;
     if (n_obs < 0) return fail(c, FDAPDE_EINVAL, "fdapde_kron_set_obs: n_obs is negative");
     HIPCHK(c, hipSetDevice(c->device));
     KronHandle& K = *c->kron;
@@ -447,7 +364,7 @@ int e_kron_set_obs(fdapde_ctx* c, int32_t p, const double* Phi, int64_t n_obs, c
     HIPCHK(c, O.phi.upload(O.h_phi.data(), O.h_phi.size(), st));
     HIPCHK(c, O.t.alloc((size_t)n_obs * p));
     HIPCHK(c, O.g.alloc((size_t)n * p));
-    by_obs_team(O.QP, [&](auto t) {
+    by_team(O.QP, [&](auto t) {
         constexpr int QP = decltype(t)::value;
         if (O.form_cols == 2)
             hipLaunchKernelGGL((k_kron_obs_diag<QP, true>), dim3((unsigned)n), dim3(256), 0, st, n, p, O.trp.p, O.tci.p, O.tv.p, O.w.p, scale, O.g.p, (const int32_t*)nullptr);
@@ -465,8 +382,8 @@ int e_kron_set_obs(fdapde_ctx* c, int32_t p, const double* Phi, int64_t n_obs, c
 
 int e_kron_obs_info(fdapde_ctx* c, int32_t* p, int64_t* n_obs, int64_t* nnz, int32_t* form_rows, int32_t* form_cols) {
     if (!c) return FDAPDE_EINVAL;
-    if (int rc = kron_guard(c)) return rc;
-    if (!kron_live(c)) return fail(c, FDAPDE_ENOTINIT, kKronFirst);
+    if (int rc = handle_guard(c, kKronWords)) return rc;
+    if (int rc = handle_live(c, c->kron, kKronWords)) return rc;
     const KronObs& O = c->kron->obs;
     if (!O.live) return fail(c, FDAPDE_ENOTINIT, "fdapde_kron_obs_info: no data term is live (fdapde_kron_set_obs)");
     if (p) *p = O.p;
@@ -479,19 +396,19 @@ int e_kron_obs_info(fdapde_ctx* c, int32_t* p, int64_t* n_obs, int64_t* nnz, int
 
 int e_kron_spmv(fdapde_ctx* c, const double* x, double* y) {
     if (!c || !x || !y) return FDAPDE_EINVAL;
-    if (int rc = kron_guard(c)) return rc;
-    if (!kron_live(c)) return fail(c, FDAPDE_ENOTINIT, kKronFirst);
+    if (int rc = handle_guard(c, kKronWords)) return rc;
+    if (int rc = handle_live(c, c->kron, kKronWords)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     KronHandle& K = *c->kron;
     hipStream_t st = c->stream;
-    const int64_t n = K.n, nq = (int64_t)K.q * n;
-    HIPCHK(c, hipMemcpyAsync(K.ext.p, x, sizeof(double) * (size_t)nq, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_kron_stage, dim3(g1(nq), 1), dim3(256), 0, st, n, K.q, c->dof_i2e.p, K.ext.p, K.w.p, (int64_t)K.q, (int64_t)1);
+    const auto ops = kron_ops(c, K);
+    HIPCHK(c, hipMemcpyAsync(K.ext.p, x, sizeof(double) * (size_t)ops.rows, hipMemcpyHostToDevice, st));
+    ops.stage(kLayoutPlain, K.ext.p, K.w.p, 1);
     launch_kron_spmv(c, K, false, K.w.p, K.t.p, nullptr);
     if (K.obs.live) launch_kron_obs(c, K, nullptr, K.w.p, K.t.p, nullptr);
-    hipLaunchKernelGGL(k_kron_unstage, dim3(g1(nq), 1), dim3(256), 0, st, n, K.q, c->dof_i2e.p, K.t.p, K.ext.p, (int64_t)K.q, (int64_t)1);
+    ops.unstage(kLayoutPlain, K.t.p, K.ext.p, 1);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(y, K.ext.p, sizeof(double) * (size_t)nq, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(y, K.ext.p, sizeof(double) * (size_t)ops.rows, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     return FDAPDE_OK;
 }
@@ -500,8 +417,8 @@ int e_kron_spmv(fdapde_ctx* c, const double* x, double* y) {
 // HIP events on the context's stream
 int e_kron_bench_spmv(fdapde_ctx* c, int32_t reps, double* avg_ms, double* algorithmic_bytes) {
     if (!c || reps < 1) return FDAPDE_EINVAL;
-    if (int rc = kron_guard(c)) return rc;
-    if (!kron_live(c)) return fail(c, FDAPDE_ENOTINIT, kKronFirst);
+    if (int rc = handle_guard(c, kKronWords)) return rc;
+    if (int rc = handle_live(c, c->kron, kKronWords)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     KronHandle& K = *c->kron;
     const int64_t n = K.n, nq = (int64_t)K.q * n;
@@ -534,110 +451,30 @@ int e_kron_bench_spmv(fdapde_ctx* c, int32_t reps, double* avg_ms, double* algor
 
 int e_kron_solve(fdapde_ctx* c, const fdapde_options* opt, const double* b, int32_t n_rhs, double* x, fdapde_info* info) {
     if (!c || !b || !x || n_rhs < 1) return FDAPDE_EINVAL;
-    if (int rc = kron_guard(c)) return rc;
-    if (!kron_live(c)) return fail(c, FDAPDE_ENOTINIT, kKronFirst);
+    if (int rc = handle_guard(c, kKronWords)) return rc;
+    if (int rc = handle_live(c, c->kron, kKronWords)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     KronHandle& K = *c->kron;
-    const int64_t n = K.n, nq = (int64_t)K.q * n;
-    {   // an in-place solve: finished columns are written to x while later ones still read b
-        const double *b0 = b, *b1 = b + (size_t)nq * n_rhs, *x0 = x, *x1 = x + (size_t)nq * n_rhs;
-        if (b0 < x1 && x0 < b1) {
-            std::vector<double> b_copy(b0, b1);
-            return e_kron_solve(c, opt, b_copy.data(), n_rhs, x, info);
-        }
+    HandleCall k;
+    if (int rc = handle_call(c, kKronWords, FDAPDE_SOLVER_KRON_AMG, (int64_t)K.q * K.n, opt, &k)) return rc;
+    if (k.amg) {
+        if (K.obs.live)
+            return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_KRON_AMG: a factored data term (fdapde_kron_set_obs) is live; the hierarchy is built from pattern entries only");
+        if (!K.have_dinv)
+            return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_KRON_AMG: the inverted diagonal blocks (8 q^2 n bytes) exceed the budget `kron_dinv_mb`: no block-Jacobi smoother");
+        if (!K.jacobi_ok)
+            return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_KRON_AMG: a DOF's diagonal block is singular (a pivot <= 1e-14 max|entry|): no block-Jacobi smoother");
+        if (!K.amg && c->kron_amg_term >= K.n_terms) return fail(c, FDAPDE_EINVAL, "FDAPDE_SOLVER_KRON_AMG: the knob `kron_amg_term` names a term the handle was not given");
+    } else {
+        if (k.method == FDAPDE_SOLVER_GMRES && !K.have_dinv)
+            return fail(c, FDAPDE_EUNSUPPORTED, "the inverted diagonal blocks (8 q^2 n bytes) exceed the budget `kron_dinv_mb`: no Krylov stage for this Kronecker handle");
+        if (k.method == FDAPDE_SOLVER_GMRES && !K.jacobi_ok)   // (the record names the method first)
+            return bare_answer(c, FDAPDE_SOLVER_GMRES, 0.0, info, fail(c, FDAPDE_ENOCONV, "a DOF's diagonal block is singular (a pivot <= 1e-14 max|entry|): no block-Jacobi form for the Krylov stage"));
+        if (k.open && !k.eligible && !K.jacobi_ok)
+            return fail(c, FDAPDE_EUNSUPPORTED, K.have_dinv ? "a DOF's diagonal block is singular: no block-Jacobi form for the Krylov stage, and the system is too large for the dense inverse"
+                                                            : "the inverted diagonal blocks exceed the budget `kron_dinv_mb`, and the system is too large for the dense inverse");
     }
-    hipStream_t st = c->stream;
-    const int method = opt ? opt->method : FDAPDE_SOLVER_AUTO;
-    const bool open = method == FDAPDE_SOLVER_AUTO, dense_named = method == FDAPDE_SOLVER_DENSE;
-    if (method == FDAPDE_SOLVER_KRON_AMG) return kron_amg_solve(c, K, opt, b, n_rhs, x, info);
-    if (!open && !dense_named && method != FDAPDE_SOLVER_GMRES)
-        return fail(c, FDAPDE_EUNSUPPORTED, "fdapde_kron_solve runs FDAPDE_SOLVER_GMRES, FDAPDE_SOLVER_DENSE, FDAPDE_SOLVER_KRON_AMG or the open method");
-    const double rtol = (opt && opt->rtol > 0) ? opt->rtol : 1e-10;
-    const int maxit = (opt && opt->maxit > 0) ? opt->maxit : 2000;
-    fdapde_info out{};
-    const auto t_call = std::chrono::steady_clock::now();
-    const bool eligible = kron_dense_eligible(c, K);
-    if (dense_named && !eligible) return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_DENSE takes Kronecker systems of up to `dense_rows` (at most 8192) rows");
-    if (method == FDAPDE_SOLVER_GMRES && !K.have_dinv)
-        return fail(c, FDAPDE_EUNSUPPORTED, "the inverted diagonal blocks (8 q^2 n bytes) exceed the budget `kron_dinv_mb`: no Krylov stage for this Kronecker handle");
-    if (method == FDAPDE_SOLVER_GMRES && !K.jacobi_ok) {
-        out.method_used = FDAPDE_SOLVER_GMRES;
-        c->info = out;
-        if (info) *info = out;
-        return fail(c, FDAPDE_ENOCONV, "a DOF's diagonal block is singular (a pivot <= 1e-14 max|entry|): no block-Jacobi form for the Krylov stage");
-    }
-    if (open && !eligible && !K.jacobi_ok)
-        return fail(c, FDAPDE_EUNSUPPORTED, K.have_dinv ? "a DOF's diagonal block is singular: no block-Jacobi form for the Krylov stage, and the system is too large for the dense inverse"
-                                                        : "the inverted diagonal blocks exceed the budget `kron_dinv_mb`, and the system is too large for the dense inverse");
-    HIPCHK(c, K.ext.alloc((size_t)std::max<int64_t>((int64_t)K.ns * K.nnz, nq)));
-    if ((open || dense_named) && eligible) {   // the rent-or-buy rule of fdapde_lin_solve, with q n as the row count
-        fdapde_ctx::Dense& D = K.dense;
-        if (!D.ready && (!D.failed || dense_named) &&
-            (dense_named || !K.jacobi_ok || c->dense_after == 0 || (K.cols + n_rhs > c->dense_after && K.krylov_ms >= 0.5 * dense_build_estimate_ms(nq))))
-            if (int rc = kron_dense_build(c, K)) return rc;
-        if ((dense_named || !K.jacobi_ok) && !D.ready) {
-            out.method_used = FDAPDE_SOLVER_DENSE, out.relres = D.check;
-            c->info = out;
-            if (info) *info = out;
-            c->err = "FDAPDE_SOLVER_DENSE: the Kronecker matrix is singular to working precision (no usable pivot, or max |I - A X| beyond 1e-6)";
-            return FDAPDE_ENOCONV;
-        }
-        if (D.ready) {
-            const size_t cnt = (size_t)nq * (size_t)n_rhs;
-            HIPCHK(c, K.dn_b.alloc(cnt));
-            HIPCHK(c, K.dn_x.alloc(cnt));
-            // the columns cross in slices of the staging buffer's size, every slice one product
-            const int per = (int)std::max<int64_t>(1, (int64_t)(K.ext.n / (size_t)nq));
-            for (int j0 = 0; j0 < n_rhs; j0 += per) {
-                const int nc = std::min(per, n_rhs - j0);
-                HIPCHK(c, hipMemcpyAsync(K.ext.p, b + (size_t)j0 * nq, sizeof(double) * (size_t)nq * nc, hipMemcpyHostToDevice, st));
-                hipLaunchKernelGGL(k_kron_stage, dim3(g1(nq), nc), dim3(256), 0, st, n, K.q, c->dof_i2e.p, K.ext.p, K.dn_b.p + (size_t)j0 * nq, (int64_t)1, n);
-            }
-            if (int rc = dense_apply(c, D, n_rhs, K.dn_b.p, K.dn_x.p)) return rc;
-            for (int j0 = 0; j0 < n_rhs; j0 += per) {
-                const int nc = std::min(per, n_rhs - j0);
-                hipLaunchKernelGGL(k_kron_unstage, dim3(g1(nq), nc), dim3(256), 0, st, n, K.q, c->dof_i2e.p, K.dn_x.p + (size_t)j0 * nq, K.ext.p, (int64_t)1, n);
-                HIPCHK(c, hipGetLastError());
-                HIPCHK(c, hipMemcpyAsync(x + (size_t)j0 * nq, K.ext.p, sizeof(double) * (size_t)nq * nc, hipMemcpyDeviceToHost, st));
-                HIPCHK(c, hipStreamSynchronize(st));
-            }
-            K.cols += n_rhs;
-            out.iters = D.refine ? 1 : 0, out.converged = 1, out.relres = D.check, out.method_used = FDAPDE_SOLVER_DENSE;
-            out.t_solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
-            c->info = out;
-            if (info) *info = out;
-            return FDAPDE_OK;
-        }
-    }
-    // Krylov stage, the columns one after another
-    K.cols += n_rhs;
-    const double tol2 = rtol * rtol;
-    int total = 0, rc_all = FDAPDE_OK;
-    double worst = 0;
-    bool broke = false;
-    for (int32_t j = 0; j < n_rhs; ++j) {
-        HIPCHK(c, hipMemcpyAsync(K.ext.p, b + (size_t)j * nq, sizeof(double) * (size_t)nq, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_kron_stage, dim3(g1(nq), 1), dim3(256), 0, st, n, K.q, c->dof_i2e.p, K.ext.p, K.bt.p, (int64_t)K.q, (int64_t)1);
-        launch_kron_dinv(c, K, K.bt.p, K.bt.p, nullptr);
-        int32_t h_ctl[4] = {0, 0, 0, 0};
-        double h_sc[4] = {0, 0, 0, 0};
-        if (int rc = kron_gmres(c, K, tol2, maxit, h_ctl, h_sc)) return rc;
-        const double bb = h_sc[0], rr = h_sc[3];
-        const double rel = bb > 0 ? std::sqrt(rr / bb) : 0.0;
-        if (!(rr <= tol2 * bb && h_ctl[2] == 0)) rc_all = FDAPDE_ENOCONV, broke = broke || h_ctl[2] != 0;
-        total += h_ctl[1], worst = rel > worst ? rel : worst;
-        hipLaunchKernelGGL(k_kron_unstage, dim3(g1(nq), 1), dim3(256), 0, st, n, K.q, c->dof_i2e.p, K.x.p, K.ext.p, (int64_t)K.q, (int64_t)1);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(x + (size_t)j * nq, K.ext.p, sizeof(double) * (size_t)nq, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-    }
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
-    K.krylov_ms += ms;
-    out.iters = total, out.relres = worst, out.converged = rc_all == FDAPDE_OK ? 1 : 0, out.method_used = FDAPDE_SOLVER_GMRES, out.t_solve_ms = ms;
-    c->info = out;
-    if (info) *info = out;
-    if (rc_all == FDAPDE_ENOCONV) c->err = broke ? "GMRES stagnated or broke down in at least one column" : "maxit reached in at least one column";
-    return rc_all;
+    return handle_solve(c, K, kron_ops(c, K), k, opt, b, n_rhs, x, info);
 }
 
 }   // namespace fdapde_engine

@@ -14,6 +14,8 @@
 //   cycle     0.7 D^-1, the coarse correction (two GCR steps below the finest level: the systems are indefinite or non-symmetric), 0.7 D^-1
 //             (kernels_kron.h k_kamg_*); amg_cycle / amg_correction unchanged.
 //   outer     fgmres_outer (eng_pmg.hip) on the UNSCALED system, right-preconditioned by the cycle; the stop rule is the true residual |b - A x| <= rtol |b|.
+//             The run of a column is amg_point_cols (amg_setup.h, shared with eng_block_amg.hip) with this handle's product; the loop over a call's columns is
+//             handle_solve's (eng_handle.h).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -35,8 +37,6 @@ namespace {
 using namespace fdapde_hip;
 
 constexpr double kKamgOmega = 0.7;   // the smoother's damping: fixed, as the block form's
-constexpr int kKamgMaxRestart = 64;  // fgmres_outer's Gram-Schmidt kernels hold that many coefficients
-inline int kron_restart_len(const fdapde_ctx* c, int maxit) { return std::max(1, std::min(std::min(c->gmres_m, kKamgMaxRestart), std::max(maxit, 1))); }
 
 // a level: the scalar level (n DOFs; a = the strength matrix on the pattern; agg, mptr, midx; np; the work vectors at q n words) and its Kronecker sum
 struct KamgLevel : AmgLevel {
@@ -49,24 +49,8 @@ struct KamgLevel : AmgLevel {
 };
 inline KamgLevel& kl(AmgLevel& L) { return static_cast<KamgLevel&>(L); }
 
-// f(std::integral_constant<int, Q>) for the team width Q in {2, 4, 8, 16, 32, 64}
-template <typename F> void by_kron_team(int Q, F&& f) {
-    switch (Q) {
-    case 2: f(std::integral_constant<int, 2>{}); break;
-    case 4: f(std::integral_constant<int, 4>{}); break;
-    case 8: f(std::integral_constant<int, 8>{}); break;
-    case 16: f(std::integral_constant<int, 16>{}); break;
-    case 32: f(std::integral_constant<int, 32>{}); break;
-    case 64: f(std::integral_constant<int, 64>{}); break;
-    }
-}
 inline size_t lds_bytes(const KamgLevel& L) { return sizeof(double) * kamg_lds_doubles(L.q, L.ns, L.t_in_lds != 0); }
 }   // namespace
-
-struct KronAmg : AmgHierarchy {   // (D: q n_L rows; the coarse corrections are GCR steps)
-    DBuf<int32_t> rp2, ci2, flag;
-    DBuf<double> val2;
-};
 
 void kron_amg_free(KronAmg* h) { delete h; }
 
@@ -74,7 +58,7 @@ namespace {
 // the cycle's launches (one column): 0.7 D^-1 with the q x q diagonal blocks as the smoother
 void kron_pre_restrict(hipStream_t st, int, AmgLevel& L0, AmgLevel& N, const double* r, double* rc, int64_t rs, int64_t) {
     KamgLevel& L = kl(L0);
-    by_kron_team(L.Q, [&](auto t) {
+    by_team(L.Q, [&](auto t) {
         constexpr int QQ = decltype(t)::value;
         hipLaunchKernelGGL(k_kamg_smooth<QQ>, dim3(g1(L.n, 256 / QQ)), dim3(256), 0, st, L.n, L.q, L.dq, kKamgOmega, r, L.zt.p);
         hipLaunchKernelGGL(k_kamg_pre_restrict<QQ>, dim3(g1(N.n, 256 / QQ)), dim3(256), lds_bytes(L), st, N.n, L.q, L.ns, L.mptr.p, L.midx.p, L.rp, L.ci, L.sv, L.tm,
@@ -83,7 +67,7 @@ void kron_pre_restrict(hipStream_t st, int, AmgLevel& L0, AmgLevel& N, const dou
 }
 void kron_post(hipStream_t st, int, AmgLevel& L0, AmgLevel& N, const double* r, double* out) {
     KamgLevel& L = kl(L0);
-    by_kron_team(L.Q, [&](auto t) {
+    by_team(L.Q, [&](auto t) {
         constexpr int QQ = decltype(t)::value;
         hipLaunchKernelGGL(k_kamg_post<QQ>, dim3(g1(L.n, 256 / QQ)), dim3(256), lds_bytes(L), st, L.n, L.q, L.ns, L.rp, L.ci, L.sv, L.tm, L.band, L.dq, kKamgOmega,
                            L.agg.p, (const double*)N.e.p, r, (const double*)L.zt.p, out, L.t_in_lds);
@@ -92,7 +76,7 @@ void kron_post(hipStream_t st, int, AmgLevel& L0, AmgLevel& N, const double* r, 
 void kron_spmv_dots(hipStream_t st, int, AmgLevel& L0, const double* x, double* y, const double* p0, const double* q0, const double* p1, const double* q1,
                     const double* p2, const double* q2) {
     KamgLevel& L = kl(L0);
-    by_kron_team(L.Q, [&](auto t) {
+    by_team(L.Q, [&](auto t) {
         constexpr int QQ = decltype(t)::value;
         hipLaunchKernelGGL(k_kamg_spmv_dots<QQ>, dim3((unsigned)L.np), dim3(256), lds_bytes(L), st, L.n, L.q, L.ns, L.rp, L.ci, L.sv, L.tm, L.band, x, y, p0, q0, p1, q1,
                            p2, q2, L.part.p, L.t_in_lds);
@@ -106,7 +90,7 @@ int level_dinv(fdapde_ctx* c, KronAmg& H, KamgLevel& L, bool* bad) {
     HIPCHK(c, H.flag.alloc(1));
     HIPCHK(c, hipMemsetAsync(H.flag.p, 0, sizeof(int32_t), st));
     HIPCHK(c, L.dq_own.alloc((size_t)L.q * L.q * (size_t)std::max<int64_t>(L.n, 1)));
-    by_kron_team(L.Q, [&](auto t) {
+    by_team(L.Q, [&](auto t) {
         constexpr int QQ = decltype(t)::value;
         hipLaunchKernelGGL(k_kron_diag_inv<QQ>, dim3(g1(L.n, 64 / QQ)), dim3(64), 0, st, L.n, L.q, L.ns, L.rp, L.ci, L.sv, L.tm, (const double*)nullptr,
                            (const double*)nullptr, 0,L.dq_own.p, H.flag.p);
@@ -208,74 +192,25 @@ int kron_amg_build(fdapde_ctx* c, KronAmg** slot, const KronAmgSource& src) {
     return amg_build_retry(c, slot, [&](int absorb, bool* stalled) { return kron_amg_build_pass(c, slot, src, absorb, stalled); });
 }
 
-int kron_amg_describe(const KronAmg* H, int32_t cap, int32_t* n_levels, int64_t* rows, int64_t* nnz, int32_t* absorbed, double* setup_ms) {
-    return amg_describe(H, cap, n_levels, rows, nnz, absorbed, setup_ms);   // (rows q n_l, entries q^2 nnz_l: per = q)
-}
-int kron_amg_aggregates(fdapde_ctx* c, const KronAmg* H, int32_t level, int64_t cap, int32_t* agg, int64_t* n_rows) {
-    return amg_aggregates(c, H, level, cap, agg, n_rows);
-}
-
-// one column: A x = b (both interleaved, internal order, on the device; x is written, from zero).  What is handed out is judged by its own residual
+// one column: A x = b (both interleaved, internal order, on the device; x is written, from zero): amg_point_cols (amg_setup.h) at one column with the
+// handle's own product
 int kron_amg_run(fdapde_ctx* c, KronAmg* hp, const double* b, double* x, double rtol, int maxit, int* iters, double* relres, bool* converged_out, bool* broke_out) {
     KronAmg& H = *hp;
     hipStream_t st = c->stream;
     KamgLevel& L0 = kl(*H.lv[0]);
     const int64_t n = L0.n, nq = (int64_t)L0.q * n;
-    const int np = (int)std::min<int64_t>(1024, std::max<int64_t>(1, (nq + 4095) / 4096));
-    const int mk = kron_restart_len(c, maxit);
-    if (int rc = amg_cols_prepare(c, H, 1)) return rc;
     HIPCHK(c, H.vec.alloc(2 * (size_t)nq));
-    HIPCHK(c, H.basis.alloc((size_t)(2 * mk + 1) * (size_t)nq));
-    HIPCHK(c, H.part.alloc((size_t)(mk + 2) * (size_t)np + 3 * (size_t)np));
-    HIPCHK(c, H.dots.alloc((size_t)(mk + 4)));
-    double *r = H.vec.p, *t = H.vec.p + nq;
-    double h[kAmgColsMax];
-    auto spmv = [&](const double* in, double* out) {   // (the handle's own product)
+    FgmresCols S{};
+    const int rc = amg_point_cols(c, H, 1, [&](const double* in, double* out) {
         const size_t lds = sizeof(double) * kron_spmv_lds_doubles(L0.q, L0.ns, false, L0.t_in_lds != 0);
-        by_kron_team(L0.Q, [&](auto tq) {
+        by_team(L0.Q, [&](auto tq) {
             constexpr int QQ = decltype(tq)::value;
             hipLaunchKernelGGL((k_kron_spmv<QQ, false>), dim3(g1(n, 256 / QQ)), dim3(256), lds, st, n, L0.q, L0.ns, L0.rp, L0.ci, L0.sv, L0.tm, L0.band,
                                (const double*)nullptr, in, out, (const int32_t*)nullptr, L0.t_in_lds);
         });
-    };
-    auto dots = [&](const double* a0) -> int {
-        fixed_dots_cols(st, nq, np, 1, a0, a0, H.part.p, H.dots.p);
-        HIPCHK(c, hipMemcpyAsync(h, H.dots.p, sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        return FDAPDE_OK;
-    };
-    auto residual = [&](double* rr_out) -> int {   // the TRUE residual of the iterate
-        spmv(x, t);
-        hipLaunchKernelGGL(k_bamg_residual, dim3(gn(nq)), dim3(256), 0, st, nq, b, (const double*)t, r);
-        if (int rc = dots(r)) return rc;
-        rr_out[0] = h[0];
-        return FDAPDE_OK;
-    };
-    FgmresCols S{};
-    HIPCHK(c, hipMemsetAsync(x, 0, sizeof(double) * (size_t)nq, st));
-    HIPCHK(c, hipMemcpyAsync(r, b, sizeof(double) * (size_t)nq, hipMemcpyDeviceToDevice, st));
-    if (int rc = dots(r)) return rc;
-    S.bb[0] = S.rr[0] = h[0], S.converged[0] = !(h[0] > 0.0) && std::isfinite(h[0]), S.broke[0] = !std::isfinite(h[0]);
-    const bool live = h[0] > 0.0 && std::isfinite(h[0]);
-    const bool one_level = H.lv.size() == 1;
-    auto precond = [&](const double* v, double* z, double* w, bool&) -> int {
-        if (one_level) {
-            if (int rc = amg_dense_cols(c, H, 1, v, z)) return rc;
-        } else if (int rc = amg_cycle(c, H, 0, 1, v, z))
-            return rc;
-        spmv(z, w);
-        return FDAPDE_OK;
-    };
-    FgmresSpace fs{nq, mk, H.basis.p, H.basis.p + (size_t)(mk + 1) * (size_t)nq, H.part.p, H.dots.p, np};
-    if (int rc = fgmres_outer(c, fs, 1, x, r, nullptr, rtol, maxit, precond, residual, S)) return rc;
-    if (live) {   // what is handed out is judged by its own residual, whichever way the loop ended
-        double rr = 0.0;
-        if (int rc = residual(&rr)) return rc;
-        S.rr[0] = rr, S.converged[0] = std::isfinite(rr) && rr <= rtol * rtol * S.bb[0];
-    }
-    *relres = S.bb[0] > 0.0 ? std::sqrt(S.rr[0] / S.bb[0]) : 0.0;
+    }, b, x, H.vec.p, H.vec.p + nq, false, rtol, maxit, S, relres);
+    if (rc != FDAPDE_OK) return rc;
     *iters = S.it[0], *converged_out = S.converged[0], *broke_out = S.broke[0];
-    HIPCHK(c, hipGetLastError());
     return FDAPDE_OK;
 }
 

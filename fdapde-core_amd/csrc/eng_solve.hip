@@ -402,11 +402,7 @@ namespace {
 
 // ---- what fdapde_solve, the parabolic stepper and the handle's solve say and decide alike -------------------------------------------------
 
-// the outcome of a Krylov run as its kernels leave it: sc[0] = |b|^2, sc[3] = |r|^2, ctl[2] = the breakdown word
-struct Outcome { double relres; int converged; };
-inline Outcome outcome_of(double bb, double rr, bool broke, double tol2) { return {bb > 0 ? sqrt(rr / bb) : 0.0, (rr <= tol2 * bb && !broke) ? 1 : 0}; }
-inline Outcome outcome_from(const double* h_sc, const int32_t* h_ctl, double tol2) { return outcome_of(h_sc[0], h_sc[3], h_ctl[2] != 0, tol2); }
-
+// (the outcome of a Krylov run -- Outcome, outcome_of, outcome_from -- and bare_answer / dense_singular: engine.h, shared with the operator handles)
 // the scalars of the run into h_sc -- with the stop flag, the iteration count and the breakdown word into h_ctl unless h_ctl holds them already -- and the wait
 int read_outcome(fdapde_ctx* c, bool ctl_too = true) {
     if (ctl_too) HIPCHK(c, hipMemcpyAsync(c->h_ctl, c->ctl.p, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
@@ -436,18 +432,8 @@ int cg_breakdown_agreed(fdapde_ctx* c, const SolveState& ss, int rc, bool open_m
     return FDAPDE_OK;
 }
 
-// FDAPDE_SOLVER_DENSE by name: the refusal of a system it does not take, and the report of a matrix (`what`) it could not invert
+// FDAPDE_SOLVER_DENSE by name: the refusal of a system it does not take
 constexpr const char* kDenseRefusal = "FDAPDE_SOLVER_DENSE takes one-GPU systems of up to `dense_rows` (at most 8192) DOFs";
-inline std::string dense_singular(const char* what) {
-    return std::string("FDAPDE_SOLVER_DENSE: ") + what + " is singular to working precision (no usable pivot, or max |I - A X| beyond 1e-6)";
-}
-// a call that ends before any solve: the record names the method (and the inverse's check), nothing of an earlier solve stays in it
-int bare_answer(fdapde_ctx* c, int method, double check, fdapde_info* info, int rc) {
-    c->info = fdapde_info{};
-    c->info.method_used = method, c->info.relres = check;
-    if (info) *info = c->info;
-    return rc;
-}
 
 }   // namespace
 

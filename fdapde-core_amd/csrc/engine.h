@@ -5,9 +5,11 @@
 #define FDAPDE_ENGINE_H
 
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <functional>
+#include <string>
 
 #include "context.h"
 
@@ -35,6 +37,23 @@ inline int fail(fdapde_ctx* c, int code, const char* msg) {
 inline int need_device(fdapde_ctx* c) {
     if (!c->has_device) return fail(c, FDAPDE_ENODEVICE, "this context has no HIP device (host-only); there is no CPU fallback");
     return FDAPDE_OK;
+}
+
+// ---- what fdapde_solve, the parabolic stepper, fdapde_lin_solve and the operator handles (eng_handle.h) say and decide alike
+// the outcome of a Krylov run as its kernels leave it: sc[0] = |b|^2, sc[3] = |r|^2, ctl[2] = the breakdown word
+struct Outcome { double relres; int converged; };
+inline Outcome outcome_of(double bb, double rr, bool broke, double tol2) { return {bb > 0 ? std::sqrt(rr / bb) : 0.0, (rr <= tol2 * bb && !broke) ? 1 : 0}; }
+inline Outcome outcome_from(const double* h_sc, const int32_t* h_ctl, double tol2) { return outcome_of(h_sc[0], h_sc[3], h_ctl[2] != 0, tol2); }
+// FDAPDE_SOLVER_DENSE's report of a matrix (`what`) it could not invert
+inline std::string dense_singular(const std::string& what) {
+    return "FDAPDE_SOLVER_DENSE: " + what + " is singular to working precision (no usable pivot, or max |I - A X| beyond 1e-6)";
+}
+// a call that ends before any solve: the record names the method (and the inverse's check), nothing of an earlier solve stays in it
+inline int bare_answer(fdapde_ctx* c, int method, double check, fdapde_info* info, int rc) {
+    c->info = fdapde_info{};
+    c->info.method_used = method, c->info.relres = check;
+    if (info) *info = c->info;
+    return rc;
 }
 
 // a DBuf takes over a device array built elsewhere (dev_setup.hip)
@@ -245,7 +264,7 @@ int kron_amg_describe_ctx(const fdapde_ctx* c, int32_t cap, int32_t* n_levels, i
 int kron_amg_aggregates_ctx(fdapde_ctx* c, int32_t level, int64_t cap, int32_t* agg, int64_t* n_rows);
 
 // eng_kron_amg.hip: FDAPDE_SOLVER_KRON_AMG, the point-block multilevel preconditioner of the Kronecker-sum handle -- the hierarchy of the handle's factors
-// on the context's pattern (src: the handle's device arrays, tnorm the Frobenius norms of its time factors, pick the spatial factor the aggregation reads or
+// (a KronAmg, amg_setup.h) on the context's pattern (src: the handle's device arrays, tnorm the Frobenius norms of its time factors, pick the spatial factor the aggregation reads or
 // -1 for the weighted sum of magnitudes), and one column A x = b against it (b, x: interleaved, internal order, device)
 struct KronAmg;
 struct KronAmgSource {
@@ -258,11 +277,9 @@ struct KronAmgSource {
 };
 void kron_amg_free(KronAmg* h);
 int kron_amg_build(fdapde_ctx* c, KronAmg** slot, const KronAmgSource& src);
-int kron_amg_describe(const KronAmg* h, int32_t cap, int32_t* n_levels, int64_t* rows, int64_t* nnz, int32_t* absorbed, double* setup_ms);   // rows: q n_l
-int kron_amg_aggregates(fdapde_ctx* c, const KronAmg* h, int32_t level, int64_t cap, int32_t* agg, int64_t* n_rows);
 int kron_amg_run(fdapde_ctx* c, KronAmg* h, const double* b_dev, double* x_dev, double rtol, int maxit, int* iters, double* relres, bool* converged, bool* broke);
 
-// eng_block_amg.hip: FDAPDE_SOLVER_BLOCK_AMG, the point-block multilevel preconditioner of the block handle -- the hierarchy of the unscaled block CSR
+// eng_block_amg.hip: FDAPDE_SOLVER_BLOCK_AMG, the point-block multilevel preconditioner of the block handle -- the hierarchy (a BlockAmg, amg_setup.h) of the unscaled block CSR
 // `raw` on the context's pattern (strength_block: which of a11 a12 a21 a22 the aggregation reads), and one column A x = b against it (b, x: interleaved,
 // internal order, device)
 struct BlockAmg;
@@ -282,10 +299,6 @@ int block_amg_build(fdapde_ctx* c, BlockAmg** slot, const double* raw, int stren
 // FDAPDE_ENOTINIT where h is NULL or carries no term
 int block_amg_obs_levels(const BlockAmg* h, int32_t cap, int32_t* n_levels, int64_t* nnz, int32_t* longest_row, int32_t* team_rows, int32_t* team_cols, double* term_ms);
 bool block_amg_has_term(const BlockAmg* h);
-int block_amg_describe(const BlockAmg* h, int32_t cap, int32_t* n_levels, int64_t* rows, int64_t* nnz, int32_t* absorbed, double* setup_ms);   // rows: 2 n_l
-int block_amg_aggregates(fdapde_ctx* c, const BlockAmg* h, int32_t level, int64_t cap, int32_t* agg, int64_t* n_rows);   // fdapde_amg_aggregates, which 2
-int block_amg_order(fdapde_ctx* c, const BlockAmg* h, int64_t cap, int32_t* order, int64_t* n_rows);   // fdapde_amg_order, which 2 (block rows)
-int block_amg_damping(const BlockAmg* h, int32_t cap, int32_t* n_levels, double* omega);   // fdapde_amg_damping, which 2: 0.7 on every level that has a next one
 int block_amg_run(fdapde_ctx* c, BlockAmg* h, const double* raw, const double* b_dev, double* x_dev, double rtol, int maxit, int* iters, double* relres,
                   bool* converged, bool* broke, bool warm = false);   // warm: x_dev holds the iterate to start from (a column a batch handed back)
 // Q in {2, 4, 8} columns side by side (knob amg_cols; block_amg_width: the widest batch for `left` columns): ext (device) holds the stacked columns in the
@@ -293,8 +306,6 @@ int block_amg_run(fdapde_ctx* c, BlockAmg* h, const double* raw, const double* b
 int block_amg_width(const fdapde_ctx* c, const BlockAmg* h, int32_t left, int maxit);
 int block_amg_batch(fdapde_ctx* c, BlockAmg* h, const double* raw, int Q, double* ext, double* col_b, double* col_x, double rtol, int maxit, int* iters, double* worst,
                     bool* not_conv, bool* broke_any);
-int block_amg_cols_trace(const BlockAmg* h, int32_t* batches, int32_t* batched_cols, int32_t* single_cols);   // fdapde_amg_cols_trace, which 2
-void block_amg_count_single(BlockAmg* h);   // a column went through block_amg_run alone
 
 // code objects of the units loaded up front (fdapde_ctx_create)
 void preload_assembly();

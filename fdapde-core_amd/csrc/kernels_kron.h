@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "kernels_block.h"
 
@@ -21,6 +22,18 @@ namespace fdapde_hip {
 
 constexpr int kKronMaxQ = 64;      // unknowns per DOF
 constexpr int kKronMaxTerms = 8;   // terms handed over, hence distinct spatial factors
+// f(std::integral_constant<int, Q>) for a team width Q in {2, 4, 8, 16, 32, 64} (the power of two >= q; the data term's: >= max(p, q)): every launch of a
+// kernel templated on the team width goes through here
+template <typename F> void by_team(int Q, F&& f) {
+    switch (Q) {
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 8: f(std::integral_constant<int, 8>{}); break;
+    case 16: f(std::integral_constant<int, 16>{}); break;
+    case 32: f(std::integral_constant<int, 32>{}); break;
+    case 64: f(std::integral_constant<int, 64>{}); break;
+    }
+}
 // The time factors ride in LDS for the whole workgroup where all of them are at most this many doubles (8 KiB), else the epilogue reads them from global
 // memory, where every workgroup shares them in cache.  Measured on the space-time system with four factors (the operator D^-1 A, 502 681 DOFs): the copy
 // wins at q = 10 and 16 (400 and 1 024 doubles: 0.502 against 0.530 ms, 0.563 against 0.600) and loses at q = 32 (4 096 doubles, 32 KiB copied by every

@@ -15,12 +15,16 @@ had measured this before.
     iteration, the set-up split into the pattern hierarchy and the term's share (FDAPDE_DEBUG_SETUP's line, read back from stderr), nnz(Psi_l) per level, the
     launches the term adds per outer iteration.  --obs-guard PARENT_LIB: the NO-term solves of this tool by this library and by the parent commit's
     (a path to its libfdapde_hip.so), a process each, alternating: the new median must lie inside the parent's spread.
+  * --driver-guard PARENT_LIB: the handle's solve path against the parent commit's -- one FDAPDE_SOLVER_GMRES and one FDAPDE_SOLVER_BLOCK_AMG solve of this
+    tool's own systems (no term, lambda 1e-4), five windows per process, the two libraries alternating twice; the gate: this library's median is at most the
+    largest of the parent's windows.  Appends to profiles/handle_driver_time.txt.
 
 usage: block_amg_time.py [OUT]      (OUT defaults to profiles/block_amg_time.txt)
        block_amg_time.py --trace
        block_amg_time.py --stats DIR OUT
        block_amg_time.py --obs [OUT] [sq-areal|sq-points|cube-areal ...]      (OUT defaults to profiles/block_obs_amg_time.txt; appends)
-       block_amg_time.py --obs-guard PARENT_LIB [OUT]"""
+       block_amg_time.py --obs-guard PARENT_LIB [OUT]
+       block_amg_time.py --driver-guard PARENT_LIB [OUT [sq|cube ...]]"""
 import csv
 import glob
 import os
@@ -238,6 +242,71 @@ def guard_child(which):
     print("GUARD_RESULT " + json.dumps({"ms": times, "iters": info.iters, "lib": capi.LIB_PATH}))
 
 
+def driver_guard_child(which):
+    """five GMRES and five BLOCK_AMG solves (no term, lambda 1e-4) of this tool's own system, each behind two warm-up solves -> one GUARD_RESULT line"""
+    import json
+
+    from fdapde_loader import load_package
+
+    capi = load_package().capi
+    from fdapde_core_amd import meshgen
+
+    c, n_nodes = space(capi, meshgen.unit_square(708) if which == "sq" else meshgen.unit_cube(118))
+    blocks, b, _ = smoothing_blocks(c, capi, n_nodes, 1e-4)
+    c.block_compute(*blocks, symmetric=True)
+    res = {"lib": capi.LIB_PATH}
+    for name, method, maxit in (("GMRES", capi.SOLVER_GMRES, 2000), ("BLOCK_AMG", capi.SOLVER_BLOCK_AMG, 200)):
+        solve = lambda: c.block_solve(b, method=method, rtol=1e-10, maxit=maxit, raise_on_noconv=False)
+        solve(), solve()
+        times = []
+        for _ in range(5):
+            (_, info), t = timed(solve)
+            times.append(t)
+        res[name] = {"ms": times, "iters": info.iters}
+    c.close()
+    print("GUARD_RESULT " + json.dumps(res))
+
+
+def driver_guard_main(parent_lib, out_path, tool=__file__, cases=("sq", "cube"), what="fdapde_block_solve, this tool's systems (no term, lambda 1e-4)"):
+    """shared with kron_time.py --driver-guard (tool: the script whose --driver-guard-child runs a case)"""
+    import json
+    import subprocess
+
+    def child(which, lib):
+        env = dict(os.environ)
+        if lib:
+            env["FDAPDE_HIP_LIB"] = lib
+        r = subprocess.run([sys.executable, os.path.abspath(tool), "--driver-guard-child", which], capture_output=True, text=True, env=env, timeout=600)
+        for line in r.stdout.splitlines():
+            if line.startswith("GUARD_RESULT "):
+                return json.loads(line[len("GUARD_RESULT "):])
+        raise SystemExit(f"guard child {which} failed:\n{r.stdout}\n{r.stderr}")
+
+    out = ["", f"tools/{os.path.basename(tool)} --driver-guard on an MI355X, {time.strftime('%Y-%m-%d %H:%M:%S')}",
+           f"one solve of {what}, wall time of the call, ms; this library and the parent commit's, a process each, alternating twice, five windows per process",
+           "the gate: this library's median <= the largest of the parent's windows"]
+    bad = 0
+    for which in cases:
+        new, old = {}, {}
+        for _ in range(2):
+            for got, lib in ((new, None), (old, parent_lib)):
+                r = child(which, lib)
+                assert lib is None or os.path.samefile(r.pop("lib"), parent_lib), "the parent's library ran"
+                r.pop("lib", None)
+                for name, v in r.items():
+                    got.setdefault(name, {"ms": [], "iters": v["iters"]})["ms"] += v["ms"]
+        for name in new:
+            assert new[name]["iters"] == old[name]["iters"], "the same count from both libraries"
+            ok = float(np.median(new[name]["ms"])) <= max(old[name]["ms"])
+            bad += 0 if ok else 1
+            out.append(f"  {which:4s} {name:16s} {new[name]['iters']} iterations: this library {spread(new[name]['ms'])} | the parent's {spread(old[name]['ms'])} -> "
+                       f"{'within' if ok else 'OUTSIDE'} the gate")
+    print("\n".join(out), flush=True)
+    with open(out_path, "a") as fh:
+        fh.write("\n".join(out) + "\n")
+    return 1 if bad else 0
+
+
 def guard_main(parent_lib, out_path):
     import json
     import subprocess
@@ -291,6 +360,11 @@ def main():
     default_obs = os.path.join(ROOT, "profiles", "block_obs_amg_time.txt")
     if len(sys.argv) == 3 and sys.argv[1] == "--guard-child":
         return guard_child(sys.argv[2])
+    if len(sys.argv) == 3 and sys.argv[1] == "--driver-guard-child":
+        return driver_guard_child(sys.argv[2])
+    if len(sys.argv) >= 3 and sys.argv[1] == "--driver-guard":
+        return driver_guard_main(os.path.abspath(sys.argv[2]), sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "handle_driver_time.txt"),
+                                 cases=tuple(sys.argv[4:]) or ("sq", "cube"))
     if len(sys.argv) >= 3 and sys.argv[1] == "--obs-guard":
         return guard_main(sys.argv[2], sys.argv[3] if len(sys.argv) > 3 else default_obs)
     from fdapde_loader import load_package

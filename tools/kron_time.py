@@ -26,6 +26,9 @@ by FDAPDE_SOLVER_KRON_AMG and the parent's solving by FDAPDE_SOLVER_GMRES altern
 
 The factored data term of fdapde_kron_set_obs:
 
+  kron_time.py --driver-guard PARENT_LIB [OUT [2d|3d ...]]     (appends to profiles/handle_driver_time.txt): the handle's solve path against the parent commit's -- one
+      FDAPDE_SOLVER_GMRES and one FDAPDE_SOLVER_KRON_AMG solve of --amg's systems at q = 2 and 10 on both meshes, five windows per process, the two libraries
+      alternating twice; the gate: this library's median is at most the largest of the parent's windows.
   kron_time.py --obs [OUT] [--parent-lib PATH] [a | a2d | a3d] [b] [c]     (OUT defaults to profiles/kron_obs_time.txt; the parts to run, all by default;
   a2d / a3d: part (a) on one of its two meshes)
 
@@ -214,6 +217,51 @@ def amg_child(mesh_key, method_name):
             row.update(refused=str(e)[:200])
         print("ROW " + json.dumps(row), flush=True)
     c.close()
+
+
+def driver_guard_child(mesh_key):
+    """one fresh process: a mesh, q = 2 and 10, five FDAPDE_SOLVER_GMRES and five FDAPDE_SOLVER_KRON_AMG solves each behind two warm-ups -> one GUARD_RESULT line"""
+    import json
+
+    from fdapde_loader import load_package
+
+    capi = load_package().capi
+    from fdapde_core_amd import meshgen
+    import block_ref as br
+    import kron_ref as kr
+
+    _, gen, nx = MESHES[mesh_key]
+    nodes, cells, bnd = getattr(meshgen, gen)(nx)
+    c = capi.Context(0)
+    c.mesh_upload(nodes, cells, bnd)
+    nd = c.dofs_build(1)
+    c.set_operator(-capi.laplacian())
+    c.set_forcing(np.zeros(c.quadrature_nodes().shape[0]))
+    c.init()
+    rp, ci = c.pattern_get()
+    r1, r0 = c.matrix_values(capi.MAT_STIFF), c.matrix_values(capi.MAT_MASS)
+    obs = br.observed_nodes(nodes.shape[0])
+    gram = br.gram_selection_values(rp, ci, obs, nd)
+    r1t = br.transpose_values(rp, ci, r1, nd)
+    res = {"lib": capi.LIB_PATH}
+    for q in (2, 10):
+        m = q // 2
+        Mt, Pt = kr.time_mass(m), kr.time_penalty(m)
+        terms = [(kr._in_block(-np.eye(m), m, 0, 0), gram), (kr._in_block(-LAMBDA * Pt, m, 0, 0), r0), (kr._in_block(LAMBDA * Mt, m, 0, 1), r1t),
+                 (kr._in_block(LAMBDA * Mt, m, 1, 0), r1), (kr._in_block(LAMBDA * Mt, m, 1, 1), r0)]   # (as amg_child)
+        b = kr.spacetime_rhs(obs, LAMBDA, nd, m)
+        c.kron_compute(terms, symmetric=True)
+        for name, method, maxit in (("GMRES", capi.SOLVER_GMRES, 1000), ("KRON_AMG", capi.SOLVER_KRON_AMG, 200)):
+            solve = lambda: c.kron_solve(b, method=method, rtol=1e-10, maxit=maxit, raise_on_noconv=False)
+            solve(), solve()
+            times = []
+            for _ in range(5):
+                t0 = time.perf_counter()
+                _, info = solve()
+                times.append(1e3 * (time.perf_counter() - t0))
+            res[f"q {q:2d} {name}"] = {"ms": times, "iters": int(info.iters)}
+    c.close()
+    print("GUARD_RESULT " + json.dumps(res))
 
 
 def amg_main(parent_lib, out_path, meshes):
@@ -441,6 +489,14 @@ def main():
         parts = [a for a in rest if a in known] or ["a", "b", "c"]
         paths = [a for a in rest if a not in known]
         return obs_main(paths[0] if paths else os.path.join(ROOT, "profiles", "kron_obs_time.txt"), parent, parts)
+    if len(sys.argv) == 3 and sys.argv[1] == "--driver-guard-child":
+        return driver_guard_child(sys.argv[2])
+    if len(sys.argv) >= 3 and sys.argv[1] == "--driver-guard":   # (the alternation and the gate are block_amg_time.py's)
+        sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+        import block_amg_time
+
+        return block_amg_time.driver_guard_main(os.path.abspath(sys.argv[2]), sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "handle_driver_time.txt"),
+                                                tool=__file__, cases=tuple(sys.argv[4:]) or ("2d", "3d"), what="fdapde_kron_solve, the space-time system of --amg (lambda = lambda_T = 1e-4), q = 2 and 10")
     if len(sys.argv) > 1 and sys.argv[1] == "--amg-child":
         return amg_child(sys.argv[2], sys.argv[3])
     if len(sys.argv) > 1 and sys.argv[1] == "--amg":
