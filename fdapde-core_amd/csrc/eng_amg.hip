@@ -21,7 +21,8 @@
 //             correction is two steps of flexible CG (GCR for a non-symmetric level) preconditioned by the next level's cycle: the K-cycle of
 //             Notay & Vassilevski -- with unsmoothed aggregation a V-cycle does not give counts independent of the mesh size.  Scalars stay on the
 //             device (fixed-order reductions, k_amg_coef); nothing returns to the host inside the cycle.
-//   outer     the flexible GMRES of the two-level solver (fgmres_outer, eng_pmg.hip).
+//   outer     the flexible GMRES of the two-level solver (fgmres_outer, eng_pmg.hip) through amg_outer_cols (amg_setup.h), the run all three multilevel solvers
+//             share; amg_run_cols brings this solver's product, residual and Dirichlet lift.  The level loop of the build pass is amg_build_levels' (amg_setup.h).
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -699,27 +700,17 @@ int amg_build_pass(fdapde_ctx* c, AmgHierarchy** slot, const double* A, int use_
     const auto t0 = std::chrono::steady_clock::now();
     std::unique_ptr<AmgHierarchy> H(new AmgHierarchy());
     H->ops = &kScalarOps, H->sym = symmetric, H->use_bnd = use_bnd, H->A = A, H->absorbed = absorb;
-    const int64_t coarse_rows = std::max<int64_t>(1, std::min<int64_t>(c->amg_coarse_rows, kDenseMaxRows));
     {
         std::unique_ptr<AmgLevel> L0(new AmgLevel());
         L0->n = c->hs.n_dofs, L0->nnz = c->hs.nnz, L0->rp = c->rowptr.p, L0->ci = c->colidx.p, L0->a = A, L0->excl = use_bnd ? c->bnd.p : nullptr;
         H->lv.push_back(std::move(L0));
     }
-    while (H->lv.back()->n > coarse_rows) {
-        AmgLevel& F = *H->lv.back();
-        std::unique_ptr<AmgLevel> N(new AmgLevel());
-        AmgVerdict verdict;
-        // (the dense limit: this solver refuses a stalled level above kDenseMaxRows whatever the knob dense_rows says; the block form of eng_block_amg.hip
-        // above min(dense_rows, kDenseMaxRows), counted in 2 n -- two rules nobody has decided between, hence a parameter)
-        if (int rc = amg_next_level(c, F, absorb, nullptr, 0, 1, coarse_rows, kDenseMaxRows, "", H->lv.size() - 1, *N, nullptr, &verdict)) return rc;
-        if (verdict == kAmgNoFreeRows) return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_AMG: a level above the dense limit has no free rows to aggregate");
-        if (verdict == kAmgStalled) {
-            *stalled = true;
-            return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_AMG: coarsening stalled above the dense limit (a level kept more than 0.8 of its rows): the matrix has too few strong couplings for pairwise aggregation");
-        }
-        if (verdict == kAmgEnd) break;
-        H->lv.push_back(std::move(N));
-    }
+    constexpr AmgBuildWords words{
+        "",
+        "FDAPDE_SOLVER_AMG: coarsening stalled above the dense limit (a level kept more than 0.8 of its rows): the matrix has too few strong couplings for pairwise aggregation",
+        "FDAPDE_SOLVER_AMG: a level above the dense limit has no free rows to aggregate", nullptr, nullptr, nullptr,
+        "FDAPDE_SOLVER_AMG: the coarsest level is singular to working precision (a pure Neumann problem has no unique solution)"};
+    if (int rc = amg_build_levels(c, *H, absorb, 0, kDenseMaxRows, words, [] { return std::unique_ptr<AmgLevel>(new AmgLevel()); }, stalled)) return rc;
     double nnz_all = 0.0;
     for (size_t l = 0; l < H->lv.size(); ++l) {
         if (int rc = level_prepare(c, *H->lv[l], l + 1 < H->lv.size())) return rc;
@@ -729,8 +720,7 @@ int amg_build_pass(fdapde_ctx* c, AmgHierarchy** slot, const double* A, int use_
     AmgLevel& C = *H->lv.back();
     const int dense_bnd = H->lv.size() == 1 ? use_bnd : 0;
     if (int rc = dense_build_csr(c, C.n, C.rp, C.ci, C.a, dense_bnd ? c->bnd.p : nullptr, dense_bnd, H->D)) return rc;
-    if (!H->D.ready)
-        return fail(c, FDAPDE_ENOCONV, "FDAPDE_SOLVER_AMG: the coarsest level is singular to working precision (a pure Neumann problem has no unique solution)");
+    if (!H->D.ready) return fail(c, FDAPDE_ENOCONV, words.coarsest_singular);
     H->setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     *slot = H.release();
     return FDAPDE_OK;
@@ -739,9 +729,6 @@ int amg_build_pass(fdapde_ctx* c, AmgHierarchy** slot, const double* A, int use_
 
 // the hierarchy of A (the context's pattern, internal order); use_bnd: level 0's Dirichlet DOFs (c->bnd) belong to no aggregate.  Knob amg_absorb: amg_build_retry
 int amg_build(fdapde_ctx* c, AmgHierarchy** slot, const double* A, int use_bnd, bool symmetric) {
-    delete *slot;
-    *slot = nullptr;
-    HIPCHK(c, hipSetDevice(c->device));
     return amg_build_retry(c, slot, [&](int absorb, bool* stalled) { return amg_build_pass(c, slot, A, use_bnd, symmetric, absorb, stalled); });
 }
 
@@ -885,69 +872,28 @@ int amg_dense_cols(fdapde_ctx* c, AmgHierarchy& H, int Q, const double* v, doubl
 
 namespace {
 // One run against the hierarchy H for Q interleaved columns: K u = rhs per column (K: A with the Dirichlet rows as unit rows if use_bnd; rhs = f on the free rows,
-// g on the Dirichlet rows), from x0 or from g / 0; f, g, x0, x interleaved on the device (x is written; g, x0 may be null).  The outer iteration is
-// fgmres_outer at width Q; relres: the true relative residuals of what is handed out.  amg_run is the call at Q = 1, a batch of the handle one at Q = 2, 4, 8
+// g on the Dirichlet rows), from x0 or from g / 0; f, g, x0, x interleaved on the device (x is written; g, x0 may be null; r: scratch).  amg_outer_cols
+// (amg_setup.h) with this solver's launches: k_amg_apply_K as the product and, rhs - K x fused into it, the residual; k_amg_start as the lift of the Dirichlet
+// data, whose residual the stop rule is relative to (as the two-level solver's).  amg_run is the call at Q = 1, a batch of the handle one at Q = 2, 4, 8
 int amg_run_cols(fdapde_ctx* c, AmgHierarchy& H, const double* A, int Q, const uint8_t* bnd, int use_bnd, const double* f, const double* g, const double* x0, double* x,
-                 double* r, double* t, double rtol, int maxit, int mk, FgmresCols& S, double* relres) {
+                 double* r, double rtol, int maxit, int mk, FgmresCols& S, double* relres) {
     hipStream_t st = c->stream;
     AmgLevel& L0 = *H.lv[0];
     const int64_t n = L0.n;
-    H.np = (int)std::min<int64_t>(1024, std::max<int64_t>(1, (n + 4095) / 4096));
-    if (int rc = amg_cols_prepare(c, H, Q)) return rc;
-    HIPCHK(c, H.basis.alloc((size_t)Q * (size_t)(2 * mk + 1) * (size_t)n));
-    HIPCHK(c, H.part.alloc((size_t)Q * (size_t)(mk + 2) * (size_t)H.np));
-    HIPCHK(c, H.dots.alloc((size_t)Q * (size_t)(mk + 4)));
-    double h[kAmgColsMax];
-    auto dots = [&](const double* a0) -> int {
-        fixed_dots_cols(st, n, H.np, Q, a0, a0, H.part.p, H.dots.p);
-        HIPCHK(c, hipMemcpyAsync(h, H.dots.p, sizeof(double) * (size_t)Q, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        return FDAPDE_OK;
-    };
     auto apply_K = [&](const double* in, const double* rhs, double* out) {   // out = K in, or (rhs given) rhs - K in
         by_team_cols<4>(L0.team, Q, [&](auto tt, auto q) {
             constexpr int T = decltype(tt)::value, QC = decltype(q)::value;
             hipLaunchKernelGGL((k_amg_apply_K<T, QC>), dim3(gn(n * T)), dim3(256), 0, st, n, L0.rp, L0.ci, A, bnd, use_bnd, in, rhs, g, out);
         });
     };
-    // the lift of the Dirichlet data: the stop rule is relative to its residual (as the two-level solver's)
-    hipLaunchKernelGGL(k_amg_start, dim3(gn(n * Q)), dim3(256), 0, st, n, Q, bnd, use_bnd, g, (const double*)nullptr, x);
-    apply_K(x, f, r);
-    if (int rc = dots(r)) return rc;
-    for (int q = 0; q < Q; ++q) S.bb[q] = S.rr[q] = h[q];
-    if (x0) {
-        hipLaunchKernelGGL(k_amg_start, dim3(gn(n * Q)), dim3(256), 0, st, n, Q, bnd, use_bnd, g, x0, x);
-        apply_K(x, f, r);
-        if (int rc = dots(r)) return rc;
-        std::copy(h, h + Q, S.rr);
-    }
-    for (int q = 0; q < Q; ++q) S.converged[q] = S.rr[q] <= rtol * rtol * S.bb[q], S.broke[q] = false;
-    const bool one_level = H.lv.size() == 1;
-    auto precond = [&](const double* v, double* z, double* w, bool&) -> int {
-        if (one_level) {
-            if (int rc = amg_dense_cols(c, H, Q, v, z)) return rc;
-        } else if (int rc = amg_cycle(c, H, 0, Q, v, z))
-            return rc;
-        apply_K(z, nullptr, w);
+    auto residual = [&](const double* in, double* out) { apply_K(in, f, out); };
+    auto start = [&](bool again) -> int {
+        hipLaunchKernelGGL(k_amg_start, dim3(gn(n * Q)), dim3(256), 0, st, n, Q, bnd, use_bnd, g, again ? x0 : (const double*)nullptr, x);
+        if (!again) residual(x, r);
         return FDAPDE_OK;
     };
-    auto residual = [&](double* rr_out) -> int {
-        apply_K(x, f, r);
-        if (int rc = dots(r)) return rc;
-        std::copy(h, h + Q, rr_out);
-        return FDAPDE_OK;
-    };
-    FgmresSpace fs{n, mk, H.basis.p, H.basis.p + (size_t)(mk + 1) * (size_t)n * (size_t)Q, H.part.p, H.dots.p, H.np};
-    if (int rc = fgmres_outer(c, fs, Q, x, r, nullptr, rtol, maxit, precond, residual, S)) return rc;
-    // the TRUE residuals of what is handed out
-    apply_K(x, f, t);
-    if (int rc = dots(t)) return rc;
-    for (int q = 0; q < Q; ++q) {
-        relres[q] = S.bb[q] > 0 ? std::sqrt(h[q] / S.bb[q]) : 0.0;
-        if (S.converged[q] && !(relres[q] <= 10.0 * rtol)) S.converged[q] = false;
-    }
-    HIPCHK(c, hipGetLastError());
-    return FDAPDE_OK;
+    return amg_outer_cols(c, H, Q, mk, kAmgRunLifted, [&](const double* in, double* out) { apply_K(in, nullptr, out); }, residual, start, x0 != nullptr, x, r, rtol, maxit, S,
+                          relres);
 }
 }   // namespace
 
@@ -958,11 +904,11 @@ int amg_run(fdapde_ctx* c, AmgHierarchy* hp, const double* A, const double* f_de
     hipStream_t st = c->stream;
     const int64_t n = H.lv[0]->n;
     const auto t_begin = std::chrono::steady_clock::now();
-    HIPCHK(c, H.vec.alloc(3 * (size_t)n));
-    double *x = H.vec.p, *r = x + n, *t = r + n;
+    HIPCHK(c, H.vec.alloc(2 * (size_t)n));
+    double *x = H.vec.p, *r = x + n;
     FgmresCols S{};
     double true_rel = 0.0;
-    if (int rc = amg_run_cols(c, H, A, 1, c->bnd.p, use_bnd, f_dev, g_dev, x0_dev, x, r, t, rtol, maxit, amg_restart_len(n, maxit), S, &true_rel)) return rc;
+    if (int rc = amg_run_cols(c, H, A, 1, c->bnd.p, use_bnd, f_dev, g_dev, x0_dev, x, r, rtol, maxit, amg_restart_len(n, maxit), S, &true_rel)) return rc;
     const int it = S.it[0];
     const bool converged = S.converged[0], broke = S.broke[0];
     HIPCHK(c, c->u.alloc((size_t)n));
@@ -974,10 +920,8 @@ int amg_run(fdapde_ctx* c, AmgHierarchy* hp, const double* A, const double* f_de
     c->info.method_used = FDAPDE_SOLVER_AMG, c->info.iters = it, c->info.converged = converged ? 1 : 0, c->info.relres = true_rel, c->info.persistent = 0;
     c->info.t_solve_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
     if (std::getenv("FDAPDE_DEBUG_SETUP")) {
-        std::string rows;
-        for (size_t l = 0; l < H.lv.size(); ++l) rows += (l ? " / " : "") + std::to_string(H.lv[l]->n);
         std::fprintf(stderr, "amg: %zu levels, rows %s, operator complexity %.3f, set-up %.2f ms, solve %.2f ms, %d iterations, true relres %.2e, absorbed %d, discarded build %.2f ms\n",
-                     H.lv.size(), rows.c_str(), H.op_complexity, H.setup_ms, c->info.t_solve_ms, it, true_rel, H.absorbed, H.discarded_ms);
+                     H.lv.size(), amg_rows_text(H).c_str(), H.op_complexity, H.setup_ms, c->info.t_solve_ms, it, true_rel, H.absorbed, H.discarded_ms);
     }
     if (!converged) {
         c->err = broke ? "FDAPDE_SOLVER_AMG: the flexible GMRES broke down" : "FDAPDE_SOLVER_AMG: maxit reached";
@@ -1048,13 +992,13 @@ int amg_lin_solve(fdapde_ctx* c, const fdapde_options* opt, const double* b, int
         if (Q > 1) {
             const size_t nq = (size_t)n * (size_t)Q;
             HIPCHK(c, H.qio.alloc(nq));
-            HIPCHK(c, H.qvec.alloc(4 * nq));
-            double *f = H.qvec.p, *xq = f + nq, *r = xq + nq, *t = r + nq;
+            HIPCHK(c, H.qvec.alloc(3 * nq));
+            double *f = H.qvec.p, *xq = f + nq, *r = xq + nq;
             HIPCHK(c, hipMemcpyAsync(H.qio.p, b + (size_t)j * n, sizeof(double) * nq, hipMemcpyHostToDevice, st));   // (one copy per batch)
             hipLaunchKernelGGL(k_amg_gather, dim3(gn(n * Q)), dim3(256), 0, st, n, Q, c->dof_i2e.p, (const double*)H.qio.p, f);
             FgmresCols S{};
             double rel[kAmgColsMax];
-            if (int rc = amg_run_cols(c, H, c->lin_mat.p, Q, nullptr, 0, f, nullptr, nullptr, xq, r, t, rtol, maxit, mk, S, rel)) return rc;
+            if (int rc = amg_run_cols(c, H, c->lin_mat.p, Q, nullptr, 0, f, nullptr, nullptr, xq, r, rtol, maxit, mk, S, rel)) return rc;
             ++H.batches, H.batched_cols += Q;
             for (int q = 0; q < Q; ++q) {
                 bool conv = S.converged[q];

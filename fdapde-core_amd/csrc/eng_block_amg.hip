@@ -16,7 +16,8 @@
 //             correction is always two GCR steps preconditioned by the next level's cycle -- GCR because the system is indefinite (flexible CG may divide
 //             by zero), no early exit (it would need a host read-back inside the cycle).
 //   outer     fgmres_outer (eng_pmg.hip) on the UNSCALED system, right-preconditioned by the cycle; the stop rule is the true residual |b - A x| <= rtol |b|.
-//             The run of Q columns is amg_point_cols (amg_setup.h, shared with eng_kron_amg.hip) with this handle's product; the loop over a call's columns is
+//             The run of Q columns is amg_outer_cols (amg_setup.h, shared with eng_amg.hip and eng_kron_amg.hip) with this handle's product; the build pass is
+//             amg_build_levels, amg_point_smoothers and amg_point_finish (amg_setup.h, shared with eng_kron_amg.hip) around this form's own steps; the loop over a call's columns is
 //             handle_solve's (eng_handle.h), which takes block_amg_run and -- for batches -- block_amg_batch from eng_block.hip's callables.
 //   the term  (knob block_amg_obs = 1) a live factored data term scale [Psi^T W Psi, 0; 0, 0] rides beside the pattern levels: P = P_s (x) I_2 with entries 1, so
 //             its Galerkin product is the term of Psi_{l+1} = Psi_l P_s (host_obs.h obs_coarsen: the same rows, columns through agg).  The aggregates do not see
@@ -60,9 +61,7 @@ struct BamgTerm {
     DBuf<double> v_own, tv_own, g_own;
     DBuf<double> t, t2, s;                        // t [n_obs]: W Psi_l zt between pre- and post-smoothing; t2 [n_obs], s [n_l]: the products of y = A x
 };
-struct BamgLevel : AmgLevel {
-    const double* bv = nullptr;                   // four doubles per entry (level 0: the handle's)
-    DBuf<double> bv_own, dinv4;                   // (dinv4: the inverted 2 x 2 diagonal blocks, four doubles per row)
+struct BamgLevel : AmgLevel {                     // (pay: the four block values per entry; dinv: the inverted 2 x 2 diagonal blocks, four doubles per row)
     std::unique_ptr<BamgTerm> term;               // the carried data term, or none
 };
 inline BamgLevel& blk(AmgLevel& L) { return static_cast<BamgLevel&>(L); }
@@ -90,19 +89,10 @@ void term_scatter_store(hipStream_t st, const BamgTerm& O, int64_t n, const doub
 void block_amg_free(BlockAmg* h) { delete h; }
 
 namespace {
-// D^-1 of a level's diagonal blocks (today's 1e-14 rule: k_block_diag_inv); *bad: a block was singular
-int level_dinv(fdapde_ctx* c, BamgLevel& L, bool* bad) {   // (with a carried term D is judged with its share g_l)
-    hipStream_t st = c->stream;
-    DBuf<int32_t> flag;
-    HIPCHK(c, flag.alloc(1));
-    HIPCHK(c, hipMemsetAsync(flag.p, 0, sizeof(int32_t), st));
-    HIPCHK(c, L.dinv4.alloc(4 * (size_t)L.n));
-    hipLaunchKernelGGL(k_block_diag_inv, dim3(gn(L.n)), dim3(256), 0, st, L.n, L.rp, L.ci, L.bv, L.term ? L.term->g : (const double*)nullptr, L.dinv4.p, flag.p);
-    HIPCHK(c, hipGetLastError());
-    int32_t h = 0;
-    HIPCHK(c, hipMemcpyAsync(&h, flag.p, sizeof h, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    *bad = h != 0;
+// D^-1 of a level's diagonal blocks (today's 1e-14 rule: k_block_diag_inv; with a carried term D is judged with its share g_l); flag: a block was singular
+int level_dinv(fdapde_ctx* c, BamgLevel& L, int32_t* flag) {
+    HIPCHK(c, L.dinv.alloc(4 * (size_t)L.n));
+    hipLaunchKernelGGL(k_block_diag_inv, dim3(gn(L.n)), dim3(256), 0, c->stream, L.n, L.rp, L.ci, L.pay, L.term ? L.term->g : (const double*)nullptr, L.dinv.p, flag);
     return FDAPDE_OK;
 }
 
@@ -117,7 +107,7 @@ void level_team(AmgLevel& L) {
 void block_pre_restrict(hipStream_t st, int Q, AmgLevel& L, AmgLevel& N, const double* r, double* rc, int64_t rs, int64_t cs) {
     by_team_cols<8>(L.team, Q, [&](auto t, auto q) {
         constexpr int T = decltype(t)::value, QC = decltype(q)::value;
-        hipLaunchKernelGGL((k_bamg_pre_restrict<T, QC>), dim3(g1(N.n, 256 / T)), dim3(256), 0, st, N.n, L.mptr.p, L.midx.p, L.rp, L.ci, blk(L).bv, blk(L).dinv4.p, kBamgOmega,
+        hipLaunchKernelGGL((k_bamg_pre_restrict<T, QC>), dim3(g1(N.n, 256 / T)), dim3(256), 0, st, N.n, L.mptr.p, L.midx.p, L.rp, L.ci, L.pay, L.dinv.p, kBamgOmega,
                            r, L.zt.p, rc, rs, cs);
     });
     if (BamgTerm* O = blk(L).term.get()) {   // (Q = 1, so rc[2 I] is the first unknown of aggregate I under either layout) rc -= P^T [scale Psi_l^T t; 0], t = W Psi_l zt
@@ -128,12 +118,12 @@ void block_pre_restrict(hipStream_t st, int Q, AmgLevel& L, AmgLevel& N, const d
 void block_post(hipStream_t st, int Q, AmgLevel& L, AmgLevel& N, const double* r, double* out) {
     by_team_cols<8>(L.team, Q, [&](auto t, auto q) {
         constexpr int T = decltype(t)::value, QC = decltype(q)::value;
-        hipLaunchKernelGGL((k_bamg_post<T, QC>), dim3(g1(L.n, 256 / T)), dim3(256), 0, st, L.n, L.rp, L.ci, blk(L).bv, blk(L).dinv4.p, kBamgOmega, L.agg.p, N.e.p, r,
+        hipLaunchKernelGGL((k_bamg_post<T, QC>), dim3(g1(L.n, 256 / T)), dim3(256), 0, st, L.n, L.rp, L.ci, L.pay, L.dinv.p, kBamgOmega, L.agg.p, N.e.p, r,
                            L.zt.p, out);
     });
     if (BamgTerm* O = blk(L).term.get()) {   // t += W Psi_{l+1} e: t = W Psi_l (zt + P e); out -= om D^-1 [scale Psi_l^T t; 0]
         term_gather(st, *blk(N).term, N.e.p, O->t.p, true);
-        term_scatter(st, *O, L.n, O->t.p, -kBamgOmega * O->scale, blk(L).dinv4.p, out);
+        term_scatter(st, *O, L.n, O->t.p, -kBamgOmega * O->scale, L.dinv.p, out);
     }
 }
 void block_spmv_dots(hipStream_t st, int Q, AmgLevel& L, const double* x, double* y, const double* p0, const double* q0, const double* p1, const double* q1,
@@ -141,13 +131,13 @@ void block_spmv_dots(hipStream_t st, int Q, AmgLevel& L, const double* x, double
     if (BamgTerm* O = blk(L).term.get()) {   // (Q = 1) the term is inside y before the dots: s = scale Psi_l^T W Psi_l x_1 joins the rows of k_bamg_spmv_dots
         term_gather(st, *O, x, O->t2.p, false);
         term_scatter_store(st, *O, L.n, O->t2.p, O->scale, O->s.p);
-        if (L.team <= 8) hipLaunchKernelGGL((k_bamg_spmv_dots<8, 1, true>), dim3((unsigned)L.np), dim3(256), 0, st, L.n, L.rp, L.ci, blk(L).bv, x, y, p0, q0, p1, q1, p2, q2, L.part.p, (const double*)O->s.p);
-        else hipLaunchKernelGGL((k_bamg_spmv_dots<16, 1, true>), dim3((unsigned)L.np), dim3(256), 0, st, L.n, L.rp, L.ci, blk(L).bv, x, y, p0, q0, p1, q1, p2, q2, L.part.p, (const double*)O->s.p);
+        if (L.team <= 8) hipLaunchKernelGGL((k_bamg_spmv_dots<8, 1, true>), dim3((unsigned)L.np), dim3(256), 0, st, L.n, L.rp, L.ci, L.pay, x, y, p0, q0, p1, q1, p2, q2, L.part.p, (const double*)O->s.p);
+        else hipLaunchKernelGGL((k_bamg_spmv_dots<16, 1, true>), dim3((unsigned)L.np), dim3(256), 0, st, L.n, L.rp, L.ci, L.pay, x, y, p0, q0, p1, q1, p2, q2, L.part.p, (const double*)O->s.p);
         return;
     }
     by_team_cols<8>(L.team, Q, [&](auto t, auto q) {
         constexpr int T = decltype(t)::value, QC = decltype(q)::value;
-        hipLaunchKernelGGL((k_bamg_spmv_dots<T, QC>), dim3((unsigned)L.np), dim3(256), 0, st, L.n, L.rp, L.ci, blk(L).bv, x, y, p0, q0, p1, q1, p2, q2, L.part.p);
+        hipLaunchKernelGGL((k_bamg_spmv_dots<T, QC>), dim3((unsigned)L.np), dim3(256), 0, st, L.n, L.rp, L.ci, L.pay, x, y, p0, q0, p1, q1, p2, q2, L.part.p);
     });
 }
 constexpr AmgCycleOps kBlockOps{block_pre_restrict, block_post, block_spmv_dots};
@@ -204,7 +194,7 @@ int block_amg_merge_coarsest(fdapde_ctx* c, BlockAmg& H, const BlockAmgTerm& src
     HIPCHK(c, hipStreamSynchronize(st));
     if (int rc = fetch(c, C.rp, (size_t)C.n + 1, rp)) return rc;
     if (int rc = fetch(c, C.ci, (size_t)C.nnz, ci)) return rc;
-    if (int rc = fetch(c, C.bv, 4 * (size_t)C.nnz, bv)) return rc;
+    if (int rc = fetch(c, C.pay, 4 * (size_t)C.nnz, bv)) return rc;
     fdapde_hip::obs_merge_dense(rp.data(), ci.data(), bv.data(), H.lv.size() == 1 ? *src.host : C.term->host, src.scale, &rp2, &ci2, &v2);
     HIPCHK(c, H.rp2.upload(rp2.data(), rp2.size(), st));
     HIPCHK(c, H.ci2.upload(ci2.data(), ci2.size(), st));
@@ -213,7 +203,17 @@ int block_amg_merge_coarsest(fdapde_ctx* c, BlockAmg& H, const BlockAmgTerm& src
     return FDAPDE_OK;
 }
 
-// the hierarchy with (absorb) or without absorption on every level; *stalled: the answer is the "coarsening stalled above the dense limit" refusal
+constexpr AmgBuildWords kBlockBuildWords{
+    "block ",
+    "FDAPDE_SOLVER_BLOCK_AMG: coarsening stalled above the dense limit (a level kept more than 0.8 of its rows): the strength block has too few strong couplings for pairwise aggregation",
+    nullptr,
+    "FDAPDE_SOLVER_BLOCK_AMG: a DOF's diagonal block is singular (|det| <= 1e-14 max|entry|^2): no block-Jacobi smoother",
+    "FDAPDE_SOLVER_BLOCK_AMG: a coarse level has a singular diagonal block and the level above it is too large for the dense inverse",
+    "FDAPDE_SOLVER_BLOCK_AMG: the coarsest level is too large for the dense inverse",
+    "FDAPDE_SOLVER_BLOCK_AMG: the coarsest level is singular to working precision"};
+
+// the hierarchy with (absorb) or without absorption on every level, in the order amg_setup.h gives a point-block pass; *stalled: the answer is the "coarsening
+// stalled above the dense limit" refusal.  This form's level 0: the strength matrix is the picked block, the four block values its payload
 int block_amg_build_pass(fdapde_ctx* c, BlockAmg** slot, const double* raw, int strength_block, const BlockAmgTerm* term, int absorb, bool* stalled) {
     *stalled = false;
     hipStream_t st = c->stream;
@@ -221,71 +221,36 @@ int block_amg_build_pass(fdapde_ctx* c, BlockAmg** slot, const double* raw, int 
     std::unique_ptr<BlockAmg> H(new BlockAmg());
     // (GCR, not flexible CG, because the system is indefinite)
     H->ops = &kBlockOps, H->per = 2, H->sym = false, H->absorbed = absorb;
-    const int64_t dense_limit = std::min<int64_t>(c->dense_rows, kDenseMaxRows);
-    const int64_t coarse_rows = std::max<int64_t>(2, std::min<int64_t>(c->amg_coarse_rows, kDenseMaxRows));
     {
         std::unique_ptr<BamgLevel> L0(new BamgLevel());
-        L0->n = c->hs.n_dofs, L0->nnz = c->hs.nnz, L0->rp = c->rowptr.p, L0->ci = c->colidx.p, L0->bv = raw;
+        L0->n = c->hs.n_dofs, L0->nnz = c->hs.nnz, L0->rp = c->rowptr.p, L0->ci = c->colidx.p, L0->pay = raw;
         HIPCHK(c, L0->a_own.alloc((size_t)std::max<int64_t>(L0->nnz, 1)));
         hipLaunchKernelGGL(k_bamg_pick, dim3(gn(L0->nnz)), dim3(256), 0, st, L0->nnz, raw, strength_block, L0->a_own.p);
         HIPCHK(c, hipGetLastError());
         L0->a = L0->a_own.p;
         H->lv.push_back(std::move(L0));
     }
-    while (2 * H->lv.back()->n > coarse_rows) {
-        BamgLevel& F = blk(*H->lv.back());
-        std::unique_ptr<BamgLevel> N(new BamgLevel());
-        AmgVerdict verdict;
-        // the level step on the strength matrix; the block values follow as its payload (the dense limit: see amg_build_pass, eng_amg.hip)
-        if (int rc = amg_next_level(c, F, absorb, F.bv, 4, 2, coarse_rows, dense_limit, "block ", H->lv.size() - 1, *N, &N->bv_own, &verdict)) return rc;
-        if (verdict == kAmgStalled) {
-            *stalled = true;
-            return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_BLOCK_AMG: coarsening stalled above the dense limit (a level kept more than 0.8 of its rows): the strength block has too few strong couplings for pairwise aggregation");
-        }
-        if (verdict != kAmgNext) break;   // (kAmgNoFreeRows does not arise: no row is excluded)
-        N->bv = N->bv_own.p;
-        H->lv.push_back(std::move(N));
-    }
-    if (term) {   // (the aggregates are the pattern's: the term follows them)
+    if (int rc = amg_build_levels(c, *H, absorb, 4, amg_point_dense_limit(c), kBlockBuildWords, [] { return std::unique_ptr<AmgLevel>(new BamgLevel()); }, stalled)) return rc;
+    if (term) {   // (the aggregates are the pattern's: the term follows them; before the smoothers, because g_l is part of D)
         const auto t1 = std::chrono::steady_clock::now();
         if (int rc = block_amg_attach_term(c, *H, *term)) return rc;
         H->term_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
     }
-    // the smoother of every level that has a next one; a singular diagonal block below level 0 ends the hierarchy one level above
-    for (size_t l = 0; l + 1 < H->lv.size(); ++l) {
-        bool bad = false;
-        if (int rc = level_dinv(c, blk(*H->lv[l]), &bad)) return rc;
-        if (!bad) continue;
-        if (l == 0) return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_BLOCK_AMG: a DOF's diagonal block is singular (|det| <= 1e-14 max|entry|^2): no block-Jacobi smoother");
-        if (2 * H->lv[l - 1]->n > dense_limit)
-            return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_BLOCK_AMG: a coarse level has a singular diagonal block and the level above it is too large for the dense inverse");
-        H->lv.resize(l);
-        BamgLevel& E = blk(*H->lv.back());
-        E.agg.release(), E.mptr.release(), E.midx.release(), E.dinv4.release();
-        break;
-    }
+    if (int rc = amg_point_smoothers(c, *H, 0, kBlockBuildWords, [&](AmgLevel& L, int32_t* flag) { return level_dinv(c, blk(L), flag); })) return rc;
     for (auto& L : H->lv) level_team(*L);
-    for (size_t l = 0; l + 1 < H->lv.size(); ++l) H->lv[l]->om = kBamgOmega;   // (what fdapde_amg_damping answers; the kernels take the constant)
-    if (int rc = amg_cols_prepare(c, *H, 1)) return rc;   // (the work vectors: one column until a batch asks for more)
-    BamgLevel& C = blk(*H->lv.back());
-    if (2 * C.n > kDenseMaxRows) return fail(c, FDAPDE_EUNSUPPORTED, "FDAPDE_SOLVER_BLOCK_AMG: the coarsest level is too large for the dense inverse");
-    if (term) {
-        if (int rc = block_amg_merge_coarsest(c, *H, *term)) return rc;
-    } else {
+    auto expand = [&](AmgLevel& C) -> int {
+        if (term) return block_amg_merge_coarsest(c, *H, *term);
         HIPCHK(c, H->rp2.alloc((size_t)(2 * C.n + 1)));
         HIPCHK(c, H->ci2.alloc((size_t)std::max<int64_t>(4 * C.nnz, 1)));
         HIPCHK(c, H->val2.alloc((size_t)std::max<int64_t>(4 * C.nnz, 1)));
-        hipLaunchKernelGGL(k_block_expand, dim3(gn(C.n + 1)), dim3(256), 0, st, C.n, C.rp, C.ci, C.bv, H->rp2.p, H->ci2.p, H->val2.p);
+        hipLaunchKernelGGL(k_block_expand, dim3(gn(C.n + 1)), dim3(256), 0, st, C.n, C.rp, C.ci, C.pay, H->rp2.p, H->ci2.p, H->val2.p);
         HIPCHK(c, hipGetLastError());
-    }
-    if (int rc = dense_build_csr(c, 2 * C.n, H->rp2.p, H->ci2.p, H->val2.p, nullptr, 0, H->D)) return rc;
-    if (!H->D.ready) return fail(c, FDAPDE_ENOCONV, "FDAPDE_SOLVER_BLOCK_AMG: the coarsest level is singular to working precision");
-    H->setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (std::getenv("FDAPDE_DEBUG_SETUP")) {
-        std::string rows;
-        for (size_t l = 0; l < H->lv.size(); ++l) rows += (l ? " / " : "") + std::to_string(2 * H->lv[l]->n);
-        std::fprintf(stderr, "block amg: %zu levels, rows %s, set-up %.2f ms (the data term %.2f), absorbed %d\n", H->lv.size(), rows.c_str(), H->setup_ms, H->term_ms, H->absorbed);
-    }
+        return FDAPDE_OK;
+    };
+    if (int rc = amg_point_finish(c, *H, kBamgOmega, kBlockBuildWords, t0, expand)) return rc;
+    if (std::getenv("FDAPDE_DEBUG_SETUP"))
+        std::fprintf(stderr, "block amg: %zu levels, rows %s, set-up %.2f ms (the data term %.2f), absorbed %d\n", H->lv.size(), amg_rows_text(*H).c_str(), H->setup_ms, H->term_ms,
+                     H->absorbed);
     *slot = H.release();
     return FDAPDE_OK;
 }
@@ -294,9 +259,6 @@ int block_amg_build_pass(fdapde_ctx* c, BlockAmg** slot, const double* raw, int 
 // the hierarchy of the handle's matrix: raw = the unscaled block CSR on the context's pattern, strength_block = which of its four blocks the aggregation reads.
 // Knob amg_absorb: amg_build_retry (amg_setup.h).  term: the handle's live data term for the levels to carry (knob block_amg_obs), or NULL
 int block_amg_build(fdapde_ctx* c, BlockAmg** slot, const double* raw, int strength_block, const BlockAmgTerm* term) {
-    delete *slot;
-    *slot = nullptr;
-    HIPCHK(c, hipSetDevice(c->device));
     return amg_build_retry(c, slot, [&](int absorb, bool* stalled) { return block_amg_build_pass(c, slot, raw, strength_block, term, absorb, stalled); });
 }
 
@@ -318,14 +280,15 @@ bool block_amg_has_term(const BlockAmg* H) { return H && H->term; }
 
 
 namespace {
-// Q columns side by side against the hierarchy: amg_point_cols (amg_setup.h) with the product of the matrix the hierarchy was built from (raw, and the carried
-// term).  block_amg_run is the call at Q = 1, block_amg_batch drives those at Q = 2, 4, 8
+// Q columns side by side against the hierarchy: amg_outer_cols (amg_setup.h) under the point-block rules, with the product of the matrix the hierarchy was
+// built from (raw, and the carried term).  block_amg_run is the call at Q = 1, block_amg_batch drives those at Q = 2, 4, 8
 int block_amg_cols(fdapde_ctx* c, BlockAmg& H, const double* raw, int Q, const double* b, double* x, double* r, double* t, bool warm, double rtol, int maxit,
                    FgmresCols& S, double* rel) {
     hipStream_t st = c->stream;
     AmgLevel& L0 = *H.lv[0];
     const int64_t n = L0.n;
-    return amg_point_cols(c, H, Q, [&](const double* in, double* out) {   // (one column: the block handle's own kernel)
+    const size_t nq = 2 * (size_t)n * (size_t)Q;
+    auto spmv = [&](const double* in, double* out) {   // (one column: the block handle's own kernel)
         if (Q == 1) {
             hipLaunchKernelGGL(k_block_spmv<kBlockTeam>, dim3(g1(n, 256 / kBlockTeam)), dim3(256), 0, st, n, L0.rp, L0.ci, raw, in, out, (const int32_t*)nullptr);
             if (BamgTerm* O = blk(L0).term.get()) {   // ... and the term's two products behind it
@@ -339,7 +302,9 @@ int block_amg_cols(fdapde_ctx* c, BlockAmg& H, const double* raw, int Q, const d
             if constexpr (QC > 1)
                 hipLaunchKernelGGL((k_block_spmv_cols<kBlockTeam, QC>), dim3(g1(n, 256 / kBlockTeam)), dim3(256), 0, st, n, L0.rp, L0.ci, raw, in, out);
         });
-    }, b, x, r, t, warm, rtol, maxit, S, rel);
+    };
+    return amg_outer_cols(c, H, Q, amg_point_restart_len(c, maxit), kAmgRunPoint, spmv, amg_point_residual(st, spmv, nq, b, t), amg_point_start(c, nq, b, x, r, warm), warm,
+                          x, r, rtol, maxit, S, rel);
 }
 }   // namespace
 

@@ -241,6 +241,8 @@ def test_pure_neumann_is_refused(env):
     with pytest.raises(capi.FdapdeError) as e:
         c.solve(method=capi.SOLVER_AMG)
     assert e.value.status == capi.ENOCONV
+    assert str(e.value) == (f"[status {capi.ENOCONV}] FDAPDE_SOLVER_AMG: the coarsest level is singular to working precision "
+                            "(a pure Neumann problem has no unique solution)")
     c.close()
 
 

@@ -284,6 +284,8 @@ def test_the_smallest_refusal_is_solved_by_the_default(env):
     with pytest.raises(capi.FdapdeError) as e:
         c.block_solve(b, method=capi.SOLVER_BLOCK_AMG, rtol=ar.RTOL, maxit=ab.CAP_BLOCK)
     assert e.value.status == capi.EUNSUPPORTED and "stalled" in str(e.value)
+    assert str(e.value) == (f"[status {capi.EUNSUPPORTED}] FDAPDE_SOLVER_BLOCK_AMG: coarsening stalled above the dense limit (a level kept more than 0.8 of its rows): "
+                            "the strength block has too few strong couplings for pairwise aggregation")
     c.close()
     x_lu = spl.splu(A.tocsc()).solve(b)
     x_ref, it_ref, ok_ref, rows_ref = ab.block_solve(rp, ci, blocks, nd, b, True, ab.BLOCK_COARSE_ROWS, ab.BLOCK_DENSE_ROWS)
@@ -334,6 +336,8 @@ def test_c3_is_solved_by_the_default(env):
     with pytest.raises(capi.FdapdeError) as e:
         c.solve(method=capi.SOLVER_AMG, rtol=1e-10)
     assert e.value.status == capi.EUNSUPPORTED and "stalled" in str(e.value)
+    assert str(e.value) == (f"[status {capi.EUNSUPPORTED}] FDAPDE_SOLVER_AMG: coarsening stalled above the dense limit (a level kept more than 0.8 of its rows): "
+                            "the matrix has too few strong couplings for pairwise aggregation")
     c.tune("amg_absorb", 2)
     info = c.solve(method=capi.SOLVER_AMG, rtol=1e-10, maxit=38, raise_on_noconv=False)
     h = c.amg_hierarchy(capi.AMG_OF_SOLVE)

@@ -250,4 +250,5 @@ def test_singular_diagonal_block_on_level_0(env):
     with pytest.raises(capi.FdapdeError) as e:
         c.block_solve(br.smoothing_rhs(obs, 1e-4, nd), method=capi.SOLVER_BLOCK_AMG)
     assert e.value.status == capi.EUNSUPPORTED
+    assert str(e.value) == f"[status {capi.EUNSUPPORTED}] FDAPDE_SOLVER_BLOCK_AMG: a DOF's diagonal block is singular (|det| <= 1e-14 max|entry|^2): no block-Jacobi smoother"
     c.close()

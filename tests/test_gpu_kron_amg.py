@@ -280,6 +280,8 @@ def test_refusals(env):
     with pytest.raises(capi.FdapdeError) as e:
         c.kron_solve(b, method=capi.SOLVER_KRON_AMG)
     assert e.value.status == capi.EUNSUPPORTED and "kron_dinv_mb" in str(e.value)
+    assert str(e.value) == (f"[status {capi.EUNSUPPORTED}] FDAPDE_SOLVER_KRON_AMG: the inverted diagonal blocks (8 q^2 n bytes) exceed the budget `kron_dinv_mb`: "
+                            "no block-Jacobi smoother")
     c.tune("kron_dinv_mb", 2048)
     c.kron_compute(terms)
     # a term the handle was not given
@@ -301,6 +303,8 @@ def test_refusals(env):
     with pytest.raises(capi.FdapdeError) as e:
         c.kron_solve(np.ones(3 * nd), method=capi.SOLVER_KRON_AMG)
     assert e.value.status == capi.EUNSUPPORTED and "diagonal block is singular" in str(e.value)
+    assert str(e.value) == (f"[status {capi.EUNSUPPORTED}] FDAPDE_SOLVER_KRON_AMG: a DOF's diagonal block is singular (a pivot <= 1e-14 max|entry|): "
+                            "no block-Jacobi smoother")
     c.close()
 
 

@@ -1,4 +1,5 @@
-"""The block and Kronecker handles through their shared solve driver (csrc/eng_handle.h) against the parent commit's library: the same bits, and no slower.
+"""The block and Kronecker handles through their shared solve driver (csrc/eng_handle.h), and the scalar entry points through FDAPDE_SOLVER_AMG's outer run
+(csrc/amg_setup.h), against the parent commit's library: the same bits, and no slower.
 
   handle_driver_bits.py PARENT_LIB [OUT]          (OUT defaults to profiles/handle_driver_bits.txt)
   handle_driver_bits.py --time PARENT_LIB [OUT]   (OUT defaults to profiles/handle_driver_time.txt)
@@ -9,9 +10,14 @@ Bits.  A case is a handle (block, kron), one of the three fixtures of tests/test
 matrix each: every method (FDAPDE_SOLVER_GMRES, FDAPDE_SOLVER_DENSE, the open method, FDAPDE_SOLVER_BLOCK_AMG / _KRON_AMG), one and five columns, in place and
 out of place.  Compared: x byte for byte (its SHA-256), info.iters, relres (as bits), converged, method_used -- or, where the call is refused, the status and
 the message.  The parent runs twice first: a sub-case where it does not repeat itself is reported with that difference instead of being compared.
+A third kind of case, "scalar", runs one fixture through fdapde_solve with FDAPDE_SOLVER_AMG (with and without Dirichlet data), fdapde_solve_parabolic with it
+over three steps (the start from x0: every step after the first starts from the step before) and fdapde_lin_solve with it at 1, 5 and 8 columns under
+`amg_cols` 8 and 1, in place and out of place.  A scalar sub-case must SOLVE: a status other than FDAPDE_OK / FDAPDE_ENOCONV ends the tool with an error instead of
+being compared as a refusal (fdapde_solve_parabolic must converge as well).
 
 Time.  Host overhead per column is what the driver could have changed: 64 columns through each stage (GMRES, DENSE, multilevel) at 289 DOFs, wall time of
-the call.  The two libraries alternate, five windows each, every window a fresh process with one warm-up call per figure.  The gate: this tree's median is at
+the call; the "scalar" rows are 64 columns through fdapde_lin_solve under FDAPDE_SOLVER_AMG and one solve at the size of amg_cols_time.py (29 791 DOFs,
+eight columns).  The two libraries alternate, five windows each, every window a fresh process with one warm-up call per figure.  The gate: this tree's median is at
 most the largest of the parent's five windows.  (One solve per stage at the sizes of DESIGN 14 / 15: block_amg_time.py --driver-guard, kron_time.py
 --driver-guard; they append to the same file.)"""
 import hashlib
@@ -92,8 +98,116 @@ def bits_child(handle, name, order, term):
     c.close()
 
 
+def _scalar(name, order, op=None, dirichlet=False, times=None):
+    """-> (capi, context, n_dofs) with the operator's system assembled (-laplacian + reaction(1) unless op says otherwise); times: one forcing column per time
+    point (what fdapde_solve_parabolic takes)"""
+    from fdapde_loader import load_package
+
+    load_package()
+    from fdapde_core_amd import capi, workloads
+
+    c = capi.Context(0)
+    c.mesh_upload(*workloads.load_fixture_mesh(os.path.join(ROOT, "tests", "golden", "mesh", name)))
+    nd = c.dofs_build(order)
+    c.tune("amg_coarse_rows", 256)
+    c.set_operator(op(capi) if op else -capi.laplacian() + capi.reaction(1.0))
+    qn = c.quadrature_nodes()
+    f = np.sin(2.0 * qn[:, 0]) + 1.0
+    c.set_forcing(f if times is None else np.stack([(1.0 + t) * f for t in times], axis=1))
+    if dirichlet:
+        c.set_dirichlet(c.dofs_get()[2].sum(axis=1))
+    c.init()
+    return capi, c, nd
+
+
+def _row(sub, x, info):
+    return {"sub": sub, "x": hashlib.sha256(np.ascontiguousarray(x).tobytes()).hexdigest(), "iters": int(info.iters), "relres": float(info.relres).hex(),
+            "converged": int(info.converged), "method_used": int(info.method_used)}
+
+
+def scalar_child(name, order):
+    import ctypes as C
+
+    from fdapde_loader import load_package
+
+    load_package()
+    from fdapde_core_amd import capi
+
+    order = int(order)
+    rows = []
+
+    def attempt(sub, run):   # (a scalar sub-case that does not reach the solver compares nothing: it is an error, not a row)
+        try:
+            x, info = run()
+        except capi.FdapdeError as e:
+            raise SystemExit(f"{name} P{order}, {sub}: status {e.status} ({e}); the case must solve")
+        assert info.method_used == capi.SOLVER_AMG and info.iters > 0, (sub, info.method_used, info.iters)
+        rows.append(_row(sub, x, info))
+
+    for sub, dirichlet in (("solve AMG", False), ("solve AMG, Dirichlet data", True)):
+        _, c, nd = _scalar(name, order, None, dirichlet)
+        attempt(sub, lambda: (lambda info: (c.solution(), info))(c.solve(method=capi.SOLVER_AMG, maxit=1000, raise_on_noconv=False)))
+        c.close()
+    times = np.linspace(0.0, 0.3, 4)
+    _, c, nd = _scalar(name, order, lambda capi: -capi.laplacian() + capi.reaction(1.0) + capi.dt(), True, times)
+    coords = c.dofs_get()[2]
+    g = np.stack([(1.0 + t) * coords.sum(axis=1) for t in times], axis=1)
+    attempt("solve_parabolic AMG, three steps", lambda: c.solve_parabolic(times, np.cos(coords[:, 0]), dirichlet=g, method=capi.SOLVER_AMG))
+    c.close()
+    _, c, nd = _scalar(name, order)
+    B = np.random.default_rng(7).standard_normal((nd, 8))
+    dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+
+    def lin(method, ncols, place):
+        c.lin_compute(capi.MAT_STIFF, symmetric=True)   # (a fresh handle: the hierarchy starts over)
+        flat = np.ascontiguousarray(B[:, :ncols].T).reshape(-1)
+        out = flat if place == "in" else np.zeros_like(flat)
+        opt, info = capi.Options(method=method, maxit=1000, rtol=1e-10, assembly=0, check_every=0, time_spmv=0), capi.Info()
+        rc = c.lib.fdapde_lin_solve(c._ctx, C.byref(opt), dp(flat), ncols, dp(out), C.byref(info))
+        if rc not in (capi.OK, capi.ENOCONV):
+            c._check(rc)
+        return out, info
+
+    for cols in (8, 1):
+        c.tune("amg_cols", cols)
+        for ncols in (1, 5, 8):
+            for place in ("out", "in"):
+                attempt(f"lin_solve AMG amg_cols {cols}, {ncols} col {place} place", lambda: lin(capi.SOLVER_AMG, ncols, place))
+    c.close()
+    for r in rows:
+        print("ROW " + json.dumps(r), flush=True)
+
+
 def time_child(handle):
     rows_out = []
+    if handle == "scalar":
+        capi, c, nd = _scalar("unit_square_16", 1)
+        B = np.random.default_rng(6).standard_normal((nd, 64))
+        c.lin_compute(capi.MAT_STIFF, symmetric=True)
+        c.lin_solve(B, method=capi.SOLVER_AMG, maxit=1000, raise_on_noconv=False)   # warm-up: buffers, the hierarchy
+        t0 = time.perf_counter()
+        _, info = c.lin_solve(B, method=capi.SOLVER_AMG, maxit=1000, raise_on_noconv=False)
+        rows_out.append({"what": f"unit_square_16 P1, {nd} rows, 64 columns, fdapde_lin_solve AMG", "ms": (time.perf_counter() - t0) * 1e3, "iters": int(info.iters)})
+        c.close()
+        # one solve at the size of tools/amg_cols_time.py (unit_cube(30), 29 791 DOFs, eight columns side by side)
+        from fdapde_core_amd import meshgen
+
+        c = capi.Context(0)
+        c.mesh_upload(*meshgen.unit_cube(30))
+        nd = c.dofs_build(1)
+        c.set_operator(-capi.laplacian() + capi.reaction(1.0))
+        c.set_forcing(np.ones(c.quadrature_nodes().shape[0]))
+        c.init()
+        c.lin_compute(capi.MAT_STIFF, symmetric=True)
+        B = np.random.default_rng(8).standard_normal((nd, 8))
+        c.lin_solve(B, method=capi.SOLVER_AMG)
+        t0 = time.perf_counter()
+        _, info = c.lin_solve(B, method=capi.SOLVER_AMG)
+        rows_out.append({"what": f"unit_cube(30) P1, {nd} rows, 8 columns, fdapde_lin_solve AMG", "ms": (time.perf_counter() - t0) * 1e3, "iters": int(info.iters)})
+        c.close()
+        for r in rows_out:
+            print("ROW " + json.dumps(r), flush=True)
+        return
     for name, order, ncols, stages in (("unit_square_16", 1, 64, ("GMRES", "DENSE", "AMG")),):
         capi, c, compute, _, rows = _setup(handle, name, order)
         solve = c.block_solve if handle == "block" else c.kron_solve
@@ -126,12 +240,12 @@ def bits_main(parent_lib, out_path):
     out = [f"tools/handle_driver_bits.py on an MI355X, {time.strftime('%Y-%m-%d %H:%M:%S')}",
            "x (SHA-256), iters, relres (bits), converged, method_used -- or status and message of a refusal -- of the parent commit's library and this tree's", ""]
     bad = 0
-    for handle in ("block", "kron"):
+    for handle in ("block", "kron", "scalar"):
         for name, order in FIXTURES:
-            for term in ("plain", "term"):
-                args = ["--bits-child", handle, name, str(order), term]
+            for term in ("plain", "term") if handle != "scalar" else ("",):
+                args = ["--bits-child", handle, name, str(order), term] if handle != "scalar" else ["--scalar-child", name, str(order)]
                 p1, p2, new = _child(args, parent_lib), _child(args, parent_lib), _child(args, None)
-                assert len(p1) == len(p2) == len(new) == 16
+                assert len(p1) == len(p2) == len(new) == (16 if handle != "scalar" else 15)
                 for a, b, n in zip(p1, p2, new):
                     head = f"{handle:5s} {name} P{order} {term:5s} {a['sub']:28s}"
                     what = f"refused, status {a['status']}" if "status" in a else f"method {a['method_used']}, {a['iters']} iterations, converged {a['converged']}"
@@ -156,15 +270,16 @@ def bits_main(parent_lib, out_path):
 
 def time_main(parent_lib, out_path):
     out = [f"tools/handle_driver_bits.py --time on an MI355X, {time.strftime('%Y-%m-%d %H:%M:%S')}",
-           "wall time of one fdapde_block_solve / fdapde_kron_solve call, ms; five windows per library, alternating, every window a fresh process with one warm-up call",
+           "wall time of one fdapde_block_solve / fdapde_kron_solve / fdapde_lin_solve call, ms; five windows per library, alternating, every window a fresh process with one warm-up call",
            "the gate: this tree's median <= the largest of the parent's five windows", ""]
     bad = 0
-    for handle in ("block", "kron"):
+    for handle in ("block", "kron", "scalar"):
         got = {"parent": {}, "new": {}}
-        for _ in range(5):
+        for window in range(5):
             for who, lib in (("parent", parent_lib), ("new", None)):
                 for r in _child(["--time-child", handle], lib):
                     got[who].setdefault(r["what"], []).append(r["ms"])
+            print(f"{handle}: window {window + 1} of 5 done", flush=True)
         for what in got["parent"]:
             p, n = got["parent"][what], got["new"][what]
             ok = float(np.median(n)) <= max(p)
@@ -183,6 +298,8 @@ if __name__ == "__main__":
     argv = sys.argv[1:]
     if argv[:1] == ["--bits-child"]:
         bits_child(*argv[1:])
+    elif argv[:1] == ["--scalar-child"]:
+        scalar_child(*argv[1:])
     elif argv[:1] == ["--time-child"]:
         time_child(argv[1])
     elif argv[:1] == ["--time"] and len(argv) >= 2:
